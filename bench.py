@@ -4,16 +4,23 @@ generate() = T3 -> S3Gen (10-step CFM, CFG) -> HiFT, Multilingual-V3 500M archit
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: one rank per GPU over RCCL -- either the caller launched the ranks with
                                                           torch.distributed.run, or this script re-runs itself under it)
+    python bench.py ... --dump-outputs DIR               (also write the last timed step's waveforms and speech tokens as DIR/<name>.npy)
+    python bench.py ... --full                           (also everything measured beside the headline: see below)
 
 A "step" is one pass of the whole hot path over one batch of synthetic utterances: 64 text tokens,
 250 speech tokens (10 s of audio, EOS banned so the length is fixed), 150-token T3 voice prompt, 250-token / 500-frame
 S3Gen prompt, seeded random-init weights in the reference's checkpoint layout (no network => no pretrained weights).
 Prints ONE JSON line (rank 0).  The headline `value` runs S3Gen in the default fp32-level numerics mode (f16x3: two fp16 planes per fp32
-operand, range-checked on the device; T3 is exact fp32 MFMA); the other fp32-level mode (bf16x6) and the opt-in bf16x3 fast mode are
-measured by the same run and reported beside it, clearly labelled.  `roofline` is the
-dominant kernel class (T3 decode weight streaming); `decode_step` is the whole decode step (weights + KV cache) timed with HIP events
-INSIDE the timed region; `cpu_baseline` is the reference itself (kind "reference", when /root/reference is present) or the oracle
-(kind "port", a CPU restatement pinned against the reference) on ONE utterance of the benched workload.
+operand, range-checked on the device; T3 is exact fp32 MFMA).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs (--dump-outputs), print the line.
+`ms_per_step` is the wall time of one timed step.  With --full the same run then also measures what is reported beside the headline: the
+other schedule, the other fp32-level mode (bf16x6) and the opt-in bf16x3 fast mode, clearly labelled; streaming latency; configs[3] (default
+on at 8 ranks); `roofline` = the dominant kernel class (T3 decode weight streaming) from an instrumented extra step and graph sweeps;
+`decode_step` = the whole decode step (weights + KV cache) timed with HIP events INSIDE the timed region; `cpu_baseline` = the reference itself
+(kind "reference", when the reference tree is present) or the oracle (kind "port", a CPU restatement pinned against the reference) on ONE
+utterance of the benched workload, and the GPU-vs-CPU parity on it.  --full also measures the decode-step geometry candidates on this GPU
+before the timed region (T3Engine.autotune) and adopts one that is faster and gives the same tokens.
 """
 import argparse
 import json
@@ -71,16 +78,22 @@ def parse():
     ap.add_argument("--no-fast-mode", action="store_true", help="skip the full fast-mode measurement (S3Gen bf16x3 + T3 bf16 decode weights)")
     ap.add_argument("--no-streaming", action="store_true", help="skip the chunked-synthesis latency measurement after the timed region")
     ap.add_argument("--config3", action="store_true",
-                    help="after the timed region also run configs[3]: 256 utterances strong-sharded over the ranks (32 per GPU at 8 GPUs); "
+                    help="with --full: after the timed region also run configs[3]: 256 utterances strong-sharded over the ranks (32 per GPU at 8 GPUs); "
                          "default on when WORLD_SIZE == 8")
     ap.add_argument("--cpu-threads", type=int, default=32)
     ap.add_argument("--no-autotune", action="store_true",
-                    help="keep the built-in decode-step geometry instead of measuring the candidates on this GPU first (T3Engine.autotune: child "
-                         "process, bit-identical candidates only)")
+                    help="with --full: keep the built-in decode-step geometry instead of measuring the candidates on this GPU first (T3Engine.autotune: "
+                         "child process, bit-identical candidates only); a plain run always keeps it")
     ap.add_argument("--no-parity", action="store_true", help="skip the GPU-vs-CPU parity block (needs the CPU baseline utterance)")
     ap.add_argument("--force-rccl", action="store_true",
                     help="initialise the RCCL process group even at world size 1 and run C1 (broadcast of the Conditionals) and C2 (gather of the "
                          "waveforms) through it on device tensors: what a single GPU can exercise of the multi-GPU path (tests/test_rccl_world1_gpu.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything reported beside the headline (decode autotune, other schedule / precisions, streaming, configs[3], "
+                         "rooflines, CPU baseline + parity); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (waveforms float32, speech tokens float64) as DIR/<name>.npy; "
+                         "at most 64 MB in all (a fixed, seeded sample of each array beyond that); with N > 1 ranks each rank writes rank<r>_<name>.npy")
     ap.add_argument("--selftest-rendezvous", action="store_true",
                     help="launcher / collective self-test WITHOUT kernels (gloo, host tensors): the N ranks rendezvous, C1 (broadcast of the "
                          "Conditionals) and C2 (gather of waveforms) fire on synthetic payloads of the benched shapes, rank 0 prints the JSON "
@@ -164,16 +177,43 @@ def selftest_rendezvous(args, rank, world):
                           "config": {"workload": "selftest", "global_batch": B * world, "parallelism": f"dp{world}"}}), flush=True)
 
 
-def pipelined_batches(eng, jobs, gatherer, **kw):
+def pipelined_batches(eng, jobs, gatherer, last=None, **kw):
     """The throughput schedule over `jobs` (engine.synthesize_pipelined): -> (audio seconds of this rank, per-batch latencies).  C2 is POSTED per batch to
     `gatherer` (dist.AsyncGatherer: a background thread runs the collectives in batch order) instead of blocking the generator between batches; the caller
-    closes the gatherer before the barrier that ends its timed region."""
+    closes the gatherer before the barrier that ends its timed region.  `last` (a dict) receives the waveforms and tokens of the last batch."""
     a, ls = 0.0, []
     for host, st_, lat in eng.synthesize_pipelined(jobs, **kw):
         a += sum(w.numel() for w in host) / 24000.0
         ls.append(lat)
         gatherer.post(host)  # C2, off the critical path
+        if last is not None:
+            last.update(wavs=host, tokens=st_)
     return a, ls
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # files included (a .npy header is 128 bytes)
+
+
+def dump_outputs(out_dir, last, rank, world):
+    """--dump-outputs: the last timed step's waveforms (float32) and speech tokens (float64, exact) as <out_dir>/[rank<r>_]{wav,speech_tokens}_<b>.npy.
+    Beyond DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its elements at indices drawn from a fixed seed (the same for the same shapes)."""
+    import numpy as np
+    arrs = {}
+    for b, w in enumerate(last["wavs"]):
+        arrs[f"wav_{b}"] = w.detach().float().cpu().reshape(-1)
+    for b, t in enumerate(last["tokens"]):
+        arrs[f"speech_tokens_{b}"] = t.detach().cpu().reshape(-1).double()
+    total, limit = sum(a.numel() * a.element_size() for a in arrs.values()), DUMP_LIMIT_BYTES - 1024 * len(arrs)
+    if total > limit:
+        frac = limit / total
+        for i, (k, a) in enumerate(sorted(arrs.items())):
+            g = torch.Generator().manual_seed(2024 + i)
+            idx = torch.randperm(a.numel(), generator=g)[: int(a.numel() * frac)].sort().values
+            arrs[k] = a[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, pre + k + ".npy"), a.numpy())
 
 
 class _StubPipelineEngine:
@@ -559,8 +599,11 @@ def vc60_main(args, dev, rank, world):
         t2 = time.perf_counter()
         tm = dict(tokenizer_s=t1 - t0, **eng.last_timing)
         cdist.gather_waveforms(wavs, dst=0)
+        last.update(wavs=host, tokens=toks)
         return sum(w.numel() for w in host) / 24000.0, t2 - t0, tm, T
 
+    last = {}
+    torch.manual_seed(4321 + rank)  # HiFT draws its source phase / noise from the default generator: the same in every run (--dump-outputs)
     for _ in range(args.warmup):
         one_step()
     if world > 1:
@@ -584,21 +627,26 @@ def vc60_main(args, dev, rank, world):
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         dist.all_reduce(sm, op=dist.ReduceOp.SUM)
         elapsed, audio = float(mx[0]), float(sm[1])
-    timer = ops.KernelTimer(["gemm_f32", "gemm_split", "flash_attn_f32", "gemm_planes", "flash_attn_planes"])
-    ops.TIMER = timer  # the instrumented extra step, outside the timed region (per-kernel HIP events; the Python launch sequencing)
-    one_step()
-    torch.cuda.synchronize()
-    ops.TIMER = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
+    roof, roofs = None, {}
+    if args.full:
+        timer = ops.KernelTimer(["gemm_f32", "gemm_split", "flash_attn_f32", "gemm_planes", "flash_attn_planes"])
+        ops.TIMER = timer  # the instrumented extra step, outside the timed region (per-kernel HIP events; the Python launch sequencing)
+        one_step()
+        torch.cuda.synchronize()
+        ops.TIMER = None
     if rank != 0:
         return
-    roofs = roofline_entries(timer.summary(), elapsed, args.steps, 1, eng.flow.precision, 0, None)
-    dom = max(roofs, key=lambda k: roofs[k]["share_of_step"]) if roofs else None
-    roof = roofs.pop(dom, None)
-    for e in [roof] + list(roofs.values()):
-        if e:  # the committed PMC passes are of the headline shape (T = 1000): not this workload's traffic
-            e["traffic"], e["traffic_source"] = None, "not collected at this shape (the committed PMC passes are of the headline workload)"
+    if args.full:
+        roofs = roofline_entries(timer.summary(), elapsed, args.steps, 1, eng.flow.precision, 0, None)
+        dom = max(roofs, key=lambda k: roofs[k]["share_of_step"]) if roofs else None
+        roof = roofs.pop(dom, None)
+        for e in [roof] + list(roofs.values()):
+            if e:  # the committed PMC passes are of the headline shape (T = 1000): not this workload's traffic
+                e["traffic"], e["traffic_source"] = None, "not collected at this shape (the committed PMC passes are of the headline workload)"
     lats.sort()
-    print(json.dumps({
+    out = {
         "metric": "audio-sec/wall-sec (xRT), voice conversion of long-form audio (configs[4]; NOT the headline metric's config)",
         "value": round(audio / elapsed, 3), "unit": "audio-s/wall-s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1e3 * elapsed / args.steps, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -611,8 +659,10 @@ def vc60_main(args, dev, rank, world):
                                 f"({T // 2 - int(ref['prompt_token'].shape[1])} tokens + {int(ref['prompt_token'].shape[1])}-token prompt: T = {T} mel frames per CFM row), "
                                 f"batch {B}/GPU in one device batch"),
                    "global_batch": B * world, "parallelism": f"dp{world}", "model_build_s": round(build_s, 1),
-                   "stage_seams": {"flow": bool(eng.flow.c_seam), "hift": bool(eng.hift.c_seam)}},
-        "roofline": roof, "roofline_secondary": list(roofs.values())}), flush=True)
+                   "stage_seams": {"flow": bool(eng.flow.c_seam), "hift": bool(eng.hift.c_seam)}}}
+    if args.full:
+        out.update(roofline=roof, roofline_secondary=list(roofs.values()))
+    print(json.dumps(out), flush=True)
 
 
 def _co_resident_on_green(t3):
@@ -696,7 +746,7 @@ def main():
     texts = [(synth.turbo_text_tokens if turbo else synth.text_tokens)(args.text_tokens, seed=100 * rank + b) for b in range(B)]
     T = 2 * (gen["prompt_token"].shape[1] + N)
 
-    if not turbo and not args.no_autotune and 2 * B <= 16:
+    if args.full and not turbo and not args.no_autotune and 2 * B <= 16:
         # chatterbox_amd/autotune.py: the candidates run in a child process (a faulting one cannot take the bench down); a geometry whose logits
         # are bit-identical to the built-in one's is adopted as is; the report goes into the JSON line (config.t3_decode_autotune).
         # the fastest candidate overall may sum the down projection in another (valid fp32) order: it is kept only if ALL B x N tokens of the
@@ -710,6 +760,8 @@ def main():
                                    validate=lambda: [t.tolist() for t in eng.t3.generate(t3c, texts, **kwv)] == want)
         tune_rep["autotune_s"] = round(time.perf_counter() - t_tune, 1)
         log(f"decode autotune: adopted {tune_rep.get('adopted')} in {tune_rep['autotune_s']} s")
+
+    step_out = {}  # waveforms + tokens of the latest one_step() (--dump-outputs takes those of the last timed step)
 
     def one_step(seed):
         g = torch.Generator(device=dev).manual_seed(1234 + 1000 * rank + seed)
@@ -727,9 +779,10 @@ def main():
         allw = cdist.gather_waveforms(wavs, dst=0, force=args.force_rccl)  # C2
         if args.force_rccl:
             assert len(allw) == len(host) and all(torch.equal(a, h) for a, h in zip(allw, host)), "C2 over RCCL returned other waveforms"
+        step_out.update(wavs=host, tokens=st)
         return sum(w.numel() for w in host) / 24000.0, lat, dict(eng.last_timing)
 
-    def pipelined_run(n, seed0, precision=None):
+    def pipelined_run(n, seed0, precision=None, last=None):
         """n batches through the throughput schedule; C2 per batch through the background gatherer (closed before the caller's barrier); -> (audio seconds, per-batch latencies)"""
         jobs = []
         for i in range(n):
@@ -738,7 +791,7 @@ def main():
                              z=torch.randn(B, T, 80, generator=g, device=dev)))
         gat = cdist.AsyncGatherer(dst=0, force=args.force_rccl)
         try:
-            return pipelined_batches(eng, jobs, gat, max_new_tokens=N, ban_eos=True, ban_from=6561, drop_last_token=True)
+            return pipelined_batches(eng, jobs, gat, last=last, max_new_tokens=N, ban_eos=True, ban_from=6561, drop_last_token=True)
         finally:
             gat.close()
 
@@ -776,11 +829,15 @@ def main():
     ops.TIMER = None
     eng.t3.time_decode, eng.t3.decode_events = True, []
     stage, other = {}, None
+    timed_out = {}  # what the last timed step returned (--dump-outputs)
+    # HiFT draws its source phase / noise from torch's default generator (hift.inference): seeded here, after the (--full) autotune, so that the
+    # warm-up and timed steps get the same inputs in every run with the same arguments
+    torch.manual_seed(4321 + rank)
     if pipelined:
         try:
             pipelined_run(max(2, args.warmup), -1000)
             eng.t3.decode_events = []
-            elapsed, (audio, lats) = timed(lambda: pipelined_run(args.steps, 0))
+            elapsed, (audio, lats) = timed(lambda: pipelined_run(args.steps, 0, last=timed_out))
         except Exception as e:  # the headline must never be lost to the throughput schedule: fall back to the serial one and say so
             if world > 1 or explicit_pipelined:  # (a rank-local fallback would desynchronise the C2 collectives of the other ranks; an explicit request is not second-guessed)
                 raise
@@ -790,7 +847,8 @@ def main():
             pipelined, schedule = False, "serial"
     pipe_events = list(eng.t3.decode_events)
     eng.t3.decode_events = []
-    if pipelined:
+    step_s, stage_n = None, 1
+    if pipelined and args.full:
         # the serial (latency) schedule on the same box, outside the timed region: its own warm-up (the decode graph of the default geometry is captured
         # again), then min(K, 5) steps -- stage split, in-run decode-step roofline and the serial headline of rounds 1-4 come from here
         one_step(-1)
@@ -808,17 +866,21 @@ def main():
                      value=round(ser_audio / ser_elapsed, 3), unit="audio-s/wall-s", steps=n_ser, ms_per_step=round(1e3 * ser_elapsed / n_ser, 2),
                      p50_first_audio_latency_ms=round(1e3 * ser_lats[len(ser_lats) // 2], 1))
         step_s, stage_n = ser_elapsed / n_ser, n_ser  # what kernel shares / stage times are relative to
-    else:
+    elif not pipelined:
         for i in range(args.warmup):
             one_step(-1 - i)
         eng.t3.decode_events = []
         elapsed, (audio, lats) = timed(lambda: serial_run(args.steps, 0, stage))
+        timed_out = dict(step_out)
         step_s, stage_n = elapsed / args.steps, args.steps
     eng.t3.time_decode = False
-    ops.TIMER = timer  # the instrumented step (every rank: one_step contains the C2 collective)
-    one_step(args.steps)
-    torch.cuda.synchronize()
-    ops.TIMER = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_out, rank, world)
+    if args.full:
+        ops.TIMER = timer  # the instrumented step (every rank: one_step contains the C2 collective)
+        one_step(args.steps)
+        torch.cuda.synchronize()
+        ops.TIMER = None
 
     stats = torch.tensor([elapsed, audio], dtype=torch.float64, device=dev)
     if world > 1:
@@ -831,7 +893,7 @@ def main():
     # ---- outside the timed region: (a) eager replay of the decode step for the gemv roofline, (b) one step at each of the other
     # S3Gen precisions so that the exact-fp32 figure is reported by the same run
     alt, gemv, dstep, cfg3, stream = {}, None, None, None, None
-    run_cfg3 = (args.config3 or world == 8) and not turbo
+    run_cfg3 = args.full and (args.config3 or world == 8) and not turbo
     if run_cfg3:  # configs[3]: 256 utterances, contiguous shards (dist.shard_range), 32 per GPU at 8 GPUs; every rank takes part
         lo, hi = cdist.shard_range(256, rank, world)
         tx = [synth.text_tokens(args.text_tokens, seed=1000 + i) for i in range(lo, hi)]
@@ -872,7 +934,7 @@ def main():
         summ = timer.summary()
         if turbo:
             dstep = decode_step_entry(eng.t3, None, gpt2=True)
-            if B == 1 and eng.t3.tune.get("row_path"):
+            if args.full and B == 1 and eng.t3.tune.get("row_path"):
                 gemv = gemv_row_sweeps(eng.t3)
         dstep_pipe = bf16x6 = repeat_ms = None
         if not turbo:
@@ -883,8 +945,9 @@ def main():
                 eng.t3.decode_events = keep
                 dstep_pipe = dict(ms_per_step=dp["ms_per_step"], frac=dp["frac"], steps=dp["steps"],
                                   note="the decode step inside the timed region: its workgroups share the CUs with the flow + vocoder of the previous batch")
-            gemv = gemv_sweeps(eng.t3, 2 * B)
-            if pipelined and s3_prec != 6 and not args.no_alt_precisions and world == 1:
+            if args.full:
+                gemv = gemv_sweeps(eng.t3, 2 * B)
+            if args.full and pipelined and s3_prec != 6 and not args.no_alt_precisions and world == 1:
                 # the THROUGHPUT schedule at strictly fp32-width S3Gen arithmetic (bf16x6: three bf16 planes = all 24 significand bits per operand, fp32
                 # exponent range; T3 is exact fp32 in every mode): same schedule, same batches, after the timed region
                 eng.flow.precision = eng.hift.precision = 6
@@ -898,7 +961,7 @@ def main():
                     bf16x6 = dict(value=None, error=f"{type(e).__name__}: {e}"[:200])
                     torch.cuda.synchronize()
                 eng.flow.precision = eng.hift.precision = s3_prec
-            if not args.no_alt_precisions and world == 1:  # one_step() contains the C2 collective: single-rank runs only
+            if args.full and not args.no_alt_precisions and world == 1:  # one_step() contains the C2 collective: single-rank runs only
                 for pr in ((1, 16, 6, 3) if args.all_precisions else (16, 6, 3)):
                     if pr == s3_prec:
                         continue
@@ -925,7 +988,7 @@ def main():
                     eng.t3 = t3_fp32
                 eng.flow.precision = eng.hift.precision = s3_prec
         stream = None
-        if not turbo and world == 1 and not args.no_streaming:
+        if args.full and not turbo and world == 1 and not args.no_streaming:
             # chunked synthesis (engine.synthesize_stream): wall time until the first audio chunk is on the host, and the cost of the
             # whole chunked run, on the benched batch (first chunk = 1 s of audio, then 2 s chunks)
             def stream_run(first_alone):
@@ -953,7 +1016,7 @@ def main():
             # the same schedule with T3 decoding beside round 0 as well: more throughput, later first audio (same-box A/B: profiles/r06_streaming_schedules_ab.jsonl)
             stream["t3_beside_first_round"] = stream_run(False)
         pipe_extra = None
-        if not turbo and world == 1 and not args.no_streaming and not pipelined and fallback is None:
+        if args.full and not turbo and world == 1 and not args.no_streaming and not pipelined and fallback is None:
             # the throughput schedule on the same workload, outside the timed region: T3 of batch k + 1 on a high-priority stream beside flow + vocoder
             # of batch k (engine.synthesize_pipelined; same kernels, same results, about twice the per-batch latency) -- 6 batches, fill and drain included
             try:  # (an extra: it must never cost the bench line)
@@ -972,11 +1035,13 @@ def main():
             except Exception as e:
                 pipe_extra = dict(error=f"{type(e).__name__}: {e}"[:200])
                 torch.cuda.synchronize()
-        roofs = roofline_entries(summ, step_s, 1, timed_steps, s3_prec, N - 1, gemv, "gpt2" if turbo else "llama")  # shares relative to a SERIAL step (kernels with the GPU to themselves)
-        dom = args.roofline_kernel
-        if dom == "auto":
-            dom = max(roofs, key=lambda k: roofs[k]["share_of_step"]) if roofs else None
-        roof = roofs.pop(dom, None)
+        roof, roofs = None, {}
+        if args.full:
+            roofs = roofline_entries(summ, step_s, 1, timed_steps, s3_prec, N - 1, gemv, "gpt2" if turbo else "llama")  # shares relative to a SERIAL step (kernels with the GPU to themselves)
+            dom = args.roofline_kernel
+            if dom == "auto":
+                dom = max(roofs, key=lambda k: roofs[k]["share_of_step"]) if roofs else None
+            roof = roofs.pop(dom, None)
         lats.sort()
         out = {
             "metric": "audio-sec/wall-sec (xRT) + p50 first-audio latency, Multilingual-V3 500M",
@@ -997,19 +1062,19 @@ def main():
             # latency of the HEADLINE schedule: enqueue of a batch's T3 -> its audio on the host (one-shot synthesis; the pipelined schedule holds two batches
             # in flight, so a batch waits for its predecessor's flow + vocoder).  The latency modes are beside it: other_schedule (serial one-shot) and streaming
             "p50_first_audio_latency_ms": round(1e3 * lats[len(lats) // 2], 1),
-            # both schedules and the precision variants as SHORT top-level keys (ADVICE r05 / VERDICT r05 items 2, 3): `value` is value_<schedule>
-            "value_pipelined": round(audio / elapsed, 3) if pipelined else (pipe_extra or {}).get("audio_s_per_wall_s"),
-            "value_serial": other["value"] if other else round(audio / elapsed, 3),
-            "p50_first_audio_latency_ms_pipelined": round(1e3 * lats[len(lats) // 2], 1) if pipelined else (pipe_extra or {}).get("p50_batch_latency_ms"),
-            "p50_first_audio_latency_ms_serial": other["p50_first_audio_latency_ms"] if other else round(1e3 * lats[len(lats) // 2], 1),
-            "p50_first_audio_latency_ms_streaming": (stream or {}).get("p50_first_audio_latency_ms"),
-            # the throughput schedule with S3Gen at strictly fp32-width operands (bf16x6: 24 significand bits, fp32 exponent range) -- THE fp32-width claim; `value` runs
-            # S3Gen at f16x3 (22 significand bits per operand, range-checked, error measured at or below the exact-fp32 MFMA's: DESIGN.md section 1)
-            "value_bf16x6": (bf16x6 or {}).get("value") if not turbo else None,
+            # (--full) both schedules and the precision variants as SHORT top-level keys (ADVICE r05 / VERDICT r05 items 2, 3): `value` is value_<schedule>
+            **({"value_pipelined": round(audio / elapsed, 3) if pipelined else (pipe_extra or {}).get("audio_s_per_wall_s"),
+                "value_serial": other["value"] if other else round(audio / elapsed, 3),
+                "p50_first_audio_latency_ms_pipelined": round(1e3 * lats[len(lats) // 2], 1) if pipelined else (pipe_extra or {}).get("p50_batch_latency_ms"),
+                "p50_first_audio_latency_ms_serial": other["p50_first_audio_latency_ms"] if other else round(1e3 * lats[len(lats) // 2], 1),
+                "p50_first_audio_latency_ms_streaming": (stream or {}).get("p50_first_audio_latency_ms"),
+                # the throughput schedule with S3Gen at strictly fp32-width operands (bf16x6: 24 significand bits, fp32 exponent range) -- THE fp32-width claim; `value`
+                # runs S3Gen at f16x3 (22 significand bits per operand, range-checked, error measured at or below the exact-fp32 MFMA's: DESIGN.md section 1)
+                "value_bf16x6": (bf16x6 or {}).get("value") if not turbo else None} if args.full else {}),
             # the fp16 range check of the default S3Gen mode: passes of THIS run (warm-up, timed region, extras) that tripped it and were repeated at bf16x6, and
-            # what one such repeat costs per batch (serial flow + vocoder at bf16x6).  Seeded random-init weights: 0 trips; trip rate against activation outliers
-            # of 1e2 .. 1e5: tests/test_models_gpu.py::test_f16x3_range_flag_trip_rate_and_repeat_cost_on_outlier_activations
-            "f16x3_range_trips": _range_trips(), "bf16x6_repeat_cost_ms": repeat_ms,
+            # (--full) what one such repeat costs per batch (serial flow + vocoder at bf16x6).  Seeded random-init weights: 0 trips; trip rate against activation
+            # outliers of 1e2 .. 1e5: tests/test_models_gpu.py::test_f16x3_range_flag_trip_rate_and_repeat_cost_on_outlier_activations
+            "f16x3_range_trips": _range_trips(), **({"bf16x6_repeat_cost_ms": repeat_ms} if args.full else {}),
             "config": {"workload": (f"configs[2]: Chatterbox-Multilingual-V3 500M architecture (T3 Llama-520M {args.t3_layers}L + S3Gen 10-step CFG CFM + "
                                     f"HiFT), batch {B}/GPU, {args.text_tokens} text tokens, {N} speech tokens = {N / 25:.0f} s audio per utterance, "
                                     f"10 s voice prompt") if not turbo else
@@ -1021,7 +1086,7 @@ def main():
                                     "the CFM + vocoder of batch k on a second one; both stages on their CO-RESIDENT kernel forms (one workgroup per CU that leaves half "
                                     "of the register file free: DESIGN 6.000), the T3 launches enqueued by a second host thread; K batches incl. fill and drain "
                                     "inside the timed region; same work and results as the serial schedule (tests/test_models_gpu.py::test_pipelined_equals_serial); "
-                                    "stage_ms / roofline / decode_step are of the SERIAL steps measured after the timed region (other_schedule)"
+                                    "with --full, stage_ms / roofline / decode_step are of the SERIAL steps measured after the timed region (other_schedule)"
                                     if pipelined else "serial: the K batches strictly one after the other" + (f" (FALLBACK: the pipelined schedule failed: {fallback})" if fallback else "")),
                        # which stages ran through their stage-level C entry point (cbx_t3_prefill + cbx_t3_decode_step / cbx_cfm_solve / cbx_hift_decode)
                        "stage_seams": {"t3": bool(getattr(eng.t3, "c_step", False)), "flow": bool(eng.flow.c_seam), "hift": bool(eng.hift.c_seam)}},
@@ -1033,9 +1098,9 @@ def main():
             "t3_geometry_throughput_schedule": ({"tune": {"half_tiles": 0, "d_ks2": 4, "d_nw2": 8}, "knobs": {"shallow": 1}, "t3_batches_in_flight": 2,
                                                   "on_green_list": _co_resident_on_green(eng.t3)} if (pipelined and not turbo) else None),
             "multi_gpu_note": ("single-GPU run: no N > 1 scaling curve exists in this repo (the driver owns multi-GPU leases)" if world == 1 else None),
-            "roofline": roof,
+            **({"roofline": roof} if args.full else {}),
             "decode_step": dstep,
-            "roofline_secondary": list(roofs.values()),
+            **({"roofline_secondary": list(roofs.values())} if args.full else {}),
         }
         if tune_rep is not None:
             out["config"]["t3_decode_autotune"] = {
@@ -1069,7 +1134,7 @@ def main():
             out["throughput_schedule_bf16x6"] = bf16x6
         if dstep_pipe:
             out["decode_step_in_throughput_schedule"] = dstep_pipe
-        if not args.no_cpu_baseline and world == 1:  # reported at N = 1 only (rank 0's host cores)
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N = 1 only (rank 0's host cores)
             log("cpu baseline ...")
             art, out["cpu_baseline"] = cpu_baseline(t3_sd, s3_sd, args, args.t3_layers)
             if not args.no_parity:

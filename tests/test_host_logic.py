@@ -187,21 +187,24 @@ def test_drop_invalid_tokens_and_text():
     assert punc_norm("a – b") == "A - b."
 
 
+def _reference_meta():
+    """tests/golden/reference_meta.json: what the reference's punc_norm returns, what its example programs call, how long its .py files are
+    (tests/golden/make_golden_reference_meta.py wrote it from the reference tree)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_meta.json"), encoding="utf-8") as fh:
+        return json.load(fh)
+
+
 def test_punc_norm_matches_reference_when_available():
-    from oracle import ref_import
-    if not ref_import.available():
-        pytest.skip("reference tree not present (GPU box)")
     from chatterbox_amd.text import punc_norm, punc_norm_en, punc_norm_turbo
     cases = ["hello world...  how are you; fine — ok", "Déjà vu: “quoted” ‘text’ ", "x", "already done!", "multi\n line\ttext - dash",
              "你好。", "こんにちは、", "ends with cjk comma，", ""]
+    gold = _reference_meta()["punc_norm"]
     for fname, ours in (("mtl_tts.py", punc_norm), ("tts.py", punc_norm_en), ("tts_turbo.py", punc_norm_turbo)):
-        src = open(os.path.join(ref_import.REF_SRC, fname)).read()
-        start = src.index("def punc_norm")
-        end = src.index("@dataclass", start)
-        ns = {}
-        exec(src[start:end], ns)
+        ref = dict(gold[fname])
+        assert sorted(ref) == sorted(cases), fname
         for t in cases:
-            assert ours(t) == ns["punc_norm"](t), (fname, t)
+            assert ours(t) == ref[t], (fname, t)
 
 
 def test_conditionals_roundtrip_and_api_surface(tmp_path):
@@ -239,17 +242,14 @@ def test_turbo_norm_loudness_is_exposed_and_never_raises(capsys):
 
 
 def test_reference_citations_point_into_existing_files():
-    """Every `path.py:line[-line]` citation of the reference in the header, the docs and the package must name a file of /root/reference and
-    lines inside it (skipped where the reference tree is absent, e.g. on the GPU box)."""
+    """Every `path.py:line[-line]` citation of the reference in the header, the docs and the package must name a file of the reference and
+    lines inside it (file names and line counts of the reference: tests/golden/reference_meta.json)."""
     import glob
     import re
-    if not os.path.isdir("/root/reference/src/chatterbox"):
-        pytest.skip("reference tree not present")
+    lines = _reference_meta()["py_line_counts"]
     ref = {}
-    for root, _, files in os.walk("/root/reference"):
-        for f in files:
-            if f.endswith(".py"):
-                ref.setdefault(f, []).append(os.path.join(root, f))
+    for q in lines:
+        ref.setdefault(os.path.basename(q), []).append(q)
     own = {os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "chatterbox_amd", "*.py")) + glob.glob(os.path.join(ROOT, "tests", "*.py")) +
            glob.glob(os.path.join(ROOT, "oracle", "*.py"))} | {"bench.py"}
     pat = re.compile(r"([A-Za-z0-9_/]+\.py):(\d+)(?:-(\d+))?")
@@ -269,7 +269,7 @@ def test_reference_citations_point_into_existing_files():
                 if not cands:
                     continue  # e.g. a citation of this repo's own t3.py / api.py
                 n += 1
-                if not any(hi <= sum(1 for _ in open(c)) for c in cands):
+                if not any(hi <= lines[c] for c in cands):
                     bad.append((fn, i, m.group(0), "past the end of the file"))
     assert n > 100 and not bad, bad[:10]
 
@@ -418,8 +418,8 @@ def _example_api_calls(src):
 
 
 def test_reference_examples_use_only_the_api_we_export():
-    """The drop-in boundary against the reference's own example programs, WITHOUT keeping their text in this repo: wherever the
-    reference is present (this container; not the GPU box) each example_*.py is parsed and every `chatterbox.*` import, every method it calls on
+    """The drop-in boundary against the reference's own example programs, WITHOUT keeping their text in this repo: what each
+    example_*.py imports and calls, as parsed from it by _example_api_calls (tests/golden/reference_meta.json) -- every `chatterbox.*` import, every method it calls on
     those classes and every keyword argument must (1) exist in the alias package with that parameter name and (2) be exercised by the scenario
     of tests/example_scenarios.py that stands in for it on the MI355X (tests/test_examples_gpu.py).  Everywhere: the scenarios' own CALLS table
     matches their code."""
@@ -434,10 +434,9 @@ def test_reference_examples_use_only_the_api_we_export():
         _, calls = _example_api_calls(fns[name])
         assert sorted(set(calls)) == sorted(set((c, m, tuple(sorted(k))) for c, m, k in want)), (name, calls)
     pairs = {"example_tts.py": "tts", "example_tts_turbo.py": "tts_turbo", "example_tts_nano.py": "tts_nano", "example_vc.py": "vc"}
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("the reference is only present in the authoring container")
+    examples = _reference_meta()["examples"]
     for ref_name, scen in pairs.items():
-        imports, calls = _example_api_calls(open(os.path.join("/root/reference", ref_name), encoding="utf-8").read())
+        imports, calls = examples[ref_name]["imports"], [(c, m, tuple(k)) for c, m, k in examples[ref_name]["calls"]]
         assert calls, ref_name
         ours = set((c, m, tuple(sorted(k))) for c, m, k in sc.CALLS[scen])
         for cls, module in imports.items():
