@@ -132,6 +132,21 @@ class Gpt2Prefill(ctypes.Structure):  # cbx_gpt2_prefill_t (ABI v16)
                 ("kc", c_f), ("vc", c_f), ("kv_layer_stride", c_long), ("kv_row_stride", c_long), ("kv_head_stride", c_long)]
 
 
+class Gpt2PackedLayer(ctypes.Structure):  # cbx_gpt2_packed_layer_t
+    _fields_ = [(k, c_f) for k in ("wqkv", "wo", "wfc", "wpr", "qkv_cw", "qkv_cb", "fc_cw", "fc_cb")]
+
+
+class Gpt2Step(ctypes.Structure):  # cbx_gpt2_step_t
+    _fields_ = ([(k, c_int) for k in ("n_layers", "rows", "dim", "n_heads", "vocab", "row_path")] + [("eps", c_float), ("attn_scale", c_float)]
+                + [("layers", ctypes.POINTER(Gpt2Layer)), ("packed", ctypes.POINTER(Gpt2PackedLayer))]
+                + [(k, c_f) for k in ("speech_emb", "wpe", "lnf_w", "lnf_b", "head", "head_b", "head_pk", "head_cw", "head_cb", "kc", "vc")]
+                + [(k, c_long) for k in ("kv_layer_stride", "kv_row_stride", "kv_head_stride")] + [("max_ctx", c_int)]
+                + [(k, c_f) for k in ("next_ids", "positions", "x", "qkv", "g", "parts")] + [("n_splits", c_int), ("chunks", c_int)]
+                + [(k, c_f) for k in ("x_a", "x_b", "att", "g_pk", "pd")]
+                + [(k, c_int) for k in ("qkv_tile", "od_tile", "d_ksplit", "o_nw", "d_nw", "head_ct", "gemv_flags", "da_unroll", "da_pipeline", "da_split_min")]
+                + [("da_ws", c_f), ("da_cnt", c_f), ("da_pairs", c_long), ("logits", c_f), ("ld_logits", c_long), ("sampler", ctypes.POINTER(SamplerParams))])
+
+
 class PlanesRef(ctypes.Structure):  # cbx_planes_t (ABI v12)
     _fields_ = [("p", c_f), ("ld", c_long), ("lo", c_long)]
 
@@ -245,6 +260,10 @@ _SIGS = {
     "cbx_t3_loop_create": ([ctypes.POINTER(T3Step), c_f, ctypes.POINTER(c_f)], c_int),
     "cbx_t3_loop_run": ([c_f, c_int, c_int, c_f, ctypes.POINTER(c_int)], c_int),
     "cbx_t3_loop_destroy": ([c_f], c_int),
+    "cbx_gpt2_decode_step": ([ctypes.POINTER(Gpt2Step), c_f], c_int),
+    "cbx_gpt2_loop_create": ([ctypes.POINTER(Gpt2Step), c_f, ctypes.POINTER(c_f)], c_int),
+    "cbx_gpt2_loop_run": ([c_f, c_int, c_int, c_f, ctypes.POINTER(c_int)], c_int),
+    "cbx_gpt2_loop_destroy": ([c_f], c_int),
     "cbx_t3_sample": ([ctypes.POINTER(SamplerParams), c_f], c_int),
     "cbx_cfm_solve": ([ctypes.POINTER(CfmSolve), c_f], c_int),
     "cbx_s3gen_encode": ([ctypes.POINTER(S3Encode), c_f], c_int),

@@ -153,6 +153,11 @@ def _watermarker():
         return None
 
 
+def _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap):
+    """The round-schedule arguments of generate_stream, passed through to the engine's synthesize_stream."""
+    return dict(first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, overlap=overlap)
+
+
 class _Base:
     sr = S3GEN_SR
 
@@ -188,6 +193,14 @@ class _Base:
         wavs, _ = self.engine.synthesize([tt], self.conds.t3.as_dict(), self.conds.gen, max_new_tokens=1000,
                                          drop_last_token=drop_last_token, **samp)
         return self._finish(wavs[0])
+
+    def _generate_stream(self, text_tokens, drop_last_token, stream_kw, **samp):
+        sot, eot = 255, 0
+        tt = torch.cat([torch.tensor([sot]), text_tokens.view(-1).long().cpu(), torch.tensor([eot])])
+        for r in self.engine.synthesize_stream([tt], self.conds.t3.as_dict(), self.conds.gen, max_new_tokens=1000, drop_last_token=drop_last_token,
+                                               **stream_kw, **samp):
+            if r["wavs"][0].numel():
+                yield self._finish(r["wavs"][0])
 
     @classmethod
     def from_synthetic(cls, device="cuda", seed=0, t3_layers=30, **kw):
@@ -234,6 +247,19 @@ class ChatterboxTTS(_Base):
         return self._generate(toks, drop_last_token=False, temperature=temperature, cfg_weight=cfg_weight,
                               repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
+    def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
+                        cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True):
+        """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
+        `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece."""
+        if audio_prompt_path:
+            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
+        else:
+            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
+        self._set_exaggeration(exaggeration)
+        toks = self.tokenizer.text_to_tokens(punc_norm_en(text))
+        return self._generate_stream(toks, False, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap), temperature=temperature,
+                                     cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+
 
 class ChatterboxMultilingualTTS(_Base):
     _TEXT_VOCAB = 2454
@@ -273,6 +299,21 @@ class ChatterboxMultilingualTTS(_Base):
         toks = self.tokenizer.text_to_tokens(punc_norm(text), language_id=language_id.lower() if language_id else None)
         return self._generate(toks, drop_last_token=True, temperature=temperature, cfg_weight=cfg_weight,
                               repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+
+    def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
+                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True):
+        """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
+        `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece."""
+        if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
+            raise ValueError(f"Unsupported language_id '{language_id}'. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
+        if audio_prompt_path:
+            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
+        else:
+            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
+        self._set_exaggeration(exaggeration)
+        toks = self.tokenizer.text_to_tokens(punc_norm(text), language_id=language_id.lower() if language_id else None)
+        return self._generate_stream(toks, True, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap), temperature=temperature,
+                                     cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
 
 class ChatterboxTurboTTS:
@@ -344,6 +385,32 @@ class ChatterboxTurboTTS:
             logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
         ids = self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids
         return self._generate(ids[0], temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
+
+    def _finish(self, wav):
+        wav = wav.detach().float().cpu()
+        if self.watermarker is not None:
+            wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
+        return wav.unsqueeze(0)
+
+    def _generate_stream(self, text_tokens, stream_kw, **samp):
+        for r in self.engine.synthesize_stream([text_tokens.view(-1).long().cpu()], self.conds.t3.as_dict(), self.conds.gen, **stream_kw, **samp):
+            if r["wavs"][0].numel():
+                yield self._finish(r["wavs"][0])
+
+    def generate_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
+                        temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True):
+        """generate() in pieces (TurboEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk`
+        tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece."""
+        if audio_prompt_path:
+            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, norm_loudness=norm_loudness)
+        else:
+            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
+        if cfg_weight > 0.0 or exaggeration > 0.0 or min_p > 0.0:
+            import logging
+            logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
+        ids = self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids
+        return self._generate_stream(ids[0], _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap), temperature=temperature, top_k=top_k,
+                                     top_p=top_p, repetition_penalty=repetition_penalty)
 
 
 class ChatterboxVC:

@@ -347,41 +347,27 @@ def stream_token_schedule(n_tokens, first_chunk=25, chunk=50, lookahead=3, chunk
         c *= chunk_growth
 
 
-def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,
-                      temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False,
-                      ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2):
-    """Chunked synthesis (SURVEY.md 8f N3): first audio after `first_chunk` tokens instead of after the whole utterance.
-
-    The reference is non-streaming; of its vestigial hooks only HiFT's `cache_source` works (hifigan.py:470-472) -- `finalize=False`
-    (flow.py:170-171) raises a shape error there -- so the schedule is this build's own, with its own oracle
-    (tests/test_stream_gpu.py restates it on the CPU oracle):
-      * round r works on the first n_r tokens, n_0 = first_chunk + lookahead, n_r = n_{r-1} + chunk * chunk_growth^(r-1) (stream_token_schedule);
-      * every round runs encoder + CFM over the tokens so far with the same noise realisation, masking the last 2 * lookahead mel frames of
-        unfinished utterances (the encoder looks 3 tokens ahead), and HiFT with the previous round's source as `cache_source`
-        (phase-continuous excitation);
-      * new samples are emitted up to `fade` samples before the end of what the round could vocode; that tail is cross-faded (linear ramp)
-        with the next round's re-synthesis of the same samples.
-    The last round is a full synthesis: identical mel to synthesize() for the same noise.
-    overlap (round 6, the default): the two stages of the SAME utterances run side by side -- a second host thread keeps the T3 decode going on
-    its own high-priority stream (at most two rounds ahead of the vocoder; graph replays of the captured step), this thread waits for a round's
-    tokens on the flow stream and runs that round's flow + vocoder there, both stages on their co-resident kernel forms (synthesize_pipelined).
-    A round still sees exactly its n_r tokens, so every yielded sample is the one the serial form (overlap=False) yields.
-    Yields dicts {wavs: [B CPU tensors of NEW samples], final: [B bools], n_tokens: [B]}; concatenating an utterance's pieces gives its waveform."""
-    torch.cuda.set_device(self.dev)
+def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw, round_tokens, n_extra, first_chunk, chunk, chunk_growth, lookahead, fade, z,
+                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead):
+    """The round schedule of synthesize_stream for either backbone (ChatterboxEngine: Llama T3, TurboEngine: GPT-2 T3; both T3 engines offer the async
+    generate / advance / peek protocol).  n_budget: tokens the T3 call can sample; t3_kw: its sampling arguments; round_tokens(toks, final flags) -> the
+    valid speech tokens a round vocodes (never empty); n_extra: tokens round_tokens may add (the default z / noise cover n_budget + n_extra)."""
+    # (a generator cannot hold a device guard across yields: pin the device for the caller; "cuda" without an index = the current device)
+    pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+    torch.cuda.set_device(pin)
     dev, B = self.dev, len(text_tokens)
     P = gen_ref["prompt_token"].shape[-1]
-    N = max_new_tokens
+    N = n_budget
     assert gen_ref["prompt_feat"].shape[-2] == 2 * P, "chunked synthesis needs a whole-token prompt (embed_ref output trimmed to 2 frames per token)"
     if z is None:
-        z = torch.randn(B, 2 * (P + N), 80, device=dev)
+        z = torch.randn(B, 2 * (P + N + n_extra), 80, device=dev)
     if phase is None:
         phase = (torch.rand(B, 9, device=dev) * 2 - 1) * 3.141592653589793
         phase[:, 0] = 0
     if noise is None:
-        noise = torch.randn(B, 9, SAMPLES_PER_TOKEN * N, device=dev)
+        noise = torch.randn(B, 9, SAMPLES_PER_TOKEN * (N + n_extra), device=dev)
     z, phase, noise = z.to(dev), phase.to(dev).reshape(B, 9), noise.to(dev)
-    t3_kw = dict(max_new_tokens=N, temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty, cfg_weight=cfg_weight,
-                 uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, async_mode=True)
+    t3_kw = dict(t3_kw, async_mode=True)
     totals = stream_token_schedule(N, first_chunk, chunk, lookahead, chunk_growth)  # tokens decoded when round r starts
     emitted, tails, closed, cache = [0] * B, [None] * B, [False] * B, [None]
     ramp = torch.linspace(0.0, 1.0, fade + 2, device=dev)[1:-1]
@@ -389,8 +375,7 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
     def one_round(toks, done, exhausted):
         """flow + vocoder over the tokens so far on the CURRENT stream -> the dict this generator yields"""
         fin, hold = _stream_plan([t.numel() for t in toks], done, exhausted, lookahead)
-        st = [drop_invalid_tokens(t) for t in toks]
-        st = [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
+        st = round_tokens(toks, fin)
         ns = [int(t.numel()) for t in st]
         Nk = max(ns)
         frames = [max(0, 2 * n - hb) for n, hb in zip(ns, hold)]
@@ -424,7 +409,7 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
                 emitted[b] = end
                 closed[b] = fin[b]
                 out[b] = new.cpu()
-        return dict(wavs=out, final=list(fin), n_tokens=ns)
+        return dict(wavs=out, final=list(fin), n_tokens=ns, tokens=st)
 
     if not overlap:  # the serial form of rounds 3-5: T3 waits while a round is synthesised
         h = self.t3.generate(t3_conds, text_tokens, run_steps=totals[0], **t3_kw)
@@ -450,7 +435,7 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
 
     def worker():
         try:
-            torch.cuda.set_device(dev)
+            torch.cuda.set_device(pin)
             h = None
             with torch.inference_mode(), torch.cuda.stream(self._s_t3):
                 for r, n_r in enumerate(totals):
@@ -499,6 +484,40 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
         self.co_resident(False)
 
 
+def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,
+                      temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False,
+                      ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2):
+    """Chunked synthesis (SURVEY.md 8f N3): first audio after `first_chunk` tokens instead of after the whole utterance.
+
+    The reference is non-streaming; of its vestigial hooks only HiFT's `cache_source` works (hifigan.py:470-472) -- `finalize=False`
+    (flow.py:170-171) raises a shape error there -- so the schedule is this build's own, with its own oracle
+    (tests/test_stream_gpu.py restates it on the CPU oracle):
+      * round r works on the first n_r tokens, n_0 = first_chunk + lookahead, n_r = n_{r-1} + chunk * chunk_growth^(r-1) (stream_token_schedule);
+      * every round runs encoder + CFM over the tokens so far with the same noise realisation, masking the last 2 * lookahead mel frames of
+        unfinished utterances (the encoder looks 3 tokens ahead), and HiFT with the previous round's source as `cache_source`
+        (phase-continuous excitation);
+      * new samples are emitted up to `fade` samples before the end of what the round could vocode; that tail is cross-faded (linear ramp)
+        with the next round's re-synthesis of the same samples.
+    The last round is a full synthesis: identical mel to synthesize() for the same noise.
+    overlap (round 6, the default): the two stages of the SAME utterances run side by side -- a second host thread keeps the T3 decode going on
+    its own high-priority stream (at most two rounds ahead of the vocoder; graph replays of the captured step), this thread waits for a round's
+    tokens on the flow stream and runs that round's flow + vocoder there, both stages on their co-resident kernel forms (synthesize_pipelined).
+    A round still sees exactly its n_r tokens, so every yielded sample is the one the serial form (overlap=False) yields.
+    Yields dicts {wavs: [B CPU tensors of NEW samples], final: [B bools], n_tokens: [B], tokens: [B CPU tensors: the speech tokens the round vocoded]};
+    concatenating an utterance's pieces gives its waveform."""
+    t3_kw = dict(max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                 cfg_weight=cfg_weight, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from)
+
+    def round_tokens(toks, fin):
+        st = [drop_invalid_tokens(t) for t in toks]
+        return [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
+
+    yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_new_tokens, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=0,
+                                  first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
+                                  noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
+                                  run_ahead=run_ahead)
+
+
 S3GEN_SIL = 4299  # reference models/s3gen/const.py:2
 
 
@@ -533,3 +552,28 @@ class TurboEngine:
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False)
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
+
+    co_resident = ChatterboxEngine.co_resident
+    _pipeline_streams = ChatterboxEngine._pipeline_streams
+
+    @torch.inference_mode()
+    def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_gen_len=1000,
+                          temperature=0.8, top_k=1000, top_p=0.95, repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
+                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2):
+        """Chunked synthesis of Turbo / Nano: the round schedule, yields and overlap / first_alone / run_ahead semantics of ChatterboxEngine.synthesize_stream
+        around the GPT-2 T3 (chunked through T3TurboEngine.generate(async_mode=True) / advance / peek) and the 2-step meanflow flow.  A round vocodes the
+        sampled ids < 6561; the FINAL round of an utterance appends the three S3GEN_SIL tokens exactly as synthesize() does and keeps every token
+        (drop_last_token=False), non-final rounds carry no silence and hold back 2 * lookahead frames.  T3 can sample max_gen_len + 1 tokens: the default
+        z / phase / noise cover that many plus the 3 silence tokens.  The last round is a full synthesis: identical mel to synthesize() for the same noise."""
+        t3_kw = dict(max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, uniforms=uniforms,
+                     ban_eos=ban_eos, ban_from=ban_from)
+        sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
+
+        def round_tokens(toks, fin):
+            st = [torch.cat([t[t < SPEECH_VOCAB], sil]) if f else t[t < SPEECH_VOCAB] for t, f in zip(toks, fin)]
+            return [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
+
+        yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_gen_len + 1, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=3,
+                                      first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
+                                      noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
+                                      run_ahead=run_ahead)

@@ -37,16 +37,16 @@ def llama3_rope_tables(max_pos, head_dim=64, theta=500000.0, factor=8.0, low=1.0
 
 
 class _LoopHandle:
-    """Owns a cbx_t3_loop_t (destroyed with the state / geometry entry that holds it)."""
+    """Owns a cbx_t3_loop_t (or, with destroy="cbx_gpt2_loop_destroy", a cbx_gpt2_loop_t; destroyed with the state / geometry entry that holds it)."""
 
-    def __init__(self, h):
-        self.h = h
+    def __init__(self, h, destroy="cbx_t3_loop_destroy"):
+        self.h, self.destroy = h, destroy
 
     def __del__(self):
         try:
             from ._lib import lib
             if self.h:
-                lib.cbx_t3_loop_destroy(self.h)
+                getattr(lib, self.destroy)(self.h)
         except Exception:
             pass
 

@@ -86,6 +86,9 @@ class T3TurboEngine(VoicePrefixCache):
         self._state = {}
         self.share_prefix, self._prefix_cache = os.environ.get("CBX_T3_SHARE_PREFIX", "1") == "1", []  # VoicePrefixCache: speaker + prompt tokens of a voice prefilled once
         self.c_prefill = os.environ.get("CBX_T3_CSTEP", "1") == "1"  # the prefill through cbx_gpt2_prefill (one ctypes call instead of nine launches per layer)
+        # chunked decoding (generate(async_mode=True) / advance) replays the token step through cbx_gpt2_loop_* (the step captured in a hipGraph by the LIBRARY);
+        # the one-shot generate() keeps its Python replay loop
+        self.c_loop = os.environ.get("CBX_TURBO_CLOOP", "1") == "1"
         self.time_decode, self.decode_events = False, []  # (start, end, steps, prefill lengths, rows) per generate() when enabled (bench.py)
 
     def _forward_decode(self, st):
@@ -189,6 +192,166 @@ class T3TurboEngine(VoicePrefixCache):
         self._forward(st)
         self._sample(st)
 
+    def _row(self, st):
+        """Does this state's step run on the few-row kernels (_forward_decode_row)?"""
+        return self.decode_mode == "v2" and st["B"] <= 2 and bool(self.tune.get("row_path")) and self.D % 256 == 0
+
+    def _use_c_step(self, st):
+        """Is this state's step served by cbx_gpt2_decode_step (the row path and the <= 16-row packed path; not the 7-launch form)?"""
+        return self.decode_mode == "v2" and st["B"] <= 16
+
+    def _c_step_desc(self, st):
+        """Build (once per state and geometry) the cbx_gpt2_step_t of this state: st["cstep"] = (descriptor, layers, packed layers, sampler[, loop handle]).
+        Every field is what _forward_decode_row / _forward_decode_v2 + _sample pass to their launches."""
+        import ctypes
+        from ._lib import Gpt2Layer, Gpt2PackedLayer, Gpt2Step, SamplerParams
+        if "cstep" in st:
+            return st["cstep"]
+        p = lambda t: t.data_ptr()
+        ws, tn, D, L = st["dws"], self.tune, self.D, self.L
+        row = self._row(st)
+        layers = (Gpt2Layer * L)()
+        for i, lw in enumerate(self.layers):
+            a = layers[i]
+            a.ln1_w, a.ln1_b, a.ln2_w, a.ln2_b = p(lw["ln1"][0]), p(lw["ln1"][1]), p(lw["ln2"][0]), p(lw["ln2"][1])
+            a.wqkv, a.bqkv, a.wo, a.bo, a.wfc, a.bfc, a.wpr, a.bpr = (p(lw[k]) for k in ("wqkv", "bqkv", "wo", "bo", "wfc", "bfc", "wpr", "bpr"))
+        packed = None
+        d = Gpt2Step()
+        d.n_layers, d.rows, d.dim, d.n_heads, d.vocab, d.row_path, d.eps, d.attn_scale = L, st["B"], D, self.H, self.V, int(row), 1e-5, 0.125
+        d.layers = layers
+        d.speech_emb, d.wpe, d.lnf_w, d.lnf_b, d.head, d.head_b = p(self.speech_emb), p(self.wpe), p(self.lnf[0]), p(self.lnf[1]), p(self.head), p(self.head_b)
+        d.kc, d.vc, d.max_ctx = p(st["kc"]), p(st["vc"]), st["kc"].shape[3]
+        d.kv_layer_stride, d.kv_row_stride, d.kv_head_stride = st["kc"].stride(0), st["kc"].stride(1), st["kc"].stride(2)
+        d.next_ids, d.positions, d.qkv = p(st["next_ids"]), p(st["positions"]), p(ws["qkv"])
+        d.logits, d.ld_logits = p(st["logits"]), st["logits"].stride(0)
+        if row:
+            d.x, d.g, d.parts, d.n_splits, d.chunks = p(ws["x"]), p(ws["g"]), p(ws["parts"]), ws["parts"].shape[2], int(tn["row_chunks"])
+        else:
+            self._prepare_tune()
+            qtc, odtc = self._tiles()
+            packed = (Gpt2PackedLayer * L)()
+            for i, lw in enumerate(self.layers):
+                a = packed[i]
+                a.wqkv, a.wo, a.wfc, a.wpr = p(self._image(lw, "wqkv", qtc)), p(self._image(lw, "wo", odtc)), p(lw["wfc_pk"]), p(self._image(lw, "wpr", odtc))
+                a.qkv_cw, a.qkv_cb, a.fc_cw, a.fc_cb = p(lw["c_qkv"][0]), p(lw["c_qkv"][1]), p(lw["c_fc"][0]), p(lw["c_fc"][1])
+            d.packed = packed
+            d.head_pk, d.head_cw, d.head_cb = p(self.head_pk), p(self.c_head[0]), p(self.c_head[1])
+            d.x_a, d.x_b, d.att, d.g_pk, d.pd = p(ws["x_pk"]), p(ws["x2_pk"]), p(ws["att_pk"]), p(ws["g_pk"]), p(ws["pd_pk"])
+            d.qkv_tile, d.od_tile = (0 if qtc == 16 else qtc), (0 if odtc == 16 else odtc)
+            d.d_ksplit, d.o_nw, d.d_nw = int(tn["d_ks"]), int(tn["o_nw"]), int(tn["d_nw"])
+            d.head_ct = int(tn.get("head_ct") or 0) if D % 256 == 0 else 0
+            d.gemv_flags = ops.gemv_flags(self.knobs.get("pre_epi"), self.knobs.get("deep"))
+            da = st["da"]
+            d.da_unroll, d.da_pipeline, d.da_split_min = da.unroll, da.pipeline, da.split_min
+            d.da_ws, d.da_cnt, d.da_pairs = ops._p(da.ws), ops._p(da.cnt), (da.max_pairs if da.ws is not None else 0)
+        sp = SamplerParams()
+        for k, v in dict(logits=st["logits"], ld=st["logits"].stride(0), V=self.V, B=st["B"], cfg=0, order=1, eos_token=STOP_SPEECH,
+                         dev_params=st["samp_dev"], seen=st["seen"], uniforms=st["uniforms"], max_steps=st["max_steps"], step=st["step"],
+                         out_tokens=st["out_tokens"], done=st["done"], n_generated=st["n_generated"], next_ids=st["next_ids"],
+                         next_pos_ids=st["next_pos_ids"], positions=st["positions"], ctx_lens=st["ctx_lens"]).items():
+            setattr(sp, k, v.data_ptr() if torch.is_tensor(v) else v)
+        d.sampler = ctypes.pointer(sp)
+        st["cstep"] = (d, layers, packed, sp)  # keep the host structures alive
+        return st["cstep"]
+
+    def _decode_step_c(self, st):
+        """The same token step through the stage-level C entry point cbx_gpt2_decode_step: one ctypes call instead of 5 launches per layer + 2."""
+        import ctypes
+        from ._lib import check, lib
+        check(lib.cbx_gpt2_decode_step(ctypes.byref(self._c_step_desc(st)[0]), ops._stream()), "cbx_gpt2_decode_step")
+
+    def _c_loop(self, st):
+        """The cbx_gpt2_loop_t of this state's current geometry, created on first use and dropped with the descriptor (co_resident)."""
+        import ctypes
+        from ._lib import check, lib
+        from .t3 import _LoopHandle
+        self._c_step_desc(st)
+        if len(st["cstep"]) == 4:
+            h = ctypes.c_void_p()
+            torch.cuda.synchronize()
+            check(lib.cbx_gpt2_loop_create(ctypes.byref(st["cstep"][0]), ops._stream(), ctypes.byref(h)), "cbx_gpt2_loop_create")
+            st["cstep"] = st["cstep"] + (_LoopHandle(h, "cbx_gpt2_loop_destroy"),)
+        return st["cstep"][4].h
+
+    def _run_c_loop(self, st, n_steps, poll_every):
+        import ctypes
+        from ._lib import check, lib
+        ran = ctypes.c_int(0)
+        check(lib.cbx_gpt2_loop_run(self._c_loop(st), int(n_steps), int(poll_every), ops._stream(), ctypes.byref(ran)), "cbx_gpt2_loop_run")
+        return int(ran.value)
+
+    @torch.inference_mode()
+    def _capture(self, st):
+        """torch-captured graph of one token step (the one-shot generate()'s replay loop; chunked decoding of more than 16 rows)."""
+        torch.cuda.synchronize()
+        saved = {k: st[k].clone() for k in ("seen", "step", "done", "n_generated", "out_tokens", "next_ids", "next_pos_ids",
+                                            "positions", "ctx_lens", "logits")}
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            self._decode_step(st)
+        for k, v in saved.items():
+            st[k].copy_(v)
+        st["graph"] = gr
+
+    def co_resident(self, on):
+        """The decode step beside the flow's co-resident forms (TurboEngine.synthesize_stream(overlap=True)).  The row path of 1 .. 2 rows keeps its launches
+        (no LDS, no partial images); the packed path of 3 .. 16 rows takes the geometry T3Engine.co_resident uses (mlp c_proj on 8-wave workgroups with 4
+        split-K partial images, 16-column c_proj tiles).
+        on=False: back to the engine's own geometry.  Switching drops the captured steps of the packed-path states."""
+        if getattr(self, "_co_res", False) == bool(on):
+            return
+        if on:
+            self._co_saved = dict(self.tune)
+            self.tune.update(d_ks=4, d_nw=8, half_tiles=0, od_tc=0)
+        else:
+            self.tune = dict(self._co_saved)
+        self._co_res = bool(on)
+        for st in self._state.values():
+            if not self._row(st):
+                st["graph"] = None
+                st.pop("cstep", None)
+
+    @ops.on_device
+    def advance(self, handle, n_steps):
+        """Enqueue up to `n_steps` further token steps of an async generate() (finished rows are no-ops inside the sampler).  Returns the number of steps
+        enqueued.  No host synchronisation (the C loop runs with poll_every = 0)."""
+        st = handle["st"]
+        n = max(0, min(int(n_steps), handle["max_new_tokens"] - handle["next_i"]))
+        if n and self.c_loop and self._use_c_step(st) and self.dev.type == "cuda":
+            self._run_c_loop(st, n, 0)
+        elif n:
+            if self.dev.type == "cuda" and st["graph"] is None:
+                self._capture(st)
+            for _ in range(n):
+                if st["graph"] is not None:
+                    st["graph"].replay()
+                else:
+                    self._decode_step(st)
+        handle["next_i"] += n
+        return n
+
+    @ops.on_device
+    def peek(self, handle):
+        """Tokens sampled so far, EOS included (synchronises with the launch stream): (list of B 1-D LongTensors, list of B done flags).  The done flags are
+        read first (see T3Engine.peek)."""
+        st, B = handle["st"], handle["B"]
+        done = st["done"].tolist()
+        n = st["n_generated"].tolist()
+        toks = st["out_tokens"].cpu()
+        return [toks[b, : n[b]].clone() for b in range(B)], [bool(d) for d in done]
+
+    @ops.on_device
+    def collect(self, handle):
+        """The tokens of an (async) generate() call as generate() returns them: without a trailing EOS.  Must run on the stream the call was enqueued on."""
+        st, B = handle["st"], handle["B"]
+        n = st["n_generated"].tolist()
+        toks = st["out_tokens"].cpu()
+        out = []
+        for b in range(B):
+            t = toks[b, : n[b]]
+            out.append(t[:-1].clone() if n[b] and int(t[-1]) == STOP_SPEECH else t.clone())
+        return out
+
     def _get_state(self, B, max_ctx, max_steps):
         key = (B, max_ctx, max_steps)
         if key in self._state:
@@ -235,9 +398,12 @@ class T3TurboEngine(VoicePrefixCache):
     @ops.on_device
     @torch.inference_mode()
     def generate(self, conds, text_tokens, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95, repetition_penalty=1.2,
-                 uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16, debug_logits=False):
+                 uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16, debug_logits=False, async_mode=False, run_steps=None):
         """conds: one cond dict (speaker_emb (1,256), cond_prompt_speech_tokens (1,375)) or a list of B; text_tokens: list of B
-        1-D LongTensors (GPT-2 BPE ids, no SOT/EOT).  Returns a list of B 1-D LongTensors without the trailing EOS."""
+        1-D LongTensors (GPT-2 BPE ids, no SOT/EOT).  Returns a list of B 1-D LongTensors without the trailing EOS.
+        Chunked use (streaming synthesis, the protocol of T3Engine.generate): `async_mode=True, run_steps=k` samples only the first k of the
+        max_gen_len + 1 tokens and returns a handle without synchronising; `advance(handle, n)` enqueues n more token steps (cbx_gpt2_loop_run),
+        `peek(handle)` fetches the tokens sampled so far, `collect(handle)` the result of the call."""
         dev, B, D = self.dev, len(text_tokens), self.D
         voice = conds if isinstance(conds, dict) else None  # one voice for the whole batch: its conditioning prefix may be cached
         conds = [conds] * B if isinstance(conds, dict) else conds
@@ -248,7 +414,7 @@ class T3TurboEngine(VoicePrefixCache):
                 f"uniforms must hold at least max_gen_len + 1 = {max_gen_len + 1} draws per utterance"
             uniforms = uniforms.view(B, -1)
         if B > self.MAX_BATCH:  # one row per utterance (no CFG); the decode GEMV serves M <= 64 rows
-            assert not debug_logits, "sub-batching is only defined for the plain token path"
+            assert not (debug_logits or async_mode), "sub-batching is only defined for the plain token path"
             out = []
             for lo in range(0, B, self.MAX_BATCH):
                 hi = min(B, lo + self.MAX_BATCH)
@@ -336,6 +502,11 @@ class T3TurboEngine(VoicePrefixCache):
         self._sample(st)
         # later processor calls see ids = tokens generated so far, without the start token (t3.py:448-449)
         st["seen"][:, START_SPEECH] = (st["out_tokens"][:, 0] == START_SPEECH).to(torch.uint8)
+        if async_mode:  # everything is enqueued on the current stream; no host synchronisation happens
+            assert not debug_logits, "async_mode is the plain token path"
+            handle = dict(st=st, B=B, next_i=1, max_new_tokens=n_samples)
+            self.advance(handle, (n_samples if run_steps is None else max(1, min(n_samples, int(run_steps)))) - 1)
+            return handle
         if debug_logits:
             use_graph = False
         if use_graph and st["graph"] is None and n_samples > 1:

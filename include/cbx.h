@@ -32,7 +32,8 @@ extern "C" {
                                   (one workgroup per CU that leaves half of the register file and 64 KiB of LDS to another stream), CBX_GEMV_SHALLOW;
                               14: the batch-1 decode path of the GPT-2 backbones (Turbo / Nano): cbx_gemv_row_f32, cbx_decode_attn_parts; the token loop in C: cbx_t3_loop_*;
                               15: cbx_flash_attn_kv_f32 (K / V head strides: attention over the KV cache in the prefill);
-                              16: cbx_gpt2_prefill (the prefill of the GPT-2 backbones as one call, optionally behind a cached conditioning prefix) */
+                              16: cbx_gpt2_prefill (the prefill of the GPT-2 backbones as one call, optionally behind a cached conditioning prefix); added
+                                  later without a version step (no existing struct or signature changed): cbx_gpt2_decode_step, cbx_gpt2_loop_* */
 #define CBX_EINVAL (-22)
 
 /* activations usable in GEMM / elementwise epilogues */
@@ -563,6 +564,56 @@ typedef struct cbx_gpt2_prefill_t {
     long kv_layer_stride, kv_row_stride, kv_head_stride;  /* floats */
 } cbx_gpt2_prefill_t;
 int cbx_gpt2_prefill(const cbx_gpt2_prefill_t* d, void* stream);
+
+/* ---- ONE token step of T3.inference_turbo's loop for every row (t3.py:392-468: the q_len == 1 HF GPT2Model forward over the KV cache, ln_f, speech_head, the
+ * Temperature -> TopK -> TopP -> RepetitionPenalty processors and the multinomial draw) ----
+ * Issues exactly the launches of chatterbox_amd/t3_turbo.py's token step, with the same arguments (bit-identical tokens and logits), and adds no arithmetic:
+ *   row_path = 1 (rows <= 4; the engine uses it for 1 .. 2 rows: T3TurboEngine._forward_decode_row): cbx_embed_f32, n_layers x [cbx_gemv_row_f32 (ln_1 + c_attn),
+ *     cbx_decode_attn_parts, cbx_gemv_row_f32 (attention merge + c_proj + residual), cbx_gemv_row_f32 (ln_2 + c_fc + gelu_new), cbx_gemv_row_f32 (mlp c_proj +
+ *     residual)], cbx_gemv_row_f32 (ln_f + speech head), cbx_t3_sample; weights row-major (cbx_gpt2_layer_t);
+ *   row_path = 0 (rows <= 16: _forward_decode_v2): cbx_embed_f32 (packed), n_layers x [cbx_gemv_f32 (LayerNorm folded into c_attn, the previous layer's split-K
+ *     partial images summed into the operand), cbx_decode_attn_rope, cbx_gemv_f32 (c_proj + bias + residual), cbx_gemv_f32 (LayerNorm folded into c_fc + gelu_new),
+ *     cbx_gemv_f32 (mlp c_proj: d_ksplit partial images, or + residual in place when d_ksplit == 1)], cbx_gemv_f32 (ln_f folded into the head), cbx_t3_sample;
+ *     weights are cbx_pack_gemv_weight_f32 images (cbx_gpt2_packed_layer_t).
+ * More than 16 rows (the engine's 7-launch form) are refused.  No allocation, no synchronisation, hipGraph-capturable. */
+typedef struct cbx_gpt2_packed_layer_t {
+    const float *wqkv, *wo, *wfc, *wpr;            /* packed images: c_attn (qkv_tile columns per tile), attention c_proj (od_tile), c_fc (16), mlp c_proj (od_tile) */
+    const float *qkv_cw, *qkv_cb, *fc_cw, *fc_cb;  /* LayerNorm-fold constants of c_attn / c_fc (cbx_gemv_t.ln_cw / ln_cb) */
+} cbx_gpt2_packed_layer_t;
+typedef struct cbx_gpt2_step_t {
+    int n_layers, rows, dim, n_heads, vocab;
+    int row_path;                         /* 1: the few-row kernels, 0: the packed 16-row-tile path */
+    float eps, attn_scale;
+    const cbx_gpt2_layer_t* layers;       /* HOST array [n_layers]: LayerNorm weights / biases, projection biases, row-major weights (row path) */
+    const cbx_gpt2_packed_layer_t* packed;/* HOST array [n_layers] (packed path) or NULL */
+    const float *speech_emb, *wpe;        /* [V][dim], [n_positions][dim]: the input is speech_emb[next_ids] + wpe[positions] */
+    const float *lnf_w, *lnf_b, *head, *head_b;   /* ln_f, row-major speech head [vocab][dim] + bias (row path; head_b unused on the packed path) */
+    const float *head_pk, *head_cw, *head_cb;     /* packed path: head image, ln_f-fold constants */
+    float *kc, *vc;                       /* KV cache [n_layers][rows][n_heads][max_ctx][64] */
+    long kv_layer_stride, kv_row_stride, kv_head_stride;  /* floats */
+    int max_ctx;
+    const long long* next_ids;            /* [rows] (written by the sampler) */
+    const int* positions;                 /* [rows] cache / wpe position of the token to embed */
+    float *x, *qkv, *g, *parts;           /* x [rows][dim], qkv [rows][3 dim] (both paths); row path: g [rows][4 dim], parts [rows][n_heads][n_splits][CBX_ATTN_PART_REC] */
+    int n_splits, chunks;                 /* row path: cbx_attn_parts_t.n_splits / chunks */
+    float *x_a, *x_b, *att, *g_pk, *pd;   /* packed path: residual images [ceil16(rows)][dim] (ping-pong), [..][dim], [..][4 dim], partial images [d_ksplit][..][dim] */
+    int qkv_tile, od_tile;                /* cbx_gemv_t.half_tile of the c_attn resp. both c_proj images (0 = 16 columns) */
+    int d_ksplit, o_nw, d_nw, head_ct, gemv_flags;  /* mlp c_proj split-K factor (1, 2, 4) and waves, attention c_proj waves, head column tiles, cbx_gemv_t.flags */
+    int da_unroll, da_pipeline, da_split_min;       /* cbx_decode_attn_t geometry + split-context workspace of the attention launches */
+    float* da_ws; int* da_cnt; long da_pairs;
+    float* logits;                        /* [rows][ld_logits] */
+    long ld_logits;
+    const cbx_sampler_t* sampler;         /* sampler descriptor (host struct, order 1, cfg 0) run at the end of the step, or NULL */
+} cbx_gpt2_step_t;
+int cbx_gpt2_decode_step(const cbx_gpt2_step_t* d, void* stream);
+/* The TOKEN LOOP of T3.inference_turbo in C (t3.py:392-468 incl. its EOS test): the contract of cbx_t3_loop_* -- deep copy of the descriptor (layers, packed,
+ * sampler), ONE cbx_gpt2_decode_step captured in a hipGraph on a stream of the library's own (one linear chain of launches), replayed up to n_steps times on
+ * `stream`; poll_every > 0 fetches the done flags every poll_every steps and ends early once every row has sampled its EOS, 0 enqueues all n_steps without
+ * synchronising; *steps_run = steps enqueued. */
+typedef struct cbx_gpt2_loop cbx_gpt2_loop_t;
+int cbx_gpt2_loop_create(const cbx_gpt2_step_t* step, void* stream, cbx_gpt2_loop_t** out);
+int cbx_gpt2_loop_run(cbx_gpt2_loop_t* h, int n_steps, int poll_every, void* stream, int* steps_run);
+int cbx_gpt2_loop_destroy(cbx_gpt2_loop_t* h);
 
 /* ---- stage-level entry points of the S3Gen flow decoder and of the HiFT vocoder (ABI v12) ----
  * A plane-format operand (see PLANE-FORMAT operands above) as the stage descriptors carry it: base of the h plane with any column offset applied, row
