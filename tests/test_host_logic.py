@@ -578,3 +578,49 @@ def test_c_blocks_of_integration_md_compile(tmp_path):
         src = tmp_path / f"block{i}.c"
         src.write_text(b)
         subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)])
+
+
+# entry points of include/cbx.h that launch no kernel, each with its reason; everything else must be named by a kernel-level test
+_NO_LAUNCH = {
+    "cbx_abi_version": "returns a constant",
+    "cbx_gemm_ln_fusable": "host-side predicate that mirrors the GEMM dispatcher's conditions",
+    "cbx_set_range_flag": "registers a device word", "cbx_set_stream_coresident": "registers a stream handle",
+    "cbx_set_planes_tile": "process-wide knob", "cbx_set_planes_persist": "process-wide knob", "cbx_set_attn_planes_version": "process-wide knob",
+    "cbx_set_gemv_deep_batches": "process-wide knob", "cbx_set_gemv_epilogue_prefetch": "process-wide knob", "cbx_set_split_tile": "process-wide knob",
+    "cbx_set_decode_attn_unroll": "process-wide knob", "cbx_set_decode_attn_pipeline": "process-wide knob", "cbx_set_decode_attn_split_min": "process-wide knob",
+    "cbx_set_decode_attn_workspace": "registers a workspace",
+    "cbx_t3_loop_destroy": "frees the captured graph", "cbx_gpt2_loop_destroy": "frees the captured graph",
+}
+_KERNEL_LEVEL_MODULES = ("test_ops_gpu", "test_planes_gpu", "test_zz_abi_v9_gpu", "test_zzz_stage_seams_gpu", "test_turbo_stream_*", "test_models_gpu", "test_sampler_gpu",
+                         "test_frontend_ops_gpu")
+
+
+def test_every_kernel_entry_point_is_named_by_a_kernel_level_test():
+    """Every `int cbx_*(` of include/cbx.h that launches a kernel is named in a kernel-level test module -- directly, through a call of its ops.py wrapper
+    (`ops.<wrapper>(`, wrappers of wrappers included), or, for the two captured-loop constructors, through the engine method that alone calls them."""
+    import glob
+    hdr = open(os.path.join(ROOT, "include", "cbx.h")).read()
+    entries = sorted(set(re.findall(r"^int (cbx_\w+)\(", hdr, re.M)))
+    assert len(entries) >= 60 and "cbx_t3_sample" in entries and "cbx_fsq_index" in entries
+    assert set(_NO_LAUNCH) <= set(entries)
+    src = open(os.path.join(ROOT, "chatterbox_amd", "ops.py")).read()
+    bodies = {m.group(1): m.group(0) for m in re.finditer(r"^def (\w+)\(.*?(?=^def |^class |\Z)", src, re.M | re.S)}
+    wrappers = {}
+    for fn, body in bodies.items():
+        for e in re.findall(r"lib\.(cbx_\w+)\(", body):
+            wrappers.setdefault(e, set()).add(fn)
+    for e, ws in wrappers.items():  # linear() / conv1d() / bmm() call gemm(), ...
+        ws |= {fn for fn, body in bodies.items() if any(re.search(rf"(?<![\w.]){w}\(", body) for w in ws if w != fn)}
+    for e, (mod, method) in {"cbx_t3_loop_create": ("t3", "_c_loop"), "cbx_gpt2_loop_create": ("t3_turbo", "_c_loop")}.items():
+        eng = open(os.path.join(ROOT, "chatterbox_amd", mod + ".py")).read()
+        body = re.search(rf"^    def {method}\(.*?(?=^    def |\Z)", eng, re.M | re.S).group(0)
+        assert f"lib.{e}(" in body
+        wrappers.setdefault(e, set()).add("." + method)
+    files = sorted(f for pat in _KERNEL_LEVEL_MODULES for f in glob.glob(os.path.join(ROOT, "tests", pat + ".py")))
+    assert len(files) >= len(_KERNEL_LEVEL_MODULES)
+    text = "\n".join(open(f).read() for f in files)
+    named = lambda e: e in text or any((w + "(" in text) if w.startswith(".") else re.search(rf"\bops\.{w}\(", text) for w in wrappers.get(e, ()))
+    missing = [e for e in entries if e not in _NO_LAUNCH and not named(e)]
+    assert not missing, f"entry points that launch kernels but that no kernel-level test names: {missing}"
+    for e in ("cbx_axpby_f32", "cbx_dwconv1d_f32", "cbx_stats_pool_f32"):  # the scan itself: these are reached through their wrappers only
+        assert e not in text and named(e)

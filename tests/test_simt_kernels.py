@@ -102,6 +102,29 @@ def test_gemv_epilogue_prefetch_on_the_emulator(emu, name, args, monkeypatch):
     test_zz_abi_v9_gpu.test_gemv_epilogue_prefetch_equals_plain(CPU, name, args, monkeypatch)
 
 
+# tests/test_sampler_gpu.py and tests/test_frontend_ops_gpu.py at emulator sizes (the sampler: 10 utterances per launch, one seed, a reduced matrix that keeps both
+# orders, cfg 0 / 1, dev_params, V < 1024, V not a multiple of 1024, the ties and the state machine)
+_SAMPLER = [("test_sampler_matrix", (0, 10, 1, True)), ("test_sampler_matrix", (1, 10, 1, True)),
+            ("test_sampler_dev_params_per_utterance", (0, 10, 704)), ("test_sampler_dev_params_per_utterance", (1, 10, 704)),
+            ("test_sampler_state_machine", (0, 1)), ("test_sampler_state_machine", (1, 0)), ("test_sampler_state_machine", (1, 1)),
+            ("test_sampler_no_mass_left_gives_the_best_allowed_raw_logit", (0,)), ("test_sampler_no_mass_left_gives_the_best_allowed_raw_logit", (1,))]
+_FRONT = [("test_dwconv1d", (2, 50, 1280, 31, 15, 1)), ("test_dwconv1d", (5, 20, 8, 4, 0, 0)), ("test_dwconv1d", (5, 20, 4, 5, 4, 1)), ("test_dwconv1d", (5, 7, 8, 31, 15, 0)),
+          ("test_dwconv1d", (3, 1, 4, 3, 1, 1)), ("test_dwconv1d", (5, 33, 12, 2, 1, 1)),
+          ("test_lstm_cell", (1, 256)), ("test_lstm_cell", (5, 40)), ("test_affine_act", (4,)), ("test_affine_act", (128,)), ("test_affine_act", (1000,)),
+          ("test_cplx_power", (201,)), ("test_cplx_power", (257,)), ("test_cplx_power", (513,)), ("test_cplx_power", (1,)), ("test_unary", ()), ("test_reduce_max", (False,)),
+          ("test_seg_context_and_gate", (100,)), ("test_seg_context_and_gate", (37,)), ("test_stats_pool", (1,)), ("test_stats_pool", (3,)), ("test_stats_pool", (512,)),
+          ("test_fsq_index", (2000,)), ("test_axpby", ()), ("test_add_norm_layernorm_form", (768, 1)), ("test_add_norm_layernorm_form", (1024, 2)),
+          ("test_add_norm_layernorm_form", (768, 4)), ("test_softmax_rows", ()), ("test_hift_stft_ragged", ()), ("test_embed_negative_ids_and_scale", ()),
+          ("test_act_kinds", (1 << 13,)), ("test_add_rmsnorm_first_abi_name", ()), ("test_flash_attn_plane_output", (130, False)), ("test_flash_attn_plane_output", (103, True))]
+
+
+@pytest.mark.parametrize("name,args", _SAMPLER + _FRONT, ids=[f"{n}{list(a)}" for n, a in _SAMPLER + _FRONT])
+def test_sampler_and_frontend_op_bodies_on_the_emulator(emu, name, args):
+    import test_frontend_ops_gpu
+    import test_sampler_gpu
+    getattr(test_sampler_gpu if hasattr(test_sampler_gpu, name) else test_frontend_ops_gpu, name)(CPU, *args)
+
+
 _PLANES = [("test_split_planes_roundtrip_and_range_flag", ()), ("test_layernorm_planes", ()), ("test_gemm_planes_transposed_rejects_bad_arguments", ()),
            ("test_range_flag_words_attribute_a_trip_to_the_batch_that_raised_it", ())]
 
