@@ -147,6 +147,12 @@ class Gpt2Step(ctypes.Structure):  # cbx_gpt2_step_t
                 + [("da_ws", c_f), ("da_cnt", c_f), ("da_pairs", c_long), ("logits", c_f), ("ld_logits", c_long), ("sampler", ctypes.POINTER(SamplerParams))])
 
 
+class PrefillEmbed(ctypes.Structure):  # cbx_prefill_embed_t
+    _fields_ = ([(k, c_int) for k in ("B", "cfg", "n_bos", "abs_pos", "S", "pos0", "dim")] + [("bos_id", ctypes.c_longlong), ("meta", c_f), ("ids", c_f), ("cond", c_f),
+                                                                                               ("cond_stride", c_long)]
+                + [(k, c_f) for k in ("text_emb", "text_pos", "speech_emb", "speech_pos", "x", "positions", "cache_rows", "last")])
+
+
 class PlanesRef(ctypes.Structure):  # cbx_planes_t (ABI v12)
     _fields_ = [("p", c_f), ("ld", c_long), ("lo", c_long)]
 
@@ -264,6 +270,8 @@ _SIGS = {
     "cbx_gpt2_loop_create": ([ctypes.POINTER(Gpt2Step), c_f, ctypes.POINTER(c_f)], c_int),
     "cbx_gpt2_loop_run": ([c_f, c_int, c_int, c_f, ctypes.POINTER(c_int)], c_int),
     "cbx_gpt2_loop_destroy": ([c_f], c_int),
+    "cbx_prefill_embed": ([ctypes.POINTER(PrefillEmbed), c_f], c_int),
+    "cbx_kv_prefix_paste_f32": ([c_f, c_int, c_f, c_f, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_f], c_int),
     "cbx_t3_sample": ([ctypes.POINTER(SamplerParams), c_f], c_int),
     "cbx_cfm_solve": ([ctypes.POINTER(CfmSolve), c_f], c_int),
     "cbx_s3gen_encode": ([ctypes.POINTER(S3Encode), c_f], c_int),

@@ -158,7 +158,116 @@ def _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap):
     return dict(first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, overlap=overlap)
 
 
-class _Base:
+
+# ---------------------------------------------------------------------------------------------------------------- generate_batch: host-side plumbing
+def _per_request(value, B, name, one):
+    """A per-request argument as a list of B.  `one` names the types that are ONE entry of this argument (a path, a Conditionals, a language id, ...): such a value,
+    or None, serves every request; anything else must be a list or tuple of exactly B entries (ValueError before anything is launched).  A (waveform, sample_rate)
+    pair is an entry, never the whole argument: it goes inside a list."""
+    if value is None or isinstance(value, one):
+        return [value] * B
+    if not isinstance(value, (list, tuple)):
+        raise TypeError(f"{name}: expected {' / '.join(t.__name__ for t in one)} or a list of {B}, got {type(value).__name__}")
+    if len(value) != B:
+        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
+    return list(value)
+
+
+_PATH = (str, bytes, os.PathLike)
+# T3 cond dicts of a voice, kept while its T3Cond lives (generate_batch): id(T3Cond) -> [emotion tensor the entry was built from, its value, {exaggeration: dict}]
+_T3_DICTS = {}
+
+
+def _t3_dict(t3, exaggeration):
+    """The cond dict of voice `t3` at `exaggeration`: one dict over the voice's own tensors at its own exaggeration, else with the emotion tensor `generate` would
+    build.  The same dict from call to call, so the engines' voice-prefix cache (which matches tensors by identity) hits; dropped when the voice is garbage."""
+    import weakref
+    ent = _T3_DICTS.get(id(t3))
+    if ent is None or ent[0] is not t3.emotion_adv:  # first sight of this voice (or its emotion was replaced): read its value once
+        if ent is None:
+            weakref.finalize(t3, _T3_DICTS.pop, id(t3), None)
+        own = None if t3.emotion_adv is None else float(torch.as_tensor(t3.emotion_adv).reshape(-1)[0])
+        ent = _T3_DICTS[id(t3)] = [t3.emotion_adv, own, {}]
+    key = None if (ent[1] is None or ent[1] == float(exaggeration)) else float(exaggeration)
+    d = ent[2].get(key)
+    if d is None or d["speaker_emb"] is not t3.speaker_emb or d["cond_prompt_speech_tokens"] is not t3.cond_prompt_speech_tokens:  # (T3Cond.to() replaces tensors)
+        d = ent[2][key] = t3.as_dict() if key is None else dict(t3.as_dict(), emotion_adv=key * torch.ones(1, 1, 1))
+    return d
+
+
+def batch_plan(lengths, max_batch):
+    """Execution order of a batch: requests sorted by length (stable), cut into consecutive sub-batches of at most `max_batch`; each sub-batch is a list of the
+    caller's indices.  Neighbours in length share a sub-batch, which keeps the padding of the prefill and of the flow down."""
+    assert max_batch >= 1
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    return [order[lo:lo + max_batch] for lo in range(0, len(order), max_batch)]
+
+
+def _sampling_lists(B, **params):
+    from .t3 import per_utterance
+    return {k: per_utterance(v, B, k) for k, v in params.items()}
+
+
+def _one_or_list(items):
+    """One object when every request uses the very same one (the engines' single-voice path), else the list."""
+    return items[0] if all(it is items[0] for it in items) else list(items)
+
+
+def _pick(lst, idx):
+    return [lst[i] for i in idx]
+
+
+class _BatchMixin:
+    """generate_batch of the three TTS classes: many requests, mixed voices, one call."""
+    max_batch = None  # utterances per device batch of generate_batch (None: the T3 engine's MAX_BATCH)
+
+    def _voices_of_batch(self, B, audio_prompt_paths, conds, exaggeration, analyse=None):
+        """One Conditionals per request: analysed from `audio_prompt_paths` (equal paths once per call), taken from `conds`, or self.conds.  Never writes self.conds."""
+        if audio_prompt_paths is not None and conds is not None:
+            raise ValueError("give audio_prompt_paths or conds, not both")
+        if audio_prompt_paths is not None:
+            paths, done, out = _per_request(audio_prompt_paths, B, "audio_prompt_paths", _PATH), {}, []
+            for pth, ex in zip(paths, exaggeration):
+                key = (os.fspath(pth) if isinstance(pth, _PATH) else id(pth), ex)
+                if key not in done:
+                    done[key] = (analyse or self._analyse)(pth, ex)
+                out.append(done[key])
+            return out
+        out = _per_request(conds, B, "conds", (Conditionals,)) if conds is not None else [self.conds] * B
+        assert all(c is not None for c in out), "Please `prepare_conditionals` first or specify `audio_prompt_path`"
+        return out
+
+    def _run_batch(self, tokens, voices, exaggeration, samp, generator, synth_kw, n_draws):
+        """Sub-batches of at most max_batch requests in order of text length: one sub-batch runs the serial schedule (synthesize), several the throughput schedule
+        (synthesize_pipelined; an engine without one runs them one after the other).  Returns the finished waveforms in the caller's order."""
+        B = len(tokens)
+        dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
+        plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
+        jobs = []
+        for idx in plan:
+            job = dict(text_tokens=_pick(tokens, idx), t3_conds=_one_or_list(_pick(dicts, idx)), gen_ref=_one_or_list([voices[i].gen for i in idx]),
+                       **{k: _pick(v, idx) for k, v in samp.items()})
+            if generator is not None:  # repeatable: the sampling draws of every sub-batch come from the generator, in execution order
+                job["uniforms"] = torch.rand(len(idx), n_draws, device=self.engine.dev, generator=generator)
+                job["generator"] = generator
+            jobs.append(job)
+        out = [None] * B
+        if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined"):
+            results = (r[0] for r in self.engine.synthesize_pipelined(jobs, **synth_kw))
+        else:
+            def serial():
+                for job in jobs:
+                    job = dict(job)
+                    args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
+                    yield self.engine.synthesize(*args, **synth_kw, **job)[0]
+            results = serial()
+        for idx, wavs in zip(plan, results):
+            for i, w in zip(idx, wavs):
+                out[i] = self._finish(w)
+        return out
+
+
+class _Base(_BatchMixin):
     sr = S3GEN_SR
 
     ENC_COND_LEN, DEC_COND_LEN = 6 * S3_SR, 10 * S3GEN_SR
@@ -201,6 +310,18 @@ class _Base:
                                                **stream_kw, **samp):
             if r["wavs"][0].numel():
                 yield self._finish(r["wavs"][0])
+
+    def _analyse(self, wav_fpath, exaggeration):
+        return _prepare_conditionals(self.analyzer, wav_fpath, exaggeration, self.PROMPT_LEN, self.device)
+
+    def _generate_batch(self, B, tokenize, audio_prompt_paths, conds, exaggeration, drop_last_token, generator, **samp):
+        """Validation of every per-request argument, then tokenisation (`tokenize()` -> B id tensors), then the device work."""
+        samp = _sampling_lists(B, **samp)
+        exaggeration = _sampling_lists(B, exaggeration=exaggeration)["exaggeration"]
+        voices = self._voices_of_batch(B, audio_prompt_paths, conds, exaggeration)
+        sot, eot = 255, 0
+        tts = [torch.cat([torch.tensor([sot]), t.view(-1).long().cpu(), torch.tensor([eot])]) for t in tokenize()]
+        return self._run_batch(tts, voices, exaggeration, samp, generator, dict(max_new_tokens=1000, drop_last_token=drop_last_token), 1000)
 
     @classmethod
     def from_synthetic(cls, device="cuda", seed=0, t3_layers=30, **kw):
@@ -246,6 +367,18 @@ class ChatterboxTTS(_Base):
         toks = self.tokenizer.text_to_tokens(punc_norm_en(text))
         return self._generate(toks, drop_last_token=False, temperature=temperature, cfg_weight=cfg_weight,
                               repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+
+    def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
+                       min_p=0.05, top_p=1.0, generator=None):
+        """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
+        request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
+        neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
+        torch.Generator on the model's device makes the call repeatable (None: the global RNG).  More requests than the device batch run as sub-batches in order
+        of text length through the throughput schedule.  Never overwrites self.conds."""
+        texts = [texts] if isinstance(texts, str) else list(texts)
+        assert len(texts) >= 1, "empty batch"
+        return self._generate_batch(len(texts), lambda: [self.tokenizer.text_to_tokens(punc_norm_en(t)) for t in texts], audio_prompt_paths, conds, exaggeration,
+                                    False, generator, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                         cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True):
@@ -300,6 +433,19 @@ class ChatterboxMultilingualTTS(_Base):
         return self._generate(toks, drop_last_token=True, temperature=temperature, cfg_weight=cfg_weight,
                               repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
+    def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
+                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None):
+        """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does."""
+        texts = [texts] if isinstance(texts, str) else list(texts)
+        assert len(texts) >= 1, "empty batch"
+        langs = _per_request(language_ids, len(texts), "language_ids", (str,))
+        for k, lid in enumerate(langs):
+            if lid and lid.lower() not in SUPPORTED_LANGUAGES:
+                raise ValueError(f"Unsupported language_id '{lid}' (request {k}). Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
+        tok = lambda: [self.tokenizer.text_to_tokens(punc_norm(t), language_id=lid.lower() if lid else None) for t, lid in zip(texts, langs)]
+        return self._generate_batch(len(texts), tok, audio_prompt_paths, conds, exaggeration, True, generator, temperature=temperature, cfg_weight=cfg_weight,
+                                    repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True):
         """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
@@ -316,7 +462,7 @@ class ChatterboxMultilingualTTS(_Base):
                                      cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
 
-class ChatterboxTurboTTS:
+class ChatterboxTurboTTS(_BatchMixin):
     """Reference tts_turbo.py:111-320: GPT2-medium (Turbo) or GPT2-small (Nano) T3, meanflow S3Gen, GPT-2 BPE tokenizer."""
     sr = S3GEN_SR
     ENC_COND_LEN, DEC_COND_LEN = 15 * S3_SR, 10 * S3GEN_SR  # tts_turbo.py:112-113: the T3 prompt covers up to 15 s (375 tokens)
@@ -385,6 +531,26 @@ class ChatterboxTurboTTS:
             logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
         ids = self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids
         return self._generate(ids[0], temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
+
+    def _analyse(self, wav_fpath, exaggeration, norm_loudness=True):
+        return _prepare_conditionals(self.analyzer, wav_fpath, exaggeration, 375, self.device, min_seconds=5.0, norm_loudness=norm_loudness,
+                                     enc_cond_len=self.ENC_COND_LEN)
+
+    def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
+                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None):
+        """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
+        of B).  CFG, min_p and exaggeration are not supported by this backbone: ignored with generate()'s warning.  Sub-batches run one after the other."""
+        texts = [texts] if isinstance(texts, str) else list(texts)
+        B = len(texts)
+        assert B >= 1, "empty batch"
+        samp = _sampling_lists(B, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
+        ign = _sampling_lists(B, cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p)
+        if any(v > 0.0 for vals in ign.values() for v in vals):
+            import logging
+            logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
+        voices = self._voices_of_batch(B, audio_prompt_paths, conds, ign["exaggeration"], lambda p, ex: self._analyse(p, ex, norm_loudness=norm_loudness))
+        ids = [self.tokenizer(punc_norm_turbo(t), return_tensors="pt", padding=True, truncation=True).input_ids[0].view(-1).long().cpu() for t in texts]
+        return self._run_batch(ids, voices, ign["exaggeration"], samp, generator, dict(max_gen_len=1000), 1001)
 
     def _finish(self, wav):
         wav = wav.detach().float().cpu()
@@ -481,3 +647,50 @@ class ChatterboxVC:
         if self.watermarker is not None:
             wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
         return wav.unsqueeze(0)
+
+    MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
+
+    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None):
+        """generate() for B conversions in one call: `audios` (WAV paths or (waveform, sample_rate) pairs) or `s3_tokens` (B id sequences); target voice per
+        request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
+        self.ref_dict.  Returns B CPU float32 tensors (1, n_b) at `.sr` in the caller's order; more than MAX_BATCH requests run as sub-batches in order of length.
+        Never overwrites self.ref_dict."""
+        src = s3_tokens if s3_tokens is not None else audios
+        assert src is not None, "give audios or s3_tokens"
+        src = [src] if (isinstance(src, _PATH) or (torch.is_tensor(src) and src.dim() <= 1)) else list(src)
+        B = len(src)
+        assert B >= 1, "empty batch"
+        if target_voice_paths is not None and ref_dicts is not None:
+            raise ValueError("give target_voice_paths or ref_dicts, not both")
+        if target_voice_paths is not None:
+            from . import frontend as fe
+            self._need_analyzer()
+            done, refs = {}, []
+            for pth in _per_request(target_voice_paths, B, "target_voice_paths", _PATH):
+                key = os.fspath(pth) if isinstance(pth, _PATH) else id(pth)
+                if key not in done:
+                    w24 = fe.resample(pth[0], pth[1], S3GEN_SR) if isinstance(pth, (tuple, list)) else fe.load_wav(pth, S3GEN_SR)[0]
+                    done[key] = self.analyzer.embed_ref(w24[: self.DEC_COND_LEN], S3GEN_SR)
+                refs.append(done[key])
+        else:
+            refs = _per_request(ref_dicts, B, "ref_dicts", (dict,)) if ref_dicts is not None else [self.ref_dict] * B
+            assert all(r is not None for r in refs), "Please `prepare_conditionals` first or specify `target_voice_path`"
+        if s3_tokens is None:
+            from . import frontend as fe
+            self._need_analyzer()
+            toks = []
+            for a in src:
+                w16 = fe.resample(a[0], a[1], S3_SR) if isinstance(a, (tuple, list)) else fe.load_wav(a, S3_SR)[0]
+                toks.append(self.analyzer.tokenizer(torch.from_numpy(w16))[0])
+        else:
+            toks = src
+        toks = [torch.as_tensor(t).view(-1).long().cpu() for t in toks]
+        out = [None] * B
+        for idx in batch_plan([int(t.numel()) for t in toks], int(self.MAX_BATCH)):
+            wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)))
+            for i, w in zip(idx, wavs):
+                w = w.detach().float().cpu()
+                if self.watermarker is not None:
+                    w = torch.from_numpy(self.watermarker.apply_watermark(w.numpy(), sample_rate=self.sr))
+                out[i] = w.unsqueeze(0)
+        return out

@@ -157,6 +157,66 @@ __global__ void cfm_euler_kernel(float* xin, const float* __restrict__ v, int B,
     }
 }
 
+// ragged prefill-input assembly (cbx_prefill_embed): one workgroup per (row, block of 4 positions); a lane moves 16 B (one float4 of a position's `dim` floats)
+__global__ __launch_bounds__(256) void prefill_embed_kernel(cbx_prefill_embed_t d, int rows, int Sx, int nblk) {
+    const int r = blockIdx.x / nblk, sb = blockIdx.x - r * nblk;
+    const int b = r % d.B;
+    const int off = d.meta[4 * b], tl = d.meta[4 * b + 1], slot = d.meta[4 * b + 2], P = d.meta[4 * b + 3];
+    const float scale = (d.cfg && r >= d.B) ? 0.f : 1.f;  // the unconditional row of an utterance: text embeddings x 0 (t3.py:310-311)
+    const int c4n = d.dim >> 2;
+    const int s_end = Sx < sb * 4 + 4 ? Sx : sb * 4 + 4;
+    for (int s = sb * 4; s < s_end; ++s) {
+        const int p = d.pos0 + s;  // absolute prompt position
+        const long o = ((long)r * Sx + s) * d.dim;
+        const float *t1 = nullptr, *t2 = nullptr;
+        float sc = 1.f;
+        if (p < P) {
+            if (slot >= 0 && d.cond) t1 = d.cond + (long)slot * d.cond_stride + (long)p * d.dim;
+        } else if (p < P + tl) {
+            t1 = d.text_emb + (long)d.ids[off + p - P] * d.dim;
+            t2 = d.text_pos + (long)(d.abs_pos ? p : p - P) * d.dim;
+            sc = scale;
+        } else if (p < P + tl + d.n_bos) {
+            t1 = d.speech_emb + (long)d.bos_id * d.dim;
+            t2 = d.speech_pos + (long)(d.abs_pos ? p : 0) * d.dim;
+        }
+        for (int c4 = threadIdx.x; c4 < c4n; c4 += 256) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (t2) {  // the arithmetic of embed_kernel, in its order
+                v = *reinterpret_cast<const f32x4*>(t1 + c4 * 4) * sc;
+                v += *reinterpret_cast<const f32x4*>(t2 + c4 * 4);
+            } else if (t1) {
+                v = *reinterpret_cast<const f32x4*>(t1 + c4 * 4);
+            }
+            *reinterpret_cast<f32x4*>(d.x + o + c4 * 4) = v;
+        }
+        if (threadIdx.x == 0) {
+            d.positions[(long)r * Sx + s] = p;
+            d.cache_rows[(long)r * Sx + s] = r;
+        }
+    }
+    if (sb == 0 && threadIdx.x == 0) d.last[r] = (long long)r * Sx + (P + tl + d.n_bos) - d.pos0 - 1;
+}
+
+// cached conditioning prefixes into the KV cache by voice index (cbx_kv_prefix_paste_f32): one workgroup per (layer, row, head) x 1024 float4 of the P x 64 block
+__global__ __launch_bounds__(256) void kv_prefix_paste_kernel(const long long* __restrict__ table, int n_voices, float* __restrict__ kc, float* __restrict__ vc,
+                                                              int rows, int n_heads, int P, long ls, long rs, long hs) {
+    const int h = blockIdx.x % n_heads, r = (blockIdx.x / n_heads) % rows, l = blockIdx.x / (n_heads * rows);
+    const int voice = (int)table[2 * n_voices + r];
+    const float* sk = reinterpret_cast<const float*>(table[voice]);
+    const float* sv = reinterpret_cast<const float*>(table[n_voices + voice]);
+    const long so = ((long)l * n_heads + h) * P * 64, dof = (long)l * ls + (long)r * rs + (long)h * hs;
+    const int n4 = P * 16;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = (blockIdx.y * 4 + j) * 256 + threadIdx.x;
+        if (i < n4) {
+            *reinterpret_cast<f32x4*>(kc + dof + (long)i * 4) = *reinterpret_cast<const f32x4*>(sk + so + (long)i * 4);
+            *reinterpret_cast<f32x4*>(vc + dof + (long)i * 4) = *reinterpret_cast<const f32x4*>(sv + so + (long)i * 4);
+        }
+    }
+}
+
 }  // namespace
 CBX_TRC_SETTER(cbx_trace_set_elementwise)
 
@@ -202,4 +262,28 @@ extern "C" int cbx_cfm_euler_f32(float* xin, const float* v, int B, long T, int 
     hipLaunchKernelGGL(cfm_euler_kernel, dim3(grid_for((long)B * T * C)), dim3(256), 0, (hipStream_t)stream, xin, v, B, T, C,
                        ld_x, ld_v, xs_b, vs_b, dt, w, cfg);
     return cbx_check_launch("cfm_euler");
+}
+
+extern "C" int cbx_prefill_embed(const cbx_prefill_embed_t* d, void* stream) {
+    CBX_REQUIRE(d, "prefill_embed: null descriptor");
+    CBX_REQUIRE(d->meta && d->ids && d->text_emb && d->text_pos && d->speech_emb && d->speech_pos && d->x && d->positions && d->cache_rows && d->last,
+                "prefill_embed: null descriptor field");
+    CBX_REQUIRE(d->B >= 1 && (d->cfg == 0 || d->cfg == 1) && d->n_bos >= 0 && d->pos0 >= 0 && d->S > d->pos0 && d->dim > 0 && d->dim % 4 == 0 && d->bos_id >= 0 &&
+                    (!d->cond || d->cond_stride % 4 == 0),
+                "prefill_embed: bad geometry B=%d cfg=%d n_bos=%d S=%d pos0=%d dim=%d", d->B, d->cfg, d->n_bos, d->S, d->pos0, d->dim);
+    const int rows = d->B * (1 + d->cfg), Sx = d->S - d->pos0, nblk = (Sx + 3) / 4;
+    CBX_REQUIRE((long)rows * nblk < (1L << 31), "prefill_embed: grid too large");
+    hipLaunchKernelGGL(prefill_embed_kernel, dim3((unsigned)(rows * nblk)), dim3(256), 0, (hipStream_t)stream, *d, rows, Sx, nblk);
+    return cbx_check_launch("prefill_embed");
+}
+
+extern "C" int cbx_kv_prefix_paste_f32(const long long* table, int n_voices, float* kc, float* vc, int n_layers, int rows, int n_heads, int P,
+                                       long kv_layer_stride, long kv_row_stride, long kv_head_stride, void* stream) {
+    CBX_REQUIRE(table && kc && vc, "kv_prefix_paste: null");
+    CBX_REQUIRE(n_voices >= 1 && n_layers >= 1 && rows >= 1 && n_heads >= 1 && P >= 1 && (long)P * 64 <= kv_head_stride && kv_layer_stride % 4 == 0 &&
+                    kv_row_stride % 4 == 0 && kv_head_stride % 4 == 0 && (long)n_layers * rows * n_heads < (1L << 31),
+                "kv_prefix_paste: bad geometry voices=%d layers=%d rows=%d heads=%d P=%d", n_voices, n_layers, rows, n_heads, P);
+    hipLaunchKernelGGL(kv_prefix_paste_kernel, dim3((unsigned)(n_layers * rows * n_heads), (unsigned)((P * 16 + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream,
+                       table, n_voices, kc, vc, rows, n_heads, P, kv_layer_stride, kv_row_stride, kv_head_stride);
+    return cbx_check_launch("kv_prefix_paste");
 }

@@ -82,10 +82,12 @@ class ChatterboxEngine:
 
     @ops.on_device
     @torch.inference_mode()
-    def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None):
+    def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
+               generator=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
-        stream is free for the next batch's encoder + CFM; the returned waveforms belong to it."""
+        stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
+        that is not injected (None: the global RNG)."""
         B = len(speech_tokens)
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
@@ -100,7 +102,7 @@ class ChatterboxEngine:
 
         def run():
             t0 = time.perf_counter()
-            mel = self.flow.inference(tok.to(self.dev), lens.to(self.dev), gen_ref, z=z, n_steps=n_cfm_timesteps)
+            mel = self.flow.inference(tok.to(self.dev), lens.to(self.dev), gen_ref, z=z, n_steps=n_cfm_timesteps, generator=generator)
             if sync:  # per-stage wall times; the pipelined mode never blocks the host between stages
                 torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -114,9 +116,9 @@ class ChatterboxEngine:
                     mel.record_stream(hift_stream)
                     if mel_lens is not None:
                         mel_lens.record_stream(hift_stream)
-                    wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True)
+                    wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator)
             else:
-                wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True)
+                wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator)
             if sync:
                 torch.cuda.synchronize()
             t2 = time.perf_counter()
@@ -134,19 +136,20 @@ class ChatterboxEngine:
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True):
-        """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list)."""
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None):
+        """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
+        temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected."""
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
                    min_p=min_p, repetition_penalty=repetition_penalty, cfg_weight=cfg_weight, uniforms=uniforms,
-                   ban_eos=ban_eos, ban_from=ban_from)
+                   ban_eos=ban_eos, ban_from=ban_from, generator=generator)
         torch.cuda.synchronize()
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         st = [drop_invalid_tokens(t) for t in toks]
         st = [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
-                              drop_last_token=drop_last_token)
+                              drop_last_token=drop_last_token, generator=generator)
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
@@ -169,7 +172,9 @@ class ChatterboxEngine:
     def synthesize_pipelined(self, jobs, co_resident=True, host_threads=True, t3_in_flight=2, stream_priorities=(-1, 0), **kw):
         """Throughput mode for a stream of batches: T3 of batch k+1 runs on a high-priority HIP stream WHILE the flow
         matching + vocoder of batch k run on a second stream.  jobs: list of dicts(text_tokens=[...], t3_conds=..., gen_ref=...); yields
-        (wavs, tokens, latency_s) per job in order.  Results are identical to synthesize() called per job.
+        (wavs, tokens, latency_s) per job in order.  Results are identical to synthesize() called per job.  A job may carry sampling parameters of its own
+        (temperature, top_p, min_p, repetition_penalty, cfg_weight: scalar or one per utterance; they override **kw for that job) and a `generator` for the flow / vocoder noise that is not injected (the
+        sampling draws of a repeatable job are injected as `uniforms`: T3 is enqueued by another host thread).
 
         What makes the two stages actually overlap (round 5, profiles/r05_overlap_*; none of it changes a result):
           * co_resident: a chain of small dependent kernels keeps its pace beside chip-filling kernels of another stream only if its workgroups FIT
@@ -185,6 +190,7 @@ class ChatterboxEngine:
         self._pipeline_streams(stream_priorities)
         t3_kw = {k: kw[k] for k in ("max_new_tokens", "temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight", "ban_eos",
                                     "ban_from") if k in kw}
+        job_kw = lambda job: dict(t3_kw, **{k: job[k] for k in ("temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight") if k in job})
         self.co_resident(bool(co_resident))
         # ... and the flow + vocoder stream carries the co-resident ATTRIBUTE: its LayerNorm / split-GEMM launches (encoder, vocoder) keep to one or two
         # workgroups per CU as well (cbx_set_stream_coresident; no effect on results)
@@ -199,14 +205,14 @@ class ChatterboxEngine:
             try:
                 torch.cuda.set_device(self.dev)
                 with torch.inference_mode(), torch.cuda.stream(self._s_t3):
-                    box["handle"] = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), **t3_kw)
+                    box["handle"] = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), **job_kw(job))
             except BaseException as e:  # re-raised by the consumer thread
                 box["error"] = e
 
         def voc_of(job, st):
             with torch.cuda.stream(self._s_voc):
                 def voc():
-                    wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"),
+                    wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"),
                                           n_cfm_timesteps=kw.get("n_cfm_timesteps", 10),
                                           drop_last_token=kw.get("drop_last_token", True), sync=False)
                     return [w.cpu() for w in wavs]  # D2H on the vocoder stream: returns when this batch's audio is on the host
@@ -259,7 +265,7 @@ class ChatterboxEngine:
                         return
                     t_start = time.perf_counter()
                     with torch.inference_mode(), torch.cuda.stream(self._s_t3x[k % n_t3]):
-                        h = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), slot=k % n_slots, **t3_kw)
+                        h = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), slot=k % n_slots, **job_kw(job))
                         ev = torch.cuda.Event()
                         ev.record()
                     q.put((h, ev, t_start))
@@ -276,7 +282,7 @@ class ChatterboxEngine:
         def start_voc(job, st, which):
             ops.select_range_flag(self.dev, which)
             with torch.cuda.stream(self._s_voc):
-                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), sync=False, **voc_kw)
+                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), sync=False, **voc_kw)
                 host = [torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True) for w in wavs]
                 ev = torch.cuda.Event()
                 ev.record()
@@ -292,7 +298,7 @@ class ChatterboxEngine:
                 self.flow.precision, self.hift.precision = (6 if p == 16 else p for p in saved)
                 try:
                     with torch.cuda.stream(self._s_voc):
-                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), sync=False, **voc_kw)
+                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), sync=False, **voc_kw)
                         host = [w.cpu() for w in wavs]
                 finally:
                     self.flow.precision, self.hift.precision = saved
@@ -541,15 +547,17 @@ class TurboEngine:
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None):
+        """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
+        for every draw that is not injected."""
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,
-                                repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from)
+                                repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator)
         torch.cuda.synchronize()
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
-        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False)
+        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator)
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 

@@ -217,15 +217,15 @@ class HiFTEngine:
 
     @ops.on_device
     @torch.inference_mode()
-    def inference(self, mel, phase=None, noise=None, lens=None, fade=True, cache_source=None):
+    def inference(self, mel, phase=None, noise=None, lens=None, fade=True, cache_source=None, generator=None):
         """HiFTGenerator.inference + S3Gen trim_fade.  mel (B,T,80) channel-last.  Returns (wav (B,480T), source (B,480T)).
         cache_source (B, L): the source of an earlier chunk replaces the first L samples (hifigan.py:470-472)."""
         B, T, _ = mel.shape
         if phase is None:
-            phase = (torch.rand(B, 9, device=self.dev) * 2 - 1) * 3.141592653589793
+            phase = (torch.rand(B, 9, device=self.dev, generator=generator) * 2 - 1) * 3.141592653589793
             phase[:, 0] = 0
         if noise is None:
-            noise = torch.randn(B, 9, 480 * T, device=self.dev)
+            noise = torch.randn(B, 9, 480 * T, device=self.dev, generator=generator)
         if self.c_seam and not ops.TIMER and mel.is_contiguous() and mel.dtype == torch.float32:
             s = self._f0_source_c(mel, phase.to(self.dev).float(), noise.to(self.dev).float(), lens)
         else:

@@ -9,7 +9,7 @@ import os
 import torch
 
 from ._lib import (ATTN_PART_REC, ATTN_PL_CORESIDENT, GEMV_DEEP, GEMV_PRE_EPI, GEMV_SHALLOW, PL_TILE_CORESIDENT, AttnPartsParams, DecodeAttnParams, GemmParams,
-                   GemmPlParams, GemvParams, GemvRowParams, SamplerParams, check, lib)
+                   GemmPlParams, GemvParams, GemvRowParams, PrefillEmbed, SamplerParams, check, lib)
 
 NONE, SILU, GELU_ERF, GELU_TANH, MISH, LRELU, ELU, TANH, SNAKE, ABS = range(10)
 
@@ -685,6 +685,65 @@ def embed(ids, table, out, table2=None, ids2=None, scale=1.0, out_packed=False):
     check(lib.cbx_embed_f32(_p(ids), _p(table), _p(table2), _p(ids2), _p(out), rows, C, out.stride(0), scale, 3 if out_packed else 1, _stream()),
           "cbx_embed_f32")
     return out
+
+
+def prefill_embed(text_tokens, *, text_emb, text_pos, speech_emb, speech_pos, bos_id, n_bos, cfg, abs_pos, cond_lens, cond=None, cond_slots=None, pos0=0):
+    """The prefill input of a ragged batch in ONE launch (cbx_prefill_embed): text_tokens a list of B 1-D id tensors; cond_lens[b] the conditioning positions
+    in front of utterance b's text; cond (slots, Pmax, D) conditioning embeddings with cond_slots[b] the slot of utterance b -- or None when those positions
+    are already in the KV cache (then pos0 = the common prefix length and x starts at the text).  Returns (x (rows, S - pos0, D), positions, cache_rows
+    (rows * (S - pos0),) int32, last (rows,) int64) with rows = B * (1 + cfg).  One host buffer {meta | ids} and one host-to-device copy per batch."""
+    B, dev, D = len(text_tokens), text_emb.device, text_emb.shape[1]
+    ids = torch.cat([t.detach().reshape(-1).to("cpu", torch.int32) for t in text_tokens]) if B else torch.zeros(0, dtype=torch.int32)
+    tl = [int(t.numel()) for t in text_tokens]
+    cond_lens = [int(c) for c in cond_lens]
+    slots = [-1] * B if cond is None else [int(c) for c in cond_slots]
+    assert B >= 1 and len(cond_lens) == B and len(slots) == B
+    assert not ids.numel() or (0 <= int(ids.min()) and int(ids.max()) < text_emb.shape[0]), "prefill_embed: a text id outside the embedding table"
+    S = max(c + n + n_bos for c, n in zip(cond_lens, tl))
+    if cond is None:
+        assert all(c == pos0 for c in cond_lens), "prefill_embed: without conditioning embeddings every row starts behind the same cached prefix"
+    else:
+        _f32(cond, "cond")
+        assert pos0 == 0 and cond.dim() == 3 and cond.shape[2] == D and cond.is_contiguous() and all(0 <= s_ < cond.shape[0] for s_ in slots) \
+            and max(cond_lens) <= cond.shape[1], "prefill_embed: conditioning slots / lengths outside `cond`"
+    assert (S <= min(text_pos.shape[0], speech_pos.shape[0])) if abs_pos else (max(tl) <= text_pos.shape[0]), "prefill_embed: position outside the position table"
+    assert 0 <= int(bos_id) < speech_emb.shape[0] and all(t.shape[1] == D and t.is_contiguous() for t in (text_emb, text_pos, speech_emb, speech_pos))
+    offs, o = [], 0
+    for n in tl:
+        offs.append(o)
+        o += n
+    meta = torch.tensor([v for b in range(B) for v in (offs[b], tl[b], slots[b], cond_lens[b])], dtype=torch.int32)
+    buf = torch.cat([meta, ids]).to(dev, non_blocking=True)
+    rows, Sx = B * (2 if cfg else 1), S - pos0
+    x = torch.empty(rows, Sx, D, device=dev)
+    positions = torch.empty(rows * Sx, dtype=torch.int32, device=dev)
+    cache_rows = torch.empty(rows * Sx, dtype=torch.int32, device=dev)
+    last = torch.empty(rows, dtype=torch.int64, device=dev)
+    d = PrefillEmbed()
+    d.B, d.cfg, d.n_bos, d.abs_pos, d.S, d.pos0, d.dim, d.bos_id = B, int(bool(cfg)), int(n_bos), int(bool(abs_pos)), S, int(pos0), D, int(bos_id)
+    d.meta, d.ids = buf.data_ptr(), buf.data_ptr() + 16 * B
+    d.cond, d.cond_stride = _p(cond), (0 if cond is None else cond.stride(0))
+    d.text_emb, d.text_pos, d.speech_emb, d.speech_pos = _p(_f32(text_emb, "text_emb")), _p(_f32(text_pos, "text_pos")), _p(_f32(speech_emb, "speech_emb")), _p(_f32(speech_pos, "speech_pos"))
+    d.x, d.positions, d.cache_rows, d.last = _p(x), _p(positions), _p(cache_rows), _p(last)
+    check(lib.cbx_prefill_embed(ctypes.byref(d), _stream()), "cbx_prefill_embed")
+    return x, positions, cache_rows, last
+
+
+def kv_prefix_paste(prefixes, voice_of_row, kc, vc):
+    """kc / vc[l, r, h, :P] = prefixes[voice_of_row[r]][0 / 1][l, h, :P] for every layer, row r < len(voice_of_row) and head in one launch
+    (cbx_kv_prefix_paste_f32).  prefixes: list of (k, v) pairs of contiguous (L, H, P, 64) tensors; kc / vc: KV caches (L, rows, H, max_ctx, 64)."""
+    L, R, H, ctx, hd = kc.shape
+    nv, rows = len(prefixes), len(voice_of_row)
+    P = prefixes[0][0].shape[2]
+    assert hd == 64 and vc.shape == kc.shape and kc.stride() == vc.stride() and kc.stride(3) == 64 and 1 <= rows <= R and 1 <= P <= ctx
+    assert all(0 <= int(v) < nv for v in voice_of_row), "kv_prefix_paste: voice index outside the prefix table"
+    for k, v in prefixes:
+        assert k.shape == (L, H, P, 64) and v.shape == (L, H, P, 64) and k.is_contiguous() and v.is_contiguous(), "kv_prefix_paste: prefix shape"
+        _f32(k, "prefix k"), _f32(v, "prefix v")
+    table = torch.tensor([k.data_ptr() for k, _ in prefixes] + [v.data_ptr() for _, v in prefixes] + [int(v) for v in voice_of_row],
+                         dtype=torch.int64).to(kc.device, non_blocking=True)
+    check(lib.cbx_kv_prefix_paste_f32(_p(table), nv, _p(_f32(kc, "kc")), _p(vc), L, rows, H, P, kc.stride(0), kc.stride(1), kc.stride(2), _stream()),
+          "cbx_kv_prefix_paste_f32")
 
 
 def rope_kv(qkv, positions, cos_t, sin_t, kc, vc, n_heads, cache_rows=None):

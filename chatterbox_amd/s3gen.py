@@ -573,11 +573,11 @@ class FlowEngine:
     # ------------------------------------------------------------------ flow.inference
     @ops.on_device
     @torch.inference_mode()
-    def inference(self, tokens, token_lens, ref, z=None, n_steps=10, hold_back=None):
+    def inference(self, tokens, token_lens, ref, z=None, n_steps=10, hold_back=None, generator=None):
         with ops.gemm_precision(self.precision):
-            return self._inference(tokens, token_lens, ref, z, n_steps, hold_back)
+            return self._inference(tokens, token_lens, ref, z, n_steps, hold_back, generator)
 
-    def _inference(self, tokens, token_lens, ref, z=None, n_steps=10, hold_back=None):
+    def _inference(self, tokens, token_lens, ref, z=None, n_steps=10, hold_back=None, generator=None):
         """tokens (B,N) int64 (right-padded), token_lens (B,), ref dict as produced by S3Gen.embed_ref -- or a LIST of B such dicts, one voice
         per utterance (the reference takes a ref_dict per call, s3gen.py:173-229; a device batch may mix voices: prompt tokens / prompt mels
         of different lengths are left-aligned per row) --, z optional injected noise (B, 2(P+N)max, 80) channel-last.  Returns mel
@@ -621,7 +621,7 @@ class FlowEngine:
             for b in range(B):
                 cond[b, : Pms[b]] = pfs[b]
         if z is None:
-            z = torch.randn(B, T, 80, device=dev)
+            z = torch.randn(B, T, 80, device=dev, generator=generator)
         mel_lens = (2 * lens).to(torch.int32)
         if hold_back is not None:  # chunked synthesis: the encoder's 3-token lookahead frames are masked out of the CFM like padding
             mel_lens = (mel_lens - torch.as_tensor(hold_back, dtype=torch.int32).to(dev)).contiguous()

@@ -36,6 +36,31 @@ def llama3_rope_tables(max_pos, head_dim=64, theta=500000.0, factor=8.0, low=1.0
     return emb.cos().contiguous(), emb.sin().contiguous()
 
 
+def per_utterance(value, B, name):
+    """A sampling parameter as B floats: a scalar serves every utterance, a sequence must hold exactly B values (ValueError before anything is launched)."""
+    if torch.is_tensor(value):
+        value = value.reshape(-1).tolist() if value.dim() else float(value)
+    if isinstance(value, (list, tuple)):
+        if len(value) != B:
+            raise ValueError(f"{name}: {len(value)} values for {B} utterances")
+        return [float(v) for v in value]
+    return [float(value)] * B
+
+
+def sampler_rows(B, cols):
+    """Host image (B, 8) of cbx_sampler_t.dev_params: `cols` = the eight columns {cfg_weight, temperature, min_p, top_p, rep_penalty, top_k, ban_token, ban_from},
+    each a scalar or a sequence of B."""
+    assert len(cols) == 8
+    per = [per_utterance(v, B, n) for n, v in cols]
+    return torch.tensor([[c[b] for c in per] for b in range(B)], dtype=torch.float32)
+
+
+def _slice_param(v, lo, hi):
+    if torch.is_tensor(v) and v.dim():
+        v = v.reshape(-1).tolist()
+    return v[lo:hi] if isinstance(v, (list, tuple)) else v
+
+
 class _LoopHandle:
     """Owns a cbx_t3_loop_t (or, with destroy="cbx_gpt2_loop_destroy", a cbx_gpt2_loop_t; destroyed with the state / geometry entry that holds it)."""
 
@@ -56,7 +81,9 @@ class VoicePrefixCache:
     1 + the prompt tokens).  The prompt of T3.inference / inference_turbo is [conditioning | text | BOS] under a causal mask (t3.py:303-335, 407-423): the conditioning
     positions see only themselves, so their K / V depend on the voice alone.  An entry keeps the conditioning tensors alive and is matched by identity + version
     counter (+ content for host tensors; a device tensor made under inference_mode has no counter: identity alone): a hit means the very tensors the prefix was
-    computed from.  No device-side compare: generate() must not synchronise (the throughput schedule enqueues ahead)."""
+    computed from.  No device-side compare: generate() must not synchronise (the throughput schedule enqueues ahead).
+    A batch may mix voices (a list of cond dicts): every DISTINCT voice has its own entry, cached ones are pasted by voice index in one launch
+    (ops.kv_prefix_paste), missing ones are prefilled once per voice -- never once per row."""
     _PREFIX_KEEP = 4
 
     @staticmethod
@@ -83,27 +110,56 @@ class VoicePrefixCache:
                 return ent
         return None
 
-    def _keep_voice_prefix(self, conds, st, P=34):
-        """After a full prefill: K / V of positions 0 .. P - 1 of cache row 0 (L, H, P, 64)."""
-        if not (self.share_prefix and isinstance(conds, dict)) or self._voice_prefix(conds) is not None:
-            return
+    def _keep_voice_prefix(self, conds, st, P=34, row=0, keep=0):
+        """After a prefill: K / V of positions 0 .. P - 1 of cache row `row` (L, H, P, 64).  keep: entries the current batch needs (never evicted by it)."""
+        if not (self.share_prefix and isinstance(conds, dict)):
+            return None
+        ent = self._voice_prefix(conds)
+        if ent is not None:
+            return ent
         items = [(k, v, self._tver(v) if torch.is_tensor(v) else None, v.clone() if torch.is_tensor(v) and v.device.type == "cpu" else None)
                  for k, v in sorted(conds.items())]
-        ent = dict(keys=sorted(conds), items=items, P=P, k=st["kc"][:, 0, :, :P].clone(), v=st["vc"][:, 0, :, :P].clone(), ev=None)
+        ent = dict(keys=sorted(conds), items=items, P=P, k=st["kc"][:, row, :, :P].clone(), v=st["vc"][:, row, :, :P].clone(), ev=None)
         if self.dev.type == "cuda":
             ent["ev"] = torch.cuda.Event()
             ent["ev"].record()
         self._prefix_cache.insert(0, ent)
-        del self._prefix_cache[self._PREFIX_KEEP:]
+        del self._prefix_cache[max(self._PREFIX_KEEP, keep):]
+        return ent
 
-    def _paste_voice_prefix(self, pre, st, rows):
-        """The cached prefix into rows 0 .. rows - 1 of the KV cache (the entry may have been written on another stream: two decode chains of the throughput schedule)."""
-        if pre["ev"] is not None:
+    @staticmethod
+    def _distinct_voices(conds, B):
+        """(voices, voice_of): the distinct cond dicts of a batch -- one dict, or a list of B in which the same dict (or dicts of the very same tensors / equal
+        scalars) may serve several utterances -- and each utterance's index into them.  Host-side identity only: no device compare, no synchronisation."""
+        if isinstance(conds, dict):
+            return [conds], [0] * B
+        assert len(conds) == B, f"{len(conds)} voices for {B} utterances"
+        keys, voices, voice_of = {}, [], []
+        for c in conds:
+            try:
+                key = tuple((k, ("t", id(v), VoicePrefixCache._tver(v)) if torch.is_tensor(v) else ("s", v)) for k, v in sorted(c.items()))
+                hash(key)
+            except TypeError:
+                key = ("d", id(c))
+            if key not in keys:
+                keys[key] = len(voices)
+                voices.append(c)
+            voice_of.append(keys[key])
+        return voices, voice_of
+
+    def _paste_voice_prefixes(self, ents, voice_of_row, st):
+        """The cached prefixes of a batch into rows 0 .. len(voice_of_row) - 1 of the KV cache in one launch (ops.kv_prefix_paste); entries may have been written on
+        another stream (two decode chains of the throughput schedule)."""
+        if self.dev.type == "cuda":
             cur = torch.cuda.current_stream()
-            cur.wait_event(pre["ev"])
-            pre["k"].record_stream(cur), pre["v"].record_stream(cur)
-        st["kc"][:, :rows, :, :pre["P"]].copy_(pre["k"][:, None])
-        st["vc"][:, :rows, :, :pre["P"]].copy_(pre["v"][:, None])
+            for e in ents:
+                if e["ev"] is not None:
+                    cur.wait_event(e["ev"])
+                    e["k"].record_stream(cur), e["v"].record_stream(cur)
+        ops.kv_prefix_paste([(e["k"], e["v"]) for e in ents], voice_of_row, st["kc"], st["vc"])
+        # a batch of more than _PREFIX_KEEP voices grew the cache for its own duration (74 MB per voice for Turbo): back to the cap; the pasted entries stay alive
+        # in `ents` until the caller returns, and their memory is reused in stream order
+        del self._prefix_cache[self._PREFIX_KEEP:]
 
 
 class T3Engine(VoicePrefixCache):
@@ -532,6 +588,19 @@ class T3Engine(VoicePrefixCache):
         ops.linear(ws["h"], lw["wgu"], ws["g"], swiglu=True)
         ops.linear(ws["g"], lw["wd"], x, residual=x)
 
+    def _prefill_rows(self, xf, S, rows, st, pos, crow, prec, pws=None):
+        """The full prefill of `rows` rows of S positions each (xf (rows * S, D) in / out): through cbx_t3_prefill, or launch by launch under a kernel timer."""
+        dev = self.dev
+        if pws is None:
+            pws = dict(h=torch.empty(rows * S, self.D, device=dev), qkv=torch.empty(rows * S, 3 * self.D, device=dev),
+                       att=torch.empty(rows * S, self.D, device=dev), g=torch.empty(rows * S, self.F, device=dev))
+        if self.c_step and not ops.TIMER:  # the same launches through the stage-level C entry point cbx_t3_prefill (one ctypes call instead of 9 per layer)
+            self._prefill_c(xf, pws, S, rows, st, pos, crow)
+        else:
+            with ops.gemm_precision(prec):
+                for i, lw in enumerate(self.layers):
+                    self._layer_prefill(lw, xf, pws, S, rows, st["kc"][i], st["vc"][i], pos, crow)
+
     def _prefill_c(self, xf, ws, S, rows, st, pos, crow):
         """The prefill through cbx_t3_prefill (include/cbx.h): the launches of _layer_prefill x n_layers, sequenced in C."""
         import ctypes
@@ -780,9 +849,11 @@ class T3Engine(VoicePrefixCache):
     @torch.inference_mode()
     def generate(self, conds, text_tokens, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                  repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16,
-                 return_prefill_logits=False, debug_logits=False, async_mode=False, slot=0, run_steps=None):
+                 return_prefill_logits=False, debug_logits=False, async_mode=False, slot=0, run_steps=None, generator=None):
         """conds: one T3 cond dict (shared voice) or a list of B; text_tokens: list of B 1-D LongTensors that already
         carry SOT/EOT (mtl_tts.py:319-322).  Returns a list of B 1-D LongTensors (EOS included if it was sampled).
+        temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar, or a sequence of B (one row of cbx_sampler_t.dev_params per utterance).
+        generator: a torch.Generator on the engine's device for the sampling draws (None: the global RNG).
         `slot` selects an independent set of workspaces / KV cache / decode graph (pipelined serving keeps two alive).
         Chunked use (streaming synthesis): `async_mode=True, run_steps=k` samples only the first k tokens and returns a handle;
         `advance(handle, n)` enqueues n more decode steps and `peek(handle)` fetches the tokens sampled so far."""
@@ -793,25 +864,29 @@ class T3Engine(VoicePrefixCache):
             assert uniforms.numel() % B == 0 and uniforms.numel() // B >= max_new_tokens, \
                 f"uniforms must hold at least max_new_tokens={max_new_tokens} draws per utterance"
             uniforms = uniforms.view(B, -1)
+        # {cfg_weight, temperature, min_p, top_p, rep_penalty, top_k, ban_token, ban_from} per utterance (cbx_sampler_t.dev_params); a wrong length raises here
+        samp = sampler_rows(B, (("cfg_weight", cfg_weight), ("temperature", temperature), ("min_p", min_p), ("top_p", top_p),
+                                ("repetition_penalty", repetition_penalty), ("top_k", 0.0), ("ban_token", float(STOP_SPEECH if ban_eos else -1)),
+                                ("ban_from", float(ban_from))))
         if B > self.MAX_BATCH:  # rows = 2B feeds the decode GEMV (M <= 64): larger batches run as consecutive sub-batches
             assert not (async_mode or debug_logits or return_prefill_logits), "sub-batching is only defined for the plain token path"
             out = []
             for lo in range(0, B, self.MAX_BATCH):
                 hi = min(B, lo + self.MAX_BATCH)
                 out += self.generate(conds if isinstance(conds, dict) else conds[lo:hi], text_tokens[lo:hi], max_new_tokens=max_new_tokens,
-                                     temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                                     cfg_weight=cfg_weight, uniforms=None if uniforms is None else uniforms[lo:hi], ban_eos=ban_eos,
-                                     ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, slot=slot)
+                                     temperature=_slice_param(temperature, lo, hi), top_p=_slice_param(top_p, lo, hi), min_p=_slice_param(min_p, lo, hi),
+                                     repetition_penalty=_slice_param(repetition_penalty, lo, hi), cfg_weight=_slice_param(cfg_weight, lo, hi),
+                                     uniforms=None if uniforms is None else uniforms[lo:hi], ban_eos=ban_eos,
+                                     ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, slot=slot, generator=generator)
             return out
         rows = 2 * B
         prec = self.tune.get("prefill_prec") or 0
-        pre = self._voice_prefix(conds) if prec in (0, 1) else None  # the cached conditioning prefix of this voice: prefill the text positions only
-        if pre is not None:
-            ce = None
-        elif isinstance(conds, dict):
-            ce = [self.cond_embeds(conds)] * B
-        else:
-            ce = [self.cond_embeds(c) for c in conds]
+        # the conditioning prefix of every voice of the batch (VoicePrefixCache): cached -> pasted; a batch of ONE voice that misses runs the full prefill and keeps
+        # that voice's K / V; a batch that MIXES voices computes the missing prefixes once per distinct voice (a prefix-only prefill), then every row prefills its
+        # text positions only
+        voices, voice_of = self._distinct_voices(conds, B)
+        share = bool(self.share_prefix) and prec in (0, 1)
+        ents = [self._voice_prefix(v) for v in voices] if share else [None] * len(voices)
         tl = [int(t.numel()) for t in text_tokens]
         s0 = [34 + n + 2 for n in tl]
         S = max(s0)
@@ -820,52 +895,49 @@ class T3Engine(VoicePrefixCache):
         st = self._get_state(B, max_ctx, max_new_tokens, slot)
         self._prepare_tune()
         # {cfg_weight, temperature, min_p, top_p, rep_penalty, top_k, ban_token, ban_from} per utterance (cbx_sampler_t.dev_params)
-        st["samp_dev"].copy_(torch.tensor([float(cfg_weight), float(temperature), float(min_p), float(top_p), float(repetition_penalty), 0.0,
-                                           float(STOP_SPEECH if ban_eos else -1), float(ban_from)]).repeat(B, 1), non_blocking=True)
+        st["samp_dev"].copy_(samp, non_blocking=True)
         for k in ("seen", "step", "done", "n_generated", "out_tokens"):
             st[k].zero_()
         st["seen"][:, START_SPEECH] = 1
         if uniforms is None:
-            st["uniforms"].uniform_()
+            st["uniforms"].uniform_(generator=generator)
         else:
             st["uniforms"].copy_(torch.as_tensor(uniforms, dtype=torch.float32).view(B, -1)[:, :max_new_tokens])
 
-        # ---- prefill embeddings (prepare_input_embeds + second BOS, t3.py:102-130,305-313)
+        # ---- the missing prefixes of a mixed-voice batch: [conditioning] alone through the layers, once per distinct voice, into cache rows 0 .. n - 1
+        missing = [j for j, e in enumerate(ents) if e is None]
+        if share and missing and len(voices) > 1:
+            xc = torch.stack([self.cond_embeds(voices[j]) for j in missing]).view(len(missing) * 34, self.D)
+            self._prefill_rows(xc, 34, len(missing), st, torch.arange(34, dtype=torch.int32, device=dev).repeat(len(missing)),
+                               torch.arange(len(missing), dtype=torch.int32, device=dev).repeat_interleave(34), prec)
+            for i, j in enumerate(missing):
+                ents[j] = self._keep_voice_prefix(voices[j], st, row=i, keep=len(voices))
+            missing = []
+        pre = None if missing else ents  # every voice cached: prefill the text positions only
+        if pre is None:
+            ce = torch.stack([self.cond_embeds(v) for v in voices])
+
+        # ---- prefill embeddings (prepare_input_embeds + second BOS, t3.py:102-130,305-313): one launch for the batch (cbx_prefill_embed)
         P0 = 34 if pre is not None else 0  # prompt positions that are NOT computed in this call
         Sx = S - P0
-        x = torch.zeros(rows, Sx, self.D, device=dev)
-        bos = torch.full((2,), START_SPEECH, dtype=torch.int64, device=dev)
-        zero2 = torch.zeros(2, dtype=torch.int32, device=dev)
-        for b in range(B):
-            ids = text_tokens[b].to(dev).long().view(-1)
-            pos = torch.arange(tl[b], dtype=torch.int32, device=dev)
-            for r, scale in ((b, 1.0), (B + b, 0.0)):
-                if pre is None:
-                    x[r, :34] = ce[b]
-                ops.embed(ids, self.text_emb, x[r, 34 - P0:34 - P0 + tl[b]], table2=self.text_pos, ids2=pos, scale=scale)
-                ops.embed(bos, self.speech_emb, x[r, 34 - P0 + tl[b]:s0[b] - P0], table2=self.speech_pos, ids2=zero2)
+        x, pos, crow, last = ops.prefill_embed(text_tokens, text_emb=self.text_emb, text_pos=self.text_pos, speech_emb=self.speech_emb, speech_pos=self.speech_pos,
+                                               bos_id=START_SPEECH, n_bos=2, cfg=True, abs_pos=False, cond_lens=[34] * B,
+                                               cond=None if pre is not None else ce, cond_slots=voice_of, pos0=P0)
         xf = x.view(rows * Sx, self.D)
         pws = dict(h=torch.empty(rows * Sx, self.D, device=dev), qkv=torch.empty(rows * Sx, 3 * self.D, device=dev),
                    att=torch.empty(rows * Sx, self.D, device=dev), g=torch.empty(rows * Sx, self.F, device=dev))
-        pos = torch.arange(P0, S, dtype=torch.int32, device=dev).repeat(rows)
-        crow = torch.arange(rows, dtype=torch.int32, device=dev).repeat_interleave(Sx)
         # prefill_prec (tune / CBX_T3_TUNE="prefill_prec=6", opt-in, untimed): the prefill's plain projections (q/k/v, o, down) and its attention
         # on the bf16x6 split kernels (24 significand bits, fp32 range, accumulation error below the exact MFMA's own: DESIGN.md section 1)
         # instead of the exact fp32 MFMA; gate|up (SwiGLU epilogue) and every decode step stay exact
         if pre is not None:
-            self._paste_voice_prefix(pre, st, rows)
+            self._paste_voice_prefixes(pre, voice_of + voice_of, st)
             with ops.gemm_precision(prec):
                 for i, lw in enumerate(self.layers):
                     self._layer_prefill_text(lw, xf, pws, Sx, S, rows, st["kc"][i], st["vc"][i], pos, crow)
-        elif self.c_step and not ops.TIMER:  # the same launches through the stage-level C entry point cbx_t3_prefill (one ctypes call instead of 9 per layer)
-            self._prefill_c(xf, pws, S, rows, st, pos, crow)
         else:
-            with ops.gemm_precision(prec):
-                for i, lw in enumerate(self.layers):
-                    self._layer_prefill(lw, xf, pws, S, rows, st["kc"][i], st["vc"][i], pos, crow)
-        if pre is None and prec in (0, 1):
-            self._keep_voice_prefix(conds, st)
-        last = torch.tensor([r * Sx + s0[r % B] - P0 - 1 for r in range(rows)], device=dev)
+            self._prefill_rows(xf, S, rows, st, pos, crow, prec, pws)
+        if pre is None and share and len(voices) == 1:
+            self._keep_voice_prefix(voices[0], st)
         hl = xf.index_select(0, last).contiguous()
         ops.layernorm(hl, self.norm, None, st["dws"]["h"], 1e-5, rms=True)
         ops.linear(st["dws"]["h"], self.head, st["logits"])

@@ -10,7 +10,7 @@ import os
 import torch
 
 from . import ops
-from .t3 import VoicePrefixCache
+from .t3 import VoicePrefixCache, _slice_param, sampler_rows
 
 START_SPEECH, STOP_SPEECH = 6561, 6562
 
@@ -395,19 +395,48 @@ class T3TurboEngine(VoicePrefixCache):
         d.kv_layer_stride, d.kv_row_stride, d.kv_head_stride = st["kc"].stride(0), st["kc"].stride(1), st["kc"].stride(2)
         check(lib.cbx_gpt2_prefill(ctypes.byref(d), ops._stream()), "cbx_gpt2_prefill")
 
+    def _prefill_rows(self, xf, posr, crow, st, B, Sx, P0, exact, S=None):
+        """The GPT-2 layers over xf (B * Sx, D) in / out, K / V appended at posr[] of cache row crow[]; P0 > 0: keys / values [cached prefix | the Sx positions] are
+        read from the KV cache.  Through cbx_gpt2_prefill, or launch by launch (split-precision scope, kernel timer)."""
+        dev, D = self.dev, self.D
+        S = P0 + Sx if S is None else S
+        h, qkv, att, g = (torch.empty(B * Sx, n, device=dev) for n in (D, 3 * D, D, 4 * D))
+        if self.c_prefill and exact and not ops.TIMER:
+            return self._prefill_c(xf, h, qkv, att, g, posr, crow, st, B, Sx, P0)
+        for i, lw in enumerate(self.layers):
+            ops.layernorm(xf, lw["ln1"][0], lw["ln1"][1], h, 1e-5)
+            ops.linear(h, lw["wqkv"], qkv, bias=lw["bqkv"])
+            ops.rope_kv(qkv, posr, None, None, st["kc"][i], st["vc"][i], self.H, cache_rows=crow)
+            q4 = qkv.view(B, Sx, 3, self.H, 64)
+            if not P0:
+                ops.flash_attn(q4[:, :, 0], q4[:, :, 1], q4[:, :, 2], att.view(B, Sx, self.H, 64), 0.125, causal=True)
+            else:  # keys / values [cached prefix | text] where the cache keeps them (cbx_flash_attn_kv_f32)
+                ops.flash_attn(q4[:, :, 0], st["kc"][i][:B, :, :S].permute(0, 2, 1, 3), st["vc"][i][:B, :, :S].permute(0, 2, 1, 3),
+                               att.view(B, Sx, self.H, 64), 0.125, causal=True)
+            ops.linear(att, lw["wo"], xf, bias=lw["bo"], residual=xf)
+            ops.layernorm(xf, lw["ln2"][0], lw["ln2"][1], h, 1e-5)
+            ops.linear(h, lw["wfc"], g, bias=lw["bfc"], act=ops.GELU_TANH)
+            ops.linear(g, lw["wpr"], xf, bias=lw["bpr"], residual=xf)
+
     @ops.on_device
     @torch.inference_mode()
     def generate(self, conds, text_tokens, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95, repetition_penalty=1.2,
-                 uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16, debug_logits=False, async_mode=False, run_steps=None):
+                 uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16, debug_logits=False, async_mode=False, run_steps=None,
+                 generator=None):
         """conds: one cond dict (speaker_emb (1,256), cond_prompt_speech_tokens (1,375)) or a list of B; text_tokens: list of B
         1-D LongTensors (GPT-2 BPE ids, no SOT/EOT).  Returns a list of B 1-D LongTensors without the trailing EOS.
+        temperature, top_k, top_p, repetition_penalty: a scalar, or a sequence of B (one row of cbx_sampler_t.dev_params per utterance).
+        generator: a torch.Generator on the engine's device for the sampling draws (None: the global RNG).
         Chunked use (streaming synthesis, the protocol of T3Engine.generate): `async_mode=True, run_steps=k` samples only the first k of the
         max_gen_len + 1 tokens and returns a handle without synchronising; `advance(handle, n)` enqueues n more token steps (cbx_gpt2_loop_run),
         `peek(handle)` fetches the tokens sampled so far, `collect(handle)` the result of the call."""
         dev, B, D = self.dev, len(text_tokens), self.D
-        voice = conds if isinstance(conds, dict) else None  # one voice for the whole batch: its conditioning prefix may be cached
+        voices, voice_of = self._distinct_voices(conds, B)  # the conditioning prefix of every distinct voice may be cached
         conds = [conds] * B if isinstance(conds, dict) else conds
         assert B >= 1, "empty batch"
+        # sampling parameters live in device memory (cbx_sampler_t.dev_params), one row per utterance; a wrong length raises here
+        samp = sampler_rows(B, (("cfg_weight", 0.0), ("temperature", temperature), ("min_p", 0.0), ("top_p", top_p), ("repetition_penalty", repetition_penalty),
+                                ("top_k", top_k), ("ban_token", float(STOP_SPEECH if ban_eos else -1)), ("ban_from", float(ban_from))))
         if uniforms is not None:
             uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
             assert uniforms.numel() % B == 0 and uniforms.numel() // B >= max_gen_len + 1, \
@@ -418,9 +447,10 @@ class T3TurboEngine(VoicePrefixCache):
             out = []
             for lo in range(0, B, self.MAX_BATCH):
                 hi = min(B, lo + self.MAX_BATCH)
-                out += self.generate(conds[lo:hi], text_tokens[lo:hi], max_gen_len=max_gen_len, temperature=temperature, top_k=top_k,
-                                     top_p=top_p, repetition_penalty=repetition_penalty, uniforms=None if uniforms is None else uniforms[lo:hi],
-                                     ban_eos=ban_eos, ban_from=ban_from, use_graph=use_graph, poll_every=poll_every)
+                out += self.generate(conds[lo:hi], text_tokens[lo:hi], max_gen_len=max_gen_len, temperature=_slice_param(temperature, lo, hi),
+                                     top_k=_slice_param(top_k, lo, hi), top_p=_slice_param(top_p, lo, hi),
+                                     repetition_penalty=_slice_param(repetition_penalty, lo, hi), uniforms=None if uniforms is None else uniforms[lo:hi],
+                                     ban_eos=ban_eos, ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, generator=generator)
             return out
         n_prompt = [int(c["cond_prompt_speech_tokens"].numel()) for c in conds]
         tl = [int(t.numel()) for t in text_tokens]
@@ -432,68 +462,61 @@ class T3TurboEngine(VoicePrefixCache):
         st = self._get_state(B, max_ctx, n_samples)
         if self.decode_mode == "v2":
             self._prepare_tune()
-        # sampling parameters live in device memory (cbx_sampler_t.dev_params): no graph re-capture when a request changes them
-        st["samp_dev"].copy_(torch.tensor([0.0, float(temperature), 0.0, float(top_p), float(repetition_penalty), float(top_k),
-                                           float(STOP_SPEECH if ban_eos else -1), float(ban_from)]).repeat(B, 1), non_blocking=True)
+        st["samp_dev"].copy_(samp, non_blocking=True)  # (no graph re-capture when a request changes them)
         for k in ("seen", "step", "done", "n_generated", "out_tokens"):
             st[k].zero_()
         st["seen"][:, START_SPEECH] = 1  # the first processor call sees ids = [start token] (t3.py:428)
         if uniforms is None:
-            st["uniforms"].uniform_()
+            st["uniforms"].uniform_(generator=generator)
         else:
             st["uniforms"].copy_(torch.as_tensor(uniforms, dtype=torch.float32).view(B, -1)[:, :n_samples])
 
         # ---- prefill: [speaker | prompt-token embeddings | text | start-speech] + wpe (prepare_input_embeds, t3.py:102-130,407-423)
         # The 1 + n_prompt conditioning positions see only themselves (causal) and carry absolute positions: with their K / V cached (VoicePrefixCache) only the
         # text positions and the start token are computed -- 65 of 441 positions at 64 text tokens -- against keys read from the KV cache.
+        # A batch of ONE voice that misses runs the full prefill and keeps that voice's K / V; a batch that MIXES voices computes the missing prefixes once per
+        # distinct voice (a prefix-only prefill), then every row prefills its text positions only.  Voices whose prompts differ in length share no common
+        # prefix length: such a batch runs the full prefill.
         exact = ops._prec() not in (3, 6, 16)
-        pre = self._voice_prefix(voice) if voice is not None and exact else None
-        if pre is not None and pre["P"] != 1 + n_prompt[0]:
-            pre = None
-        P0 = pre["P"] if pre is not None else 0
+        vP = [1 + int(v["cond_prompt_speech_tokens"].numel()) for v in voices]
+        share = bool(self.share_prefix) and exact and len(set(vP)) == 1
+        ents = [self._voice_prefix(v) for v in voices] if share else [None] * len(voices)
+        ents = [e if e is not None and e["P"] == vP[0] else None for e in ents]
+        missing = [j for j, e in enumerate(ents) if e is None]
+
+        def cond_rows(idx):
+            """[speaker projection + wpe[0] | prompt-token embeddings + wpe] of voices[idx]: (len(idx), Pmax, D), zero behind a shorter prompt"""
+            out = torch.zeros(len(idx), max(vP[j] for j in idx), D, device=dev)
+            for i, j in enumerate(idx):
+                ops.linear(voices[j]["speaker_emb"].to(dev).float().view(1, 256), self.spkr_w, out[i, 0:1], bias=self.spkr_b)
+                ops.axpby(self.wpe[0:1], out[i, 0:1], 1.0, 1.0)
+                ops.embed(voices[j]["cond_prompt_speech_tokens"].to(dev).long().view(-1), self.speech_emb, out[i, 1:vP[j]], table2=self.wpe,
+                          ids2=torch.arange(1, vP[j], dtype=torch.int32, device=dev))
+            return out
+
+        if share and missing and len(voices) > 1:
+            n, P = len(missing), vP[0]
+            self._prefill_rows(cond_rows(missing).view(n * P, D), torch.arange(P, dtype=torch.int32, device=dev).repeat(n),
+                               torch.arange(n, dtype=torch.int32, device=dev).repeat_interleave(P), st, n, P, 0, exact)
+            for i, j in enumerate(missing):
+                ents[j] = self._keep_voice_prefix(voices[j], st, P=P, row=i, keep=len(voices))
+            missing = []
+        pre = None if (missing or not share) else ents
+        P0 = vP[0] if pre is not None else 0
         Sx = S - P0
-        x = torch.zeros(B, Sx, D, device=dev)
-        for b in range(B):
-            pos = torch.arange(s0[b], dtype=torch.int32, device=dev)
-            if pre is None:
-                ops.linear(conds[b]["speaker_emb"].to(dev).float().view(1, 256), self.spkr_w, x[b, 0:1], bias=self.spkr_b)
-                ops.axpby(self.wpe[0:1], x[b, 0:1], 1.0, 1.0)
-                a, e = 1, 1 + n_prompt[b]
-                ops.embed(conds[b]["cond_prompt_speech_tokens"].to(dev).long().view(-1), self.speech_emb, x[b, a:e], table2=self.wpe, ids2=pos[a:e])
-            a, e = 1 + n_prompt[b], 1 + n_prompt[b] + tl[b]
-            ops.embed(text_tokens[b].to(dev).long().view(-1), self.text_emb, x[b, a - P0:e - P0], table2=self.wpe, ids2=pos[a:e])
-            ops.embed(torch.full((1,), START_SPEECH, dtype=torch.int64, device=dev), self.speech_emb, x[b, e - P0:e - P0 + 1], table2=self.wpe, ids2=pos[e:e + 1])
-        M = B * Sx
-        xf = x.view(M, D)
-        h, qkv, att, g = (torch.empty(M, n, device=dev) for n in (D, 3 * D, D, 4 * D))
-        posr = torch.arange(P0, S, dtype=torch.int32, device=dev).repeat(B)
-        crow = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(Sx)
+        x, posr, crow, last = ops.prefill_embed(text_tokens, text_emb=self.text_emb, text_pos=self.wpe, speech_emb=self.speech_emb, speech_pos=self.wpe,
+                                                bos_id=START_SPEECH, n_bos=1, cfg=False, abs_pos=True, cond_lens=[vP[j] for j in voice_of],
+                                                cond=None if pre is not None else cond_rows(list(range(len(voices)))), cond_slots=voice_of, pos0=P0)
+        xf = x.view(B * Sx, D)
         if pre is not None:
-            self._paste_voice_prefix(pre, st, B)
-        if self.c_prefill and exact and not ops.TIMER:
-            self._prefill_c(xf, h, qkv, att, g, posr, crow, st, B, Sx, P0)
-        else:
-            for i, lw in enumerate(self.layers):
-                ops.layernorm(xf, lw["ln1"][0], lw["ln1"][1], h, 1e-5)
-                ops.linear(h, lw["wqkv"], qkv, bias=lw["bqkv"])
-                ops.rope_kv(qkv, posr, None, None, st["kc"][i], st["vc"][i], self.H, cache_rows=crow)
-                q4 = qkv.view(B, Sx, 3, self.H, 64)
-                if pre is None:
-                    ops.flash_attn(q4[:, :, 0], q4[:, :, 1], q4[:, :, 2], att.view(B, Sx, self.H, 64), 0.125, causal=True)
-                else:  # keys / values [cached prefix | text] where the cache keeps them (cbx_flash_attn_kv_f32)
-                    ops.flash_attn(q4[:, :, 0], st["kc"][i][:B, :, :S].permute(0, 2, 1, 3), st["vc"][i][:B, :, :S].permute(0, 2, 1, 3),
-                                   att.view(B, Sx, self.H, 64), 0.125, causal=True)
-                ops.linear(att, lw["wo"], xf, bias=lw["bo"], residual=xf)
-                ops.layernorm(xf, lw["ln2"][0], lw["ln2"][1], h, 1e-5)
-                ops.linear(h, lw["wfc"], g, bias=lw["bfc"], act=ops.GELU_TANH)
-                ops.linear(g, lw["wpr"], xf, bias=lw["bpr"], residual=xf)
-        if pre is None and voice is not None and exact:
-            self._keep_voice_prefix(voice, st, P=1 + n_prompt[0])
-        last = torch.tensor([b * Sx + s0[b] - P0 - 1 for b in range(B)], device=dev)
+            self._paste_voice_prefixes(pre, voice_of, st)
+        self._prefill_rows(xf, posr, crow, st, B, Sx, P0, exact, S=S)
+        if pre is None and share and len(voices) == 1:
+            self._keep_voice_prefix(voices[0], st, P=vP[0])
         hl = xf.index_select(0, last).contiguous()
         ops.layernorm(hl, self.lnf[0], self.lnf[1], st["dws"]["h"], 1e-5)
         ops.linear(st["dws"]["h"], self.head, st["logits"], bias=self.head_b)
-        del x, xf, h, qkv, att, g
+        del x, xf
 
         s0t = torch.tensor(s0, dtype=torch.int32, device=dev)
         st["positions"].copy_(s0t - 1)

@@ -33,7 +33,8 @@ extern "C" {
                               14: the batch-1 decode path of the GPT-2 backbones (Turbo / Nano): cbx_gemv_row_f32, cbx_decode_attn_parts; the token loop in C: cbx_t3_loop_*;
                               15: cbx_flash_attn_kv_f32 (K / V head strides: attention over the KV cache in the prefill);
                               16: cbx_gpt2_prefill (the prefill of the GPT-2 backbones as one call, optionally behind a cached conditioning prefix); added
-                                  later without a version step (no existing struct or signature changed): cbx_gpt2_decode_step, cbx_gpt2_loop_* */
+                                  later without a version step (no existing struct or signature changed): cbx_gpt2_decode_step, cbx_gpt2_loop_*; cbx_prefill_embed,
+                                  cbx_kv_prefix_paste_f32 (batched public API: the prefill input and the cached voice prefixes of a mixed-voice batch, one launch each) */
 #define CBX_EINVAL (-22)
 
 /* activations usable in GEMM / elementwise epilogues */
@@ -564,6 +565,37 @@ typedef struct cbx_gpt2_prefill_t {
     long kv_layer_stride, kv_row_stride, kv_head_stride;  /* floats */
 } cbx_gpt2_prefill_t;
 int cbx_gpt2_prefill(const cbx_gpt2_prefill_t* d, void* stream);
+
+/* ---- the prefill INPUT of a ragged batch in one launch (added after ABI v16 without a version step) ----
+ * Replaces the per-utterance host loop over cbx_embed_f32 + slice copies that builds the (rows, S - pos0, dim) prefill input of T3.inference (prepare_input_embeds +
+ * the second BOS, t3.py:102-130,305-313: [conditioning | text_emb[id] (x 0 on the CFG-unconditional row) + text_pos[i] | 2 x (speech_emb[bos] + speech_pos[0])]) and of
+ * T3.inference_turbo (t3.py:407-423: [conditioning | text_emb[id] + wpe[p] | speech_emb[bos] + wpe[p]], absolute positions p), zeros in the padding, and writes the
+ * index vectors the prefill takes: positions[r * Sx + s] = pos0 + s, cache_rows[r * Sx + s] = r, last[r] = flat index of row r's last prompt position (Sx = S - pos0).
+ * Utterance b = r % B; meta[b] = {offset of its ids in `ids`, text length, conditioning slot (-1: none), conditioning length P_b}.  Positions below P_b are copied from
+ * cond[slot] (P_b x dim floats) -- or, with pos0 > 0, are not part of x at all (they are in the KV cache: cbx_kv_prefix_paste_f32; then every P_b == pos0).
+ * One multiply-add per element in cbx_embed_f32's order: bit-identical to the loop it replaces.  The caller guarantees 0 <= ids < text vocabulary, offsets inside
+ * `ids`, slots inside `cond` and P_b + text length + n_bos <= S. */
+typedef struct cbx_prefill_embed_t {
+    int B, cfg;                           /* utterances; cfg = 1: rows = 2 B, rows B .. 2 B - 1 are the unconditional rows (text embeddings x 0), else rows = B */
+    int n_bos, abs_pos;                   /* BOS positions behind the text (Llama 2, GPT-2 1); 1: both position tables are indexed by the absolute position (wpe) */
+    int S, pos0, dim;                     /* common (padded) prompt length; first absolute position held in x (0, or the cached prefix length); model width */
+    long long bos_id;                     /* start-of-speech id (row of speech_emb) */
+    const int* meta;                      /* [B][4] */
+    const int* ids;                       /* text ids of all utterances, back to back */
+    const float* cond;                    /* [slots][cond_stride] conditioning embeddings, or NULL */
+    long cond_stride;                     /* floats */
+    const float *text_emb, *text_pos, *speech_emb, *speech_pos;   /* [.][dim] tables (GPT-2: text_pos == speech_pos == wpe) */
+    float* x;                             /* [rows][S - pos0][dim] out */
+    int *positions, *cache_rows;          /* [rows * (S - pos0)] out */
+    long long* last;                      /* [rows] out */
+} cbx_prefill_embed_t;
+int cbx_prefill_embed(const cbx_prefill_embed_t* d, void* stream);
+/* kc / vc[l][r][h][0 .. P - 1][:] = prefix_k / prefix_v[voice_of_row[r]][l][h][0 .. P - 1][:]: the cached conditioning prefixes of a batch that mixes voices, pasted in one
+ * launch (replaces one broadcast copy_ pair per voice; the K / V that LlamaModel / GPT2Model would recompute for the conditioning positions of every row, t3.py:326-333,
+ * 425-432).  table (device): n_voices pointers to K prefixes [n_layers][n_heads][P][64] contiguous, n_voices pointers to V prefixes, then voice_of_row[rows] (each in
+ * [0, n_voices)).  Pure copy. */
+int cbx_kv_prefix_paste_f32(const long long* table, int n_voices, float* kc, float* vc, int n_layers, int rows, int n_heads, int P,
+                            long kv_layer_stride, long kv_row_stride, long kv_head_stride, void* stream);
 
 /* ---- ONE token step of T3.inference_turbo's loop for every row (t3.py:392-468: the q_len == 1 HF GPT2Model forward over the KV cache, ln_f, speech_head, the
  * Temperature -> TopK -> TopP -> RepetitionPenalty processors and the multinomial draw) ----
