@@ -276,8 +276,11 @@ _SIGS = {
     "cbx_cfm_solve": ([ctypes.POINTER(CfmSolve), c_f], c_int),
     "cbx_s3gen_encode": ([ctypes.POINTER(S3Encode), c_f], c_int),
     "cbx_hift_f0_source": ([ctypes.POINTER(HiftF0), c_f], c_int),
+    "cbx_hift_f0_source_carry": ([ctypes.POINTER(HiftF0), c_f, c_f], c_int),
     "cbx_hift_decode": ([ctypes.POINTER(HiftDecode), c_f], c_int),
     "cbx_hift_source_f32": ([c_f, c_f, c_f, c_f, c_float, c_f, c_f, c_int, c_int, c_int, c_float, c_f], c_int),
+    "cbx_hift_source_carry_f32": ([c_f, c_f, c_f, c_f, c_float, c_f, c_f, c_f, c_int, c_int, c_int, c_float, c_f], c_int),
+    "cbx_stream_emit_f32": ([c_f, c_long, c_long, c_f, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_long, c_f, c_int, c_f], c_int),
     "cbx_hift_stft_f32": ([c_f, c_f, c_f, c_int, c_long, c_long, c_f], c_int),
     "cbx_hift_istft_f32": ([c_f, c_f, c_int, c_long, c_long, c_float, c_int, c_f], c_int),
 }

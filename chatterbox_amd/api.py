@@ -153,9 +153,12 @@ def _watermarker():
         return None
 
 
-def _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap):
-    """The round-schedule arguments of generate_stream, passed through to the engine's synthesize_stream."""
-    return dict(first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, overlap=overlap)
+def _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window=None):
+    """The round-schedule arguments of generate_stream, passed through to the engine's synthesize_stream.  `window` is checked here, when generate_stream is
+    CALLED (the engine's generator would raise at the first next() only)."""
+    from .engine import check_stream_window
+    return dict(first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, overlap=overlap,
+                window=check_stream_window(window, fade))
 
 
 
@@ -381,16 +384,17 @@ class ChatterboxTTS(_Base):
                                     False, generator, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
-                        cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True):
+                        cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None):
         """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
-        `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece."""
+        `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
+        window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream)."""
         if audio_prompt_path:
             self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
         else:
             assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
         self._set_exaggeration(exaggeration)
         toks = self.tokenizer.text_to_tokens(punc_norm_en(text))
-        return self._generate_stream(toks, False, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap), temperature=temperature,
+        return self._generate_stream(toks, False, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window), temperature=temperature,
                                      cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
 
@@ -447,9 +451,10 @@ class ChatterboxMultilingualTTS(_Base):
                                     repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True):
+                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None):
         """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
-        `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece."""
+        `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
+        window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream)."""
         if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
             raise ValueError(f"Unsupported language_id '{language_id}'. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
         if audio_prompt_path:
@@ -458,7 +463,7 @@ class ChatterboxMultilingualTTS(_Base):
             assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
         self._set_exaggeration(exaggeration)
         toks = self.tokenizer.text_to_tokens(punc_norm(text), language_id=language_id.lower() if language_id else None)
-        return self._generate_stream(toks, True, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap), temperature=temperature,
+        return self._generate_stream(toks, True, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window), temperature=temperature,
                                      cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
 
@@ -564,9 +569,10 @@ class ChatterboxTurboTTS(_BatchMixin):
                 yield self._finish(r["wavs"][0])
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
-                        temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True):
+                        temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None):
         """generate() in pieces (TurboEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk`
-        tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece."""
+        tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
+        window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream)."""
         if audio_prompt_path:
             self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, norm_loudness=norm_loudness)
         else:
@@ -575,7 +581,7 @@ class ChatterboxTurboTTS(_BatchMixin):
             import logging
             logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
         ids = self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids
-        return self._generate_stream(ids[0], _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap), temperature=temperature, top_k=top_k,
+        return self._generate_stream(ids[0], _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window), temperature=temperature, top_k=top_k,
                                      top_p=top_p, repetition_penalty=repetition_penalty)
 
 
@@ -631,8 +637,9 @@ class ChatterboxVC:
         w24 = fe.resample(wav_fpath[0], wav_fpath[1], S3GEN_SR) if isinstance(wav_fpath, (tuple, list)) else fe.load_wav(wav_fpath, S3GEN_SR)[0]
         self.ref_dict = self.analyzer.embed_ref(w24[: self.DEC_COND_LEN], S3GEN_SR)
 
-    def generate(self, audio=None, target_voice_path=None, s3_tokens=None):
-        """reference vc.py:83-104.  audio: a WAV path or a (waveform, sample_rate) pair."""
+    def _source_tokens(self, audio, target_voice_path, s3_tokens):
+        """The argument handling of generate (reference vc.py:83-104) -> the source's S3 tokens, 1-D on the host.  self.ref_dict is written only when a
+        target_voice_path is given."""
         if target_voice_path:
             self.set_target_voice(target_voice_path)
         else:
@@ -642,11 +649,46 @@ class ChatterboxVC:
             self._need_analyzer()
             w16 = fe.resample(audio[0], audio[1], S3_SR) if isinstance(audio, (tuple, list)) else fe.load_wav(audio, S3_SR)[0]
             s3_tokens, _ = self.analyzer.tokenizer(torch.from_numpy(w16))
-        wavs, _ = self.engine.vocode([torch.as_tensor(s3_tokens).view(-1).long().cpu()], self.ref_dict)
-        wav = wavs[0].detach().float().cpu()
+        return torch.as_tensor(s3_tokens).view(-1).long().cpu()
+
+    def _finish(self, wav):
+        wav = wav.detach().float().cpu()
         if self.watermarker is not None:
             wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
         return wav.unsqueeze(0)
+
+    def generate(self, audio=None, target_voice_path=None, s3_tokens=None):
+        """reference vc.py:83-104.  audio: a WAV path or a (waveform, sample_rate) pair."""
+        wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict)
+        return self._finish(wavs[0])
+
+    def generate_stream(self, audio=None, target_voice_path=None, s3_tokens=None, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=200):
+        """generate() in pieces (ChatterboxEngine.vocode_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk` tokens of
+        the source; concatenated along dim 1 they give the conversion.  A round synthesises the target voice's prompt, `window` tokens of left context, the new
+        chunk and the lookahead, so its cost does not grow with the length of the source (window=None: every round re-synthesises everything so far); the
+        default 200 + chunk 50 is the 250-token round the flow is tuned at.  Arguments are checked and the source is tokenised when this is CALLED, as generate
+        does; self.ref_dict is written only when target_voice_path is given.  The target voice's prompt must be a whole number of tokens (2 mel frames per
+        prompt token).  If a watermarker is loaded it is applied to each piece."""
+        from .engine import check_stream_window
+        for name, v, lo in (("first_chunk", first_chunk, 1), ("chunk", chunk, 1), ("lookahead", lookahead, 0), ("fade", fade, 0)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise ValueError(f"{name}={v!r}: expected an int >= {lo}")
+        check_stream_window(window, fade)
+        if not chunk_growth >= 1.0:
+            raise ValueError(f"chunk_growth={chunk_growth!r}: expected a number >= 1")
+        if audio is None and s3_tokens is None:
+            raise ValueError("give audio or s3_tokens")
+        toks = self._source_tokens(audio, target_voice_path, s3_tokens)
+        if toks.numel() == 0:
+            raise ValueError("the source has no S3 tokens")
+        ref = self.ref_dict  # (the voice of THIS call: a later set_target_voice does not reach into a running stream)
+
+        def pieces():
+            for r in self.engine.vocode_stream([toks], ref, first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade,
+                                               window=window):
+                if r["wavs"][0].numel():
+                    yield self._finish(r["wavs"][0])
+        return pieces()
 
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 

@@ -18,15 +18,17 @@ __device__ __forceinline__ float harmonic_inc(float f0, int h, float sr) {
     return t / sr;
 }
 
-// exclusive scan over frames of up * F[b][h][frame], in fp64: one lane per (b, h)
-__global__ void source_scan_kernel(const float* __restrict__ f0, double* __restrict__ frame_cum, int B, int T, int up,
-                                   float sr) {
+// exclusive scan over frames of up * F[b][h][frame], in fp64: one lane per (b, h).  cum_in (B, 9) or NULL: the cumulative cycles the scan of
+// (b, h) starts from -- a window that begins at frame w0 of a longer signal carries frame_cum[b][h][w0] of that signal in and continues the very same
+// chain of fp64 additions (NULL, or zeros: the scan of a signal that starts at sample 0)
+__global__ void source_scan_kernel(const float* __restrict__ f0, double* __restrict__ frame_cum, const double* __restrict__ cum_in, int B, int T,
+                                   int up, float sr) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * 9) return;
     int b = i / 9, h = i - b * 9;
     const float* fr = f0 + (long)b * T;
     double* out = frame_cum + (long)i * T;
-    double acc = 0.0;
+    double acc = cum_in ? cum_in[i] : 0.0;
     for (int t = 0; t < T; ++t) {
         out[t] = acc;
         acc += (double)up * (double)harmonic_inc(fr[t], h, sr);
@@ -165,15 +167,20 @@ __global__ __launch_bounds__(IS_BLK) void istft_kernel(const float* __restrict__
 
 }  // namespace
 
-extern "C" int cbx_hift_source_f32(const float* f0, const float* phase, const float* noise, const float* lin_w, float lin_b,
-                                   float* s, double* frame_cum, int B, int T, int up, float sr, void* stream) {
+extern "C" int cbx_hift_source_carry_f32(const float* f0, const float* phase, const float* noise, const float* lin_w, float lin_b, float* s,
+                                         double* frame_cum, const double* cum_in, int B, int T, int up, float sr, void* stream) {
     CBX_REQUIRE(f0 && phase && noise && lin_w && s && frame_cum && B > 0 && T > 0, "hift_source: bad args");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(source_scan_kernel, dim3((B * 9 + 63) / 64), dim3(64), 0, st, f0, frame_cum, B, T, up, sr);
+    hipLaunchKernelGGL(source_scan_kernel, dim3((B * 9 + 63) / 64), dim3(64), 0, st, f0, frame_cum, cum_in, B, T, up, sr);
     long total = (long)B * T * up;
     unsigned grid = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
     hipLaunchKernelGGL(source_kernel, dim3(grid), dim3(256), 0, st, f0, phase, noise, lin_w, lin_b, s, frame_cum, B, T, up, sr);
     return cbx_check_launch("hift_source");
+}
+
+extern "C" int cbx_hift_source_f32(const float* f0, const float* phase, const float* noise, const float* lin_w, float lin_b,
+                                   float* s, double* frame_cum, int B, int T, int up, float sr, void* stream) {
+    return cbx_hift_source_carry_f32(f0, phase, noise, lin_w, lin_b, s, frame_cum, nullptr, B, T, up, sr, stream);
 }
 
 extern "C" int cbx_hift_stft_f32(const float* s, float* spec, const int* sample_lens, int B, long L, long ld_spec,

@@ -360,7 +360,7 @@ extern "C" int cbx_s3gen_encode(const cbx_s3enc_t* d, void* stream) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------ HiFT F0 predictor + source
-extern "C" int cbx_hift_f0_source(const cbx_hift_f0_t* d, void* stream) {
+extern "C" int cbx_hift_f0_source_carry(const cbx_hift_f0_t* d, const double* cum_in, void* stream) {
     CBX_REQUIRE(d && d->mel && d->cls_w && d->cls_b && d->src_w && d->phase && d->noise && d->buf0 && d->buf1 && d->f0 && d->s && d->cum,
                 "hift_f0_source: null descriptor field");
     CBX_REQUIRE(d->B >= 1 && d->T >= 1, "hift_f0_source: bad shape");
@@ -382,5 +382,7 @@ extern "C" int cbx_hift_f0_source(const cbx_hift_f0_t* d, void* stream) {
     g.M = (int)(d->B * T), g.N = 1, g.K = 512, g.Cin = 512, g.taps = 1, g.dil = 1, g.stride = 1, g.up = 1, g.nz1 = 1, g.nz2 = 1;
     g.act1 = CBX_ACT_ABS, g.alpha = 1.0f, g.lda = 512, g.ldw = 512, g.ldc = 1, g.precision = 1;
     if ((rc = cbx_gemm_f32(&g, stream))) return rc;
-    return cbx_hift_source_f32(d->f0, d->phase, d->noise, d->src_w, d->src_b, d->s, d->cum, d->B, (int)T, 480, 24000.0f, stream);
+    return cbx_hift_source_carry_f32(d->f0, d->phase, d->noise, d->src_w, d->src_b, d->s, d->cum, cum_in, d->B, (int)T, 480, 24000.0f, stream);
 }
+
+extern "C" int cbx_hift_f0_source(const cbx_hift_f0_t* d, void* stream) { return cbx_hift_f0_source_carry(d, nullptr, stream); }

@@ -353,70 +353,168 @@ def stream_token_schedule(n_tokens, first_chunk=25, chunk=50, lookahead=3, chunk
         c *= chunk_growth
 
 
-def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw, round_tokens, n_extra, first_chunk, chunk, chunk_growth, lookahead, fade, z,
-                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead):
-    """The round schedule of synthesize_stream for either backbone (ChatterboxEngine: Llama T3, TurboEngine: GPT-2 T3; both T3 engines offer the async
-    generate / advance / peek protocol).  n_budget: tokens the T3 call can sample; t3_kw: its sampling arguments; round_tokens(toks, final flags) -> the
-    valid speech tokens a round vocodes (never empty); n_extra: tokens round_tokens may add (the default z / noise cover n_budget + n_extra)."""
-    # (a generator cannot hold a device guard across yields: pin the device for the caller; "cuda" without an index = the current device)
-    pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-    torch.cuda.set_device(pin)
-    dev, B = self.dev, len(text_tokens)
+STREAM_RECEPTIVE_FIELD = 8000  # samples of context the vocoder needs on the left of a sample (measured on the oracle: tests/test_stream_gpu.py)
+
+
+def check_stream_window(window, fade):
+    """window=None (every round re-synthesises everything so far) or a left context in TOKENS that covers the vocoder's receptive field and the cross-fade:
+    at least ceil((8000 + fade) / 960).  Anything else is a ValueError, raised before a launch."""
+    if window is None:
+        return None
+    need = -(-(STREAM_RECEPTIVE_FIELD + int(fade)) // SAMPLES_PER_TOKEN)
+    if isinstance(window, bool) or not isinstance(window, int) or window < need:
+        raise ValueError(f"window={window!r}: expected None or an int >= {need} tokens (the vocoder's receptive field of {STREAM_RECEPTIVE_FIELD} samples + fade={fade})")
+    return window
+
+
+def stream_window_schedule(n_tokens, first_chunk=25, chunk=50, lookahead=3, chunk_growth=1.0, window=None, fade=480):
+    """[(a_r, n_r), ...]: round r of a stream of an utterance of `n_tokens` tokens synthesises tokens [a_r, n_r).  n_r is stream_token_schedule's; with
+    window=None every a_r is 0 (the work of a round grows with r), with window=W tokens a_r = max(0, E_r // 960 - W), E_r = the samples emitted before round r
+    (all but the last `fade` of what round r - 1 could vocode): once the window slides a round is W + chunk + lookahead + 1 tokens long whatever r is
+    (fade <= 960).  Pure host arithmetic: the engine computes the same a_r from what it has emitted."""
+    window = check_stream_window(window, fade)
+    out, emitted = [], 0
+    for n in stream_token_schedule(n_tokens, first_chunk, chunk, lookahead, chunk_growth):
+        out.append((0 if window is None else max(0, emitted // SAMPLES_PER_TOKEN - window), n))
+        final = n >= n_tokens
+        avail = (SAMPLES_PER_TOKEN // 2) * (2 * n - (0 if final else 2 * lookahead))
+        emitted = avail if final else max(emitted, avail - fade)
+    return out
+
+
+def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade, z, phase, noise, n_cfm_timesteps, drop_last_token, window):
+    """The state of one stream of B utterances and its round function: -> (one_round, closed flags).  one_round(toks, done, exhausted) runs flow + vocoder
+    on the CURRENT stream and returns the dict the stream generators yield.  n_tokens: the most tokens an utterance can have (the default z / noise cover them).
+
+    window=None: a round synthesises every token so far.  window=W (tokens; check_stream_window): a round synthesises the voice prompt and tokens [a, n) only,
+    a = max(0, E // 960 - W) with E the samples already emitted (of the utterances still open) -- W tokens of left context in front of the first new sample:
+      * the CFM noise of absolute frame t is z[:, 2P + t] in every round, the source noise of absolute sample q is noise[:, :, q];
+      * the vocoder's excitation stays phase-continuous although the window does not start at sample 0: the source's phase scan starts from the previous
+        round's cumulative cycles at the frame the window now begins (HiFTEngine.inference(cum_in=), cbx_hift_f0_source_carry), and the previous round's source
+        from that sample on is the `cache_source`;
+      * S3Gen's trim_fade belongs to sample 0: applied while a == 0 only;
+      * emitted / end / avail stay ABSOLUTE samples of the utterance; the round's waveform starts at sample 960 a.  The emission (new samples, cross-fade
+        with the kept tail, next tail) is one cbx_stream_emit_f32 launch and one D2H copy for all utterances.
+    The cache keeps the source of the rows that go on (the window=None form keeps the shortest row's, finished rows included); with every a == 0 and no row
+    finishing before the others the two forms yield the same bits."""
+    dev = self.dev
+    W = check_stream_window(window, fade)
     P = gen_ref["prompt_token"].shape[-1]
-    N = n_budget
+    N = n_tokens
     assert gen_ref["prompt_feat"].shape[-2] == 2 * P, "chunked synthesis needs a whole-token prompt (embed_ref output trimmed to 2 frames per token)"
     if z is None:
-        z = torch.randn(B, 2 * (P + N + n_extra), 80, device=dev)
+        z = torch.randn(B, 2 * (P + N), 80, device=dev)
     if phase is None:
         phase = (torch.rand(B, 9, device=dev) * 2 - 1) * 3.141592653589793
         phase[:, 0] = 0
     if noise is None:
-        noise = torch.randn(B, 9, SAMPLES_PER_TOKEN * (N + n_extra), device=dev)
+        noise = torch.randn(B, 9, SAMPLES_PER_TOKEN * N, device=dev)
     z, phase, noise = z.to(dev), phase.to(dev).reshape(B, 9), noise.to(dev)
-    t3_kw = dict(t3_kw, async_mode=True)
-    totals = stream_token_schedule(N, first_chunk, chunk, lookahead, chunk_growth)  # tokens decoded when round r starts
     emitted, tails, closed, cache = [0] * B, [None] * B, [False] * B, [None]
     ramp = torch.linspace(0.0, 1.0, fade + 2, device=dev)[1:-1]
+    win = dict(a=0, cum=None, tail_len=[0] * B, bufs=None, cur=0)  # window form: origin (tokens) and phase scan of the last round, the kept tails (device, ping-pong)
+    HALF = SAMPLES_PER_TOKEN // 2  # samples per mel frame
 
     def one_round(toks, done, exhausted):
-        """flow + vocoder over the tokens so far on the CURRENT stream -> the dict this generator yields"""
+        """flow + vocoder over the tokens so far (window form: over the window) on the CURRENT stream -> the dict this generator yields"""
         fin, hold = _stream_plan([t.numel() for t in toks], done, exhausted, lookahead)
         st = round_tokens(toks, fin)
         ns = [int(t.numel()) for t in st]
-        Nk = max(ns)
-        frames = [max(0, 2 * n - hb) for n, hb in zip(ns, hold)]
+        a, cum_in, cache_src = 0, None, cache[0]
+        if W is not None:
+            live = [emitted[b] for b in range(B) if not closed[b]]
+            a = max(0, min(live) // SAMPLES_PER_TOKEN - W) if live else win["a"]
+            assert all(closed[b] or ns[b] > a for b in range(B)), "an open utterance ends left of the window"
+            if win["cum"] is not None:  # continue the previous round's excitation from where this window begins
+                d = a - win["a"]
+                assert 0 <= 2 * d < win["cum"].shape[2]
+                cum_in = win["cum"][:, :, 2 * d].contiguous()
+                cache_src = cache[0][:, SAMPLES_PER_TOKEN * d:] if cache[0] is not None and cache[0].shape[1] > SAMPLES_PER_TOKEN * d else None
+        ws = st if a == 0 else [t[a:] if t.numel() > a else t.new_zeros(1) for t in st]  # (a finished utterance left of the window: one dummy token)
+        wn = [int(t.numel()) for t in ws]
+        Nk = max(wn)
+        frames = [max(0, 2 * n - hb) for n, hb in zip(wn, hold)]
         out = [torch.zeros(0)] * B
         if max(frames) > 0:
             tok = torch.zeros(B, Nk, dtype=torch.long)
-            for b, t in enumerate(st):
-                tok[b, : ns[b]] = t
+            for b, t in enumerate(ws):
+                tok[b, : wn[b]] = t
             fl = torch.tensor(frames, dtype=torch.int32, device=dev)
+            o = SAMPLES_PER_TOKEN * a  # absolute sample of wav[:, 0]
 
             def run():
-                mel = self.flow.inference(tok.to(dev), torch.tensor(ns, dtype=torch.int32, device=dev), gen_ref, z=z[:, : 2 * (P + Nk)],
+                zz = z[:, : 2 * (P + Nk)] if a == 0 else torch.cat([z[:, : 2 * P], z[:, 2 * (P + a): 2 * (P + a + Nk)]], 1)
+                mel = self.flow.inference(tok.to(dev), torch.tensor(wn, dtype=torch.int32, device=dev), gen_ref, z=zz,
                                           n_steps=n_cfm_timesteps, hold_back=hold)
-                return self.hift.inference(mel, phase=phase, noise=noise[:, :, : 480 * mel.shape[1]], lens=fl, fade=True,
-                                           cache_source=cache[0])
+                return self.hift.inference(mel, phase=phase, noise=noise[:, :, o: o + HALF * mel.shape[1]], lens=fl, fade=a == 0,
+                                           cache_source=cache_src, cum_in=cum_in)
             wav, src = _range_checked(self, run)
-            cache[0] = src[:, : 480 * min(frames)].clone() if min(frames) > 0 else None
-            for b in range(B):
-                if closed[b]:
-                    continue
-                avail = 480 * frames[b]
-                if fin[b]:
-                    keep = max(1, ns[b] - 1) if drop_last_token else ns[b]
-                    avail = min(avail, keep * SAMPLES_PER_TOKEN)
-                end = avail if fin[b] else max(emitted[b], avail - fade)
-                new = wav[b, emitted[b]: end].clone()
-                if tails[b] is not None and new.numel() > 0:
-                    k = min(tails[b].numel(), new.numel())
-                    new[:k] = tails[b][:k] * (1.0 - ramp[:k]) + new[:k] * ramp[:k]
-                tails[b] = None if fin[b] else wav[b, end: min(avail, end + fade)].clone()
-                emitted[b] = end
-                closed[b] = fin[b]
-                out[b] = new.cpu()
+            if W is None:
+                cache[0] = src[:, : HALF * min(frames)].clone() if min(frames) > 0 else None
+                for b in range(B):
+                    if closed[b]:
+                        continue
+                    avail = HALF * frames[b]
+                    if fin[b]:
+                        keep = max(1, ns[b] - 1) if drop_last_token else ns[b]
+                        avail = min(avail, keep * SAMPLES_PER_TOKEN)
+                    end = avail if fin[b] else max(emitted[b], avail - fade)
+                    new = wav[b, emitted[b]: end].clone()
+                    if tails[b] is not None and new.numel() > 0:
+                        k = min(tails[b].numel(), new.numel())
+                        new[:k] = tails[b][:k] * (1.0 - ramp[:k]) + new[:k] * ramp[:k]
+                    tails[b] = None if fin[b] else wav[b, end: min(avail, end + fade)].clone()
+                    emitted[b] = end
+                    closed[b] = fin[b]
+                    out[b] = new.cpu()
+            else:
+                go_on = [frames[b] for b in range(B) if not fin[b]]
+                cache[0] = src[:, : HALF * min(go_on)].clone() if go_on and min(go_on) > 0 else None
+                win.update(a=a, cum=self.hift.frame_cum)
+                meta, news, nxt = torch.zeros(4, B, dtype=torch.int32), [0] * B, [0] * B
+                for b in range(B):
+                    if closed[b]:
+                        meta[:3, b] = emitted[b]
+                        continue
+                    avail = o + HALF * frames[b]
+                    if fin[b]:
+                        keep = max(1, ns[b] - 1) if drop_last_token else ns[b]
+                        avail = min(avail, keep * SAMPLES_PER_TOKEN)
+                    end = avail if fin[b] else max(emitted[b], avail - fade)
+                    meta[:, b] = torch.tensor([emitted[b], end, avail, win["tail_len"][b]], dtype=torch.int32)
+                    news[b], nxt[b] = max(0, end - emitted[b]), 0 if fin[b] else max(0, min(avail, end + fade) - end)
+                    emitted[b] = end
+                    closed[b] = fin[b]
+                if fade and win["bufs"] is None:
+                    win["bufs"] = [torch.zeros(B, fade, device=dev) for _ in range(2)]
+                t_in, t_out = (win["bufs"][win["cur"]], win["bufs"][1 - win["cur"]]) if fade else (None, None)
+                new = torch.empty(B, max(news), device=dev)
+                ops.stream_emit(wav, o, meta.to(dev), t_in, ramp if fade else None, new, t_out)
+                win.update(tail_len=nxt, cur=1 - win["cur"])
+                host = new.cpu()
+                for b in range(B):
+                    if news[b]:
+                        out[b] = host[b, : news[b]].clone()
         return dict(wavs=out, final=list(fin), n_tokens=ns, tokens=st)
 
+    return one_round, closed
+
+
+def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw, round_tokens, n_extra, first_chunk, chunk, chunk_growth, lookahead, fade, z,
+                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead, window=None):
+    """The round schedule of synthesize_stream for either backbone (ChatterboxEngine: Llama T3, TurboEngine: GPT-2 T3; both T3 engines offer the async
+    generate / advance / peek protocol).  n_budget: tokens the T3 call can sample; t3_kw: its sampling arguments; round_tokens(toks, final flags) -> the
+    valid speech tokens a round vocodes (never empty); n_extra: tokens round_tokens may add (the default z / noise cover n_budget + n_extra).
+    window: None, or the left context in tokens of a bounded round (_stream_rounds)."""
+    check_stream_window(window, fade)
+    # (a generator cannot hold a device guard across yields: pin the device for the caller; "cuda" without an index = the current device)
+    pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+    torch.cuda.set_device(pin)
+    B, N = len(text_tokens), n_budget
+    t3_kw = dict(t3_kw, async_mode=True)
+    totals = stream_token_schedule(N, first_chunk, chunk, lookahead, chunk_growth)  # tokens decoded when round r starts
+    one_round, closed = _stream_rounds(self, B, gen_ref, n_tokens=N + n_extra, round_tokens=round_tokens, lookahead=lookahead, fade=fade, z=z, phase=phase, noise=noise,
+                                       n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window)
     if not overlap:  # the serial form of rounds 3-5: T3 waits while a round is synthesised
         h = self.t3.generate(t3_conds, text_tokens, run_steps=totals[0], **t3_kw)
         for r, n_r in enumerate(totals):
@@ -492,7 +590,8 @@ def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw,
 
 def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,
                       temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False,
-                      ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2):
+                      ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2,
+                      window=None):
     """Chunked synthesis: first audio after `first_chunk` tokens instead of after the whole utterance.
 
     The reference is non-streaming; of its vestigial hooks only HiFT's `cache_source` works (hifigan.py:470-472) -- `finalize=False`
@@ -509,6 +608,9 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
     its own high-priority stream (at most two rounds ahead of the vocoder; graph replays of the captured step), this thread waits for a round's
     tokens on the flow stream and runs that round's flow + vocoder there, both stages on their co-resident kernel forms (synthesize_pipelined).
     A round still sees exactly its n_r tokens, so every yielded sample is the one the serial form (overlap=False) yields.
+    window (None: the schedule above): the left context, in tokens, of a round of BOUNDED cost -- a round then synthesises the voice prompt, `window`
+    tokens in front of the first sample it has not emitted yet, the new chunk and the lookahead, whatever the round's number (_stream_rounds,
+    stream_window_schedule); at least ceil((8000 + fade) / 960) tokens, else ValueError.  The last round is then no longer the full synthesis.
     Yields dicts {wavs: [B CPU tensors of NEW samples], final: [B bools], n_tokens: [B], tokens: [B CPU tensors: the speech tokens the round vocoded]};
     concatenating an utterance's pieces gives its waveform."""
     t3_kw = dict(max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
@@ -521,13 +623,35 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
     yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_new_tokens, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=0,
                                   first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                   noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                  run_ahead=run_ahead)
+                                  run_ahead=run_ahead, window=window)
+
+
+def vocode_stream(self, speech_tokens, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=None, z=None, phase=None,
+                  noise=None, n_cfm_timesteps=10, drop_last_token=False):
+    """vocode() in rounds: the schedule, the yields and the `window` of synthesize_stream with a list of B 1-D token tensors (valid ids; lengths may differ) in
+    place of T3 -- round r synthesises the first n_r tokens of every utterance (stream_token_schedule over the longest), utterance b is final once
+    n_r >= N_b.  No T3 is touched: this is the streaming form of voice conversion (the engine ChatterboxVC builds has none), where every token exists up
+    front and the input can be arbitrarily long -- give a `window`.  gen_ref: one voice with a whole-token prompt."""
+    check_stream_window(window, fade)
+    pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+    torch.cuda.set_device(pin)  # (a generator cannot hold a device guard across yields)
+    toks = [torch.as_tensor(t).view(-1).long().cpu() for t in speech_tokens]
+    assert toks and all(t.numel() > 0 for t in toks), "vocode_stream: every utterance needs at least one token"
+    lens = [int(t.numel()) for t in toks]
+    self.co_resident(False)
+    one_round, closed = _stream_rounds(self, len(toks), gen_ref, n_tokens=max(lens), round_tokens=lambda ts, fin: ts, lookahead=lookahead, fade=fade, z=z,
+                                       phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window)
+    for n_r in stream_token_schedule(max(lens), first_chunk, chunk, lookahead, chunk_growth):
+        yield one_round([t[:n_r] for t in toks], [n_r >= n for n in lens], n_r >= max(lens))
+        if all(closed):
+            return
 
 
 S3GEN_SIL = 4299  # reference models/s3gen/const.py:2
 
 
 ChatterboxEngine.synthesize_stream = torch.inference_mode()(synthesize_stream)
+ChatterboxEngine.vocode_stream = torch.inference_mode()(vocode_stream)
 
 
 class TurboEngine:
@@ -543,6 +667,7 @@ class TurboEngine:
         self.last_timing = {}
 
     vocode = ChatterboxEngine.vocode
+    vocode_stream = ChatterboxEngine.vocode_stream
 
     @ops.on_device
     @torch.inference_mode()
@@ -567,12 +692,13 @@ class TurboEngine:
     @torch.inference_mode()
     def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_gen_len=1000,
                           temperature=0.8, top_k=1000, top_p=0.95, repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2):
+                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2, window=None):
         """Chunked synthesis of Turbo / Nano: the round schedule, yields and overlap / first_alone / run_ahead semantics of ChatterboxEngine.synthesize_stream
         around the GPT-2 T3 (chunked through T3TurboEngine.generate(async_mode=True) / advance / peek) and the 2-step meanflow flow.  A round vocodes the
         sampled ids < 6561; the FINAL round of an utterance appends the three S3GEN_SIL tokens exactly as synthesize() does and keeps every token
         (drop_last_token=False), non-final rounds carry no silence and hold back 2 * lookahead frames.  T3 can sample max_gen_len + 1 tokens: the default
-        z / phase / noise cover that many plus the 3 silence tokens.  The last round is a full synthesis: identical mel to synthesize() for the same noise."""
+        z / phase / noise cover that many plus the 3 silence tokens.  The last round is a full synthesis: identical mel to synthesize() for the same noise.
+        window: the bounded-cost rounds of ChatterboxEngine.synthesize_stream."""
         t3_kw = dict(max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, uniforms=uniforms,
                      ban_eos=ban_eos, ban_from=ban_from)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
@@ -584,4 +710,4 @@ class TurboEngine:
         yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_gen_len + 1, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=3,
                                       first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                       noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                      run_ahead=run_ahead)
+                                      run_ahead=run_ahead, window=window)

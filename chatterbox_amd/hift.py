@@ -103,12 +103,14 @@ class HiFTEngine:
 
     @ops.on_device
     @torch.inference_mode()
-    def source(self, f0, phase, noise):
-        """f0_upsamp + SourceModuleHnNSF (hifigan.py:467-469, 201-231, 267-283) -> s (B, 480*T)."""
+    def source(self, f0, phase, noise, cum_in=None):
+        """f0_upsamp + SourceModuleHnNSF (hifigan.py:467-469, 201-231, 267-283) -> s (B, 480*T).  cum_in (B, 9) float64: the cumulative cycles the phase
+        scan starts from (ops.hift_source); the scan of this call, (B, 9, T) float64, stays in self.frame_cum."""
         B, T = f0.shape
         s = torch.empty(B, 480 * T, device=self.dev)
         cum = torch.empty(B, 9, T, dtype=torch.float64, device=self.dev)
-        ops.hift_source(f0, phase.reshape(B, 9).contiguous(), noise.contiguous(), self.src_w, self.src_b, s, cum)
+        ops.hift_source(f0, phase.reshape(B, 9).contiguous(), noise.contiguous(), self.src_w, self.src_b, s, cum, cum_in=cum_in)
+        self.frame_cum = cum
         return s
 
     def _decode_c(self, mel, s, lens, fade):
@@ -145,8 +147,8 @@ class HiFTEngine:
         check(lib.cbx_hift_decode(ctypes.byref(d), ops._stream()), "cbx_hift_decode")
         return wav
 
-    def _f0_source_c(self, mel, phase, noise, lens):
-        """f0_predict + source as ONE call of cbx_hift_f0_source (ABI v12): the same launches with the same arguments."""
+    def _f0_source_c(self, mel, phase, noise, lens, cum_in=None):
+        """f0_predict + source as ONE call of cbx_hift_f0_source (ABI v12): the same launches with the same arguments.  cum_in: cbx_hift_f0_source_carry."""
         import ctypes
 
         from ._lib import HiftF0, check, lib
@@ -160,7 +162,12 @@ class HiFTEngine:
         s = f(B, 480 * T)
         d.B, d.T, d.mel, d.lens, d.cls_w, d.cls_b, d.src_w, d.src_b = B, T, p(mel), p(lens), p(self.f0_cls[0]), p(self.f0_cls[1]), p(self.src_w), self.src_b
         d.buf0, d.buf1, d.f0, d.cum, d.phase, d.noise, d.s = p(keep[0]), p(keep[1]), p(keep[2]), p(keep[3]), p(keep[4]), p(keep[5]), p(s)
-        check(lib.cbx_hift_f0_source(ctypes.byref(d), ops._stream()), "cbx_hift_f0_source")
+        if cum_in is None:
+            check(lib.cbx_hift_f0_source(ctypes.byref(d), ops._stream()), "cbx_hift_f0_source")
+        else:
+            assert cum_in.dtype == torch.float64 and cum_in.shape == (B, 9) and cum_in.is_contiguous() and cum_in.device == mel.device, "cum_in: (B, 9) float64"
+            check(lib.cbx_hift_f0_source_carry(ctypes.byref(d), ops._p(cum_in), ops._stream()), "cbx_hift_f0_source_carry")
+        self.frame_cum = keep[3]
         return s
 
     @ops.on_device
@@ -217,9 +224,11 @@ class HiFTEngine:
 
     @ops.on_device
     @torch.inference_mode()
-    def inference(self, mel, phase=None, noise=None, lens=None, fade=True, cache_source=None, generator=None):
+    def inference(self, mel, phase=None, noise=None, lens=None, fade=True, cache_source=None, generator=None, cum_in=None):
         """HiFTGenerator.inference + S3Gen trim_fade.  mel (B,T,80) channel-last.  Returns (wav (B,480T), source (B,480T)).
-        cache_source (B, L): the source of an earlier chunk replaces the first L samples (hifigan.py:470-472)."""
+        cache_source (B, L): the source of an earlier chunk replaces the first L samples (hifigan.py:470-472).
+        cum_in (B, 9) float64: mel is a window of a longer signal -- the source's phase scan starts from these cumulative cycles instead of 0 (the
+        carry of an earlier call: its self.frame_cum (B, 9, T) at the frame this window starts)."""
         B, T, _ = mel.shape
         if phase is None:
             phase = (torch.rand(B, 9, device=self.dev, generator=generator) * 2 - 1) * 3.141592653589793
@@ -227,11 +236,11 @@ class HiFTEngine:
         if noise is None:
             noise = torch.randn(B, 9, 480 * T, device=self.dev, generator=generator)
         if self.c_seam and not ops.TIMER and mel.is_contiguous() and mel.dtype == torch.float32:
-            s = self._f0_source_c(mel, phase.to(self.dev).float(), noise.to(self.dev).float(), lens)
+            s = self._f0_source_c(mel, phase.to(self.dev).float(), noise.to(self.dev).float(), lens, cum_in)
         else:
             with ops.gemm_precision(1):
                 f0 = self.f0_predict(mel, lens)
-            s = self.source(f0, phase.to(self.dev).float(), noise.to(self.dev).float())
+            s = self.source(f0, phase.to(self.dev).float(), noise.to(self.dev).float(), cum_in)
         if cache_source is not None and cache_source.shape[1]:
             s[:, : cache_source.shape[1]] = cache_source.to(self.dev)
         with ops.gemm_precision(self.precision):

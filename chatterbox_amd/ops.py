@@ -767,11 +767,31 @@ def t3_sample(**kw):
     check(lib.cbx_t3_sample(ctypes.byref(p), _stream()), "cbx_t3_sample")
 
 
-def hift_source(f0, phase, noise, lin_w, lin_b, s, frame_cum, up=480, sr=24000.0):
+def hift_source(f0, phase, noise, lin_w, lin_b, s, frame_cum, up=480, sr=24000.0, cum_in=None):
+    """cum_in (B, 9) float64 or None: the cumulative cycles the frame scan starts from (a window of a longer signal: frame_cum[:, :, w0] of that signal)."""
     B, T = f0.shape
-    check(lib.cbx_hift_source_f32(_p(f0), _p(phase), _p(noise), _p(lin_w), float(lin_b), _p(s), _p(frame_cum), B, T, up, sr,
-                                  _stream()), "cbx_hift_source_f32")
+    if cum_in is None:
+        check(lib.cbx_hift_source_f32(_p(f0), _p(phase), _p(noise), _p(lin_w), float(lin_b), _p(s), _p(frame_cum), B, T, up, sr,
+                                      _stream()), "cbx_hift_source_f32")
+    else:
+        assert cum_in.dtype == torch.float64 and cum_in.shape == (B, 9) and cum_in.is_contiguous() and cum_in.device == f0.device, "cum_in: (B, 9) float64"
+        check(lib.cbx_hift_source_carry_f32(_p(f0), _p(phase), _p(noise), _p(lin_w), float(lin_b), _p(s), _p(frame_cum), _p(cum_in), B, T, up, sr,
+                                            _stream()), "cbx_hift_source_carry_f32")
     return s
+
+
+def stream_emit(wav, origin, meta, tail_in, ramp, out, tail_out):
+    """cbx_stream_emit_f32.  wav (B, L) of the round, wav[b, q] = absolute sample origin + q; meta (4, B) int32 = emitted, end, avail, tail length (absolute
+    samples); tail_in / tail_out (B, fade), ramp (fade,) -- or None when fade is 0; out (B, max_new).  Fills out[b, : end - emitted] and tail_out."""
+    B, L = wav.shape
+    assert wav.is_contiguous() and meta.dtype == torch.int32 and meta.shape == (4, B) and meta.is_contiguous() and meta.device == wav.device
+    fade = 0 if ramp is None else int(ramp.numel())
+    assert out.shape[0] == B and out.is_contiguous() and (fade == 0 or (tail_in.shape == tail_out.shape == (B, fade) and tail_in.is_contiguous()
+                                                                        and tail_out.is_contiguous() and ramp.is_contiguous()))
+    m = meta.data_ptr()
+    check(lib.cbx_stream_emit_f32(_p(_f32(wav, "wav")), wav.stride(0), int(origin), m, m + 4 * B, m + 8 * B, _p(tail_in), m + 12 * B, _p(ramp), fade,
+                                  _p(_f32(out, "out")), out.shape[1], _p(tail_out), B, _stream()), "cbx_stream_emit_f32")
+    return out
 
 
 def hift_stft(s, spec, sample_lens=None):

@@ -734,6 +734,10 @@ typedef struct cbx_hift_f0_t {
     double* cum;
 } cbx_hift_f0_t;
 int cbx_hift_f0_source(const cbx_hift_f0_t* d, void* stream);
+/* cbx_hift_f0_source for a WINDOW of a longer signal (hifigan.py:201-231, 467-472: the reference keeps the excitation continuous across chunks by pasting the
+ * earlier chunk's source, `cache_source`; beyond it the phase has to continue too): cum_in = NULL or (B, 9) doubles, see cbx_hift_source_carry_f32.  NULL
+ * or zeros: the bits of cbx_hift_f0_source.  d->cum of this call stays readable: the next window takes its carry from it. */
+int cbx_hift_f0_source_carry(const cbx_hift_f0_t* d, const double* cum_in, void* stream);
 
 /* ResBlock of HiFT (hifigan.py:118-161): three (Snake, dilated conv, Snake, conv, + x) rounds; conv weights tap-major (C, k * C), weight_norm folded */
 typedef struct cbx_hift_resblock_t {
@@ -759,6 +763,19 @@ int cbx_hift_decode(const cbx_hift_t* d, void* stream);
 /* ---- HiFT source + (i)STFT (hifigan.py:201-231,267-283,396-410) ---- */
 int cbx_hift_source_f32(const float* f0, const float* phase, const float* noise, const float* lin_w, float lin_b,
                         float* s, double* frame_cum, int B, int T, int up, float sr, void* stream);
+/* SourceModuleHnNSF with a phase carry-in (hifigan.py:201-231, 467-472): cum_in = NULL or (B, 9) doubles, the cumulative cycles `cumsum(f0 (h + 1) / sr)` with
+ * which the frame scan of (b, h) starts in place of 0.  Run over frames [w0, T) of a signal with cum_in = frame_cum[:, :, w0] of the full-length call and the
+ * matching slices of f0 and noise, s is bit-identical to samples [up w0, up T) of the full-length source.  NULL or zeros: the bits of cbx_hift_source_f32. */
+int cbx_hift_source_carry_f32(const float* f0, const float* phase, const float* noise, const float* lin_w, float lin_b,
+                              float* s, double* frame_cum, const double* cum_in, int B, int T, int up, float sr, void* stream);
+/* End of a round of chunked synthesis, one launch for B utterances (the schedule is this build's own; it extends the reference's one streaming hook, the
+ * `cache_source` of hifigan.py:467-472).  wav (B, ld_wav): the round's waveform, wav[b][q] = absolute sample origin + q of utterance b.  emitted / end / avail
+ * [B] ints, absolute samples: out[b][i] = sample emitted[b] + i for i < end[b] - emitted[b] (out (B, max_new)); the first min(tail_len[b], fade) of them are
+ * tail_in[b][i] * (1 - ramp[i]) + new * ramp[i], rounded product by product as the torch expression is (no fma); tail_out[b][j] = sample end[b] + j for
+ * j < min(avail[b], end[b] + fade) - end[b] (tail_in, tail_out (B, fade), distinct buffers; ramp [fade]).  A row with end == emitted == avail is left alone.
+ * Positions outside the window read as 0 / are not written. */
+int cbx_stream_emit_f32(const float* wav, long ld_wav, long origin, const int* emitted, const int* end, const int* avail, const float* tail_in,
+                        const int* tail_len, const float* ramp, int fade, float* out, long max_new, float* tail_out, int B, void* stream);
 /* sample_lens[b] (or NULL): per-row signal length; the centre-reflect padding mirrors at that row's own end */
 int cbx_hift_stft_f32(const float* s, float* spec, const int* sample_lens, int B, long L, long ld_spec, void* stream);
 /* x[b][frame][0..8] log-magnitude, [9..17] phase pre-sin (conv_post output); fade_n>0 applies S3Gen trim_fade. */
