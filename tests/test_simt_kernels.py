@@ -135,6 +135,37 @@ def test_gpu_planes_bodies_on_the_emulator(emu, name, args):
     getattr(test_planes_gpu, name)(CPU, *args)
 
 
+# tests/test_softmax_stress_gpu.py (prescribed scores: rescale, "no key seen yet", masks, merges of partial (m, l, O) triples) at emulator sizes: every kernel of
+# that module at least once, the patterns asc / late_spike / two / neg / masked_spike, T <= 150, contexts <= 129
+_CTX = (1, 17, 65, 129)
+_STRESS = [("test_prefill_attention_stress", ("f32", "asc", [(150, 150, None), (150, 150, "causal")])), ("test_prefill_attention_stress", ("f32", "masked_spike", [(150, 150, "70"), (65, 65, "causal")])),
+           ("test_prefill_attention_stress", ("kv", "late_spike", [(33, 65, "causal"), (130, 150, None)])), ("test_prefill_attention_stress", ("kv", "masked_spike", [(130, 150, "causal")])),
+           ("test_prefill_attention_stress", ("p3", "asc", [(150, 150, None)])), ("test_prefill_attention_stress", ("p3", "two", [(150, 150, "70")])),
+           ("test_prefill_attention_stress", ("p6", "late_spike", [(150, 150, None)])), ("test_prefill_attention_stress", ("p6", "masked_spike", [(150, 150, "causal")])),
+           ("test_prefill_attention_stress", ("p16", "asc", [(150, 150, "causal")])), ("test_prefill_attention_stress", ("p16", "neg", [(65, 65, "0")])),
+           ("test_prefill_attention_stress", ("po", "two", [(130, 130, None)])), ("test_prefill_attention_stress", ("po", "masked_spike", [(150, 150, "70")])),
+           ("test_prefill_attention_stress", ("planes1", "asc", [(150, 150, "causal")])), ("test_prefill_attention_stress", ("planes2", "late_spike", [(150, 150, None)])),
+           ("test_prefill_attention_stress", ("planes3", "two", [(150, 150, "70")])), ("test_prefill_attention_stress", ("planes4", "asc", [(150, 150, None)])),
+           ("test_prefill_attention_stress", ("planes4", "masked_spike", [(150, 150, "70"), (65, 65, "0")])), ("test_prefill_attention_stress", ("planes5", "neg", [(130, 130, None)])),
+           ("test_prefill_attention_stress", ("planes6", "late_spike", [(150, 150, "1")])),
+           ("test_flash_relpos_stress", ("content", "asc", [(150, None)])), ("test_flash_relpos_stress", ("position", "two", [(150, "70")])),
+           ("test_flash_relpos_stress", ("position", "masked_spike", [(65, "1")])),
+           ("test_softmax_relpos_stress", ("content", "late_spike")), ("test_softmax_relpos_stress", ("position", "masked_spike")), ("test_softmax_rows_stress", ("two",)),
+           ("test_softmax_rows_stress", ("neg",)),
+           ("test_decode_attn_stress", (12, "asc", _CTX)), ("test_decode_attn_stress", (16, "masked_spike", _CTX)),
+           ("test_decode_attn_rope_stress", (12, "none", "asc", _CTX)), ("test_decode_attn_rope_stress", (16, "quarter", "late_spike", _CTX)),
+           ("test_decode_attn_rope_stress", (16, "identity", "two", _CTX)), ("test_decode_attn_rope_stress", (12, "quarter", "masked_spike", _CTX)),
+           ("test_decode_attn_rope_stress", (12, "none", "neg", _CTX, ((3, 4),), (1,))),
+           ("test_decode_attn_parts_stress", (12, "none", 2, 3, "two", _CTX)), ("test_decode_attn_parts_stress", (16, "quarter", 4, 8, "asc", _CTX)),
+           ("test_decode_attn_parts_stress", (16, "identity", 8, 2, "masked_spike", _CTX)), ("test_decode_attn_parts_stress", (12, "quarter", 4, 16, "late_spike", _CTX))]
+
+
+@pytest.mark.parametrize("name,args", _STRESS, ids=[f"{n}{list(a)}" for n, a in _STRESS])
+def test_softmax_stress_bodies_on_the_emulator(emu, name, args):
+    import test_softmax_stress_gpu
+    getattr(test_softmax_stress_gpu, name)(CPU, *args)
+
+
 @pytest.mark.parametrize("tile,persist", [(0, 1), (1, 0), (3, 8), (7, 1), (12, 0), (15, 8), (21, 1), (24, 8), (26, 0), (28, 1), (31, 8), (32, 1), (33, 0), (34, 8), (36, 1)])
 def test_gemm_planes_tiles_small(emu, tile, persist):
     """tests/test_planes_gpu.py::test_gemm_planes_linear_tiles at emulator-sized shapes: symmetric, loader-wave (21+) and 16-wave (26+) tile
