@@ -241,3 +241,108 @@ __device__ __forceinline__ int cbx_xcd_remap(int orig, int nwg) {
     const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
 }
+
+// ---- The token loop in C (include/cbx.h "handle-level entry points": cbx_t3_loop_*, cbx_gpt2_loop_*), once for both backbones.  STEP: the step descriptor type
+// (cbx_t3_step_t / cbx_gpt2_step_t); its host arrays are deep-copied -- `layers`, the sampler, and whatever adopt_arrays() of the derived handle owns besides
+// (cbx_gpt2_loop: `packed`).  The graph is what the Python engines capture through torch.cuda.graph: ONE call of step_fn.  On the SIMT emulator (tests/simt: no
+// graph API) the steps are issued one by one.  `who`: prefix of the error messages ("t3" / "gpt2").
+#include <type_traits>
+#include <vector>
+template <typename STEP>
+struct cbx_loop {
+    using layer_t = typename std::remove_cv<typename std::remove_pointer<decltype(STEP::layers)>::type>::type;
+    STEP step;
+    std::vector<layer_t> layers;
+    cbx_sampler_t sampler;
+    bool has_sampler = false;
+    std::vector<int> done_host;
+#ifndef CBX_SIMT_EMU
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+#endif
+    void adopt_arrays() {}  // (shadowed by a handle that owns further host arrays of its descriptor)
+};
+
+template <typename LOOP>
+static int cbx_loop_destroy(LOOP* h) {
+    if (!h) return 0;
+#ifndef CBX_SIMT_EMU
+    if (h->exec) (void)hipGraphExecDestroy(h->exec);
+    if (h->graph) (void)hipGraphDestroy(h->graph);
+#endif
+    delete h;
+    return 0;
+}
+
+template <typename LOOP, typename STEP>
+static int cbx_loop_create(const char* who, int (*step_fn)(const STEP*, void*), const STEP* step, LOOP** out) {
+    CBX_REQUIRE(step && out && step->layers && step->n_layers > 0, "%s_loop_create: null argument", who);
+    LOOP* h = new LOOP();
+    h->step = *step;
+    h->layers.assign(step->layers, step->layers + step->n_layers);
+    h->step.layers = h->layers.data();
+    h->adopt_arrays();
+    if (step->sampler) {
+        h->sampler = *step->sampler;
+        h->step.sampler = &h->sampler;
+        h->has_sampler = true;
+        h->done_host.assign(h->sampler.B > 0 ? h->sampler.B : 1, 0);
+    }
+#ifndef CBX_SIMT_EMU
+    // captured on a stream of the library's own: the caller's stream may be the legacy default stream, which cannot capture, and nothing executes during a
+    // capture anyway -- the graph is LAUNCHED on the caller's stream (cbx_loop_run)
+    hipStream_t st = nullptr;
+    const char* what = "hipStreamBeginCapture";
+    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+    int rc = 0;
+    if (e == hipSuccess) {
+        rc = step_fn(&h->step, st);
+        what = "hipStreamEndCapture";
+        e = hipStreamEndCapture(st, &h->graph);  // (always ended, also after a failed step: the stream must leave capture mode)
+        if (rc == 0 && e == hipSuccess && !h->graph) e = hipErrorUnknown;
+    }
+    if (st) (void)hipStreamDestroy(st);
+    if (rc == 0 && e == hipSuccess) {
+        what = "hipGraphInstantiate";
+        e = hipGraphInstantiate(&h->exec, h->graph, nullptr, nullptr, 0);
+    }
+    if (rc != 0 || e != hipSuccess) {  // the one unwind: the step's own error code and message win over the capture's
+        cbx_loop_destroy(h);
+        return rc ? rc : cbx_set_error((int)e, "%s_loop_create: %s: %s", who, what, hipGetErrorString(e));
+    }
+#endif
+    *out = h;
+    return 0;
+}
+
+template <typename LOOP, typename STEP>
+static int cbx_loop_run(const char* who, int (*step_fn)(const STEP*, void*), LOOP* h, int n_steps, int poll_every, void* stream, int* steps_run) {
+    CBX_REQUIRE(h && n_steps >= 0 && poll_every >= 0, "%s_loop_run: bad arguments", who);
+    CBX_REQUIRE(poll_every == 0 || h->has_sampler, "%s_loop_run: polling the done flags needs a sampler in the step descriptor", who);
+    int ran = 0;
+    for (int i = 0; i < n_steps; ++i) {
+#ifndef CBX_SIMT_EMU
+        const hipError_t e = hipGraphLaunch(h->exec, (hipStream_t)stream);
+        if (e != hipSuccess) return cbx_set_error((int)e, "%s_loop_run: hipGraphLaunch: %s", who, hipGetErrorString(e));
+#else
+        const int rc = step_fn(&h->step, stream);
+        if (rc) return rc;
+#endif
+        ++ran;
+        if (poll_every > 0 && ran % poll_every == 0 && i + 1 < n_steps) {  // the reference tests EOS on the host after every token (t3.py:366)
+#ifndef CBX_SIMT_EMU
+            hipError_t e2 = hipMemcpyAsync(h->done_host.data(), h->sampler.done, sizeof(int) * h->done_host.size(), hipMemcpyDeviceToHost, (hipStream_t)stream);
+            if (e2 == hipSuccess) e2 = hipStreamSynchronize((hipStream_t)stream);
+            if (e2 != hipSuccess) return cbx_set_error((int)e2, "%s_loop_run: fetching the done flags: %s", who, hipGetErrorString(e2));
+#else
+            for (size_t b = 0; b < h->done_host.size(); ++b) h->done_host[b] = h->sampler.done[b];
+#endif
+            bool all = true;
+            for (int d : h->done_host) all = all && d != 0;
+            if (all) break;
+        }
+    }
+    if (steps_run) *steps_run = ran;
+    return 0;
+}

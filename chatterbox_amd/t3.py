@@ -17,8 +17,8 @@ import os
 import torch
 
 from . import ops, weights
+from .decode import START_SPEECH, STOP_SPEECH, DecodeRuntime
 
-START_SPEECH, STOP_SPEECH = 6561, 6562
 START_TEXT, STOP_TEXT = 255, 0
 
 
@@ -59,21 +59,6 @@ def _slice_param(v, lo, hi):
     if torch.is_tensor(v) and v.dim():
         v = v.reshape(-1).tolist()
     return v[lo:hi] if isinstance(v, (list, tuple)) else v
-
-
-class _LoopHandle:
-    """Owns a cbx_t3_loop_t (or, with destroy="cbx_gpt2_loop_destroy", a cbx_gpt2_loop_t; destroyed with the state / geometry entry that holds it)."""
-
-    def __init__(self, h, destroy="cbx_t3_loop_destroy"):
-        self.h, self.destroy = h, destroy
-
-    def __del__(self):
-        try:
-            from ._lib import lib
-            if self.h:
-                getattr(lib, self.destroy)(self.h)
-        except Exception:
-            pass
 
 
 class VoicePrefixCache:
@@ -162,8 +147,17 @@ class VoicePrefixCache:
         del self._prefix_cache[self._PREFIX_KEEP:]
 
 
-class T3Engine(VoicePrefixCache):
+class T3Engine(DecodeRuntime, VoicePrefixCache):
     D, H, HD, F = 1024, 16, 64, 4096
+    # ---- the decode runtime of this backbone (decode.py).  Rows: utterance b is row b (conditional) and row B + b (CFG unconditional), rows = 2 B; a state is
+    # keyed by (B, max_ctx, max_steps, slot).
+    _SAMPLER_CFG, _SAMPLER_ORDER = 1, 0
+    _C_ENTRY = dict(step="cbx_t3_decode_step", create="cbx_t3_loop_create", run="cbx_t3_loop_run", destroy="cbx_t3_loop_destroy")
+    _ONE_SHOT_C_LOOP = True      # generate() runs its token loop through cbx_t3_loop_run wherever the C step serves the state (_use_c_step)
+    # thread_local: a capture on the T3-enqueue thread of synthesize_pipelined must not make the OTHER host thread's allocations / launches
+    # (flow + vocoder of the previous batch, on their own stream) illegal
+    _CAPTURE_THREAD_LOCAL = True
+    _ADVANCE_KEEPS_GRAPH = True  # advance() takes the C loop only while the state holds no torch-captured graph, and never captures one itself
     MAX_BATCH = 32  # utterances per device batch: 2 CFG rows each, decode GEMV serves M <= 64 rows
     # decode launch geometry: waves per 16-column tile (nw) / cross-workgroup K splits; *2 = the packed-operand (v2) path
     # qkv_tc / od_tc: output columns per workgroup of the q/k/v resp. the o / down projections (0: 16 resp. what half_tiles says; 12 puts
@@ -309,19 +303,8 @@ class T3Engine(VoicePrefixCache):
     def _hct(self):
         return int(self.tune.get("head_ct") or 0) if self.weight_dtype == "fp32" and self.D % 256 == 0 else 0
 
-    def _tiles(self):
-        """(q/k/v tile width, o / down tile width) of the current tune: 16, 12, 8 or 4 output columns per workgroup."""
-        tn = self.tune
-        od = tn.get("od_tc") or (8 if tn.get("half_tiles") and "wo_pk8" in self.layers[0] else 16)
-        return tn.get("qkv_tc") or 16, od
-
-    def _image(self, lw, name, tc):
-        """The packed decode image of layer weight `name` for `tc`-column tiles (packed on first use: never inside a stream capture,
-        generate() calls _prepare_tune() first)."""
-        key = f"{name}_pk" if tc == 16 else f"{name}_pk{tc}"
-        if key not in lw:
-            lw[key] = ops.pack_gemv_weight(lw[name], half_tile=tc, bf16=self.weight_dtype == "bf16")
-        return lw[key]
+    def _half_tiles(self):
+        return bool(self.tune.get("half_tiles")) and "wo_pk8" in self.layers[0]
 
     def _prepare_tune(self):
         if self.decode_mode != "v2":
@@ -349,10 +332,9 @@ class T3Engine(VoicePrefixCache):
             # the captured graph / C step descriptor of a state are kept PER GEOMETRY (alternating synthesize() and synthesize_pipelined()
             # re-captured the decode graph on every switch); they reference the state's own buffers and the weight images, which both outlive the switch
             cache = st.setdefault("geom_cache", {})
-            cache[old_key] = (st.get("graph"), st.pop("cstep", None))
-            st["graph"], cstep = cache.pop(new_key, (None, None))
-            if cstep is not None:
-                st["cstep"] = cstep
+            cache[old_key] = {k: st.pop(k) for k in ("graph", "cstep", "cloop") if k in st}
+            st["graph"] = None
+            st.update(cache.pop(new_key, {}))
             self._sync_geom(st)
         if getattr(self, "_co_res", False) and not getattr(self, "_co_switching", False):
             # a geometry adopted WHILE the co-resident form is on becomes the one co_resident(False) returns to (its co-resident keys aside)
@@ -391,7 +373,7 @@ class T3Engine(VoicePrefixCache):
         st = self._get_state(B, max_ctx, total + 1, slot)
         self._prepare_tune()
         st["graph"] = None
-        st.pop("cstep", None)
+        self._drop_c_step(st)
         st.pop("geom_cache", None)
         gen = torch.Generator(device=self.dev).manual_seed(20240229)
         for k in ("kc", "vc"):
@@ -440,7 +422,7 @@ class T3Engine(VoicePrefixCache):
         # the state the whole run ended in (a pure function of the seed and of the arithmetic)
         self.last_measure = dict(final_logits=st["logits"].clone(), out_tokens=st["out_tokens"].clone())
         st["graph"] = None
-        st.pop("cstep", None)
+        self._drop_c_step(st)
         return best, logits
 
     @ops.on_device
@@ -453,7 +435,7 @@ class T3Engine(VoicePrefixCache):
         st = self._get_state(B, max_ctx, 4, slot)
         self._prepare_tune()
         st["graph"] = None
-        st.pop("cstep", None)
+        self._drop_c_step(st)
         gen = torch.Generator(device=self.dev).manual_seed(20250922)
         for k in ("kc", "vc"):
             st[k].normal_(0.0, 0.5, generator=gen)
@@ -601,15 +583,24 @@ class T3Engine(VoicePrefixCache):
                 for i, lw in enumerate(self.layers):
                     self._layer_prefill(lw, xf, pws, S, rows, st["kc"][i], st["vc"][i], pos, crow)
 
+    def _layer_array(self, decode=False):
+        """A fresh cbx_t3_layer_t[L] of the row-major weights the prefill reads, or (decode) of the packed decode images of the current tile widths."""
+        from ._lib import T3Layer
+        arr = (T3Layer * self.L)()
+        qtc, odtc = self._tiles()
+        for i, lw in enumerate(self.layers):
+            ws = (self._image(lw, "wqkv", qtc), self._image(lw, "wo", odtc), lw["wgu_pk"], self._image(lw, "wd", odtc)) if decode else \
+                (lw["wqkv"], lw["wo"], lw["wgu"], lw["wd"])
+            arr[i].ln1, arr[i].ln2 = lw["ln1"].data_ptr(), lw["ln2"].data_ptr()
+            arr[i].wqkv, arr[i].wo, arr[i].wgu, arr[i].wd = (w.data_ptr() for w in ws)
+        return arr
+
     def _prefill_c(self, xf, ws, S, rows, st, pos, crow):
         """The prefill through cbx_t3_prefill (include/cbx.h): the launches of _layer_prefill x n_layers, sequenced in C."""
         import ctypes
-        from ._lib import T3Layer, T3Prefill, check, lib
+        from ._lib import T3Prefill, check, lib
         p = lambda t: t.data_ptr()
-        # built per call (30 x 6 pointers): a cached array would outlive a re-packed / re-loaded weight tensor (ADVICE r04)
-        arr = (T3Layer * self.L)()
-        for i, lw in enumerate(self.layers):
-            arr[i].ln1, arr[i].ln2, arr[i].wqkv, arr[i].wo, arr[i].wgu, arr[i].wd = p(lw["ln1"]), p(lw["ln2"]), p(lw["wqkv"]), p(lw["wo"]), p(lw["wgu"]), p(lw["wd"])
+        arr = self._layer_array()  # built per call (30 x 6 pointers): a cached array would outlive a re-packed / re-loaded weight tensor (ADVICE r04)
         d = T3Prefill()
         d.n_layers, d.rows, d.S, d.dim, d.ffn, d.n_heads, d.precision = self.L, rows, S, self.D, self.F, self.H, int(self.tune.get("prefill_prec") or 0)
         d.eps, d.attn_scale, d.layers = 1e-5, 0.125, arr
@@ -690,53 +681,16 @@ class T3Engine(VoicePrefixCache):
     def _use_c_step(self, st):
         return self.c_step and self.decode_mode == "v2" and st["rows"] <= 16 and self.tune["d_ks2"] in (1, 2, 4)
 
-    def _c_loop(self, st):
-        """The cbx_t3_loop_t of this state's current geometry (include/cbx.h: the decode step captured in a hipGraph by the LIBRARY, replayed by
-        cbx_t3_loop_run), created on first use; kept beside the step descriptor and dropped / cached with it (apply_variant)."""
-        import ctypes
-        from ._lib import check, lib
-        self._c_step_desc(st)
-        if len(st["cstep"]) == 3:
-            h = ctypes.c_void_p()
-            torch.cuda.synchronize()
-            check(lib.cbx_t3_loop_create(ctypes.byref(st["cstep"][0]), torch.cuda.current_stream().cuda_stream, ctypes.byref(h)), "cbx_t3_loop_create")
-            st["cstep"] = st["cstep"] + (_LoopHandle(h),)
-        return st["cstep"][3].h
-
-    def _run_c_loop(self, st, n_steps, poll_every):
-        import ctypes
-        from ._lib import check, lib
-        ran = ctypes.c_int(0)
-        check(lib.cbx_t3_loop_run(self._c_loop(st), int(n_steps), int(poll_every), torch.cuda.current_stream().cuda_stream, ctypes.byref(ran)), "cbx_t3_loop_run")
-        return int(ran.value)
-
-    def _decode_step_c(self, st):
-        """The same token step through the stage-level C entry point cbx_t3_decode_step (include/cbx.h): one ctypes call enqueues the
+    def _c_step_desc(self, st):
+        """Build (once per state and geometry) the cbx_t3_step_t of this state: st["cstep"] = (descriptor, layers, sampler).  One call of it enqueues the
         153 launches that _forward_decode_v2 + _sample issue one by one."""
         import ctypes
-        from ._lib import check, lib
-        self._c_step_desc(st)
-        check(lib.cbx_t3_decode_step(ctypes.byref(st["cstep"][0]), torch.cuda.current_stream().cuda_stream), "cbx_t3_decode_step")
-
-    def _c_step_desc(self, st):
-        """Build (once per state and geometry) the cbx_t3_step_t of this state: st["cstep"] = (descriptor, layers, sampler[, loop handle])."""
-        import ctypes
-        from ._lib import SamplerParams, T3Layer, T3Step
+        from ._lib import T3Step
         if "cstep" not in st:
             p = lambda t: t.data_ptr()
             ws, tn = st["dws"], self.tune
-            layers = (T3Layer * self.L)()
             qtc, odtc = self._tiles()
-            for i, lw in enumerate(self.layers):
-                layers[i].ln1, layers[i].ln2 = p(lw["ln1"]), p(lw["ln2"])
-                layers[i].wqkv, layers[i].wgu = p(self._image(lw, "wqkv", qtc)), p(lw["wgu_pk"])
-                layers[i].wo, layers[i].wd = p(self._image(lw, "wo", odtc)), p(self._image(lw, "wd", odtc))
-            sp = SamplerParams()
-            for k, v in dict(logits=st["logits"], ld=st["logits"].stride(0), V=self.V, B=st["B"], cfg=1, order=0, eos_token=STOP_SPEECH,
-                             dev_params=st["samp_dev"], seen=st["seen"], uniforms=st["uniforms"], max_steps=st["max_steps"], step=st["step"],
-                             out_tokens=st["out_tokens"], done=st["done"], n_generated=st["n_generated"], next_ids=st["next_ids"],
-                             next_pos_ids=st["next_pos_ids"], positions=st["positions"], ctx_lens=st["ctx_lens"]).items():
-                setattr(sp, k, v.data_ptr() if torch.is_tensor(v) else v)
+            layers, sp = self._layer_array(decode=True), self._sampler_desc(st)
             d = T3Step()
             d.n_layers, d.rows, d.dim, d.ffn, d.n_heads, d.vocab = self.L, st["rows"], self.D, self.F, self.H, self.V
             d.o_nw, d.gu_nw, d.d_nw, d.d_ksplit, d.eps, d.attn_scale = tn["o_nw2"], tn["gu_nw"], tn["d_nw2"], tn["d_ks2"], 1e-5, 0.125
@@ -757,15 +711,7 @@ class T3Engine(VoicePrefixCache):
             d.head_ct = self._hct()
             d.da_ws, d.da_cnt, d.da_pairs = ops._p(da.ws), ops._p(da.cnt), (da.max_pairs if da.ws is not None else 0)  # None: >= 128 (row, head) pairs never split
             st["cstep"] = (d, layers, sp)  # keep the host structures alive
-
-    def _sample(self, st):
-        # the sampling parameters are read from device memory (st["samp_dev"], one row per utterance): a request with other settings
-        # replays the SAME captured decode graph
-        ops.t3_sample(logits=st["logits"], ld=st["logits"].stride(0), V=self.V, B=st["B"], cfg=1, order=0, eos_token=STOP_SPEECH,
-                      dev_params=st["samp_dev"], seen=st["seen"],
-                      uniforms=st["uniforms"], max_steps=st["max_steps"], step=st["step"], out_tokens=st["out_tokens"],
-                      done=st["done"], n_generated=st["n_generated"], next_ids=st["next_ids"], next_pos_ids=st["next_pos_ids"],
-                      positions=st["positions"], ctx_lens=st["ctx_lens"])
+        return st["cstep"]
 
     # ------------------------------------------------------------------ state / workspaces
     def release_state(self, slot):
@@ -807,43 +753,6 @@ class T3Engine(VoicePrefixCache):
         self._state[key] = st
         return st
 
-    @ops.on_device
-    def advance(self, handle, n_steps):
-        """Enqueue up to `n_steps` further decode steps of an async generate() (replays of its captured graph; finished utterances are
-        no-ops inside the sampler).  Returns the number of steps enqueued."""
-        st = handle["st"]
-        n = max(0, min(int(n_steps), handle["max_new_tokens"] - handle["next_i"]))
-        if n and self.c_loop and self._use_c_step(st) and self.dev.type == "cuda" and st["graph"] is None:
-            self._run_c_loop(st, n, 0)
-            handle["next_i"] += n
-            return n
-        for _ in range(n):
-            if st["graph"] is not None:
-                st["graph"].replay()
-            else:
-                self._decode_step(st)
-        handle["next_i"] += n
-        return n
-
-    @ops.on_device
-    def peek(self, handle):
-        """Tokens sampled so far (synchronises with the launch stream): (list of B 1-D LongTensors, list of B done flags)."""
-        st, B = handle["st"], handle["B"]
-        # (order matters when the decode is still running on ANOTHER stream -- engine.synthesize_stream(overlap=True): the sampler writes token, count, then
-        # the done flag, so a done flag read FIRST implies the count read after it is final; a count that is still growing just means "not final yet")
-        done = st["done"].tolist()
-        n = st["n_generated"].tolist()
-        toks = st["out_tokens"].cpu()
-        return [toks[b, : n[b]].clone() for b in range(B)], [bool(d) for d in done]
-
-    @ops.on_device
-    def collect(self, handle):
-        """Fetch the tokens of an (async) generate() call.  Must run on the stream the call was enqueued on."""
-        st, B = handle["st"], handle["B"]
-        n = st["n_generated"].tolist()
-        toks = st["out_tokens"].cpu()
-        return [toks[b, : n[b]].clone() for b in range(B)]
-
     # ------------------------------------------------------------------ T3.inference
     @ops.on_device
     @torch.inference_mode()
@@ -859,11 +768,7 @@ class T3Engine(VoicePrefixCache):
         `advance(handle, n)` enqueues n more decode steps and `peek(handle)` fetches the tokens sampled so far."""
         dev, B = self.dev, len(text_tokens)
         assert B >= 1, "empty batch"
-        if uniforms is not None:
-            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
-            assert uniforms.numel() % B == 0 and uniforms.numel() // B >= max_new_tokens, \
-                f"uniforms must hold at least max_new_tokens={max_new_tokens} draws per utterance"
-            uniforms = uniforms.view(B, -1)
+        uniforms = self._uniform_rows(uniforms, B, max_new_tokens, f"max_new_tokens={max_new_tokens}")
         # {cfg_weight, temperature, min_p, top_p, rep_penalty, top_k, ban_token, ban_from} per utterance (cbx_sampler_t.dev_params); a wrong length raises here
         samp = sampler_rows(B, (("cfg_weight", cfg_weight), ("temperature", temperature), ("min_p", min_p), ("top_p", top_p),
                                 ("repetition_penalty", repetition_penalty), ("top_k", 0.0), ("ban_token", float(STOP_SPEECH if ban_eos else -1)),
@@ -894,15 +799,7 @@ class T3Engine(VoicePrefixCache):
         assert max_ctx <= self.max_pos, "context exceeds the RoPE table"
         st = self._get_state(B, max_ctx, max_new_tokens, slot)
         self._prepare_tune()
-        # {cfg_weight, temperature, min_p, top_p, rep_penalty, top_k, ban_token, ban_from} per utterance (cbx_sampler_t.dev_params)
-        st["samp_dev"].copy_(samp, non_blocking=True)
-        for k in ("seen", "step", "done", "n_generated", "out_tokens"):
-            st[k].zero_()
-        st["seen"][:, START_SPEECH] = 1
-        if uniforms is None:
-            st["uniforms"].uniform_(generator=generator)
-        else:
-            st["uniforms"].copy_(torch.as_tensor(uniforms, dtype=torch.float32).view(B, -1)[:, :max_new_tokens])
+        self._begin_request(st, samp, uniforms, max_new_tokens, generator)
 
         # ---- the missing prefixes of a mixed-voice batch: [conditioning] alone through the layers, once per distinct voice, into cache rows 0 .. n - 1
         missing = [j for j, e in enumerate(ents) if e is None]
@@ -952,48 +849,12 @@ class T3Engine(VoicePrefixCache):
         self._sample(st)
         if debug_logits:
             use_graph = False
-        c_loop = bool(use_graph and self.c_loop and self._use_c_step(st) and self.dev.type == "cuda" and max_new_tokens > 1)
-        if c_loop:
-            self._c_loop(st)  # (captures the step on first use: before the timed events below)
-        if use_graph and not c_loop and st["graph"] is None and max_new_tokens > 1:
-            torch.cuda.synchronize()
-            saved = {k: st[k].clone() for k in ("seen", "step", "done", "n_generated", "out_tokens", "next_ids",
-                                                "next_pos_ids", "positions", "ctx_lens", "logits")}
-            g = torch.cuda.CUDAGraph()
-            # thread_local: a capture on the T3-enqueue thread of synthesize_pipelined must not make the OTHER host thread's allocations / launches
-            # (flow + vocoder of the previous batch, on their own stream) illegal
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._decode_step(st)
-            for k, v in saved.items():  # the capture warm-up must not leak into the real sequence
-                st[k].copy_(v)
-            st["graph"] = g
-        ev = None
-        if self.time_decode:  # two HIP events around the decode loop on its launch stream (bench.py: in-run decode-step roofline)
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        n_replays = 0
+        c_loop = self._ready_step(st, use_graph)  # the library's token loop (one ctypes call), or the torch-captured graph replayed from here
         last = max_new_tokens if run_steps is None else max(1, min(max_new_tokens, int(run_steps)))
-        if c_loop and last > 1:  # the token loop in C: one ctypes call; EOS polled every `poll_every` steps unless the caller wants no synchronisation
-            n_replays = self._run_c_loop(st, last - 1, 0 if (ban_eos or async_mode) else poll_every)
-            if async_mode:
-                last = 1 + n_replays
-        for i in range(1, 1 if c_loop else last):
-            n_replays += 1
-            if use_graph and st["graph"] is not None:
-                st["graph"].replay()
-            elif debug_logits:  # forward and sampler split so that the raw logits of every step can be inspected
-                self._forward(st)
-                step_logits.append(st["logits"].clone())
-                self._sample(st)
-            else:
-                self._decode_step(st)
-            if not ban_eos and not async_mode and (i % poll_every == 0) and bool(st["done"].all()):
-                break
-        if ev is not None:
-            ev[1].record()
-            self.decode_events.append((ev[0], ev[1], n_replays, list(s0), rows))
+        # EOS is polled every `poll_every` steps unless the caller wants no synchronisation
+        ran = self._replay(st, last - 1, 0 if (ban_eos or async_mode) else poll_every, c_loop, use_graph, step_logits, event_tag=(list(s0), rows))
         if async_mode:  # everything is enqueued on the current stream; no host synchronisation happened
-            return dict(st=st, B=B, next_i=last, max_new_tokens=max_new_tokens)
+            return dict(st=st, B=B, next_i=1 + ran, max_new_tokens=max_new_tokens)
         out = self.collect(dict(st=st, B=B))
         if debug_logits:
             return out, torch.stack(step_logits)  # (steps, 2B, V)

@@ -10,13 +10,19 @@ import os
 import torch
 
 from . import ops
+from .decode import START_SPEECH, STOP_SPEECH, DecodeRuntime
 from .t3 import VoicePrefixCache, _slice_param, sampler_rows
 
-START_SPEECH, STOP_SPEECH = 6561, 6562
 
-
-class T3TurboEngine(VoicePrefixCache):
+class T3TurboEngine(DecodeRuntime, VoicePrefixCache):
     MAX_BATCH = 64
+    # ---- the decode runtime of this backbone (decode.py).  Rows: one per utterance (no CFG), rows = B; ONE live state, keyed by (B, max_ctx, max_steps).
+    _SAMPLER_CFG, _SAMPLER_ORDER = 0, 1  # Temperature -> TopK -> TopP -> RepetitionPenalty
+    _C_ENTRY = dict(step="cbx_gpt2_decode_step", create="cbx_gpt2_loop_create", run="cbx_gpt2_loop_run", destroy="cbx_gpt2_loop_destroy")
+    _ONE_SHOT_C_LOOP = False   # the one-shot generate() replays the torch-captured graph from Python; cbx_gpt2_loop_run serves advance() only (CBX_TURBO_CLOOP)
+    _ADVANCE_CAPTURES = True   # advance() of more than 16 rows (or with CBX_TURBO_CLOOP=0) captures the step with torch on first use
+    _COLLECT_STRIPS_EOS = True
+
     @ops.on_device
     def __init__(self, sd, device="cuda", n_layers=None):
         self.dev = dev = torch.device(device)
@@ -156,30 +162,11 @@ class T3TurboEngine(VoicePrefixCache):
             ops.gemv_row(g, lw["wpr"], x, bias=lw["bpr"], res=x)
         ops.gemv_row(x, self.head, st["logits"], bias=self.head_b, ln=self.lnf)
 
-    def _tiles(self):
-        """(c_attn tile width, attention / MLP projection tile width) of the current tune: 16, 12, 8 or 4 output columns per workgroup."""
-        tn = self.tune
-        return tn.get("qkv_tc") or 16, tn.get("od_tc") or (8 if tn.get("half_tiles") else 16)
-
-    def _image(self, lw, name, tc):
-        """Packed decode image of layer weight `name` for `tc`-column tiles (packed on first use; generate() calls _prepare_tune() before
-        anything is captured)."""
-        key = f"{name}_pk" if tc == 16 else f"{name}_pk{tc}"
-        if key not in lw:
-            lw[key] = ops.pack_gemv_weight(lw[name], half_tile=tc)
-        return lw[key]
-
     def _prepare_tune(self):
         qtc, odtc = self._tiles()
         assert qtc in (16, 12) and odtc in (16, 8, 4) and self.tune["d_ks"] in (1, 2, 4), f"decode tune {self.tune}"
         for lw in self.layers:
             self._image(lw, "wqkv", qtc), self._image(lw, "wo", odtc), self._image(lw, "wpr", odtc)
-
-    def _sample(self, st):
-        ops.t3_sample(logits=st["logits"], ld=st["logits"].stride(0), V=self.V, B=st["B"], cfg=0, order=1, eos_token=STOP_SPEECH,
-                      dev_params=st["samp_dev"], seen=st["seen"], uniforms=st["uniforms"], max_steps=st["max_steps"], step=st["step"],
-                      out_tokens=st["out_tokens"], done=st["done"], n_generated=st["n_generated"], next_ids=st["next_ids"],
-                      next_pos_ids=st["next_pos_ids"], positions=st["positions"], ctx_lens=st["ctx_lens"])
 
     def _forward(self, st):
         if self.decode_mode == "v2" and st["B"] <= 2 and self.tune.get("row_path") and self.D % 256 == 0:
@@ -201,21 +188,16 @@ class T3TurboEngine(VoicePrefixCache):
         return self.decode_mode == "v2" and st["B"] <= 16
 
     def _c_step_desc(self, st):
-        """Build (once per state and geometry) the cbx_gpt2_step_t of this state: st["cstep"] = (descriptor, layers, packed layers, sampler[, loop handle]).
+        """Build (once per state and geometry) the cbx_gpt2_step_t of this state: st["cstep"] = (descriptor, layers, packed layers, sampler).
         Every field is what _forward_decode_row / _forward_decode_v2 + _sample pass to their launches."""
         import ctypes
-        from ._lib import Gpt2Layer, Gpt2PackedLayer, Gpt2Step, SamplerParams
+        from ._lib import Gpt2PackedLayer, Gpt2Step
         if "cstep" in st:
             return st["cstep"]
         p = lambda t: t.data_ptr()
         ws, tn, D, L = st["dws"], self.tune, self.D, self.L
         row = self._row(st)
-        layers = (Gpt2Layer * L)()
-        for i, lw in enumerate(self.layers):
-            a = layers[i]
-            a.ln1_w, a.ln1_b, a.ln2_w, a.ln2_b = p(lw["ln1"][0]), p(lw["ln1"][1]), p(lw["ln2"][0]), p(lw["ln2"][1])
-            a.wqkv, a.bqkv, a.wo, a.bo, a.wfc, a.bfc, a.wpr, a.bpr = (p(lw[k]) for k in ("wqkv", "bqkv", "wo", "bo", "wfc", "bfc", "wpr", "bpr"))
-        packed = None
+        layers, packed = self._layer_array(), None
         d = Gpt2Step()
         d.n_layers, d.rows, d.dim, d.n_heads, d.vocab, d.row_path, d.eps, d.attn_scale = L, st["B"], D, self.H, self.V, int(row), 1e-5, 0.125
         d.layers = layers
@@ -244,54 +226,10 @@ class T3TurboEngine(VoicePrefixCache):
             da = st["da"]
             d.da_unroll, d.da_pipeline, d.da_split_min = da.unroll, da.pipeline, da.split_min
             d.da_ws, d.da_cnt, d.da_pairs = ops._p(da.ws), ops._p(da.cnt), (da.max_pairs if da.ws is not None else 0)
-        sp = SamplerParams()
-        for k, v in dict(logits=st["logits"], ld=st["logits"].stride(0), V=self.V, B=st["B"], cfg=0, order=1, eos_token=STOP_SPEECH,
-                         dev_params=st["samp_dev"], seen=st["seen"], uniforms=st["uniforms"], max_steps=st["max_steps"], step=st["step"],
-                         out_tokens=st["out_tokens"], done=st["done"], n_generated=st["n_generated"], next_ids=st["next_ids"],
-                         next_pos_ids=st["next_pos_ids"], positions=st["positions"], ctx_lens=st["ctx_lens"]).items():
-            setattr(sp, k, v.data_ptr() if torch.is_tensor(v) else v)
+        sp = self._sampler_desc(st)
         d.sampler = ctypes.pointer(sp)
         st["cstep"] = (d, layers, packed, sp)  # keep the host structures alive
         return st["cstep"]
-
-    def _decode_step_c(self, st):
-        """The same token step through the stage-level C entry point cbx_gpt2_decode_step: one ctypes call instead of 5 launches per layer + 2."""
-        import ctypes
-        from ._lib import check, lib
-        check(lib.cbx_gpt2_decode_step(ctypes.byref(self._c_step_desc(st)[0]), ops._stream()), "cbx_gpt2_decode_step")
-
-    def _c_loop(self, st):
-        """The cbx_gpt2_loop_t of this state's current geometry, created on first use and dropped with the descriptor (co_resident)."""
-        import ctypes
-        from ._lib import check, lib
-        from .t3 import _LoopHandle
-        self._c_step_desc(st)
-        if len(st["cstep"]) == 4:
-            h = ctypes.c_void_p()
-            torch.cuda.synchronize()
-            check(lib.cbx_gpt2_loop_create(ctypes.byref(st["cstep"][0]), ops._stream(), ctypes.byref(h)), "cbx_gpt2_loop_create")
-            st["cstep"] = st["cstep"] + (_LoopHandle(h, "cbx_gpt2_loop_destroy"),)
-        return st["cstep"][4].h
-
-    def _run_c_loop(self, st, n_steps, poll_every):
-        import ctypes
-        from ._lib import check, lib
-        ran = ctypes.c_int(0)
-        check(lib.cbx_gpt2_loop_run(self._c_loop(st), int(n_steps), int(poll_every), ops._stream(), ctypes.byref(ran)), "cbx_gpt2_loop_run")
-        return int(ran.value)
-
-    @torch.inference_mode()
-    def _capture(self, st):
-        """torch-captured graph of one token step (the one-shot generate()'s replay loop; chunked decoding of more than 16 rows)."""
-        torch.cuda.synchronize()
-        saved = {k: st[k].clone() for k in ("seen", "step", "done", "n_generated", "out_tokens", "next_ids", "next_pos_ids",
-                                            "positions", "ctx_lens", "logits")}
-        gr = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr):
-            self._decode_step(st)
-        for k, v in saved.items():
-            st[k].copy_(v)
-        st["graph"] = gr
 
     def co_resident(self, on):
         """The decode step beside the flow's co-resident forms (TurboEngine.synthesize_stream(overlap=True)).  The row path of 1 .. 2 rows keeps its launches
@@ -309,48 +247,7 @@ class T3TurboEngine(VoicePrefixCache):
         for st in self._state.values():
             if not self._row(st):
                 st["graph"] = None
-                st.pop("cstep", None)
-
-    @ops.on_device
-    def advance(self, handle, n_steps):
-        """Enqueue up to `n_steps` further token steps of an async generate() (finished rows are no-ops inside the sampler).  Returns the number of steps
-        enqueued.  No host synchronisation (the C loop runs with poll_every = 0)."""
-        st = handle["st"]
-        n = max(0, min(int(n_steps), handle["max_new_tokens"] - handle["next_i"]))
-        if n and self.c_loop and self._use_c_step(st) and self.dev.type == "cuda":
-            self._run_c_loop(st, n, 0)
-        elif n:
-            if self.dev.type == "cuda" and st["graph"] is None:
-                self._capture(st)
-            for _ in range(n):
-                if st["graph"] is not None:
-                    st["graph"].replay()
-                else:
-                    self._decode_step(st)
-        handle["next_i"] += n
-        return n
-
-    @ops.on_device
-    def peek(self, handle):
-        """Tokens sampled so far, EOS included (synchronises with the launch stream): (list of B 1-D LongTensors, list of B done flags).  The done flags are
-        read first (see T3Engine.peek)."""
-        st, B = handle["st"], handle["B"]
-        done = st["done"].tolist()
-        n = st["n_generated"].tolist()
-        toks = st["out_tokens"].cpu()
-        return [toks[b, : n[b]].clone() for b in range(B)], [bool(d) for d in done]
-
-    @ops.on_device
-    def collect(self, handle):
-        """The tokens of an (async) generate() call as generate() returns them: without a trailing EOS.  Must run on the stream the call was enqueued on."""
-        st, B = handle["st"], handle["B"]
-        n = st["n_generated"].tolist()
-        toks = st["out_tokens"].cpu()
-        out = []
-        for b in range(B):
-            t = toks[b, : n[b]]
-            out.append(t[:-1].clone() if n[b] and int(t[-1]) == STOP_SPEECH else t.clone())
-        return out
+                self._drop_c_step(st)
 
     def _get_state(self, B, max_ctx, max_steps):
         key = (B, max_ctx, max_steps)
@@ -379,16 +276,22 @@ class T3TurboEngine(VoicePrefixCache):
         self._state[key] = st
         return st
 
+    def _layer_array(self):
+        """A fresh cbx_gpt2_layer_t[L]: LayerNorm parameters, row-major weights and biases of every layer (the prefill and the row path read these)."""
+        from ._lib import Gpt2Layer
+        p = lambda t: t.data_ptr()
+        arr = (Gpt2Layer * self.L)()
+        for a, lw in zip(arr, self.layers):
+            a.ln1_w, a.ln1_b, a.ln2_w, a.ln2_b = p(lw["ln1"][0]), p(lw["ln1"][1]), p(lw["ln2"][0]), p(lw["ln2"][1])
+            a.wqkv, a.bqkv, a.wo, a.bo, a.wfc, a.bfc, a.wpr, a.bpr = (p(lw[k]) for k in ("wqkv", "bqkv", "wo", "bo", "wfc", "bfc", "wpr", "bpr"))
+        return arr
+
     def _prefill_c(self, xf, h, qkv, att, g, pos, crow, st, B, S, prefix):
         """The prefill through cbx_gpt2_prefill (include/cbx.h, ABI v16): the nine launches per layer of generate()'s Python sequence, issued in C."""
         import ctypes
-        from ._lib import Gpt2Layer, Gpt2Prefill, check, lib
+        from ._lib import Gpt2Prefill, check, lib
         p = lambda t: t.data_ptr()
-        arr = (Gpt2Layer * self.L)()  # built per call: a cached array would outlive a re-loaded weight tensor
-        for i, lw in enumerate(self.layers):
-            a = arr[i]
-            a.ln1_w, a.ln1_b, a.ln2_w, a.ln2_b = p(lw["ln1"][0]), p(lw["ln1"][1]), p(lw["ln2"][0]), p(lw["ln2"][1])
-            a.wqkv, a.bqkv, a.wo, a.bo, a.wfc, a.bfc, a.wpr, a.bpr = (p(lw[k]) for k in ("wqkv", "bqkv", "wo", "bo", "wfc", "bfc", "wpr", "bpr"))
+        arr = self._layer_array()  # built per call: a cached array would outlive a re-loaded weight tensor
         d = Gpt2Prefill()
         d.n_layers, d.rows, d.S, d.prefix, d.dim, d.n_heads, d.eps, d.attn_scale, d.layers = self.L, B, S, prefix, self.D, self.H, 1e-5, 0.125, arr
         d.x, d.h, d.qkv, d.att, d.g, d.positions, d.cache_rows, d.kc, d.vc = p(xf), p(h), p(qkv), p(att), p(g), p(pos), p(crow), p(st["kc"]), p(st["vc"])
@@ -437,11 +340,7 @@ class T3TurboEngine(VoicePrefixCache):
         # sampling parameters live in device memory (cbx_sampler_t.dev_params), one row per utterance; a wrong length raises here
         samp = sampler_rows(B, (("cfg_weight", 0.0), ("temperature", temperature), ("min_p", 0.0), ("top_p", top_p), ("repetition_penalty", repetition_penalty),
                                 ("top_k", top_k), ("ban_token", float(STOP_SPEECH if ban_eos else -1)), ("ban_from", float(ban_from))))
-        if uniforms is not None:
-            uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
-            assert uniforms.numel() % B == 0 and uniforms.numel() // B >= max_gen_len + 1, \
-                f"uniforms must hold at least max_gen_len + 1 = {max_gen_len + 1} draws per utterance"
-            uniforms = uniforms.view(B, -1)
+        uniforms = self._uniform_rows(uniforms, B, max_gen_len + 1, f"max_gen_len + 1 = {max_gen_len + 1}")
         if B > self.MAX_BATCH:  # one row per utterance (no CFG); the decode GEMV serves M <= 64 rows
             assert not (debug_logits or async_mode), "sub-batching is only defined for the plain token path"
             out = []
@@ -462,14 +361,7 @@ class T3TurboEngine(VoicePrefixCache):
         st = self._get_state(B, max_ctx, n_samples)
         if self.decode_mode == "v2":
             self._prepare_tune()
-        st["samp_dev"].copy_(samp, non_blocking=True)  # (no graph re-capture when a request changes them)
-        for k in ("seen", "step", "done", "n_generated", "out_tokens"):
-            st[k].zero_()
-        st["seen"][:, START_SPEECH] = 1  # the first processor call sees ids = [start token] (t3.py:428)
-        if uniforms is None:
-            st["uniforms"].uniform_(generator=generator)
-        else:
-            st["uniforms"].copy_(torch.as_tensor(uniforms, dtype=torch.float32).view(B, -1)[:, :n_samples])
+        self._begin_request(st, samp, uniforms, n_samples, generator)  # (the first processor call sees ids = [start token]: t3.py:428)
 
         # ---- prefill: [speaker | prompt-token embeddings | text | start-speech] + wpe (prepare_input_embeds, t3.py:102-130,407-423)
         # The 1 + n_prompt conditioning positions see only themselves (causal) and carry absolute positions: with their K / V cached (VoicePrefixCache) only the
@@ -532,40 +424,7 @@ class T3TurboEngine(VoicePrefixCache):
             return handle
         if debug_logits:
             use_graph = False
-        if use_graph and st["graph"] is None and n_samples > 1:
-            torch.cuda.synchronize()
-            saved = {k: st[k].clone() for k in ("seen", "step", "done", "n_generated", "out_tokens", "next_ids", "next_pos_ids",
-                                                "positions", "ctx_lens", "logits")}
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
-                self._decode_step(st)
-            for k, v in saved.items():
-                st[k].copy_(v)
-            st["graph"] = gr
-        ev = None
-        if self.time_decode:  # two HIP events around the decode loop on its launch stream (bench.py: in-run decode-step roofline)
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        n_replays = 0
-        for i in range(1, n_samples):
-            n_replays += 1
-            if use_graph and st["graph"] is not None:
-                st["graph"].replay()
-            elif debug_logits:
-                self._forward(st)
-                step_logits.append(st["logits"].clone())
-                self._sample(st)
-            else:
-                self._decode_step(st)
-            if not ban_eos and (i % poll_every == 0) and bool(st["done"].all()):
-                break
-        if ev is not None:
-            ev[1].record()
-            self.decode_events.append((ev[0], ev[1], n_replays, list(s0), B))
-        n = st["n_generated"].tolist()
-        toks = st["out_tokens"].cpu()
-        out = []
-        for b in range(B):
-            t = toks[b, : n[b]]
-            out.append(t[:-1].clone() if n[b] and int(t[-1]) == STOP_SPEECH else t.clone())
+        c_loop = self._ready_step(st, use_graph)  # (False: _ONE_SHOT_C_LOOP; the step is captured by torch on first use)
+        self._replay(st, n_samples - 1, 0 if ban_eos else poll_every, c_loop, use_graph, step_logits, event_tag=(list(s0), B))
+        out = self.collect(dict(st=st, B=B))
         return (out, torch.stack(step_logits)) if debug_logits else out

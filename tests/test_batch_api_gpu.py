@@ -85,7 +85,7 @@ def test_t3_per_utterance_sampling_params_in_one_batch(dev):
     s1 = dict(temperature=0.8, cfg_weight=0.5, repetition_penalty=1.2, min_p=0.05, top_p=1.0)
     s2 = dict(temperature=1.3, cfg_weight=0.2, repetition_penalty=1.0, min_p=0.0, top_p=0.9)
     a = T3Engine(sd, dev)
-    captured = lambda: (lambda st: st["cstep"][3] if a.c_loop else st["graph"])(next(iter(a._state.values())))
+    captured = lambda: (lambda st: st["cloop"] if a.c_loop else st["graph"])(next(iter(a._state.values())))
     a.generate(synth.t3_cond(), tt, **kw, **s1)
     g1 = captured()
     mixed = a.generate(synth.t3_cond(), tt, **kw, **{k: [s1[k], s2[k]] for k in s1})

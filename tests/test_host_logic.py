@@ -611,11 +611,16 @@ def test_every_kernel_entry_point_is_named_by_a_kernel_level_test():
             wrappers.setdefault(e, set()).add(fn)
     for e, ws in wrappers.items():  # linear() / conv1d() / bmm() call gemm(), ...
         ws |= {fn for fn, body in bodies.items() if any(re.search(rf"(?<![\w.]){w}\(", body) for w in ws if w != fn)}
-    for e, (mod, method) in {"cbx_t3_loop_create": ("t3", "_c_loop"), "cbx_gpt2_loop_create": ("t3_turbo", "_c_loop")}.items():
-        eng = open(os.path.join(ROOT, "chatterbox_amd", mod + ".py")).read()
-        body = re.search(rf"^    def {method}\(.*?(?=^    def |\Z)", eng, re.M | re.S).group(0)
-        assert f"lib.{e}(" in body
-        wrappers.setdefault(e, set()).add("." + method)
+    # the two constructors are called by name from ONE method, DecodeRuntime._c_loop (decode.py), which neither engine overrides; each engine names its own in _C_ENTRY
+    from chatterbox_amd.decode import DecodeRuntime
+    from chatterbox_amd.t3 import T3Engine
+    from chatterbox_amd.t3_turbo import T3TurboEngine
+    rt = open(os.path.join(ROOT, "chatterbox_amd", "decode.py")).read()
+    body = re.search(r"^    def _c_loop\(.*?(?=^    def |\Z)", rt, re.M | re.S).group(0)
+    assert 'getattr(lib, self._C_ENTRY["create"])(' in body and rt.count('_C_ENTRY["create"])(') == 1
+    for e, cls in {"cbx_t3_loop_create": T3Engine, "cbx_gpt2_loop_create": T3TurboEngine}.items():
+        assert cls._C_ENTRY["create"] == e and cls._c_loop is DecodeRuntime._c_loop
+        wrappers.setdefault(e, set()).add("._c_loop")
     files = sorted(f for pat in _KERNEL_LEVEL_MODULES for f in glob.glob(os.path.join(ROOT, "tests", pat + ".py")))
     assert len(files) >= len(_KERNEL_LEVEL_MODULES)
     text = "\n".join(open(f).read() for f in files)

@@ -437,19 +437,64 @@ def test_t3_decode_step_c_entry_point_and_tile_variants(emu, tiny_llama, qtc, od
     assert torch.equal(a["positions"], torch.tensor([21, 32, 21, 32], dtype=torch.int32))
 
 
-@pytest.mark.parametrize("tune,c_step", [(dict(qkv_tc=12, od_tc=4, d_ks2=1), True), (dict(qkv_tc=12, od_tc=4, d_ks2=1, d_nw2=8), False)])  # the default tune: the e2e test below
-def test_t3_engine_decode_step_code_on_the_emulator(emu, tiny_llama, tune, c_step, monkeypatch):
-    """chatterbox_amd/t3.py's own decode-step code (T3Engine._prepare_tune / _tiles / _image / _forward_decode_v2 / _decode_step_c) driven on
-    the emulator: an engine object assembled around the tiny model, one token step, against the hand-written launch sequence above."""
+def _tiny_engine(m, tune, c_step):
+    """A T3Engine object assembled around the tiny model (no checkpoint, no conditioning encoder: the decode step's own attributes)."""
     from chatterbox_amd.t3 import T3Engine
-    m = tiny_llama
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: type("S", (), {"cuda_stream": None})())
     eng = T3Engine.__new__(T3Engine)
     eng.dev, eng.L, eng.V, eng.weight_dtype, eng.decode_mode, eng.c_step = CPU, m["L"], m["V"], "fp32", "v2", c_step
     eng.layers = [dict(ln1=w["ln1"], ln2=w["ln2"], wqkv=w["wqkv"], wo=w["wo"], wd=w["wd"], wgu_pk=w["wgu_pk"], wqkv_pk=w["wqkv_pk16"], wo_pk=w["wo_pk16"],
                        wd_pk=w["wd_pk16"], wo_pk8=w["wo_pk8"], wd_pk8=w["wd_pk8"]) for w in m["lw"]]
     eng.norm, eng.head_pk, eng.speech_emb, eng.speech_pos, eng.cos, eng.sin = m["norm"], m["head_pk"], m["emb"], m["pos_emb"], m["cos"], m["sin"]
     eng.tune, eng._state, eng.knobs = dict(T3Engine._TUNE, **tune), {}, T3Engine._env_knobs()
+    return eng
+
+
+def test_t3_token_loop_equals_python_steps_on_the_emulator(emu, tiny_llama):
+    """cbx_t3_loop_run of n steps == n token steps issued launch by launch from Python (T3Engine._forward_decode_v2 + _sample on the default geometry: split-K
+    q/k/v, column-tile head) from the same mid-utterance state of ONE utterance (its CFG row pair) -- logits, sampler state and KV cache bit for bit;
+    *steps_run reports the steps issued, and with every utterance flagged done a polled run stops at its first poll (the Llama twin of
+    tests/test_turbo_stream_host.py::test_gpt2_token_loop_equals_python_steps_on_the_emulator)."""
+    import ctypes
+    m = tiny_llama
+    eng = _tiny_engine(m, {}, False)  # c_step off: _decode_step is the Python launch sequence; the loop goes through cbx_t3_decode_step whatever it says
+    eng._prepare_tune()
+    ref_st, _ = _tiny_state(m)
+    st = eng._get_state(1, m["maxp"], 8)
+    assert st["rows"] == 2 and not eng._use_c_step(st)
+    pair = [0, m["B"]]  # utterance 0 of the 2-utterance reference state: its conditional and its unconditional row
+    for k in ("kc", "vc"):
+        st[k].copy_(ref_st[k][:, pair])
+    for k in ("next_ids", "next_pos_ids", "positions", "ctx_lens"):
+        st[k].copy_(ref_st[k][pair])
+    st["uniforms"].copy_(ref_st["uniforms"][:1])
+    st["samp_dev"].copy_(ref_st["samp"][:1])
+    tensors = lambda: [(d, k) for d in (st, st["dws"]) for k, v in d.items() if torch.is_tensor(v)]
+    snap = [(d, k, d[k].clone()) for d, k in tensors()]
+    for _ in range(3):
+        eng._decode_step(st)
+    keys = ("logits", "out_tokens", "n_generated", "next_ids", "next_pos_ids", "positions", "ctx_lens", "kc", "vc", "seen", "step", "done")
+    want = {k: st[k].clone() for k in keys}
+    assert torch.isfinite(want["logits"]).all() and float(want["logits"].abs().max()) > 0 and int(want["n_generated"].min()) == 3
+    assert "cstep" not in st and "cloop" not in st
+    for d, k, v in snap:
+        d[k].copy_(v)
+    assert eng._run_c_loop(st, 3, 0) == 3
+    for k in keys:
+        assert torch.equal(want[k], st[k]), f"cbx_t3_loop_run differs from the Python steps in {k}"
+    # the EOS poll: everything flagged done, 12 steps asked for with a poll every 4 -> the loop stops after the first poll
+    st["done"].fill_(1)
+    ran = ctypes.c_int(-1)
+    assert emu.cbx_t3_loop_run(eng._c_loop(st), 12, 4, None, ctypes.byref(ran)) == 0, emu.cbx_last_error()
+    assert ran.value == 4 and torch.equal(st["step"], want["step"]), "finished utterances are no-ops in the sampler; the loop ended at the first poll"
+
+
+@pytest.mark.parametrize("tune,c_step", [(dict(qkv_tc=12, od_tc=4, d_ks2=1), True), (dict(qkv_tc=12, od_tc=4, d_ks2=1, d_nw2=8), False)])  # the default tune: the e2e test below
+def test_t3_engine_decode_step_code_on_the_emulator(emu, tiny_llama, tune, c_step, monkeypatch):
+    """chatterbox_amd/t3.py's own decode-step code (T3Engine._prepare_tune / _tiles / _image / _forward_decode_v2 / _decode_step_c) driven on
+    the emulator: an engine object assembled around the tiny model, one token step, against the hand-written launch sequence above."""
+    m = tiny_llama
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: type("S", (), {"cuda_stream": None})())
+    eng = _tiny_engine(m, tune, c_step)
     qtc, odtc = eng._tiles()
     assert (qtc, odtc) == ((12, 4) if tune else (16, 8))
     eng._prepare_tune()
