@@ -22,6 +22,13 @@ CBX_TRC_TU
 // RMS: LlamaRMSNorm of the x operand folded in: the lanes multiply their x values by norm_w[k] on the way to the MFMA, accumulate
 // sum_k x^2 per row as a by-product (every workgroup reads whole rows), and the per-row rstd -- a scalar that factors out of the
 // contraction -- is applied in the epilogue:  out[m][n] = rstd[m] * sum_k (x[m][k] * norm_w[k]) * W[n][k].  (ksplit must be 1.)
+// LayerNorm form (ln_cw / ln_cb, GPT-2): the row is SHIFTED by a per-row pivot c[m] on the way in -- x' = x - c feeds the MFMAs and the
+// two running sums -- so that neither the one-pass variance nor the mean term cancels when |mean| >> std (a residual stream with a large
+// common offset):  mean' = sum_k x' / K (= mean - c),  rstd = rsqrt(sum_k x'^2 / K - mean'^2 + eps),
+//   out[m][n] = rstd[m] * (sum_k (x'[m][k] * norm_w[k]) * W[n][k] - mean'[m] * ln_cw[n]) + ln_cb[n].
+// c[m] = the median of channels 0, K/2 and K - 1 of the (summed) row (gemv_ln_pivot): a value of the row itself, so x - c is exact
+// wherever the row's spread is small against its offset, and one outlier channel cannot become the pivot.  The form is a template
+// parameter (LN): the RMSNorm kernels carry none of it.
 // NP > 0 (RMS variants, <= 16 rows): the x operand is x + sum_{j < NP} xpart[j] -- the split-K partial images of the PRODUCING
 // projection are reduced (fixed order) on the way to the MFMA instead of by a separate kernel; workgroup 0 also writes the sum
 // (the new residual stream) to x_out.  Every workgroup re-reads the NP + 1 images from L2: NP * 64 KiB extra per workgroup,
@@ -38,19 +45,36 @@ __device__ __forceinline__ f32x4 bf16x4_widen(const u32x4 u, int h) {
 // cbx_gemv_t.half_tile -> output columns per workgroup (0: 16; 1 or 8: 8; 12; 4)
 __host__ __device__ __forceinline__ int gemv_tile_cols(int half_tile) { return half_tile == 0 ? 16 : half_tile == 1 ? 8 : half_tile; }
 
+// LayerNorm form: the pivot of row `r` (< 16) of the packed x image `x` ([K/32][2][64][4], one 16-row tile) plus its NP partial images --
+// the median of channels 0, K/2 and K - 1 of x + sum_j xpart[j], each summed in the order of the K loop (the value the loop itself forms).
+template <int NP>
+__device__ __forceinline__ float gemv_ln_pivot(const float* __restrict__ x, const float* __restrict__ xpart, long xpart_stride, int K, int r) {
+    float v[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int k = i == 0 ? 0 : i == 1 ? K >> 1 : K - 1;
+        const long o = ((long)(k >> 5) * 2 + ((k >> 2) & 1)) * 256 + ((((k >> 3) & 3) << 4) + r) * 4 + (k & 3);
+        v[i] = x[o];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) v[i] += xpart[(long)j * xpart_stride + o];
+    }
+    return fmaxf(fminf(v[0], v[1]), fminf(fmaxf(v[0], v[1]), v[2]));
+}
+
 // D8: eight K blocks (instead of four) requested before the first MFMA -- for a wave whose K slice is >= 256 deep (the down projection
 // without split-K partials: K = 4096 over 16 waves) the whole slice is then ONE batch of loads instead of two dependent ones.
 // D2 (round 5, cbx_gemv_t.flags & CBX_GEMV_SHALLOW): TWO K blocks per batch -- the SwiGLU launch then needs <= 128 VGPRs instead of 162, so its workgroups (2 waves per
 // SIMD) fit on a CU beside a workgroup of another stream that leaves half of the register file free (the throughput schedule: profiles/r05_overlap_*).
 // Same loads, same MFMA order: bit-identical results.
-template <int MT, int NW, bool SWIGLU, bool PK, bool XPK, bool RMS, int NP, bool WB = false, bool D8 = false, bool D2 = false>
+template <int MT, int NW, bool SWIGLU, bool PK, bool XPK, bool RMS, int NP, bool WB = false, bool D8 = false, bool D2 = false, bool LN = false>
 __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
     __builtin_amdgcn_s_setprio(3);  // decode-step kernels are latency-bound and issue little: beside a co-resident workgroup of another stream (the throughput schedule, profiles/r05_overlap_*) their waves go first at the SIMD's issue arbiter; alone on the CU it changes nothing
     static_assert(NP == 0 || (RMS && MT == 1), "partial-sum operand: RMS variant, one row tile");
     static_assert(!WB || (PK && XPK), "bf16 weights: packed operands only");
+    static_assert(!LN || (RMS && !SWIGLU), "LayerNorm form: the norm-folded packed kernel, no swiglu");
     __shared__ __attribute__((aligned(16))) float red[(SWIGLU ? 2 : 1) * NW * MT * 256];
     __shared__ float ssq[RMS ? NW * MT * 16 : 1];
-    __shared__ float ssx[RMS ? NW * MT * 16 : 1];  // row sums (LayerNorm form only)
+    __shared__ float ssx[LN ? NW * MT * 16 : 1];   // row sums (LayerNorm form)
     CBX_TRC_DECL;
     CBX_TRC_STAMP(0);  // entry
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -114,14 +138,22 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
     }
 
     const float* nwp = RMS ? p.norm_w + kbeg + 8 * q : nullptr;  // this lane's k indices: kbeg + 32*blk + 8*q + 4*h + s
-    float ss[MT], sx[MT];
+    float ss[MT];
+    [[maybe_unused]] float sx[MT];  // row sums (LayerNorm form)
     f32x4 acc[MT], acc2[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
         acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         ss[t] = 0.f;
-        sx[t] = 0.f;
+        if constexpr (LN) sx[t] = 0.f;
+    }
+    // LayerNorm form: this lane's row pivot (header comment); its loads go out before the first weight batch
+    [[maybe_unused]] float piv[MT];
+    if constexpr (LN) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+            piv[t] = gemv_ln_pivot<NP>(p.x + (long)t * (p.K >> 5) * 512, NP > 0 ? p.xpart + (long)t * (p.K >> 5) * 512 : nullptr, p.xpart_stride, p.K, xok[t] ? c : 0);
     }
     // ---- epilogue operands requested FIRST (opt-in: cbx_gemv_t.flags & CBX_GEMV_PRE_EPI).  The element(s) a thread finishes after the reduction are known now; its
     // residual, bias and LayerNorm-fold constants do not depend on the contraction, so their loads go out with the first weight batch instead
@@ -159,7 +191,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
         }
     }
     if constexpr (RMS) {
-        if (PRE && p.ln_cw) {
+        if (LN && PRE) {
 #pragma unroll
             for (int j = 0; j < EIT; ++j) e_cw[j] = p.ln_cw[e_n[j]], e_cb[j] = p.ln_cb[e_n[j]];
         }
@@ -228,10 +260,11 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
                         if (p.x_out && blockIdx.x == 0 && on[d] && xok[0])  // the reduced residual stream, same packed address as x (pad rows stay as allocated: zero)
                             cbx_store_out4(p.x_out + (xp[0] - p.x) + (it0 + d) * 512 + h * 256, xq);
                     }
+                    if constexpr (LN) xq -= piv[t];  // after x_out took the unshifted sum
                     xq = (on[d] && xok[t]) ? xq : zero4;
                     if constexpr (RMS) {
                         ss[t] += (xq[0] * xq[0] + xq[1] * xq[1]) + (xq[2] * xq[2] + xq[3] * xq[3]);
-                        sx[t] += (xq[0] + xq[1]) + (xq[2] + xq[3]);
+                        if constexpr (LN) sx[t] += (xq[0] + xq[1]) + (xq[2] + xq[3]);
                         xq *= nv[d][h];
                     }
 #pragma unroll
@@ -271,12 +304,12 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
             float v = ss[t];
             v += cbx_xor_lane<16>(v);
             v += cbx_xor_lane<32>(v);
-            float u = sx[t];
-            u += cbx_xor_lane<16>(u);
-            u += cbx_xor_lane<32>(u);
-            if (q == 0) {
-                ssq[(w * MT + t) * 16 + c] = v;
-                ssx[(w * MT + t) * 16 + c] = u;
+            if (q == 0) ssq[(w * MT + t) * 16 + c] = v;
+            if constexpr (LN) {
+                float u = sx[t];
+                u += cbx_xor_lane<16>(u);
+                u += cbx_xor_lane<32>(u);
+                if (q == 0) ssx[(w * MT + t) * 16 + c] = u;
             }
         }
     }
@@ -299,7 +332,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
             float sq = 0.f;
 #pragma unroll
             for (int ww = 0; ww < NW; ++ww) sq += ssq[(ww * MT + t) * 16 + row];
-            if (p.ln_cw) {  // LayerNorm form (GPT-2): y = (x - mean) rstd w + b  =>  out = rstd (acc - mean cw[n]) + cb[n]
+            if constexpr (LN) {  // LayerNorm form (GPT-2) on the shifted row x' = x - c (header comment): sq, su and v are sums over x', mean = mean(x) - c
                 float su = 0.f;
 #pragma unroll
                 for (int ww = 0; ww < NW; ++ww) su += ssx[(ww * MT + t) * 16 + row];
@@ -342,13 +375,13 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
 // ssq_out[ks][m] (written by column group 0): rstd factors out of the contraction, so the CONSUMER -- the decode attention, which reads 192
 // values per workgroup -- adds the ksplit partials in fixed order and applies rstd = rsqrt(sum_ks ssq / K + eps).  ksplit == 1: rstd in the
 // epilogue as above.  Same MFMA, same fixed-order LDS reduction over the 8 waves; deterministic.
-template <int CT, int NP, int DEPTH>
+template <int CT, int NP, int DEPTH, bool LN = false>
 __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
     __builtin_amdgcn_s_setprio(3);  // decode-step kernels are latency-bound and issue little: beside a co-resident workgroup of another stream (the throughput schedule, profiles/r05_overlap_*) their waves go first at the SIMD's issue arbiter; alone on the CU it changes nothing
     constexpr int NW = 8;
     __shared__ __attribute__((aligned(16))) float red[NW * CT * 256];
     __shared__ float ssq[NW * 16];
-    __shared__ float ssx[NW * 16];  // row sums (LayerNorm form: ln_cw / ln_cb, ksplit == 1)
+    __shared__ float ssx[LN ? NW * 16 : 1];  // row sums (LayerNorm form: ln_cw / ln_cb, ksplit == 1)
     CBX_TRC_DECL;
     CBX_TRC_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -371,8 +404,12 @@ __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
     f32x4 acc[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float ss = 0.f, sx = 0.f;
+    float ss = 0.f;
+    [[maybe_unused]] float sx = 0.f;  // row sum (LayerNorm form)
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    // LayerNorm form: this lane's row pivot, the expression of gemv_kernel
+    [[maybe_unused]] float piv = 0.f;
+    if constexpr (LN) piv = gemv_ln_pivot<NP>(p.x, p.xpart, p.xpart_stride, p.K, xok ? (lane & 15) : 0);
     // DEPTH = K blocks requested per batch (picked by the host so that it divides the wave's block count: an idle slot would re-read a block,
     // i.e. spend the very per-CU bytes this form saves; registers: DEPTH * 2 * (CT + NP + 2) float4)
     for (int it0 = 0; it0 < nit; it0 += DEPTH) {
@@ -415,9 +452,10 @@ __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
                     if (p.x_out && blockIdx.x == 0 && on[d] && xok)  // the reduced residual stream (this wave's K slice), same packed address as x; pad rows stay zero
                         cbx_store_out4(p.x_out + xo + (it0 + d) * 512 + h * 256, xq);
                 }
+                if constexpr (LN) xq -= piv;  // after x_out took the unshifted sum
                 xq = (on[d] && xok) ? xq : zero4;
                 ss += (xq[0] * xq[0] + xq[1] * xq[1]) + (xq[2] * xq[2] + xq[3] * xq[3]);
-                sx += (xq[0] + xq[1]) + (xq[2] + xq[3]);
+                if constexpr (LN) sx += (xq[0] + xq[1]) + (xq[2] + xq[3]);
                 xq *= nv[d][h];
 #pragma unroll
                 for (int c = 0; c < CT; ++c) {
@@ -446,12 +484,16 @@ __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[(w * CT + c) * 256 + (q * 4 + r) * 16 + c16] = acc[c][r];
     {
-        float v = ss, u = sx;
+        float v = ss;
         v += cbx_xor_lane<16>(v);
         v += cbx_xor_lane<32>(v);
-        u += cbx_xor_lane<16>(u);
-        u += cbx_xor_lane<32>(u);
-        if (q == 0) ssq[w * 16 + c16] = v, ssx[w * 16 + c16] = u;
+        if (q == 0) ssq[w * 16 + c16] = v;
+        if constexpr (LN) {
+            float u = sx;
+            u += cbx_xor_lane<16>(u);
+            u += cbx_xor_lane<32>(u);
+            if (q == 0) ssx[w * 16 + c16] = u;
+        }
     }
     __syncthreads();
     CBX_TRC_STAMP(4);
@@ -464,7 +506,7 @@ __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
         for (int ww = 0; ww < NW; ++ww) v += red[(ww * CT + c) * 256 + rc];
 #pragma unroll
         for (int ww = 0; ww < NW; ++ww) sq += ssq[ww * 16 + row];
-        if (p.ln_cw) {  // LayerNorm form (GPT-2 ln_f + head; ksplit == 1): the expression of gemv_kernel
+        if constexpr (LN) {  // LayerNorm form (GPT-2 ln_f + head; ksplit == 1) on the shifted row: the expression of gemv_kernel
             float su = 0.f;
 #pragma unroll
             for (int ww = 0; ww < NW; ++ww) su += ssx[ww * 16 + row];
@@ -491,7 +533,10 @@ int launch_ct_np(const cbx_gemv_t& p, hipStream_t st) {
     const int ntiles = (p.N + 15) / 16;
     dim3 grid((ntiles + CT - 1) / CT, p.ksplit);
     const int nit = p.K / (32 * p.ksplit * 8);  // K blocks per wave
-    if (nit % 2 == 0) hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 2>), grid, dim3(512), 0, st, p);
+    if (p.ln_cw) {  // LayerNorm form (checked: ksplit == 1)
+        if (nit % 2 == 0) hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 2, true>), grid, dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 1, true>), grid, dim3(512), 0, st, p);
+    } else if (nit % 2 == 0) hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 2>), grid, dim3(512), 0, st, p);
     else hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 1>), grid, dim3(512), 0, st, p);
     return cbx_check_launch("gemv (column tiles)");
 }
@@ -507,8 +552,11 @@ int launch_ct(const cbx_gemv_t& p, hipStream_t st) {
 int g_gemv_deep = 0;     // cbx_set_gemv_deep_batches
 int g_gemv_pre_epi = 0;  // cbx_set_gemv_epilogue_prefetch
 
-template <int MT, bool SWIGLU, bool PK, bool XPK, bool RMS, int NP = 0, bool WB = false>
+template <int MT, bool SWIGLU, bool PK, bool XPK, bool RMS, int NP = 0, bool WB = false, bool LN = false>
 int launch_nw(const cbx_gemv_t& p, hipStream_t st) {
+    if constexpr (RMS && !SWIGLU && !LN) {
+        if (p.ln_cw) return launch_nw<MT, false, PK, XPK, true, NP, WB, true>(p, st);  // LayerNorm form: the kernels with the pivot shift
+    }
     const int tc = PK ? gemv_tile_cols(p.half_tile) : 16;
     dim3 grid((p.N + tc - 1) / tc, p.ksplit);
     if constexpr (MT == 1 && !SWIGLU && !RMS && (PK == XPK)) {
@@ -531,9 +579,9 @@ int launch_nw(const cbx_gemv_t& p, hipStream_t st) {
         }
     }
     if (p.nw >= 8 || NP > 0) {
-        hipLaunchKernelGGL((gemv_kernel<MT, 8, SWIGLU, PK, XPK, RMS, NP, WB>), grid, dim3(512), 0, st, p);
+        hipLaunchKernelGGL((gemv_kernel<MT, 8, SWIGLU, PK, XPK, RMS, NP, WB, false, false, LN>), grid, dim3(512), 0, st, p);
     } else {
-        hipLaunchKernelGGL((gemv_kernel<MT, 4, SWIGLU, PK, XPK, RMS, 0, WB>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL((gemv_kernel<MT, 4, SWIGLU, PK, XPK, RMS, 0, WB, false, false, LN>), grid, dim3(256), 0, st, p);
     }
     return cbx_check_launch("gemv");
 }

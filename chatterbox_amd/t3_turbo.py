@@ -74,8 +74,10 @@ class T3TurboEngine(DecodeRuntime, VoicePrefixCache):
         self.head, self.head_b = d(sd["speech_head.weight"]), d(sd["speech_head.bias"])
         self.V = self.head.shape[0]
         self.head_pk = ops.pack_gemv_weight(self.head)
-        # LayerNorm folded into the consuming GEMV (cbx_gemv_t.ln_cw / ln_cb): out = rstd (sum_k x w W - mean cw) + cb with the layer
-        # constants cw[n] = sum_k w[k] W[n][k], cb[n] = sum_k b[k] W[n][k] + bias[n]
+        # LayerNorm folded into the consuming GEMV (cbx_gemv_t.ln_cw / ln_cb): out = rstd (sum_k x' w W - mean' cw) + cb with the layer
+        # constants cw[n] = sum_k w[k] W[n][k], cb[n] = sum_k b[k] W[n][k] + bias[n]; the kernel takes the sums over the row shifted by a
+        # per-row pivot (x' = x - c, mean' = mean - c: gemv_decode.hip), so a residual stream with |mean| >> std normalises as the two-pass
+        # row path (ops.gemv_row) does
         def ln_consts(ln, W, bias):
             cw, cb = torch.empty(1, W.shape[0], device=dev), torch.empty(1, W.shape[0], device=dev)
             ops.gemv(ln[0].view(1, -1), W, cw, nw=4)

@@ -209,7 +209,9 @@ typedef struct cbx_gemv_t {
     int flags;           /* (was reserved1) ABI v10, CBX_GEMV_* bits below; 0 = the plain launch */
     const float* ln_cw;  /* or NULL: LayerNorm instead of RMSNorm (GPT-2 ln_1 / ln_2 / ln_f): with norm_w = LN weight w, ln_cw[n] = */
     const float* ln_cb;  /* sum_k w[k] W[n][k] and ln_cb[n] = sum_k b[k] W[n][k] + bias[n] (constants of the layer, computed at load): */
-                         /* out[m][n] = rstd[m] (sum_k x w W - mean[m] ln_cw[n]) + ln_cb[n], then `act` */
+                         /* out[m][n] = rstd[m] (sum_k x' w W - mean'[m] ln_cw[n]) + ln_cb[n], then `act`, on the SHIFTED row x' = x - c[m], c[m] = the */
+                         /* median of channels 0, K/2, K - 1 of the (summed) row: mean' = sum_k x' / K, rstd = rsqrt(sum_k x'^2 / K - mean'^2 + eps) -- */
+                         /* the one-pass variance and the mean term do not cancel when |mean| >> std; x_out still receives the unshifted row */
     /* ABI v11 -- column-tile / split-K form of the RMSNorm-folded packed GEMV (norm_w, packed fp32 operands in the 16-column image, M <= 16, no
      * bias / residual / activation; xpart / x_out as above).  col_tiles = 1 .. 4: a workgroup owns that many 16-column tiles, which share every x
      * register (activation : weight bytes per workgroup = 1 : col_tiles instead of 1 : 1 -- the decode GEMVs are bound by the bytes a CU moves,

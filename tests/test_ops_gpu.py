@@ -726,7 +726,7 @@ def test_decode_attn_packed_output_and_embed_packed(dev):
 @pytest.mark.parametrize("M,N,K,npart,act", [(16, 3072, 1024, 0, False), (5, 2304, 768, 4, False), (16, 4096, 1024, 0, True), (1, 6563, 1024, 4, False)])
 def test_gemv_layernorm_fused(dev, M, N, K, npart, act):
     """GPT-2 form of the fused decode GEMV: out = act(LayerNorm(x + sum partials) W^T + bias) with the LayerNorm folded in as
-    rstd (sum_k x w W - mean cw) + cb (cbx_gemv_t.ln_cw / ln_cb), against torch fp32."""
+    rstd (sum_k x' w W - mean' cw) + cb on the pivot-shifted row x' (cbx_gemv_t.ln_cw / ln_cb), against torch fp32."""
     from chatterbox_amd import ops
     x, parts = _r((M, K), 1) + 0.3, _r((max(npart, 1), M, K), 2, 0.3)
     lw, lb = 1 + 0.1 * _r((K,), 3), 0.1 * _r((K,), 4)

@@ -166,6 +166,25 @@ def test_softmax_stress_bodies_on_the_emulator(emu, name, args):
     getattr(test_softmax_stress_gpu, name)(CPU, *args)
 
 
+# tests/test_norm_stress_gpu.py (prescribed rows: large offsets, one outlier channel, zero variance) at emulator sizes: every kernel of that module at least once at its
+# smallest C / K / N, the patterns offset1024 / outlier_first / constant for each
+_NSP = ("offset1024", "outlier_first", "constant")
+_NORMSTRESS = [("test_layernorm_stress", (80, 37, _NSP)), ("test_layernorm_stress", (256, 77, _NSP)), ("test_row_stats_stress", (37, _NSP)),
+               ("test_layernorm_planes_stress", (37, _NSP)), ("test_gemm_planes_layernorm_epilogue_stress", (False, 37, _NSP)),
+               ("test_gemm_planes_layernorm_epilogue_stress", (True, 37, _NSP)), ("test_add_norm_stress", (768, 1, 5, _NSP)), ("test_add_norm_stress", (768, 4, 5, _NSP)),
+               ("test_gemv_rms_fold_stress", (5, _NSP)), ("test_gemv_rms_fold_split_k_into_attention_stress", (5, _NSP)),
+               ("test_gemv_layernorm_fold_stress", (768, 70, 5, _NSP)), ("test_gemv_layernorm_fold_stress", (768, 70, 1, _NSP)), ("test_gemv_layernorm_fold_stress", (768, 70, 33, _NSP)),
+               ("test_gemv_row_layernorm_stress", (256, 3, 1, 70, _NSP)), ("test_gemv_row_layernorm_stress", (256, 4, 4, 70, _NSP)),
+               ("test_layernorm_paths_agree_on_offset_rows", (768,)), ("test_stats_pool_stress", (1, _NSP)), ("test_stats_pool_stress", (3, _NSP)),
+               ("test_stats_pool_stress", (512, _NSP))]
+
+
+@pytest.mark.parametrize("name,args", _NORMSTRESS, ids=[f"{n}{list(a)}" for n, a in _NORMSTRESS])
+def test_normstress_bodies_on_the_emulator(emu, name, args):
+    import test_norm_stress_gpu
+    getattr(test_norm_stress_gpu, name)(CPU, *args)
+
+
 @pytest.mark.parametrize("tile,persist", [(0, 1), (1, 0), (3, 8), (7, 1), (12, 0), (15, 8), (21, 1), (24, 8), (26, 0), (28, 1), (31, 8), (32, 1), (33, 0), (34, 8), (36, 1)])
 def test_gemm_planes_tiles_small(emu, tile, persist):
     """tests/test_planes_gpu.py::test_gemm_planes_linear_tiles at emulator-sized shapes: symmetric, loader-wave (21+) and 16-wave (26+) tile
