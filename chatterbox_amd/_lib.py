@@ -84,6 +84,8 @@ class AttnPartsParams(ctypes.Structure):  # cbx_attn_parts_t (ABI v14)
 
 
 ATTN_PART_REC = 68  # CBX_ATTN_PART_REC
+RNG_UNIFORM, RNG_NORMAL = 0, 1  # cbx_rng_fill_f32 dist
+RNG_T3_UNIFORMS, RNG_CFM_Z, RNG_VOC_PHASE, RNG_VOC_NOISE = range(4)  # CBX_RNG_STREAM_*: the `stream` word of a cbx_rng_fill_f32 key
 
 
 class SamplerParams(ctypes.Structure):
@@ -281,6 +283,7 @@ _SIGS = {
     "cbx_hift_source_f32": ([c_f, c_f, c_f, c_f, c_float, c_f, c_f, c_int, c_int, c_int, c_float, c_f], c_int),
     "cbx_hift_source_carry_f32": ([c_f, c_f, c_f, c_f, c_float, c_f, c_f, c_f, c_int, c_int, c_int, c_float, c_f], c_int),
     "cbx_stream_emit_f32": ([c_f, c_long, c_long, c_f, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_long, c_f, c_int, c_f], c_int),
+    "cbx_rng_fill_f32": ([c_f, c_long, c_f, c_int, c_long, ctypes.c_ulonglong, c_int, c_f], c_int),
     "cbx_hift_stft_f32": ([c_f, c_f, c_f, c_int, c_long, c_long, c_f], c_int),
     "cbx_hift_istft_f32": ([c_f, c_f, c_int, c_long, c_long, c_float, c_int, c_f], c_int),
 }

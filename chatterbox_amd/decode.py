@@ -134,17 +134,20 @@ class DecodeRuntime:
         assert uniforms.numel() % B == 0 and uniforms.numel() // B >= n, f"uniforms must hold at least {what} draws per utterance"
         return uniforms.view(B, -1)
 
-    def _begin_request(self, st, samp, uniforms, n, generator):
+    def _begin_request(self, st, samp, uniforms, n, generator, seeds=None):
         """Reset the per-request state: sampling parameters (B, 8) into device memory (no graph re-capture when a request changes them), sampler counters,
-        the n draws of every utterance."""
+        the n draws of every utterance -- injected, else row b = columns [0, n) of seeds[b]'s RNG_T3_UNIFORMS stream (cbx_rng_fill_f32: no torch RNG is
+        consumed), else from the generator / the global RNG."""
         st["samp_dev"].copy_(samp, non_blocking=True)
         for k in ("seen", "step", "done", "n_generated", "out_tokens"):
             st[k].zero_()
         st["seen"][:, START_SPEECH] = 1  # the first processor call sees ids = [start token]
-        if uniforms is None:
-            st["uniforms"].uniform_(generator=generator)
-        else:
+        if uniforms is not None:
             st["uniforms"].copy_(uniforms[:, :n])
+        elif seeds is not None:
+            ops.rng_fill(st["uniforms"], ops.rng_keys(seeds, ops.RNG_T3_UNIFORMS, device=st["uniforms"].device), n=n)
+        else:
+            st["uniforms"].uniform_(generator=generator)
 
     def _ready_step(self, st, use_graph):
         """Capture what _replay will replay, on first use and BEFORE its timed events: the library's loop handle (returns True: the token loop runs in C) or

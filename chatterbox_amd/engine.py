@@ -83,12 +83,15 @@ class ChatterboxEngine:
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None):
+               generator=None, seeds=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
-        that is not injected (None: the global RNG)."""
+        that is not injected (None: the global RNG).  seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance) -- the noise that is not injected
+        is then a function of the utterance's seed alone (ops.seeded_z / seeded_phase / seeded_noise: cbx_rng_fill_f32), whatever its row and the batch around it,
+        and no torch RNG is consumed; not together with a generator."""
         B = len(speech_tokens)
+        seeds = ops.request_seeds(seeds, B, generator)
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
         tok = torch.zeros(B, Nmax, dtype=torch.long)
@@ -102,7 +105,7 @@ class ChatterboxEngine:
 
         def run():
             t0 = time.perf_counter()
-            mel = self.flow.inference(tok.to(self.dev), lens.to(self.dev), gen_ref, z=z, n_steps=n_cfm_timesteps, generator=generator)
+            mel = self.flow.inference(tok.to(self.dev), lens.to(self.dev), gen_ref, z=z, n_steps=n_cfm_timesteps, generator=generator, seeds=seeds)
             if sync:  # per-stage wall times; the pipelined mode never blocks the host between stages
                 torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -116,9 +119,9 @@ class ChatterboxEngine:
                     mel.record_stream(hift_stream)
                     if mel_lens is not None:
                         mel_lens.record_stream(hift_stream)
-                    wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator)
+                    wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator, seeds=seeds)
             else:
-                wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator)
+                wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator, seeds=seeds)
             if sync:
                 torch.cuda.synchronize()
             t2 = time.perf_counter()
@@ -136,20 +139,23 @@ class ChatterboxEngine:
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None):
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
-        temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected."""
+        temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
+        seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
+        (T3Engine.generate(seeds=), vocode(seeds=)); not together with a generator."""
+        seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
                    min_p=min_p, repetition_penalty=repetition_penalty, cfg_weight=cfg_weight, uniforms=uniforms,
-                   ban_eos=ban_eos, ban_from=ban_from, generator=generator)
+                   ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
         torch.cuda.synchronize()
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         st = [drop_invalid_tokens(t) for t in toks]
         st = [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
-                              drop_last_token=drop_last_token, generator=generator)
+                              drop_last_token=drop_last_token, generator=generator, seeds=seeds)
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
@@ -174,7 +180,8 @@ class ChatterboxEngine:
         matching + vocoder of batch k run on a second stream.  jobs: list of dicts(text_tokens=[...], t3_conds=..., gen_ref=...); yields
         (wavs, tokens, latency_s) per job in order.  Results are identical to synthesize() called per job.  A job may carry sampling parameters of its own
         (temperature, top_p, min_p, repetition_penalty, cfg_weight: scalar or one per utterance; they override **kw for that job) and a `generator` for the flow / vocoder noise that is not injected (the
-        sampling draws of a repeatable job are injected as `uniforms`: T3 is enqueued by another host thread).
+        sampling draws of a repeatable job are injected as `uniforms`: T3 is enqueued by another host thread), or `seeds` (one int per utterance, or one int for all:
+        every draw of the job that is not injected, as synthesize(seeds=); not together with a generator).
 
         What makes the two stages actually overlap (round 5, profiles/r05_overlap_*; none of it changes a result):
           * co_resident: a chain of small dependent kernels keeps its pace beside chip-filling kernels of another stream only if its workgroups FIT
@@ -186,6 +193,7 @@ class ChatterboxEngine:
             (scripts/overlap_probe.py: the flow started 180 ms late).  The T3 enqueue runs on a second host thread (graph launches and the ctypes
             calls of the C stage seams release the GIL)."""
         import threading
+        jobs = [dict(job, seeds=ops.request_seeds(job["seeds"], len(job["text_tokens"]), job.get("generator"))) if job.get("seeds") is not None else job for job in jobs]
         torch.cuda.set_device(self.dev)  # a generator cannot hold a device guard across yields: pin the device for the caller
         self._pipeline_streams(stream_priorities)
         t3_kw = {k: kw[k] for k in ("max_new_tokens", "temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight", "ban_eos",
@@ -205,14 +213,14 @@ class ChatterboxEngine:
             try:
                 torch.cuda.set_device(self.dev)
                 with torch.inference_mode(), torch.cuda.stream(self._s_t3):
-                    box["handle"] = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), **job_kw(job))
+                    box["handle"] = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), seeds=job.get("seeds"), **job_kw(job))
             except BaseException as e:  # re-raised by the consumer thread
                 box["error"] = e
 
         def voc_of(job, st):
             with torch.cuda.stream(self._s_voc):
                 def voc():
-                    wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"),
+                    wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
                                           n_cfm_timesteps=kw.get("n_cfm_timesteps", 10),
                                           drop_last_token=kw.get("drop_last_token", True), sync=False)
                     return [w.cpu() for w in wavs]  # D2H on the vocoder stream: returns when this batch's audio is on the host
@@ -265,7 +273,7 @@ class ChatterboxEngine:
                         return
                     t_start = time.perf_counter()
                     with torch.inference_mode(), torch.cuda.stream(self._s_t3x[k % n_t3]):
-                        h = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), slot=k % n_slots, **job_kw(job))
+                        h = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), seeds=job.get("seeds"), slot=k % n_slots, **job_kw(job))
                         ev = torch.cuda.Event()
                         ev.record()
                     q.put((h, ev, t_start))
@@ -282,7 +290,7 @@ class ChatterboxEngine:
         def start_voc(job, st, which):
             ops.select_range_flag(self.dev, which)
             with torch.cuda.stream(self._s_voc):
-                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), sync=False, **voc_kw)
+                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), sync=False, **voc_kw)
                 host = [torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True) for w in wavs]
                 ev = torch.cuda.Event()
                 ev.record()
@@ -298,7 +306,7 @@ class ChatterboxEngine:
                 self.flow.precision, self.hift.precision = (6 if p == 16 else p for p in saved)
                 try:
                     with torch.cuda.stream(self._s_voc):
-                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), sync=False, **voc_kw)
+                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), sync=False, **voc_kw)
                         host = [w.cpu() for w in wavs]
                 finally:
                     self.flow.precision, self.hift.precision = saved
@@ -382,7 +390,7 @@ def stream_window_schedule(n_tokens, first_chunk=25, chunk=50, lookahead=3, chun
     return out
 
 
-def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade, z, phase, noise, n_cfm_timesteps, drop_last_token, window):
+def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade, z, phase, noise, n_cfm_timesteps, drop_last_token, window, seeds=None):
     """The state of one stream of B utterances and its round function: -> (one_round, closed flags).  one_round(toks, done, exhausted) runs flow + vocoder
     on the CURRENT stream and returns the dict the stream generators yield.  n_tokens: the most tokens an utterance can have (the default z / noise cover them).
 
@@ -396,20 +404,44 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
       * emitted / end / avail stay ABSOLUTE samples of the utterance; the round's waveform starts at sample 960 a.  The emission (new samples, cross-fade
         with the kept tail, next tail) is one cbx_stream_emit_f32 launch and one D2H copy for all utterances.
     The cache keeps the source of the rows that go on (the window=None form keeps the shortest row's, finished rows included); with every a == 0 and no row
-    finishing before the others the two forms yield the same bits."""
+    finishing before the others the two forms yield the same bits.
+    seeds (B ints or None): the z / phase / noise that is not injected comes from each utterance's seed (ops.seeded_*).  window=None: filled once, at the sizes of
+    the unseeded defaults.  window=W: z and noise are NOT materialised for the whole budget -- a round fills the columns it reads (z frames [0, 2P) and
+    [2(P + a), 2(P + a + Nk)), noise samples [o, o + 480 frames)), which are those of the full fill by construction (cbx_rng_fill_f32's col0)."""
     dev = self.dev
     W = check_stream_window(window, fade)
     P = gen_ref["prompt_token"].shape[-1]
     N = n_tokens
     assert gen_ref["prompt_feat"].shape[-2] == 2 * P, "chunked synthesis needs a whole-token prompt (embed_ref output trimmed to 2 frames per token)"
-    if z is None:
-        z = torch.randn(B, 2 * (P + N), 80, device=dev)
-    if phase is None:
-        phase = (torch.rand(B, 9, device=dev) * 2 - 1) * 3.141592653589793
-        phase[:, 0] = 0
-    if noise is None:
-        noise = torch.randn(B, 9, SAMPLES_PER_TOKEN * N, device=dev)
-    z, phase, noise = z.to(dev), phase.to(dev).reshape(B, 9), noise.to(dev)
+    per_round = seeds is not None and W is not None  # seeded and windowed: z / noise that is not injected is filled round by round (z_frames, noise_samples)
+    if seeds is not None:
+        if phase is None:
+            phase = ops.seeded_phase(seeds, dev)
+        if not per_round:
+            z = ops.seeded_z(seeds, 2 * (P + N), dev) if z is None else z
+            noise = ops.seeded_noise(seeds, SAMPLES_PER_TOKEN * N, dev) if noise is None else noise
+    else:
+        if z is None:
+            z = torch.randn(B, 2 * (P + N), 80, device=dev)
+        if phase is None:
+            phase = (torch.rand(B, 9, device=dev) * 2 - 1) * 3.141592653589793
+            phase[:, 0] = 0
+        if noise is None:
+            noise = torch.randn(B, 9, SAMPLES_PER_TOKEN * N, device=dev)
+    z, phase, noise = None if z is None else z.to(dev), phase.to(dev).reshape(B, 9), None if noise is None else noise.to(dev)
+
+    def z_frames(a, Nk):
+        """CFM noise of the prompt's frames and of tokens [a, a + Nk): (B, 2 (P + Nk), 80)"""
+        if z is not None:
+            return z[:, : 2 * (P + Nk)] if a == 0 else torch.cat([z[:, : 2 * P], z[:, 2 * (P + a): 2 * (P + a + Nk)]], 1)
+        if a == 0:
+            return ops.seeded_z(seeds, 2 * (P + Nk), dev)
+        return torch.cat([ops.seeded_z(seeds, 2 * P, dev), ops.seeded_z(seeds, 2 * Nk, dev, frame0=2 * (P + a))], 1)
+
+    def noise_samples(o, n):
+        """source noise of absolute samples [o, o + n): (B, 9, n)"""
+        return noise[:, :, o: o + n] if noise is not None else ops.seeded_noise(seeds, n, dev, col0=o)
+
     emitted, tails, closed, cache = [0] * B, [None] * B, [False] * B, [None]
     ramp = torch.linspace(0.0, 1.0, fade + 2, device=dev)[1:-1]
     win = dict(a=0, cum=None, tail_len=[0] * B, bufs=None, cur=0)  # window form: origin (tokens) and phase scan of the last round, the kept tails (device, ping-pong)
@@ -443,10 +475,9 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
             o = SAMPLES_PER_TOKEN * a  # absolute sample of wav[:, 0]
 
             def run():
-                zz = z[:, : 2 * (P + Nk)] if a == 0 else torch.cat([z[:, : 2 * P], z[:, 2 * (P + a): 2 * (P + a + Nk)]], 1)
-                mel = self.flow.inference(tok.to(dev), torch.tensor(wn, dtype=torch.int32, device=dev), gen_ref, z=zz,
+                mel = self.flow.inference(tok.to(dev), torch.tensor(wn, dtype=torch.int32, device=dev), gen_ref, z=z_frames(a, Nk),
                                           n_steps=n_cfm_timesteps, hold_back=hold)
-                return self.hift.inference(mel, phase=phase, noise=noise[:, :, o: o + HALF * mel.shape[1]], lens=fl, fade=a == 0,
+                return self.hift.inference(mel, phase=phase, noise=noise_samples(o, HALF * mel.shape[1]), lens=fl, fade=a == 0,
                                            cache_source=cache_src, cum_in=cum_in)
             wav, src = _range_checked(self, run)
             if W is None:
@@ -501,20 +532,22 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
 
 
 def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw, round_tokens, n_extra, first_chunk, chunk, chunk_growth, lookahead, fade, z,
-                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead, window=None):
+                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead, window=None, seeds=None):
     """The round schedule of synthesize_stream for either backbone (ChatterboxEngine: Llama T3, TurboEngine: GPT-2 T3; both T3 engines offer the async
     generate / advance / peek protocol).  n_budget: tokens the T3 call can sample; t3_kw: its sampling arguments; round_tokens(toks, final flags) -> the
     valid speech tokens a round vocodes (never empty); n_extra: tokens round_tokens may add (the default z / noise cover n_budget + n_extra).
-    window: None, or the left context in tokens of a bounded round (_stream_rounds)."""
+    window: None, or the left context in tokens of a bounded round (_stream_rounds).  seeds: None, an int or B ints -- the sampling draws (generate(seeds=))
+    and the flow / vocoder noise (_stream_rounds) that are not injected."""
     check_stream_window(window, fade)
+    seeds = ops.check_seeds(seeds, len(text_tokens))
     # (a generator cannot hold a device guard across yields: pin the device for the caller; "cuda" without an index = the current device)
     pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
     torch.cuda.set_device(pin)
     B, N = len(text_tokens), n_budget
-    t3_kw = dict(t3_kw, async_mode=True)
+    t3_kw = dict(t3_kw, async_mode=True, seeds=seeds)
     totals = stream_token_schedule(N, first_chunk, chunk, lookahead, chunk_growth)  # tokens decoded when round r starts
     one_round, closed = _stream_rounds(self, B, gen_ref, n_tokens=N + n_extra, round_tokens=round_tokens, lookahead=lookahead, fade=fade, z=z, phase=phase, noise=noise,
-                                       n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window)
+                                       n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds)
     if not overlap:  # the serial form of rounds 3-5: T3 waits while a round is synthesised
         h = self.t3.generate(t3_conds, text_tokens, run_steps=totals[0], **t3_kw)
         for r, n_r in enumerate(totals):
@@ -591,7 +624,7 @@ def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw,
 def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,
                       temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False,
                       ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2,
-                      window=None):
+                      window=None, seeds=None):
     """Chunked synthesis: first audio after `first_chunk` tokens instead of after the whole utterance.
 
     The reference is non-streaming; of its vestigial hooks only HiFT's `cache_source` works (hifigan.py:470-472) -- `finalize=False`
@@ -611,6 +644,8 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
     window (None: the schedule above): the left context, in tokens, of a round of BOUNDED cost -- a round then synthesises the voice prompt, `window`
     tokens in front of the first sample it has not emitted yet, the new chunk and the lookahead, whatever the round's number (_stream_rounds,
     stream_window_schedule); at least ceil((8000 + fade) / 960) tokens, else ValueError.  The last round is then no longer the full synthesis.
+    seeds (None, an int, or B ints in [0, 2^64)): every draw that is not injected comes from its utterance's seed (synthesize(seeds=)); with a window, z and
+    noise are then filled round by round and never for the whole budget (_stream_rounds).
     Yields dicts {wavs: [B CPU tensors of NEW samples], final: [B bools], n_tokens: [B], tokens: [B CPU tensors: the speech tokens the round vocoded]};
     concatenating an utterance's pieces gives its waveform."""
     t3_kw = dict(max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
@@ -623,16 +658,18 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
     yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_new_tokens, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=0,
                                   first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                   noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                  run_ahead=run_ahead, window=window)
+                                  run_ahead=run_ahead, window=window, seeds=seeds)
 
 
 def vocode_stream(self, speech_tokens, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=None, z=None, phase=None,
-                  noise=None, n_cfm_timesteps=10, drop_last_token=False):
+                  noise=None, n_cfm_timesteps=10, drop_last_token=False, seeds=None):
     """vocode() in rounds: the schedule, the yields and the `window` of synthesize_stream with a list of B 1-D token tensors (valid ids; lengths may differ) in
     place of T3 -- round r synthesises the first n_r tokens of every utterance (stream_token_schedule over the longest), utterance b is final once
     n_r >= N_b.  No T3 is touched: this is the streaming form of voice conversion (the engine ChatterboxVC builds has none), where every token exists up
-    front and the input can be arbitrarily long -- give a `window`.  gen_ref: one voice with a whole-token prompt."""
+    front and the input can be arbitrarily long -- give a `window`.  gen_ref: one voice with a whole-token prompt.  seeds: as vocode(seeds=); with a window the
+    noise is filled round by round (_stream_rounds)."""
     check_stream_window(window, fade)
+    seeds = ops.check_seeds(seeds, len(speech_tokens))
     pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
     torch.cuda.set_device(pin)  # (a generator cannot hold a device guard across yields)
     toks = [torch.as_tensor(t).view(-1).long().cpu() for t in speech_tokens]
@@ -640,7 +677,7 @@ def vocode_stream(self, speech_tokens, gen_ref, *, first_chunk=25, chunk=50, chu
     lens = [int(t.numel()) for t in toks]
     self.co_resident(False)
     one_round, closed = _stream_rounds(self, len(toks), gen_ref, n_tokens=max(lens), round_tokens=lambda ts, fin: ts, lookahead=lookahead, fade=fade, z=z,
-                                       phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window)
+                                       phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds)
     for n_r in stream_token_schedule(max(lens), first_chunk, chunk, lookahead, chunk_growth):
         yield one_round([t[:n_r] for t in toks], [n_r >= n for n in lens], n_r >= max(lens))
         if all(closed):
@@ -672,17 +709,18 @@ class TurboEngine:
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
-        for every draw that is not injected."""
+        for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=)."""
+        seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,
-                                repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator)
+                                repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
         torch.cuda.synchronize()
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
-        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator)
+        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds)
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
@@ -692,13 +730,13 @@ class TurboEngine:
     @torch.inference_mode()
     def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_gen_len=1000,
                           temperature=0.8, top_k=1000, top_p=0.95, repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2, window=None):
+                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2, window=None, seeds=None):
         """Chunked synthesis of Turbo / Nano: the round schedule, yields and overlap / first_alone / run_ahead semantics of ChatterboxEngine.synthesize_stream
         around the GPT-2 T3 (chunked through T3TurboEngine.generate(async_mode=True) / advance / peek) and the 2-step meanflow flow.  A round vocodes the
         sampled ids < 6561; the FINAL round of an utterance appends the three S3GEN_SIL tokens exactly as synthesize() does and keeps every token
         (drop_last_token=False), non-final rounds carry no silence and hold back 2 * lookahead frames.  T3 can sample max_gen_len + 1 tokens: the default
         z / phase / noise cover that many plus the 3 silence tokens.  The last round is a full synthesis: identical mel to synthesize() for the same noise.
-        window: the bounded-cost rounds of ChatterboxEngine.synthesize_stream."""
+        window: the bounded-cost rounds of ChatterboxEngine.synthesize_stream; seeds: its per-utterance seeds."""
         t3_kw = dict(max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, uniforms=uniforms,
                      ban_eos=ban_eos, ban_from=ban_from)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
@@ -710,4 +748,4 @@ class TurboEngine:
         yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_gen_len + 1, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=3,
                                       first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                       noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                      run_ahead=run_ahead, window=window)
+                                      run_ahead=run_ahead, window=window, seeds=seeds)

@@ -224,12 +224,18 @@ class HiFTEngine:
 
     @ops.on_device
     @torch.inference_mode()
-    def inference(self, mel, phase=None, noise=None, lens=None, fade=True, cache_source=None, generator=None, cum_in=None):
+    def inference(self, mel, phase=None, noise=None, lens=None, fade=True, cache_source=None, generator=None, cum_in=None, seeds=None):
         """HiFTGenerator.inference + S3Gen trim_fade.  mel (B,T,80) channel-last.  Returns (wav (B,480T), source (B,480T)).
         cache_source (B, L): the source of an earlier chunk replaces the first L samples (hifigan.py:470-472).
         cum_in (B, 9) float64: mel is a window of a longer signal -- the source's phase scan starts from these cumulative cycles instead of 0 (the
-        carry of an earlier call: its self.frame_cum (B, 9, T) at the frame this window starts)."""
+        carry of an earlier call: its self.frame_cum (B, 9, T) at the frame this window starts).
+        seeds (B ints): the phase / noise that is not injected comes from seeds[b]'s RNG_VOC_PHASE / RNG_VOC_NOISE streams (ops.seeded_phase, seeded_noise; the
+        noise from sample 0), not from torch's RNG; not together with a generator."""
         B, T, _ = mel.shape
+        seeds = ops.request_seeds(seeds, B, generator)
+        if seeds is not None:
+            phase = ops.seeded_phase(seeds, self.dev) if phase is None else phase
+            noise = ops.seeded_noise(seeds, 480 * T, self.dev) if noise is None else noise
         if phase is None:
             phase = (torch.rand(B, 9, device=self.dev, generator=generator) * 2 - 1) * 3.141592653589793
             phase[:, 0] = 0

@@ -8,6 +8,7 @@ import os
 
 import torch
 
+from . import _lib
 from ._lib import (ATTN_PART_REC, ATTN_PL_CORESIDENT, GEMV_DEEP, GEMV_PRE_EPI, GEMV_SHALLOW, PL_TILE_CORESIDENT, AttnPartsParams, DecodeAttnParams, GemmParams,
                    GemmPlParams, GemvParams, GemvRowParams, PrefillEmbed, SamplerParams, check, lib)
 
@@ -792,6 +793,85 @@ def stream_emit(wav, origin, meta, tail_in, ramp, out, tail_out):
     check(lib.cbx_stream_emit_f32(_p(_f32(wav, "wav")), wav.stride(0), int(origin), m, m + 4 * B, m + 8 * B, _p(tail_in), m + 12 * B, _p(ramp), fade,
                                   _p(_f32(out, "out")), out.shape[1], _p(tail_out), B, _stream()), "cbx_stream_emit_f32")
     return out
+
+
+# ----------------------------------------------------------------------------- per-request seeds: the counter-based RNG (cbx_rng_fill_f32)
+
+RNG_T3_UNIFORMS, RNG_CFM_Z, RNG_VOC_PHASE, RNG_VOC_NOISE = _lib.RNG_T3_UNIFORMS, _lib.RNG_CFM_Z, _lib.RNG_VOC_PHASE, _lib.RNG_VOC_NOISE
+
+
+def check_seeds(seeds, B, name="seeds"):
+    """Per-request seeds as a list of B Python ints in [0, 2^64) (None stays None).  An int serves every request; anything else must be a list or tuple of
+    exactly B ints.  TypeError / ValueError, before anything is launched."""
+    if seeds is None:
+        return None
+    one = lambda s: isinstance(s, int) and not isinstance(s, bool)
+    if one(seeds):
+        seeds = [seeds] * B
+    elif not isinstance(seeds, (list, tuple)):
+        raise TypeError(f"{name}: expected an int or a list of {B} ints, got {type(seeds).__name__}")
+    if len(seeds) != B:
+        raise ValueError(f"{name}: {len(seeds)} entries for {B} requests")
+    for k, s in enumerate(seeds):
+        if not one(s):
+            raise TypeError(f"{name}[{k}]: expected an int, got {type(s).__name__}")
+        if not 0 <= s < 1 << 64:
+            raise ValueError(f"{name}[{k}] = {s}: a seed is an int in [0, 2^64)")
+    return list(seeds)
+
+
+def request_seeds(seeds, B, generator=None):
+    """An engine entry's `seeds` as a list of B ints or None (check_seeds).  Seeds and a torch.Generator exclude each other: ValueError."""
+    seeds = check_seeds(seeds, B)
+    if seeds is not None and generator is not None:
+        raise ValueError("give seeds or generator, not both")
+    return seeds
+
+
+def rng_keys(seeds, stream, substreams=(0,), device="cpu"):
+    """The (len(seeds) * len(substreams), 4) int32 key tensor of cbx_rng_fill_f32: row b * len(substreams) + h = (seed_b & 0xffffffff, seed_b >> 32,
+    substreams[h], stream), the 32-bit words stored as their two's-complement int32."""
+    import numpy as np
+    k = np.array([[s & 0xFFFFFFFF, s >> 32, int(h), int(stream)] for s in seeds for h in substreams], dtype=np.uint32).reshape(-1, 4)
+    return torch.from_numpy(k.view(np.int32)).to(device)
+
+
+def rng_fill(out, keys, n=None, col0=0, normal=False):
+    """cbx_rng_fill_f32: out[r, :n] = the draws of key row r at absolute columns [col0, col0 + n) -- uniform in [0, 1), or standard normal.  out (rows, >= n)
+    fp32 with unit column stride (a view is fine; columns from n on are left alone), keys (rows, 4) int32 on out's device (rng_keys)."""
+    assert out.dim() == 2 and (out.shape[1] <= 1 or out.stride(1) == 1), "rng_fill: out is (rows, columns) with unit column stride"
+    rows = out.shape[0]
+    n = out.shape[1] if n is None else int(n)
+    assert 0 <= n <= out.shape[1] and (rows <= 1 or out.stride(0) >= n), "rng_fill: n exceeds the row"
+    assert keys.dtype == torch.int32 and keys.shape == (rows, 4) and keys.is_contiguous() and keys.device == out.device, "rng_fill: keys is (rows, 4) int32 on out's device"
+    assert 0 <= int(col0) and int(col0) + n <= 1 << 64, "rng_fill: columns are 64-bit"
+    check(lib.cbx_rng_fill_f32(_p(_f32(out, "out")), out.stride(0) if rows > 1 else max(out.stride(0), n), _p(keys), rows, n, int(col0), _lib.RNG_NORMAL if normal else _lib.RNG_UNIFORM,
+                               _stream()), "cbx_rng_fill_f32")
+    return out
+
+
+def seeded_z(seeds, frames, device, frame0=0):
+    """The CFM noise of B seeded requests, (B, frames, 80) channel-last: frames [frame0, frame0 + frames) of each request's RNG_CFM_Z stream (one row per
+    request, column = frame * 80 + channel, the request's own frame index -- whatever the batch's padded length)."""
+    z = torch.empty(len(seeds), frames, 80, device=device)
+    rng_fill(z.view(len(seeds), frames * 80), rng_keys(seeds, RNG_CFM_Z, device=device), col0=80 * int(frame0), normal=True)
+    return z
+
+
+def seeded_phase(seeds, device):
+    """The vocoder's initial phases of B seeded requests, (B, 9): the RNG_VOC_PHASE uniforms scaled to [-pi, pi), harmonic 0 zeroed, as the unseeded draw is."""
+    u = torch.empty(len(seeds), 9, device=device)
+    rng_fill(u, rng_keys(seeds, RNG_VOC_PHASE, device=device))
+    phase = (u * 2 - 1) * 3.141592653589793
+    phase[:, 0] = 0
+    return phase
+
+
+def seeded_noise(seeds, n, device, col0=0):
+    """The vocoder's source noise of B seeded requests, (B, 9, n): samples [col0, col0 + n) of each request's RNG_VOC_NOISE stream, substream = harmonic."""
+    noise = torch.empty(len(seeds), 9, n, device=device)
+    rng_fill(noise.view(len(seeds) * 9, n), rng_keys(seeds, RNG_VOC_NOISE, substreams=range(9), device=device), col0=col0, normal=True)
+    return noise
 
 
 def hift_stft(s, spec, sample_lens=None):

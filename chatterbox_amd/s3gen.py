@@ -573,17 +573,19 @@ class FlowEngine:
     # ------------------------------------------------------------------ flow.inference
     @ops.on_device
     @torch.inference_mode()
-    def inference(self, tokens, token_lens, ref, z=None, n_steps=10, hold_back=None, generator=None):
+    def inference(self, tokens, token_lens, ref, z=None, n_steps=10, hold_back=None, generator=None, seeds=None):
+        seeds = ops.request_seeds(seeds, tokens.shape[0], generator)
         with ops.gemm_precision(self.precision):
-            return self._inference(tokens, token_lens, ref, z, n_steps, hold_back, generator)
+            return self._inference(tokens, token_lens, ref, z, n_steps, hold_back, generator, seeds)
 
-    def _inference(self, tokens, token_lens, ref, z=None, n_steps=10, hold_back=None, generator=None):
+    def _inference(self, tokens, token_lens, ref, z=None, n_steps=10, hold_back=None, generator=None, seeds=None):
         """tokens (B,N) int64 (right-padded), token_lens (B,), ref dict as produced by S3Gen.embed_ref -- or a LIST of B such dicts, one voice
         per utterance (the reference takes a ref_dict per call, s3gen.py:173-229; a device batch may mix voices: prompt tokens / prompt mels
         of different lengths are left-aligned per row) --, z optional injected noise (B, 2(P+N)max, 80) channel-last.  Returns mel
         (B, frames, 80) channel-last, row b valid for 2 N_b - (prompt_feat frames_b - 2 P_b) frames: (B, 2N, 80) for whole-token prompts.
         hold_back (B,) ints: chunked synthesis -- the last hold_back[b] frames of utterance b are not generated (`finalize=False` of
-        flow.py:170-171, whose reference branch raises; semantics restated)."""
+        flow.py:170-171, whose reference branch raises; semantics restated).
+        seeds (B ints, with z=None): row b of the noise is seeds[b]'s RNG_CFM_Z stream over its own frames (ops.seeded_z); no torch RNG is consumed."""
         dev = self.dev
         B, N = tokens.shape
         refs = list(ref) if isinstance(ref, (list, tuple)) else [ref] * B
@@ -621,7 +623,7 @@ class FlowEngine:
             for b in range(B):
                 cond[b, : Pms[b]] = pfs[b]
         if z is None:
-            z = torch.randn(B, T, 80, device=dev, generator=generator)
+            z = ops.seeded_z(seeds, T, dev) if seeds is not None else torch.randn(B, T, 80, device=dev, generator=generator)
         mel_lens = (2 * lens).to(torch.int32)
         if hold_back is not None:  # chunked synthesis: the encoder's 3-token lookahead frames are masked out of the CFM like padding
             mel_lens = (mel_lens - torch.as_tensor(hold_back, dtype=torch.int32).to(dev)).contiguous()

@@ -758,16 +758,19 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
     @torch.inference_mode()
     def generate(self, conds, text_tokens, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                  repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16,
-                 return_prefill_logits=False, debug_logits=False, async_mode=False, slot=0, run_steps=None, generator=None):
+                 return_prefill_logits=False, debug_logits=False, async_mode=False, slot=0, run_steps=None, generator=None, seeds=None):
         """conds: one T3 cond dict (shared voice) or a list of B; text_tokens: list of B 1-D LongTensors that already
         carry SOT/EOT (mtl_tts.py:319-322).  Returns a list of B 1-D LongTensors (EOS included if it was sampled).
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar, or a sequence of B (one row of cbx_sampler_t.dev_params per utterance).
         generator: a torch.Generator on the engine's device for the sampling draws (None: the global RNG).
+        seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance) -- utterance b's draw of step i is column i of seeds[b]'s
+        RNG_T3_UNIFORMS stream (ops.rng_fill), whatever its row and the batch around it; injected `uniforms` win; not together with a generator.
         `slot` selects an independent set of workspaces / KV cache / decode graph (pipelined serving keeps two alive).
         Chunked use (streaming synthesis): `async_mode=True, run_steps=k` samples only the first k tokens and returns a handle;
         `advance(handle, n)` enqueues n more decode steps and `peek(handle)` fetches the tokens sampled so far."""
         dev, B = self.dev, len(text_tokens)
         assert B >= 1, "empty batch"
+        seeds = ops.request_seeds(seeds, B, generator)
         uniforms = self._uniform_rows(uniforms, B, max_new_tokens, f"max_new_tokens={max_new_tokens}")
         # {cfg_weight, temperature, min_p, top_p, rep_penalty, top_k, ban_token, ban_from} per utterance (cbx_sampler_t.dev_params); a wrong length raises here
         samp = sampler_rows(B, (("cfg_weight", cfg_weight), ("temperature", temperature), ("min_p", min_p), ("top_p", top_p),
@@ -782,7 +785,8 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
                                      temperature=_slice_param(temperature, lo, hi), top_p=_slice_param(top_p, lo, hi), min_p=_slice_param(min_p, lo, hi),
                                      repetition_penalty=_slice_param(repetition_penalty, lo, hi), cfg_weight=_slice_param(cfg_weight, lo, hi),
                                      uniforms=None if uniforms is None else uniforms[lo:hi], ban_eos=ban_eos,
-                                     ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, slot=slot, generator=generator)
+                                     ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, slot=slot, generator=generator,
+                                     seeds=None if seeds is None else seeds[lo:hi])
             return out
         rows = 2 * B
         prec = self.tune.get("prefill_prec") or 0
@@ -799,7 +803,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         assert max_ctx <= self.max_pos, "context exceeds the RoPE table"
         st = self._get_state(B, max_ctx, max_new_tokens, slot)
         self._prepare_tune()
-        self._begin_request(st, samp, uniforms, max_new_tokens, generator)
+        self._begin_request(st, samp, uniforms, max_new_tokens, generator, seeds)
 
         # ---- the missing prefixes of a mixed-voice batch: [conditioning] alone through the layers, once per distinct voice, into cache rows 0 .. n - 1
         missing = [j for j, e in enumerate(ents) if e is None]

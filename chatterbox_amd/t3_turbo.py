@@ -327,11 +327,12 @@ class T3TurboEngine(DecodeRuntime, VoicePrefixCache):
     @torch.inference_mode()
     def generate(self, conds, text_tokens, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95, repetition_penalty=1.2,
                  uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16, debug_logits=False, async_mode=False, run_steps=None,
-                 generator=None):
+                 generator=None, seeds=None):
         """conds: one cond dict (speaker_emb (1,256), cond_prompt_speech_tokens (1,375)) or a list of B; text_tokens: list of B
         1-D LongTensors (GPT-2 BPE ids, no SOT/EOT).  Returns a list of B 1-D LongTensors without the trailing EOS.
         temperature, top_k, top_p, repetition_penalty: a scalar, or a sequence of B (one row of cbx_sampler_t.dev_params per utterance).
         generator: a torch.Generator on the engine's device for the sampling draws (None: the global RNG).
+        seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): the per-request draws of T3Engine.generate(seeds=).
         Chunked use (streaming synthesis, the protocol of T3Engine.generate): `async_mode=True, run_steps=k` samples only the first k of the
         max_gen_len + 1 tokens and returns a handle without synchronising; `advance(handle, n)` enqueues n more token steps (cbx_gpt2_loop_run),
         `peek(handle)` fetches the tokens sampled so far, `collect(handle)` the result of the call."""
@@ -339,6 +340,7 @@ class T3TurboEngine(DecodeRuntime, VoicePrefixCache):
         voices, voice_of = self._distinct_voices(conds, B)  # the conditioning prefix of every distinct voice may be cached
         conds = [conds] * B if isinstance(conds, dict) else conds
         assert B >= 1, "empty batch"
+        seeds = ops.request_seeds(seeds, B, generator)
         # sampling parameters live in device memory (cbx_sampler_t.dev_params), one row per utterance; a wrong length raises here
         samp = sampler_rows(B, (("cfg_weight", 0.0), ("temperature", temperature), ("min_p", 0.0), ("top_p", top_p), ("repetition_penalty", repetition_penalty),
                                 ("top_k", top_k), ("ban_token", float(STOP_SPEECH if ban_eos else -1)), ("ban_from", float(ban_from))))
@@ -351,7 +353,8 @@ class T3TurboEngine(DecodeRuntime, VoicePrefixCache):
                 out += self.generate(conds[lo:hi], text_tokens[lo:hi], max_gen_len=max_gen_len, temperature=_slice_param(temperature, lo, hi),
                                      top_k=_slice_param(top_k, lo, hi), top_p=_slice_param(top_p, lo, hi),
                                      repetition_penalty=_slice_param(repetition_penalty, lo, hi), uniforms=None if uniforms is None else uniforms[lo:hi],
-                                     ban_eos=ban_eos, ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, generator=generator)
+                                     ban_eos=ban_eos, ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, generator=generator,
+                                     seeds=None if seeds is None else seeds[lo:hi])
             return out
         n_prompt = [int(c["cond_prompt_speech_tokens"].numel()) for c in conds]
         tl = [int(t.numel()) for t in text_tokens]
@@ -363,7 +366,7 @@ class T3TurboEngine(DecodeRuntime, VoicePrefixCache):
         st = self._get_state(B, max_ctx, n_samples)
         if self.decode_mode == "v2":
             self._prepare_tune()
-        self._begin_request(st, samp, uniforms, n_samples, generator)  # (the first processor call sees ids = [start token]: t3.py:428)
+        self._begin_request(st, samp, uniforms, n_samples, generator, seeds)  # (the first processor call sees ids = [start token]: t3.py:428)
 
         # ---- prefill: [speaker | prompt-token embeddings | text | start-speech] + wpe (prepare_input_embeds, t3.py:102-130,407-423)
         # The 1 + n_prompt conditioning positions see only themselves (causal) and carry absolute positions: with their K / V cached (VoicePrefixCache) only the

@@ -784,6 +784,26 @@ int cbx_hift_stft_f32(const float* s, float* spec, const int* sample_lens, int B
 int cbx_hift_istft_f32(const float* x, float* wav, int B, long frames, long ldx, float clamp, int fade_n,
                        void* stream);
 
+/* ---- counter-based device RNG: per-request seeds (added after ABI v16 without a version step: a new function only) ----
+ * Replaces, for a request that carries a seed, the draws the reference takes from torch's sequential generator: the draw inside torch.multinomial of the
+ * sampling loops (t3.py:360,430,455), torch.randn_like of the CFM noise (flow_matching.py:63,216), and the Uniform(-pi, pi) phase / torch.randn_like noise
+ * of SineGen and SourceModuleHnNSF (hifigan.py:212-213,226,282).  Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, key increments
+ * 0x9E3779B9 / 0xBB67AE85).
+ * out (rows, ld_out >= n): out[r][j - col0] for j in [col0, col0 + n) is defined by the ABSOLUTE column j alone; elements [n, ld_out) are not written.
+ * keys (rows, 4) 32-bit words in device memory: seed_lo, seed_hi, substream, stream.  Philox key = (seed_lo, seed_hi); counter = (blk & 0xffffffff, blk >> 32,
+ * substream, stream) with blk = j / 4; column j takes output word x = j % 4 of that block.  So a slice equals the same slice of a longer fill for ANY col0.
+ *   CBX_RNG_UNIFORM: (x >> 8) * 2^-24, in [0, 1), exact in fp32 (the sampler's inverse CDF takes it as it takes uniform_'s).
+ *   CBX_RNG_NORMAL:  Box-Muller over the word pairs (0, 1) and (2, 3) of a block: u1 = ((xa >> 8) + 1) * 2^-24 in (0, 1], u2 = (xb >> 8) * 2^-24,
+ *                    r = sqrtf(-2 logf(u1)); the even word gives r cosf(2 pi u2), the odd word r sinf(2 pi u2) (precise libm forms). */
+#define CBX_RNG_UNIFORM 0
+#define CBX_RNG_NORMAL 1
+/* the `stream` key word: what the number is for */
+#define CBX_RNG_STREAM_T3_UNIFORMS 0 /* substream 0; column = token step */
+#define CBX_RNG_STREAM_CFM_Z 1       /* substream 0; one row per request, column = frame * 80 + channel (the request's own frame index) */
+#define CBX_RNG_STREAM_VOC_PHASE 2   /* substream 0; 9 columns (harmonics) */
+#define CBX_RNG_STREAM_VOC_NOISE 3   /* substream = harmonic 0 .. 8; column = absolute sample */
+int cbx_rng_fill_f32(float* out, long ld_out, const unsigned* keys, int rows, long n, unsigned long long col0, int dist, void* stream);
+
 /* ---- voice-prompt / voice-conversion front-end ----
  * Contractions (framed DFT as a GEMM over overlapping waveform rows, mel filterbanks, Conv1d/Conv2d-as-Toeplitz, attention, LSTM
  * projections) use cbx_gemm_f32 / cbx_flash_attn_f32 / cbx_gemv_f32; these are the remaining element-wise / reduction passes. */
