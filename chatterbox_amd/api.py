@@ -192,6 +192,13 @@ def _seed_kw(seed):
     if isinstance(seed, bool) or not isinstance(seed, int):
         raise TypeError(f"seed: expected an int, got {type(seed).__name__}")
     return dict(seeds=ops.check_seeds(seed, 1, "seed"))
+
+
+def _speed_kw(speed, B=1):
+    """`speed` as the engines' speed= keyword ({} at 1.0 / None: the call is then exactly the one without it).  generate: one number; generate_batch: a number
+    or a sequence of B (entries may be None: 1.0).  TypeError / ValueError (ops.check_speed: numbers in [0.5, 2.0]) before anything is launched."""
+    speed = ops.check_speed(speed, B)
+    return {} if speed is None else dict(speed=speed)
 # T3 cond dicts of a voice, kept while its T3Cond lives (generate_batch): id(T3Cond) -> [emotion tensor the entry was built from, its value, {exaggeration: dict}]
 _T3_DICTS = {}
 
@@ -255,10 +262,10 @@ class _BatchMixin:
         assert all(c is not None for c in out), "Please `prepare_conditionals` first or specify `audio_prompt_path`"
         return out
 
-    def _run_batch(self, tokens, voices, exaggeration, samp, generator, synth_kw, n_draws, seeds=None):
+    def _run_batch(self, tokens, voices, exaggeration, samp, generator, synth_kw, n_draws, seeds=None, speed=None):
         """Sub-batches of at most max_batch requests in order of text length: one sub-batch runs the serial schedule (synthesize), several the throughput schedule
         (synthesize_pipelined; an engine without one runs them one after the other).  Returns the finished waveforms in the caller's order.  seeds (B ints or None)
-        travel with their requests: a request's draws do not depend on the sub-batch or the row it lands in."""
+        travel with their requests: a request's draws do not depend on the sub-batch or the row it lands in.  speed (B floats or None) travels the same way."""
         B = len(tokens)
         dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
         plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
@@ -271,6 +278,8 @@ class _BatchMixin:
                 job["generator"] = generator
             if seeds is not None:
                 job["seeds"] = _pick(seeds, idx)
+            if speed is not None:
+                job["speed"] = _pick(speed, idx)
             jobs.append(job)
         out = [None] * B
         if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined"):
@@ -335,15 +344,16 @@ class _Base(_BatchMixin):
     def _analyse(self, wav_fpath, exaggeration):
         return _prepare_conditionals(self.analyzer, wav_fpath, exaggeration, self.PROMPT_LEN, self.device)
 
-    def _generate_batch(self, B, tokenize, audio_prompt_paths, conds, exaggeration, drop_last_token, generator, seeds=None, **samp):
+    def _generate_batch(self, B, tokenize, audio_prompt_paths, conds, exaggeration, drop_last_token, generator, seeds=None, speed=None, **samp):
         """Validation of every per-request argument, then tokenisation (`tokenize()` -> B id tensors), then the device work."""
         seeds = _batch_seeds(seeds, B, generator)
+        speed = ops.check_speed(speed, B)
         samp = _sampling_lists(B, **samp)
         exaggeration = _sampling_lists(B, exaggeration=exaggeration)["exaggeration"]
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, exaggeration)
         sot, eot = 255, 0
         tts = [torch.cat([torch.tensor([sot]), t.view(-1).long().cpu(), torch.tensor([eot])]) for t in tokenize()]
-        return self._run_batch(tts, voices, exaggeration, samp, generator, dict(max_new_tokens=1000, drop_last_token=drop_last_token), 1000, seeds)
+        return self._run_batch(tts, voices, exaggeration, samp, generator, dict(max_new_tokens=1000, drop_last_token=drop_last_token), 1000, seeds, speed)
 
     @classmethod
     def from_synthetic(cls, device="cuda", seed=0, t3_layers=30, **kw):
@@ -380,10 +390,13 @@ class ChatterboxTTS(_Base):
         return cls.from_local(Path(local).parent, device)
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
-                 cfg_weight=0.5, temperature=0.8, seed=None):
+                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
-        alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch."""
-        seed_kw = _seed_kw(seed)
+        alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
+        speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
+        the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
+        speed 1.0 gives K * 480."""
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
         if audio_prompt_path:
             self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
         else:
@@ -394,7 +407,7 @@ class ChatterboxTTS(_Base):
                               repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
-                       min_p=0.05, top_p=1.0, generator=None, seeds=None):
+                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
         request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
         neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
@@ -402,11 +415,13 @@ class ChatterboxTTS(_Base):
         of text length through the throughput schedule.  Never overwrites self.conds.
         seeds (None, an int for every request, or a sequence of B ints in [0, 2^64); not together with a generator): request b's random draws depend on seeds[b]
         alone -- not on the other requests, its row, the sub-batch split or the order of calls -- and are those of generate(seed=seeds[b]).  Its tokens and audio
-        then agree with that call's as far as batched and single arithmetic agree: the kernels pick their forms by row count, so this is not bit equality."""
+        then agree with that call's as far as batched and single arithmetic agree: the kernels pick their forms by row count, so this is not bit equality.
+        speed (a number for every request, or a sequence of B numbers in [0.5, 2.0]; None entries are 1.0): request b's speaking rate, generate(speed=)'s; it
+        travels with its request through the sub-batches like its seed."""
         texts = [texts] if isinstance(texts, str) else list(texts)
         assert len(texts) >= 1, "empty batch"
         return self._generate_batch(len(texts), lambda: [self.tokenizer.text_to_tokens(punc_norm_en(t)) for t in texts], audio_prompt_paths, conds, exaggeration,
-                                    False, generator, seeds, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+                                    False, generator, seeds, speed, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                         cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None):
@@ -452,10 +467,13 @@ class ChatterboxMultilingualTTS(_Base):
         return cls.from_local(d, device, t3_model=t3_model)
 
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None):
+                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
-        alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch."""
-        seed_kw = _seed_kw(seed)
+        alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
+        speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
+        the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
+        speed 1.0 gives K * 480."""
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
         if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
             raise ValueError(f"Unsupported language_id '{language_id}'. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
         if audio_prompt_path:
@@ -468,17 +486,18 @@ class ChatterboxMultilingualTTS(_Base):
                               repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None):
+                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does."""
         texts = [texts] if isinstance(texts, str) else list(texts)
         assert len(texts) >= 1, "empty batch"
         seeds = _batch_seeds(seeds, len(texts), generator)
+        speed = ops.check_speed(speed, len(texts))
         langs = _per_request(language_ids, len(texts), "language_ids", (str,))
         for k, lid in enumerate(langs):
             if lid and lid.lower() not in SUPPORTED_LANGUAGES:
                 raise ValueError(f"Unsupported language_id '{lid}' (request {k}). Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
         tok = lambda: [self.tokenizer.text_to_tokens(punc_norm(t), language_id=lid.lower() if lid else None) for t, lid in zip(texts, langs)]
-        return self._generate_batch(len(texts), tok, audio_prompt_paths, conds, exaggeration, True, generator, seeds, temperature=temperature, cfg_weight=cfg_weight,
+        return self._generate_batch(len(texts), tok, audio_prompt_paths, conds, exaggeration, True, generator, seeds, speed, temperature=temperature, cfg_weight=cfg_weight,
                                     repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
@@ -560,10 +579,13 @@ class ChatterboxTurboTTS(_BatchMixin):
         return wav.unsqueeze(0)
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
-                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None):
+                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
-        alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch."""
-        seed_kw = _seed_kw(seed)
+        alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
+        speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
+        the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
+        speed 1.0 gives K * 480."""
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
         if audio_prompt_path:
             self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, norm_loudness=norm_loudness)
         else:
@@ -579,13 +601,14 @@ class ChatterboxTurboTTS(_BatchMixin):
                                      enc_cond_len=self.ENC_COND_LEN)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
-                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None):
+                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0):
         """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
-        of B).  CFG, min_p and exaggeration are not supported by this backbone: ignored with generate()'s warning.  Sub-batches run one after the other.  seeds: as ChatterboxTTS.generate_batch."""
+        of B).  CFG, min_p and exaggeration are not supported by this backbone: ignored with generate()'s warning.  Sub-batches run one after the other.  seeds, speed: as ChatterboxTTS.generate_batch."""
         texts = [texts] if isinstance(texts, str) else list(texts)
         B = len(texts)
         assert B >= 1, "empty batch"
         seeds = _batch_seeds(seeds, B, generator)
+        speed = ops.check_speed(speed, B)
         samp = _sampling_lists(B, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         ign = _sampling_lists(B, cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p)
         if any(v > 0.0 for vals in ign.values() for v in vals):
@@ -593,7 +616,7 @@ class ChatterboxTurboTTS(_BatchMixin):
             logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, ign["exaggeration"], lambda p, ex: self._analyse(p, ex, norm_loudness=norm_loudness))
         ids = [self.tokenizer(punc_norm_turbo(t), return_tensors="pt", padding=True, truncation=True).input_ids[0].view(-1).long().cpu() for t in texts]
-        return self._run_batch(ids, voices, ign["exaggeration"], samp, generator, dict(max_gen_len=1000), 1001, seeds)
+        return self._run_batch(ids, voices, ign["exaggeration"], samp, generator, dict(max_gen_len=1000), 1001, seeds, speed)
 
     def _finish(self, wav):
         wav = wav.detach().float().cpu()
@@ -698,10 +721,13 @@ class ChatterboxVC:
             wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
         return wav.unsqueeze(0)
 
-    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None):
+    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0):
         """reference vc.py:83-104.  audio: a WAV path or a (waveform, sample_rate) pair.  seed (None, or an int in [0, 2^64)): the flow noise and the vocoder's
-        phase and noise are a function of the seed alone (no torch RNG is consumed), those generate_batch(seeds=) gives the request in any batch."""
-        seed_kw = _seed_kw(seed)
+        phase and noise are a function of the seed alone (no torch RNG is consumed), those generate_batch(seeds=) gives the request in any batch.
+        speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
+        the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
+        speed 1.0 gives K * 480."""
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
         wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **seed_kw)
         return self._finish(wavs[0])
 
@@ -736,18 +762,20 @@ class ChatterboxVC:
 
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 
-    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None):
+    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0):
         """generate() for B conversions in one call: `audios` (WAV paths or (waveform, sample_rate) pairs) or `s3_tokens` (B id sequences); target voice per
         request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
         self.ref_dict.  Returns B CPU float32 tensors (1, n_b) at `.sr` in the caller's order; more than MAX_BATCH requests run as sub-batches in order of length.
         Never overwrites self.ref_dict.  seeds (None, an int for every request, or a sequence of B ints in [0, 2^64)): request b's noise depends on seeds[b]
-        alone and is that of generate(seed=seeds[b]) (ChatterboxTTS.generate_batch states the guarantee)."""
+        alone and is that of generate(seed=seeds[b]) (ChatterboxTTS.generate_batch states the guarantee).  speed: a number, or a sequence of B numbers in
+        [0.5, 2.0] (None entries: 1.0) -- request b's speaking rate, generate(speed=)'s."""
         src = s3_tokens if s3_tokens is not None else audios
         assert src is not None, "give audios or s3_tokens"
         src = [src] if (isinstance(src, _PATH) or (torch.is_tensor(src) and src.dim() <= 1)) else list(src)
         B = len(src)
         assert B >= 1, "empty batch"
         seeds = _batch_seeds(seeds, B)
+        speed = ops.check_speed(speed, B)
         if target_voice_paths is not None and ref_dicts is not None:
             raise ValueError("give target_voice_paths or ref_dicts, not both")
         if target_voice_paths is not None:
@@ -775,7 +803,8 @@ class ChatterboxVC:
         toks = [torch.as_tensor(t).view(-1).long().cpu() for t in toks]
         out = [None] * B
         for idx in batch_plan([int(t.numel()) for t in toks], int(self.MAX_BATCH)):
-            wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **({} if seeds is None else dict(seeds=_pick(seeds, idx))))
+            wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **({} if seeds is None else dict(seeds=_pick(seeds, idx))),
+                                         **({} if speed is None else dict(speed=_pick(speed, idx))))
             for i, w in zip(idx, wavs):
                 w = w.detach().float().cpu()
                 if self.watermarker is not None:

@@ -83,15 +83,22 @@ class ChatterboxEngine:
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None, seeds=None):
+               generator=None, seeds=None, speed=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
         that is not injected (None: the global RNG).  seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance) -- the noise that is not injected
         is then a function of the utterance's seed alone (ops.seeded_z / seeded_phase / seeded_noise: cbx_rng_fill_f32), whatever its row and the batch around it,
-        and no torch RNG is consumed; not together with a generator."""
+        and no torch RNG is consumed; not together with a generator.
+        speed: None, a number or B numbers in [0.5, 2.0] (ops.check_speed; None entries are 1.0) -- the speaking rate.  None or all 1.0: exactly the call without
+        it.  Otherwise the flow runs as ever and ONE ops.mel_time_scale launch stretches row b's M_b = 2 n_b - short_b valid mel frames to O_b =
+        ops.scaled_len(M_b, speed[b]) (models/s3gen/s3gen.py:289 leaves this out); the vocoder runs on the stretched mel with lens = O_b, so the F0 predictor
+        sees it and the pitch is kept.  Utterance b's waveform is max(1, floor(K_b / speed[b])) * 480 samples where the unscaled call returns K_b * 480.
+        Noise and phase that are not injected are sized from the stretched mel; injected ones must have ITS shapes: phase (B, 9), noise
+        (B, 9, 480 * max_b O_b).  z is the flow's and does not change.  The returned mel stays the unscaled flow mel."""
         B = len(speech_tokens)
         seeds = ops.request_seeds(seeds, B, generator)
+        speed = ops.check_speed(speed, B)
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
         tok = torch.zeros(B, Nmax, dtype=torch.long)
@@ -110,18 +117,21 @@ class ChatterboxEngine:
                 torch.cuda.synchronize()
             t1 = time.perf_counter()
             # short_b > 0 only when the prompt mel has an odd frame more than 2 * prompt tokens (flow.py:170-195); per voice when the batch mixes voices
-            mel_lens = None if same and len(set(shorts)) == 1 else (2 * lens - torch.tensor(shorts, dtype=torch.int32)).to(self.dev)
+            if speed is None:
+                vmel, mel_lens = mel, None if same and len(set(shorts)) == 1 else (2 * lens - torch.tensor(shorts, dtype=torch.int32)).to(self.dev)
+            else:  # the vocoder's input is the stretched mel; lens always: the rows differ
+                vmel, mel_lens = ops.mel_time_scale(mel, speed, in_lens=[2 * n - sh for n, sh in zip(ns, shorts)])
             if hift_stream is not None:
                 ev = torch.cuda.Event()
                 ev.record()
                 with torch.cuda.stream(hift_stream):
                     hift_stream.wait_event(ev)
-                    mel.record_stream(hift_stream)
+                    vmel.record_stream(hift_stream)
                     if mel_lens is not None:
                         mel_lens.record_stream(hift_stream)
-                    wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator, seeds=seeds)
+                    wav, _ = self.hift.inference(vmel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator, seeds=seeds)
             else:
-                wav, _ = self.hift.inference(mel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator, seeds=seeds)
+                wav, _ = self.hift.inference(vmel, phase=phase, noise=noise, lens=mel_lens, fade=True, generator=generator, seeds=seeds)
             if sync:
                 torch.cuda.synchronize()
             t2 = time.perf_counter()
@@ -132,19 +142,24 @@ class ChatterboxEngine:
         out = []
         for b, n in enumerate(ns):
             keep = max(1, n - 1) if drop_last_token else n
-            out.append(wav[b, : min(keep * SAMPLES_PER_TOKEN, (2 * n - shorts[b]) * (SAMPLES_PER_TOKEN // 2))])
+            frames = min(2 * keep, 2 * n - shorts[b])  # K_b: what the unscaled call returns, in mel frames of 480 samples
+            if speed is not None:
+                frames = ops.scaled_len(frames, speed[b])
+            out.append(wav[b, : frames * (SAMPLES_PER_TOKEN // 2)])
         return out, mel
 
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None):
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
-        (T3Engine.generate(seeds=), vocode(seeds=)); not together with a generator."""
+        (T3Engine.generate(seeds=), vocode(seeds=)); not together with a generator.
+        speed: None, a number or B numbers in [0.5, 2.0]: the speaking rate of vocode(speed=); T3 and its tokens do not depend on it."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
+        speed = ops.check_speed(speed, len(text_tokens))
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
@@ -155,7 +170,7 @@ class ChatterboxEngine:
         st = [drop_invalid_tokens(t) for t in toks]
         st = [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
-                              drop_last_token=drop_last_token, generator=generator, seeds=seeds)
+                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed)
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
@@ -181,7 +196,7 @@ class ChatterboxEngine:
         (wavs, tokens, latency_s) per job in order.  Results are identical to synthesize() called per job.  A job may carry sampling parameters of its own
         (temperature, top_p, min_p, repetition_penalty, cfg_weight: scalar or one per utterance; they override **kw for that job) and a `generator` for the flow / vocoder noise that is not injected (the
         sampling draws of a repeatable job are injected as `uniforms`: T3 is enqueued by another host thread), or `seeds` (one int per utterance, or one int for all:
-        every draw of the job that is not injected, as synthesize(seeds=); not together with a generator).
+        every draw of the job that is not injected, as synthesize(seeds=); not together with a generator), or `speed` (a number or one per utterance: vocode(speed=)).
 
         What makes the two stages actually overlap (round 5, profiles/r05_overlap_*; none of it changes a result):
           * co_resident: a chain of small dependent kernels keeps its pace beside chip-filling kernels of another stream only if its workgroups FIT
@@ -194,6 +209,7 @@ class ChatterboxEngine:
             calls of the C stage seams release the GIL)."""
         import threading
         jobs = [dict(job, seeds=ops.request_seeds(job["seeds"], len(job["text_tokens"]), job.get("generator"))) if job.get("seeds") is not None else job for job in jobs]
+        jobs = [dict(job, speed=ops.check_speed(job["speed"], len(job["text_tokens"]))) if job.get("speed") is not None else job for job in jobs]
         torch.cuda.set_device(self.dev)  # a generator cannot hold a device guard across yields: pin the device for the caller
         self._pipeline_streams(stream_priorities)
         t3_kw = {k: kw[k] for k in ("max_new_tokens", "temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight", "ban_eos",
@@ -221,7 +237,7 @@ class ChatterboxEngine:
             with torch.cuda.stream(self._s_voc):
                 def voc():
                     wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
-                                          n_cfm_timesteps=kw.get("n_cfm_timesteps", 10),
+                                          speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10),
                                           drop_last_token=kw.get("drop_last_token", True), sync=False)
                     return [w.cpu() for w in wavs]  # D2H on the vocoder stream: returns when this batch's audio is on the host
                 return _range_checked(self, voc)
@@ -290,7 +306,7 @@ class ChatterboxEngine:
         def start_voc(job, st, which):
             ops.select_range_flag(self.dev, which)
             with torch.cuda.stream(self._s_voc):
-                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), sync=False, **voc_kw)
+                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), speed=job.get("speed"), sync=False, **voc_kw)
                 host = [torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True) for w in wavs]
                 ev = torch.cuda.Event()
                 ev.record()
@@ -306,7 +322,7 @@ class ChatterboxEngine:
                 self.flow.precision, self.hift.precision = (6 if p == 16 else p for p in saved)
                 try:
                     with torch.cuda.stream(self._s_voc):
-                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), sync=False, **voc_kw)
+                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), speed=job.get("speed"), sync=False, **voc_kw)
                         host = [w.cpu() for w in wavs]
                 finally:
                     self.flow.precision, self.hift.precision = saved
@@ -709,10 +725,12 @@ class TurboEngine:
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
-        for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=)."""
+        for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=);
+        speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=)."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
+        speed = ops.check_speed(speed, len(text_tokens))
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                 repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
@@ -720,7 +738,7 @@ class TurboEngine:
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
-        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds)
+        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed)
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 

@@ -874,6 +874,80 @@ def seeded_noise(seeds, n, device, col0=0):
     return noise
 
 
+# ----------------------------------------------------------------------------- speed control: the mel stretched along time (cbx_mel_time_scale_f32)
+
+SPEED_MIN, SPEED_MAX = 0.5, 2.0
+
+
+def scaled_len(n, rate):
+    """Frames (or any other unit of time) that `n` of them become at speaking rate `rate`: max(1, floor(n / rate)) in Python floats.  THE definition: the
+    kernel's out_lens, the vocoder's lens and the trim of the waveform all come from here."""
+    import math
+    return max(1, int(math.floor(int(n) / float(rate))))
+
+
+def check_speed(value, B, name="speed"):
+    """A `speed` argument as a list of B floats, or None when no request is scaled (None, or every entry 1.0 or None).  A number serves every request; anything
+    else must be a list or tuple of exactly B numbers (or None: 1.0) in [0.5, 2.0].  A bool or a non-number is a TypeError; a non-finite or out-of-range value and
+    a wrong length are ValueErrors -- raised before anything is launched."""
+    import math
+    import numbers
+    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    if value is None:
+        return None
+    if one(value):
+        value = [value] * B
+    elif not isinstance(value, (list, tuple)):
+        raise TypeError(f"{name}: expected a number or a list of {B} numbers, got {type(value).__name__}")
+    if len(value) != B:
+        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
+    out = []
+    for k, v in enumerate(value):
+        if v is None:
+            v = 1.0
+        if not one(v):
+            raise TypeError(f"{name}[{k}]: expected a number, got {type(v).__name__}")
+        v = float(v)
+        if not math.isfinite(v) or not SPEED_MIN <= v <= SPEED_MAX:
+            raise ValueError(f"{name}[{k}] = {v}: a speed is a finite number in [{SPEED_MIN}, {SPEED_MAX}]")
+        out.append(v)
+    return None if all(v == 1.0 for v in out) else out
+
+
+def mel_time_scale(mel, rates, in_lens=None, out=None):
+    """cbx_mel_time_scale_f32: mel (B, T_in, C) fp32 channel-last (any batch / row stride, unit channel stride) stretched along time, row b at rates[b] (B Python
+    floats) over its in_lens[b] valid frames (B ints on the host; None: T_in) -> (out, out_lens): out (B, T_out, C), frames from scaled_len(in_lens[b], rates[b])
+    on zero, and out_lens the (B,) int32 device tensor of those lengths (what the vocoder takes as `lens`).  out: None (a fresh contiguous tensor, T_out = the
+    longest row) or a (B, T_out, C) fp32 view with unit channel stride that holds the longest row; its columns beyond C are not touched."""
+    assert mel.dim() == 3 and mel.shape[2] >= 1 and (mel.shape[2] == 1 or mel.stride(2) == 1), "mel_time_scale: mel is (B, T_in, C) with unit channel stride"
+    B, T_in, C = mel.shape
+    rates = [float(r) for r in rates]
+    M = [T_in] * B if in_lens is None else [int(v) for v in in_lens]
+    if len(rates) != B or len(M) != B:
+        raise ValueError(f"mel_time_scale: {len(rates)} rates and {len(M)} lengths for {B} rows")
+    if not all(0 <= m <= T_in for m in M):
+        raise ValueError(f"mel_time_scale: in_lens {M} outside [0, {T_in}]")
+    O = [scaled_len(m, r) for m, r in zip(M, rates)]
+    if out is None:
+        out = torch.empty(B, max(O), C, device=mel.device)
+    assert out.dim() == 3 and out.shape[0] == B and out.shape[2] == C and (C == 1 or out.stride(2) == 1) and out.device == mel.device, "mel_time_scale: out is (B, T_out, C)"
+    T_out = out.shape[1]
+    if max(O) > T_out:
+        raise ValueError(f"mel_time_scale: out holds {T_out} frames, the longest row needs {max(O)}")
+    # rates (B doubles), in_lens and out_lens (B ints each) travel as ONE pinned buffer and one asynchronous copy: a pageable copy would hold the host until the
+    # flow in front of it on this stream has finished, which is what the throughput schedule (sync=False) must not do
+    dev = mel.device
+    host = torch.empty(4 * B, dtype=torch.int32, pin_memory=dev.type == "cuda")
+    host[: 2 * B].view(torch.float64).copy_(torch.tensor(rates, dtype=torch.float64))
+    host[2 * B:].copy_(torch.tensor(M + O, dtype=torch.int32))
+    args = host.to(dev, non_blocking=True)
+    sb = lambda t, T: t.stride(0) if B > 1 else max(t.stride(0), T * t.stride(1), C)  # (the stride of a dimension of size 1 is arbitrary)
+    check(lib.cbx_mel_time_scale_f32(_p(_f32(mel, "mel")), sb(mel, T_in), mel.stride(1) if T_in > 1 else max(mel.stride(1), C), T_in,
+                                     None if in_lens is None else args.data_ptr() + 8 * B, args.data_ptr(), _p(_f32(out, "out")), sb(out, T_out),
+                                     out.stride(1) if T_out > 1 else max(out.stride(1), C), T_out, args.data_ptr() + 12 * B, B, C, _stream()), "cbx_mel_time_scale_f32")
+    return out, args[3 * B:]
+
+
 def hift_stft(s, spec, sample_lens=None):
     B, L = s.shape
     check(lib.cbx_hift_stft_f32(_p(s), _p(spec), _p(sample_lens), B, L, spec.stride(1), _stream()), "cbx_hift_stft_f32")

@@ -804,6 +804,19 @@ int cbx_hift_istft_f32(const float* x, float* wav, int B, long frames, long ldx,
 #define CBX_RNG_STREAM_VOC_NOISE 3   /* substream = harmonic 0 .. 8; column = absolute sample */
 int cbx_rng_fill_f32(float* out, long ld_out, const unsigned* keys, int rows, long n, unsigned long long col0, int dist, void* stream);
 
+/* ---- speed control: the mel stretched along time between the flow decoder and the vocoder (added after ABI v16 without a version step: a new function only) ----
+ * The reference leaves it out (models/s3gen/s3gen.py:289: "ignoring the speed control (mel interpolation) ... for now"); the F0 predictor runs on the stretched
+ * mel, so the pitch is kept.  in (B, T_in, C) and out (B, T_out, C) channel-last with batch strides in_sb / out_sb and row strides in_ld / out_ld (floats, >= C).
+ * Row b has M = in_lens[b] valid frames (in_lens NULL: T_in) and rate s = rate[b] (s > 1: faster, fewer frames); the caller supplies out_lens[b] =
+ * max(1, floor(M / s)).  Output frame j < out_lens[b] samples the input at x = max(0, (j + 0.5) s - 0.5), evaluated in fp64:
+ *   i0 = min(floor(x), M - 1), i1 = min(i0 + 1, M - 1), l = x - i0, out[b][j] = (1 - l) in[b][i0] + l in[b][i1] in fp32
+ * -- F.interpolate(mode="linear", align_corners=False, scale_factor=1 / s, recompute_scale_factor=False) with the position in fp64 and no copy shortcut when
+ * out_lens[b] == M.  Frames [out_lens[b], T_out) are written as zeros (out_lens[b] is cut to T_out), columns [C, out_ld) are not touched, input frames from
+ * in_lens[b] on are never read.  in_lens, rate, out_lens: device memory.  One thread per output float4 when every pointer and stride allows 16-byte access, per
+ * float otherwise. */
+int cbx_mel_time_scale_f32(const float* in, long in_sb, long in_ld, int T_in, const int* in_lens, const double* rate, float* out, long out_sb, long out_ld,
+                           int T_out, const int* out_lens, int B, int C, void* stream);
+
 /* ---- voice-prompt / voice-conversion front-end ----
  * Contractions (framed DFT as a GEMM over overlapping waveform rows, mel filterbanks, Conv1d/Conv2d-as-Toeplitz, attention, LSTM
  * projections) use cbx_gemm_f32 / cbx_flash_attn_f32 / cbx_gemv_f32; these are the remaining element-wise / reduction passes. */
