@@ -153,12 +153,22 @@ def _watermarker():
         return None
 
 
-def _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window=None):
-    """The round-schedule arguments of generate_stream, passed through to the engine's synthesize_stream.  `window` is checked here, when generate_stream is
-    CALLED (the engine's generator would raise at the first next() only)."""
+def _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window=None, speed=None):
+    """The round-schedule arguments of generate_stream, passed through to the engine's synthesize_stream.  `window` and `speed` are checked here, when
+    generate_stream is CALLED (the engine's generator would raise at the first next() only); the window against the rate (engine.check_stream_window).
+    speed 1.0 / None adds no keyword: the engine call is then exactly the one without it."""
     from .engine import check_stream_window
+    speed_kw = _stream_speed_kw(speed)
     return dict(first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, overlap=overlap,
-                window=check_stream_window(window, fade))
+                window=check_stream_window(window, fade, speed_kw.get("speed")), **speed_kw)
+
+
+def _stream_speed_kw(speed):
+    """generate_stream's `speed` as the engines' speed= keyword: ONE number in [0.5, 2.0] for the stream ({} at 1.0 / None).  TypeError / ValueError
+    (engine.check_stream_speed) before anything is launched."""
+    from .engine import check_stream_speed
+    speed = check_stream_speed(speed)
+    return {} if speed is None else dict(speed=speed)
 
 
 
@@ -424,11 +434,12 @@ class ChatterboxTTS(_Base):
                                     False, generator, seeds, speed, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
-                        cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None):
+                        cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, speed=1.0):
         """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
         `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
         window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream).
-        seed: generate()'s."""
+        seed: generate()'s.  speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate -- the pieces add up to the length generate(speed=) returns;
+        checked, with the window it asks for (engine.check_stream_window), when this is called."""
         seed_kw = _seed_kw(seed)
         if audio_prompt_path:
             self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
@@ -436,7 +447,7 @@ class ChatterboxTTS(_Base):
             assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
         self._set_exaggeration(exaggeration)
         toks = self.tokenizer.text_to_tokens(punc_norm_en(text))
-        return self._generate_stream(toks, False, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window), temperature=temperature,
+        return self._generate_stream(toks, False, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature,
                                      cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
 
 
@@ -502,11 +513,12 @@ class ChatterboxMultilingualTTS(_Base):
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
-                        seed=None):
+                        seed=None, speed=1.0):
         """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
         `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
         window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream).
-        seed: generate()'s."""
+        seed: generate()'s.  speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate -- the pieces add up to the length generate(speed=) returns;
+        checked, with the window it asks for (engine.check_stream_window), when this is called."""
         seed_kw = _seed_kw(seed)
         if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
             raise ValueError(f"Unsupported language_id '{language_id}'. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
@@ -516,7 +528,7 @@ class ChatterboxMultilingualTTS(_Base):
             assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
         self._set_exaggeration(exaggeration)
         toks = self.tokenizer.text_to_tokens(punc_norm(text), language_id=language_id.lower() if language_id else None)
-        return self._generate_stream(toks, True, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window), temperature=temperature,
+        return self._generate_stream(toks, True, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature,
                                      cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
 
 
@@ -631,11 +643,12 @@ class ChatterboxTurboTTS(_BatchMixin):
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
                         temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
-                        seed=None):
+                        seed=None, speed=1.0):
         """generate() in pieces (TurboEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk`
         tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
         window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream).
-        seed: generate()'s."""
+        seed: generate()'s.  speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate -- the pieces add up to the length generate(speed=) returns;
+        checked, with the window it asks for (engine.check_stream_window), when this is called."""
         seed_kw = _seed_kw(seed)
         if audio_prompt_path:
             self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, norm_loudness=norm_loudness)
@@ -645,7 +658,7 @@ class ChatterboxTurboTTS(_BatchMixin):
             import logging
             logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
         ids = self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids
-        return self._generate_stream(ids[0], _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window), temperature=temperature, top_k=top_k,
+        return self._generate_stream(ids[0], _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature, top_k=top_k,
                                      top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
 
 
@@ -731,19 +744,20 @@ class ChatterboxVC:
         wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **seed_kw)
         return self._finish(wavs[0])
 
-    def generate_stream(self, audio=None, target_voice_path=None, s3_tokens=None, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=200, seed=None):
+    def generate_stream(self, audio=None, target_voice_path=None, s3_tokens=None, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=200, seed=None, speed=1.0):
         """generate() in pieces (ChatterboxEngine.vocode_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk` tokens of
         the source; concatenated along dim 1 they give the conversion.  A round synthesises the target voice's prompt, `window` tokens of left context, the new
         chunk and the lookahead, so its cost does not grow with the length of the source (window=None: every round re-synthesises everything so far); the
         default 200 + chunk 50 is the 250-token round the flow is tuned at.  Arguments are checked and the source is tokenised when this is CALLED, as generate
         does; self.ref_dict is written only when target_voice_path is given.  The target voice's prompt must be a whole number of tokens (2 mel frames per
-        prompt token).  If a watermarker is loaded it is applied to each piece.  seed: generate()'s; the noise of a windowed stream is then filled round by round."""
+        prompt token).  If a watermarker is loaded it is applied to each piece.  seed: generate()'s; the noise of a windowed stream is then filled round by round.
+        speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate at the bounded cost of a windowed round; the pieces add up to generate(speed=)'s length."""
         from .engine import check_stream_window
-        seed_kw = _seed_kw(seed)
+        seed_kw = dict(_seed_kw(seed), **_stream_speed_kw(speed))
         for name, v, lo in (("first_chunk", first_chunk, 1), ("chunk", chunk, 1), ("lookahead", lookahead, 0), ("fade", fade, 0)):
             if isinstance(v, bool) or not isinstance(v, int) or v < lo:
                 raise ValueError(f"{name}={v!r}: expected an int >= {lo}")
-        check_stream_window(window, fade)
+        check_stream_window(window, fade, seed_kw.get("speed"))
         if not chunk_growth >= 1.0:
             raise ValueError(f"chunk_growth={chunk_growth!r}: expected a number >= 1")
         if audio is None and s3_tokens is None:

@@ -10,6 +10,10 @@
 // Memory-bound and tiny: one thread per output float4 (two 16-byte loads, one 16-byte store) when pointers and strides allow 16-byte access, one thread per
 // float otherwise; plain loads and stores, no LDS.  Frames [out_lens[b], T_out) are written as zeros; columns [C, row stride) are not touched; input frames from
 // in_lens[b] on are never read.
+//
+// cbx_mel_time_scale_win_f32 evaluates a WINDOW of the same map for the streaming rounds (engine._stream_rounds(speed=)): output frame jj is absolute frame
+// j0 + jj, the input's frame 0 is absolute frame i_org, the position comes from the one device function both kernels share (mel_taps), and the tap indices are
+// clamped into the window whatever the host passes.
 #include <math.h>
 
 #include "cbx_common.h"
@@ -18,6 +22,38 @@ namespace {
 
 // (1 - l) a + l b: 1 - l, l b and the fma round once each
 __device__ __forceinline__ float blend(float a, float b, float l) { return fmaf(1.0f - l, a, l * b); }
+
+// The taps of ABSOLUTE output frame j at rate s, for an input whose frame 0 is absolute frame i_org and which holds M frames: THE position expression of both
+// kernels -- x = max(0, (j + 0.5) s - 0.5) as one contracted fp64 multiply-add -- so a window of the map (mel_time_scale_win_kernel) reproduces the whole map's
+// bits.  i0 / i1 are indices INTO the input, clamped to [0, M - 1] whatever j, s and i_org are (M >= 1); l is cut to [0, 1].
+struct mel_taps_t {
+    int i0, i1;
+    float l;
+};
+__device__ __forceinline__ mel_taps_t mel_taps(long j, double s, long i_org, int M) {
+    const double x = fmax(0.0, ((double)j + 0.5) * s - 0.5);  // (a NaN rate gives 0; an infinite one is cut by the min below)
+    const double r = floor(x) - (double)i_org;                // exact: both are integers far below 2^53
+    mel_taps_t t;
+    t.i0 = r < (double)(M - 1) ? (r > 0.0 ? (int)r : 0) : M - 1;
+    t.i1 = t.i0 + 1 < M ? t.i0 + 1 : M - 1;
+    t.l = (float)fmin(fmax(x - (double)((long)t.i0 + i_org), 0.0), 1.0);
+    return t;
+}
+
+// out[o] = (1 - l) r0 + l r1 over VEC channels, or zeros when r0 is null
+template <int VEC>
+__device__ __forceinline__ void blend_store(float* o, const float* r0, const float* r1, float l) {
+    if (VEC == 4) {
+        if (!r0) {
+            *reinterpret_cast<f32x4*>(o) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            return;
+        }
+        const f32x4 a = *reinterpret_cast<const f32x4*>(r0), bb = *reinterpret_cast<const f32x4*>(r1);
+        *reinterpret_cast<f32x4*>(o) = f32x4{blend(a[0], bb[0], l), blend(a[1], bb[1], l), blend(a[2], bb[2], l), blend(a[3], bb[3], l)};
+    } else {
+        *o = r0 ? blend(*r0, *r1, l) : 0.0f;
+    }
+}
 
 // grid (ceil(T_out * CV / 256), B): thread = (output frame j, channel group c) of batch row blockIdx.y; CV = C / VEC channel groups of VEC floats
 template <int VEC>
@@ -34,26 +70,36 @@ __global__ __launch_bounds__(256) void mel_time_scale_kernel(const float* __rest
     O = O < T_out ? O : T_out;  // the host entry cannot see out_lens: clamped here
     float* o = out + (long)b * out_sb + (long)j * out_ld + c;
     if (j >= O || M <= 0) {
-        if (VEC == 4) {
-            *reinterpret_cast<f32x4*>(o) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        } else {
-            *o = 0.0f;
-        }
+        blend_store<VEC>(o, nullptr, nullptr, 0.0f);
         return;
     }
-    const double x = fmax(0.0, ((double)j + 0.5) * rate[b] - 0.5);  // (a NaN rate gives 0; an infinite one is cut by the min below)
-    const double fx = floor(x);
-    const int i0 = fx < (double)(M - 1) ? (int)fx : M - 1;
-    const int i1 = i0 + 1 < M ? i0 + 1 : M - 1;
-    const float l = (float)fmin(x - (double)i0, 1.0);
-    const float* r0 = in + (long)b * in_sb + (long)i0 * in_ld + c;
-    const float* r1 = in + (long)b * in_sb + (long)i1 * in_ld + c;
-    if (VEC == 4) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(r0), bb = *reinterpret_cast<const f32x4*>(r1);
-        *reinterpret_cast<f32x4*>(o) = f32x4{blend(a[0], bb[0], l), blend(a[1], bb[1], l), blend(a[2], bb[2], l), blend(a[3], bb[3], l)};
-    } else {
-        *o = blend(*r0, *r1, l);
+    const mel_taps_t p = mel_taps(j, rate[b], 0, M);
+    const float* row = in + (long)b * in_sb + c;
+    blend_store<VEC>(o, row + (long)p.i0 * in_ld, row + (long)p.i1 * in_ld, p.l);
+}
+
+// A WINDOW of the same map (cbx_mel_time_scale_win_f32): output frame jj is absolute frame j0 + jj, input frame 0 is absolute frame i_org, one rate for all rows.
+// Same grid, same dispatch, same loads and stores as the kernel above.
+template <int VEC>
+__global__ __launch_bounds__(256) void mel_time_scale_win_kernel(const float* __restrict__ in, long in_sb, long in_ld, int T_in, const int* __restrict__ in_lens,
+                                                                 double rate, long j0, long i_org, float* __restrict__ out, long out_sb, long out_ld, int T_out,
+                                                                 const int* __restrict__ out_lens, int CV) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)T_out * CV) return;
+    const int b = blockIdx.y;
+    const int jj = (int)(t / CV), c = (int)(t - (long)jj * CV) * VEC;
+    int M = in_lens ? in_lens[b] : T_in;
+    M = M < T_in ? M : T_in;  // never read past the buffer, whatever in_lens holds
+    int O = out_lens[b];
+    O = O < T_out ? O : T_out;
+    float* o = out + (long)b * out_sb + (long)jj * out_ld + c;
+    if (jj >= O || M <= 0) {
+        blend_store<VEC>(o, nullptr, nullptr, 0.0f);
+        return;
     }
+    const mel_taps_t p = mel_taps(j0 + jj, rate, i_org, M);  // indices into the window, clamped to [0, M - 1] whatever the host passed
+    const float* row = in + (long)b * in_sb + c;
+    blend_store<VEC>(o, row + (long)p.i0 * in_ld, row + (long)p.i1 * in_ld, p.l);
 }
 
 }  // namespace
@@ -77,4 +123,27 @@ extern "C" int cbx_mel_time_scale_f32(const float* in, long in_sb, long in_ld, i
         hipLaunchKernelGGL(mel_time_scale_kernel<1>, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, in, in_sb, in_ld, T_in, in_lens, rate, out,
                            out_sb, out_ld, T_out, out_lens, CV);
     return cbx_check_launch("mel_time_scale");
+}
+
+extern "C" int cbx_mel_time_scale_win_f32(const float* in, long in_sb, long in_ld, int T_in, const int* in_lens, double rate, long j0, long i_org, float* out,
+                                          long out_sb, long out_ld, int T_out, const int* out_lens, int B, int C, void* stream) {
+    CBX_REQUIRE(in && out && out_lens, "mel_time_scale_win: null pointer");
+    CBX_REQUIRE(C > 0, "mel_time_scale_win: C = %d", C);
+    CBX_REQUIRE(in_ld >= C && out_ld >= C && in_sb >= C && out_sb >= C, "mel_time_scale_win: a stride is below C = %d (in %ld / %ld, out %ld / %ld)", C, in_sb,
+                in_ld, out_sb, out_ld);
+    CBX_REQUIRE(B >= 0 && B <= 65535 && T_in >= 0 && T_out >= 0, "mel_time_scale_win: bad shape (B %d, T_in %d, T_out %d)", B, T_in, T_out);
+    CBX_REQUIRE(rate > 0.0 && rate < INFINITY && j0 >= 0 && i_org >= 0 && j0 < (1l << 40) && i_org < (1l << 40),
+                "mel_time_scale_win: bad window (rate %g, j0 %ld, i_org %ld)", rate, j0, i_org);
+    if (B == 0 || T_out == 0) return 0;
+    const bool vec = C % 4 == 0 && in_ld % 4 == 0 && out_ld % 4 == 0 && in_sb % 4 == 0 && out_sb % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    const int CV = vec ? C / 4 : C;
+    const long n = (long)T_out * CV, gx = (n + 255) / 256;
+    CBX_REQUIRE(gx <= 0x7fffffffl, "mel_time_scale_win: T_out * C too large for one launch");
+    if (vec)
+        hipLaunchKernelGGL(mel_time_scale_win_kernel<4>, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, in, in_sb, in_ld, T_in, in_lens, rate, j0,
+                           i_org, out, out_sb, out_ld, T_out, out_lens, CV);
+    else
+        hipLaunchKernelGGL(mel_time_scale_win_kernel<1>, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, in, in_sb, in_ld, T_in, in_lens, rate, j0,
+                           i_org, out, out_sb, out_ld, T_out, out_lens, CV);
+    return cbx_check_launch("mel_time_scale_win");
 }

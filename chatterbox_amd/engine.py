@@ -5,6 +5,7 @@ speech tokens are stripped of SOS/EOS (`drop_invalid_tokens`, s3tokenizer/__init
 on the padded batch, and each waveform is cut to its own length (the multilingual path also drops the last
 token's 40 ms, mtl_tts.py:348-352).
 """
+import math
 import os
 import time
 import warnings
@@ -380,14 +381,38 @@ def stream_token_schedule(n_tokens, first_chunk=25, chunk=50, lookahead=3, chunk
 STREAM_RECEPTIVE_FIELD = 8000  # samples of context the vocoder needs on the left of a sample (measured on the oracle: tests/test_stream_gpu.py)
 
 
-def check_stream_window(window, fade):
+def check_stream_speed(speed):
+    """The speaking rate of a stream: None (also for 1.0: the stream is then exactly the one without the argument) or ONE float in [0.5, 2.0] for all its
+    utterances (ops.check_speed).  A sequence is a TypeError: the rows of a stream share the window origin, so they share the rate."""
+    if speed is None:
+        return None
+    if isinstance(speed, (list, tuple)):
+        raise TypeError(f"speed: a stream takes one number for all its utterances, got a {type(speed).__name__}")
+    v = ops.check_speed(speed, 1)
+    return None if v is None else v[0]
+
+
+def check_stream_window(window, fade, speed=None):
     """window=None (every round re-synthesises everything so far) or a left context in TOKENS that covers the vocoder's receptive field and the cross-fade:
-    at least ceil((8000 + fade) / 960).  Anything else is a ValueError, raised before a launch."""
+    at least ceil((8000 + fade) / 960).  Anything else is a ValueError, raised before a launch.
+    speed (None, or a rate != 1 in [0.5, 2.0]): the stream is stretched, and the context the vocoder sees is counted in STRETCHED frames.  With F =
+    ceil((8000 + fade) / 480) frames, je = E // 480 the first frame not yet emitted whole, c = max(0, s - 1), ie = floor(x_je + c), a = ie // 2 - W and j0 the
+    first frame with x_j0 >= 2a + 0.25 (stream_window_origin, stream_origin_frame; x_j = (j + 0.5) s - 0.5):
+        je = (x_je + 0.5) / s - 0.5
+        x_(j0 - 1) < 2a + 0.25   =>  j0 < (2a + 0.75) / s + 0.5
+        2a <= x_je + c - 2W      =>  je - j0 > (2W - c - 0.25) / s - 1
+    so 2W >= F s + c + 0.25 gives je - j0 > F - 1, i.e. 480 (je - j0) >= 8000 + fade, the invariant a round asserts whenever a > 0.  The bound asked for is
+    ceil((F s + c + 0.5) / 2) -- 0.5 in place of 0.25 keeps the roundings of x_j in Python floats away from the edge -- and never less than the bound without a
+    rate, so the flow sees no less context than an unscaled stream gives it."""
     if window is None:
         return None
     need = -(-(STREAM_RECEPTIVE_FIELD + int(fade)) // SAMPLES_PER_TOKEN)
+    why = ""
+    if speed is not None:
+        F = -(-(STREAM_RECEPTIVE_FIELD + int(fade)) // (SAMPLES_PER_TOKEN // 2))
+        need, why = max(need, int(math.ceil((F * float(speed) + max(0.0, float(speed) - 1.0) + 0.5) / 2.0))), f" at speed={speed}"
     if isinstance(window, bool) or not isinstance(window, int) or window < need:
-        raise ValueError(f"window={window!r}: expected None or an int >= {need} tokens (the vocoder's receptive field of {STREAM_RECEPTIVE_FIELD} samples + fade={fade})")
+        raise ValueError(f"window={window!r}: expected None or an int >= {need} tokens (the vocoder's receptive field of {STREAM_RECEPTIVE_FIELD} samples + fade={fade}{why})")
     return window
 
 
@@ -395,7 +420,7 @@ def stream_window_schedule(n_tokens, first_chunk=25, chunk=50, lookahead=3, chun
     """[(a_r, n_r), ...]: round r of a stream of an utterance of `n_tokens` tokens synthesises tokens [a_r, n_r).  n_r is stream_token_schedule's; with
     window=None every a_r is 0 (the work of a round grows with r), with window=W tokens a_r = max(0, E_r // 960 - W), E_r = the samples emitted before round r
     (all but the last `fade` of what round r - 1 could vocode): once the window slides a round is W + chunk + lookahead + 1 tokens long whatever r is
-    (fade <= 960).  Pure host arithmetic: the engine computes the same a_r from what it has emitted."""
+    (fade <= 960).  Pure host arithmetic: the engine computes the same a_r from what it has emitted.  (A stream at a speaking rate: stream_speed_schedule.)"""
     window = check_stream_window(window, fade)
     out, emitted = [], 0
     for n in stream_token_schedule(n_tokens, first_chunk, chunk, lookahead, chunk_growth):
@@ -406,7 +431,85 @@ def stream_window_schedule(n_tokens, first_chunk=25, chunk=50, lookahead=3, chun
     return out
 
 
-def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade, z, phase, noise, n_cfm_timesteps, drop_last_token, window, seeds=None):
+# ---- a stream at a speaking rate s: everything upstream of the stretch (tokens, flow, z, hold_back, the window origin a) stays in unscaled units; everything
+# downstream (the vocoder's lens, noise columns, cache_source, the phase carry, emitted / end / avail, the tails, the emission's origin) is in absolute frames or
+# samples of the STRETCHED signal.  Stretched frame j is cbx_mel_time_scale_f32's function of (j, s) alone.  Host and device evaluate x_j differently (two
+# roundings here, one fused multiply-add there) and can disagree on floor(x_j) only when x_j is within an ulp of an integer:
+#   * on the LEFT of a window the origin is chosen with a quarter frame of margin (stream_origin_frame), so the device never needs a tap left of it;
+#   * on the RIGHT the disagreement is benign: there l is ~0 or ~1 and both readings blend to in[n] to within rounding (a frame the host calls ready while the
+#     device's floor is one higher reads the last frame twice, clamped; the other way round the frame is just emitted one round later).
+# Memory safety depends on neither: the kernel clamps every tap into the window (cbx_mel_time_scale_win_f32).
+def stretch_position(j, s):
+    """x_j = max(0, (j + 0.5) s - 0.5): where stretched frame j samples the unscaled mel"""
+    return max(0.0, (j + 0.5) * s - 0.5)
+
+
+def _first_frame_at(x0, s):
+    """the smallest j >= 0 with x_j >= x0"""
+    j = max(0, int(math.ceil((x0 + 0.5) / s - 0.5)))
+    while j > 0 and stretch_position(j - 1, s) >= x0:
+        j -= 1
+    while stretch_position(j, s) < x0:
+        j += 1
+    return j
+
+
+def stream_ready_frames(M_abs, s):
+    """Stretched frames [0, R) a NON-FINAL round may vocode when unscaled frames [0, M_abs) exist: both taps of frame j exist, floor(x_j) + 1 <= M_abs - 1, i.e.
+    x_j < M_abs - 1.  A frame that would clamp its right tap to the current end is not ready: it changes once more tokens arrive."""
+    return 0 if M_abs < 2 else _first_frame_at(float(M_abs - 1), s)
+
+
+def stream_round_frames(M_abs, s, final):
+    """Stretched frames [0, R) that exist after a round over unscaled frames [0, M_abs): the ready ones, or all ops.scaled_len(M_abs, s) of a final round (whose
+    last taps clamp to the end, as vocode(speed=) does)."""
+    return ops.scaled_len(M_abs, s) if final else stream_ready_frames(M_abs, s)
+
+
+def stream_origin_frame(a, s):
+    """j0: the first stretched frame all of whose taps lie at or right of unscaled frame 2a, with a margin (x_j0 >= 2a + 0.25) that host / device rounding cannot
+    cross; 0 when a == 0.  A windowed round's waveform starts at absolute stretched sample 480 j0."""
+    return 0 if a == 0 else _first_frame_at(2 * a + 0.25, s)
+
+
+def stream_window_origin(E, W, s):
+    """The window origin a (tokens) of a round that has emitted E stretched samples: je = E // 480 is the first frame not emitted whole, ie = floor(x_je) its
+    left tap, a = max(0, ie // 2 - W).  At s = 1 this is E // 960 - W.
+    For s > 1 the position is advanced by c = s - 1 first, ie = floor(x_je + c): a stretched frame then steps over MORE than one unscaled frame, the emitted count
+    trails what the last round held (M_abs = 2m frames: x_je >= 2m - 1 - s, fade <= 480) by up to 1 + s of them, and with ie = floor(x_je) a round at 1 < s < 2
+    would at times be W + chunk + lookahead + 2 tokens long; with c, x_je + c >= 2m - 2, so ie // 2 >= m - 1 and a round is at most W + chunk + lookahead + 1 tokens
+    at every rate, as without one (check_stream_window accounts for c).  1e-9 keeps a product that is an integer in exact arithmetic from rounding below it."""
+    x = stretch_position(E // (SAMPLES_PER_TOKEN // 2), s) + max(0.0, s - 1.0)
+    return max(0, int(math.floor(x + 1e-9)) // 2 - W)
+
+
+def stream_speed_schedule(n_tokens, speed=None, first_chunk=25, chunk=50, lookahead=3, chunk_growth=1.0, window=None, fade=480, drop_last_token=False):
+    """[(a_r, n_r, j0_r, E_r), ...] of a stream at speaking rate `speed`: round r synthesises tokens [a_r, n_r), its waveform starts at absolute stretched sample
+    480 j0_r, and E_r stretched samples are emitted once it is done -- the arithmetic _stream_rounds runs, for one utterance that ends with its n_tokens-th token.
+    speed None / 1.0: (a_r, n_r) are stream_window_schedule's, j0_r = 2 a_r.  The last E_r is 480 * ops.scaled_len(2 * keep, speed), what vocode(speed=) returns."""
+    s = check_stream_speed(speed)
+    W = check_stream_window(window, fade, s)
+    HALF = SAMPLES_PER_TOKEN // 2
+    out, emitted = [], 0
+    for n in stream_token_schedule(n_tokens, first_chunk, chunk, lookahead, chunk_growth):
+        final = n >= n_tokens
+        M_abs = 2 * n - (0 if final else 2 * lookahead)
+        keep = max(1, n - 1) if drop_last_token else n
+        if s is None:
+            a = 0 if W is None else max(0, emitted // SAMPLES_PER_TOKEN - W)
+            j0, avail = 2 * a, HALF * (min(M_abs, 2 * keep) if final else M_abs)
+        else:
+            a = 0 if W is None else stream_window_origin(emitted, W, s)
+            j0 = stream_origin_frame(a, s)
+            avail = HALF * max(j0, stream_round_frames(M_abs, s, final))
+            if final:
+                avail = min(avail, HALF * ops.scaled_len(2 * keep, s))
+        emitted = avail if final else max(emitted, avail - fade)
+        out.append((a, n, j0, emitted))
+    return out
+
+
+def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade, z, phase, noise, n_cfm_timesteps, drop_last_token, window, seeds=None, speed=None):
     """The state of one stream of B utterances and its round function: -> (one_round, closed flags).  one_round(toks, done, exhausted) runs flow + vocoder
     on the CURRENT stream and returns the dict the stream generators yield.  n_tokens: the most tokens an utterance can have (the default z / noise cover them).
 
@@ -423,11 +526,22 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
     finishing before the others the two forms yield the same bits.
     seeds (B ints or None): the z / phase / noise that is not injected comes from each utterance's seed (ops.seeded_*).  window=None: filled once, at the sizes of
     the unseeded defaults.  window=W: z and noise are NOT materialised for the whole budget -- a round fills the columns it reads (z frames [0, 2P) and
-    [2(P + a), 2(P + a + Nk)), noise samples [o, o + 480 frames)), which are those of the full fill by construction (cbx_rng_fill_f32's col0)."""
+    [2(P + a), 2(P + a + Nk)), noise samples [o, o + 480 frames)), which are those of the full fill by construction (cbx_rng_fill_f32's col0).
+    speed (None / 1.0: every launch and every bit of the stream without it; else ONE rate s for all rows, check_stream_speed): the flow runs as ever on tokens
+    [a, n) and ONE ops.mel_time_scale_window launch per round stretches its mel -- absolute stretched frames [j0, R_b) from the window's unscaled frames
+    [2a, 2a + frames_b), R_b = stream_round_frames (the ready frames of a row that goes on, all ops.scaled_len(2 n_b, s) of a final one), j0 =
+    stream_origin_frame(a, s) (window=None: a = j0 = 0, the whole mel so far).  From there on every quantity is in frames / samples of the STRETCHED signal: the
+    vocoder's lens, the noise columns [480 j0, ...), the cache and the phase carry (offset j0 - j0 of the last round), emitted / end / avail, the tails and the
+    emission's origin 480 j0; a = stream_window_origin(E, W, s).  trim_fade while j0 == 0.  A final row's avail is 480 * ops.scaled_len(min(2 keep, 2 n), s),
+    what vocode(speed=) returns.  Default noise is sized 480 * ops.scaled_len(2 n_tokens, s); an injected one must cover the stretched utterance; z is the
+    flow's and does not change."""
     dev = self.dev
-    W = check_stream_window(window, fade)
+    rate = check_stream_speed(speed)
+    W = check_stream_window(window, fade, rate)
     P = gen_ref["prompt_token"].shape[-1]
     N = n_tokens
+    HALF = SAMPLES_PER_TOKEN // 2  # samples per mel frame
+    n_noise = SAMPLES_PER_TOKEN * N if rate is None else HALF * ops.scaled_len(2 * N, rate)  # samples of the longest (stretched) utterance
     assert gen_ref["prompt_feat"].shape[-2] == 2 * P, "chunked synthesis needs a whole-token prompt (embed_ref output trimmed to 2 frames per token)"
     per_round = seeds is not None and W is not None  # seeded and windowed: z / noise that is not injected is filled round by round (z_frames, noise_samples)
     if seeds is not None:
@@ -435,7 +549,7 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
             phase = ops.seeded_phase(seeds, dev)
         if not per_round:
             z = ops.seeded_z(seeds, 2 * (P + N), dev) if z is None else z
-            noise = ops.seeded_noise(seeds, SAMPLES_PER_TOKEN * N, dev) if noise is None else noise
+            noise = ops.seeded_noise(seeds, n_noise, dev) if noise is None else noise
     else:
         if z is None:
             z = torch.randn(B, 2 * (P + N), 80, device=dev)
@@ -443,7 +557,7 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
             phase = (torch.rand(B, 9, device=dev) * 2 - 1) * 3.141592653589793
             phase[:, 0] = 0
         if noise is None:
-            noise = torch.randn(B, 9, SAMPLES_PER_TOKEN * N, device=dev)
+            noise = torch.randn(B, 9, n_noise, device=dev)
     z, phase, noise = None if z is None else z.to(dev), phase.to(dev).reshape(B, 9), None if noise is None else noise.to(dev)
 
     def z_frames(a, Nk):
@@ -456,44 +570,58 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
 
     def noise_samples(o, n):
         """source noise of absolute samples [o, o + n): (B, 9, n)"""
+        assert rate is None or noise is None or noise.shape[2] >= o + n, f"noise: {noise.shape[2]} samples, the stretched stream reads up to {o + n} (480 * ops.scaled_len(2 N, speed))"
         return noise[:, :, o: o + n] if noise is not None else ops.seeded_noise(seeds, n, dev, col0=o)
 
     emitted, tails, closed, cache = [0] * B, [None] * B, [False] * B, [None]
     ramp = torch.linspace(0.0, 1.0, fade + 2, device=dev)[1:-1]
-    win = dict(a=0, cum=None, tail_len=[0] * B, bufs=None, cur=0)  # window form: origin (tokens) and phase scan of the last round, the kept tails (device, ping-pong)
-    HALF = SAMPLES_PER_TOKEN // 2  # samples per mel frame
+    win = dict(a=0, j0=0, cum=None, tail_len=[0] * B, bufs=None, cur=0)  # window form: origin (tokens; vocoder frames) and phase scan of the last round, the kept tails (device, ping-pong)
 
     def one_round(toks, done, exhausted):
         """flow + vocoder over the tokens so far (window form: over the window) on the CURRENT stream -> the dict this generator yields"""
         fin, hold = _stream_plan([t.numel() for t in toks], done, exhausted, lookahead)
         st = round_tokens(toks, fin)
         ns = [int(t.numel()) for t in st]
-        a, cum_in, cache_src = 0, None, cache[0]
+        a, j0, cum_in, cache_src = 0, 0, None, cache[0]  # j0: the vocoder frame (480 samples) the round's waveform starts at
         if W is not None:
             live = [emitted[b] for b in range(B) if not closed[b]]
-            a = max(0, min(live) // SAMPLES_PER_TOKEN - W) if live else win["a"]
+            if rate is None:
+                a = max(0, min(live) // SAMPLES_PER_TOKEN - W) if live else win["a"]
+                j0 = 2 * a
+            else:
+                a = stream_window_origin(min(live), W, rate) if live else win["a"]
+                j0 = stream_origin_frame(a, rate)
+                assert a == 0 or not live or HALF * (min(live) // HALF - j0) >= STREAM_RECEPTIVE_FIELD + fade, "the window is shorter than the vocoder's receptive field + fade"
             assert all(closed[b] or ns[b] > a for b in range(B)), "an open utterance ends left of the window"
             if win["cum"] is not None:  # continue the previous round's excitation from where this window begins
-                d = a - win["a"]
-                assert 0 <= 2 * d < win["cum"].shape[2]
-                cum_in = win["cum"][:, :, 2 * d].contiguous()
-                cache_src = cache[0][:, SAMPLES_PER_TOKEN * d:] if cache[0] is not None and cache[0].shape[1] > SAMPLES_PER_TOKEN * d else None
+                d = j0 - win["j0"]
+                assert 0 <= d < win["cum"].shape[2]
+                cum_in = win["cum"][:, :, d].contiguous()
+                cache_src = cache[0][:, HALF * d:] if cache[0] is not None and cache[0].shape[1] > HALF * d else None
         ws = st if a == 0 else [t[a:] if t.numel() > a else t.new_zeros(1) for t in st]  # (a finished utterance left of the window: one dummy token)
         wn = [int(t.numel()) for t in ws]
         Nk = max(wn)
         frames = [max(0, 2 * n - hb) for n, hb in zip(wn, hold)]
+        mel_frames = frames  # the flow's frames of the window, unscaled
+        if rate is not None:  # vocoder frames of the window: absolute stretched frames [j0, R_b); a row that finished earlier only rides along
+            frames = [max(0, stream_round_frames(2 * a + f, rate, fin[b]) - j0) if f > 0 else 0 for b, f in enumerate(mel_frames)]
+            cap = max([f for b, f in enumerate(frames) if not closed[b]], default=0)
+            frames = [min(f, cap) if closed[b] else f for b, f in enumerate(frames)]
         out = [torch.zeros(0)] * B
         if max(frames) > 0:
             tok = torch.zeros(B, Nk, dtype=torch.long)
             for b, t in enumerate(ws):
                 tok[b, : wn[b]] = t
-            fl = torch.tensor(frames, dtype=torch.int32, device=dev)
-            o = SAMPLES_PER_TOKEN * a  # absolute sample of wav[:, 0]
+            fl = torch.tensor(frames, dtype=torch.int32, device=dev) if rate is None else None
+            o = HALF * j0  # absolute sample of wav[:, 0]
 
             def run():
                 mel = self.flow.inference(tok.to(dev), torch.tensor(wn, dtype=torch.int32, device=dev), gen_ref, z=z_frames(a, Nk),
                                           n_steps=n_cfm_timesteps, hold_back=hold)
-                return self.hift.inference(mel, phase=phase, noise=noise_samples(o, HALF * mel.shape[1]), lens=fl, fade=a == 0,
+                lens = fl
+                if rate is not None:  # the vocoder's input is the stretched window
+                    mel, lens = ops.mel_time_scale_window(mel, rate, j0, 2 * a, mel_frames, frames)
+                return self.hift.inference(mel, phase=phase, noise=noise_samples(o, HALF * mel.shape[1]), lens=lens, fade=j0 == 0,
                                            cache_source=cache_src, cum_in=cum_in)
             wav, src = _range_checked(self, run)
             if W is None:
@@ -504,7 +632,7 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
                     avail = HALF * frames[b]
                     if fin[b]:
                         keep = max(1, ns[b] - 1) if drop_last_token else ns[b]
-                        avail = min(avail, keep * SAMPLES_PER_TOKEN)
+                        avail = min(avail, keep * SAMPLES_PER_TOKEN if rate is None else HALF * ops.scaled_len(2 * keep, rate))
                     end = avail if fin[b] else max(emitted[b], avail - fade)
                     new = wav[b, emitted[b]: end].clone()
                     if tails[b] is not None and new.numel() > 0:
@@ -517,7 +645,7 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
             else:
                 go_on = [frames[b] for b in range(B) if not fin[b]]
                 cache[0] = src[:, : HALF * min(go_on)].clone() if go_on and min(go_on) > 0 else None
-                win.update(a=a, cum=self.hift.frame_cum)
+                win.update(a=a, j0=j0, cum=self.hift.frame_cum)
                 meta, news, nxt = torch.zeros(4, B, dtype=torch.int32), [0] * B, [0] * B
                 for b in range(B):
                     if closed[b]:
@@ -526,7 +654,7 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
                     avail = o + HALF * frames[b]
                     if fin[b]:
                         keep = max(1, ns[b] - 1) if drop_last_token else ns[b]
-                        avail = min(avail, keep * SAMPLES_PER_TOKEN)
+                        avail = min(avail, keep * SAMPLES_PER_TOKEN if rate is None else HALF * ops.scaled_len(2 * keep, rate))
                     end = avail if fin[b] else max(emitted[b], avail - fade)
                     meta[:, b] = torch.tensor([emitted[b], end, avail, win["tail_len"][b]], dtype=torch.int32)
                     news[b], nxt[b] = max(0, end - emitted[b]), 0 if fin[b] else max(0, min(avail, end + fade) - end)
@@ -548,13 +676,14 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
 
 
 def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw, round_tokens, n_extra, first_chunk, chunk, chunk_growth, lookahead, fade, z,
-                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead, window=None, seeds=None):
+                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead, window=None, seeds=None, speed=None):
     """The round schedule of synthesize_stream for either backbone (ChatterboxEngine: Llama T3, TurboEngine: GPT-2 T3; both T3 engines offer the async
     generate / advance / peek protocol).  n_budget: tokens the T3 call can sample; t3_kw: its sampling arguments; round_tokens(toks, final flags) -> the
     valid speech tokens a round vocodes (never empty); n_extra: tokens round_tokens may add (the default z / noise cover n_budget + n_extra).
     window: None, or the left context in tokens of a bounded round (_stream_rounds).  seeds: None, an int or B ints -- the sampling draws (generate(seeds=))
-    and the flow / vocoder noise (_stream_rounds) that are not injected."""
-    check_stream_window(window, fade)
+    and the flow / vocoder noise (_stream_rounds) that are not injected.  speed: None or one rate for the stream (_stream_rounds(speed=)); T3 does not depend on it,
+    so the serial and the overlapped schedule take it alike."""
+    check_stream_window(window, fade, check_stream_speed(speed))
     seeds = ops.check_seeds(seeds, len(text_tokens))
     # (a generator cannot hold a device guard across yields: pin the device for the caller; "cuda" without an index = the current device)
     pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
@@ -563,7 +692,7 @@ def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw,
     t3_kw = dict(t3_kw, async_mode=True, seeds=seeds)
     totals = stream_token_schedule(N, first_chunk, chunk, lookahead, chunk_growth)  # tokens decoded when round r starts
     one_round, closed = _stream_rounds(self, B, gen_ref, n_tokens=N + n_extra, round_tokens=round_tokens, lookahead=lookahead, fade=fade, z=z, phase=phase, noise=noise,
-                                       n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds)
+                                       n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds, speed=speed)
     if not overlap:  # the serial form of rounds 3-5: T3 waits while a round is synthesised
         h = self.t3.generate(t3_conds, text_tokens, run_steps=totals[0], **t3_kw)
         for r, n_r in enumerate(totals):
@@ -640,7 +769,7 @@ def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw,
 def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,
                       temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False,
                       ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2,
-                      window=None, seeds=None):
+                      window=None, seeds=None, speed=None):
     """Chunked synthesis: first audio after `first_chunk` tokens instead of after the whole utterance.
 
     The reference is non-streaming; of its vestigial hooks only HiFT's `cache_source` works (hifigan.py:470-472) -- `finalize=False`
@@ -662,6 +791,10 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
     stream_window_schedule); at least ceil((8000 + fade) / 960) tokens, else ValueError.  The last round is then no longer the full synthesis.
     seeds (None, an int, or B ints in [0, 2^64)): every draw that is not injected comes from its utterance's seed (synthesize(seeds=)); with a window, z and
     noise are then filled round by round and never for the whole budget (_stream_rounds).
+    speed (None, or ONE number in [0.5, 2.0] for all utterances; None / 1.0: exactly the stream without it): the speaking rate of synthesize(speed=).  Every round
+    stretches its mel (the window's, with a window) by one ops.mel_time_scale_window launch in front of the vocoder, and samples are counted in the stretched
+    signal (_stream_rounds): utterance b's pieces add up to the length synthesize(speed=) returns, and with window=None the last round vocodes the very mel the
+    one-shot call stretches.  An injected `noise` covers 480 * ops.scaled_len(2 n, speed) samples; a window must satisfy check_stream_window(window, fade, speed).
     Yields dicts {wavs: [B CPU tensors of NEW samples], final: [B bools], n_tokens: [B], tokens: [B CPU tensors: the speech tokens the round vocoded]};
     concatenating an utterance's pieces gives its waveform."""
     t3_kw = dict(max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
@@ -674,17 +807,18 @@ def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, c
     yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_new_tokens, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=0,
                                   first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                   noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                  run_ahead=run_ahead, window=window, seeds=seeds)
+                                  run_ahead=run_ahead, window=window, seeds=seeds, speed=speed)
 
 
 def vocode_stream(self, speech_tokens, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=None, z=None, phase=None,
-                  noise=None, n_cfm_timesteps=10, drop_last_token=False, seeds=None):
+                  noise=None, n_cfm_timesteps=10, drop_last_token=False, seeds=None, speed=None):
     """vocode() in rounds: the schedule, the yields and the `window` of synthesize_stream with a list of B 1-D token tensors (valid ids; lengths may differ) in
     place of T3 -- round r synthesises the first n_r tokens of every utterance (stream_token_schedule over the longest), utterance b is final once
     n_r >= N_b.  No T3 is touched: this is the streaming form of voice conversion (the engine ChatterboxVC builds has none), where every token exists up
     front and the input can be arbitrarily long -- give a `window`.  gen_ref: one voice with a whole-token prompt.  seeds: as vocode(seeds=); with a window the
-    noise is filled round by round (_stream_rounds)."""
-    check_stream_window(window, fade)
+    noise is filled round by round (_stream_rounds).  speed: None or ONE number in [0.5, 2.0] -- the speaking rate of vocode(speed=), as synthesize_stream(speed=)
+    takes it: utterance b's pieces add up to the length vocode(speed=) returns."""
+    check_stream_window(window, fade, check_stream_speed(speed))
     seeds = ops.check_seeds(seeds, len(speech_tokens))
     pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
     torch.cuda.set_device(pin)  # (a generator cannot hold a device guard across yields)
@@ -693,7 +827,7 @@ def vocode_stream(self, speech_tokens, gen_ref, *, first_chunk=25, chunk=50, chu
     lens = [int(t.numel()) for t in toks]
     self.co_resident(False)
     one_round, closed = _stream_rounds(self, len(toks), gen_ref, n_tokens=max(lens), round_tokens=lambda ts, fin: ts, lookahead=lookahead, fade=fade, z=z,
-                                       phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds)
+                                       phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds, speed=speed)
     for n_r in stream_token_schedule(max(lens), first_chunk, chunk, lookahead, chunk_growth):
         yield one_round([t[:n_r] for t in toks], [n_r >= n for n in lens], n_r >= max(lens))
         if all(closed):
@@ -748,13 +882,13 @@ class TurboEngine:
     @torch.inference_mode()
     def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_gen_len=1000,
                           temperature=0.8, top_k=1000, top_p=0.95, repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2, window=None, seeds=None):
+                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2, window=None, seeds=None, speed=None):
         """Chunked synthesis of Turbo / Nano: the round schedule, yields and overlap / first_alone / run_ahead semantics of ChatterboxEngine.synthesize_stream
         around the GPT-2 T3 (chunked through T3TurboEngine.generate(async_mode=True) / advance / peek) and the 2-step meanflow flow.  A round vocodes the
         sampled ids < 6561; the FINAL round of an utterance appends the three S3GEN_SIL tokens exactly as synthesize() does and keeps every token
         (drop_last_token=False), non-final rounds carry no silence and hold back 2 * lookahead frames.  T3 can sample max_gen_len + 1 tokens: the default
         z / phase / noise cover that many plus the 3 silence tokens.  The last round is a full synthesis: identical mel to synthesize() for the same noise.
-        window: the bounded-cost rounds of ChatterboxEngine.synthesize_stream; seeds: its per-utterance seeds."""
+        window: the bounded-cost rounds of ChatterboxEngine.synthesize_stream; seeds: its per-utterance seeds; speed: its speaking rate (one number for the stream)."""
         t3_kw = dict(max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, uniforms=uniforms,
                      ban_eos=ban_eos, ban_from=ban_from)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
@@ -766,4 +900,4 @@ class TurboEngine:
         yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_gen_len + 1, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=3,
                                       first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                       noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                      run_ahead=run_ahead, window=window, seeds=seeds)
+                                      run_ahead=run_ahead, window=window, seeds=seeds, speed=speed)

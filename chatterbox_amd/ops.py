@@ -948,6 +948,39 @@ def mel_time_scale(mel, rates, in_lens=None, out=None):
     return out, args[3 * B:]
 
 
+def mel_time_scale_window(mel, rate, j0, i_org, in_lens, out_lens, out=None):
+    """cbx_mel_time_scale_win_f32: a WINDOW of mel_time_scale's map for the rounds of a stream.  mel (B, T_in, C) holds absolute input frames [i_org, i_org + T_in),
+    row b in_lens[b] of them; out[b, jj] for jj < out_lens[b] is absolute output frame j0 + jj at `rate` (one Python float for every row), frames from out_lens[b] on
+    zero.  in_lens / out_lens: B host ints each, relative to the window; the caller decides which frames are ready (engine.stream_ready_frames).  The kernel clamps
+    every tap into the row's window, so no argument can make it read outside mel.  out: None (fresh, T_out = max(out_lens)) or a (B, T_out, C) view as in
+    mel_time_scale.  -> (out, the (B,) int32 device tensor of out_lens: the vocoder's `lens`)."""
+    assert mel.dim() == 3 and mel.shape[2] >= 1 and (mel.shape[2] == 1 or mel.stride(2) == 1), "mel_time_scale_window: mel is (B, T_in, C) with unit channel stride"
+    B, T_in, C = mel.shape
+    rate, j0, i_org = float(rate), int(j0), int(i_org)
+    M, O = [int(v) for v in in_lens], [int(v) for v in out_lens]
+    if len(M) != B or len(O) != B:
+        raise ValueError(f"mel_time_scale_window: {len(M)} input and {len(O)} output lengths for {B} rows")
+    if not all(0 <= m <= T_in for m in M) or min(O, default=0) < 0:
+        raise ValueError(f"mel_time_scale_window: in_lens {M} outside [0, {T_in}] or a negative out_lens {O}")
+    if not (SPEED_MIN <= rate <= SPEED_MAX) or j0 < 0 or i_org < 0:
+        raise ValueError(f"mel_time_scale_window: rate {rate} outside [{SPEED_MIN}, {SPEED_MAX}], or a negative origin (j0 {j0}, i_org {i_org})")
+    if out is None:
+        out = torch.empty(B, max(O, default=0), C, device=mel.device)
+    assert out.dim() == 3 and out.shape[0] == B and out.shape[2] == C and (C == 1 or out.stride(2) == 1) and out.device == mel.device, "mel_time_scale_window: out is (B, T_out, C)"
+    T_out = out.shape[1]
+    if max(O, default=0) > T_out:
+        raise ValueError(f"mel_time_scale_window: out holds {T_out} frames, the longest row needs {max(O)}")
+    dev = mel.device
+    host = torch.empty(2 * B, dtype=torch.int32, pin_memory=dev.type == "cuda")  # one pinned buffer, one asynchronous copy (mel_time_scale)
+    host.copy_(torch.tensor(M + O, dtype=torch.int32))
+    args = host.to(dev, non_blocking=True)
+    sb = lambda t, T: t.stride(0) if B > 1 else max(t.stride(0), T * t.stride(1), C)
+    check(lib.cbx_mel_time_scale_win_f32(_p(_f32(mel, "mel")), sb(mel, T_in), mel.stride(1) if T_in > 1 else max(mel.stride(1), C), T_in, args.data_ptr(), rate, j0, i_org,
+                                         _p(_f32(out, "out")), sb(out, T_out), out.stride(1) if T_out > 1 else max(out.stride(1), C), T_out, args.data_ptr() + 4 * B, B, C,
+                                         _stream()), "cbx_mel_time_scale_win_f32")
+    return out, args[B:]
+
+
 def hift_stft(s, spec, sample_lens=None):
     B, L = s.shape
     check(lib.cbx_hift_stft_f32(_p(s), _p(spec), _p(sample_lens), B, L, spec.stride(1), _stream()), "cbx_hift_stft_f32")

@@ -816,6 +816,15 @@ int cbx_rng_fill_f32(float* out, long ld_out, const unsigned* keys, int rows, lo
  * float otherwise. */
 int cbx_mel_time_scale_f32(const float* in, long in_sb, long in_ld, int T_in, const int* in_lens, const double* rate, float* out, long out_sb, long out_ld,
                            int T_out, const int* out_lens, int B, int C, void* stream);
+/* A WINDOW of that map, for the rounds of a stream at a speaking rate (added after ABI v16 without a version step: a new function only; the reference has neither
+ * the stretch, models/s3gen/s3gen.py:289, nor a streaming schedule).  The layout arguments are those of cbx_mel_time_scale_f32; `rate` is one host double for every
+ * row, j0 the ABSOLUTE index of output frame 0 and i_org the ABSOLUTE index of input frame 0; in_lens / out_lens are relative to the window (in_lens NULL: T_in).
+ * Output frame jj < out_lens[b] is frame j = j0 + jj of the whole map: x = max(0, (j + 0.5) rate - 0.5) through the same device function (one fp64 multiply-add),
+ * i0 = floor(x) - i_org, i1 = i0 + 1, both clamped into [0, in_lens[b] - 1] whatever the caller passed, l = x - floor(x) cut to [0, 1].  Where both taps lie inside
+ * the window the result is bit for bit the frame j of one cbx_mel_time_scale_f32 launch over the whole row; j0 = i_org = 0 gives that launch's bits.  Frames
+ * [out_lens[b], T_out) are written as zeros, columns [C, out_ld) are not touched.  rate must be finite and > 0, j0 and i_org in [0, 2^40): else -22 before a launch. */
+int cbx_mel_time_scale_win_f32(const float* in, long in_sb, long in_ld, int T_in, const int* in_lens, double rate, long j0, long i_org, float* out, long out_sb,
+                               long out_ld, int T_out, const int* out_lens, int B, int C, void* stream);
 
 /* ---- voice-prompt / voice-conversion front-end ----
  * Contractions (framed DFT as a GEMM over overlapping waveform rows, mel filterbanks, Conv1d/Conv2d-as-Toeplitz, attention, LSTM
