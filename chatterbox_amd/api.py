@@ -19,7 +19,7 @@ import torch
 
 from . import ops, synth
 from .engine import ChatterboxEngine, TurboEngine
-from .text import EnTokenizer, MTLTokenizer, punc_norm, punc_norm_en, punc_norm_turbo
+from .text import CJK_LANGUAGES, EnTokenizer, MTLTokenizer, default_max_chars, punc_norm, punc_norm_en, punc_norm_turbo, split_text
 
 S3GEN_SR, S3_SR = 24000, 16000
 REPO_ID = "ResembleAI/chatterbox"
@@ -209,6 +209,85 @@ def _speed_kw(speed, B=1):
     or a sequence of B (entries may be None: 1.0).  TypeError / ValueError (ops.check_speed: numbers in [0.5, 2.0]) before anything is launched."""
     speed = ops.check_speed(speed, B)
     return {} if speed is None else dict(speed=speed)
+
+
+# ---------------------------------------------------------------------------------------------------------------- generate_long: host-side plumbing
+CHUNK_SEED_STEP = 0x9E3779B97F4A7C15  # 2^64 / golden ratio: consecutive chunks get seeds that are far apart
+
+
+def chunk_seed(seed, k):
+    """The seed of chunk k of a seeded generate_long call: (seed + k * 0x9E3779B97F4A7C15) mod 2^64.  Chunk 0 uses `seed` itself, so a one-chunk text draws as
+    generate(seed=) does."""
+    return (int(seed) + int(k) * CHUNK_SEED_STEP) % (1 << 64)
+
+
+def _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, cjk):
+    """generate_long's own arguments, validated when the method is CALLED (TypeError / ValueError before anything is launched) -> dict(max_chars, pause,
+    paragraph_pause, trim_db, trim_pad, join_fade, seed, speed: a float, or None at 1.0)."""
+    import math
+    import numbers
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    is_num = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    if max_chars is None:
+        max_chars = default_max_chars(cjk)
+    if not is_int(max_chars):
+        raise TypeError(f"max_chars: expected None or an int, got {type(max_chars).__name__}")
+    if max_chars < 1:
+        raise ValueError(f"max_chars = {max_chars}: expected an int >= 1")
+    for name, v in (("pause", pause), ("paragraph_pause", paragraph_pause)):
+        if not is_num(v):
+            raise TypeError(f"{name}: expected a number of seconds, got {type(v).__name__}")
+        if not math.isfinite(v) or not 0.0 <= v <= 60.0:
+            raise ValueError(f"{name} = {v}: expected a finite number of seconds in [0, 60]")
+    if trim_db is not None:
+        if not is_num(trim_db):
+            raise TypeError(f"trim_db: expected None or a number, got {type(trim_db).__name__}")
+        if not math.isfinite(trim_db) or trim_db < 0.0:
+            raise ValueError(f"trim_db = {trim_db}: expected None or a finite number >= 0")
+        trim_db = float(trim_db)
+    for name, v in (("trim_pad", trim_pad), ("join_fade", join_fade)):
+        if not is_int(v):
+            raise TypeError(f"{name}: expected an int, got {type(v).__name__}")
+        if not 0 <= v <= 1 << 20:
+            raise ValueError(f"{name} = {v}: expected an int in [0, 2^20]")
+    seed = _seed_kw(seed).get("seeds", [None])[0]
+    speed = ops.check_speed(speed, 1)
+    return dict(max_chars=max_chars, pause=float(pause), paragraph_pause=float(paragraph_pause), trim_db=trim_db, trim_pad=trim_pad, join_fade=join_fade, seed=seed,
+                speed=None if speed is None else speed[0])
+
+
+def _long_numbers(**params):
+    """generate_long's sampling arguments: one finite number each for the whole text (TypeError / ValueError before anything is launched)"""
+    import math
+    import numbers
+    for name, v in params.items():
+        if not isinstance(v, numbers.Real) or isinstance(v, bool):
+            raise TypeError(f"{name}: expected a number, got {type(v).__name__}")
+        if not math.isfinite(v):
+            raise ValueError(f"{name} = {v}: expected a finite number")
+
+
+def long_plan(chunks, max_batch, a):
+    """The jobs of a generate_long call, WITHOUT their tokens and voices: chunks = split_text's list, a = _long_args' dict.  Chunks keep the text's order (no length
+    sort: a piece is a run of consecutive chunks) and are cut into consecutive device batches of at most max_batch (and at most 64, the join's row limit).  Per job:
+    dict(chunks=[indices], join=the engines' join dict, seeds=[...] if seeded, speed=[...] if not 1.0).  The gap behind a chunk is round(pause * 24000 / speed)
+    samples, paragraph_pause behind a paragraph's last chunk; the first job carries first=True, the last one last=True."""
+    step = max(1, min(int(max_batch), ops.WAVE_JOIN_MAX_ROWS))
+    rate = 1.0 if a["speed"] is None else a["speed"]
+    gap = lambda para_end: int(round((a["paragraph_pause"] if para_end else a["pause"]) * S3GEN_SR / rate))
+    groups = [list(range(lo, min(lo + step, len(chunks)))) for lo in range(0, len(chunks), step)]
+    jobs = []
+    for g, idx in enumerate(groups):
+        job = dict(chunks=idx, join=dict(gaps=[gap(chunks[k][1]) for k in idx], trim_db=a["trim_db"], pad_frames=a["trim_pad"], fade=a["join_fade"], first=g == 0,
+                                         last=g == len(groups) - 1))
+        if a["seed"] is not None:
+            job["seeds"] = [chunk_seed(a["seed"], k) for k in idx]
+        if a["speed"] is not None:
+            job["speed"] = [a["speed"]] * len(idx)
+        jobs.append(job)
+    return jobs
+
+
 # T3 cond dicts of a voice, kept while its T3Cond lives (generate_batch): id(T3Cond) -> [emotion tensor the entry was built from, its value, {exaggeration: dict}]
 _T3_DICTS = {}
 
@@ -307,6 +386,41 @@ class _BatchMixin:
         return out
 
 
+    def _run_long(self, text, a, tokenize, samp, synth_kw, return_segments):
+        """generate_long behind its validation: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), run the jobs of long_plan -- one through
+        synthesize, several through synthesize_pipelined where the engine has it --, concatenate the joined pieces on the host, watermark the whole once."""
+        chunks = split_text(text, a["max_chars"])
+        tokens = [tokenize(c) for c, _ in chunks]
+        plan = long_plan(chunks, int(self.max_batch or self.engine.t3.MAX_BATCH), a)
+        t3, gen = self.conds.t3.as_dict(), self.conds.gen
+        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join") if k in p}) for p in plan]
+        if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined"):
+            results = ((r[0], r[1]) for r in self.engine.synthesize_pipelined(jobs, **synth_kw))
+        else:
+            def serial():
+                for job in jobs:
+                    job = dict(job)
+                    args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
+                    yield self.engine.synthesize(*args, **synth_kw, **job)
+            results = serial()
+        pieces, segments, base = [], [], 0
+        for p, (piece, st) in zip(plan, results):
+            pieces.append(piece["wav"].detach().float().cpu())
+            assert pieces[-1].numel() == piece["total"], "a joined piece and its layout record disagree"
+            for r, k in enumerate(p["chunks"]):
+                a0, b0 = piece["edges"][r]
+                segments.append(dict(text=chunks[k][0], start=base + piece["offsets"][r], stop=base + piece["offsets"][r] + (b0 - a0), src_start=a0, src_stop=b0,
+                                     tokens=None if st is None else st[r], truncated=bool(piece["truncated"][r])))
+            base += piece["total"]
+        cut = [k for k, s in enumerate(segments) if s["truncated"]]
+        if cut:
+            import logging
+            logging.getLogger(__name__).warning("generate_long: chunk(s) %s of %d reached the speech-token budget without an end-of-speech token and are cut "
+                                                "off; use a smaller max_chars (now %d)", cut, len(segments), a["max_chars"])
+        wav = self._finish(torch.cat(pieces))
+        return (wav, segments) if return_segments else wav
+
+
 class _Base(_BatchMixin):
     sr = S3GEN_SR
 
@@ -365,6 +479,24 @@ class _Base(_BatchMixin):
         tts = [torch.cat([torch.tensor([sot]), t.view(-1).long().cpu(), torch.tensor([eot])]) for t in tokenize()]
         return self._run_batch(tts, voices, exaggeration, samp, generator, dict(max_new_tokens=1000, drop_last_token=drop_last_token), 1000, seeds, speed)
 
+    def _generate_long(self, text, language_id, norm, drop_last_token, audio_prompt_path, exaggeration, a, return_segments, **samp):
+        """The body of generate_long of the two Llama-backbone classes: the remaining checks, the voice as generate() prepares it, then _run_long."""
+        if not isinstance(text, str):
+            raise TypeError(f"text: expected a str, got {type(text).__name__}")
+        _long_numbers(exaggeration=exaggeration, **samp)
+        if audio_prompt_path:
+            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
+        else:
+            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
+        self._set_exaggeration(exaggeration)
+        sot, eot = 255, 0
+        lang = {} if language_id is None and norm is punc_norm_en else dict(language_id=language_id)
+
+        def tokenize(chunk):
+            toks = self.tokenizer.text_to_tokens(norm(chunk), **lang)
+            return torch.cat([torch.tensor([sot]), toks.view(-1).long().cpu(), torch.tensor([eot])])
+        return self._run_long(text, a, tokenize, samp, dict(max_new_tokens=1000, drop_last_token=drop_last_token), return_segments)
+
     @classmethod
     def from_synthetic(cls, device="cuda", seed=0, t3_layers=30, **kw):
         """Seeded random-init model in the reference checkpoint layout + a synthetic voice (no network / no checkpoints)."""
@@ -415,6 +547,25 @@ class ChatterboxTTS(_Base):
         toks = self.tokenizer.text_to_tokens(punc_norm_en(text))
         return self._generate(toks, drop_last_token=False, temperature=temperature, cfg_weight=cfg_weight,
                               repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
+
+    def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
+                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False):
+        """generate() for a text of ANY length: the reference stops at 1000 speech tokens (40 s) and cuts a longer text off.  The text is split into chunks of at
+        most max_chars characters at paragraph, sentence and clause boundaries (text.split_text), the chunks are synthesised in text order as device batches
+        (one: synthesize; several: the throughput schedule where the engine has it), and each batch's waveforms are trimmed of their leading / trailing silence and
+        joined ON THE DEVICE (ChatterboxEngine.vocode(join=)): a batch leaves the device as one piece in one copy.  Returns the (1, n) CPU tensor at `.sr`; the
+        watermarker, if loaded, is applied once to the whole.
+        max_chars (None: 300, or 100 for zh / ja / ko), pause / paragraph_pause (seconds of silence behind a chunk / behind a paragraph's last chunk, divided by
+        speed), trim_db (a frame of 480 samples is silence when its mean square is that many dB below the chunk's loudest frame; None: no trimming), trim_pad
+        (frames kept on either side), join_fade (samples of linear fade at every seam): UNMEASURED defaults -- nobody has tuned them with trained weights.
+        seed: chunk k draws from chunk_seed(seed, k), chunk 0 from `seed` itself; without one the call draws as generate_batch does.  speed: generate()'s.
+        return_segments=True: also a list of dict(text, start, stop, src_start, src_stop, tokens, truncated) per chunk -- [start, stop) are its samples in the
+        result (usable for captions), [src_start, src_stop) the part of its own waveform that was kept.  A chunk whose T3 spent the token budget without an
+        end-of-speech token is `truncated`; one warning names them.  Every argument is checked before anything is launched; self.conds is written only as
+        generate() writes it (audio_prompt_path)."""
+        return self._generate_long(text, None, punc_norm_en, False, audio_prompt_path, exaggeration,
+                                   _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False), return_segments,
+                                   temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
                        min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0):
@@ -495,6 +646,17 @@ class ChatterboxMultilingualTTS(_Base):
         toks = self.tokenizer.text_to_tokens(punc_norm(text), language_id=language_id.lower() if language_id else None)
         return self._generate(toks, drop_last_token=True, temperature=temperature, cfg_weight=cfg_weight,
                               repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
+
+    def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
+                      top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
+                      return_segments=False):
+        """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
+        if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
+            raise ValueError(f"Unsupported language_id '{language_id}'. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
+        lid = language_id.lower() if language_id else None
+        return self._generate_long(text, lid, punc_norm, True, audio_prompt_path, exaggeration,
+                                   _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES), return_segments,
+                                   temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0):
@@ -607,6 +769,25 @@ class ChatterboxTurboTTS(_BatchMixin):
             logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
         ids = self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids
         return self._generate(ids[0], temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
+
+    def generate_long(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
+                      top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
+                      return_segments=False):
+        """ChatterboxTTS.generate_long on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other)."""
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
+        if not isinstance(text, str):
+            raise TypeError(f"text: expected a str, got {type(text).__name__}")
+        samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
+        _long_numbers(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p, **samp)
+        if audio_prompt_path:
+            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, norm_loudness=norm_loudness)
+        else:
+            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
+        if cfg_weight > 0.0 or exaggeration > 0.0 or min_p > 0.0:
+            import logging
+            logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
+        tokenize = lambda chunk: self.tokenizer(punc_norm_turbo(chunk), return_tensors="pt", padding=True, truncation=True).input_ids[0].view(-1).long().cpu()
+        return self._run_long(text, a, tokenize, samp, {}, return_segments)
 
     def _analyse(self, wav_fpath, exaggeration, norm_loudness=True):
         return _prepare_conditionals(self.analyzer, wav_fpath, exaggeration, 375, self.device, min_seconds=5.0, norm_loudness=norm_loudness,

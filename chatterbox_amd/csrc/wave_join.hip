@@ -1,0 +1,216 @@
+// Long-form synthesis (cbx_wave_edges_f32, cbx_wave_join_f32, include/cbx.h): the waveforms of one sub-batch of text chunks are trimmed of their leading and
+// trailing silence and laid out, with pauses between them and short fades at the seams, as ONE piece in one buffer -- behind the vocoder, on its stream, so that a
+// sub-batch leaves the device in one copy.  The reference stops at 1000 speech tokens (tts.py:249, mtl_tts.py:328: max_new_tokens=1000, 40 s) and has no chunking.
+//
+// Rows: R <= 64 waveforms `wav + off[r]`, n[r] samples each, in text order; off / n / gap are HOST arrays that travel to the kernels by value (1 KiB of kernel
+// arguments), so a call needs no upload.  Frame = 480 samples (one mel frame).
+//
+// Edges: frame f of row r covers [480 f, min(480 (f + 1), n)); m_f = its mean square in fp64.  One WAVE per frame: lane l squares and adds elements [4 l, 4 l + 4)
+// and [256 + 4 l, 256 + 4 l + 4) in that order (16-byte loads where the row allows them, the same order where it does not), then a 6-step xor butterfly -- a fixed
+// order per frame whatever the grid, no floating-point atomics, so the table is reproducible run to run.  The per-frame results go to a workspace; a second launch
+// of the same entry (one workgroup per row) takes peak = max_f m_f and the first / last frame with m_f > peak * ratio and m_f > 0.  A row of 960 000 samples is read
+// once by 500 workgroups.
+//
+// Join: workgroups (x, r) write the span of row r -- its kept samples [start, stop) with the fades, then its gap as zeros -- at off_r, which every workgroup derives
+// itself as a prefix over the <= 64 entries of the edge table (no host round trip).  Aligned 16-byte stores inside the span, 4-byte stores at its ragged ends; nothing
+// at or beyond `total` is written.  One fp32 multiply per faded sample.
+#include <math.h>
+
+#include "cbx_common.h"
+
+namespace {
+
+constexpr int WJ_MAX_ROWS = 64, WJ_FRAME = 480;
+constexpr int WJ_TILE = 4096;  // output samples of one join workgroup: 256 threads x 4 quads
+
+struct wj_rows_t {
+    long off[WJ_MAX_ROWS];
+    int n[WJ_MAX_ROWS];
+    int gap[WJ_MAX_ROWS];
+};
+
+// grid (ceil(max frames / 4), R) x 256: wave w of workgroup (x, r) owns frame 4 x + w of row r
+__global__ __launch_bounds__(256) void wave_frame_ms_kernel(const float* __restrict__ wav, wj_rows_t rows, double* __restrict__ ws, long ws_ld) {
+    const int r = blockIdx.y, lane = threadIdx.x & 63;
+    const int f = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const int n = rows.n[r];
+    const long s0 = (long)f * WJ_FRAME;
+    if (s0 >= n) return;  // (wave-uniform)
+    const int cnt = n - s0 < WJ_FRAME ? (int)(n - s0) : WJ_FRAME;
+    const float* p = wav + rows.off[r] + s0;
+    const bool aligned = ((uintptr_t)p & 15) == 0;
+    double acc = 0.0;
+    for (int q = lane; q < WJ_FRAME / 4; q += 64) {
+        const int e = 4 * q;
+        if (e >= cnt) break;
+        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // (elements beyond the row add an exact zero)
+        if (aligned && e + 4 <= cnt) {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(p + e);
+            v[0] = t[0], v[1] = t[1], v[2] = t[2], v[3] = t[3];
+        } else {
+            for (int k = 0; k < 4; ++k)
+                if (e + k < cnt) v[k] = p[e + k];
+        }
+        for (int k = 0; k < 4; ++k) acc += (double)v[k] * (double)v[k];
+    }
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+    if (lane == 0) ws[(long)r * ws_ld + f] = acc / (double)cnt;
+}
+
+// grid R x 256: the kept part of row r from its frames' mean squares
+__global__ __launch_bounds__(256) void wave_edges_kernel(wj_rows_t rows, const double* __restrict__ ws, long ws_ld, double ratio, int pad, int* __restrict__ edges) {
+    __shared__ double s_pk[256];
+    __shared__ int s_lo[256], s_hi[256];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int n = rows.n[r];
+    const int nf = (int)(((long)n + WJ_FRAME - 1) / WJ_FRAME);
+    const double* m = ws + (long)r * ws_ld;
+    double pk = 0.0;
+    for (int f = tid; f < nf; f += 256) pk = fmax(pk, m[f]);
+    s_pk[tid] = pk;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (tid < s) s_pk[tid] = fmax(s_pk[tid], s_pk[tid + s]);
+        __syncthreads();
+    }
+    const double thr = s_pk[0] * ratio;
+    int lo = 0x7fffffff, hi = -1;
+    for (int f = tid; f < nf; f += 256) {
+        const double v = m[f];
+        if (v > thr && v > 0.0) {
+            lo = f < lo ? f : lo;
+            hi = f > hi ? f : hi;
+        }
+    }
+    s_lo[tid] = lo, s_hi[tid] = hi;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (tid < s) {
+            s_lo[tid] = s_lo[tid + s] < s_lo[tid] ? s_lo[tid + s] : s_lo[tid];
+            s_hi[tid] = s_hi[tid + s] > s_hi[tid] ? s_hi[tid + s] : s_hi[tid];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        int start = 0, stop = 0;
+        if (s_hi[0] >= 0) {
+            const long f0 = (long)s_lo[0] - pad, e1 = ((long)s_hi[0] + 1 + pad) * WJ_FRAME;
+            start = (int)((f0 > 0 ? f0 : 0) * WJ_FRAME);
+            stop = (int)(e1 < n ? e1 : n);
+        }
+        edges[2 * r] = start;
+        edges[2 * r + 1] = stop;
+    }
+}
+
+// grid (ceil((max span + 3) / WJ_TILE), R) x 256: workgroup (x, r) writes quads [1024 x, 1024 (x + 1)) of row r's span, counted from the 16-byte boundary at or
+// below out + off_r
+__global__ __launch_bounds__(256) void wave_join_kernel(const float* __restrict__ wav, wj_rows_t rows, int R, const int* __restrict__ edges, const float* __restrict__ ramp,
+                                                        int fade, int first, int last, float* __restrict__ out, int* __restrict__ layout) {
+    const int r = blockIdx.y;
+    long off = 0;
+    int start = 0, stop = 0, L = 0, gap = 0;
+    for (int q = 0; q <= r; ++q) {  // the layout prefix; the table is device data: cut into [0, n] whatever it holds
+        const int n = rows.n[q];
+        int a = edges[2 * q], b = edges[2 * q + 1];
+        a = a < 0 ? 0 : (a > n ? n : a);
+        b = b < a ? a : (b > n ? n : b);
+        const int l = b - a;
+        const int g = (l > 0 && !(last && q == R - 1)) ? rows.gap[q] : 0;
+        if (q < r) off += (long)l + g;
+        else start = a, stop = b, L = l, gap = g;
+    }
+    const long end = off + L + gap;  // the span of this row: out[off, end)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        layout[r] = (int)off;
+        if (r == R - 1) layout[R] = (int)end;
+    }
+    const int F = fade < L / 2 ? fade : L / 2;
+    const bool fin = !(first && r == 0 && start == 0), fout = !(last && r == R - 1 && stop == rows.n[r]);
+    const float* src = wav + rows.off[r] + start;
+    const bool out16 = ((uintptr_t)out & 15) == 0;
+    const long q0 = out16 ? (off & ~3l) : off;  // where quad 0 of this row begins
+    for (int it = 0; it < 4; ++it) {
+        const long p0 = q0 + 4 * ((long)blockIdx.x * (WJ_TILE / 4) + it * 256 + threadIdx.x);
+        if (p0 >= end) return;
+        float v[4];
+        const long i0 = p0 - off;  // (may be -3 .. -1 in the first quad)
+        const bool whole = p0 >= off && p0 + 4 <= end;
+        if (whole && i0 + 4 <= L && ((uintptr_t)(src + i0) & 15) == 0) {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(src + i0);
+            v[0] = t[0], v[1] = t[1], v[2] = t[2], v[3] = t[3];
+        } else {
+            for (int k = 0; k < 4; ++k) v[k] = (i0 + k >= 0 && i0 + k < L) ? src[i0 + k] : 0.0f;
+        }
+        for (int k = 0; k < 4; ++k) {
+            const long i = i0 + k;
+            if (i < 0 || i >= L) continue;
+            if (fin && i < F) v[k] = v[k] * ramp[i];
+            else if (fout && i >= L - F) v[k] = v[k] * ramp[L - 1 - i];
+        }
+        if (whole && out16) {
+            *reinterpret_cast<f32x4*>(out + p0) = f32x4{v[0], v[1], v[2], v[3]};
+        } else {
+            for (int k = 0; k < 4; ++k)
+                if (p0 + k >= off && p0 + k < end) out[p0 + k] = v[k];
+        }
+    }
+}
+
+// the host arrays of a call -> the by-value descriptor; returns the longest row through *n_max, the sum of the lengths through *n_sum
+int wj_rows(const char* who, const long* row_off, const int* row_len, const int* gaps, int R, wj_rows_t* rows, long* n_max, long* n_sum) {
+    CBX_REQUIRE(row_off && row_len, "%s: null pointer", who);
+    CBX_REQUIRE(R >= 1 && R <= WJ_MAX_ROWS, "%s: R = %d outside [1, %d]", who, R, WJ_MAX_ROWS);
+    *n_max = *n_sum = 0;
+    for (int r = 0; r < WJ_MAX_ROWS; ++r) rows->off[r] = 0, rows->n[r] = 0, rows->gap[r] = 0;
+    for (int r = 0; r < R; ++r) {
+        CBX_REQUIRE(row_len[r] >= 0 && row_off[r] >= 0, "%s: row %d has length %d at offset %ld", who, r, row_len[r], row_off[r]);
+        CBX_REQUIRE(!gaps || gaps[r] >= 0, "%s: row %d has gap %d", who, r, gaps ? gaps[r] : 0);
+        rows->off[r] = row_off[r], rows->n[r] = row_len[r], rows->gap[r] = gaps ? gaps[r] : 0;
+        *n_max = row_len[r] > *n_max ? row_len[r] : *n_max;
+        *n_sum += (long)row_len[r] + rows->gap[r];
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cbx_wave_edges_f32(const float* wav, const long* row_off, const int* row_len, int R, double ratio, int pad, int* edges, double* ws, long ws_cap,
+                                  void* stream) {
+    wj_rows_t rows;
+    long n_max, n_sum;
+    const int rc = wj_rows("wave_edges", row_off, row_len, nullptr, R, &rows, &n_max, &n_sum);
+    if (rc) return rc;
+    CBX_REQUIRE(wav && edges && ws, "wave_edges: null pointer");
+    CBX_REQUIRE(ratio >= 0.0 && ratio < INFINITY && pad >= 0 && pad <= (1 << 20), "wave_edges: bad threshold (ratio %g, pad %d)", ratio, pad);
+    const long nf = (n_max + WJ_FRAME - 1) / WJ_FRAME;
+    CBX_REQUIRE(ws_cap >= (long)R * nf, "wave_edges: workspace of %ld doubles, %d rows of %ld frames need %ld", ws_cap, R, nf, (long)R * nf);
+    if (nf > 0) {
+        const long gx = (nf + 3) / 4;
+        CBX_REQUIRE(gx <= 0x7fffffffl, "wave_edges: a row of %ld samples is too long for one launch", n_max);
+        hipLaunchKernelGGL(wave_frame_ms_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, ws, nf);
+        const int e = cbx_check_launch("wave_edges");
+        if (e) return e;
+    }
+    hipLaunchKernelGGL(wave_edges_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, (const double*)ws, nf, ratio, pad, edges);
+    return cbx_check_launch("wave_edges");
+}
+
+extern "C" int cbx_wave_join_f32(const float* wav, const long* row_off, const int* row_len, const int* gaps, int R, const int* edges, const float* ramp, int fade,
+                                 int first, int last, float* out, long out_cap, int* layout, void* stream) {
+    wj_rows_t rows;
+    long n_max, n_sum;
+    CBX_REQUIRE(gaps, "wave_join: null pointer");
+    const int rc = wj_rows("wave_join", row_off, row_len, gaps, R, &rows, &n_max, &n_sum);
+    if (rc) return rc;
+    CBX_REQUIRE(wav && edges && out && layout, "wave_join: null pointer");
+    CBX_REQUIRE(fade >= 0 && (fade == 0 || ramp), "wave_join: fade = %d%s", fade, fade > 0 ? " without a ramp" : "");
+    CBX_REQUIRE(n_sum <= 0x7fffffffl, "wave_join: %ld samples do not fit the int32 layout record", n_sum);
+    CBX_REQUIRE(out_cap >= n_sum, "wave_join: out holds %ld samples, the rows and their gaps may need %ld", out_cap, n_sum);
+    long span = 0;
+    for (int r = 0; r < R; ++r) span = (long)rows.n[r] + rows.gap[r] > span ? (long)rows.n[r] + rows.gap[r] : span;
+    const long gx = (span + 3 + WJ_TILE - 1) / WJ_TILE;  // (+ 3: the span may begin up to three samples into its first quad; >= 1: the layout record is always written)
+    hipLaunchKernelGGL(wave_join_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, R, edges, ramp, fade, first != 0, last != 0, out,
+                       layout);
+    return cbx_check_launch("wave_join");
+}

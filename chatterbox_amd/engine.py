@@ -84,7 +84,7 @@ class ChatterboxEngine:
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None, seeds=None, speed=None):
+               generator=None, seeds=None, speed=None, join=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
@@ -96,10 +96,16 @@ class ChatterboxEngine:
         ops.scaled_len(M_b, speed[b]) (models/s3gen/s3gen.py:289 leaves this out); the vocoder runs on the stretched mel with lens = O_b, so the F0 predictor
         sees it and the pitch is kept.  Utterance b's waveform is max(1, floor(K_b / speed[b])) * 480 samples where the unscaled call returns K_b * 480.
         Noise and phase that are not injected are sized from the stretched mel; injected ones must have ITS shapes: phase (B, 9), noise
-        (B, 9, 480 * max_b O_b).  z is the flow's and does not change.  The returned mel stays the unscaled flow mel."""
+        (B, 9, 480 * max_b O_b).  z is the flow's and does not change.  The returned mel stays the unscaled flow mel.
+        join (None: this call, launch for launch; else ops.check_join's dict(gaps=[B ints], trim_db=float|None, pad_frames=int, fade=int, first=bool, last=bool)):
+        long-form synthesis -- the B utterances are consecutive chunks of one text, and two launches behind the vocoder, on the stream that owns the waveforms,
+        trim each of its silence (cbx_wave_edges_f32; skipped with trim_db=None) and lay them out with their gaps and fades as ONE piece (cbx_wave_join_f32).  The
+        call then returns (piece, mel), piece = ops.wave_join's dict on the device: the `out` buffer, its layout record and the edge table.  Nothing is synchronised
+        for it; ops.piece_on_host reads it once it is on the host."""
         B = len(speech_tokens)
         seeds = ops.request_seeds(seeds, B, generator)
         speed = ops.check_speed(speed, B)
+        join = ops.check_join(join, B)
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
         tok = torch.zeros(B, Nmax, dtype=torch.long)
@@ -147,20 +153,28 @@ class ChatterboxEngine:
             if speed is not None:
                 frames = ops.scaled_len(frames, speed[b])
             out.append(wav[b, : frames * (SAMPLES_PER_TOKEN // 2)])
+        if join is not None:
+            if hift_stream is not None:
+                with torch.cuda.stream(hift_stream):
+                    return ops.wave_join(out, **join), mel
+            return ops.wave_join(out, **join), mel
         return out, mel
 
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None):
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
         (T3Engine.generate(seeds=), vocode(seeds=)); not together with a generator.
-        speed: None, a number or B numbers in [0.5, 2.0]: the speaking rate of vocode(speed=); T3 and its tokens do not depend on it."""
+        speed: None, a number or B numbers in [0.5, 2.0]: the speaking rate of vocode(speed=); T3 and its tokens do not depend on it.
+        join: None, or vocode(join=)'s dict -- the B utterances are consecutive chunks of one text; the call then returns (piece, speech_tokens) with piece =
+        ops.piece_on_host's dict (wav = the joined piece on the device, offsets, total, edges, n) plus truncated = [B bools: T3 spent its budget without EOS]."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
+        join = ops.check_join(join, len(text_tokens))
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
@@ -171,7 +185,9 @@ class ChatterboxEngine:
         st = [drop_invalid_tokens(t) for t in toks]
         st = [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
-                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed)
+                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)))
+        if join is not None:  # (the record's copy waits for the two launches behind the vocoder)
+            wavs = dict(ops.piece_on_host(wavs["out"], wavs["rec"], wavs["n"]), truncated=[not bool((t == STOP_SPEECH).any()) for t in toks])
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
@@ -197,7 +213,10 @@ class ChatterboxEngine:
         (wavs, tokens, latency_s) per job in order.  Results are identical to synthesize() called per job.  A job may carry sampling parameters of its own
         (temperature, top_p, min_p, repetition_penalty, cfg_weight: scalar or one per utterance; they override **kw for that job) and a `generator` for the flow / vocoder noise that is not injected (the
         sampling draws of a repeatable job are injected as `uniforms`: T3 is enqueued by another host thread), or `seeds` (one int per utterance, or one int for all:
-        every draw of the job that is not injected, as synthesize(seeds=); not together with a generator), or `speed` (a number or one per utterance: vocode(speed=)).
+        every draw of the job that is not injected, as synthesize(seeds=); not together with a generator), or `speed` (a number or one per utterance: vocode(speed=)),
+        or `join` (vocode(join=)'s dict: the job's utterances are consecutive chunks of one text; `wavs` is then synthesize(join=)'s piece dict with `wav` on the host.
+        The two launches run behind the vocoder on its stream, the piece leaves the device as ONE pinned copy plus one of its small records where a job without
+        it makes one copy per utterance, and it is sliced after the event this schedule waits for anyway: no host synchronisation is added).
 
         What makes the two stages actually overlap (round 5, profiles/r05_overlap_*; none of it changes a result):
           * co_resident: a chain of small dependent kernels keeps its pace beside chip-filling kernels of another stream only if its workgroups FIT
@@ -211,6 +230,8 @@ class ChatterboxEngine:
         import threading
         jobs = [dict(job, seeds=ops.request_seeds(job["seeds"], len(job["text_tokens"]), job.get("generator"))) if job.get("seeds") is not None else job for job in jobs]
         jobs = [dict(job, speed=ops.check_speed(job["speed"], len(job["text_tokens"]))) if job.get("speed") is not None else job for job in jobs]
+        jobs = [dict(job, join=ops.check_join(job["join"], len(job["text_tokens"]))) if job.get("join") is not None else {k: v for k, v in job.items() if k != "join"}
+                for job in jobs]  # (from here on `"join" in job` says whether the job is joined)
         torch.cuda.set_device(self.dev)  # a generator cannot hold a device guard across yields: pin the device for the caller
         self._pipeline_streams(stream_priorities)
         t3_kw = {k: kw[k] for k in ("max_new_tokens", "temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight", "ban_eos",
@@ -239,13 +260,21 @@ class ChatterboxEngine:
                 def voc():
                     wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
                                           speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10),
-                                          drop_last_token=kw.get("drop_last_token", True), sync=False)
+                                          drop_last_token=kw.get("drop_last_token", True), sync=False, **join_kw(job))
+                    if "join" in job:
+                        return ops.piece_on_host(wavs["out"].cpu(), wavs["rec"].cpu(), wavs["n"])
                     return [w.cpu() for w in wavs]  # D2H on the vocoder stream: returns when this batch's audio is on the host
                 return _range_checked(self, voc)
+
+        join_kw = lambda job: dict(join=job["join"]) if "join" in job else {}  # (a job without it: vocode is called exactly as before)
 
         def tokens_of(toks):
             st = [drop_invalid_tokens(t) for t in toks]
             return [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
+
+        def truncated_of(job, host, toks):
+            """a joined piece also says which chunks spent T3's budget without EOS"""
+            return dict(host, truncated=[not bool((t == STOP_SPEECH).any()) for t in toks]) if "join" in job else host
 
         if not host_threads:  # round 4's form: one host thread enqueues T3(k + 1), then flow + vocoder(k)
             try:
@@ -258,14 +287,14 @@ class ChatterboxEngine:
                         if "error" in box:
                             raise box["error"]
                     if pending is not None:
-                        job, st, t0 = pending
+                        job, st, t0, raw = pending
                         host = voc_of(job, st)
-                        yield host, st, time.perf_counter() - t0
+                        yield truncated_of(job, host, raw), st, time.perf_counter() - t0
                     pending = None
                     if "handle" in box:
                         with torch.cuda.stream(self._s_t3):
-                            toks = self.t3.collect(box["handle"])
-                        pending = (jobs[k], tokens_of(toks), t_start)
+                            raw = self.t3.collect(box["handle"])
+                        pending = (jobs[k], tokens_of(raw), t_start, raw)
             finally:
                 torch.cuda.synchronize()
                 self.co_resident(False)
@@ -307,13 +336,17 @@ class ChatterboxEngine:
         def start_voc(job, st, which):
             ops.select_range_flag(self.dev, which)
             with torch.cuda.stream(self._s_voc):
-                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), speed=job.get("speed"), sync=False, **voc_kw)
-                host = [torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True) for w in wavs]
+                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), speed=job.get("speed"), sync=False, **voc_kw, **join_kw(job))
+                pinned = lambda w: torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True)
+                if "join" in job:  # one copy of the piece and one of its records; read in finish(), behind the event
+                    host = (pinned(wavs["out"]), pinned(wavs["rec"]), wavs["n"])
+                else:
+                    host = [pinned(w) for w in wavs]
                 ev = torch.cuda.Event()
                 ev.record()
             return host, ev
 
-        def finish(job, st, t0, host, ev, which):
+        def finish(job, st, t0, host, ev, which, raw):
             ev.synchronize()
             if 16 in (self.flow.precision, self.hift.precision) and ops.range_flag_tripped(self.dev, which):
                 warnings.warn("an S3Gen operand exceeded the fp16 range: repeating flow matching + vocoder of this batch at bf16x6")
@@ -323,10 +356,12 @@ class ChatterboxEngine:
                 self.flow.precision, self.hift.precision = (6 if p == 16 else p for p in saved)
                 try:
                     with torch.cuda.stream(self._s_voc):
-                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), speed=job.get("speed"), sync=False, **voc_kw)
-                        host = [w.cpu() for w in wavs]
+                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), speed=job.get("speed"), sync=False, **voc_kw, **join_kw(job))
+                        host = (wavs["out"].cpu(), wavs["rec"].cpu(), wavs["n"]) if "join" in job else [w.cpu() for w in wavs]  # (the repeat repeats the join)
                 finally:
                     self.flow.precision, self.hift.precision = saved
+            if "join" in job:
+                host = truncated_of(job, ops.piece_on_host(*host), raw)
             return host, st, time.perf_counter() - t0
 
         th = threading.Thread(target=worker, name="cbx-t3-enqueue", daemon=True)
@@ -343,7 +378,7 @@ class ChatterboxEngine:
                 slot_free[k % n_slots].release()
                 st = tokens_of(toks)
                 host, evv = start_voc(job, st, k % 2)
-                inflight.append((job, st, t0, host, evv, k % 2))
+                inflight.append((job, st, t0, host, evv, k % 2, toks))
                 yield finish(*inflight.popleft())
             while inflight:
                 yield finish(*inflight.popleft())
@@ -859,12 +894,14 @@ class TurboEngine:
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
         for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=);
-        speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=)."""
+        speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=); join: None, or vocode(join=)'s dict -- the call then returns
+        ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS)."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
+        join = ops.check_join(join, len(text_tokens))
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                 repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
@@ -872,7 +909,10 @@ class TurboEngine:
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
-        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed)
+        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed,
+                              **({} if join is None else dict(join=join)))
+        if join is not None:  # (generate strips a sampled EOS: a chunk that still has max_gen_len + 1 tokens never sampled one)
+            wavs = dict(ops.piece_on_host(wavs["out"], wavs["rec"], wavs["n"]), truncated=[int(t.numel()) > max_gen_len for t in toks])
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 

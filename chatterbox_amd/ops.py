@@ -981,6 +981,136 @@ def mel_time_scale_window(mel, rate, j0, i_org, in_lens, out_lens, out=None):
     return out, args[B:]
 
 
+# ----------------------------------------------------------------------------- long-form synthesis: trim + join the waveforms of a sub-batch (wave_join.hip)
+WAVE_FRAME, WAVE_JOIN_MAX_ROWS = 480, 64
+JOIN_KEYS = ("gaps", "trim_db", "pad_frames", "fade", "first", "last")
+_JOIN_RAMPS = {}
+
+
+def check_join(join, R, name="join"):
+    """A `join` argument of the engines as a dict with every key of JOIN_KEYS, or None: gaps (R ints >= 0, samples behind each row), trim_db (None: no trimming, or
+    a finite number >= 0), pad_frames (int >= 0), fade (int >= 0, samples), first / last (bools: the piece begins / ends the whole text).  Defaults: pad_frames 2,
+    fade 240, first = last = True, trim_db None.  TypeError / ValueError before anything is launched."""
+    import math
+    import numbers
+    if join is None:
+        return None
+    if not isinstance(join, dict):
+        raise TypeError(f"{name}: expected a dict with {JOIN_KEYS}, got {type(join).__name__}")
+    extra = set(join) - set(JOIN_KEYS)
+    if extra or "gaps" not in join:
+        raise ValueError(f"{name}: keys {sorted(join)}: `gaps` is required, the others are {JOIN_KEYS[1:]}")
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    gaps = join["gaps"]
+    if not isinstance(gaps, (list, tuple)) or not all(is_int(g) for g in gaps):
+        raise TypeError(f"{name}['gaps']: expected a list of {R} ints")
+    if len(gaps) != R or not 1 <= R <= WAVE_JOIN_MAX_ROWS or any(g < 0 for g in gaps):
+        raise ValueError(f"{name}['gaps']: {len(gaps)} entries for {R} rows (1 .. {WAVE_JOIN_MAX_ROWS} rows, every gap >= 0)")
+    trim_db = join.get("trim_db")
+    if trim_db is not None:
+        if not isinstance(trim_db, numbers.Real) or isinstance(trim_db, bool):
+            raise TypeError(f"{name}['trim_db']: expected None or a number, got {type(trim_db).__name__}")
+        trim_db = float(trim_db)
+        if not math.isfinite(trim_db) or trim_db < 0.0:
+            raise ValueError(f"{name}['trim_db'] = {trim_db}: a finite number >= 0 (decibels below the loudest frame)")
+    out = dict(gaps=[int(g) for g in gaps], trim_db=trim_db)
+    for key, default in (("pad_frames", 2), ("fade", 240)):
+        v = join.get(key, default)
+        if not is_int(v):
+            raise TypeError(f"{name}['{key}']: expected an int, got {type(v).__name__}")
+        if not 0 <= v <= 1 << 20:
+            raise ValueError(f"{name}['{key}'] = {v}: expected an int in [0, 2^20]")
+        out[key] = v
+    for key in ("first", "last"):
+        v = join.get(key, True)
+        if not isinstance(v, bool):
+            raise TypeError(f"{name}['{key}']: expected a bool, got {type(v).__name__}")
+        out[key] = v
+    return out
+
+
+def join_ramp(fade, device):
+    """The fade ramp of cbx_wave_join_f32 on `device`: ramp[i] = (2 i + 1) / (2 fade), evaluated in fp64 and rounded to fp32 (None for fade 0); built once per
+    (fade, device)."""
+    fade = int(fade)
+    if fade == 0:
+        return None
+    key = (fade, str(device))
+    if key not in _JOIN_RAMPS:
+        _JOIN_RAMPS[key] = ((2.0 * torch.arange(fade, dtype=torch.float64) + 1.0) / (2.0 * fade)).float().to(device)
+    return _JOIN_RAMPS[key]
+
+
+def _wave_rows(rows, who):
+    """rows: 1 .. 64 1-D fp32 tensors with unit stride, all views of ONE allocation (what vocode cuts out of its padded (B, L) waveform) -> (pointer of the
+    allocation, ctypes arrays of the per-row element offsets and lengths).  Rows of different allocations are refused."""
+    rows = list(rows)
+    if not 1 <= len(rows) <= WAVE_JOIN_MAX_ROWS:
+        raise ValueError(f"{who}: {len(rows)} rows (1 .. {WAVE_JOIN_MAX_ROWS})")
+    dev = rows[0].device
+    for r, w in enumerate(rows):
+        _f32(w, f"{who}: row {r}")
+        if w.dim() != 1 or (w.numel() > 1 and w.stride(0) != 1) or w.device != dev:
+            raise ValueError(f"{who}: row {r} is not a 1-D tensor with unit stride on {dev}")
+    base = rows[0].untyped_storage().data_ptr()
+    if any(w.untyped_storage().data_ptr() != base for w in rows):
+        raise ValueError(f"{who}: the rows are views of different allocations; pass views of one (B, L) tensor")
+    R = len(rows)
+    offs = (ctypes.c_long * R)(*[(w.data_ptr() - base) // 4 if w.numel() else 0 for w in rows])
+    lens = (ctypes.c_int * R)(*[int(w.numel()) for w in rows])
+    return base, offs, lens
+
+
+def wave_edges(rows, trim_db, pad_frames=2, edges=None):
+    """cbx_wave_edges_f32: the kept part {start, stop} of every row as an (R, 2) int32 device tensor -- from the first to the last 480-sample frame whose mean
+    square is above the loudest frame's times 10^(-trim_db / 10), `pad_frames` frames more on either side.  No host synchronisation."""
+    base, offs, lens = _wave_rows(rows, "wave_edges")
+    R, dev = len(lens), rows[0].device
+    if edges is None:
+        edges = torch.empty(R, 2, dtype=torch.int32, device=dev)
+    assert edges.dtype == torch.int32 and edges.numel() == 2 * R and edges.is_contiguous() and edges.device == dev, "wave_edges: edges is (R, 2) int32 on the rows' device"
+    n_frames = -(-max(lens) // WAVE_FRAME)
+    ws = torch.empty(max(1, R * n_frames), dtype=torch.float64, device=dev)
+    check(lib.cbx_wave_edges_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, 10.0 ** (-float(trim_db) / 10.0), int(pad_frames), _p(edges), _p(ws),
+                                 ws.numel(), _stream()), "cbx_wave_edges_f32")
+    return edges
+
+
+def wave_join(rows, gaps, trim_db=None, pad_frames=2, fade=240, first=True, last=True, out=None):
+    """cbx_wave_edges_f32 (unless trim_db is None) + cbx_wave_join_f32 on the current stream: the rows' kept parts laid out in ONE buffer with their gaps and
+    fades (include/cbx.h states the layout).  rows: _wave_rows; gaps: R ints.  Returns the piece, everything on the device and nothing synchronised:
+    dict(out=(capacity,) fp32 of which [0, total) is the piece -- capacity = sum of the lengths and gaps; the rest is NOT written --, rec=(3 R + 1,) int32 = the
+    layout record off_0 .. off_(R-1), total followed by the edge table, layout / edges = views of rec, n = the R row lengths)."""
+    base, offs, lens = _wave_rows(rows, "wave_join")
+    R, dev = len(lens), rows[0].device
+    n = [int(v) for v in lens]
+    gaps = [int(g) for g in gaps]
+    if len(gaps) != R:
+        raise ValueError(f"wave_join: {len(gaps)} gaps for {R} rows")
+    cap = sum(n) + sum(gaps)
+    if out is None:
+        out = torch.empty(max(1, cap), device=dev)
+    assert out.dim() == 1 and out.is_contiguous() and out.device == dev, "wave_join: out is a contiguous 1-D fp32 tensor on the rows' device"
+    rec = torch.empty(3 * R + 1, dtype=torch.int32, device=dev)
+    layout, edges = rec[: R + 1], rec[R + 1:].view(R, 2)
+    if trim_db is None:  # (0, n_r) written by the host: one small pinned copy, no synchronisation
+        host = torch.tensor([v for k in n for v in (0, k)], dtype=torch.int32)
+        edges.view(-1).copy_(host.pin_memory() if dev.type == "cuda" else host, non_blocking=True)
+    else:
+        wave_edges(rows, trim_db, pad_frames, edges=edges)
+    g = (ctypes.c_int * R)(*gaps)
+    check(lib.cbx_wave_join_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(g), R, _p(edges), _p(join_ramp(fade, dev)), int(fade),
+                                int(bool(first)), int(bool(last)), _p(_f32(out, "out")), out.numel(), _p(layout), _stream()), "cbx_wave_join_f32")
+    return dict(out=out, rec=rec, layout=layout, edges=edges, n=n)
+
+
+def piece_on_host(out, rec, n):
+    """The host's reading of a joined piece once `out` and `rec` (wave_join) are readable: dict(wav = out[:total], offsets, total, edges = [(start, stop)], n)."""
+    R = len(n)
+    rec = [int(v) for v in rec.tolist()]
+    return dict(wav=out[: rec[R]], offsets=rec[:R], total=rec[R], edges=[(rec[R + 1 + 2 * r], rec[R + 2 + 2 * r]) for r in range(R)], n=list(n))
+
+
 def hift_stft(s, spec, sample_lens=None):
     B, L = s.shape
     check(lib.cbx_hift_stft_f32(_p(s), _p(spec), _p(sample_lens), B, L, spec.stride(1), _stream()), "cbx_hift_stft_f32")

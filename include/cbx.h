@@ -826,6 +826,26 @@ int cbx_mel_time_scale_f32(const float* in, long in_sb, long in_ld, int T_in, co
 int cbx_mel_time_scale_win_f32(const float* in, long in_sb, long in_ld, int T_in, const int* in_lens, double rate, long j0, long i_org, float* out, long out_sb,
                                long out_ld, int T_out, const int* out_lens, int B, int C, void* stream);
 
+/* ---- long-form synthesis: trim and join the waveforms of one sub-batch of text chunks on the device (added after ABI v16 without a version step: new functions
+ * only).  The reference stops at 1000 speech tokens (tts.py:249, mtl_tts.py:328) and has no chunking.  Rows: R in [1, 64] waveforms in text order, row r = the
+ * row_len[r] floats at wav + row_off[r]; row_off, row_len and gaps are HOST arrays (they travel to the kernels by value).  Frame = 480 samples.
+ * cbx_wave_edges_f32: which part of each row is kept.  Frame f of row r covers [480 f, min(480 (f + 1), n_r)), m_f is its mean square, peak = max_f m_f; a frame is
+ * live iff m_f > peak * ratio and m_f > 0 (ratio = 10^(-trim_db / 10), computed by the caller in fp64).  With f0 / f1 the first / last live frame: start =
+ * 480 max(0, f0 - pad), stop = min(n_r, 480 (f1 + 1 + pad)); no live frame or n_r = 0: (0, 0).  edges: (R, 2) int32 device table {start, stop}.  Squares and sums
+ * in fp64, one wave per frame in a fixed order that does not depend on the grid or on the row's alignment, no floating-point atomics: the table is reproducible
+ * run to run.  ws: device workspace of ws_cap >= R * ceil(max_r n_r / 480) doubles (the per-frame results; a second launch of this entry reduces them per row).
+ * -22 before any launch: a null pointer, R outside [1, 64], a negative length or offset, ratio negative / not finite, pad < 0, a workspace that is too small. */
+int cbx_wave_edges_f32(const float* wav, const long* row_off, const int* row_len, int R, double ratio, int pad, int* edges, double* ws, long ws_cap, void* stream);
+/* cbx_wave_join_f32: ONE launch lays the kept parts out in `out`.  edges: the (R, 2) device table of cbx_wave_edges_f32, or {0, n_r} written by the caller (no
+ * trimming); every entry is cut into [0, n_r] by the kernel.  L_r = stop_r - start_r; off_0 = 0, off_(r+1) = off_r + L_r + gap_r with gap_r = gaps[r] iff L_r > 0 and
+ * not (last and r = R - 1), else 0; total = off_R.  out[off_r + i] = wav_r[start_r + i] for i < L_r, times ramp[i] for i < F (fade-in; not when first and r = 0 and
+ * start_r = 0), times ramp[L_r - 1 - i] for i >= L_r - F (fade-out; not when last and r = R - 1 and stop_r = n_r), F = min(fade, L_r / 2): one fp32 multiply.
+ * ramp: `fade` device floats, (2 i + 1) / (2 fade) by convention (NULL when fade = 0).  The gap behind a row is written as zeros; nothing at or beyond `total` is
+ * written.  layout: R + 1 device ints, off_0 .. off_(R-1) and total.  first / last: this piece begins / ends the whole text.
+ * -22 before any launch: a null pointer, R outside [1, 64], a negative gap, fade, length or offset, out_cap below sum n_r + sum gaps[r] (or that sum >= 2^31). */
+int cbx_wave_join_f32(const float* wav, const long* row_off, const int* row_len, const int* gaps, int R, const int* edges, const float* ramp, int fade, int first,
+                      int last, float* out, long out_cap, int* layout, void* stream);
+
 /* ---- voice-prompt / voice-conversion front-end ----
  * Contractions (framed DFT as a GEMM over overlapping waveform rows, mel filterbanks, Conv1d/Conv2d-as-Toeplitz, attention, LSTM
  * projections) use cbx_gemm_f32 / cbx_flash_attn_f32 / cbx_gemv_f32; these are the remaining element-wise / reduction passes. */
