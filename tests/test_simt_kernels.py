@@ -185,6 +185,34 @@ def test_normstress_bodies_on_the_emulator(emu, name, args):
     getattr(test_norm_stress_gpu, name)(CPU, *args)
 
 
+# tests/test_range_edges_gpu.py (both ends of the fp16 range: one prescribed outlier per launch and its twin, the flag contract C1 .. C4; operands far below 2^-14) at
+# the GPU test's own shapes: every copy of the range check at least once -- the plain plane epilogue on a symmetric, a loader-wave, a 16-wave and the deferred forms
+# (last element; the position sweep on tile 3), amax_df through folded tiles and the drain, the V^T store (plain and deferred), the LayerNorm epilogue, layernorm_planes
+# (narrow and generic kernel), the split GEMM's three loaders and its LayerNorm fold, the split attention with fp32 and plane output.  The engine bodies need a GPU.
+_RANGEEDGE = [("test_split_planes_range", ()),
+              ("test_gemm_planes_plain_epilogue_range", (0, (1,), False)), ("test_gemm_planes_plain_epilogue_range", (3, (2,), True, ("gelu",))),
+              ("test_gemm_planes_plain_epilogue_range", (21, (0,), False)), ("test_gemm_planes_plain_epilogue_range", (26, (1,), False)),
+              ("test_gemm_planes_plain_epilogue_range", (32, (1, 2, 0), False)), ("test_gemm_planes_plain_epilogue_range", (35, (2,), False)),
+              ("test_gemm_planes_plain_epilogue_range", (41, (2,), False)), ("test_gemm_planes_plain_epilogue_range", (42, (1,), False)),
+              ("test_gemm_planes_deferred_epilogue_range", (41, 2, ((0, 0), (0, 1), (1, 1), (2, 1), (2, 2)))), ("test_gemm_planes_deferred_epilogue_range", (42, 1, ((0, 0), (1, 2), (2, 2)))),
+              ("test_gemm_planes_transposed_range", (3, 36, 0, 1, slice(1, 4))), ("test_gemm_planes_transposed_range", (2, 132, 41, 2, slice(0, 4, 2))), ("test_gemm_planes_transposed_range", (3, 36, 42, 1)),
+              ("test_gemm_planes_layernorm_epilogue_range", (False,)), ("test_gemm_planes_layernorm_epilogue_range", (True,)),
+              ("test_layernorm_planes_range", (77,)), ("test_layernorm_planes_range", (37,)),
+              ("test_split_gemm_linear_range", (129, 257, 320)), ("test_split_gemm_linear_range", (65, 100, 36)), ("test_split_gemm_layernorm_fold_range", ()),
+              ("test_split_gemm_conv_range", ("fast_taps",)), ("test_split_gemm_conv_range", ("dilated",)), ("test_split_gemm_conv_range", ("upsample",)),
+              ("test_split_gemm_conv_range", ("ragged",)), ("test_split_gemm_conv_range", ("transpose",)), ("test_precision16_shapes_on_the_exact_kernels_range", ()),
+              ("test_split_flash_attn_range", (130, False, False)), ("test_split_flash_attn_range", (103, True, False)), ("test_split_flash_attn_range", (130, False, True)),
+              ("test_split_flash_attn_range", (103, True, True)),
+              ("test_lower_end_linear", (64, 96, 256)), ("test_lower_end_linear", (65, 100, 36)), ("test_lower_end_linear_planes", (9,)), ("test_lower_end_linear_planes", (35,)),
+              ("test_lower_end_conv", ()), ("test_lower_end_attention_v", ())]
+
+
+@pytest.mark.parametrize("name,args", _RANGEEDGE, ids=[f"{n}{list(a)}" for n, a in _RANGEEDGE])
+def test_range_edge_bodies_on_the_emulator(emu, name, args):
+    import test_range_edges_gpu
+    getattr(test_range_edges_gpu, name)(CPU, *args)
+
+
 @pytest.mark.parametrize("tile,persist", [(0, 1), (1, 0), (3, 8), (7, 1), (12, 0), (15, 8), (21, 1), (24, 8), (26, 0), (28, 1), (31, 8), (32, 1), (33, 0), (34, 8), (36, 1)])
 def test_gemm_planes_tiles_small(emu, tile, persist):
     """tests/test_planes_gpu.py::test_gemm_planes_linear_tiles at emulator-sized shapes: symmetric, loader-wave (21+) and 16-wave (26+) tile
