@@ -18,7 +18,7 @@ from typing import Optional
 import torch
 
 from . import ops, synth
-from .engine import ChatterboxEngine, TurboEngine
+from .engine import ChatterboxEngine, S3GenEngine, TurboEngine
 from .text import CJK_LANGUAGES, EnTokenizer, MTLTokenizer, default_max_chars, punc_norm, punc_norm_en, punc_norm_turbo, split_text
 
 S3GEN_SR, S3_SR = 24000, 16000
@@ -123,6 +123,12 @@ def _norm_loudness(wav, sr, target_lufs=-27.0):
     return wav
 
 
+def _load_wave(wav, sr):
+    """A file path or a (waveform, sample_rate) pair -> the waveform at rate `sr` (a float32 array)."""
+    from . import frontend as fe
+    return fe.resample(wav[0], wav[1], sr) if isinstance(wav, (tuple, list)) else fe.load_wav(wav, sr)[0]
+
+
 def _prepare_conditionals(analyzer, wav, exaggeration, prompt_len, device, min_seconds=None, norm_loudness=False, enc_cond_len=None):
     """The common body of prepare_conditionals (tts.py:182-206, mtl_tts.py:253-277, tts_turbo.py:241-270).  `wav`: a file path or a
     (waveform, sample_rate) pair."""
@@ -130,10 +136,7 @@ def _prepare_conditionals(analyzer, wav, exaggeration, prompt_len, device, min_s
     if analyzer is None or not analyzer.tokenizer.available or not analyzer.speaker_encoder.available or analyzer.ve is None:
         raise RuntimeError("voice-prompt analysis needs the `tokenizer.*` and `speaker_encoder.*` tensors of the S3Gen checkpoint and "
                            "ve.safetensors; this model was built without them -- load a prepared voice with Conditionals.load('conds.pt')")
-    if isinstance(wav, (tuple, list)):
-        w24 = fe.resample(wav[0], wav[1], S3GEN_SR)
-    else:
-        w24, _ = fe.load_wav(wav, S3GEN_SR)
+    w24 = _load_wave(wav, S3GEN_SR)
     if min_seconds is not None:
         assert len(w24) / S3GEN_SR > min_seconds, "Audio prompt must be longer than 5 seconds!"
     if norm_loudness:
@@ -331,31 +334,129 @@ def _pick(lst, idx):
     return [lst[i] for i in idx]
 
 
-class _BatchMixin:
-    """generate_batch of the three TTS classes: many requests, mixed voices, one call."""
-    max_batch = None  # utterances per device batch of generate_batch (None: the T3 engine's MAX_BATCH)
+def _voice_key(wav):
+    """What makes two voice prompts of one call the same prompt: a path by its name, a (waveform, sample_rate) pair by identity."""
+    return os.fspath(wav) if isinstance(wav, _PATH) else id(wav)
 
-    def _voices_of_batch(self, B, audio_prompt_paths, conds, exaggeration, analyse=None):
+
+def _analysed_once(requests, analyse):
+    """analyse(wav, *rest) for every (wav, *rest) of `requests`, in their order; requests that are equal (_voice_key, and equal rest) are analysed once per call and
+    share the result."""
+    done, out = {}, []
+    for wav, *rest in requests:
+        key = (_voice_key(wav), *rest)
+        if key not in done:
+            done[key] = analyse(wav, *rest)
+        out.append(done[key])
+    return out
+
+
+_NO_VOICE = "Please `prepare_conditionals` first or specify `audio_prompt_path`"
+
+
+class _Finish:
+    """The epilogue of every public method that returns audio."""
+    sr = S3GEN_SR
+
+    def _finish(self, wav):
+        """A device waveform as the reference returns it: CPU float32 (1, n), watermarked if a watermarker is loaded."""
+        wav = wav.detach().float().cpu()
+        if self.watermarker is not None:
+            wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
+        return wav.unsqueeze(0)
+
+
+class _TTS(_Finish):
+    """The host side of the three TTS classes: the voice of a request, the device batches of generate_batch and generate_long, the pieces of generate_stream.  A
+    backbone says how it differs in a few hooks: _text_ids (text -> tokenizer ids), _engine_tokens (ids -> what its engine takes), _synth_kw (the fixed keywords of
+    its engine calls), N_DRAWS, PROMPT_LEN / ANALYSIS_KW (voice-prompt analysis), _set_exaggeration and _warn_ignored.
+    Only engine, tokenizer, device, analyzer, watermarker and conds are read from the instance (plus model_label on Turbo)."""
+    ENC_COND_LEN, DEC_COND_LEN = 6 * S3_SR, 10 * S3GEN_SR
+    PROMPT_LEN = 150    # T3Config.speech_cond_prompt_len
+    ANALYSIS_KW = {}    # further keywords of the voice-prompt analysis (_prepare_conditionals)
+    max_batch = None    # utterances per device batch of generate_batch / generate_long (None: the T3 engine's MAX_BATCH)
+
+    def __init__(self, engine, tokenizer, device, conds: Optional[Conditionals] = None, analyzer=None):
+        self.engine, self.tokenizer, self.device, self.conds = engine, tokenizer, device, conds
+        self.analyzer = analyzer  # frontend.PromptAnalyzer (S3 tokenizer + CAMPPlus + voice encoder + 24 kHz mel) or None
+        self.t3, self.s3gen, self.ve = engine.t3, engine, (analyzer.ve if analyzer is not None else None)
+        self.watermarker = _watermarker()
+
+    # ------------------------------------------------------------------------------------------------------------ the voice
+    def _analyse(self, wav, exaggeration, **kw):
+        return _prepare_conditionals(self.analyzer, wav, exaggeration, self.PROMPT_LEN, self.device, **self.ANALYSIS_KW, **kw)
+
+    def _use_voice(self, audio_prompt_path, exaggeration, **prepare_kw):
+        """The voice prologue of generate, generate_stream and generate_long: a given prompt is analysed into self.conds, else self.conds must be there; then the
+        exaggeration of the request (a backbone without emotion conditioning ignores it)."""
+        if audio_prompt_path:
+            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, **prepare_kw)
+        else:
+            assert self.conds is not None, _NO_VOICE
+        self._set_exaggeration(exaggeration)
+
+    def _warn_ignored(self, *values):
+        """cfg_weight, exaggeration and min_p of a request (of every request of a batch), for a backbone that does not support them to warn about."""
+
+    def _voices_of_batch(self, B, audio_prompt_paths, conds, exaggeration, **analyse_kw):
         """One Conditionals per request: analysed from `audio_prompt_paths` (equal paths once per call), taken from `conds`, or self.conds.  Never writes self.conds."""
         if audio_prompt_paths is not None and conds is not None:
             raise ValueError("give audio_prompt_paths or conds, not both")
         if audio_prompt_paths is not None:
-            paths, done, out = _per_request(audio_prompt_paths, B, "audio_prompt_paths", _PATH), {}, []
-            for pth, ex in zip(paths, exaggeration):
-                key = (os.fspath(pth) if isinstance(pth, _PATH) else id(pth), ex)
-                if key not in done:
-                    done[key] = (analyse or self._analyse)(pth, ex)
-                out.append(done[key])
-            return out
+            paths = _per_request(audio_prompt_paths, B, "audio_prompt_paths", _PATH)
+            return _analysed_once(zip(paths, exaggeration), lambda wav, ex: self._analyse(wav, ex, **analyse_kw))
         out = _per_request(conds, B, "conds", (Conditionals,)) if conds is not None else [self.conds] * B
-        assert all(c is not None for c in out), "Please `prepare_conditionals` first or specify `audio_prompt_path`"
+        assert all(c is not None for c in out), _NO_VOICE
         return out
 
-    def _run_batch(self, tokens, voices, exaggeration, samp, generator, synth_kw, n_draws, seeds=None, speed=None):
-        """Sub-batches of at most max_batch requests in order of text length: one sub-batch runs the serial schedule (synthesize), several the throughput schedule
-        (synthesize_pipelined; an engine without one runs them one after the other).  Returns the finished waveforms in the caller's order.  seeds (B ints or None)
-        travel with their requests: a request's draws do not depend on the sub-batch or the row it lands in.  speed (B floats or None) travels the same way."""
-        B = len(tokens)
+    # ------------------------------------------------------------------------------------------------------------ one utterance
+    def _generate(self, text_ids, **kw):
+        """generate() behind its argument handling: tokenizer ids -> the finished waveform.  kw: sampling arguments, and _synth_kw's if they are to differ."""
+        wavs, _ = self.engine.synthesize([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw))
+        return self._finish(wavs[0])
+
+    def _generate_stream(self, text_ids, stream_kw, **samp):
+        for r in self.engine.synthesize_stream([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **self._synth_kw(), **stream_kw, **samp):
+            if r["wavs"][0].numel():
+                yield self._finish(r["wavs"][0])
+
+    # ------------------------------------------------------------------------------------------------------------ device batches
+    def _run_jobs(self, jobs, synth_kw):
+        """(wavs or joined piece, speech tokens) of every job, in order: several jobs run the throughput schedule (synthesize_pipelined) where the engine has one;
+        one job, or an engine without it, the serial schedule (synthesize), one job after the other."""
+        if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined"):
+            for r in self.engine.synthesize_pipelined(jobs, **synth_kw):
+                yield r[0], r[1]
+            return
+        for job in jobs:
+            job = dict(job)
+            args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
+            yield self.engine.synthesize(*args, **synth_kw, **job)
+
+    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, **analyse_kw):
+        """generate_batch behind its signature: validation of every per-request argument (seeds and speed first), then the voices, then tokenisation, then the
+        device work.  samp: the sampling arguments the engine takes; unsampled: those it does not -- exaggeration, which picks the voice's cond dict, and what the
+        backbone ignores."""
+        texts = [texts] if isinstance(texts, str) else list(texts)
+        B = len(texts)
+        assert B >= 1, "empty batch"
+        seeds = _batch_seeds(seeds, B, generator)
+        speed = ops.check_speed(speed, B)
+        langs = self._languages(language_ids, B)
+        samp = _sampling_lists(B, **samp)
+        unsampled = _sampling_lists(B, **unsampled)
+        self._warn_ignored(*(v for vals in unsampled.values() for v in vals))
+        voices = self._voices_of_batch(B, audio_prompt_paths, conds, unsampled["exaggeration"], **analyse_kw)
+        tokens = [self._engine_tokens(self._text_ids(t, lid)) for t, lid in zip(texts, langs)]
+        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed)
+
+    def _languages(self, language_ids, B):
+        return [None] * B
+
+    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None):
+        """Sub-batches of at most max_batch requests in order of text length (_run_jobs: one runs the serial schedule, several the throughput schedule).  Returns the
+        finished waveforms in the caller's order.  seeds (B ints or None) travel with their requests: a request's draws do not depend on the sub-batch or the row
+        it lands in.  speed (B floats or None) travels the same way."""
         dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
         plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
         jobs = []
@@ -363,48 +464,39 @@ class _BatchMixin:
             job = dict(text_tokens=_pick(tokens, idx), t3_conds=_one_or_list(_pick(dicts, idx)), gen_ref=_one_or_list([voices[i].gen for i in idx]),
                        **{k: _pick(v, idx) for k, v in samp.items()})
             if generator is not None:  # repeatable: the sampling draws of every sub-batch come from the generator, in execution order
-                job["uniforms"] = torch.rand(len(idx), n_draws, device=self.engine.dev, generator=generator)
+                job["uniforms"] = torch.rand(len(idx), self.N_DRAWS, device=self.engine.dev, generator=generator)
                 job["generator"] = generator
             if seeds is not None:
                 job["seeds"] = _pick(seeds, idx)
             if speed is not None:
                 job["speed"] = _pick(speed, idx)
             jobs.append(job)
-        out = [None] * B
-        if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined"):
-            results = (r[0] for r in self.engine.synthesize_pipelined(jobs, **synth_kw))
-        else:
-            def serial():
-                for job in jobs:
-                    job = dict(job)
-                    args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
-                    yield self.engine.synthesize(*args, **synth_kw, **job)[0]
-            results = serial()
-        for idx, wavs in zip(plan, results):
+        out = [None] * len(tokens)
+        for idx, (wavs, _) in zip(plan, self._run_jobs(jobs, self._synth_kw(batch=True))):
             for i, w in zip(idx, wavs):
                 out[i] = self._finish(w)
         return out
 
+    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, **prepare_kw):
+        """generate_long behind its signature and _long_args: the remaining checks, the voice as generate() prepares it, then _run_long.  samp / unsampled: as
+        _generate_batch takes them, one number each."""
+        if not isinstance(text, str):
+            raise TypeError(f"text: expected a str, got {type(text).__name__}")
+        _long_numbers(**unsampled, **samp)
+        self._use_voice(audio_prompt_path, unsampled["exaggeration"], **prepare_kw)
+        self._warn_ignored(*unsampled.values())
+        return self._run_long(text, a, lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id)), samp, return_segments)
 
-    def _run_long(self, text, a, tokenize, samp, synth_kw, return_segments):
-        """generate_long behind its validation: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), run the jobs of long_plan -- one through
-        synthesize, several through synthesize_pipelined where the engine has it --, concatenate the joined pieces on the host, watermark the whole once."""
+    def _run_long(self, text, a, tokenize, samp, return_segments):
+        """generate_long behind its validation: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), run the jobs of long_plan (_run_jobs), concatenate
+        the joined pieces on the host, watermark the whole once."""
         chunks = split_text(text, a["max_chars"])
         tokens = [tokenize(c) for c, _ in chunks]
         plan = long_plan(chunks, int(self.max_batch or self.engine.t3.MAX_BATCH), a)
         t3, gen = self.conds.t3.as_dict(), self.conds.gen
         jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join") if k in p}) for p in plan]
-        if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined"):
-            results = ((r[0], r[1]) for r in self.engine.synthesize_pipelined(jobs, **synth_kw))
-        else:
-            def serial():
-                for job in jobs:
-                    job = dict(job)
-                    args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
-                    yield self.engine.synthesize(*args, **synth_kw, **job)
-            results = serial()
         pieces, segments, base = [], [], 0
-        for p, (piece, st) in zip(plan, results):
+        for p, (piece, st) in zip(plan, self._run_jobs(jobs, self._synth_kw())):
             pieces.append(piece["wav"].detach().float().cpu())
             assert pieces[-1].numel() == piece["total"], "a joined piece and its layout record disagree"
             for r, k in enumerate(p["chunks"]):
@@ -421,27 +513,14 @@ class _BatchMixin:
         return (wav, segments) if return_segments else wav
 
 
-class _Base(_BatchMixin):
-    sr = S3GEN_SR
-
-    ENC_COND_LEN, DEC_COND_LEN = 6 * S3_SR, 10 * S3GEN_SR
-    PROMPT_LEN = 150  # T3Config.speech_cond_prompt_len
-
-    def __init__(self, engine: ChatterboxEngine, tokenizer, device, conds: Optional[Conditionals] = None, analyzer=None):
-        self.engine, self.tokenizer, self.device, self.conds = engine, tokenizer, device, conds
-        self.analyzer = analyzer  # frontend.PromptAnalyzer (S3 tokenizer + CAMPPlus + voice encoder + 24 kHz mel) or None
-        self.t3, self.s3gen, self.ve = engine.t3, engine, (analyzer.ve if analyzer is not None else None)
-        self.watermarker = _watermarker()
+class _LlamaTTS(_TTS):
+    """The two classes on the Llama T3: text ids wrapped in start / end-of-text, CFG, min_p and an emotion scalar in the voice."""
+    N_DRAWS = 1000             # sampling draws of an utterance: max_new_tokens
+    DROP_LAST_TOKEN = False    # the multilingual path drops the last token's 40 ms (mtl_tts.py:348-352)
 
     def prepare_conditionals(self, wav_fpath, exaggeration=0.5):
         """reference tts.py:182-206 / mtl_tts.py:253-277: waveform file -> self.conds."""
-        self.conds = _prepare_conditionals(self.analyzer, wav_fpath, exaggeration, self.PROMPT_LEN, self.device)
-
-    def _finish(self, wav):
-        wav = wav.detach().float().cpu()
-        if self.watermarker is not None:
-            wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
-        return wav.unsqueeze(0)
+        self.conds = self._analyse(wav_fpath, exaggeration)
 
     def _set_exaggeration(self, exaggeration):
         cur = float(torch.as_tensor(self.conds.t3.emotion_adv).reshape(-1)[0])
@@ -450,52 +529,12 @@ class _Base(_BatchMixin):
             self.conds.t3 = T3Cond(speaker_emb=c.speaker_emb, cond_prompt_speech_tokens=c.cond_prompt_speech_tokens,
                                    emotion_adv=exaggeration * torch.ones(1, 1, 1))
 
-    def _generate(self, text_tokens, drop_last_token, **samp):
+    def _engine_tokens(self, text_ids):
         sot, eot = 255, 0
-        tt = torch.cat([torch.tensor([sot]), text_tokens.view(-1).long().cpu(), torch.tensor([eot])])
-        wavs, _ = self.engine.synthesize([tt], self.conds.t3.as_dict(), self.conds.gen, max_new_tokens=1000,
-                                         drop_last_token=drop_last_token, **samp)
-        return self._finish(wavs[0])
+        return torch.cat([torch.tensor([sot]), text_ids.view(-1).long().cpu(), torch.tensor([eot])])
 
-    def _generate_stream(self, text_tokens, drop_last_token, stream_kw, **samp):
-        sot, eot = 255, 0
-        tt = torch.cat([torch.tensor([sot]), text_tokens.view(-1).long().cpu(), torch.tensor([eot])])
-        for r in self.engine.synthesize_stream([tt], self.conds.t3.as_dict(), self.conds.gen, max_new_tokens=1000, drop_last_token=drop_last_token,
-                                               **stream_kw, **samp):
-            if r["wavs"][0].numel():
-                yield self._finish(r["wavs"][0])
-
-    def _analyse(self, wav_fpath, exaggeration):
-        return _prepare_conditionals(self.analyzer, wav_fpath, exaggeration, self.PROMPT_LEN, self.device)
-
-    def _generate_batch(self, B, tokenize, audio_prompt_paths, conds, exaggeration, drop_last_token, generator, seeds=None, speed=None, **samp):
-        """Validation of every per-request argument, then tokenisation (`tokenize()` -> B id tensors), then the device work."""
-        seeds = _batch_seeds(seeds, B, generator)
-        speed = ops.check_speed(speed, B)
-        samp = _sampling_lists(B, **samp)
-        exaggeration = _sampling_lists(B, exaggeration=exaggeration)["exaggeration"]
-        voices = self._voices_of_batch(B, audio_prompt_paths, conds, exaggeration)
-        sot, eot = 255, 0
-        tts = [torch.cat([torch.tensor([sot]), t.view(-1).long().cpu(), torch.tensor([eot])]) for t in tokenize()]
-        return self._run_batch(tts, voices, exaggeration, samp, generator, dict(max_new_tokens=1000, drop_last_token=drop_last_token), 1000, seeds, speed)
-
-    def _generate_long(self, text, language_id, norm, drop_last_token, audio_prompt_path, exaggeration, a, return_segments, **samp):
-        """The body of generate_long of the two Llama-backbone classes: the remaining checks, the voice as generate() prepares it, then _run_long."""
-        if not isinstance(text, str):
-            raise TypeError(f"text: expected a str, got {type(text).__name__}")
-        _long_numbers(exaggeration=exaggeration, **samp)
-        if audio_prompt_path:
-            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
-        else:
-            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
-        self._set_exaggeration(exaggeration)
-        sot, eot = 255, 0
-        lang = {} if language_id is None and norm is punc_norm_en else dict(language_id=language_id)
-
-        def tokenize(chunk):
-            toks = self.tokenizer.text_to_tokens(norm(chunk), **lang)
-            return torch.cat([torch.tensor([sot]), toks.view(-1).long().cpu(), torch.tensor([eot])])
-        return self._run_long(text, a, tokenize, samp, dict(max_new_tokens=1000, drop_last_token=drop_last_token), return_segments)
+    def _synth_kw(self, batch=False):
+        return dict(max_new_tokens=1000, drop_last_token=self.DROP_LAST_TOKEN)
 
     @classmethod
     def from_synthetic(cls, device="cuda", seed=0, t3_layers=30, **kw):
@@ -512,7 +551,7 @@ class _Base(_BatchMixin):
         return cls(eng, None, device, conds, analyzer)
 
 
-class ChatterboxTTS(_Base):
+class ChatterboxTTS(_LlamaTTS):
     _TEXT_VOCAB = 704
 
     @classmethod
@@ -531,22 +570,21 @@ class ChatterboxTTS(_Base):
             local = hf_hub_download(repo_id=REPO_ID, filename=f)
         return cls.from_local(Path(local).parent, device)
 
+    def _text_ids(self, text, language_id=None):
+        return self.tokenizer.text_to_tokens(punc_norm_en(text))
+
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                  cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
         alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
         speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
         the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
-        speed 1.0 gives K * 480."""
+        speed 1.0 gives K * 480.
+        This is the statement of `seed` and `speed` for generate() of every class of this module; the others say only what differs."""
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
-        if audio_prompt_path:
-            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
-        else:
-            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
-        self._set_exaggeration(exaggeration)
-        toks = self.tokenizer.text_to_tokens(punc_norm_en(text))
-        return self._generate(toks, drop_last_token=False, temperature=temperature, cfg_weight=cfg_weight,
-                              repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
+        self._use_voice(audio_prompt_path, exaggeration)
+        return self._generate(self._text_ids(text), temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
+                              top_p=top_p, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                       max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False):
@@ -563,9 +601,9 @@ class ChatterboxTTS(_Base):
         result (usable for captions), [src_start, src_stop) the part of its own waveform that was kept.  A chunk whose T3 spent the token budget without an
         end-of-speech token is `truncated`; one warning names them.  Every argument is checked before anything is launched; self.conds is written only as
         generate() writes it (audio_prompt_path)."""
-        return self._generate_long(text, None, punc_norm_en, False, audio_prompt_path, exaggeration,
-                                   _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False), return_segments,
-                                   temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
+        samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration))
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
                        min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0):
@@ -578,32 +616,36 @@ class ChatterboxTTS(_Base):
         alone -- not on the other requests, its row, the sub-batch split or the order of calls -- and are those of generate(seed=seeds[b]).  Its tokens and audio
         then agree with that call's as far as batched and single arithmetic agree: the kernels pick their forms by row count, so this is not bit equality.
         speed (a number for every request, or a sequence of B numbers in [0.5, 2.0]; None entries are 1.0): request b's speaking rate, generate(speed=)'s; it
-        travels with its request through the sub-batches like its seed."""
-        texts = [texts] if isinstance(texts, str) else list(texts)
-        assert len(texts) >= 1, "empty batch"
-        return self._generate_batch(len(texts), lambda: [self.tokenizer.text_to_tokens(punc_norm_en(t)) for t in texts], audio_prompt_paths, conds, exaggeration,
-                                    False, generator, seeds, speed, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        travels with its request through the sub-batches like its seed.
+        This is the contract of generate_batch of every class of this module; the others say only what differs."""
+        samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration))
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                         cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, speed=1.0):
-        """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
+        """generate() in pieces (the engine's synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
         `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
         window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream).
         seed: generate()'s.  speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate -- the pieces add up to the length generate(speed=) returns;
-        checked, with the window it asks for (engine.check_stream_window), when this is called."""
+        checked, with the window it asks for (engine.check_stream_window), when this is called.
+        This is the contract of generate_stream of the three TTS classes; the others say only what differs."""
         seed_kw = _seed_kw(seed)
-        if audio_prompt_path:
-            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
-        else:
-            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
-        self._set_exaggeration(exaggeration)
-        toks = self.tokenizer.text_to_tokens(punc_norm_en(text))
-        return self._generate_stream(toks, False, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature,
+        self._use_voice(audio_prompt_path, exaggeration)
+        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature,
                                      cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
 
 
-class ChatterboxMultilingualTTS(_Base):
+def _language(language_id, request=""):
+    """A language id as the tokenizer takes it: lower case, or None for none.  An unknown one is the reference's ValueError (mtl_tts.py); `request` names the
+    request of a batch it belongs to."""
+    if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
+        raise ValueError(f"Unsupported language_id '{language_id}'{request}. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
+    return language_id.lower() if language_id else None
+
+
+class ChatterboxMultilingualTTS(_LlamaTTS):
     _TEXT_VOCAB = 2454
+    DROP_LAST_TOKEN = True
 
     @classmethod
     def get_supported_languages(cls):
@@ -628,82 +670,63 @@ class ChatterboxMultilingualTTS(_Base):
                                               "Cangjie5_TC.json"])
         return cls.from_local(d, device, t3_model=t3_model)
 
+    def _text_ids(self, text, language_id=None):
+        """language_id: checked and lower case already (_language)"""
+        return self.tokenizer.text_to_tokens(punc_norm(text), language_id=language_id)
+
+    def _languages(self, language_ids, B):
+        langs = _per_request(language_ids, B, "language_ids", (str,))
+        return [_language(lid, f" (request {k})") for k, lid in enumerate(langs)]
+
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                  repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0):
-        """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
-        alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
-        speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
-        the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
-        speed 1.0 gives K * 480."""
+        """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
+        token's 40 ms are dropped as the reference does.  seed, speed: as there."""
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
-        if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
-            raise ValueError(f"Unsupported language_id '{language_id}'. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
-        if audio_prompt_path:
-            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
-        else:
-            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
-        self._set_exaggeration(exaggeration)
-        toks = self.tokenizer.text_to_tokens(punc_norm(text), language_id=language_id.lower() if language_id else None)
-        return self._generate(toks, drop_last_token=True, temperature=temperature, cfg_weight=cfg_weight,
-                              repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
+        lid = _language(language_id)
+        self._use_voice(audio_prompt_path, exaggeration)
+        return self._generate(self._text_ids(text, lid), temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
+                              top_p=top_p, **seed_kw)
 
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                       return_segments=False):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
-        if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
-            raise ValueError(f"Unsupported language_id '{language_id}'. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
-        lid = language_id.lower() if language_id else None
-        return self._generate_long(text, lid, punc_norm, True, audio_prompt_path, exaggeration,
-                                   _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES), return_segments,
-                                   temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        lid = _language(language_id)
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
+        samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration))
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0):
-        """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does."""
-        texts = [texts] if isinstance(texts, str) else list(texts)
-        assert len(texts) >= 1, "empty batch"
-        seeds = _batch_seeds(seeds, len(texts), generator)
-        speed = ops.check_speed(speed, len(texts))
-        langs = _per_request(language_ids, len(texts), "language_ids", (str,))
-        for k, lid in enumerate(langs):
-            if lid and lid.lower() not in SUPPORTED_LANGUAGES:
-                raise ValueError(f"Unsupported language_id '{lid}' (request {k}). Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
-        tok = lambda: [self.tokenizer.text_to_tokens(punc_norm(t), language_id=lid.lower() if lid else None) for t, lid in zip(texts, langs)]
-        return self._generate_batch(len(texts), tok, audio_prompt_paths, conds, exaggeration, True, generator, seeds, speed, temperature=temperature, cfg_weight=cfg_weight,
-                                    repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
+        speed, before the sampling arguments)."""
+        samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration))
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
                         seed=None, speed=1.0):
-        """generate() in pieces (ChatterboxEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
-        `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
-        window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream).
-        seed: generate()'s.  speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate -- the pieces add up to the length generate(speed=) returns;
-        checked, with the window it asks for (engine.check_stream_window), when this is called."""
+        """ChatterboxTTS.generate_stream with generate()'s language_id."""
         seed_kw = _seed_kw(seed)
-        if language_id and language_id.lower() not in SUPPORTED_LANGUAGES:
-            raise ValueError(f"Unsupported language_id '{language_id}'. Supported languages: {', '.join(SUPPORTED_LANGUAGES)}")
-        if audio_prompt_path:
-            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration)
-        else:
-            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
-        self._set_exaggeration(exaggeration)
-        toks = self.tokenizer.text_to_tokens(punc_norm(text), language_id=language_id.lower() if language_id else None)
-        return self._generate_stream(toks, True, _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature,
-                                     cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
+        lid = _language(language_id)
+        self._use_voice(audio_prompt_path, exaggeration)
+        return self._generate_stream(self._text_ids(text, lid), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed),
+                                     temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
 
 
-class ChatterboxTurboTTS(_BatchMixin):
-    """Reference tts_turbo.py:111-320: GPT2-medium (Turbo) or GPT2-small (Nano) T3, meanflow S3Gen, GPT-2 BPE tokenizer."""
-    sr = S3GEN_SR
-    ENC_COND_LEN, DEC_COND_LEN = 15 * S3_SR, 10 * S3GEN_SR  # tts_turbo.py:112-113: the T3 prompt covers up to 15 s (375 tokens)
+class ChatterboxTurboTTS(_TTS):
+    """Reference tts_turbo.py:111-320: GPT2-medium (Turbo) or GPT2-small (Nano) T3, meanflow S3Gen, GPT-2 BPE tokenizer.  CFG, min_p and exaggeration are not
+    supported by this backbone: the arguments are there for the reference's signatures and ignored with its warning.  The engine has no throughput schedule: the
+    device batches of generate_batch and generate_long run one after the other."""
+    ENC_COND_LEN = 15 * S3_SR  # tts_turbo.py:112-113: the T3 prompt covers up to 15 s (375 tokens)
+    PROMPT_LEN = 375
+    ANALYSIS_KW = dict(min_seconds=5.0, enc_cond_len=ENC_COND_LEN)
+    N_DRAWS = 1001  # T3 can sample max_gen_len + 1 tokens
 
     def __init__(self, engine, tokenizer, device, conds=None, model_label="Turbo", analyzer=None):
-        self.engine, self.tokenizer, self.device, self.conds, self.model_label = engine, tokenizer, device, conds, model_label
-        self.analyzer = analyzer
-        self.t3, self.s3gen, self.ve = engine.t3, engine, (analyzer.ve if analyzer is not None else None)
-        self.watermarker = _watermarker()
+        super().__init__(engine, tokenizer, device, conds, analyzer)
+        self.model_label = model_label
 
     @classmethod
     def from_local(cls, ckpt_dir, device, nano=False):
@@ -742,112 +765,66 @@ class ChatterboxTurboTTS(_BatchMixin):
 
     def prepare_conditionals(self, wav_fpath, exaggeration=0.0, norm_loudness=True):
         """reference tts_turbo.py:241-270 (prompt > 5 s, optional loudness normalisation to -27 LUFS, 375 prompt tokens)."""
-        self.conds = _prepare_conditionals(self.analyzer, wav_fpath, exaggeration, 375, self.device, min_seconds=5.0,
-                                           norm_loudness=norm_loudness, enc_cond_len=self.ENC_COND_LEN)
+        self.conds = self._analyse(wav_fpath, exaggeration, norm_loudness=norm_loudness)
 
-    def _generate(self, text_tokens, **samp):
-        wavs, _ = self.engine.synthesize([text_tokens.view(-1).long().cpu()], self.conds.t3.as_dict(), self.conds.gen, **samp)
-        wav = wavs[0].detach().float().cpu()
-        if self.watermarker is not None:
-            wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
-        return wav.unsqueeze(0)
+    def _set_exaggeration(self, exaggeration):
+        """(no emotion conditioning on this backbone: the voice stays as it is)"""
+
+    def _warn_ignored(self, *values):
+        if any(v > 0.0 for v in values):
+            import logging
+            logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
+
+    def _text_ids(self, text, language_id=None):
+        return self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids[0]
+
+    def _engine_tokens(self, text_ids):
+        return text_ids.view(-1).long().cpu()
+
+    def _synth_kw(self, batch=False):
+        """(generate_batch spells the token budget out; generate, generate_stream and generate_long leave it to the engine's default, the same 1000)"""
+        return dict(max_gen_len=1000) if batch else {}
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
                  temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0):
-        """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
-        alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
-        speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
-        the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
-        speed 1.0 gives K * 480."""
+        """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed: as ChatterboxTTS.generate."""
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
-        if audio_prompt_path:
-            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, norm_loudness=norm_loudness)
-        else:
-            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
-        if cfg_weight > 0.0 or exaggeration > 0.0 or min_p > 0.0:
-            import logging
-            logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
-        ids = self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids
-        return self._generate(ids[0], temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
+        self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
+        self._warn_ignored(cfg_weight, exaggeration, min_p)
+        return self._generate(self._text_ids(text), temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                       top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                       return_segments=False):
         """ChatterboxTTS.generate_long on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other)."""
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        if not isinstance(text, str):
-            raise TypeError(f"text: expected a str, got {type(text).__name__}")
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
-        _long_numbers(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p, **samp)
-        if audio_prompt_path:
-            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, norm_loudness=norm_loudness)
-        else:
-            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
-        if cfg_weight > 0.0 or exaggeration > 0.0 or min_p > 0.0:
-            import logging
-            logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
-        tokenize = lambda chunk: self.tokenizer(punc_norm_turbo(chunk), return_tensors="pt", padding=True, truncation=True).input_ids[0].view(-1).long().cpu()
-        return self._run_long(text, a, tokenize, samp, {}, return_segments)
-
-    def _analyse(self, wav_fpath, exaggeration, norm_loudness=True):
-        return _prepare_conditionals(self.analyzer, wav_fpath, exaggeration, 375, self.device, min_seconds=5.0, norm_loudness=norm_loudness,
-                                     enc_cond_len=self.ENC_COND_LEN)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
+                                   norm_loudness=norm_loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
                        top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0):
         """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
-        of B).  CFG, min_p and exaggeration are not supported by this backbone: ignored with generate()'s warning.  Sub-batches run one after the other.  seeds, speed: as ChatterboxTTS.generate_batch."""
-        texts = [texts] if isinstance(texts, str) else list(texts)
-        B = len(texts)
-        assert B >= 1, "empty batch"
-        seeds = _batch_seeds(seeds, B, generator)
-        speed = ops.check_speed(speed, B)
-        samp = _sampling_lists(B, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
-        ign = _sampling_lists(B, cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p)
-        if any(v > 0.0 for vals in ign.values() for v in vals):
-            import logging
-            logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
-        voices = self._voices_of_batch(B, audio_prompt_paths, conds, ign["exaggeration"], lambda p, ex: self._analyse(p, ex, norm_loudness=norm_loudness))
-        ids = [self.tokenizer(punc_norm_turbo(t), return_tensors="pt", padding=True, truncation=True).input_ids[0].view(-1).long().cpu() for t in texts]
-        return self._run_batch(ids, voices, ign["exaggeration"], samp, generator, dict(max_gen_len=1000), 1001, seeds, speed)
-
-    def _finish(self, wav):
-        wav = wav.detach().float().cpu()
-        if self.watermarker is not None:
-            wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
-        return wav.unsqueeze(0)
-
-    def _generate_stream(self, text_tokens, stream_kw, **samp):
-        for r in self.engine.synthesize_stream([text_tokens.view(-1).long().cpu()], self.conds.t3.as_dict(), self.conds.gen, **stream_kw, **samp):
-            if r["wavs"][0].numel():
-                yield self._finish(r["wavs"][0])
+        of B).  CFG, min_p and exaggeration are ignored with generate()'s warning.  Sub-batches run one after the other."""
+        samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
+        return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
+                                    norm_loudness=norm_loudness)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
                         temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
                         seed=None, speed=1.0):
-        """generate() in pieces (TurboEngine.synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk`
-        tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
-        window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream).
-        seed: generate()'s.  speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate -- the pieces add up to the length generate(speed=) returns;
-        checked, with the window it asks for (engine.check_stream_window), when this is called."""
+        """ChatterboxTTS.generate_stream on the Turbo / Nano backbone (TurboEngine.synthesize_stream; generate()'s sampling arguments)."""
         seed_kw = _seed_kw(seed)
-        if audio_prompt_path:
-            self.prepare_conditionals(audio_prompt_path, exaggeration=exaggeration, norm_loudness=norm_loudness)
-        else:
-            assert self.conds is not None, "Please `prepare_conditionals` first or specify `audio_prompt_path`"
-        if cfg_weight > 0.0 or exaggeration > 0.0 or min_p > 0.0:
-            import logging
-            logging.getLogger(__name__).warning(f"CFG, min_p and exaggeration are not supported by the {self.model_label} version and will be ignored.")
-        ids = self.tokenizer(punc_norm_turbo(text), return_tensors="pt", padding=True, truncation=True).input_ids
-        return self._generate_stream(ids[0], _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature, top_k=top_k,
-                                     top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
+        self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
+        self._warn_ignored(cfg_weight, exaggeration, min_p)
+        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature,
+                                     top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
 
 
-class ChatterboxVC:
+class ChatterboxVC(_Finish):
     """Voice conversion (reference vc.py:16-104): S3 tokens of the source audio (S3 tokenizer on the device) -> S3Gen with the target
     voice -> HiFT.  `generate` also accepts the source as S3 tokens (`s3_tokens=`): the parity contract of config 5 starts at the token
     boundary because the tokenizer's arithmetic is third-party."""
-    sr = S3GEN_SR
     ENC_COND_LEN, DEC_COND_LEN = 6 * S3_SR, 10 * S3GEN_SR
 
     def __init__(self, engine, device, ref_dict=None, analyzer=None):
@@ -857,11 +834,8 @@ class ChatterboxVC:
 
     @staticmethod
     def _engine(s3, device):
-        from .hift import HiFTEngine
-        from .s3gen import FlowEngine
-        eng = ChatterboxEngine.__new__(ChatterboxEngine)
-        eng.dev, eng.t3, eng.flow, eng.hift, eng.last_timing = torch.device(device), None, FlowEngine(s3, device), HiFTEngine(s3, device), {}
-        return eng
+        """The flow-and-vocoder engine of a voice conversion: no T3."""
+        return S3GenEngine(s3, device)
 
     @classmethod
     def from_local(cls, ckpt_dir, device):
@@ -888,12 +862,18 @@ class ChatterboxVC:
             raise RuntimeError("this S3Gen checkpoint carries no `tokenizer.*` / `speaker_encoder.*` tensors: pass s3_tokens= and a prepared "
                                "ref_dict instead of waveforms")
 
+    def _embed_ref(self, wav):
+        """A target voice (a WAV path or a (waveform, sample_rate) pair) -> its S3Gen reference dict"""
+        return self.analyzer.embed_ref(_load_wave(wav, S3GEN_SR)[: self.DEC_COND_LEN], S3GEN_SR)
+
+    def _tokens_of(self, audio):
+        """A source (a WAV path or a (waveform, sample_rate) pair) -> its S3 tokens"""
+        return self.analyzer.tokenizer(torch.from_numpy(_load_wave(audio, S3_SR)))[0]
+
     def set_target_voice(self, wav_fpath):
         """reference vc.py:76-81"""
-        from . import frontend as fe
         self._need_analyzer()
-        w24 = fe.resample(wav_fpath[0], wav_fpath[1], S3GEN_SR) if isinstance(wav_fpath, (tuple, list)) else fe.load_wav(wav_fpath, S3GEN_SR)[0]
-        self.ref_dict = self.analyzer.embed_ref(w24[: self.DEC_COND_LEN], S3GEN_SR)
+        self.ref_dict = self._embed_ref(wav_fpath)
 
     def _source_tokens(self, audio, target_voice_path, s3_tokens):
         """The argument handling of generate (reference vc.py:83-104) -> the source's S3 tokens, 1-D on the host.  self.ref_dict is written only when a
@@ -903,30 +883,19 @@ class ChatterboxVC:
         else:
             assert self.ref_dict is not None, "Please `prepare_conditionals` first or specify `target_voice_path`"
         if s3_tokens is None:
-            from . import frontend as fe
             self._need_analyzer()
-            w16 = fe.resample(audio[0], audio[1], S3_SR) if isinstance(audio, (tuple, list)) else fe.load_wav(audio, S3_SR)[0]
-            s3_tokens, _ = self.analyzer.tokenizer(torch.from_numpy(w16))
+            s3_tokens = self._tokens_of(audio)
         return torch.as_tensor(s3_tokens).view(-1).long().cpu()
 
-    def _finish(self, wav):
-        wav = wav.detach().float().cpu()
-        if self.watermarker is not None:
-            wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
-        return wav.unsqueeze(0)
-
     def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0):
-        """reference vc.py:83-104.  audio: a WAV path or a (waveform, sample_rate) pair.  seed (None, or an int in [0, 2^64)): the flow noise and the vocoder's
-        phase and noise are a function of the seed alone (no torch RNG is consumed), those generate_batch(seeds=) gives the request in any batch.
-        speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
-        the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
-        speed 1.0 gives K * 480."""
+        """reference vc.py:83-104.  audio: a WAV path or a (waveform, sample_rate) pair.  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
+        are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's."""
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
         wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **seed_kw)
         return self._finish(wavs[0])
 
     def generate_stream(self, audio=None, target_voice_path=None, s3_tokens=None, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=200, seed=None, speed=1.0):
-        """generate() in pieces (ChatterboxEngine.vocode_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk` tokens of
+        """generate() in pieces (the engine's vocode_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk` tokens of
         the source; concatenated along dim 1 they give the conversion.  A round synthesises the target voice's prompt, `window` tokens of left context, the new
         chunk and the lookahead, so its cost does not grow with the length of the source (window=None: every round re-synthesises everything so far); the
         default 200 + chunk 50 is the 250-token round the flow is tuned at.  Arguments are checked and the source is tokenised when this is CALLED, as generate
@@ -961,9 +930,8 @@ class ChatterboxVC:
         """generate() for B conversions in one call: `audios` (WAV paths or (waveform, sample_rate) pairs) or `s3_tokens` (B id sequences); target voice per
         request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
         self.ref_dict.  Returns B CPU float32 tensors (1, n_b) at `.sr` in the caller's order; more than MAX_BATCH requests run as sub-batches in order of length.
-        Never overwrites self.ref_dict.  seeds (None, an int for every request, or a sequence of B ints in [0, 2^64)): request b's noise depends on seeds[b]
-        alone and is that of generate(seed=seeds[b]) (ChatterboxTTS.generate_batch states the guarantee).  speed: a number, or a sequence of B numbers in
-        [0.5, 2.0] (None entries: 1.0) -- request b's speaking rate, generate(speed=)'s."""
+        Never overwrites self.ref_dict.  seeds, speed: per request as ChatterboxTTS.generate_batch states them -- request b's noise is that of
+        generate(seed=seeds[b]), its speaking rate generate(speed=speed[b])'s."""
         src = s3_tokens if s3_tokens is not None else audios
         assert src is not None, "give audios or s3_tokens"
         src = [src] if (isinstance(src, _PATH) or (torch.is_tensor(src) and src.dim() <= 1)) else list(src)
@@ -974,35 +942,19 @@ class ChatterboxVC:
         if target_voice_paths is not None and ref_dicts is not None:
             raise ValueError("give target_voice_paths or ref_dicts, not both")
         if target_voice_paths is not None:
-            from . import frontend as fe
             self._need_analyzer()
-            done, refs = {}, []
-            for pth in _per_request(target_voice_paths, B, "target_voice_paths", _PATH):
-                key = os.fspath(pth) if isinstance(pth, _PATH) else id(pth)
-                if key not in done:
-                    w24 = fe.resample(pth[0], pth[1], S3GEN_SR) if isinstance(pth, (tuple, list)) else fe.load_wav(pth, S3GEN_SR)[0]
-                    done[key] = self.analyzer.embed_ref(w24[: self.DEC_COND_LEN], S3GEN_SR)
-                refs.append(done[key])
+            refs = _analysed_once(((p,) for p in _per_request(target_voice_paths, B, "target_voice_paths", _PATH)), self._embed_ref)
         else:
             refs = _per_request(ref_dicts, B, "ref_dicts", (dict,)) if ref_dicts is not None else [self.ref_dict] * B
             assert all(r is not None for r in refs), "Please `prepare_conditionals` first or specify `target_voice_path`"
         if s3_tokens is None:
-            from . import frontend as fe
             self._need_analyzer()
-            toks = []
-            for a in src:
-                w16 = fe.resample(a[0], a[1], S3_SR) if isinstance(a, (tuple, list)) else fe.load_wav(a, S3_SR)[0]
-                toks.append(self.analyzer.tokenizer(torch.from_numpy(w16))[0])
-        else:
-            toks = src
-        toks = [torch.as_tensor(t).view(-1).long().cpu() for t in toks]
+            src = [self._tokens_of(a) for a in src]
+        toks = [torch.as_tensor(t).view(-1).long().cpu() for t in src]
         out = [None] * B
         for idx in batch_plan([int(t.numel()) for t in toks], int(self.MAX_BATCH)):
             wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **({} if seeds is None else dict(seeds=_pick(seeds, idx))),
                                          **({} if speed is None else dict(speed=_pick(speed, idx))))
             for i, w in zip(idx, wavs):
-                w = w.detach().float().cpu()
-                if self.watermarker is not None:
-                    w = torch.from_numpy(self.watermarker.apply_watermark(w.numpy(), sample_rate=self.sr))
-                out[i] = w.unsqueeze(0)
+                out[i] = self._finish(w)
         return out

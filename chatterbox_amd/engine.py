@@ -5,6 +5,7 @@ speech tokens are stripped of SOS/EOS (`drop_invalid_tokens`, s3tokenizer/__init
 on the padded batch, and each waveform is cut to its own length (the multilingual path also drops the last
 token's 40 ms, mtl_tts.py:348-352).
 """
+import contextlib
 import math
 import os
 import time
@@ -30,16 +31,24 @@ def _range_checked(eng, run, check=True):
     exponent range.  check=False: the caller looks at ops.range_flag_tripped() itself at its next synchronisation point."""
     out = run()
     if check and 16 in (eng.flow.precision, eng.hift.precision) and ops.range_flag_tripped():
-        warnings.warn("an S3Gen operand exceeded the fp16 range: repeating flow matching + vocoder at bf16x6")
-        global RANGE_TRIPS
-        RANGE_TRIPS += 1
-        saved = eng.flow.precision, eng.hift.precision
-        eng.flow.precision, eng.hift.precision = (6 if p == 16 else p for p in saved)
-        try:
+        with _repeat_at_bf16x6(eng):
             out = run()
-        finally:
-            eng.flow.precision, eng.hift.precision = saved
     return out
+
+
+@contextlib.contextmanager
+def _repeat_at_bf16x6(eng, what=""):
+    """The repeat of S3Gen work whose f16x3 pass raised the range flag: one warning (`what` names the work if it is not the whole call), one count in RANGE_TRIPS,
+    and inside the block every engine that runs at precision 16 runs at 6; the precisions are restored behind it, also when the repeat raises."""
+    warnings.warn(f"an S3Gen operand exceeded the fp16 range: repeating flow matching + vocoder{what} at bf16x6")
+    global RANGE_TRIPS
+    RANGE_TRIPS += 1
+    saved = eng.flow.precision, eng.hift.precision
+    eng.flow.precision, eng.hift.precision = (6 if p == 16 else p for p in saved)
+    try:
+        yield
+    finally:
+        eng.flow.precision, eng.hift.precision = saved
 
 
 def drop_invalid_tokens(x):
@@ -53,33 +62,38 @@ def drop_invalid_tokens(x):
     return x[x < SPEECH_VOCAB]
 
 
-class ChatterboxEngine:
-    def __init__(self, t3_sd, s3gen_sd, device="cuda", n_t3_layers=None, meanflow=False, t3_weights=None):
+def _valid_tokens(toks):
+    """What T3 sampled, per utterance, as the flow takes it: drop_invalid_tokens, and the single token 0 for an utterance of which nothing is left (flow and
+    vocoder need a frame to work on)."""
+    st = [drop_invalid_tokens(t) for t in toks]
+    return [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
+
+
+def _checked_job(job):
+    """A job of synthesize_pipelined with its optional keys checked as synthesize checks its arguments: seeds (ops.request_seeds; not together with the job's
+    generator), speed (ops.check_speed), join (ops.check_join).  A join of None is dropped: from here on `"join" in job` says whether the job is joined."""
+    n = len(job["text_tokens"])
+    job = {k: v for k, v in job.items() if k != "join" or v is not None}
+    if job.get("seeds") is not None:
+        job["seeds"] = ops.request_seeds(job["seeds"], n, job.get("generator"))
+    if job.get("speed") is not None:
+        job["speed"] = ops.check_speed(job["speed"], n)
+    if "join" in job:
+        job["join"] = ops.check_join(job["join"], n)
+    return job
+
+
+class S3GenEngine:
+    """The S3Gen half of every engine -- flow matching (FlowEngine) and vocoder (HiFTEngine) of one checkpoint on one device -- and what is built on the two alone:
+    vocode, vocode_stream and the streams and kernel forms of the overlapped schedules.  On its own it is the engine of voice conversion (no T3);
+    ChatterboxEngine and TurboEngine put their T3 in front of it."""
+    t3 = None
+
+    def __init__(self, s3gen_sd, device="cuda", meanflow=False):
         self.dev = torch.device(device)
-        self.t3_weights = t3_weights  # None / "fp32" (parity path) or "bf16" (opt-in: decode weight images rounded to bf16)
-        self.t3 = self._build_t3(t3_sd, n_t3_layers)
         self.flow = FlowEngine(s3gen_sd, self.dev, meanflow=meanflow)
         self.hift = HiFTEngine(s3gen_sd, self.dev)
         self.last_timing = {}
-
-    def _build_t3(self, t3_sd, n_layers):
-        """CBX_PACK_CACHE=<dir>: keep the packed device layout of the T3 weights (4 GB: row-major + lane-ordered GEMV images) on disk,
-        keyed by a fingerprint of the checkpoint, and map it straight to the device on later starts (formats.py, SURVEY.md 8f N4)."""
-        cache = os.environ.get("CBX_PACK_CACHE")
-        if not cache:
-            return T3Engine(t3_sd, self.dev, n_layers=n_layers, weight_dtype=self.t3_weights)
-        from . import formats
-        fp = formats.fingerprint(t3_sd) + f"-L{n_layers}"
-        path = os.path.join(cache, f"t3_{fp}.cbxpack")
-        kind = formats.packed_kind("t3-llama-" + os.environ.get("CBX_T3_DECODE", "v2") + "-" + (self.t3_weights or os.environ.get("CBX_T3_WEIGHTS", "fp32"))
-                                   + f"-ht{int(bool(T3Engine._TUNE.get('half_tiles')))}")  # the half-tile images are part of the packed set
-        t = formats.load_packed(path, fp, kind)
-        if t is not None:
-            return T3Engine.from_packed(t, self.dev)
-        eng = T3Engine(t3_sd, self.dev, n_layers=n_layers, weight_dtype=self.t3_weights)
-        os.makedirs(cache, exist_ok=True)
-        formats.save_packed(eng.export_packed(), path, fp, kind)
-        return eng
 
     @ops.on_device
     @torch.inference_mode()
@@ -160,6 +174,71 @@ class ChatterboxEngine:
             return ops.wave_join(out, **join), mel
         return out, mel
 
+    def co_resident(self, on):
+        """Both stages on (or off) the kernel forms whose workgroups can share a CU with the other stage's (T3Engine.co_resident, FlowEngine.co_resident)."""
+        if self.t3 is not None and hasattr(self.t3, "co_resident"):
+            self.t3.co_resident(on)
+        self.flow.co_resident(on)
+
+    def _pipeline_streams(self, priorities=(-1, 0)):
+        """The T3 / flow streams of the overlapped schedules (created once; HIP priorities: measured, no effect either way)."""
+        if not hasattr(self, "_s_t3"):
+            pt3, pvoc = priorities
+            self._s_t3 = torch.cuda.Stream(device=self.dev, priority=pt3)
+            self._s_t3x = [self._s_t3] + [torch.cuda.Stream(device=self.dev, priority=pt3) for _ in range(2)]  # one per T3 state in flight
+            self._s_voc = torch.cuda.Stream(device=self.dev, priority=pvoc)
+
+    @torch.inference_mode()
+    def vocode_stream(self, speech_tokens, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=None, z=None, phase=None,
+                      noise=None, n_cfm_timesteps=10, drop_last_token=False, seeds=None, speed=None):
+        """vocode() in rounds: the schedule, the yields and the `window` of synthesize_stream with a list of B 1-D token tensors (valid ids; lengths may differ) in
+        place of T3 -- round r synthesises the first n_r tokens of every utterance (stream_token_schedule over the longest), utterance b is final once
+        n_r >= N_b.  No T3 is touched: this is the streaming form of voice conversion (the engine ChatterboxVC builds has none), where every token exists up
+        front and the input can be arbitrarily long -- give a `window`.  gen_ref: one voice with a whole-token prompt.  seeds: as vocode(seeds=); with a window the
+        noise is filled round by round (_stream_rounds).  speed: None or ONE number in [0.5, 2.0] -- the speaking rate of vocode(speed=), as synthesize_stream(speed=)
+        takes it: utterance b's pieces add up to the length vocode(speed=) returns."""
+        check_stream_window(window, fade, check_stream_speed(speed))
+        seeds = ops.check_seeds(seeds, len(speech_tokens))
+        pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        torch.cuda.set_device(pin)  # (a generator cannot hold a device guard across yields)
+        toks = [torch.as_tensor(t).view(-1).long().cpu() for t in speech_tokens]
+        assert toks and all(t.numel() > 0 for t in toks), "vocode_stream: every utterance needs at least one token"
+        lens = [int(t.numel()) for t in toks]
+        self.co_resident(False)
+        one_round, closed = _stream_rounds(self, len(toks), gen_ref, n_tokens=max(lens), round_tokens=lambda ts, fin: ts, lookahead=lookahead, fade=fade, z=z,
+                                           phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds, speed=speed)
+        for n_r in stream_token_schedule(max(lens), first_chunk, chunk, lookahead, chunk_growth):
+            yield one_round([t[:n_r] for t in toks], [n_r >= n for n in lens], n_r >= max(lens))
+            if all(closed):
+                return
+
+
+class ChatterboxEngine(S3GenEngine):
+    def __init__(self, t3_sd, s3gen_sd, device="cuda", n_t3_layers=None, meanflow=False, t3_weights=None):
+        self.dev = torch.device(device)
+        self.t3_weights = t3_weights  # None / "fp32" (parity path) or "bf16" (opt-in: decode weight images rounded to bf16)
+        self.t3 = self._build_t3(t3_sd, n_t3_layers)  # (T3 first, then flow and vocoder: the order in which the engines have always taken their device memory)
+        super().__init__(s3gen_sd, device, meanflow=meanflow)
+
+    def _build_t3(self, t3_sd, n_layers):
+        """CBX_PACK_CACHE=<dir>: keep the packed device layout of the T3 weights (4 GB: row-major + lane-ordered GEMV images) on disk,
+        keyed by a fingerprint of the checkpoint, and map it straight to the device on later starts (formats.py, SURVEY.md 8f N4)."""
+        cache = os.environ.get("CBX_PACK_CACHE")
+        if not cache:
+            return T3Engine(t3_sd, self.dev, n_layers=n_layers, weight_dtype=self.t3_weights)
+        from . import formats
+        fp = formats.fingerprint(t3_sd) + f"-L{n_layers}"
+        path = os.path.join(cache, f"t3_{fp}.cbxpack")
+        kind = formats.packed_kind("t3-llama-" + os.environ.get("CBX_T3_DECODE", "v2") + "-" + (self.t3_weights or os.environ.get("CBX_T3_WEIGHTS", "fp32"))
+                                   + f"-ht{int(bool(T3Engine._TUNE.get('half_tiles')))}")  # the half-tile images are part of the packed set
+        t = formats.load_packed(path, fp, kind)
+        if t is not None:
+            return T3Engine.from_packed(t, self.dev)
+        eng = T3Engine(t3_sd, self.dev, n_layers=n_layers, weight_dtype=self.t3_weights)
+        os.makedirs(cache, exist_ok=True)
+        formats.save_packed(eng.export_packed(), path, fp, kind)
+        return eng
+
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
@@ -182,30 +261,18 @@ class ChatterboxEngine:
                    ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
         torch.cuda.synchronize()
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
-        st = [drop_invalid_tokens(t) for t in toks]
-        st = [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
+        st = _valid_tokens(toks)
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
                               drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)))
         if join is not None:  # (the record's copy waits for the two launches behind the vocoder)
-            wavs = dict(ops.piece_on_host(wavs["out"], wavs["rec"], wavs["n"]), truncated=[not bool((t == STOP_SPEECH).any()) for t in toks])
+            wavs = dict(ops.piece_on_host(wavs["out"], wavs["rec"], wavs["n"]), truncated=self._truncated(toks))
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
-
-    def co_resident(self, on):
-        """Both stages on (or off) the kernel forms whose workgroups can share a CU with the other stage's (T3Engine.co_resident, FlowEngine.co_resident)."""
-        if self.t3 is not None and hasattr(self.t3, "co_resident"):
-            self.t3.co_resident(on)
-        self.flow.co_resident(on)
-
-    def _pipeline_streams(self, priorities=(-1, 0)):
-        """The T3 / flow streams of the overlapped schedules (created once; HIP priorities: measured, no effect either way)."""
-        if not hasattr(self, "_s_t3"):
-            pt3, pvoc = priorities
-            self._s_t3 = torch.cuda.Stream(device=self.dev, priority=pt3)
-            self._s_t3x = [self._s_t3] + [torch.cuda.Stream(device=self.dev, priority=pt3) for _ in range(2)]  # one per T3 state in flight
-            self._s_voc = torch.cuda.Stream(device=self.dev, priority=pvoc)
-
+    @staticmethod
+    def _truncated(toks):
+        """Per utterance of a joined piece: T3 spent its budget without sampling an end-of-speech token (generate keeps a sampled one in `toks`)."""
+        return [not bool((t == STOP_SPEECH).any()) for t in toks]
     @torch.inference_mode()
     def synthesize_pipelined(self, jobs, co_resident=True, host_threads=True, t3_in_flight=2, stream_priorities=(-1, 0), **kw):
         """Throughput mode for a stream of batches: T3 of batch k+1 runs on a high-priority HIP stream WHILE the flow
@@ -228,10 +295,7 @@ class ChatterboxEngine:
             (scripts/overlap_probe.py: the flow started 180 ms late).  The T3 enqueue runs on a second host thread (graph launches and the ctypes
             calls of the C stage seams release the GIL)."""
         import threading
-        jobs = [dict(job, seeds=ops.request_seeds(job["seeds"], len(job["text_tokens"]), job.get("generator"))) if job.get("seeds") is not None else job for job in jobs]
-        jobs = [dict(job, speed=ops.check_speed(job["speed"], len(job["text_tokens"]))) if job.get("speed") is not None else job for job in jobs]
-        jobs = [dict(job, join=ops.check_join(job["join"], len(job["text_tokens"]))) if job.get("join") is not None else {k: v for k, v in job.items() if k != "join"}
-                for job in jobs]  # (from here on `"join" in job` says whether the job is joined)
+        jobs = [_checked_job(job) for job in jobs]
         torch.cuda.set_device(self.dev)  # a generator cannot hold a device guard across yields: pin the device for the caller
         self._pipeline_streams(stream_priorities)
         t3_kw = {k: kw[k] for k in ("max_new_tokens", "temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight", "ban_eos",
@@ -255,26 +319,27 @@ class ChatterboxEngine:
             except BaseException as e:  # re-raised by the consumer thread
                 box["error"] = e
 
-        def voc_of(job, st):
-            with torch.cuda.stream(self._s_voc):
-                def voc():
-                    wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
-                                          speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10),
-                                          drop_last_token=kw.get("drop_last_token", True), sync=False, **join_kw(job))
-                    if "join" in job:
-                        return ops.piece_on_host(wavs["out"].cpu(), wavs["rec"].cpu(), wavs["n"])
-                    return [w.cpu() for w in wavs]  # D2H on the vocoder stream: returns when this batch's audio is on the host
-                return _range_checked(self, voc)
+        def vocode_job(job, st):
+            """flow + vocoder of a job on the CURRENT stream, not synchronised -> its device waveforms, or its joined piece on the device (a job without a join: vocode
+            is called exactly as before there was one)"""
+            wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
+                                  speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10), drop_last_token=kw.get("drop_last_token", True), sync=False,
+                                  **({"join": job["join"]} if "join" in job else {}))
+            return wavs
 
-        join_kw = lambda job: dict(join=job["join"]) if "join" in job else {}  # (a job without it: vocode is called exactly as before)
+        def to_host(job, wavs, pinned):
+            """The D2H copies of a job's audio on the CURRENT stream.  pinned=False: blocking copies, which return when the audio is on the host.  pinned=True: copies
+            into pinned buffers that are only enqueued -- read them behind an event.  A joined piece is ONE copy plus one of its small record (-> the arguments of
+            ops.piece_on_host), any other job one copy per utterance."""
+            copy = (lambda w: torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True)) if pinned else (lambda w: w.cpu())
+            if "join" in job:
+                return copy(wavs["out"]), copy(wavs["rec"]), wavs["n"]
+            return [copy(w) for w in wavs]
 
-        def tokens_of(toks):
-            st = [drop_invalid_tokens(t) for t in toks]
-            return [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
-
-        def truncated_of(job, host, toks):
-            """a joined piece also says which chunks spent T3's budget without EOS"""
-            return dict(host, truncated=[not bool((t == STOP_SPEECH).any()) for t in toks]) if "join" in job else host
+        def result_of(job, host, toks):
+            """What a job yields as `wavs` once `host` is readable: the waveforms, or the joined piece as its record lays it out, which also says which chunks spent
+            T3's budget without EOS"""
+            return dict(ops.piece_on_host(*host), truncated=self._truncated(toks)) if "join" in job else host
 
         if not host_threads:  # round 4's form: one host thread enqueues T3(k + 1), then flow + vocoder(k)
             try:
@@ -288,13 +353,14 @@ class ChatterboxEngine:
                             raise box["error"]
                     if pending is not None:
                         job, st, t0, raw = pending
-                        host = voc_of(job, st)
-                        yield truncated_of(job, host, raw), st, time.perf_counter() - t0
+                        with torch.cuda.stream(self._s_voc):  # (the copies block: this returns when the batch's audio is on the host)
+                            host = _range_checked(self, lambda: to_host(job, vocode_job(job, st), pinned=False))
+                        yield result_of(job, host, raw), st, time.perf_counter() - t0
                     pending = None
                     if "handle" in box:
                         with torch.cuda.stream(self._s_t3):
                             raw = self.t3.collect(box["handle"])
-                        pending = (jobs[k], tokens_of(raw), t_start, raw)
+                        pending = (jobs[k], _valid_tokens(raw), t_start, raw)
             finally:
                 torch.cuda.synchronize()
                 self.co_resident(False)
@@ -331,17 +397,11 @@ class ChatterboxEngine:
         # alternating flag words (ops.select_range_flag: a launch carries the word that was registered when it was ENQUEUED).
         import collections
         inflight = collections.deque()
-        voc_kw = dict(n_cfm_timesteps=kw.get("n_cfm_timesteps", 10), drop_last_token=kw.get("drop_last_token", True))
 
         def start_voc(job, st, which):
             ops.select_range_flag(self.dev, which)
             with torch.cuda.stream(self._s_voc):
-                wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), speed=job.get("speed"), sync=False, **voc_kw, **join_kw(job))
-                pinned = lambda w: torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True)
-                if "join" in job:  # one copy of the piece and one of its records; read in finish(), behind the event
-                    host = (pinned(wavs["out"]), pinned(wavs["rec"]), wavs["n"])
-                else:
-                    host = [pinned(w) for w in wavs]
+                host = to_host(job, vocode_job(job, st), pinned=True)  # read in finish(), behind the event
                 ev = torch.cuda.Event()
                 ev.record()
             return host, ev
@@ -349,20 +409,9 @@ class ChatterboxEngine:
         def finish(job, st, t0, host, ev, which, raw):
             ev.synchronize()
             if 16 in (self.flow.precision, self.hift.precision) and ops.range_flag_tripped(self.dev, which):
-                warnings.warn("an S3Gen operand exceeded the fp16 range: repeating flow matching + vocoder of this batch at bf16x6")
-                global RANGE_TRIPS
-                RANGE_TRIPS += 1
-                saved = self.flow.precision, self.hift.precision
-                self.flow.precision, self.hift.precision = (6 if p == 16 else p for p in saved)
-                try:
-                    with torch.cuda.stream(self._s_voc):
-                        wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"), speed=job.get("speed"), sync=False, **voc_kw, **join_kw(job))
-                        host = (wavs["out"].cpu(), wavs["rec"].cpu(), wavs["n"]) if "join" in job else [w.cpu() for w in wavs]  # (the repeat repeats the join)
-                finally:
-                    self.flow.precision, self.hift.precision = saved
-            if "join" in job:
-                host = truncated_of(job, ops.piece_on_host(*host), raw)
-            return host, st, time.perf_counter() - t0
+                with _repeat_at_bf16x6(self, " of this batch"), torch.cuda.stream(self._s_voc):
+                    host = to_host(job, vocode_job(job, st), pinned=False)  # (the repeat repeats the join)
+            return result_of(job, host, raw), st, time.perf_counter() - t0
 
         th = threading.Thread(target=worker, name="cbx-t3-enqueue", daemon=True)
         th.start()
@@ -376,7 +425,7 @@ class ChatterboxEngine:
                     self._s_voc.wait_event(ev)
                     toks = self.t3.collect(h)  # blocks this thread until T3(k) is done; T3(k + 1) is already enqueued behind it
                 slot_free[k % n_slots].release()
-                st = tokens_of(toks)
+                st = _valid_tokens(toks)
                 host, evv = start_voc(job, st, k % 2)
                 inflight.append((job, st, t0, host, evv, k % 2, toks))
                 yield finish(*inflight.popleft())
@@ -390,6 +439,46 @@ class ChatterboxEngine:
             ops.select_range_flag(self.dev, 0)
             torch.cuda.synchronize()
             self.co_resident(False)  # callers of vocode() / flow.inference() / synthesize_stream() get the fastest-alone forms back
+
+    @torch.inference_mode()
+    def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,
+                          temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False,
+                          ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2,
+                          window=None, seeds=None, speed=None):
+        """Chunked synthesis: first audio after `first_chunk` tokens instead of after the whole utterance.
+
+        The reference is non-streaming; of its vestigial hooks only HiFT's `cache_source` works (hifigan.py:470-472) -- `finalize=False`
+        (flow.py:170-171) raises a shape error there -- so the schedule is this build's own, with its own oracle
+        (tests/test_stream_gpu.py restates it on the CPU oracle):
+          * round r works on the first n_r tokens, n_0 = first_chunk + lookahead, n_r = n_{r-1} + chunk * chunk_growth^(r-1) (stream_token_schedule);
+          * every round runs encoder + CFM over the tokens so far with the same noise realisation, masking the last 2 * lookahead mel frames of
+            unfinished utterances (the encoder looks 3 tokens ahead), and HiFT with the previous round's source as `cache_source`
+            (phase-continuous excitation);
+          * new samples are emitted up to `fade` samples before the end of what the round could vocode; that tail is cross-faded (linear ramp)
+            with the next round's re-synthesis of the same samples.
+        The last round is a full synthesis: identical mel to synthesize() for the same noise.
+        overlap (round 6, the default): the two stages of the SAME utterances run side by side -- a second host thread keeps the T3 decode going on
+        its own high-priority stream (at most two rounds ahead of the vocoder; graph replays of the captured step), this thread waits for a round's
+        tokens on the flow stream and runs that round's flow + vocoder there, both stages on their co-resident kernel forms (synthesize_pipelined).
+        A round still sees exactly its n_r tokens, so every yielded sample is the one the serial form (overlap=False) yields.
+        window (None: the schedule above): the left context, in tokens, of a round of BOUNDED cost -- a round then synthesises the voice prompt, `window`
+        tokens in front of the first sample it has not emitted yet, the new chunk and the lookahead, whatever the round's number (_stream_rounds,
+        stream_window_schedule); at least ceil((8000 + fade) / 960) tokens, else ValueError.  The last round is then no longer the full synthesis.
+        seeds (None, an int, or B ints in [0, 2^64)): every draw that is not injected comes from its utterance's seed (synthesize(seeds=)); with a window, z and
+        noise are then filled round by round and never for the whole budget (_stream_rounds).
+        speed (None, or ONE number in [0.5, 2.0] for all utterances; None / 1.0: exactly the stream without it): the speaking rate of synthesize(speed=).  Every round
+        stretches its mel (the window's, with a window) by one ops.mel_time_scale_window launch in front of the vocoder, and samples are counted in the stretched
+        signal (_stream_rounds): utterance b's pieces add up to the length synthesize(speed=) returns, and with window=None the last round vocodes the very mel the
+        one-shot call stretches.  An injected `noise` covers 480 * ops.scaled_len(2 n, speed) samples; a window must satisfy check_stream_window(window, fade, speed).
+        Yields dicts {wavs: [B CPU tensors of NEW samples], final: [B bools], n_tokens: [B], tokens: [B CPU tensors: the speech tokens the round vocoded]};
+        concatenating an utterance's pieces gives its waveform."""
+        t3_kw = dict(max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
+                     cfg_weight=cfg_weight, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from)
+
+        yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_new_tokens, t3_kw=t3_kw, round_tokens=lambda toks, fin: _valid_tokens(toks), n_extra=0,
+                                      first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
+                                      noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
+                                      run_ahead=run_ahead, window=window, seeds=seeds, speed=speed)
 
 
 def _stream_plan(n_tokens, done, exhausted, lookahead):
@@ -659,16 +748,22 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
                 return self.hift.inference(mel, phase=phase, noise=noise_samples(o, HALF * mel.shape[1]), lens=lens, fade=j0 == 0,
                                            cache_source=cache_src, cum_in=cum_in)
             wav, src = _range_checked(self, run)
-            if W is None:
+
+            def span(b):
+                """(end, avail) of open row b, in absolute samples of its utterance: `avail` of them exist after this round (a final row: no more than the one-shot
+                call returns), [emitted, end) leave now, and [end, avail) -- at most `fade` samples, none of a final row -- is the tail the next round cross-fades"""
+                avail = o + HALF * frames[b]
+                if fin[b]:
+                    keep = max(1, ns[b] - 1) if drop_last_token else ns[b]
+                    avail = min(avail, keep * SAMPLES_PER_TOKEN if rate is None else HALF * ops.scaled_len(2 * keep, rate))
+                return (avail if fin[b] else max(emitted[b], avail - fade)), avail
+
+            if W is None:  # (o == 0: every round starts at sample 0)
                 cache[0] = src[:, : HALF * min(frames)].clone() if min(frames) > 0 else None
                 for b in range(B):
                     if closed[b]:
                         continue
-                    avail = HALF * frames[b]
-                    if fin[b]:
-                        keep = max(1, ns[b] - 1) if drop_last_token else ns[b]
-                        avail = min(avail, keep * SAMPLES_PER_TOKEN if rate is None else HALF * ops.scaled_len(2 * keep, rate))
-                    end = avail if fin[b] else max(emitted[b], avail - fade)
+                    end, avail = span(b)
                     new = wav[b, emitted[b]: end].clone()
                     if tails[b] is not None and new.numel() > 0:
                         k = min(tails[b].numel(), new.numel())
@@ -686,11 +781,7 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
                     if closed[b]:
                         meta[:3, b] = emitted[b]
                         continue
-                    avail = o + HALF * frames[b]
-                    if fin[b]:
-                        keep = max(1, ns[b] - 1) if drop_last_token else ns[b]
-                        avail = min(avail, keep * SAMPLES_PER_TOKEN if rate is None else HALF * ops.scaled_len(2 * keep, rate))
-                    end = avail if fin[b] else max(emitted[b], avail - fade)
+                    end, avail = span(b)
                     meta[:, b] = torch.tensor([emitted[b], end, avail, win["tail_len"][b]], dtype=torch.int32)
                     news[b], nxt[b] = max(0, end - emitted[b]), 0 if fin[b] else max(0, min(avail, end + fade) - end)
                     emitted[b] = end
@@ -801,95 +892,17 @@ def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw,
         self.co_resident(False)
 
 
-def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,
-                      temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False,
-                      ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2,
-                      window=None, seeds=None, speed=None):
-    """Chunked synthesis: first audio after `first_chunk` tokens instead of after the whole utterance.
-
-    The reference is non-streaming; of its vestigial hooks only HiFT's `cache_source` works (hifigan.py:470-472) -- `finalize=False`
-    (flow.py:170-171) raises a shape error there -- so the schedule is this build's own, with its own oracle
-    (tests/test_stream_gpu.py restates it on the CPU oracle):
-      * round r works on the first n_r tokens, n_0 = first_chunk + lookahead, n_r = n_{r-1} + chunk * chunk_growth^(r-1) (stream_token_schedule);
-      * every round runs encoder + CFM over the tokens so far with the same noise realisation, masking the last 2 * lookahead mel frames of
-        unfinished utterances (the encoder looks 3 tokens ahead), and HiFT with the previous round's source as `cache_source`
-        (phase-continuous excitation);
-      * new samples are emitted up to `fade` samples before the end of what the round could vocode; that tail is cross-faded (linear ramp)
-        with the next round's re-synthesis of the same samples.
-    The last round is a full synthesis: identical mel to synthesize() for the same noise.
-    overlap (round 6, the default): the two stages of the SAME utterances run side by side -- a second host thread keeps the T3 decode going on
-    its own high-priority stream (at most two rounds ahead of the vocoder; graph replays of the captured step), this thread waits for a round's
-    tokens on the flow stream and runs that round's flow + vocoder there, both stages on their co-resident kernel forms (synthesize_pipelined).
-    A round still sees exactly its n_r tokens, so every yielded sample is the one the serial form (overlap=False) yields.
-    window (None: the schedule above): the left context, in tokens, of a round of BOUNDED cost -- a round then synthesises the voice prompt, `window`
-    tokens in front of the first sample it has not emitted yet, the new chunk and the lookahead, whatever the round's number (_stream_rounds,
-    stream_window_schedule); at least ceil((8000 + fade) / 960) tokens, else ValueError.  The last round is then no longer the full synthesis.
-    seeds (None, an int, or B ints in [0, 2^64)): every draw that is not injected comes from its utterance's seed (synthesize(seeds=)); with a window, z and
-    noise are then filled round by round and never for the whole budget (_stream_rounds).
-    speed (None, or ONE number in [0.5, 2.0] for all utterances; None / 1.0: exactly the stream without it): the speaking rate of synthesize(speed=).  Every round
-    stretches its mel (the window's, with a window) by one ops.mel_time_scale_window launch in front of the vocoder, and samples are counted in the stretched
-    signal (_stream_rounds): utterance b's pieces add up to the length synthesize(speed=) returns, and with window=None the last round vocodes the very mel the
-    one-shot call stretches.  An injected `noise` covers 480 * ops.scaled_len(2 n, speed) samples; a window must satisfy check_stream_window(window, fade, speed).
-    Yields dicts {wavs: [B CPU tensors of NEW samples], final: [B bools], n_tokens: [B], tokens: [B CPU tensors: the speech tokens the round vocoded]};
-    concatenating an utterance's pieces gives its waveform."""
-    t3_kw = dict(max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
-                 cfg_weight=cfg_weight, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from)
-
-    def round_tokens(toks, fin):
-        st = [drop_invalid_tokens(t) for t in toks]
-        return [t if t.numel() > 0 else torch.zeros(1, dtype=torch.long) for t in st]
-
-    yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_new_tokens, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=0,
-                                  first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
-                                  noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                  run_ahead=run_ahead, window=window, seeds=seeds, speed=speed)
-
-
-def vocode_stream(self, speech_tokens, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=None, z=None, phase=None,
-                  noise=None, n_cfm_timesteps=10, drop_last_token=False, seeds=None, speed=None):
-    """vocode() in rounds: the schedule, the yields and the `window` of synthesize_stream with a list of B 1-D token tensors (valid ids; lengths may differ) in
-    place of T3 -- round r synthesises the first n_r tokens of every utterance (stream_token_schedule over the longest), utterance b is final once
-    n_r >= N_b.  No T3 is touched: this is the streaming form of voice conversion (the engine ChatterboxVC builds has none), where every token exists up
-    front and the input can be arbitrarily long -- give a `window`.  gen_ref: one voice with a whole-token prompt.  seeds: as vocode(seeds=); with a window the
-    noise is filled round by round (_stream_rounds).  speed: None or ONE number in [0.5, 2.0] -- the speaking rate of vocode(speed=), as synthesize_stream(speed=)
-    takes it: utterance b's pieces add up to the length vocode(speed=) returns."""
-    check_stream_window(window, fade, check_stream_speed(speed))
-    seeds = ops.check_seeds(seeds, len(speech_tokens))
-    pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-    torch.cuda.set_device(pin)  # (a generator cannot hold a device guard across yields)
-    toks = [torch.as_tensor(t).view(-1).long().cpu() for t in speech_tokens]
-    assert toks and all(t.numel() > 0 for t in toks), "vocode_stream: every utterance needs at least one token"
-    lens = [int(t.numel()) for t in toks]
-    self.co_resident(False)
-    one_round, closed = _stream_rounds(self, len(toks), gen_ref, n_tokens=max(lens), round_tokens=lambda ts, fin: ts, lookahead=lookahead, fade=fade, z=z,
-                                       phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds, speed=speed)
-    for n_r in stream_token_schedule(max(lens), first_chunk, chunk, lookahead, chunk_growth):
-        yield one_round([t[:n_r] for t in toks], [n_r >= n for n in lens], n_r >= max(lens))
-        if all(closed):
-            return
-
-
 S3GEN_SIL = 4299  # reference models/s3gen/const.py:2
 
 
-ChatterboxEngine.synthesize_stream = torch.inference_mode()(synthesize_stream)
-ChatterboxEngine.vocode_stream = torch.inference_mode()(vocode_stream)
-
-
-class TurboEngine:
+class TurboEngine(S3GenEngine):
     """ChatterboxTurboTTS hot path (reference tts_turbo.py:298-317): GPT-2 T3 (no CFG) -> ids < 6561 + 3 silence tokens ->
     2-step meanflow S3Gen (no CFG) -> HiFT."""
 
     def __init__(self, t3_sd, s3gen_sd, device="cuda", n_t3_layers=None):
         from .t3_turbo import T3TurboEngine
-        self.dev = torch.device(device)
-        self.t3 = T3TurboEngine(t3_sd, self.dev, n_layers=n_t3_layers)
-        self.flow = FlowEngine(s3gen_sd, self.dev, meanflow=True)
-        self.hift = HiFTEngine(s3gen_sd, self.dev)
-        self.last_timing = {}
-
-    vocode = ChatterboxEngine.vocode
-    vocode_stream = ChatterboxEngine.vocode_stream
+        self.t3 = T3TurboEngine(t3_sd, torch.device(device), n_layers=n_t3_layers)  # (T3 first, as in ChatterboxEngine)
+        super().__init__(s3gen_sd, device, meanflow=True)
 
     @ops.on_device
     @torch.inference_mode()
@@ -911,13 +924,16 @@ class TurboEngine:
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed,
                               **({} if join is None else dict(join=join)))
-        if join is not None:  # (generate strips a sampled EOS: a chunk that still has max_gen_len + 1 tokens never sampled one)
-            wavs = dict(ops.piece_on_host(wavs["out"], wavs["rec"], wavs["n"]), truncated=[int(t.numel()) > max_gen_len for t in toks])
+        if join is not None:
+            wavs = dict(ops.piece_on_host(wavs["out"], wavs["rec"], wavs["n"]), truncated=self._truncated(toks, max_gen_len))
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
-    co_resident = ChatterboxEngine.co_resident
-    _pipeline_streams = ChatterboxEngine._pipeline_streams
+    @staticmethod
+    def _truncated(toks, max_gen_len):
+        """Per utterance of a joined piece: T3 spent its budget without EOS (generate strips a sampled EOS: a chunk that still has max_gen_len + 1 tokens never
+        sampled one)."""
+        return [int(t.numel()) > max_gen_len for t in toks]
 
     @torch.inference_mode()
     def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_gen_len=1000,
