@@ -10,6 +10,7 @@ the device through chatterbox_amd/frontend.py (S3 tokenizer, CAMPPlus, voice enc
 them.  The watermarker (third-party `perth`) is applied only if importable -- parity is defined on the pre-watermark waveform;
 Turbo's `norm_loudness` needs `pyloudnorm` and is skipped with a warning when that is missing (as the reference does on error).
 """
+import contextlib
 import os
 from dataclasses import dataclass
 from pathlib import Path
@@ -358,12 +359,55 @@ class _Finish:
     """The epilogue of every public method that returns audio."""
     sr = S3GEN_SR
 
-    def _finish(self, wav):
-        """A device waveform as the reference returns it: CPU float32 (1, n), watermarked if a watermarker is loaded."""
+    def _finish(self, wav, fmt=None, converted=True):
+        """A device waveform as the reference returns it: CPU float32 (1, n), watermarked if a watermarker is loaded.
+        fmt (ops.check_format's dict; None: exactly the above): the (1, n) CPU tensor at fmt's rate in fmt's encoding.  Without a watermarker the engine was given the
+        format and `wav` is the converted audio already (converted=True): one copy to the host.  With one -- or when the caller kept the format from the engine
+        (converted=False: generate_long) -- `wav` is 24 kHz fp32: it is watermarked on the host as ever, then converted on the device (_to_format)."""
+        if fmt is not None and converted and self.watermarker is None:
+            return wav.detach().cpu().unsqueeze(0)
         wav = wav.detach().float().cpu()
         if self.watermarker is not None:
             wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
-        return wav.unsqueeze(0)
+        return (wav if fmt is None else self._to_format(wav, fmt)).unsqueeze(0)
+
+    def _device_scope(self):
+        dev = torch.device(self.engine.dev)
+        return dev, (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext())
+
+    def _to_format(self, wav, fmt):
+        """A 24 kHz fp32 waveform on the host -> the device, ONE ops.wave_format launch, back to the host (1-D)"""
+        dev, scope = self._device_scope()
+        with scope:
+            return ops.wave_format([wav.to(dev)], fmt)[0].cpu()
+
+    def _engine_format(self, fmt):
+        """The engines' format= keyword: {} for the default format (the engine call is then exactly the one without it) and when a watermarker is loaded (it works
+        on the 24 kHz fp32 waveform: the conversion then follows it, in _finish)."""
+        return {} if fmt is None or self.watermarker is not None else dict(format=fmt)
+
+    def _stream_pieces(self, rounds, fmt):
+        """The pieces of generate_stream from an engine stream's rounds: (1, n) CPU tensors, empty ones left out.  With a format and a watermarker every piece is
+        watermarked as 24 kHz fp32 and then goes through an ops.WaveFormatStream held here, so the pieces add up to the conversion of the whole."""
+        conv = None
+        for r in rounds:
+            w = r["wavs"][0]
+            if fmt is None or self.watermarker is None:
+                if w.numel():
+                    yield self._finish(w, fmt)
+                continue
+            final = bool(r["final"][0])
+            if not (w.numel() or final):
+                continue
+            dev, scope = self._device_scope()
+            w = w.detach().float().cpu()
+            if w.numel():
+                w = torch.from_numpy(self.watermarker.apply_watermark(w.numpy(), sample_rate=self.sr))
+            with scope:
+                conv = conv or ops.WaveFormatStream(1, fmt, dev)
+                out = conv.push([w.to(dev)], [final])[0].cpu()
+            if out.numel():
+                yield out.unsqueeze(0)
 
 
 class _TTS(_Finish):
@@ -410,15 +454,14 @@ class _TTS(_Finish):
         return out
 
     # ------------------------------------------------------------------------------------------------------------ one utterance
-    def _generate(self, text_ids, **kw):
+    def _generate(self, text_ids, fmt=None, **kw):
         """generate() behind its argument handling: tokenizer ids -> the finished waveform.  kw: sampling arguments, and _synth_kw's if they are to differ."""
-        wavs, _ = self.engine.synthesize([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw))
-        return self._finish(wavs[0])
+        wavs, _ = self.engine.synthesize([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw), **self._engine_format(fmt))
+        return self._finish(wavs[0], fmt)
 
-    def _generate_stream(self, text_ids, stream_kw, **samp):
-        for r in self.engine.synthesize_stream([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **self._synth_kw(), **stream_kw, **samp):
-            if r["wavs"][0].numel():
-                yield self._finish(r["wavs"][0])
+    def _generate_stream(self, text_ids, stream_kw, fmt=None, **samp):
+        return self._stream_pieces(self.engine.synthesize_stream([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **self._synth_kw(), **stream_kw,
+                                                                 **samp, **self._engine_format(fmt)), fmt)
 
     # ------------------------------------------------------------------------------------------------------------ device batches
     def _run_jobs(self, jobs, synth_kw):
@@ -433,7 +476,7 @@ class _TTS(_Finish):
             args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
             yield self.engine.synthesize(*args, **synth_kw, **job)
 
-    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, **analyse_kw):
+    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, **analyse_kw):
         """generate_batch behind its signature: validation of every per-request argument (seeds and speed first), then the voices, then tokenisation, then the
         device work.  samp: the sampling arguments the engine takes; unsampled: those it does not -- exaggeration, which picks the voice's cond dict, and what the
         backbone ignores."""
@@ -448,15 +491,16 @@ class _TTS(_Finish):
         self._warn_ignored(*(v for vals in unsampled.values() for v in vals))
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, unsampled["exaggeration"], **analyse_kw)
         tokens = [self._engine_tokens(self._text_ids(t, lid)) for t, lid in zip(texts, langs)]
-        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed)
+        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt)
 
     def _languages(self, language_ids, B):
         return [None] * B
 
-    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None):
+    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None):
         """Sub-batches of at most max_batch requests in order of text length (_run_jobs: one runs the serial schedule, several the throughput schedule).  Returns the
         finished waveforms in the caller's order.  seeds (B ints or None) travel with their requests: a request's draws do not depend on the sub-batch or the row
-        it lands in.  speed (B floats or None) travels the same way."""
+        it lands in.  speed (B floats or None) travels the same way.  fmt (one format for the call, or None): every job carries it as `format` unless a
+        watermarker is loaded (_engine_format)."""
         dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
         plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
         jobs = []
@@ -470,14 +514,15 @@ class _TTS(_Finish):
                 job["seeds"] = _pick(seeds, idx)
             if speed is not None:
                 job["speed"] = _pick(speed, idx)
+            job.update(self._engine_format(fmt))
             jobs.append(job)
         out = [None] * len(tokens)
         for idx, (wavs, _) in zip(plan, self._run_jobs(jobs, self._synth_kw(batch=True))):
             for i, w in zip(idx, wavs):
-                out[i] = self._finish(w)
+                out[i] = self._finish(w, fmt)
         return out
 
-    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, **prepare_kw):
+    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, fmt=None, **prepare_kw):
         """generate_long behind its signature and _long_args: the remaining checks, the voice as generate() prepares it, then _run_long.  samp / unsampled: as
         _generate_batch takes them, one number each."""
         if not isinstance(text, str):
@@ -485,11 +530,13 @@ class _TTS(_Finish):
         _long_numbers(**unsampled, **samp)
         self._use_voice(audio_prompt_path, unsampled["exaggeration"], **prepare_kw)
         self._warn_ignored(*unsampled.values())
-        return self._run_long(text, a, lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id)), samp, return_segments)
+        return self._run_long(text, a, lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id)), samp, return_segments, fmt)
 
-    def _run_long(self, text, a, tokenize, samp, return_segments):
+    def _run_long(self, text, a, tokenize, samp, return_segments, fmt=None):
         """generate_long behind its validation: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), run the jobs of long_plan (_run_jobs), concatenate
-        the joined pieces on the host, watermark the whole once."""
+        the joined pieces on the host, watermark the whole once.  fmt: the engine jobs do not carry it -- the concatenated 24 kHz waveform is converted once, in
+        _finish (host -> device -> host; no converter state travels through the joined pieces on the device), and the segments' start / stop become output samples,
+        ceil(s U / D), so the last stop is the length; src_start / src_stop stay 24 kHz samples."""
         chunks = split_text(text, a["max_chars"])
         tokens = [tokenize(c) for c, _ in chunks]
         plan = long_plan(chunks, int(self.max_batch or self.engine.t3.MAX_BATCH), a)
@@ -509,7 +556,10 @@ class _TTS(_Finish):
             import logging
             logging.getLogger(__name__).warning("generate_long: chunk(s) %s of %d reached the speech-token budget without an end-of-speech token and are cut "
                                                 "off; use a smaller max_chars (now %d)", cut, len(segments), a["max_chars"])
-        wav = self._finish(torch.cat(pieces))
+        wav = self._finish(torch.cat(pieces), fmt, converted=False)
+        if fmt is not None:
+            for seg in segments:
+                seg.update(start=ops.formatted_len(seg["start"], fmt["sample_rate"]), stop=ops.formatted_len(seg["stop"], fmt["sample_rate"]))
         return (wav, segments) if return_segments else wav
 
 
@@ -574,20 +624,25 @@ class ChatterboxTTS(_LlamaTTS):
         return self.tokenizer.text_to_tokens(punc_norm_en(text))
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
-                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0):
+                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
         alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
         speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
         the vocoder (ChatterboxEngine.vocode(speed=)).  With a seed the tokens do not depend on it; the result has max(1, floor(K / speed)) * 480 samples where
         speed 1.0 gives K * 480.
-        This is the statement of `seed` and `speed` for generate() of every class of this module; the others say only what differs."""
+        sample_rate (None / 24000, or 8000, 16000, 22050, 32000, 44100, 48000) and encoding (None / "f32", "s16", "mulaw", "alaw"): the delivery format.  The
+        result is then the (1, n) CPU tensor of float32, int16 (PCM16) or uint8 (G.711) at that rate, n = ceil(n24 U / D) -- resampled as
+        scipy.signal.resample_poly does (frontend.resample's definition; its default filter, no dither) and encoded by ONE launch on the device, ahead of the only
+        copy to the host (ops.wave_format); with a watermarker loaded, after the watermark.  `.sr` stays 24000.  The defaults are the call without the arguments.
+        This is the statement of `seed`, `speed`, `sample_rate` and `encoding` for every method of every class of this module; the others say only what differs."""
+        fmt = ops.check_format(sample_rate, encoding)
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate(self._text_ids(text), temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
+        return self._generate(self._text_ids(text), fmt, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
                               top_p=top_p, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False):
+                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None):
         """generate() for a text of ANY length: the reference stops at 1000 speech tokens (40 s) and cuts a longer text off.  The text is split into chunks of at
         most max_chars characters at paragraph, sentence and clause boundaries (text.split_text), the chunks are synthesised in text order as device batches
         (one: synthesize; several: the throughput schedule where the engine has it), and each batch's waveforms are trimmed of their leading / trailing silence and
@@ -600,13 +655,16 @@ class ChatterboxTTS(_LlamaTTS):
         return_segments=True: also a list of dict(text, start, stop, src_start, src_stop, tokens, truncated) per chunk -- [start, stop) are its samples in the
         result (usable for captions), [src_start, src_stop) the part of its own waveform that was kept.  A chunk whose T3 spent the token budget without an
         end-of-speech token is `truncated`; one warning names them.  Every argument is checked before anything is launched; self.conds is written only as
-        generate() writes it (audio_prompt_path)."""
+        generate() writes it (audio_prompt_path).
+        sample_rate, encoding: generate()'s; the whole waveform is converted once, after the watermark, and the segments' [start, stop) are then samples of the
+        converted result (ceil(s U / D)) while [src_start, src_stop) stay 24 kHz samples."""
+        fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration))
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
-                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0):
+                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
         request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
         neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
@@ -616,22 +674,25 @@ class ChatterboxTTS(_LlamaTTS):
         alone -- not on the other requests, its row, the sub-batch split or the order of calls -- and are those of generate(seed=seeds[b]).  Its tokens and audio
         then agree with that call's as far as batched and single arithmetic agree: the kernels pick their forms by row count, so this is not bit equality.
         speed (a number for every request, or a sequence of B numbers in [0.5, 2.0]; None entries are 1.0): request b's speaking rate, generate(speed=)'s; it
-        travels with its request through the sub-batches like its seed.
+        travels with its request through the sub-batches like its seed.  sample_rate, encoding: generate()'s, ONE format for the call (checked first).
         This is the contract of generate_batch of every class of this module; the others say only what differs."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration))
+        return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
+                                    ops.check_format(sample_rate, encoding))
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
-                        cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, speed=1.0):
+                        cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, sample_rate=None, encoding=None, speed=1.0):
         """generate() in pieces (the engine's synthesize_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after
         `first_chunk` tokens; concatenated along dim 1 they give the utterance.  If a watermarker is loaded it is applied to each piece.
         window (None: every round re-synthesises the utterance so far): tokens of left context of a round of bounded cost (synthesize_stream).
         seed: generate()'s.  speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate -- the pieces add up to the length generate(speed=) returns;
-        checked, with the window it asks for (engine.check_stream_window), when this is called.
+        checked, with the window it asks for (engine.check_stream_window), when this is called.  sample_rate, encoding: generate()'s -- every round's new samples
+        are converted ahead of the round's copy to the host (one ops.WaveFormatStream for the stream); the pieces add up to the conversion of the whole utterance.
         This is the contract of generate_stream of the three TTS classes; the others say only what differs."""
+        fmt = ops.check_format(sample_rate, encoding)
         seed_kw = _seed_kw(seed)
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature,
+        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), fmt, temperature=temperature,
                                      cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
 
 
@@ -679,39 +740,43 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
         return [_language(lid, f" (request {k})") for k, lid in enumerate(langs)]
 
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0):
+                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None):
         """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
-        token's 40 ms are dropped as the reference does.  seed, speed: as there."""
+        token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding: as there."""
+        fmt = ops.check_format(sample_rate, encoding)
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate(self._text_ids(text, lid), temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
+        return self._generate(self._text_ids(text, lid), fmt, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
                               top_p=top_p, **seed_kw)
 
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False):
+                      return_segments=False, sample_rate=None, encoding=None):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
+        fmt = ops.check_format(sample_rate, encoding)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration))
+        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0):
+                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
         speed, before the sampling arguments)."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration))
+        return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
+                                    ops.check_format(sample_rate, encoding))
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
-                        seed=None, speed=1.0):
+                        seed=None, sample_rate=None, encoding=None, speed=1.0):
         """ChatterboxTTS.generate_stream with generate()'s language_id."""
+        fmt = ops.check_format(sample_rate, encoding)
         seed_kw = _seed_kw(seed)
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate_stream(self._text_ids(text, lid), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed),
+        return self._generate_stream(self._text_ids(text, lid), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), fmt,
                                      temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
 
 
@@ -786,38 +851,42 @@ class ChatterboxTurboTTS(_TTS):
         return dict(max_gen_len=1000) if batch else {}
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
-                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0):
-        """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed: as ChatterboxTTS.generate."""
+                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None):
+        """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed, sample_rate, encoding: as
+        ChatterboxTTS.generate."""
+        fmt = ops.check_format(sample_rate, encoding)
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
         self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
         self._warn_ignored(cfg_weight, exaggeration, min_p)
-        return self._generate(self._text_ids(text), temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
+        return self._generate(self._text_ids(text), fmt, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                       top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False):
+                      return_segments=False, sample_rate=None, encoding=None):
         """ChatterboxTTS.generate_long on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other)."""
+        fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
-        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), fmt,
                                    norm_loudness=norm_loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
-                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0):
+                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None):
         """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
         of B).  CFG, min_p and exaggeration are ignored with generate()'s warning.  Sub-batches run one after the other."""
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
-                                    norm_loudness=norm_loudness)
+                                    ops.check_format(sample_rate, encoding), norm_loudness=norm_loudness)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
                         temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
-                        seed=None, speed=1.0):
+                        seed=None, sample_rate=None, encoding=None, speed=1.0):
         """ChatterboxTTS.generate_stream on the Turbo / Nano backbone (TurboEngine.synthesize_stream; generate()'s sampling arguments)."""
+        fmt = ops.check_format(sample_rate, encoding)
         seed_kw = _seed_kw(seed)
         self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
         self._warn_ignored(cfg_weight, exaggeration, min_p)
-        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), temperature=temperature,
+        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), fmt, temperature=temperature,
                                      top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
 
 
@@ -887,23 +956,26 @@ class ChatterboxVC(_Finish):
             s3_tokens = self._tokens_of(audio)
         return torch.as_tensor(s3_tokens).view(-1).long().cpu()
 
-    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0):
+    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None):
         """reference vc.py:83-104.  audio: a WAV path or a (waveform, sample_rate) pair.  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
-        are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's."""
+        are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding: as there."""
+        fmt = ops.check_format(sample_rate, encoding)
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
-        wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **seed_kw)
-        return self._finish(wavs[0])
+        wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **seed_kw, **self._engine_format(fmt))
+        return self._finish(wavs[0], fmt)
 
-    def generate_stream(self, audio=None, target_voice_path=None, s3_tokens=None, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=200, seed=None, speed=1.0):
+    def generate_stream(self, audio=None, target_voice_path=None, s3_tokens=None, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=200, seed=None, sample_rate=None, encoding=None, speed=1.0):
         """generate() in pieces (the engine's vocode_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk` tokens of
         the source; concatenated along dim 1 they give the conversion.  A round synthesises the target voice's prompt, `window` tokens of left context, the new
         chunk and the lookahead, so its cost does not grow with the length of the source (window=None: every round re-synthesises everything so far); the
         default 200 + chunk 50 is the 250-token round the flow is tuned at.  Arguments are checked and the source is tokenised when this is CALLED, as generate
         does; self.ref_dict is written only when target_voice_path is given.  The target voice's prompt must be a whole number of tokens (2 mel frames per
         prompt token).  If a watermarker is loaded it is applied to each piece.  seed: generate()'s; the noise of a windowed stream is then filled round by round.
-        speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate at the bounded cost of a windowed round; the pieces add up to generate(speed=)'s length."""
+        speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate at the bounded cost of a windowed round; the pieces add up to generate(speed=)'s length.
+        sample_rate, encoding: as ChatterboxTTS.generate_stream."""
         from .engine import check_stream_window
-        seed_kw = dict(_seed_kw(seed), **_stream_speed_kw(speed))
+        fmt = ops.check_format(sample_rate, encoding)
+        seed_kw = dict(_seed_kw(seed), **_stream_speed_kw(speed), **self._engine_format(fmt))
         for name, v, lo in (("first_chunk", first_chunk, 1), ("chunk", chunk, 1), ("lookahead", lookahead, 0), ("fade", fade, 0)):
             if isinstance(v, bool) or not isinstance(v, int) or v < lo:
                 raise ValueError(f"{name}={v!r}: expected an int >= {lo}")
@@ -917,21 +989,18 @@ class ChatterboxVC(_Finish):
             raise ValueError("the source has no S3 tokens")
         ref = self.ref_dict  # (the voice of THIS call: a later set_target_voice does not reach into a running stream)
 
-        def pieces():
-            for r in self.engine.vocode_stream([toks], ref, first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade,
-                                               window=window, **seed_kw):
-                if r["wavs"][0].numel():
-                    yield self._finish(r["wavs"][0])
-        return pieces()
+        return self._stream_pieces(self.engine.vocode_stream([toks], ref, first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead,
+                                                             fade=fade, window=window, **seed_kw), fmt)
 
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 
-    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0):
+    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None):
         """generate() for B conversions in one call: `audios` (WAV paths or (waveform, sample_rate) pairs) or `s3_tokens` (B id sequences); target voice per
         request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
         self.ref_dict.  Returns B CPU float32 tensors (1, n_b) at `.sr` in the caller's order; more than MAX_BATCH requests run as sub-batches in order of length.
         Never overwrites self.ref_dict.  seeds, speed: per request as ChatterboxTTS.generate_batch states them -- request b's noise is that of
-        generate(seed=seeds[b]), its speaking rate generate(speed=speed[b])'s."""
+        generate(seed=seeds[b]), its speaking rate generate(speed=speed[b])'s; sample_rate, encoding: one format for the call."""
+        fmt = ops.check_format(sample_rate, encoding)
         src = s3_tokens if s3_tokens is not None else audios
         assert src is not None, "give audios or s3_tokens"
         src = [src] if (isinstance(src, _PATH) or (torch.is_tensor(src) and src.dim() <= 1)) else list(src)
@@ -954,7 +1023,7 @@ class ChatterboxVC(_Finish):
         out = [None] * B
         for idx in batch_plan([int(t.numel()) for t in toks], int(self.MAX_BATCH)):
             wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **({} if seeds is None else dict(seeds=_pick(seeds, idx))),
-                                         **({} if speed is None else dict(speed=_pick(speed, idx))))
+                                         **({} if speed is None else dict(speed=_pick(speed, idx))), **self._engine_format(fmt))
             for i, w in zip(idx, wavs):
-                out[i] = self._finish(w)
+                out[i] = self._finish(w, fmt)
         return out

@@ -71,9 +71,14 @@ def _valid_tokens(toks):
 
 def _checked_job(job):
     """A job of synthesize_pipelined with its optional keys checked as synthesize checks its arguments: seeds (ops.request_seeds; not together with the job's
-    generator), speed (ops.check_speed), join (ops.check_join).  A join of None is dropped: from here on `"join" in job` says whether the job is joined."""
+    generator), speed (ops.check_speed), join (ops.check_join), format (ops.check_format_arg).  A join of None is dropped: from here on `"join" in job` says whether
+    the job is joined; likewise a format that is None or the default (24 kHz fp32)."""
     n = len(job["text_tokens"])
-    job = {k: v for k, v in job.items() if k != "join" or v is not None}
+    job = {k: v for k, v in job.items() if k not in ("join", "format") or v is not None}
+    if "format" in job:
+        job["format"] = ops.check_format_arg(job["format"])
+        if job["format"] is None:
+            del job["format"]
     if job.get("seeds") is not None:
         job["seeds"] = ops.request_seeds(job["seeds"], n, job.get("generator"))
     if job.get("speed") is not None:
@@ -98,7 +103,7 @@ class S3GenEngine:
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None, seeds=None, speed=None, join=None):
+               generator=None, seeds=None, speed=None, join=None, format=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
@@ -115,11 +120,17 @@ class S3GenEngine:
         long-form synthesis -- the B utterances are consecutive chunks of one text, and two launches behind the vocoder, on the stream that owns the waveforms,
         trim each of its silence (cbx_wave_edges_f32; skipped with trim_db=None) and lay them out with their gaps and fades as ONE piece (cbx_wave_join_f32).  The
         call then returns (piece, mel), piece = ops.wave_join's dict on the device: the `out` buffer, its layout record and the edge table.  Nothing is synchronised
-        for it; ops.piece_on_host reads it once it is on the host."""
+        for it; ops.piece_on_host reads it once it is on the host.
+        format (None or the default: this call, launch for launch; else ops.check_format's dict(sample_rate=, encoding=)): the delivery format -- ONE
+        ops.wave_format launch (cbx_wave_format_f32) behind the vocoder, on the stream that owns the waveforms, resamples the B cut waveforms and encodes them; the
+        call returns them as views (float32, int16 or uint8) of one packed buffer, utterance b with ops.formatted_len(n_b, sample_rate) elements.  With a join the
+        launch converts the joined piece instead: the join writes into a zeroed buffer, so converting all of it gives, in [0, formatted_len(total)), exactly the
+        conversion of the piece's [0, total); the piece dict gains `formatted` (that buffer) and `format`; layout and edges stay in 24 kHz samples."""
         B = len(speech_tokens)
         seeds = ops.request_seeds(seeds, B, generator)
         speed = ops.check_speed(speed, B)
         join = ops.check_join(join, B)
+        fmt = ops.check_format_arg(format)
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
         tok = torch.zeros(B, Nmax, dtype=torch.long)
@@ -167,11 +178,18 @@ class S3GenEngine:
             if speed is not None:
                 frames = ops.scaled_len(frames, speed[b])
             out.append(wav[b, : frames * (SAMPLES_PER_TOKEN // 2)])
-        if join is not None:
+        if join is not None and fmt is None:
             if hift_stream is not None:
                 with torch.cuda.stream(hift_stream):
                     return ops.wave_join(out, **join), mel
             return ops.wave_join(out, **join), mel
+        if fmt is not None:
+            with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
+                if join is None:
+                    return ops.wave_format(out, fmt), mel
+                cap = sum(int(w.numel()) for w in out) + sum(join["gaps"])
+                piece = ops.wave_join(out, out=torch.zeros(max(1, cap), device=wav.device), **join)
+                return dict(piece, formatted=ops.wave_format([piece["out"]], fmt)[0], format=fmt), mel
         return out, mel
 
     def co_resident(self, on):
@@ -190,15 +208,16 @@ class S3GenEngine:
 
     @torch.inference_mode()
     def vocode_stream(self, speech_tokens, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=None, z=None, phase=None,
-                      noise=None, n_cfm_timesteps=10, drop_last_token=False, seeds=None, speed=None):
+                      noise=None, n_cfm_timesteps=10, drop_last_token=False, seeds=None, speed=None, format=None):
         """vocode() in rounds: the schedule, the yields and the `window` of synthesize_stream with a list of B 1-D token tensors (valid ids; lengths may differ) in
         place of T3 -- round r synthesises the first n_r tokens of every utterance (stream_token_schedule over the longest), utterance b is final once
         n_r >= N_b.  No T3 is touched: this is the streaming form of voice conversion (the engine ChatterboxVC builds has none), where every token exists up
         front and the input can be arbitrarily long -- give a `window`.  gen_ref: one voice with a whole-token prompt.  seeds: as vocode(seeds=); with a window the
         noise is filled round by round (_stream_rounds).  speed: None or ONE number in [0.5, 2.0] -- the speaking rate of vocode(speed=), as synthesize_stream(speed=)
-        takes it: utterance b's pieces add up to the length vocode(speed=) returns."""
+        takes it: utterance b's pieces add up to the length vocode(speed=) returns.  format: vocode(format=)'s dict, as synthesize_stream(format=) takes it."""
         check_stream_window(window, fade, check_stream_speed(speed))
         seeds = ops.check_seeds(seeds, len(speech_tokens))
+        format = ops.check_format_arg(format)
         pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
         torch.cuda.set_device(pin)  # (a generator cannot hold a device guard across yields)
         toks = [torch.as_tensor(t).view(-1).long().cpu() for t in speech_tokens]
@@ -206,7 +225,8 @@ class S3GenEngine:
         lens = [int(t.numel()) for t in toks]
         self.co_resident(False)
         one_round, closed = _stream_rounds(self, len(toks), gen_ref, n_tokens=max(lens), round_tokens=lambda ts, fin: ts, lookahead=lookahead, fade=fade, z=z,
-                                           phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds, speed=speed)
+                                           phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds, speed=speed,
+                                           format=format)
         for n_r in stream_token_schedule(max(lens), first_chunk, chunk, lookahead, chunk_growth):
             yield one_round([t[:n_r] for t in toks], [n_r >= n for n in lens], n_r >= max(lens))
             if all(closed):
@@ -243,17 +263,19 @@ class ChatterboxEngine(S3GenEngine):
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None):
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
         (T3Engine.generate(seeds=), vocode(seeds=)); not together with a generator.
         speed: None, a number or B numbers in [0.5, 2.0]: the speaking rate of vocode(speed=); T3 and its tokens do not depend on it.
         join: None, or vocode(join=)'s dict -- the B utterances are consecutive chunks of one text; the call then returns (piece, speech_tokens) with piece =
-        ops.piece_on_host's dict (wav = the joined piece on the device, offsets, total, edges, n) plus truncated = [B bools: T3 spent its budget without EOS]."""
+        ops.piece_on_host's dict (wav = the joined piece on the device, offsets, total, edges, n) plus truncated = [B bools: T3 spent its budget without EOS].
+        format: None, or vocode(format=)'s dict -- the waveforms (the joined piece's `wav`) come back at that sample rate in that encoding."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
         join = ops.check_join(join, len(text_tokens))
+        fmt = ops.check_format_arg(format)
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
@@ -263,9 +285,10 @@ class ChatterboxEngine(S3GenEngine):
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         st = _valid_tokens(toks)
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
-                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)))
+                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)),
+                              **({} if fmt is None else dict(format=fmt)))
         if join is not None:  # (the record's copy waits for the two launches behind the vocoder)
-            wavs = dict(ops.piece_on_host(wavs["out"], wavs["rec"], wavs["n"]), truncated=self._truncated(toks))
+            wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks))
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
@@ -281,6 +304,7 @@ class ChatterboxEngine(S3GenEngine):
         (temperature, top_p, min_p, repetition_penalty, cfg_weight: scalar or one per utterance; they override **kw for that job) and a `generator` for the flow / vocoder noise that is not injected (the
         sampling draws of a repeatable job are injected as `uniforms`: T3 is enqueued by another host thread), or `seeds` (one int per utterance, or one int for all:
         every draw of the job that is not injected, as synthesize(seeds=); not together with a generator), or `speed` (a number or one per utterance: vocode(speed=)),
+        or `format` (vocode(format=)'s dict: the job's audio is converted on the device ahead of its copies, which then carry the encoded samples),
         or `join` (vocode(join=)'s dict: the job's utterances are consecutive chunks of one text; `wavs` is then synthesize(join=)'s piece dict with `wav` on the host.
         The two launches run behind the vocoder on its stream, the piece leaves the device as ONE pinned copy plus one of its small records where a job without
         it makes one copy per utterance, and it is sliced after the event this schedule waits for anyway: no host synchronisation is added).
@@ -324,7 +348,7 @@ class ChatterboxEngine(S3GenEngine):
             is called exactly as before there was one)"""
             wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
                                   speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10), drop_last_token=kw.get("drop_last_token", True), sync=False,
-                                  **({"join": job["join"]} if "join" in job else {}))
+                                  **({k: job[k] for k in ("join", "format") if k in job}))
             return wavs
 
         def to_host(job, wavs, pinned):
@@ -333,7 +357,7 @@ class ChatterboxEngine(S3GenEngine):
             ops.piece_on_host), any other job one copy per utterance."""
             copy = (lambda w: torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True)) if pinned else (lambda w: w.cpu())
             if "join" in job:
-                return copy(wavs["out"]), copy(wavs["rec"]), wavs["n"]
+                return copy(wavs.get("formatted", wavs["out"])), copy(wavs["rec"]), wavs["n"], job.get("format")
             return [copy(w) for w in wavs]
 
         def result_of(job, host, toks):
@@ -444,7 +468,7 @@ class ChatterboxEngine(S3GenEngine):
     def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,
                           temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False,
                           ban_from=0, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=True, overlap=True, first_alone=True, run_ahead=2,
-                          window=None, seeds=None, speed=None):
+                          window=None, seeds=None, speed=None, format=None):
         """Chunked synthesis: first audio after `first_chunk` tokens instead of after the whole utterance.
 
         The reference is non-streaming; of its vestigial hooks only HiFT's `cache_source` works (hifigan.py:470-472) -- `finalize=False`
@@ -470,6 +494,9 @@ class ChatterboxEngine(S3GenEngine):
         stretches its mel (the window's, with a window) by one ops.mel_time_scale_window launch in front of the vocoder, and samples are counted in the stretched
         signal (_stream_rounds): utterance b's pieces add up to the length synthesize(speed=) returns, and with window=None the last round vocodes the very mel the
         one-shot call stretches.  An injected `noise` covers 480 * ops.scaled_len(2 n, speed) samples; a window must satisfy check_stream_window(window, fade, speed).
+        format (None or the default: exactly the stream without it; else vocode(format=)'s dict): ONE ops.WaveFormatStream lives for the whole stream and every
+        round's new samples of all open rows go through one push (one cbx_wave_format_f32 launch) ahead of the round's copy to the host, which then carries the
+        encoded pieces; utterance b's pieces add up to ops.formatted_len of what the stream without it emits, and are bit for bit ops.wave_format of that.
         Yields dicts {wavs: [B CPU tensors of NEW samples], final: [B bools], n_tokens: [B], tokens: [B CPU tensors: the speech tokens the round vocoded]};
         concatenating an utterance's pieces gives its waveform."""
         t3_kw = dict(max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p, min_p=min_p, repetition_penalty=repetition_penalty,
@@ -478,7 +505,7 @@ class ChatterboxEngine(S3GenEngine):
         yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_new_tokens, t3_kw=t3_kw, round_tokens=lambda toks, fin: _valid_tokens(toks), n_extra=0,
                                       first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                       noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                      run_ahead=run_ahead, window=window, seeds=seeds, speed=speed)
+                                      run_ahead=run_ahead, window=window, seeds=seeds, speed=speed, format=format)
 
 
 def _stream_plan(n_tokens, done, exhausted, lookahead):
@@ -633,7 +660,7 @@ def stream_speed_schedule(n_tokens, speed=None, first_chunk=25, chunk=50, lookah
     return out
 
 
-def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade, z, phase, noise, n_cfm_timesteps, drop_last_token, window, seeds=None, speed=None):
+def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade, z, phase, noise, n_cfm_timesteps, drop_last_token, window, seeds=None, speed=None, format=None):
     """The state of one stream of B utterances and its round function: -> (one_round, closed flags).  one_round(toks, done, exhausted) runs flow + vocoder
     on the CURRENT stream and returns the dict the stream generators yield.  n_tokens: the most tokens an utterance can have (the default z / noise cover them).
 
@@ -658,8 +685,12 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
     vocoder's lens, the noise columns [480 j0, ...), the cache and the phase carry (offset j0 - j0 of the last round), emitted / end / avail, the tails and the
     emission's origin 480 j0; a = stream_window_origin(E, W, s).  trim_fade while j0 == 0.  A final row's avail is 480 * ops.scaled_len(min(2 keep, 2 n), s),
     what vocode(speed=) returns.  Default noise is sized 480 * ops.scaled_len(2 n_tokens, s); an injected one must cover the stretched utterance; z is the
-    flow's and does not change."""
+    flow's and does not change.
+    format (None or the default: every launch of the stream without it; else ops.check_format's dict): the stream's ops.WaveFormatStream -- a round's new samples
+    (after the cross-fade) of all rows go through ONE push, and the round's single copy to the host takes the packed, encoded buffer."""
     dev = self.dev
+    fmt = ops.check_format_arg(format)
+    wfs = None if fmt is None else ops.WaveFormatStream(B, fmt, dev)
     rate = check_stream_speed(speed)
     W = check_stream_window(window, fade, rate)
     P = gen_ref["prompt_token"].shape[-1]
@@ -758,8 +789,15 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
                     avail = min(avail, keep * SAMPLES_PER_TOKEN if rate is None else HALF * ops.scaled_len(2 * keep, rate))
                 return (avail if fin[b] else max(emitted[b], avail - fade)), avail
 
+            def formatted(rows):
+                """one push of the round's new samples (views of one device tensor, None for a row that was closed before) -> the encoded pieces on the host"""
+                wfs.push(rows, [fin[b] or rows[b] is None for b in range(B)])
+                host = wfs.packed.cpu()
+                return [host[s: s + c].clone() if c else out[b] for b, (s, c) in enumerate(wfs.spans)]
+
             if W is None:  # (o == 0: every round starts at sample 0)
                 cache[0] = src[:, : HALF * min(frames)].clone() if min(frames) > 0 else None
+                dnew = [None] * B
                 for b in range(B):
                     if closed[b]:
                         continue
@@ -771,12 +809,22 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
                     tails[b] = None if fin[b] else wav[b, end: min(avail, end + fade)].clone()
                     emitted[b] = end
                     closed[b] = fin[b]
-                    out[b] = new.cpu()
+                    if wfs is None:
+                        out[b] = new.cpu()
+                    else:
+                        dnew[b] = new
+                if wfs is not None:  # the rows as views of one tensor
+                    pack = torch.empty(B, max([0] + [w.numel() for w in dnew if w is not None]), device=dev)
+                    for b, w in enumerate(dnew):
+                        if w is not None:
+                            pack[b, : w.numel()] = w
+                    out = formatted([None if w is None else pack[b, : w.numel()] for b, w in enumerate(dnew)])
             else:
                 go_on = [frames[b] for b in range(B) if not fin[b]]
                 cache[0] = src[:, : HALF * min(go_on)].clone() if go_on and min(go_on) > 0 else None
                 win.update(a=a, j0=j0, cum=self.hift.frame_cum)
                 meta, news, nxt = torch.zeros(4, B, dtype=torch.int32), [0] * B, [0] * B
+                was_closed = list(closed)
                 for b in range(B):
                     if closed[b]:
                         meta[:3, b] = emitted[b]
@@ -792,25 +840,29 @@ def _stream_rounds(self, B, gen_ref, *, n_tokens, round_tokens, lookahead, fade,
                 new = torch.empty(B, max(news), device=dev)
                 ops.stream_emit(wav, o, meta.to(dev), t_in, ramp if fade else None, new, t_out)
                 win.update(tail_len=nxt, cur=1 - win["cur"])
-                host = new.cpu()
-                for b in range(B):
-                    if news[b]:
-                        out[b] = host[b, : news[b]].clone()
+                if wfs is not None:
+                    out = formatted([None if was_closed[b] else new[b, : news[b]] for b in range(B)])
+                else:
+                    host = new.cpu()
+                    for b in range(B):
+                        if news[b]:
+                            out[b] = host[b, : news[b]].clone()
         return dict(wavs=out, final=list(fin), n_tokens=ns, tokens=st)
 
     return one_round, closed
 
 
 def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw, round_tokens, n_extra, first_chunk, chunk, chunk_growth, lookahead, fade, z,
-                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead, window=None, seeds=None, speed=None):
+                       phase, noise, n_cfm_timesteps, drop_last_token, overlap, first_alone, run_ahead, window=None, seeds=None, speed=None, format=None):
     """The round schedule of synthesize_stream for either backbone (ChatterboxEngine: Llama T3, TurboEngine: GPT-2 T3; both T3 engines offer the async
     generate / advance / peek protocol).  n_budget: tokens the T3 call can sample; t3_kw: its sampling arguments; round_tokens(toks, final flags) -> the
     valid speech tokens a round vocodes (never empty); n_extra: tokens round_tokens may add (the default z / noise cover n_budget + n_extra).
     window: None, or the left context in tokens of a bounded round (_stream_rounds).  seeds: None, an int or B ints -- the sampling draws (generate(seeds=))
     and the flow / vocoder noise (_stream_rounds) that are not injected.  speed: None or one rate for the stream (_stream_rounds(speed=)); T3 does not depend on it,
-    so the serial and the overlapped schedule take it alike."""
+    so the serial and the overlapped schedule take it alike.  format: None or the stream's delivery format (_stream_rounds(format=))."""
     check_stream_window(window, fade, check_stream_speed(speed))
     seeds = ops.check_seeds(seeds, len(text_tokens))
+    format = ops.check_format_arg(format)
     # (a generator cannot hold a device guard across yields: pin the device for the caller; "cuda" without an index = the current device)
     pin = self.dev if self.dev.index is not None else torch.device("cuda", torch.cuda.current_device())
     torch.cuda.set_device(pin)
@@ -818,7 +870,7 @@ def _synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, n_budget, t3_kw,
     t3_kw = dict(t3_kw, async_mode=True, seeds=seeds)
     totals = stream_token_schedule(N, first_chunk, chunk, lookahead, chunk_growth)  # tokens decoded when round r starts
     one_round, closed = _stream_rounds(self, B, gen_ref, n_tokens=N + n_extra, round_tokens=round_tokens, lookahead=lookahead, fade=fade, z=z, phase=phase, noise=noise,
-                                       n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds, speed=speed)
+                                       n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, window=window, seeds=seeds, speed=speed, format=format)
     if not overlap:  # the serial form of rounds 3-5: T3 waits while a round is synthesised
         h = self.t3.generate(t3_conds, text_tokens, run_steps=totals[0], **t3_kw)
         for r, n_r in enumerate(totals):
@@ -907,14 +959,15 @@ class TurboEngine(S3GenEngine):
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
         for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=);
         speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=); join: None, or vocode(join=)'s dict -- the call then returns
-        ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS)."""
+        ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
         join = ops.check_join(join, len(text_tokens))
+        fmt = ops.check_format_arg(format)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                 repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
@@ -923,9 +976,9 @@ class TurboEngine(S3GenEngine):
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed,
-                              **({} if join is None else dict(join=join)))
+                              **({} if join is None else dict(join=join)), **({} if fmt is None else dict(format=fmt)))
         if join is not None:
-            wavs = dict(ops.piece_on_host(wavs["out"], wavs["rec"], wavs["n"]), truncated=self._truncated(toks, max_gen_len))
+            wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks, max_gen_len))
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
@@ -938,13 +991,13 @@ class TurboEngine(S3GenEngine):
     @torch.inference_mode()
     def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_gen_len=1000,
                           temperature=0.8, top_k=1000, top_p=0.95, repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2, window=None, seeds=None, speed=None):
+                          noise=None, n_cfm_timesteps=2, drop_last_token=False, overlap=True, first_alone=True, run_ahead=2, window=None, seeds=None, speed=None, format=None):
         """Chunked synthesis of Turbo / Nano: the round schedule, yields and overlap / first_alone / run_ahead semantics of ChatterboxEngine.synthesize_stream
         around the GPT-2 T3 (chunked through T3TurboEngine.generate(async_mode=True) / advance / peek) and the 2-step meanflow flow.  A round vocodes the
         sampled ids < 6561; the FINAL round of an utterance appends the three S3GEN_SIL tokens exactly as synthesize() does and keeps every token
         (drop_last_token=False), non-final rounds carry no silence and hold back 2 * lookahead frames.  T3 can sample max_gen_len + 1 tokens: the default
         z / phase / noise cover that many plus the 3 silence tokens.  The last round is a full synthesis: identical mel to synthesize() for the same noise.
-        window: the bounded-cost rounds of ChatterboxEngine.synthesize_stream; seeds: its per-utterance seeds; speed: its speaking rate (one number for the stream)."""
+        window: the bounded-cost rounds of ChatterboxEngine.synthesize_stream; seeds: its per-utterance seeds; speed: its speaking rate (one number for the stream); format: its delivery format."""
         t3_kw = dict(max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, uniforms=uniforms,
                      ban_eos=ban_eos, ban_from=ban_from)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
@@ -956,4 +1009,4 @@ class TurboEngine(S3GenEngine):
         yield from _synthesize_stream(self, text_tokens, t3_conds, gen_ref, n_budget=max_gen_len + 1, t3_kw=t3_kw, round_tokens=round_tokens, n_extra=3,
                                       first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                       noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
-                                      run_ahead=run_ahead, window=window, seeds=seeds, speed=speed)
+                                      run_ahead=run_ahead, window=window, seeds=seeds, speed=speed, format=format)

@@ -1104,11 +1104,169 @@ def wave_join(rows, gaps, trim_db=None, pad_frames=2, fade=240, first=True, last
     return dict(out=out, rec=rec, layout=layout, edges=edges, n=n)
 
 
-def piece_on_host(out, rec, n):
-    """The host's reading of a joined piece once `out` and `rec` (wave_join) are readable: dict(wav = out[:total], offsets, total, edges = [(start, stop)], n)."""
+def piece_on_host(out, rec, n, fmt=None):
+    """The host's reading of a joined piece once `out` and `rec` (wave_join) are readable: dict(wav = out[:total], offsets, total, edges = [(start, stop)], n).
+    fmt (a format dict; `out` is then the converted buffer of vocode(join=, format=)): wav = out[:formatted_len(total)] and the dict names the `format`; offsets,
+    total and edges stay in 24 kHz samples."""
     R = len(n)
     rec = [int(v) for v in rec.tolist()]
-    return dict(wav=out[: rec[R]], offsets=rec[:R], total=rec[R], edges=[(rec[R + 1 + 2 * r], rec[R + 2 + 2 * r]) for r in range(R)], n=list(n))
+    piece = dict(wav=out[: rec[R]], offsets=rec[:R], total=rec[R], edges=[(rec[R + 1 + 2 * r], rec[R + 2 + 2 * r]) for r in range(R)], n=list(n))
+    return piece if fmt is None else dict(piece, wav=out[: formatted_len(rec[R], fmt["sample_rate"])], format=fmt)
+
+
+# ----------------------------------------------------------------------------- output formats: resample + encode ahead of the copy to the host (wave_format.hip)
+WAVE_IN_RATE = 24000
+WAVE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+WAVE_ENCODINGS = ("f32", "s16", "mulaw", "alaw")   # cbx_wave_format_f32's encoding 0 .. 3
+_WAVE_DTYPES = (torch.float32, torch.int16, torch.uint8, torch.uint8)
+_WAVE_FILTERS, _WAVE_TABLES = {}, {}
+
+
+def check_format(sample_rate=None, encoding=None, name="format"):
+    """The output format of a call: None for the default (sample_rate None / 24000 and encoding None / "f32": the call is then exactly the one without the
+    arguments), else dict(sample_rate=int, encoding=str).  sample_rate: an int of WAVE_RATES (a bool or a non-int is a TypeError); encoding: a str of
+    WAVE_ENCODINGS.  TypeError / ValueError before anything is launched."""
+    if sample_rate is None:
+        sample_rate = WAVE_IN_RATE
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int):
+        raise TypeError(f"{name}: sample_rate: expected None or an int, got {type(sample_rate).__name__}")
+    if sample_rate not in WAVE_RATES:
+        raise ValueError(f"{name}: sample_rate = {sample_rate}: expected one of {WAVE_RATES}")
+    if encoding is None:
+        encoding = "f32"
+    if not isinstance(encoding, str):
+        raise TypeError(f"{name}: encoding: expected None or a str, got {type(encoding).__name__}")
+    if encoding not in WAVE_ENCODINGS:
+        raise ValueError(f"{name}: encoding = {encoding!r}: expected one of {WAVE_ENCODINGS}")
+    return None if (sample_rate, encoding) == (WAVE_IN_RATE, "f32") else dict(sample_rate=sample_rate, encoding=encoding)
+
+
+def check_format_arg(fmt, name="format"):
+    """A `format` argument of the engines -- None, or a dict with the keys sample_rate and / or encoding -- as check_format returns it."""
+    if fmt is None:
+        return None
+    if not isinstance(fmt, dict):
+        raise TypeError(f"{name}: expected None or a dict(sample_rate=, encoding=), got {type(fmt).__name__}")
+    if set(fmt) - {"sample_rate", "encoding"}:
+        raise ValueError(f"{name}: keys {sorted(fmt)}: expected sample_rate and / or encoding")
+    return check_format(fmt.get("sample_rate"), fmt.get("encoding"), name)
+
+
+def _wave_fmt(fmt):
+    """(rate, encoding index) of a format dict; None is 24 kHz fp32 (the identity, still one launch)"""
+    fmt = check_format_arg(fmt) or dict(sample_rate=WAVE_IN_RATE, encoding="f32")
+    return fmt["sample_rate"], WAVE_ENCODINGS.index(fmt["encoding"])
+
+
+def wave_filter(sample_rate):
+    """The resampler 24000 -> sample_rate as scipy.signal.resample_poly designs it, restated in NumPy fp64 (no SciPy in the product path): U / D the reduced
+    ratio, hl = 10 max(U, D), h = U firwin(2 hl + 1, 1 / max(U, D), window=("kaiser", 5.0)) -- the windowed sinc cutoff sinc(cutoff (i - hl)) times np.kaiser,
+    scaled to unit gain at 0 --, tab (U, T) fp32 = h[p + j U] (zero past 2 hl), T = ceil((2 hl + 1) / U) taps per output, H = ceil(2 hl / U) samples of history.
+    24000: no filter (hl = H = 0, T = 1, tab = [[1]]).  Built once per rate."""
+    import math
+    import numpy as np
+    if sample_rate not in _WAVE_FILTERS:
+        if sample_rate not in WAVE_RATES:
+            raise ValueError(f"sample_rate = {sample_rate}: expected one of {WAVE_RATES}")
+        g = math.gcd(sample_rate, WAVE_IN_RATE)
+        U, D = sample_rate // g, WAVE_IN_RATE // g
+        if U == D:
+            f = dict(U=1, D=1, hl=0, T=1, H=0, h=np.ones(1), tab=np.ones((1, 1), np.float32))
+        else:
+            hl, cutoff = 10 * max(U, D), 1.0 / max(U, D)
+            i = np.arange(2 * hl + 1, dtype=np.float64) - hl
+            h = cutoff * np.sinc(cutoff * i) * np.kaiser(2 * hl + 1, 5.0)
+            h = U * (h / h.sum())
+            T = -(-(2 * hl + 1) // U)
+            pad = np.zeros(U * T)
+            pad[: 2 * hl + 1] = h
+            f = dict(U=U, D=D, hl=hl, T=T, H=-(-2 * hl // U), h=h, tab=np.ascontiguousarray(pad.reshape(T, U).T.astype(np.float32)))
+        _WAVE_FILTERS[sample_rate] = f
+    return _WAVE_FILTERS[sample_rate]
+
+
+def _wave_table(sample_rate, device):
+    """wave_filter's phase table on `device`, uploaded once per (device, rate)"""
+    key = (str(device), sample_rate)
+    if key not in _WAVE_TABLES:
+        _WAVE_TABLES[key] = torch.from_numpy(wave_filter(sample_rate)["tab"]).to(device)
+    return _WAVE_TABLES[key]
+
+
+def formatted_len(n, sample_rate):
+    """Samples at `sample_rate` of n samples at 24 kHz: ceil(n U / D)"""
+    f = wave_filter(WAVE_IN_RATE if sample_rate is None else sample_rate)
+    return -(-int(n) * f["U"] // f["D"])
+
+
+def _wave_counts(f, n0, m0, lens, final):
+    """outputs of one cbx_wave_format_f32 launch per row (include/cbx.h states the rule)"""
+    out = []
+    for a, b, L, fin in zip(n0, m0, lens, final):
+        N = a + L
+        m1 = -(-N * f["U"] // f["D"]) if fin else max(0, ((N - 1) * f["U"] - f["hl"]) // f["D"] + 1)
+        out.append(max(0, m1 - b))
+    return out
+
+
+def _wave_format_launch(rows, rate, enc, n0=None, m0=None, final=None, hist_in=None, hist_out=None):
+    """One cbx_wave_format_f32 launch on the current stream -> (packed output buffer, [(offset, count)] per row).  No host synchronisation."""
+    base, offs, lens = _wave_rows(rows, "wave_format")
+    R, dev, f = len(lens), rows[0].device, wave_filter(rate)
+    one_shot = n0 is None
+    cnt = _wave_counts(f, [0] * R if one_shot else n0, [0] * R if one_shot else m0, [int(v) for v in lens], [True] * R if one_shot else final)
+    starts = [sum(cnt[:r]) for r in range(R)]
+    packed = torch.empty(max(1, sum(cnt)), dtype=_WAVE_DTYPES[enc], device=dev)
+    o = (ctypes.c_long * R)(*starts)
+    cont = [None] * 3 if one_shot else [(ctypes.c_long * R)(*n0), (ctypes.c_long * R)(*m0), (ctypes.c_int * R)(*[int(bool(v)) for v in final])]
+    check(lib.cbx_wave_format_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, rate, enc, _p(_wave_table(rate, dev)) if f["hl"] else None, f["U"], f["T"],
+                                  *[None if c is None else ctypes.addressof(c) for c in cont], _p(hist_in), _p(hist_out), _p(packed), ctypes.addressof(o),
+                                  packed.numel(), _stream()), "cbx_wave_format_f32")
+    return packed, list(zip(starts, cnt))
+
+
+def wave_format(rows, fmt):
+    """cbx_wave_format_f32 on the current stream: rows (_wave_rows: 1 .. 64 1-D fp32 views of ONE allocation, 24 kHz) resampled to fmt["sample_rate"] and stored
+    as fmt["encoding"] (check_format's dict; None: 24 kHz fp32) in ONE launch.  Returns R 1-D tensors (float32, int16 or uint8; row r has
+    formatted_len(n_r, sample_rate) elements) that are views of one packed device buffer: `rows[0]._base` of the result is what a single copy takes to the host.
+    No host synchronisation."""
+    rate, enc = _wave_fmt(fmt)
+    rows = list(rows)
+    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+        return [torch.empty(0, dtype=_WAVE_DTYPES[enc], device=w.device) for w in rows]
+    packed, spans = _wave_format_launch(rows, rate, enc)
+    return [packed[a: a + c] for a, c in spans]
+
+
+class WaveFormatStream:
+    """cbx_wave_format_f32 over the pieces of B signals that arrive round by round: per row the samples consumed (n0), the outputs produced (m0) and the last H
+    samples (two (B, H) device buffers, ping-pong).  push(rows, final) converts the rows' new pieces in ONE launch; the concatenated results of a row are bit for
+    bit wave_format of the concatenated pieces.  A row is flushed by the push that carries final[b] = True; later pushes give it nothing."""
+
+    def __init__(self, B, fmt, device):
+        self.rate, self.enc = _wave_fmt(fmt)
+        self.B, self.dev, self.f = int(B), torch.device(device), wave_filter(self.rate)
+        self.n0, self.m0, self.closed = [0] * self.B, [0] * self.B, [False] * self.B
+        self.hist = [torch.zeros(self.B, max(1, self.f["H"]), device=self.dev) for _ in range(2)]
+        self.cur, self.packed, self.spans = 0, None, None
+
+    def push(self, rows, final):
+        """rows: B 1-D fp32 tensors on the device, views of ONE allocation (None or an empty tensor: nothing new for that row); final: B bools.  Returns B 1-D
+        tensors, views of self.packed (one buffer: a single copy takes the round to the host; self.spans = [(offset, count)])."""
+        rows, final = list(rows), [bool(v) for v in final]
+        if len(rows) != self.B or len(final) != self.B:
+            raise ValueError(f"WaveFormatStream.push: {len(rows)} rows and {len(final)} flags for {self.B} signals")
+        anchor = next((w for w in rows if w is not None and w.numel()), self.hist[0].view(-1))  # (an empty tensor may have no allocation at all)
+        rows = [anchor[:0] if (w is None or not w.numel() or self.closed[b]) else w for b, w in enumerate(rows)]
+        final = [fin or self.closed[b] for b, fin in enumerate(final)]
+        lens = [int(w.numel()) for w in rows]
+        self.packed, self.spans = _wave_format_launch(rows, self.rate, self.enc, self.n0, self.m0, final, self.hist[self.cur], self.hist[1 - self.cur])
+        self.cur = 1 - self.cur
+        for b in range(self.B):
+            self.n0[b] += lens[b]
+            self.m0[b] += self.spans[b][1]
+            self.closed[b] = final[b]
+        return [self.packed[a: a + c] for a, c in self.spans]
 
 
 def hift_stft(s, spec, sample_lens=None):

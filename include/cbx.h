@@ -846,6 +846,29 @@ int cbx_wave_edges_f32(const float* wav, const long* row_off, const int* row_len
 int cbx_wave_join_f32(const float* wav, const long* row_off, const int* row_len, const int* gaps, int R, const int* edges, const float* ramp, int fade, int first,
                       int last, float* out, long out_cap, int* layout, void* stream);
 
+/* ---- output formats: resample 24 kHz fp32 to the delivery rate and encode it, one launch for the rows of a batch or of a stream's round (added after ABI v16
+ * without a version step: a new function only).  The reference returns 24 kHz fp32 and leaves this to its caller (tts.py:272, mtl_tts.py:352, tts_turbo.py:320,
+ * vc.py:104).  Rows as cbx_wave_join_f32 takes them: R in [1, 64] pieces of row_len[r] floats at wav + row_off[r] (HOST arrays; 4-byte alignment is enough).
+ * rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000; U / D = rate / 24000 reduced.  The filter is scipy.signal.resample_poly's default design, built by the
+ * CALLER in fp64: hl = 10 max(U, D), h = U firwin(2 hl + 1, 1 / max(U, D), window = ("kaiser", 5.0)); tab: its fp32 phase table in device memory, tab[p * T + j] =
+ * h[p + j U] (zero past 2 hl), T = ceil((2 hl + 1) / U) taps per output; the U and T of the table are passed and must be the rate's.  Output m of a row of n samples:
+ *   c = m D + hl, p = c mod U, k_hi = c div U, y[m] = sum_(j = 0 .. T - 1) tab[p][j] x[k_hi - j], x[k] = 0 outside [0, n), m in [0, ceil(n U / D))
+ * accumulated in fp32 by fmaf in the order j = 0 .. T - 1, starting from 0 -- resample_poly(x, U, D) to fp32 rounding.  24000: no filter, y = x (tab may be NULL,
+ * U = T = 1).  encoding, fused into the store: 0 fp32 y as it is; 1 int16 clamp(rintf(y * 32768), -32768, 32767), ties to even, NaN -> 0; 2 / 3 one byte, the
+ * G.711 mu-law / A-law code of that int16 (audioop.lin2ulaw / lin2alaw at width 2).  The y under an encoded store is bit for bit the y encoding 0 stores.  No dither.
+ * out: ONE buffer of out_cap elements of the encoding's type; row r's outputs go to out + out_off[r] (HOST array, elements).
+ * Continuation (n0, m0, fin: HOST arrays of R entries, all three or none; none = {0, 0, 1}: the one-shot call).  Row r's piece holds absolute samples
+ * [n0[r], n0[r] + L) of its signal, m0[r] outputs exist already, and the launch produces m0 <= m < m1: m1 = ceil((n0 + L) U / D) when fin[r], else
+ * floor(((n0 + L - 1) U - hl) / D) + 1, the outputs all of whose taps lie below n0 + L (never less than m0; 0 when the numerator is negative).  Sample k is read from
+ * hist_in[r * H + k - (n0 - H)] for n0 - H <= k < n0 (H = ceil(2 hl / U), the last H samples before the piece; NULL when every n0 is 0), from the piece for
+ * n0 <= k < n0 + L, as zero elsewhere; hist_out (NULL: not kept) receives the last H samples before n0 + L, and is another buffer than hist_in (ping-pong).  Pieces
+ * of 0 samples or of fewer than H are fine.  For finite samples the concatenated outputs of ANY split of a row are bit for bit its one-shot outputs.  All positions
+ * are 64-bit.
+ * -22 before any launch: a null pointer, R outside [1, 64], a negative length, offset, n0 or m0, an unknown rate or encoding, U / T that are not the rate's, a
+ * continued row without a history, hist_out == hist_in, a row that would write outside [0, out_cap), out_cap below the sum of the rows' outputs. */
+int cbx_wave_format_f32(const float* wav, const long* row_off, const int* row_len, int R, int rate, int encoding, const float* tab, int U, int T, const long* n0,
+                        const long* m0, const int* fin, const float* hist_in, float* hist_out, void* out, const long* out_off, long out_cap, void* stream);
+
 /* ---- voice-prompt / voice-conversion front-end ----
  * Contractions (framed DFT as a GEMM over overlapping waveform rows, mel filterbanks, Conv1d/Conv2d-as-Toeplitz, attention, LSTM
  * projections) use cbx_gemm_f32 / cbx_flash_attn_f32 / cbx_gemv_f32; these are the remaining element-wise / reduction passes. */
