@@ -8,7 +8,8 @@ backbone.  Voice-prompt analysis (`prepare_conditionals`, `ChatterboxVC.set_targ
 the device through chatterbox_amd/frontend.py (S3 tokenizer, CAMPPlus, voice encoder, 24 kHz mel); it needs the `tokenizer.*` /
 `speaker_encoder.*` tensors of the S3Gen checkpoint and `ve.safetensors`, and fails with a clear message when a checkpoint lacks
 them.  The watermarker (third-party `perth`) is applied only if importable -- parity is defined on the pre-watermark waveform;
-Turbo's `norm_loudness` needs `pyloudnorm` and is skipped with a warning when that is missing (as the reference does on error).
+Turbo's `norm_loudness` needs `pyloudnorm` and is skipped with a warning when that is missing (as the reference does on error); norm_loudness="device" uses this
+project's own meter instead.
 """
 import contextlib
 import os
@@ -124,6 +125,18 @@ def _norm_loudness(wav, sr, target_lufs=-27.0):
     return wav
 
 
+def _norm_loudness_device(wav, device, target_lufs=-27.0):
+    """_norm_loudness without pyloudnorm: the 24 kHz prompt goes to the device, cbx_wave_loudness_f32 measures it (ITU-R BS.1770-4 as include/cbx.h states it: whole
+    400 ms blocks only, where pyloudnorm may add a partial one) and cbx_wave_gain_f32 gains it to `target_lufs`; no peak ceiling, as the reference applies none.  A
+    silent prompt or one shorter than 0.4 s comes back as it is."""
+    import numpy as np
+    dev = torch.device(device)
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        w = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)).to(dev, copy=True)  # (the gain is applied in place: never to the caller's array)
+        ops.wave_normalize([w], [float(target_lufs)], ceiling=None, fs=S3GEN_SR)
+        return w.cpu().numpy()
+
+
 def _load_wave(wav, sr):
     """A file path or a (waveform, sample_rate) pair -> the waveform at rate `sr` (a float32 array)."""
     from . import frontend as fe
@@ -140,7 +153,11 @@ def _prepare_conditionals(analyzer, wav, exaggeration, prompt_len, device, min_s
     w24 = _load_wave(wav, S3GEN_SR)
     if min_seconds is not None:
         assert len(w24) / S3GEN_SR > min_seconds, "Audio prompt must be longer than 5 seconds!"
-    if norm_loudness:
+    if isinstance(norm_loudness, str):
+        if norm_loudness != "device":
+            raise ValueError(f"norm_loudness = {norm_loudness!r}: expected True, False or 'device'")
+        w24 = _norm_loudness_device(w24, device)
+    elif norm_loudness:
         w24 = _norm_loudness(w24, S3GEN_SR)
     w16 = fe.resample(w24, S3GEN_SR, S3_SR)
     gen = analyzer.embed_ref(w24[: analyzer.DEC_COND_LEN], S3GEN_SR)
@@ -165,6 +182,20 @@ def _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, windo
     speed_kw = _stream_speed_kw(speed)
     return dict(first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, overlap=overlap,
                 window=check_stream_window(window, fade, speed_kw.get("speed")), **speed_kw)
+
+
+def _one_loudness(loudness):
+    """The `loudness` of a method that takes ONE request: None, or the LUFS target as a float (ops.check_loudness; a sequence is a TypeError)"""
+    if isinstance(loudness, (list, tuple)):
+        raise TypeError(f"loudness: expected None or a number, got a {type(loudness).__name__}")
+    loud = ops.check_loudness(loudness, 1)
+    return None if loud is None else loud[0]
+
+
+def _loudness_kw(loudness):
+    """generate's `loudness` as the engines' loudness= keyword ({} for None: the engine call is then exactly the one without it)"""
+    loud = _one_loudness(loudness)
+    return {} if loud is None else dict(loudness=loud)
 
 
 def _stream_speed_kw(speed):
@@ -359,14 +390,18 @@ class _Finish:
     """The epilogue of every public method that returns audio."""
     sr = S3GEN_SR
 
-    def _finish(self, wav, fmt=None, converted=True):
+    def _finish(self, wav, fmt=None, converted=True, loud=None):
         """A device waveform as the reference returns it: CPU float32 (1, n), watermarked if a watermarker is loaded.
         fmt (ops.check_format's dict; None: exactly the above): the (1, n) CPU tensor at fmt's rate in fmt's encoding.  Without a watermarker the engine was given the
         format and `wav` is the converted audio already (converted=True): one copy to the host.  With one -- or when the caller kept the format from the engine
-        (converted=False: generate_long) -- `wav` is 24 kHz fp32: it is watermarked on the host as ever, then converted on the device (_to_format)."""
+        (converted=False: generate_long) -- `wav` is 24 kHz fp32: it is watermarked on the host as ever, then converted on the device (_to_format).
+        loud (a LUFS target; generate_long): the 24 kHz waveform is normalised as ONE signal first (_to_loudness); the watermark follows the gain, the conversion
+        the watermark."""
         if fmt is not None and converted and self.watermarker is None:
             return wav.detach().cpu().unsqueeze(0)
         wav = wav.detach().float().cpu()
+        if loud is not None:
+            wav = self._to_loudness(wav, loud)
         if self.watermarker is not None:
             wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
         return (wav if fmt is None else self._to_format(wav, fmt)).unsqueeze(0)
@@ -380,6 +415,15 @@ class _Finish:
         dev, scope = self._device_scope()
         with scope:
             return ops.wave_format([wav.to(dev)], fmt)[0].cpu()
+
+    def _to_loudness(self, wav, target):
+        """A 24 kHz fp32 waveform on the host -> the device, ops.wave_normalize to `target` LUFS (sample peak limited to 1.0), back to the host (1-D); the stats stay
+        on the device as engine.last_loudness"""
+        dev, scope = self._device_scope()
+        with scope:
+            w = wav.to(dev).contiguous()
+            self.engine.last_loudness = ops.wave_normalize([w], [float(target)])
+            return w.cpu()
 
     def _engine_format(self, fmt):
         """The engines' format= keyword: {} for the default format (the engine call is then exactly the one without it) and when a watermarker is loaded (it works
@@ -476,7 +520,7 @@ class _TTS(_Finish):
             args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
             yield self.engine.synthesize(*args, **synth_kw, **job)
 
-    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, **analyse_kw):
+    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, loudness=None, **analyse_kw):
         """generate_batch behind its signature: validation of every per-request argument (seeds and speed first), then the voices, then tokenisation, then the
         device work.  samp: the sampling arguments the engine takes; unsampled: those it does not -- exaggeration, which picks the voice's cond dict, and what the
         backbone ignores."""
@@ -485,22 +529,24 @@ class _TTS(_Finish):
         assert B >= 1, "empty batch"
         seeds = _batch_seeds(seeds, B, generator)
         speed = ops.check_speed(speed, B)
+        loud = ops.check_loudness(loudness, B)
         langs = self._languages(language_ids, B)
         samp = _sampling_lists(B, **samp)
         unsampled = _sampling_lists(B, **unsampled)
         self._warn_ignored(*(v for vals in unsampled.values() for v in vals))
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, unsampled["exaggeration"], **analyse_kw)
         tokens = [self._engine_tokens(self._text_ids(t, lid)) for t, lid in zip(texts, langs)]
-        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt)
+        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt, loud)
 
     def _languages(self, language_ids, B):
         return [None] * B
 
-    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None):
+    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None, loud=None):
         """Sub-batches of at most max_batch requests in order of text length (_run_jobs: one runs the serial schedule, several the throughput schedule).  Returns the
         finished waveforms in the caller's order.  seeds (B ints or None) travel with their requests: a request's draws do not depend on the sub-batch or the row
         it lands in.  speed (B floats or None) travels the same way.  fmt (one format for the call, or None): every job carries it as `format` unless a
-        watermarker is loaded (_engine_format)."""
+        watermarker is loaded (_engine_format).  loud (B LUFS targets / Nones, or None) travels with its requests like speed: a job carries `loudness` only when
+        one of its requests has a target."""
         dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
         plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
         jobs = []
@@ -514,6 +560,8 @@ class _TTS(_Finish):
                 job["seeds"] = _pick(seeds, idx)
             if speed is not None:
                 job["speed"] = _pick(speed, idx)
+            if loud is not None and any(v is not None for v in _pick(loud, idx)):
+                job["loudness"] = _pick(loud, idx)
             job.update(self._engine_format(fmt))
             jobs.append(job)
         out = [None] * len(tokens)
@@ -522,21 +570,23 @@ class _TTS(_Finish):
                 out[i] = self._finish(w, fmt)
         return out
 
-    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, fmt=None, **prepare_kw):
+    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, fmt=None, loudness=None, **prepare_kw):
         """generate_long behind its signature and _long_args: the remaining checks, the voice as generate() prepares it, then _run_long.  samp / unsampled: as
         _generate_batch takes them, one number each."""
         if not isinstance(text, str):
             raise TypeError(f"text: expected a str, got {type(text).__name__}")
         _long_numbers(**unsampled, **samp)
+        loud = _one_loudness(loudness)
         self._use_voice(audio_prompt_path, unsampled["exaggeration"], **prepare_kw)
         self._warn_ignored(*unsampled.values())
-        return self._run_long(text, a, lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id)), samp, return_segments, fmt)
+        return self._run_long(text, a, lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id)), samp, return_segments, fmt, loud)
 
-    def _run_long(self, text, a, tokenize, samp, return_segments, fmt=None):
+    def _run_long(self, text, a, tokenize, samp, return_segments, fmt=None, loud=None):
         """generate_long behind its validation: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), run the jobs of long_plan (_run_jobs), concatenate
         the joined pieces on the host, watermark the whole once.  fmt: the engine jobs do not carry it -- the concatenated 24 kHz waveform is converted once, in
         _finish (host -> device -> host; no converter state travels through the joined pieces on the device), and the segments' start / stop become output samples,
-        ceil(s U / D), so the last stop is the length; src_start / src_stop stay 24 kHz samples."""
+        ceil(s U / D), so the last stop is the length; src_start / src_stop stay 24 kHz samples.  loud (a LUFS target or None): the engine jobs do not carry it
+        either -- the concatenated waveform is measured and gained as ONE signal in _finish, ahead of the watermark, so the chunks keep their relative level."""
         chunks = split_text(text, a["max_chars"])
         tokens = [tokenize(c) for c, _ in chunks]
         plan = long_plan(chunks, int(self.max_batch or self.engine.t3.MAX_BATCH), a)
@@ -556,7 +606,7 @@ class _TTS(_Finish):
             import logging
             logging.getLogger(__name__).warning("generate_long: chunk(s) %s of %d reached the speech-token budget without an end-of-speech token and are cut "
                                                 "off; use a smaller max_chars (now %d)", cut, len(segments), a["max_chars"])
-        wav = self._finish(torch.cat(pieces), fmt, converted=False)
+        wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=loud)
         if fmt is not None:
             for seg in segments:
                 seg.update(start=ops.formatted_len(seg["start"], fmt["sample_rate"]), stop=ops.formatted_len(seg["stop"], fmt["sample_rate"]))
@@ -624,7 +674,7 @@ class ChatterboxTTS(_LlamaTTS):
         return self.tokenizer.text_to_tokens(punc_norm_en(text))
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
-                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None):
+                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
         alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
         speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
@@ -634,15 +684,19 @@ class ChatterboxTTS(_LlamaTTS):
         result is then the (1, n) CPU tensor of float32, int16 (PCM16) or uint8 (G.711) at that rate, n = ceil(n24 U / D) -- resampled as
         scipy.signal.resample_poly does (frontend.resample's definition; its default filter, no dither) and encoded by ONE launch on the device, ahead of the only
         copy to the host (ops.wave_format); with a watermarker loaded, after the watermark.  `.sr` stays 24000.  The defaults are the call without the arguments.
-        This is the statement of `seed`, `speed`, `sample_rate` and `encoding` for every method of every class of this module; the others say only what differs."""
+        loudness (None, or a number in [-50, -5]): the target integrated loudness in LUFS (ITU-R BS.1770-4, e.g. -16 for podcasts, -23 for broadcast).  The
+        waveform is measured and multiplied by the gain that brings it to the target on the device, behind the vocoder and ahead of the format conversion and the
+        only copy to the host (ops.wave_normalize); the gain is limited so that no sample exceeds a peak of 1.0, so a quiet target is met exactly and a loud one
+        may fall short.  A silent result and one shorter than 0.4 s are returned as they are.  None is the call without the argument.
+        This is the statement of `seed`, `speed`, `sample_rate`, `encoding` and `loudness` for every method of every class of this module; the others say only what differs."""
         fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness))
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text), fmt, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
                               top_p=top_p, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None):
+                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None):
         """generate() for a text of ANY length: the reference stops at 1000 speech tokens (40 s) and cuts a longer text off.  The text is split into chunks of at
         most max_chars characters at paragraph, sentence and clause boundaries (text.split_text), the chunks are synthesised in text order as device batches
         (one: synthesize; several: the throughput schedule where the engine has it), and each batch's waveforms are trimmed of their leading / trailing silence and
@@ -657,14 +711,16 @@ class ChatterboxTTS(_LlamaTTS):
         end-of-speech token is `truncated`; one warning names them.  Every argument is checked before anything is launched; self.conds is written only as
         generate() writes it (audio_prompt_path).
         sample_rate, encoding: generate()'s; the whole waveform is converted once, after the watermark, and the segments' [start, stop) are then samples of the
-        converted result (ceil(s U / D)) while [src_start, src_stop) stay 24 kHz samples."""
+        converted result (ceil(s U / D)) while [src_start, src_stop) stay 24 kHz samples.
+        loudness: generate()'s, of the WHOLE assembled waveform measured as one signal (pauses included), so the chunks keep their relative level: one gain for
+        all of it, limited to a sample peak of 1.0, applied on the device ahead of the watermark and the conversion."""
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
-                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None):
+                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
         request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
         neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
@@ -675,10 +731,12 @@ class ChatterboxTTS(_LlamaTTS):
         then agree with that call's as far as batched and single arithmetic agree: the kernels pick their forms by row count, so this is not bit equality.
         speed (a number for every request, or a sequence of B numbers in [0.5, 2.0]; None entries are 1.0): request b's speaking rate, generate(speed=)'s; it
         travels with its request through the sub-batches like its seed.  sample_rate, encoding: generate()'s, ONE format for the call (checked first).
+        loudness (None, a number for every request, or a sequence of B numbers / Nones in [-50, -5]): request b's LUFS target, generate(loudness=)'s; a None entry
+        leaves that request as it is; it travels with its request through the sub-batches like its speed.
         This is the contract of generate_batch of every class of this module; the others say only what differs."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding))
+                                    ops.check_format(sample_rate, encoding), loudness)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                         cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, sample_rate=None, encoding=None, speed=1.0):
@@ -740,11 +798,11 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
         return [_language(lid, f" (request {k})") for k, lid in enumerate(langs)]
 
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None):
+                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
         """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
-        token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding: as there."""
+        token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness: as there."""
         fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness))
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text, lid), fmt, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
@@ -752,21 +810,21 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False, sample_rate=None, encoding=None):
+                      return_segments=False, sample_rate=None, encoding=None, loudness=None):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         fmt = ops.check_format(sample_rate, encoding)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt)
+        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None):
+                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
         speed, before the sampling arguments)."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding))
+                                    ops.check_format(sample_rate, encoding), loudness)
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
@@ -829,7 +887,9 @@ class ChatterboxTurboTTS(_TTS):
         return _norm_loudness(wav, sr, target_lufs)
 
     def prepare_conditionals(self, wav_fpath, exaggeration=0.0, norm_loudness=True):
-        """reference tts_turbo.py:241-270 (prompt > 5 s, optional loudness normalisation to -27 LUFS, 375 prompt tokens)."""
+        """reference tts_turbo.py:241-270 (prompt > 5 s, optional loudness normalisation to -27 LUFS, 375 prompt tokens).  norm_loudness: True is the reference's
+        (pyloudnorm on the host; skipped with its warning where that is missing), False none, "device" the same gain from this project's own BS.1770-4 meter on
+        the device (_norm_loudness_device): no third-party dependency, no ceiling."""
         self.conds = self._analyse(wav_fpath, exaggeration, norm_loudness=norm_loudness)
 
     def _set_exaggeration(self, exaggeration):
@@ -851,32 +911,32 @@ class ChatterboxTurboTTS(_TTS):
         return dict(max_gen_len=1000) if batch else {}
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
-                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None):
-        """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed, sample_rate, encoding: as
+                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
+        """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed, sample_rate, encoding, loudness: as
         ChatterboxTTS.generate."""
         fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness))
         self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
         self._warn_ignored(cfg_weight, exaggeration, min_p)
         return self._generate(self._text_ids(text), fmt, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                       top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False, sample_rate=None, encoding=None):
+                      return_segments=False, sample_rate=None, encoding=None, loudness=None):
         """ChatterboxTTS.generate_long on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other)."""
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), fmt,
-                                   norm_loudness=norm_loudness)
+                                   loudness, norm_loudness=norm_loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
-                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None):
+                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
         """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
         of B).  CFG, min_p and exaggeration are ignored with generate()'s warning.  Sub-batches run one after the other."""
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
-                                    ops.check_format(sample_rate, encoding), norm_loudness=norm_loudness)
+                                    ops.check_format(sample_rate, encoding), loudness, norm_loudness=norm_loudness)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
                         temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
@@ -956,11 +1016,11 @@ class ChatterboxVC(_Finish):
             s3_tokens = self._tokens_of(audio)
         return torch.as_tensor(s3_tokens).view(-1).long().cpu()
 
-    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None):
+    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
         """reference vc.py:83-104.  audio: a WAV path or a (waveform, sample_rate) pair.  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
-        are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding: as there."""
+        are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding, loudness: as there."""
         fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness))
         wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **seed_kw, **self._engine_format(fmt))
         return self._finish(wavs[0], fmt)
 
@@ -994,12 +1054,13 @@ class ChatterboxVC(_Finish):
 
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 
-    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None):
+    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
         """generate() for B conversions in one call: `audios` (WAV paths or (waveform, sample_rate) pairs) or `s3_tokens` (B id sequences); target voice per
         request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
         self.ref_dict.  Returns B CPU float32 tensors (1, n_b) at `.sr` in the caller's order; more than MAX_BATCH requests run as sub-batches in order of length.
         Never overwrites self.ref_dict.  seeds, speed: per request as ChatterboxTTS.generate_batch states them -- request b's noise is that of
-        generate(seed=seeds[b]), its speaking rate generate(speed=speed[b])'s; sample_rate, encoding: one format for the call."""
+        generate(seed=seeds[b]), its speaking rate generate(speed=speed[b])'s; sample_rate, encoding: one format for the call; loudness: a LUFS target for every
+        request or one number / None per request, as there."""
         fmt = ops.check_format(sample_rate, encoding)
         src = s3_tokens if s3_tokens is not None else audios
         assert src is not None, "give audios or s3_tokens"
@@ -1008,6 +1069,7 @@ class ChatterboxVC(_Finish):
         assert B >= 1, "empty batch"
         seeds = _batch_seeds(seeds, B)
         speed = ops.check_speed(speed, B)
+        loud = ops.check_loudness(loudness, B)
         if target_voice_paths is not None and ref_dicts is not None:
             raise ValueError("give target_voice_paths or ref_dicts, not both")
         if target_voice_paths is not None:
@@ -1023,7 +1085,8 @@ class ChatterboxVC(_Finish):
         out = [None] * B
         for idx in batch_plan([int(t.numel()) for t in toks], int(self.MAX_BATCH)):
             wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **({} if seeds is None else dict(seeds=_pick(seeds, idx))),
-                                         **({} if speed is None else dict(speed=_pick(speed, idx))), **self._engine_format(fmt))
+                                         **({} if speed is None else dict(speed=_pick(speed, idx))), **self._engine_format(fmt),
+                                         **({} if loud is None or all(v is None for v in _pick(loud, idx)) else dict(loudness=_pick(loud, idx))))
             for i, w in zip(idx, wavs):
                 out[i] = self._finish(w, fmt)
         return out

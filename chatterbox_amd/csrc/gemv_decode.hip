@@ -132,7 +132,9 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
             // A lane whose row is past M reads ROW 0's 16 bytes of its k group instead of its own pad row (its value is zeroed below either way):
             // a wave-level load then touches 64 M bytes instead of 1 KiB -- at M = 1 (Turbo / Nano at batch 1: profiles/r04_decode_launch_timeline_turbo.txt)
             // the x operand and the partial images cost 1/16 of the lines, and the packed images of small batches stop being "16 rows wide".
-            xp[t] = p.x + ((long)t * (p.K >> 5) + (kbeg >> 5)) * 512 + (xok[t] ? lane : (lane & 48)) * 4;
+            // A row tile WHOLLY past M is read from tile 0 (all its lanes are zeroed below): the image of M = 33 .. 48 rows holds three tiles, and the
+            // four-tile kernel that serves them would otherwise read K * 64 bytes past its end.
+            xp[t] = p.x + ((long)((MT > 2 && t * 16 >= p.M) ? 0 : t) * (p.K >> 5) + (kbeg >> 5)) * 512 + (xok[t] ? lane : (lane & 48)) * 4;
         else
             xp[t] = p.x + (long)(xok[t] ? m : 0) * p.ldx + kbeg + 8 * q;
     }
@@ -153,7 +155,8 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
     if constexpr (LN) {
 #pragma unroll
         for (int t = 0; t < MT; ++t)
-            piv[t] = gemv_ln_pivot<NP>(p.x + (long)t * (p.K >> 5) * 512, NP > 0 ? p.xpart + (long)t * (p.K >> 5) * 512 : nullptr, p.xpart_stride, p.K, xok[t] ? c : 0);
+            piv[t] = gemv_ln_pivot<NP>(p.x + (long)((MT > 2 && t * 16 >= p.M) ? 0 : t) * (p.K >> 5) * 512, NP > 0 ? p.xpart + (long)t * (p.K >> 5) * 512 : nullptr, p.xpart_stride, p.K,
+                                       xok[t] ? c : 0);  // (a tile wholly past M: tile 0, as xp[t])
     }
     // ---- epilogue operands requested FIRST (opt-in: cbx_gemv_t.flags & CBX_GEMV_PRE_EPI).  The element(s) a thread finishes after the reduction are known now; its
     // residual, bias and LayerNorm-fold constants do not depend on the contraction, so their loads go out with the first weight batch instead

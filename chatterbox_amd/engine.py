@@ -71,10 +71,17 @@ def _valid_tokens(toks):
 
 def _checked_job(job):
     """A job of synthesize_pipelined with its optional keys checked as synthesize checks its arguments: seeds (ops.request_seeds; not together with the job's
-    generator), speed (ops.check_speed), join (ops.check_join), format (ops.check_format_arg).  A join of None is dropped: from here on `"join" in job` says whether
-    the job is joined; likewise a format that is None or the default (24 kHz fp32)."""
+    generator), speed (ops.check_speed), join (ops.check_join), format (ops.check_format_arg), loudness (ops.check_loudness; not together with a join).  A join of
+    None is dropped: from here on `"join" in job` says whether the job is joined; likewise a format that is None or the default (24 kHz fp32) and a loudness that
+    normalises no utterance."""
     n = len(job["text_tokens"])
-    job = {k: v for k, v in job.items() if k not in ("join", "format") or v is not None}
+    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness") or v is not None}
+    if "loudness" in job:
+        job["loudness"] = ops.check_loudness(job["loudness"], n)
+        if job["loudness"] is None:
+            del job["loudness"]
+        elif "join" in job:
+            raise ValueError(LOUDNESS_JOIN)
     if "format" in job:
         job["format"] = ops.check_format_arg(job["format"])
         if job["format"] is None:
@@ -88,6 +95,9 @@ def _checked_job(job):
     return job
 
 
+LOUDNESS_JOIN = "loudness together with join: a long text is normalised as a whole, after its pieces are assembled (generate_long(loudness=))"
+
+
 class S3GenEngine:
     """The S3Gen half of every engine -- flow matching (FlowEngine) and vocoder (HiFTEngine) of one checkpoint on one device -- and what is built on the two alone:
     vocode, vocode_stream and the streams and kernel forms of the overlapped schedules.  On its own it is the engine of voice conversion (no T3);
@@ -99,11 +109,12 @@ class S3GenEngine:
         self.flow = FlowEngine(s3gen_sd, self.dev, meanflow=meanflow)
         self.hift = HiFTEngine(s3gen_sd, self.dev)
         self.last_timing = {}
+        self.last_loudness = None  # the (B, 4) float64 device tensor {L, peak, gain, blocks used} of the last call with loudness=; not synchronised
 
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None, seeds=None, speed=None, join=None, format=None):
+               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
@@ -125,12 +136,21 @@ class S3GenEngine:
         ops.wave_format launch (cbx_wave_format_f32) behind the vocoder, on the stream that owns the waveforms, resamples the B cut waveforms and encodes them; the
         call returns them as views (float32, int16 or uint8) of one packed buffer, utterance b with ops.formatted_len(n_b, sample_rate) elements.  With a join the
         launch converts the joined piece instead: the join writes into a zeroed buffer, so converting all of it gives, in [0, formatted_len(total)), exactly the
-        conversion of the piece's [0, total); the piece dict gains `formatted` (that buffer) and `format`; layout and edges stay in 24 kHz samples."""
+        conversion of the piece's [0, total); the piece dict gains `formatted` (that buffer) and `format`; layout and edges stay in 24 kHz samples.
+        loudness (None, or no utterance with a target: this call, launch for launch; else ops.check_loudness's list -- a number or B numbers / Nones in [-50, -5]
+        LUFS): ops.wave_normalize behind the vocoder, on the stream that owns the waveforms -- the BS.1770-4 integrated loudness of each cut waveform (after the
+        speed stretch has shaped it) is measured and the waveform multiplied in place by the gain that brings it to its target, limited so that no sample exceeds
+        1.0; a None entry, a silent utterance and one shorter than 0.4 s keep their samples.  It runs ahead of the format launch, whose s16 / G.711 store therefore
+        sees the normalised signal and does not clip.  The stats {L, peak, gain, blocks used} of the call stay on the device as self.last_loudness; nothing is
+        synchronised.  Not together with a join (ValueError): a long text is normalised as a whole."""
         B = len(speech_tokens)
         seeds = ops.request_seeds(seeds, B, generator)
         speed = ops.check_speed(speed, B)
         join = ops.check_join(join, B)
         fmt = ops.check_format_arg(format)
+        loud = ops.check_loudness(loudness, B)
+        if loud is not None and join is not None:
+            raise ValueError(LOUDNESS_JOIN)
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
         tok = torch.zeros(B, Nmax, dtype=torch.long)
@@ -178,6 +198,9 @@ class S3GenEngine:
             if speed is not None:
                 frames = ops.scaled_len(frames, speed[b])
             out.append(wav[b, : frames * (SAMPLES_PER_TOKEN // 2)])
+        if loud is not None:
+            with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
+                self.last_loudness = ops.wave_normalize(out, loud)
         if join is not None and fmt is None:
             if hift_stream is not None:
                 with torch.cuda.stream(hift_stream):
@@ -263,7 +286,7 @@ class ChatterboxEngine(S3GenEngine):
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None):
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
@@ -271,11 +294,16 @@ class ChatterboxEngine(S3GenEngine):
         speed: None, a number or B numbers in [0.5, 2.0]: the speaking rate of vocode(speed=); T3 and its tokens do not depend on it.
         join: None, or vocode(join=)'s dict -- the B utterances are consecutive chunks of one text; the call then returns (piece, speech_tokens) with piece =
         ops.piece_on_host's dict (wav = the joined piece on the device, offsets, total, edges, n) plus truncated = [B bools: T3 spent its budget without EOS].
-        format: None, or vocode(format=)'s dict -- the waveforms (the joined piece's `wav`) come back at that sample rate in that encoding."""
+        format: None, or vocode(format=)'s dict -- the waveforms (the joined piece's `wav`) come back at that sample rate in that encoding.
+        loudness: None, a number or B numbers / Nones in [-50, -5] LUFS -- vocode(loudness=): every utterance with a target is brought to it on the device (sample
+        peak limited to 1.0); not together with a join."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
         join = ops.check_join(join, len(text_tokens))
         fmt = ops.check_format_arg(format)
+        loud = ops.check_loudness(loudness, len(text_tokens))
+        if loud is not None and join is not None:
+            raise ValueError(LOUDNESS_JOIN)
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
@@ -286,7 +314,7 @@ class ChatterboxEngine(S3GenEngine):
         st = _valid_tokens(toks)
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
                               drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)),
-                              **({} if fmt is None else dict(format=fmt)))
+                              **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)))
         if join is not None:  # (the record's copy waits for the two launches behind the vocoder)
             wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks))
         self.last_timing["total_s"] = time.perf_counter() - t0
@@ -305,6 +333,7 @@ class ChatterboxEngine(S3GenEngine):
         sampling draws of a repeatable job are injected as `uniforms`: T3 is enqueued by another host thread), or `seeds` (one int per utterance, or one int for all:
         every draw of the job that is not injected, as synthesize(seeds=); not together with a generator), or `speed` (a number or one per utterance: vocode(speed=)),
         or `format` (vocode(format=)'s dict: the job's audio is converted on the device ahead of its copies, which then carry the encoded samples),
+        or `loudness` (vocode(loudness=): a number or one number / None per utterance; the meter and the gain run behind the vocoder on its stream; not with a join),
         or `join` (vocode(join=)'s dict: the job's utterances are consecutive chunks of one text; `wavs` is then synthesize(join=)'s piece dict with `wav` on the host.
         The two launches run behind the vocoder on its stream, the piece leaves the device as ONE pinned copy plus one of its small records where a job without
         it makes one copy per utterance, and it is sliced after the event this schedule waits for anyway: no host synchronisation is added).
@@ -348,7 +377,7 @@ class ChatterboxEngine(S3GenEngine):
             is called exactly as before there was one)"""
             wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
                                   speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10), drop_last_token=kw.get("drop_last_token", True), sync=False,
-                                  **({k: job[k] for k in ("join", "format") if k in job}))
+                                  **({k: job[k] for k in ("join", "format", "loudness") if k in job}))
             return wavs
 
         def to_host(job, wavs, pinned):
@@ -959,15 +988,18 @@ class TurboEngine(S3GenEngine):
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
         for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=);
         speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=); join: None, or vocode(join=)'s dict -- the call then returns
-        ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict."""
+        ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict; loudness: None, or vocode(loudness=)'s targets (not with a join)."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
         join = ops.check_join(join, len(text_tokens))
         fmt = ops.check_format_arg(format)
+        loud = ops.check_loudness(loudness, len(text_tokens))
+        if loud is not None and join is not None:
+            raise ValueError(LOUDNESS_JOIN)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                 repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
@@ -976,7 +1008,7 @@ class TurboEngine(S3GenEngine):
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed,
-                              **({} if join is None else dict(join=join)), **({} if fmt is None else dict(format=fmt)))
+                              **({} if join is None else dict(join=join)), **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)))
         if join is not None:
             wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks, max_gen_len))
         self.last_timing["total_s"] = time.perf_counter() - t0

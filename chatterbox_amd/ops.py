@@ -1269,6 +1269,102 @@ class WaveFormatStream:
         return [self.packed[a: a + c] for a, c in self.spans]
 
 
+# ----------------------------------------------------------------------------- loudness: BS.1770 meter, gain to a LUFS target (wave_loudness.hip)
+LOUDNESS_MIN, LOUDNESS_MAX = -50.0, -5.0   # LUFS targets a caller may ask for
+_LOUDNESS_FILTERS = {}
+
+
+def loudness_filter(fs=WAVE_IN_RATE):
+    """The K-weighting of ITU-R BS.1770-4 at sample rate fs as pyloudnorm.Meter builds it (RBJ biquads, fp64 NumPy, normalised by a0): a high shelf of +4 dB,
+    Q = 1 / sqrt 2 at 1500 Hz, then a high pass of Q = 0.5 at 38 Hz.  -> dict(fs, hop = fs / 10 samples, coef = 10 doubles b0 b1 b2 a1 a2 of the shelf, then of
+    the high pass: cbx_wave_loudness_f32's `coef`).  fs must be a multiple of 10.  Built once per rate."""
+    import numpy as np
+    fs = int(fs)
+    if fs not in _LOUDNESS_FILTERS:
+        if fs < 10 or fs % 10:
+            raise ValueError(f"loudness_filter: fs = {fs}: a tenth of a second must be a whole number of samples")
+        A = 10.0 ** (4.0 / 40.0)
+        w0 = 2.0 * np.pi * (1500.0 / fs)
+        al, cs = np.sin(w0) / (2.0 * (1.0 / np.sqrt(2.0))), np.cos(w0)
+        shelf = np.array([A * ((A + 1) + (A - 1) * cs + 2 * np.sqrt(A) * al), -2 * A * ((A - 1) + (A + 1) * cs), A * ((A + 1) + (A - 1) * cs - 2 * np.sqrt(A) * al),
+                          (A + 1) - (A - 1) * cs + 2 * np.sqrt(A) * al, 2 * ((A - 1) - (A + 1) * cs), (A + 1) - (A - 1) * cs - 2 * np.sqrt(A) * al], dtype=np.float64)
+        w0 = 2.0 * np.pi * (38.0 / fs)
+        al, cs = np.sin(w0) / (2.0 * 0.5), np.cos(w0)
+        hp = np.array([(1 + cs) / 2, -(1 + cs), (1 + cs) / 2, 1 + al, -2 * cs, 1 - al], dtype=np.float64)
+        coef = np.concatenate([np.delete(q / q[3], 3) for q in (shelf, hp)])
+        _LOUDNESS_FILTERS[fs] = dict(fs=fs, hop=fs // 10, coef=coef)
+    return _LOUDNESS_FILTERS[fs]
+
+
+def check_loudness(value, B, name="loudness"):
+    """A `loudness` argument as a list of B entries -- a float (the LUFS target of that request) or None (that request is left alone) --, or None when no request
+    is normalised.  A number serves every request; anything else must be a list or tuple of exactly B numbers or Nones, each number finite and in [-50, -5].  A
+    bool or a non-number is a TypeError; a non-finite or out-of-range value and a wrong length are ValueErrors -- raised before anything is launched."""
+    import math
+    import numbers
+    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    if value is None:
+        return None
+    if one(value):
+        value = [value] * B
+    elif not isinstance(value, (list, tuple)):
+        raise TypeError(f"{name}: expected None, a number or a list of {B} numbers, got {type(value).__name__}")
+    if len(value) != B:
+        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
+    out = []
+    for k, v in enumerate(value):
+        if v is not None:
+            if not one(v):
+                raise TypeError(f"{name}[{k}]: expected None or a number, got {type(v).__name__}")
+            v = float(v)
+            if not math.isfinite(v) or not LOUDNESS_MIN <= v <= LOUDNESS_MAX:
+                raise ValueError(f"{name}[{k}] = {v}: a loudness target is a finite number of LUFS in [{LOUDNESS_MIN}, {LOUDNESS_MAX}]")
+        out.append(v)
+    return None if all(v is None for v in out) else out
+
+
+def wave_loudness(rows, target=None, ceiling=1.0, fs=WAVE_IN_RATE):
+    """cbx_wave_loudness_f32 on the current stream: the BS.1770-4 integrated loudness and the sample peak of every row (_wave_rows: 1 .. 64 1-D fp32 views of ONE
+    allocation, sampled at fs), and the gain that brings it to its target.  target: None (measure only), a number, or R numbers / Nones (None: gain 1); no range is
+    imposed here (check_loudness is the public arguments' check).  ceiling: the sample peak the gain may not exceed (None or 0: no limit).  Returns (stats, gain):
+    stats (R, 4) float64 {L in LUFS (-inf: silence or shorter than 0.4 s), peak, gain in fp64, blocks used} and gain (R,) float32, both on the device; nothing is
+    synchronised (include/cbx.h states the definition)."""
+    base, offs, lens = _wave_rows(rows, "wave_loudness")
+    R, dev, f = len(lens), rows[0].device, loudness_filter(fs)
+    if target is None or not isinstance(target, (list, tuple)):
+        target = [target] * R
+    if len(target) != R:
+        raise ValueError(f"wave_loudness: {len(target)} targets for {R} rows")
+    tg = (ctypes.c_double * R)(*[float("nan") if t is None else float(t) for t in target])
+    coef = (ctypes.c_double * 10)(*f["coef"].tolist())
+    stats = torch.empty(R, 4, dtype=torch.float64, device=dev)
+    gain = torch.empty(R, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(1, 6 * R * -(-max(lens) // f["hop"])), dtype=torch.float64, device=dev)
+    check(lib.cbx_wave_loudness_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, ctypes.addressof(coef), f["hop"], ctypes.addressof(tg),
+                                    0.0 if ceiling is None else float(ceiling), _p(stats), _p(gain), _p(ws), ws.numel(), _stream()), "cbx_wave_loudness_f32")
+    return stats, gain
+
+
+def wave_gain(rows, gain):
+    """cbx_wave_gain_f32 on the current stream: row r times gain[r] (an (R,) fp32 device tensor), in place, one launch.  Returns rows."""
+    base, offs, lens = _wave_rows(rows, "wave_gain")
+    R = len(lens)
+    assert gain.dtype == torch.float32 and gain.numel() == R and gain.is_contiguous() and gain.device == rows[0].device, "wave_gain: gain is (R,) fp32 on the rows' device"
+    check(lib.cbx_wave_gain_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, _p(gain), _stream()), "cbx_wave_gain_f32")
+    return rows
+
+
+def wave_normalize(rows, target, ceiling=1.0, fs=WAVE_IN_RATE):
+    """wave_loudness + wave_gain: every row with a target is brought to it in place (limited to a sample peak of `ceiling`); rows whose target is None, silent rows
+    and rows shorter than 0.4 s keep their samples.  Returns the (R, 4) stats.  Five launches, no host synchronisation."""
+    rows = list(rows)
+    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+        return torch.tensor([[float("-inf"), 0.0, 1.0, 0.0]] * len(rows), dtype=torch.float64).to(rows[0].device)
+    stats, gain = wave_loudness(rows, target, ceiling, fs)
+    wave_gain(rows, gain)
+    return stats
+
+
 def hift_stft(s, spec, sample_lens=None):
     B, L = s.shape
     check(lib.cbx_hift_stft_f32(_p(s), _p(spec), _p(sample_lens), B, L, spec.stride(1), _stream()), "cbx_hift_stft_f32")

@@ -869,6 +869,37 @@ int cbx_wave_join_f32(const float* wav, const long* row_off, const int* row_len,
 int cbx_wave_format_f32(const float* wav, const long* row_off, const int* row_len, int R, int rate, int encoding, const float* tab, int U, int T, const long* n0,
                         const long* m0, const int* fin, const float* hist_in, float* hist_out, void* out, const long* out_off, long out_cap, void* stream);
 
+/* ---- loudness: measure the integrated loudness of the rows of a batch, derive the gain to a LUFS target, apply it in place (added after ABI v16 without a
+ * version step: new functions only).  The reference levels only Turbo's voice prompt, on the host with pyloudnorm (tts_turbo.py:223-239: norm_loudness to -27 LUFS);
+ * its outputs keep whatever level the vocoder gives them.  Rows as cbx_wave_join_f32 takes them: R in [1, 64] rows of row_len[r] floats at wav + row_off[r] (HOST
+ * arrays; 4-byte alignment is enough).
+ * Definition: ITU-R BS.1770-4 integrated loudness of one channel at sample rate fs.
+ *   K-weighting: two biquads in cascade, coefficients built by the CALLER in fp64 with the RBJ forms pyloudnorm.Meter uses -- high shelf G = +4 dB, Q = 1 / sqrt 2,
+ *     fc = 1500 Hz; high pass Q = 0.5, fc = 38 Hz; both normalised by a0 --, coef[10] = b0 b1 b2 a1 a2 of the shelf, then of the high pass (HOST doubles).  At 24 kHz
+ *     the high pass has a double pole at ~0.9901: state and sums are fp64 (an fp32 recurrence loses ~5e-3 LU).
+ *   Segments: hop = fs / 10 samples (an integer); segment s covers [s hop, (s + 1) hop) for s < S = floor(n / hop); E_s = the fp64 sum of squares of the filtered
+ *     signal over segment s.
+ *   Blocks: z_j = (E_j + E_(j+1) + E_(j+2) + E_(j+3)) / (4 hop) for j <= S - 4, l_j = -0.691 + 10 log10(z_j).  The incomplete block at the end is not used (the
+ *     Recommendation's rule; pyloudnorm counts round() blocks and may add a partial one -- we follow the Recommendation; the difference is not measured).
+ *   Gates: absolute l_j >= -70; relative G = -0.691 + 10 log10(mean z over the absolute gate) - 10; L = -0.691 + 10 log10(mean z over the blocks with l_j >= -70
+ *     and l_j > G); L = -inf when no block passes or n < 4 hop.
+ *   Peak: max |x| over [0, n) (0 for n = 0; NaN when the row holds a NaN).
+ *   Gain, in fp64: g = 10^((target - L) / 20); if ceiling > 0 and peak g > ceiling then g = ceiling / peak; g = 1 when target is NaN (measure only) or when L,
+ *     peak or g is not finite.  The stored gain is (float)g; the applied signal is x[i] * g, one fp32 multiply, in place.
+ * cbx_wave_loudness_f32: target: R HOST doubles.  stats: (R, 4) device doubles {L, peak, g, blocks used}; gain: R device floats.  The filter is run exactly, not
+ * from a warm-up: every 1/64th of a segment from zero state, a wave-level scan of the 4-vector states with powers of the 4 x 4 transition matrix (built by the entry
+ * on the host, passed by value), a chain over each row's segments, then a second pass from the true states (wave_loudness.hip).  A row's segments from the first one
+ * whose E is not finite on count as NaN, and a block with a NaN passes no gate.  Fixed reduction order, independent of the grid and of the rows' alignment, no
+ * floating-point atomics: the numbers are reproducible run to run.  Four launches (one when every row is empty), nothing synchronises the host.
+ * ws: device workspace of ws_cap >= 6 * R * ceil(max_r n_r / hop) doubles (not NULL).
+ * -22 before any launch: a null pointer, R outside [1, 64], a negative length or offset, hop < 1, a coefficient that is not finite, a workspace that is too small. */
+int cbx_wave_loudness_f32(const float* wav, const long* row_off, const int* row_len, int R, const double* coef, int hop, const double* target, double ceiling,
+                          double* stats, float* gain, double* ws, long ws_cap, void* stream);
+/* cbx_wave_gain_f32: wav_r[i] = wav_r[i] * gain[r] for i < n_r, ONE launch (none when every row is empty); gain: R device floats (cbx_wave_loudness_f32's).
+ * 16-byte accesses inside a row where alignment allows, 4-byte accesses at the ragged ends; nothing outside the rows is touched.
+ * -22 before any launch: a null pointer, R outside [1, 64], a negative length or offset. */
+int cbx_wave_gain_f32(float* wav, const long* row_off, const int* row_len, int R, const float* gain, void* stream);
+
 /* ---- voice-prompt / voice-conversion front-end ----
  * Contractions (framed DFT as a GEMM over overlapping waveform rows, mel filterbanks, Conv1d/Conv2d-as-Toeplitz, attention, LSTM
  * projections) use cbx_gemm_f32 / cbx_flash_attn_f32 / cbx_gemv_f32; these are the remaining element-wise / reduction passes. */
