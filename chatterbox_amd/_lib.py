@@ -293,6 +293,7 @@ _SIGS = {
     "cbx_wave_gain_f32": ([c_f, c_f, c_f, c_int, c_f, c_f], c_int),
     "cbx_hift_stft_f32": ([c_f, c_f, c_f, c_int, c_long, c_long, c_f], c_int),
     "cbx_hift_istft_f32": ([c_f, c_f, c_int, c_long, c_long, c_float, c_int, c_f], c_int),
+    "cbx_hift_istft_rows_f32": ([c_f, c_f, c_f, c_int, c_long, c_long, c_float, c_int, c_f], c_int),
 }
 
 

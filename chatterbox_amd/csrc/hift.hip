@@ -7,6 +7,10 @@
 //  * STFT(16, hop 4, hann, center/reflect) of the excitation as a direct 16-point DFT per frame.
 //  * conv_post head -> magnitude/phase -> inverse DFT + windowed overlap-add + envelope normalisation + clamp,
 //    fused; spectra of the ~68 frames a 256-sample block touches are converted once into LDS.
+//    ROW ENDS (ragged batch, frame_lens): row b owns frames [0, frame_lens[b]) and samples [0, 4 (frame_lens[b] - 1)).  A sample overlap-adds
+//    (signal and envelope) the frames of its own row only -- frames at or beyond frame_lens[b] are never read, whatever they hold -- so every owned
+//    sample has the bits of a batch-1 launch on the row cut to frame_lens[b] frames; samples at or beyond the row's length are written as 0.0f
+//    (frame_lens[b] < 2: the whole row; frame_lens[b] > frames counts as frames).
 #include "cbx_common.h"
 
 namespace {
@@ -108,12 +112,15 @@ __global__ void stft_kernel(const float* __restrict__ s, float* __restrict__ spe
 constexpr int IS_BLK = 256;
 constexpr int IS_FR = IS_BLK / 4 + 5;
 
-__global__ __launch_bounds__(IS_BLK) void istft_kernel(const float* __restrict__ x, float* __restrict__ wav, long frames,
-                                                      long ldx, float clampv, int fade_n) {
+__global__ __launch_bounds__(IS_BLK) void istft_kernel(const float* __restrict__ x, float* __restrict__ wav, const int* __restrict__ frame_lens,
+                                                      long frames, long ldx, float clampv, int fade_n) {
     __shared__ float re[IS_FR][9];
     __shared__ float im[IS_FR][9];
     const int b = blockIdx.y;
     const long out_len = 4 * (frames - 1);
+    long fb = frames;  // frames of THIS row: the overlap-add stops at its last one
+    if (frame_lens) fb = min(max((long)frame_lens[b], 0L), frames);  // device memory: the host cannot refuse a value, so every value is defined
+    const long row_len = fb >= 2 ? 4 * (fb - 1) : 0;                 // fewer than 2 frames: the row owns no sample
     const long m0 = (long)blockIdx.x * IS_BLK;
     // frames touched by padded positions q in [m0+8, m0+8+255]: t in [ceil((q-15)/4), floor(q/4)]
     long t_lo = (m0 + 8 - 15 + 3) / 4;
@@ -121,7 +128,7 @@ __global__ __launch_bounds__(IS_BLK) void istft_kernel(const float* __restrict__
     const int tid = threadIdx.x;
     if (tid < IS_FR) {
         long t = t_lo + tid;
-        if (t < frames) {
+        if (t < fb) {
             const float* xr = x + ((long)b * frames + t) * ldx;
 #pragma unroll
             for (int f = 0; f < 9; ++f) {
@@ -135,10 +142,14 @@ __global__ __launch_bounds__(IS_BLK) void istft_kernel(const float* __restrict__
     __syncthreads();
     const long m = m0 + tid;
     if (m >= out_len) return;
+    if (m >= row_len) {  // beyond the row: defined as silence
+        wav[(long)b * out_len + m] = 0.0f;
+        return;
+    }
     const long q = m + 8;
     float acc = 0.f, env = 0.f;
     long t_hi = q / 4;
-    if (t_hi > frames - 1) t_hi = frames - 1;
+    if (t_hi > fb - 1) t_hi = fb - 1;
     long t_first = (q - 15 + 3) / 4;
     if (q - 15 < 0) t_first = 0;
     for (long t = t_first; t <= t_hi; ++t) {
@@ -192,11 +203,16 @@ extern "C" int cbx_hift_stft_f32(const float* s, float* spec, const int* sample_
     return cbx_check_launch("hift_stft");
 }
 
-extern "C" int cbx_hift_istft_f32(const float* x, float* wav, int B, long frames, long ldx, float clampv, int fade_n,
-                                  void* stream) {
+extern "C" int cbx_hift_istft_rows_f32(const float* x, float* wav, const int* frame_lens, int B, long frames, long ldx, float clampv, int fade_n,
+                                       void* stream) {
     CBX_REQUIRE(x && wav && B > 0 && frames >= 2 && ldx >= 18, "hift_istft: bad args");
+    CBX_REQUIRE(fade_n == 0 || fade_n >= 2, "hift_istft: fade_n is 0 (no fade) or at least 2 (the ramp divides by fade_n - 1)");
     long out_len = 4 * (frames - 1);
     dim3 grid((unsigned)((out_len + IS_BLK - 1) / IS_BLK), B);
-    hipLaunchKernelGGL(istft_kernel, grid, dim3(IS_BLK), 0, (hipStream_t)stream, x, wav, frames, ldx, clampv, fade_n);
+    hipLaunchKernelGGL(istft_kernel, grid, dim3(IS_BLK), 0, (hipStream_t)stream, x, wav, frame_lens, frames, ldx, clampv, fade_n);
     return cbx_check_launch("hift_istft");
+}
+
+extern "C" int cbx_hift_istft_f32(const float* x, float* wav, int B, long frames, long ldx, float clampv, int fade_n, void* stream) {
+    return cbx_hift_istft_rows_f32(x, wav, nullptr, B, frames, ldx, clampv, fade_n, stream);
 }

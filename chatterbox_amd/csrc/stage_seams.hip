@@ -275,7 +275,7 @@ extern "C" int cbx_hift_decode(const cbx_hift_t* d, void* stream) {
     p.x = x, p.w = d->conv_post_w, p.bias = d->conv_post_b, p.out = d->post, p.lens = ln[3], p.Tin = p.Tout = L3, p.ldx = 64, p.xs = L3 * 64, p.ldo = 32, p.os = L3 * 32;
     p.N = 18, p.taps = 7, p.cin = 64, p.pad_left = 3;
     if ((rc = h.run(p))) return rc;
-    return cbx_hift_istft_f32(d->post, d->wav, B, L3, 32, 0.99f, d->fade ? 480 : 0, stream);
+    return cbx_hift_istft_rows_f32(d->post, d->wav, ln[3], B, L3, 32, 0.99f, d->fade ? 480 : 0, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ S3Gen token encoder

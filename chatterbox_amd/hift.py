@@ -6,8 +6,9 @@ Channel-last activations (B, time, C); every Conv1d / ConvTranspose1d is the imp
     the (T*s, Cout) upsampled tensor (no scatter, no zero-stuffing);
   * Snake / leaky-ReLU / ELU ride in GEMM epilogues (second output = activation the NEXT conv needs), the residual
     adds, the source fusion `x + si` and the 1/3 average of the three ResBlocks are epilogue accumulations;
-  * ragged batches: non-causal convs zero-fill beyond each row's own length (`lens`), so every valid sample equals
-    the batch-1 reference value.
+  * ragged batches: non-causal convs zero-fill beyond each row's own length (`lens`) and the iSTFT overlap-adds the
+    row's own 120 n + 1 frames only, so every valid sample -- the last three of a shorter row included, which the
+    frame after the row would otherwise reach -- equals the batch-1 reference value; samples at or beyond 480 n are 0.
 """
 import os
 
@@ -219,7 +220,7 @@ class HiFTEngine:
         post = torch.zeros(B, L3, 32, device=dev)
         ops.conv1d(x, self.conv_post[0], post, taps=7, cin=64, bias=self.conv_post[1], pad_left=3, lens=ln[3])
         wav = f(B, 480 * T)
-        ops.hift_istft(post, wav, 0.99, 480 if fade else 0)
+        ops.hift_istft(post, wav, 0.99, 480 if fade else 0, frame_lens=ln[3])
         return wav
 
     @ops.on_device

@@ -1371,9 +1371,15 @@ def hift_stft(s, spec, sample_lens=None):
     return spec
 
 
-def hift_istft(x, wav, clamp=0.99, fade_n=0):
+def hift_istft(x, wav, clamp=0.99, fade_n=0, frame_lens=None):
+    """x (B, frames, ld >= 18) -> wav (B, 4 (frames - 1)).  frame_lens (B,) int32 on x's device: row b owns frame_lens[b] frames; its samples equal the
+    batch-1 launch on the cut row, everything beyond them is 0 (include/cbx.h cbx_hift_istft_rows_f32)."""
     B, frames = x.shape[0], x.shape[1]
-    check(lib.cbx_hift_istft_f32(_p(x), _p(wav), B, frames, x.stride(1), clamp, fade_n, _stream()), "cbx_hift_istft_f32")
+    if frame_lens is None:
+        check(lib.cbx_hift_istft_f32(_p(x), _p(wav), B, frames, x.stride(1), clamp, fade_n, _stream()), "cbx_hift_istft_f32")
+        return wav
+    assert frame_lens.dtype == torch.int32 and frame_lens.numel() == B and frame_lens.is_contiguous() and frame_lens.device == x.device, "hift_istft: frame_lens is (B,) int32 on x's device"
+    check(lib.cbx_hift_istft_rows_f32(_p(x), _p(wav), _p(frame_lens), B, frames, x.stride(1), clamp, fade_n, _stream()), "cbx_hift_istft_rows_f32")
     return wav
 
 

@@ -748,6 +748,7 @@ typedef struct cbx_hift_resblock_t {
 /* HiFTGenerator.decode (hifigan.py:412-444) for B rows: STFT of the source s, conv_pre, 3 x [leaky ReLU, ConvTranspose1d (phase-packed 3-tap form, cbx_gemm_t),
  * + source_resblock(source_down(STFT)), mean of 3 ResBlocks], conv_post, iSTFT (+ S3Gen's trim_fade when fade).  mel (B, T, 80) channel-last, s (B, 480 T),
  * wav (B, 480 T).  lens: NULL or [5][B] = valid rows of {mel, stage 1, stage 2, stage 3 = STFT frames, source samples} = {n, 8 n, 40 n, 120 n + 1, 480 n}.
+ * With lens, wav[b][m] for m >= 480 n is 0 and every sample below equals the B = 1 call on the cut row (cbx_hift_istft_rows_f32).
  * precision: cbx_gemm_t.precision of every conv.  Workspaces: spec, post (B, 120 T + 1, 32); x0 (B, T, 512); xs .. nxt[1]: (B, 120 T + 1, 64) floats each
  * (the widest stage; stages 1 and 2 use a prefix).  Same contract as cbx_cfm_solve. */
 typedef struct cbx_hift_t {
@@ -783,6 +784,16 @@ int cbx_hift_stft_f32(const float* s, float* spec, const int* sample_lens, int B
 /* x[b][frame][0..8] log-magnitude, [9..17] phase pre-sin (conv_post output); fade_n>0 applies S3Gen trim_fade. */
 int cbx_hift_istft_f32(const float* x, float* wav, int B, long frames, long ldx, float clamp, int fade_n,
                        void* stream);
+/* The same for a RAGGED batch (added after ABI v16 without a version step: a new function only; cbx_hift_istft_f32 is this call with frame_lens = NULL).
+ * frame_lens: NULL (every row has `frames` frames) or [B] ints in device memory.  Row b owns frames [0, frame_lens[b]) and samples [0, 4 (frame_lens[b] - 1)):
+ *   - an owned sample overlap-adds, in the signal and in the window envelope, the frames of its own row only; frames at or beyond frame_lens[b] and columns
+ *     18 .. ldx - 1 are never read, whatever they hold.  It therefore has the bits of a B = 1 call on the row cut to frame_lens[b] frames -- torch.istft of the
+ *     cut row -- up to and including its last three samples, which a neighbour frame beyond the row would otherwise reach;
+ *   - wav[b][m] for 4 (frame_lens[b] - 1) <= m < 4 (frames - 1) is written as exactly 0.0f.  frame_lens[b] < 2: the row owns no sample (all 0.0f);
+ *     frame_lens[b] > frames counts as frames.  (The values live in device memory and the callee never synchronises, so none of them can be refused.)
+ * wav (B, 4 (frames - 1)).  fade_n is 0 or >= 2 (the ramp divides by fade_n - 1): 1 is refused with CBX_EINVAL before anything is launched, by both entries.
+ * cbx_hift_decode passes its lens row 3 (120 n + 1), so the tail of a shorter row of a batch equals its batch-1 synthesis. */
+int cbx_hift_istft_rows_f32(const float* x, float* wav, const int* frame_lens, int B, long frames, long ldx, float clamp, int fade_n, void* stream);
 
 /* ---- counter-based device RNG: per-request seeds (added after ABI v16 without a version step: a new function only) ----
  * Replaces, for a request that carries a seed, the draws the reference takes from torch's sequential generator: the draw inside torch.multinomial of the

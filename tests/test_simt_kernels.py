@@ -213,6 +213,29 @@ def test_range_edge_bodies_on_the_emulator(emu, name, args):
     getattr(test_range_edges_gpu, name)(CPU, *args)
 
 
+# tests/test_vocoder_edges_gpu.py (vocoder_edges_common.py: the HiFT tail kernels and the conv forms of the vocoder at their edge shapes) at emulator sizes: the iSTFT
+# geometry set and the ragged iSTFT (per-row frame counts: rows equal solo launches bit for bit, zeros beyond), the value case, the refusals, the f0 thresholds, the
+# minimum STFT lengths, every row of the conv table at every precision it lists (the rows longer than T = 140 too: each takes under 2 s here).  The grid-stride second laps are left to the GPU.
+def _vocoder_edge_cases():
+    import vocoder_edges_common as V
+    cases = [("check_istft_geometry", (fr, B, ldx)) for fr in V.ISTFT_FRAMES for B, ldx in ((1, 18), (3, 32))]
+    cases += [("check_istft_geometry", (66, 1, 32)), ("check_istft_geometry", (66, 3, 18))]
+    cases += [("check_istft_ragged", ()), ("check_istft_values", ()), ("check_istft_refusals", ()), ("check_source_thresholds", ())]
+    cases += [("check_stft", (2, L, ld)) for L in (16, 20) for ld in (18, 32)]
+    cases += [("check_conv_case", (c["name"], p)) for c in V.CONV_CASES for p in c["precisions"]]
+    return cases
+
+
+_VOCODER = _vocoder_edge_cases()
+
+
+@pytest.mark.parametrize("name,args", _VOCODER, ids=[f"{n}{list(a)}" for n, a in _VOCODER])
+def test_vocoder_edge_bodies_on_the_emulator(emu, name, args):
+    import vocoder_edges_common as V
+    from chatterbox_amd import ops
+    getattr(V, name)(ops, CPU, *args)
+
+
 @pytest.mark.parametrize("tile,persist", [(0, 1), (1, 0), (3, 8), (7, 1), (12, 0), (15, 8), (21, 1), (24, 8), (26, 0), (28, 1), (31, 8), (32, 1), (33, 0), (34, 8), (36, 1)])
 def test_gemm_planes_tiles_small(emu, tile, persist):
     """tests/test_planes_gpu.py::test_gemm_planes_linear_tiles at emulator-sized shapes: symmetric, loader-wave (21+) and 16-wave (26+) tile
