@@ -291,6 +291,8 @@ _SIGS = {
     "cbx_wave_format_f32": ([c_f, c_f, c_f, c_int, c_int, c_int, c_f, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_loudness_f32": ([c_f, c_f, c_f, c_int, c_f, c_int, c_f, ctypes.c_double, c_f, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_gain_f32": ([c_f, c_f, c_f, c_int, c_f, c_f], c_int),
+    "cbx_wave_ingest": ([c_f, c_f, c_f, c_int, c_int, c_int, c_f, c_int, c_int, c_int, c_f, c_f, c_long, c_f], c_int),
+    "cbx_wave_trim_edges_f32": ([c_f, c_f, c_f, c_int, ctypes.c_double, c_f, c_f, c_long, c_f], c_int),
     "cbx_hift_stft_f32": ([c_f, c_f, c_f, c_int, c_long, c_long, c_f], c_int),
     "cbx_hift_istft_f32": ([c_f, c_f, c_int, c_long, c_long, c_float, c_int, c_f], c_int),
     "cbx_hift_istft_rows_f32": ([c_f, c_f, c_f, c_int, c_long, c_long, c_float, c_int, c_f], c_int),

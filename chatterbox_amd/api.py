@@ -138,18 +138,33 @@ def _norm_loudness_device(wav, device, target_lufs=-27.0):
 
 
 def _load_wave(wav, sr):
-    """A file path or a (waveform, sample_rate) pair -> the waveform at rate `sr` (a float32 array)."""
+    """A file path, a (waveform, sample_rate) pair or a (data, sample_rate, encoding[, channels]) tuple -> the waveform at rate `sr` (a float32 array), on the host
+    (audio_in = "host").  The raw form is decoded and mixed down by frontend.decode_pcm and then treated as a pair."""
     from . import frontend as fe
+    if isinstance(wav, (tuple, list)) and len(wav) != 2:
+        a = ops.check_audio_in(wav)
+        wav = (fe.decode_pcm(a["data"], a["encoding"], a["channels"]), a["rate"])
     return fe.resample(wav[0], wav[1], sr) if isinstance(wav, (tuple, list)) else fe.load_wav(wav, sr)[0]
 
 
+def _check_audio_in_mode(value):
+    if not isinstance(value, str):
+        raise TypeError(f"audio_in: expected 'host' or 'device', got {type(value).__name__}")
+    if value not in ("host", "device"):
+        raise ValueError(f"audio_in = {value!r}: expected 'host' or 'device'")
+    return value
+
+
 def _prepare_conditionals(analyzer, wav, exaggeration, prompt_len, device, min_seconds=None, norm_loudness=False, enc_cond_len=None):
-    """The common body of prepare_conditionals (tts.py:182-206, mtl_tts.py:253-277, tts_turbo.py:241-270).  `wav`: a file path or a
-    (waveform, sample_rate) pair."""
+    """The common body of prepare_conditionals (tts.py:182-206, mtl_tts.py:253-277, tts_turbo.py:241-270).  `wav`: a file path, a
+    (waveform, sample_rate) pair or raw samples (data, sample_rate, encoding[, channels]) (ops.check_audio_in).  analyzer.audio_in = "device": the same stages
+    with the waveform on the device (_prepare_conditionals_device)."""
     from . import frontend as fe
     if analyzer is None or not analyzer.tokenizer.available or not analyzer.speaker_encoder.available or analyzer.ve is None:
         raise RuntimeError("voice-prompt analysis needs the `tokenizer.*` and `speaker_encoder.*` tensors of the S3Gen checkpoint and "
                            "ve.safetensors; this model was built without them -- load a prepared voice with Conditionals.load('conds.pt')")
+    if getattr(analyzer, "audio_in", "host") == "device":
+        return _prepare_conditionals_device(analyzer, wav, exaggeration, prompt_len, device, min_seconds, norm_loudness, enc_cond_len)
     w24 = _load_wave(wav, S3GEN_SR)
     if min_seconds is not None:
         assert len(w24) / S3GEN_SR > min_seconds, "Audio prompt must be longer than 5 seconds!"
@@ -162,6 +177,24 @@ def _prepare_conditionals(analyzer, wav, exaggeration, prompt_len, device, min_s
     w16 = fe.resample(w24, S3GEN_SR, S3_SR)
     gen = analyzer.embed_ref(w24[: analyzer.DEC_COND_LEN], S3GEN_SR)
     spk, ptoks = analyzer.t3_prompt(w16, prompt_len, enc_cond_len=enc_cond_len)
+    t3 = T3Cond(speaker_emb=spk, cond_prompt_speech_tokens=ptoks, emotion_adv=exaggeration * torch.ones(1, 1, 1)).to(device=device)
+    return Conditionals(t3, {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in gen.items()})
+
+
+def _prepare_conditionals_device(analyzer, wav, exaggeration, prompt_len, device, min_seconds, norm_loudness, enc_cond_len):
+    """_prepare_conditionals with audio_in = "device": the same stages in the same order (PromptAnalyzer.stage), the waveform on the device from the upload of its
+    raw bytes on.  norm_loudness="device" gains the 24 kHz waveform in place where it is; True (pyloudnorm) is a round trip through the host."""
+    if isinstance(norm_loudness, str) and norm_loudness != "device":
+        raise ValueError(f"norm_loudness = {norm_loudness!r}: expected True, False or 'device'")
+
+    def norm(w24):
+        if isinstance(norm_loudness, str):
+            ops.wave_normalize([w24], [-27.0], ceiling=None, fs=S3GEN_SR)
+            return w24
+        return torch.from_numpy(_norm_loudness(w24.cpu().numpy(), S3GEN_SR).astype("float32")).to(w24.device)
+    st = analyzer.stage(wav, t3=True, norm=norm if norm_loudness else None, min_seconds=min_seconds)
+    gen = analyzer.embed_ref_staged(st["ref24"], st["ref16"])
+    spk, ptoks = analyzer.t3_prompt(st["w16"], prompt_len, enc_cond_len=enc_cond_len, ve_wav=st["ve16"])
     t3 = T3Cond(speaker_emb=spk, cond_prompt_speech_tokens=ptoks, emotion_adv=exaggeration * torch.ones(1, 1, 1)).to(device=device)
     return Conditionals(t3, {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in gen.items()})
 
@@ -387,8 +420,23 @@ _NO_VOICE = "Please `prepare_conditionals` first or specify `audio_prompt_path`"
 
 
 class _Finish:
-    """The epilogue of every public method that returns audio."""
+    """The epilogue of every public method that returns audio, and the `audio_in` switch of every method that takes audio."""
     sr = S3GEN_SR
+
+    @property
+    def audio_in(self):
+        """Where audio inputs (voice prompts, conversion sources, target voices) are decoded, mixed down, resampled and trimmed: "host" (the default: NumPy / SciPy
+        in fp64, every call as it always was) or "device" (the raw bytes are uploaded; cbx_wave_ingest and cbx_wave_trim_edges_f32 do it in fp32, so results differ
+        from host mode in rounding).  It lives on the analyzer (frontend.PromptAnalyzer.audio_in)."""
+        return getattr(self.analyzer, "audio_in", "host") if self.analyzer is not None else getattr(self, "_audio_in", "host")
+
+    @audio_in.setter
+    def audio_in(self, value):
+        value = _check_audio_in_mode(value)
+        if self.analyzer is not None:
+            self.analyzer.audio_in = value
+        else:
+            self._audio_in = value
 
     def _finish(self, wav, fmt=None, converted=True, loud=None):
         """A device waveform as the reference returns it: CPU float32 (1, n), watermarked if a watermarker is loaded.
@@ -889,7 +937,8 @@ class ChatterboxTurboTTS(_TTS):
     def prepare_conditionals(self, wav_fpath, exaggeration=0.0, norm_loudness=True):
         """reference tts_turbo.py:241-270 (prompt > 5 s, optional loudness normalisation to -27 LUFS, 375 prompt tokens).  norm_loudness: True is the reference's
         (pyloudnorm on the host; skipped with its warning where that is missing), False none, "device" the same gain from this project's own BS.1770-4 meter on
-        the device (_norm_loudness_device): no third-party dependency, no ceiling."""
+        the device (_norm_loudness_device): no third-party dependency, no ceiling.  With self.audio_in = "device" the prompt is on the device already: "device"
+        gains it in place there, True (pyloudnorm) copies the 24 kHz waveform to the host and back -- a host round trip."""
         self.conds = self._analyse(wav_fpath, exaggeration, norm_loudness=norm_loudness)
 
     def _set_exaggeration(self, exaggeration):
@@ -993,10 +1042,15 @@ class ChatterboxVC(_Finish):
 
     def _embed_ref(self, wav):
         """A target voice (a WAV path or a (waveform, sample_rate) pair) -> its S3Gen reference dict"""
+        if self.audio_in == "device":
+            st = self.analyzer.stage(wav, dec_cond_len=self.DEC_COND_LEN)
+            return self.analyzer.embed_ref_staged(st["ref24"], st["ref16"])
         return self.analyzer.embed_ref(_load_wave(wav, S3GEN_SR)[: self.DEC_COND_LEN], S3GEN_SR)
 
     def _tokens_of(self, audio):
-        """A source (a WAV path or a (waveform, sample_rate) pair) -> its S3 tokens"""
+        """A source (a WAV path, a (waveform, sample_rate) pair or a raw (data, sample_rate, encoding[, channels]) tuple) -> its S3 tokens"""
+        if self.audio_in == "device":
+            return self.analyzer.tokenizer(self.analyzer.ingest([audio], S3_SR)[0])[0]
         return self.analyzer.tokenizer(torch.from_numpy(_load_wave(audio, S3_SR)))[0]
 
     def set_target_voice(self, wav_fpath):
@@ -1017,7 +1071,9 @@ class ChatterboxVC(_Finish):
         return torch.as_tensor(s3_tokens).view(-1).long().cpu()
 
     def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
-        """reference vc.py:83-104.  audio: a WAV path or a (waveform, sample_rate) pair.  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
+        """reference vc.py:83-104.  audio: a WAV path, a (waveform, sample_rate) pair or raw samples (data, sample_rate, encoding[, channels]) -- bytes or a uint8 /
+        int16 / int32 / float32 array of interleaved frames in one of ops.WAVE_IN_ENCODINGS; with self.audio_in = "device" it is decoded and resampled on the device
+        (a path then opens G.711 and 24-bit WAVs too).  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
         are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding, loudness: as there."""
         fmt = ops.check_format(sample_rate, encoding)
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness))
@@ -1055,7 +1111,8 @@ class ChatterboxVC(_Finish):
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 
     def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
-        """generate() for B conversions in one call: `audios` (WAV paths or (waveform, sample_rate) pairs) or `s3_tokens` (B id sequences); target voice per
+        """generate() for B conversions in one call: `audios` (WAV paths, (waveform, sample_rate) pairs or raw (data, sample_rate, encoding[, channels]) tuples; with
+        audio_in = "device" the sources of one (rate, encoding, channels) are uploaded and converted together) or `s3_tokens` (B id sequences); target voice per
         request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
         self.ref_dict.  Returns B CPU float32 tensors (1, n_b) at `.sr` in the caller's order; more than MAX_BATCH requests run as sub-batches in order of length.
         Never overwrites self.ref_dict.  seeds, speed: per request as ChatterboxTTS.generate_batch states them -- request b's noise is that of
@@ -1080,7 +1137,10 @@ class ChatterboxVC(_Finish):
             assert all(r is not None for r in refs), "Please `prepare_conditionals` first or specify `target_voice_path`"
         if s3_tokens is None:
             self._need_analyzer()
-            src = [self._tokens_of(a) for a in src]
+            if self.audio_in == "device":  # the sources of one (rate, encoding, channels) share an upload and a launch; the tokeniser stays one source per pass
+                src = [self.analyzer.tokenizer(w)[0] for w in self.analyzer.ingest(src, S3_SR)]
+            else:
+                src = [self._tokens_of(a) for a in src]
         toks = [torch.as_tensor(t).view(-1).long().cpu() for t in src]
         out = [None] * B
         for idx in batch_plan([int(t.numel()) for t in toks], int(self.MAX_BATCH)):

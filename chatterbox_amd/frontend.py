@@ -13,9 +13,11 @@ kernels: a framed DFT is `frames @ basis^T` where `frames` is the waveform itsel
 no frame matrix is materialised; Kaldi's per-frame DC removal / pre-emphasis / povey window are linear and folded into its DFT basis;
 the 2-D convolutions of CAMPPlus' front module become 1-D convolutions over time whose "channels" are (channel, frequency) pairs
 (block-Toeplitz weights built once at load, BatchNorm folded in).  This path runs once per voice, in exact fp32 (precision 1).
-Host-side signal conditioning that the reference also does on the CPU (file decoding, resampling, silence trimming) is numpy / scipy.
+Host-side signal conditioning that the reference also does on the CPU (file decoding, resampling, silence trimming) is numpy / scipy by default
+(PromptAnalyzer.audio_in = "host"); with audio_in = "device" the raw sample bytes are uploaded and cbx_wave_ingest / cbx_wave_trim_edges_f32 do it there.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -490,11 +492,25 @@ class VoiceEncoderEngine:
         """VoiceEncoder.embeds_from_wavs (as_spk=False): list of numpy waveforms -> (B, 256) CPU tensor."""
         out = []
         for w in wavs:
+            if torch.is_tensor(w) and w.device.type != "cpu":  # audio_in = "device": the waveform stays where it is (fp32, 1-D)
+                if int(sample_rate) != S3_SR:
+                    w = ops.wave_ingest([w.contiguous().view(-1)], "f32", 1, int(sample_rate), S3_SR)[0]
+                if trim_top_db:
+                    w = self.trim(w, trim_top_db)
+                out.append(self.inference(self.melspectrogram(w), rate=rate).cpu())
+                continue
             w = resample(np.asarray(w, dtype=np.float32), sample_rate, S3_SR)
             if trim_top_db:
                 w = trim_silence(w, trim_top_db)
             out.append(self.inference(self.melspectrogram(torch.from_numpy(w)), rate=rate).cpu())
         return torch.stack(out)
+
+    @ops.on_device
+    def trim(self, w, top_db=20.0):
+        """trim_silence of a 1-D fp32 device waveform: ops.wave_trim_edges finds {start, stop} on the device, one 8-byte copy brings them to the host (the length of
+        the mel depends on them), the result is a view of `w`."""
+        start, stop = ops.wave_trim_edges([w], top_db).view(-1).tolist()
+        return w[start:stop]
 
 
 # ----------------------------------------------------------------------------- host-side signal conditioning (CPU, as in the reference)
@@ -539,6 +555,110 @@ def load_wav(path, sr):
     return resample(data, rate, sr), sr
 
 
+def g711_expand(codes, law):
+    """ITU-T G.711 expansion of uint8 code words to the 16-bit sample (int32 array): with the code's sign s, exponent e and mantissa m (after the law's bit
+    inversion), mu-law = +-4 ((2 m + 33) 2^e - 33); A-law = +-(16 m + 8) for e = 0 and +-4 (2 m + 33) 2^e otherwise."""
+    c = np.asarray(codes, dtype=np.uint8).astype(np.int32)
+    if law == "mulaw":
+        c = c ^ 0xFF
+        mag = 4 * (((2 * (c & 15) + 33) << ((c >> 4) & 7)) - 33)
+        return np.where(c & 0x80, -mag, mag)
+    assert law == "alaw", law
+    c = c ^ 0x55
+    e, m = (c >> 4) & 7, c & 15
+    mag = np.where(e == 0, 16 * m + 8, (4 * (2 * m + 33)) << e)
+    return np.where(c & 0x80, mag, -mag)
+
+
+def decode_pcm(data, encoding, channels=1):
+    """Raw interleaved samples -> the mono float32 waveform, cbx_wave_ingest's decode and mixdown restated in NumPy (include/cbx.h states the rules; for the
+    encodings load_wav reads, load_wav's values bit for bit): data: bytes-like, or a uint8 / int16 / int32 / float32 array of interleaved frames; the mixdown is
+    the fp32 sum over the channels in channel order, then one division by float32(channels)."""
+    if torch.is_tensor(data):
+        data = data.detach().cpu().numpy()
+    raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    if encoding == "u8":
+        x = (raw.astype(np.float32) - np.float32(128.0)) / np.float32(128.0)
+    elif encoding == "s16":
+        x = raw.view("<i2").astype(np.float32) / np.float32(32768.0)
+    elif encoding == "s24":
+        b = raw.reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        x = np.where(v & 0x800000, v - (1 << 24), v).astype(np.float32) / np.float32(8388608.0)
+    elif encoding == "s32":
+        x = raw.view("<i4").astype(np.float32) / np.float32(2147483648.0)
+    elif encoding == "f32":
+        x = raw.view("<f4").copy()
+    elif encoding in ("mulaw", "alaw"):
+        x = g711_expand(raw, encoding).astype(np.float32) / np.float32(32768.0)
+    else:
+        raise ValueError(f"encoding = {encoding!r}: expected one of {ops.WAVE_IN_ENCODINGS}")
+    if channels == 1:
+        return x
+    f = x.reshape(-1, channels)
+    acc = f[:, 0].copy()
+    for ch in range(1, channels):
+        acc += f[:, ch]
+    return acc / np.float32(channels)
+
+
+_WAV_FORMATS = {(1, 8): "u8", (1, 16): "s16", (1, 24): "s24", (1, 32): "s32", (3, 32): "f32", (6, 8): "alaw", (7, 8): "mulaw"}
+
+
+def read_riff(path):
+    """A RIFF / WAVE file -> dict(data = the `data` chunk's bytes cut to whole frames, rate, encoding, channels): `fmt ` tags 1 (PCM 8 / 16 / 24 / 32 bit), 3 (IEEE
+    float 32), 6 (A-law), 7 (mu-law) and 0xFFFE (extensible, with those as its sub-format); chunks in any order, odd-sized chunks padded to even as RIFF pads them.
+    Nothing is decoded here: the bytes go to the device as they are."""
+    import struct
+    with open(os.fspath(path), "rb") as fh:
+        blob = fh.read()
+    if len(blob) < 12 or blob[:4] != b"RIFF" or blob[8:12] != b"WAVE":
+        raise ValueError(f"{path}: not a RIFF / WAVE file")
+    pos, fmt, data = 12, None, None
+    while pos + 8 <= len(blob):
+        cid, size = blob[pos: pos + 4], struct.unpack("<I", blob[pos + 4: pos + 8])[0]
+        body = blob[pos + 8: pos + 8 + size]
+        if cid == b"fmt " and fmt is None:
+            if len(body) < 16:
+                raise ValueError(f"{path}: a `fmt ` chunk of {len(body)} bytes")
+            tag, ch, rate, _, _, bits = struct.unpack("<HHIIHH", body[:16])
+            if tag == 0xFFFE:
+                if len(body) < 40:
+                    raise ValueError(f"{path}: an extensible `fmt ` chunk of {len(body)} bytes")
+                tag = struct.unpack("<H", body[24:26])[0]
+            fmt = (tag, ch, rate, bits)
+        elif cid == b"data" and data is None:
+            data = body
+        pos += 8 + size + (size & 1)
+    if fmt is None or data is None:
+        raise ValueError(f"{path}: no `fmt ` or no `data` chunk")
+    tag, ch, rate, bits = fmt
+    if (tag, bits) not in _WAV_FORMATS:
+        raise ValueError(f"{path}: format tag {tag} at {bits} bits per sample is not supported (PCM 8 / 16 / 24 / 32, float 32, G.711)")
+    if not 1 <= ch <= ops.WAVE_IN_MAX_CHANNELS or rate < 1:
+        raise ValueError(f"{path}: {ch} channels at {rate} samples per second")
+    enc = _WAV_FORMATS[(tag, bits)]
+    fb = ch * ops.WAVE_IN_SAMPLE_BYTES[enc]
+    return dict(data=data[: len(data) // fb * fb], rate=int(rate), encoding=enc, channels=int(ch))
+
+
+def trim_edges_rule(y, top_db=20.0):
+    """cbx_wave_trim_edges_f32's rule in NumPy fp64 -> (start, stop): per block of 512 samples the sum of squares, a frame = four blocks over the row padded by
+    1024 zeros, mean square floored at 1e-20, kept while above the loudest frame's times 10^(-top_db / 10)."""
+    y = np.asarray(y, dtype=np.float32)
+    n = len(y)
+    nb, nf = -(-n // 512), 1 + n // 512
+    blocks = np.zeros(nb + 4)
+    sq = y.astype(np.float64) ** 2
+    for b in range(nb):
+        blocks[b + 2] = sq[512 * b: 512 * (b + 1)].sum()
+    ms = np.maximum(np.array([((blocks[f] + blocks[f + 1]) + blocks[f + 2]) + blocks[f + 3] for f in range(nf)]) / 2048.0, 1e-20)
+    nz = np.flatnonzero(ms > ms.max() * 10.0 ** (-float(top_db) / 10.0))
+    if nz.size == 0:
+        return 0, 0
+    return int(nz[0]) * 512, min(n, (int(nz[-1]) + 1) * 512)
+
+
 # ----------------------------------------------------------------------------- embed_ref / prepare_conditionals
 
 
@@ -547,8 +667,11 @@ class PromptAnalyzer:
     mtl_tts.py:253-277): everything that turns a reference waveform into `Conditionals`."""
     ENC_COND_LEN, DEC_COND_LEN = 6 * S3_SR, 10 * S3GEN_SR
 
+    AUDIO_IN = ("host", "device")
+
     def __init__(self, s3gen_sd, ve_sd=None, device="cuda"):
         self.dev = torch.device(device)
+        self.audio_in = "host"
         self.tokenizer = S3TokenizerEngine(s3gen_sd, device)
         self.speaker_encoder = CAMPPlusEngine(s3gen_sd, device)
         self.mel = Mel24kExtractor(device)
@@ -559,21 +682,113 @@ class PromptAnalyzer:
         w = np.asarray(ref_wav, dtype=np.float32).reshape(-1)
         w24 = resample(w, ref_sr, S3GEN_SR)
         w16 = resample(w, ref_sr, S3_SR)
-        feat = self.mel(torch.from_numpy(w24))[None]
-        xvec = self.speaker_encoder.inference(torch.from_numpy(w16))
-        tok, tlen = self.tokenizer(torch.from_numpy(w16))
+        return self.embed_ref_staged(torch.from_numpy(w24), torch.from_numpy(w16))
+
+    def embed_ref_staged(self, w24, w16):
+        """embed_ref behind its resampling: the 24 kHz reference and its 16 kHz form (1-D fp32 tensors, host or device) -> embed_ref's dict."""
+        feat = self.mel(w24)[None]
+        xvec = self.speaker_encoder.inference(w16)
+        tok, tlen = self.tokenizer(w16)
         if feat.shape[1] != 2 * tok.shape[1]:  # s3gen.py:152-158
             tok = tok[:, : feat.shape[1] // 2]
             tlen = torch.tensor([tok.shape[1]])
         return dict(prompt_token=tok, prompt_token_len=tlen, prompt_feat=feat, prompt_feat_len=None, embedding=xvec)
 
-    def t3_prompt(self, ref_16k_wav, plen, enc_cond_len=None):
+    def t3_prompt(self, ref_16k_wav, plen, enc_cond_len=None, ve_wav=None):
         """(speaker_emb (1, 256), cond_prompt_speech_tokens (1, <= plen)) of T3Cond.  enc_cond_len: samples of the 16 kHz prompt that
-        are tokenised -- 6 s for English / Multilingual (tts.py:107,194), 15 s for Turbo / Nano (tts_turbo.py:112,258: 375 tokens)."""
+        are tokenised -- 6 s for English / Multilingual (tts.py:107,194), 15 s for Turbo / Nano (tts_turbo.py:112,258: 375 tokens).
+        ref_16k_wav: a float array, or (audio_in = "device") a 1-D fp32 device tensor; ve_wav: the voice encoder's input when it is trimmed already (stage())."""
         assert self.ve is not None, "no voice-encoder weights (ve.safetensors) loaded"
         tokens = None
         if plen:
             cut = self.ENC_COND_LEN if enc_cond_len is None else int(enc_cond_len)
-            tokens, _ = self.tokenizer(torch.from_numpy(np.asarray(ref_16k_wav[:cut], dtype=np.float32)), max_len=plen)
-        ve = self.ve.embeds_from_wavs([ref_16k_wav], sample_rate=S3_SR).mean(0, keepdim=True)
+            head = ref_16k_wav[:cut] if torch.is_tensor(ref_16k_wav) else torch.from_numpy(np.asarray(ref_16k_wav[:cut], dtype=np.float32))
+            tokens, _ = self.tokenizer(head, max_len=plen)
+        if ve_wav is not None:
+            ve = self.ve.embeds_from_wavs([ve_wav], sample_rate=S3_SR, trim_top_db=None).mean(0, keepdim=True)
+        else:
+            ve = self.ve.embeds_from_wavs([ref_16k_wav], sample_rate=S3_SR).mean(0, keepdim=True)
         return ve, tokens
+
+    # ------------------------------------------------------------------------------------------------ audio_in = "device"
+    @staticmethod
+    def raw_form(audio):
+        """An audio input (ops.check_audio_in's forms) as what goes to the device: dict(data = a 1-D uint8 / int16 / int32 / float32 host array, or the caller's
+        device tensor flattened, rate, encoding, channels, frames).  A path is parsed by read_riff (its `data` chunk's bytes, undecoded); a pair's waveform keeps
+        its dtype when that is float32 (any other is converted to float32 on the host, which is what host mode computes from it); a triple's data is taken as it is."""
+        a = ops.check_audio_in(audio)
+        if a["kind"] == "path":
+            a = dict(read_riff(a["path"]), kind="raw")
+        if a["kind"] == "pair":
+            w = a["wav"]
+            if not (torch.is_tensor(w) and w.dtype == torch.float32):
+                w = np.ascontiguousarray(np.asarray(w.detach().cpu() if torch.is_tensor(w) else w, dtype=np.float32))
+            a = dict(kind="raw", data=w, rate=a["rate"], encoding="f32", channels=1)
+        d = a["data"]
+        if isinstance(d, (bytes, bytearray, memoryview)):
+            d = np.frombuffer(d, dtype=np.uint8)
+        elif torch.is_tensor(d):
+            d = d.detach().contiguous().view(-1)
+            d = d.numpy() if d.device.type == "cpu" else d
+        else:
+            d = np.ascontiguousarray(d).reshape(-1)
+        fb = a["channels"] * ops.WAVE_IN_SAMPLE_BYTES[a["encoding"]]
+        nbytes = d.numel() * d.element_size() if torch.is_tensor(d) else d.nbytes
+        return dict(data=d, rate=a["rate"], encoding=a["encoding"], channels=a["channels"], frames=nbytes // fb)
+
+    @ops.on_device
+    def ingest(self, audios, rate_out):
+        """Audio inputs -> their mono fp32 waveforms at rate_out on the device, in the caller's order.  The inputs are grouped by (rate, encoding, channels); a
+        group's bytes are laid out in ONE host buffer (every source on a 16-byte boundary), uploaded once and converted by ONE ops.wave_ingest launch (64 sources
+        per launch).  A device tensor is used where it lies, in a launch of its own.  A rate that cbx_wave_ingest cannot convert is a ValueError before any
+        upload; nothing is decoded or resampled on the host."""
+        forms = [self.raw_form(a) for a in audios]
+        for f in forms:
+            ops.resample_filter(f["rate"], int(rate_out))
+        out, groups = [None] * len(forms), {}
+        for i, f in enumerate(forms):
+            key = ("device", i) if torch.is_tensor(f["data"]) else (f["rate"], f["encoding"], f["channels"])
+            groups.setdefault(key, []).append(i)
+        for key, idx in groups.items():
+            for lo in range(0, len(idx), 64):
+                part = idx[lo: lo + 64]
+                f0 = forms[part[0]]
+                if key[0] == "device":
+                    rows = [f0["data"].to(self.dev)]
+                else:
+                    arrs = [forms[i]["data"].view(np.uint8) for i in part]
+                    offs = np.cumsum([0] + [(a.size + 15) // 16 * 16 for a in arrs])
+                    buf = np.zeros(max(16, int(offs[-1])), np.uint8)
+                    for o, a in zip(offs, arrs):
+                        buf[o: o + a.size] = a
+                    big = torch.from_numpy(buf).to(self.dev)
+                    rows = [big[o: o + a.size] for o, a in zip(offs, arrs)]
+                    if f0["encoding"] in ("s16", "s32", "f32"):   # (typed views of the same bytes: no copy)
+                        dt = dict(s16=torch.int16, s32=torch.int32, f32=torch.float32)[f0["encoding"]]
+                        rows = [w.view(dt) for w in rows]
+                for i, w in zip(part, ops.wave_ingest(rows, f0["encoding"], f0["channels"], f0["rate"], int(rate_out))):
+                    out[i] = w
+        return out
+
+    @ops.on_device
+    def stage(self, audio, t3=False, norm=None, min_seconds=None, dec_cond_len=None):
+        """audio_in = "device": the conditioned waveforms of one voice prompt, every one a 1-D fp32 device tensor, in the stage order of host mode:
+          w24    the input decoded, mixed down and resampled to 24 kHz (ingest), then `norm`-ed (a callable device waveform -> device waveform: Turbo's loudness step)
+          ref24  w24[:DEC_COND_LEN], what embed_ref analyses;  ref16 = ref24 resampled 24000 -> 16000 (a second wave_ingest launch, f32 / 1 channel)
+        and with t3=True, the T3 half of prepare_conditionals:
+          w16    w24 resampled 24000 -> 16000;  ve16 = w16 trimmed (VoiceEncoderEngine.trim), the voice encoder's input;  edges = its (start, stop).
+        min_seconds: the prompt must be longer (checked on w24's length, known on the host)."""
+        w24 = self.ingest([audio], S3GEN_SR)[0]
+        if min_seconds is not None:
+            assert w24.numel() / S3GEN_SR > min_seconds, "Audio prompt must be longer than 5 seconds!"
+        if norm is not None:
+            w24 = norm(w24)
+        ref24 = w24[: self.DEC_COND_LEN if dec_cond_len is None else int(dec_cond_len)]
+        to16 = lambda w: ops.wave_ingest([w], "f32", 1, S3GEN_SR, S3_SR)[0]
+        st = dict(w24=w24, ref24=ref24, ref16=to16(ref24))
+        if t3:
+            st["w16"] = to16(w24)
+            st["ve16"] = self.ve.trim(st["w16"], 20.0)
+            off = (st["ve16"].data_ptr() - st["w16"].data_ptr()) // 4 if st["ve16"].numel() else 0
+            st["edges"] = (off, off + st["ve16"].numel())
+        return st

@@ -1365,6 +1365,177 @@ def wave_normalize(rows, target, ceiling=1.0, fs=WAVE_IN_RATE):
     return stats
 
 
+# ----------------------------------------------------------------------------- audio in: decode + mixdown + resample, trim edges (wave_ingest.hip)
+WAVE_IN_ENCODINGS = ("u8", "s16", "s24", "s32", "f32", "mulaw", "alaw")   # cbx_wave_ingest's encoding 0 .. 6 (CBX_WAVE_IN_*)
+WAVE_IN_SAMPLE_BYTES = dict(u8=1, s16=2, s24=3, s32=4, f32=4, mulaw=1, alaw=1)
+WAVE_IN_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000)   # the source rates every analysis rate (16000, 24000) is tested at
+WAVE_INGEST_MAX_SPAN, WAVE_INGEST_MAX_TAB = 2048, 16384   # CBX_WAVE_INGEST_MAX_SPAN / _TAB of include/cbx.h
+WAVE_IN_MAX_CHANNELS = 8
+_WAVE_IN_DTYPES = {torch.uint8: None, torch.int16: "s16", torch.int32: "s32", torch.float32: "f32"}   # a typed row must hold its own encoding; uint8 rows hold any
+_RESAMPLE_FILTERS, _RESAMPLE_TABLES = {}, {}
+
+
+def resample_filter(rate_in, rate_out):
+    """wave_filter for any pair of rates: the resampler rate_in -> rate_out as scipy.signal.resample_poly designs it (NumPy fp64; wave_filter states the design):
+    dict(U, D, hl, T, h, tab (U, T) fp32).  Equal rates: no filter (U = D = T = 1, hl = 0).  Rates are positive ints (TypeError / ValueError); a pair whose reduced
+    table or tile span is over cbx_wave_ingest's caps is a ValueError -- there is no host fallback.  Built once per pair."""
+    import math
+    import numpy as np
+    for name, v in (("rate_in", rate_in), ("rate_out", rate_out)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"{name}: expected an int, got {type(v).__name__}")
+        if v < 1:
+            raise ValueError(f"{name} = {v}: a sample rate is a positive int")
+    key = (rate_in, rate_out)
+    if key not in _RESAMPLE_FILTERS:
+        g = math.gcd(rate_in, rate_out)
+        U, D = rate_out // g, rate_in // g
+        if U == D:
+            f = dict(U=1, D=1, hl=0, T=1, h=np.ones(1), tab=np.ones((1, 1), np.float32))
+        else:
+            hl = 10 * max(U, D)
+            T = -(-(2 * hl + 1) // U)
+            if U * T > WAVE_INGEST_MAX_TAB or 255 * D // U + T + 1 > WAVE_INGEST_MAX_SPAN:
+                raise ValueError(f"no conversion from {rate_in} to {rate_out} samples per second: U / D = {U} / {D} needs a table of {U * T} floats (cap "
+                                 f"{WAVE_INGEST_MAX_TAB}) and a span of {255 * D // U + T + 1} frames (cap {WAVE_INGEST_MAX_SPAN})")
+            cutoff = 1.0 / max(U, D)
+            i = np.arange(2 * hl + 1, dtype=np.float64) - hl
+            h = cutoff * np.sinc(cutoff * i) * np.kaiser(2 * hl + 1, 5.0)
+            h = U * (h / h.sum())
+            pad = np.zeros(U * T)
+            pad[: 2 * hl + 1] = h
+            f = dict(U=U, D=D, hl=hl, T=T, h=h, tab=np.ascontiguousarray(pad.reshape(T, U).T.astype(np.float32)))
+        _RESAMPLE_FILTERS[key] = f
+    return _RESAMPLE_FILTERS[key]
+
+
+def _resample_table(rate_in, rate_out, device):
+    """resample_filter's phase table on `device`, uploaded once per (device, pair)"""
+    key = (str(device), rate_in, rate_out)
+    if key not in _RESAMPLE_TABLES:
+        _RESAMPLE_TABLES[key] = torch.from_numpy(resample_filter(rate_in, rate_out)["tab"]).to(device)
+    return _RESAMPLE_TABLES[key]
+
+
+def resampled_len(n, rate_in, rate_out):
+    """Samples at rate_out of n samples at rate_in: ceil(n U / D)"""
+    f = resample_filter(rate_in, rate_out)
+    return -(-int(n) * f["U"] // f["D"])
+
+
+def check_audio_in(audio, name="audio"):
+    """An audio input of the public classes, checked before anything is launched (TypeError / ValueError) -> a dict:
+      a path (str / bytes / os.PathLike)                      dict(kind="path", path=)
+      (waveform, sample_rate)                                 dict(kind="pair", wav=, rate=)
+      (data, sample_rate, encoding[, channels])               dict(kind="raw", data=, rate=, encoding=, channels=, frames=)
+    data: bytes / bytearray / memoryview, or a uint8 / int16 / int32 / float32 NumPy array or tensor holding interleaved frames (an int16, int32 or float32
+    container must carry the encoding s16, s32 or f32; bytes and uint8 carry any); encoding: one of WAVE_IN_ENCODINGS; channels: an int in [1, 8], default 1;
+    sample_rate: a positive int.  The data must be a whole number of frames."""
+    import numpy as np
+    if isinstance(audio, (str, bytes, os.PathLike)):
+        return dict(kind="path", path=os.fspath(audio))
+    if not isinstance(audio, (tuple, list)) or not 2 <= len(audio) <= 4:
+        raise TypeError(f"{name}: expected a path, a (waveform, sample_rate) pair or a (data, sample_rate, encoding[, channels]) tuple, got {type(audio).__name__}")
+    rate = audio[1]
+    if isinstance(rate, (np.integer,)):
+        rate = int(rate)
+    if isinstance(rate, bool) or not isinstance(rate, int):
+        raise TypeError(f"{name}: sample_rate: expected an int, got {type(audio[1]).__name__}")
+    if rate < 1:
+        raise ValueError(f"{name}: sample_rate = {rate}: a sample rate is a positive int")
+    if len(audio) == 2:
+        return dict(kind="pair", wav=audio[0], rate=rate)
+    data, enc, ch = audio[0], audio[2], (audio[3] if len(audio) == 4 else 1)
+    if not isinstance(enc, str):
+        raise TypeError(f"{name}: encoding: expected a str, got {type(enc).__name__}")
+    if enc not in WAVE_IN_ENCODINGS:
+        raise ValueError(f"{name}: encoding = {enc!r}: expected one of {WAVE_IN_ENCODINGS}")
+    if isinstance(ch, bool) or not isinstance(ch, int):
+        raise TypeError(f"{name}: channels: expected an int, got {type(ch).__name__}")
+    if not 1 <= ch <= WAVE_IN_MAX_CHANNELS:
+        raise ValueError(f"{name}: channels = {ch}: expected 1 .. {WAVE_IN_MAX_CHANNELS}")
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        nbytes, own = memoryview(data).nbytes, None
+    elif torch.is_tensor(data) or isinstance(data, np.ndarray):
+        dt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int16): torch.int16, np.dtype(np.int32): torch.int32, np.dtype(np.float32): torch.float32}.get(data.dtype, data.dtype) \
+            if isinstance(data, np.ndarray) else data.dtype
+        if dt not in _WAVE_IN_DTYPES:
+            raise TypeError(f"{name}: data of dtype {data.dtype}: expected uint8, int16, int32 or float32")
+        nbytes, own = (data.nbytes if isinstance(data, np.ndarray) else data.numel() * data.element_size()), _WAVE_IN_DTYPES[dt]
+    else:
+        raise TypeError(f"{name}: data: expected bytes, a bytearray, a memoryview, a NumPy array or a tensor, got {type(data).__name__}")
+    if own is not None and own != enc:
+        raise ValueError(f"{name}: {data.dtype} data holds the encoding {own!r}, not {enc!r} (pass bytes or uint8 for any encoding)")
+    fb = ch * WAVE_IN_SAMPLE_BYTES[enc]
+    if nbytes % fb:
+        raise ValueError(f"{name}: {nbytes} bytes are not a whole number of frames of {ch} x {WAVE_IN_SAMPLE_BYTES[enc]} bytes")
+    return dict(kind="raw", data=data, rate=rate, encoding=enc, channels=ch, frames=nbytes // fb)
+
+
+def _ingest_rows(rows, enc, channels):
+    """rows: 1 .. 64 1-D tensors of raw samples with unit stride, all views of ONE allocation -- uint8 for any encoding, or int16 / int32 / float32 holding s16 / s32
+    / f32 -> (pointer of the allocation, ctypes arrays of the per-row byte offsets and frame counts)."""
+    rows = list(rows)
+    if not 1 <= len(rows) <= WAVE_JOIN_MAX_ROWS:
+        raise ValueError(f"wave_ingest: {len(rows)} rows (1 .. {WAVE_JOIN_MAX_ROWS})")
+    dev, fb = rows[0].device, channels * WAVE_IN_SAMPLE_BYTES[enc]
+    frames = []
+    for r, w in enumerate(rows):
+        if w.dtype not in _WAVE_IN_DTYPES or _WAVE_IN_DTYPES[w.dtype] not in (None, enc):
+            raise TypeError(f"wave_ingest: row {r} of dtype {w.dtype} cannot hold the encoding {enc!r}")
+        if w.dim() != 1 or (w.numel() > 1 and w.stride(0) != 1) or w.device != dev:
+            raise ValueError(f"wave_ingest: row {r} is not a 1-D tensor with unit stride on {dev}")
+        nbytes = w.numel() * w.element_size()
+        if nbytes % fb:
+            raise ValueError(f"wave_ingest: row {r}: {nbytes} bytes are not a whole number of frames of {fb} bytes")
+        frames.append(nbytes // fb)
+    base = rows[0].untyped_storage().data_ptr()
+    if any(w.untyped_storage().data_ptr() != base for w in rows):
+        raise ValueError("wave_ingest: the rows are views of different allocations; pass views of one buffer")
+    R = len(rows)
+    offs = (ctypes.c_long * R)(*[w.data_ptr() - base if w.numel() else 0 for w in rows])
+    return base, offs, (ctypes.c_long * R)(*frames), frames
+
+
+def wave_ingest(rows, encoding, channels, rate_in, rate_out):
+    """cbx_wave_ingest on the current stream: rows (_ingest_rows: 1 .. 64 1-D views of ONE allocation holding interleaved frames of `channels` samples in
+    `encoding`, sampled at rate_in) decoded, mixed down to mono and resampled to rate_out in ONE launch.  Returns R 1-D fp32 tensors (row r has
+    resampled_len(frames_r, rate_in, rate_out) samples) that are views of one packed device buffer.  No host synchronisation.  ValueError / TypeError before the
+    launch: an unknown encoding, channels outside [1, 8], a pair of rates over the caps (resample_filter), rows that are not whole frames."""
+    if encoding not in WAVE_IN_ENCODINGS:
+        raise ValueError(f"wave_ingest: encoding = {encoding!r}: expected one of {WAVE_IN_ENCODINGS}")
+    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= WAVE_IN_MAX_CHANNELS:
+        raise ValueError(f"wave_ingest: channels = {channels!r}: expected an int in 1 .. {WAVE_IN_MAX_CHANNELS}")
+    f = resample_filter(rate_in, rate_out)
+    rows = list(rows)
+    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+        return [torch.empty(0, dtype=torch.float32, device=w.device) for w in rows]
+    base, offs, nfr, frames = _ingest_rows(rows, encoding, channels)
+    R, dev = len(frames), rows[0].device
+    cnt = [-(-n * f["U"] // f["D"]) for n in frames]
+    starts = [sum(cnt[:r]) for r in range(R)]
+    packed = torch.empty(max(1, sum(cnt)), dtype=torch.float32, device=dev)
+    o = (ctypes.c_long * R)(*starts)
+    check(lib.cbx_wave_ingest(base, ctypes.addressof(offs), ctypes.addressof(nfr), R, WAVE_IN_ENCODINGS.index(encoding), channels,
+                              _p(_resample_table(rate_in, rate_out, dev)) if f["hl"] else None, f["U"], f["D"], f["T"], _p(packed), ctypes.addressof(o), packed.numel(),
+                              _stream()), "cbx_wave_ingest")
+    return [packed[a: a + c] for a, c in zip(starts, cnt)]
+
+
+def wave_trim_edges(rows, top_db=20.0, edges=None):
+    """cbx_wave_trim_edges_f32 on the current stream: the part {start, stop} of every row (_wave_rows) that frontend.trim_silence keeps, as an (R, 2) int32 device
+    tensor.  Two launches, no host synchronisation."""
+    base, offs, lens = _wave_rows(rows, "wave_trim_edges")
+    R, dev = len(lens), rows[0].device
+    if edges is None:
+        edges = torch.empty(R, 2, dtype=torch.int32, device=dev)
+    assert edges.dtype == torch.int32 and edges.numel() == 2 * R and edges.is_contiguous() and edges.device == dev, "wave_trim_edges: edges is (R, 2) int32 on the rows' device"
+    ws = torch.empty(max(1, R * -(-max(lens) // 512)), dtype=torch.float64, device=dev)
+    check(lib.cbx_wave_trim_edges_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, 10.0 ** (-float(top_db) / 10.0), _p(edges), _p(ws), ws.numel(), _stream()),
+          "cbx_wave_trim_edges_f32")
+    return edges
+
+
 def hift_stft(s, spec, sample_lens=None):
     B, L = s.shape
     check(lib.cbx_hift_stft_f32(_p(s), _p(spec), _p(sample_lens), B, L, spec.stride(1), _stream()), "cbx_hift_stft_f32")

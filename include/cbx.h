@@ -911,6 +911,46 @@ int cbx_wave_loudness_f32(const float* wav, const long* row_off, const int* row_
  * -22 before any launch: a null pointer, R outside [1, 64], a negative length or offset. */
 int cbx_wave_gain_f32(float* wav, const long* row_off, const int* row_len, int R, const float* gain, void* stream);
 
+/* ---- audio in: decode, mix down and resample the raw sample bytes of voice prompts and conversion sources, and find the silence at their ends, on the device
+ * (added after ABI v16 without a version step: new functions only).  The mirror image of cbx_wave_format_f32.  It replaces frontend.load_wav / resample /
+ * trim_silence (NumPy / SciPy on the host), which restate librosa.load, librosa.resample and librosa.effects.trim of the reference (tts.py:184-187,
+ * s3gen.py:139, vc.py:88, voice_encoder.py:224).
+ * cbx_wave_ingest: rows: R in [1, 64] rows of interleaved frames in ONE device allocation `raw`; row r = row_frames[r] frames of `channels` samples from the
+ * byte raw + row_off[r] (HOST arrays, by value to the kernel).  encoding (CBX_WAVE_IN_*), decoded to fp32 as load_wav does: u8 (v - 128) / 128; s16 v / 32768;
+ * s24 three bytes little-endian, v / 2^23; s32 (float)v / 2^31; f32 the bits; mulaw / alaw the ITU-T G.711 expansion to the 16-bit value, / 32768.  Mixdown: the
+ * fp32 sum over the channels in channel order, then one IEEE division by (float)channels (one channel: the decoded value's bits).  Resampling by U / D = rate_out /
+ * rate_in reduced, cbx_wave_format_f32's definition: hl = 10 max(U, D), h = U firwin(2 hl + 1, 1 / max(U, D), window = ("kaiser", 5.0)) built by the CALLER in
+ * fp64, tab[p * T + j] = h[p + j U] (zero past 2 hl) in device memory, T = ceil((2 hl + 1) / U);
+ *   c = m D + hl, p = c mod U, k = c div U, y[m] = sum_(j = 0 .. T - 1) tab[p][j] x[k - j], x = 0 outside [0, n), m in [0, ceil(n U / D))
+ * by fmaf in the order j = 0 .. T - 1 from 0.  U = D = 1 (T = 1, tab may be NULL): decode and mixdown only.  No continuation state: a row is a whole signal.
+ * out: ONE fp32 buffer of out_cap floats; row r's ceil(n_r U / D) outputs go to out + out_off[r] (HOST array); nothing else is written, nothing outside a row's
+ * bytes is read.  16-byte loads where a row's address allows, byte loads at the ragged ends.  All positions are 64-bit.  One launch (none when every row is empty).
+ * Caps: a tile's span 255 D / U + T + 1 <= CBX_WAVE_INGEST_MAX_SPAN frames and U T <= CBX_WAVE_INGEST_MAX_TAB floats -- every pair of {8000, 11025, 12000, 16000,
+ * 22050, 24000, 32000, 44100, 48000, 88200, 96000} -> {16000, 24000} fits (largest span 96000 -> 16000: 1652; largest table 11025 -> 16000: 640 x 21).
+ * -22 before any launch: a null pointer, R outside [1, 64], a negative frame count or offset, an offset (or `raw`) that is not a multiple of the sample size (1
+ * for u8 / mulaw / alaw / s24, 2 for s16, 4 for s32 / f32), channels outside [1, 8], an unknown encoding, U / D not reduced, T not that of U / D, a span or table
+ * over the caps, a row that would write outside [0, out_cap), out_cap below the sum of the rows' outputs. */
+#define CBX_WAVE_IN_U8 0
+#define CBX_WAVE_IN_S16 1
+#define CBX_WAVE_IN_S24 2
+#define CBX_WAVE_IN_S32 3
+#define CBX_WAVE_IN_F32 4
+#define CBX_WAVE_IN_MULAW 5
+#define CBX_WAVE_IN_ALAW 6
+#define CBX_WAVE_INGEST_MAX_SPAN 2048
+#define CBX_WAVE_INGEST_MAX_TAB 16384
+int cbx_wave_ingest(const void* raw, const long* row_off, const long* row_frames, int R, int encoding, int channels, const float* tab, int U, int D, int T, float* out,
+                    const long* out_off, long out_cap, void* stream);
+/* cbx_wave_trim_edges_f32: frontend.trim_silence (librosa.effects.trim) for R in [1, 64] fp32 rows, rows as cbx_wave_join_f32 takes them.  Frames of 2048 samples
+ * at hop 512 over the row padded by 1024 zeros on either side: F = 1 + n / 512 frames, frame f covers samples [512 f - 1024, 512 f + 1024).  ms_f = the fp64 sum
+ * of squares / 2048, floored at 1e-20 (trim_silence floors the RMS at 1e-10: in an all-zero row every frame is level with the loudest, and all of it is kept,
+ * as librosa keeps it); a frame passes iff ms_f > max_f ms_f * ratio, compared in fp64 (ratio = 10^(-top_db / 10), computed by the caller in fp64).  With f0 / f1
+ * the first / last passing frame: start = 512 f0, stop = min(n, 512 (f1 + 1)); no passing frame: (0, 0).  edges: (R, 2) int32 device table {start, stop}.  Sums
+ * per block of 512 samples, one wave per block in a fixed order, a frame = its four blocks added in ascending order: no floating-point atomics, independent of
+ * the grid and of the row's alignment.  Two launches.  ws: device workspace of ws_cap >= R * ceil(max_r n_r / 512) doubles (not NULL).
+ * -22 before any launch: a null pointer, R outside [1, 64], a negative length or offset, ratio negative / not finite, a workspace that is too small. */
+int cbx_wave_trim_edges_f32(const float* wav, const long* row_off, const int* row_len, int R, double ratio, int* edges, double* ws, long ws_cap, void* stream);
+
 /* ---- voice-prompt / voice-conversion front-end ----
  * Contractions (framed DFT as a GEMM over overlapping waveform rows, mel filterbanks, Conv1d/Conv2d-as-Toeplitz, attention, LSTM
  * projections) use cbx_gemm_f32 / cbx_flash_attn_f32 / cbx_gemv_f32; these are the remaining element-wise / reduction passes. */
