@@ -335,15 +335,36 @@ def _long_numbers(**params):
             raise ValueError(f"{name} = {v}: expected a finite number")
 
 
-def long_plan(chunks, max_batch, a):
-    """The jobs of a generate_long call, WITHOUT their tokens and voices: chunks = split_text's list, a = _long_args' dict.  Chunks keep the text's order (no length
-    sort: a piece is a run of consecutive chunks) and are cut into consecutive device batches of at most max_batch (and at most 64, the join's row limit).  Per job:
-    dict(chunks=[indices], join=the engines' join dict, seeds=[...] if seeded, speed=[...] if not 1.0).  The gap behind a chunk is round(pause * 24000 / speed)
-    samples, paragraph_pause behind a paragraph's last chunk; the first job carries first=True, the last one last=True."""
+def _long_stream_args(first_batch, batch_growth):
+    """generate_long_stream's own arguments, validated when the method is CALLED -> (first_batch: None or an int >= 1, batch_growth: a finite float >= 1)"""
+    import math
+    import numbers
+    if first_batch is not None:
+        if not isinstance(first_batch, int) or isinstance(first_batch, bool):
+            raise TypeError(f"first_batch: expected None or an int, got {type(first_batch).__name__}")
+        if first_batch < 1:
+            raise ValueError(f"first_batch = {first_batch}: expected None or an int >= 1")
+    if not isinstance(batch_growth, numbers.Real) or isinstance(batch_growth, bool):
+        raise TypeError(f"batch_growth: expected a number, got {type(batch_growth).__name__}")
+    if not math.isfinite(batch_growth) or batch_growth < 1.0:
+        raise ValueError(f"batch_growth = {batch_growth}: expected a finite number >= 1")
+    return first_batch, float(batch_growth)
+
+
+def _long_jobs(chunks, max_batch, a, sizes=None):
+    """long_plan / long_stream_plan: the chunks in text order, cut into consecutive groups of `sizes` (an iterable of group sizes, each clipped to
+    [1, min(max_batch, 64)]; None: every group is that step) and each group as a job."""
+    import itertools
     step = max(1, min(int(max_batch), ops.WAVE_JOIN_MAX_ROWS))
     rate = 1.0 if a["speed"] is None else a["speed"]
     gap = lambda para_end: int(round((a["paragraph_pause"] if para_end else a["pause"]) * S3GEN_SR / rate))
-    groups = [list(range(lo, min(lo + step, len(chunks)))) for lo in range(0, len(chunks), step)]
+    groups, lo = [], 0
+    for size in itertools.repeat(step) if sizes is None else sizes:
+        if lo >= len(chunks):
+            break
+        size = max(1, min(int(size), step))
+        groups.append(list(range(lo, min(lo + size, len(chunks)))))
+        lo += size
     jobs = []
     for g, idx in enumerate(groups):
         job = dict(chunks=idx, join=dict(gaps=[gap(chunks[k][1]) for k in idx], trim_db=a["trim_db"], pad_frames=a["trim_pad"], fade=a["join_fade"], first=g == 0,
@@ -354,6 +375,31 @@ def long_plan(chunks, max_batch, a):
             job["speed"] = [a["speed"]] * len(idx)
         jobs.append(job)
     return jobs
+
+
+def long_plan(chunks, max_batch, a):
+    """The jobs of a generate_long call, WITHOUT their tokens and voices: chunks = split_text's list, a = _long_args' dict.  Chunks keep the text's order (no length
+    sort: a piece is a run of consecutive chunks) and are cut into consecutive device batches of at most max_batch (and at most 64, the join's row limit).  Per job:
+    dict(chunks=[indices], join=the engines' join dict, seeds=[...] if seeded, speed=[...] if not 1.0).  The gap behind a chunk is round(pause * 24000 / speed)
+    samples, paragraph_pause behind a paragraph's last chunk; the first job carries first=True, the last one last=True."""
+    return _long_jobs(chunks, max_batch, a)
+
+
+def long_stream_plan(chunks, max_batch, a, first_batch=1, batch_growth=2.0):
+    """The jobs of a generate_long_stream call: long_plan's, with device batches that start small so that the first piece comes early.  With
+    step = min(max_batch, 64) the group sizes are s_0 = min(first_batch, step), s_(g+1) = min(step, max(s_g, ceil(s_g * batch_growth))); chunks stay in text order,
+    and gaps, first / last, chunk seeds and speed are exactly long_plan's.  first_batch=None IS long_plan."""
+    import math
+    if first_batch is None:
+        return long_plan(chunks, max_batch, a)
+    step = max(1, min(int(max_batch), ops.WAVE_JOIN_MAX_ROWS))
+
+    def sizes():
+        size = min(int(first_batch), step)
+        while True:
+            yield size
+            size = min(step, max(size, math.ceil(size * batch_growth)))
+    return _long_jobs(chunks, max_batch, a, sizes())
 
 
 # T3 cond dicts of a voice, kept while its T3Cond lives (generate_batch): id(T3Cond) -> [emotion tensor the entry was built from, its value, {exaggeration: dict}]
@@ -560,8 +606,12 @@ class _TTS(_Finish):
         """(wavs or joined piece, speech tokens) of every job, in order: several jobs run the throughput schedule (synthesize_pipelined) where the engine has one;
         one job, or an engine without it, the serial schedule (synthesize), one job after the other."""
         if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined"):
-            for r in self.engine.synthesize_pipelined(jobs, **synth_kw):
-                yield r[0], r[1]
+            results = self.engine.synthesize_pipelined(jobs, **synth_kw)
+            try:
+                for r in results:
+                    yield r[0], r[1]
+            finally:  # closed with this generator (generate_long_stream): the engine's own `finally` runs now, not when the garbage is collected
+                getattr(results, "close", lambda: None)()
             return
         for job in jobs:
             job = dict(job)
@@ -618,16 +668,49 @@ class _TTS(_Finish):
                 out[i] = self._finish(w, fmt)
         return out
 
-    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, fmt=None, loudness=None, **prepare_kw):
+    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, fmt=None, loudness=None, ramp=None, **prepare_kw):
         """generate_long behind its signature and _long_args: the remaining checks, the voice as generate() prepares it, then _run_long.  samp / unsampled: as
-        _generate_batch takes them, one number each."""
+        _generate_batch takes them, one number each.  ramp (_long_stream_args' pair): generate_long_stream -- the same checks and the same voice, all of it when
+        the method is CALLED, then the generator of _stream_long."""
         if not isinstance(text, str):
             raise TypeError(f"text: expected a str, got {type(text).__name__}")
         _long_numbers(**unsampled, **samp)
         loud = _one_loudness(loudness)
         self._use_voice(audio_prompt_path, unsampled["exaggeration"], **prepare_kw)
         self._warn_ignored(*unsampled.values())
-        return self._run_long(text, a, lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id)), samp, return_segments, fmt, loud)
+        tokenize = lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id))
+        if ramp is not None:
+            return self._stream_long(*self._long_work(text, a, tokenize, samp, ramp), a, return_segments, fmt, loud)
+        return self._run_long(text, a, tokenize, samp, return_segments, fmt, loud)
+
+    def _long_work(self, text, a, tokenize, samp, ramp=None):
+        """(chunks, plan, engine jobs) of a long-form call: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), long_plan -- long_stream_plan with
+        a ramp (first_batch, batch_growth)"""
+        chunks = split_text(text, a["max_chars"])
+        tokens = [tokenize(c) for c, _ in chunks]
+        max_batch = int(self.max_batch or self.engine.t3.MAX_BATCH)
+        plan = long_plan(chunks, max_batch, a) if ramp is None else long_stream_plan(chunks, max_batch, a, *ramp)
+        t3, gen = self.conds.t3.as_dict(), self.conds.gen
+        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join") if k in p}) for p in plan]
+        return chunks, plan, jobs
+
+    @staticmethod
+    def _long_segments(chunks, p, piece, st, base):
+        """The segment records of one joined piece that begins at sample `base` of the whole"""
+        out = []
+        for r, k in enumerate(p["chunks"]):
+            a0, b0 = piece["edges"][r]
+            out.append(dict(text=chunks[k][0], start=base + piece["offsets"][r], stop=base + piece["offsets"][r] + (b0 - a0), src_start=a0, src_stop=b0,
+                            tokens=None if st is None else st[r], truncated=bool(piece["truncated"][r])))
+        return out
+
+    @staticmethod
+    def _warn_truncated(who, truncated, max_chars):
+        cut = [k for k, t in enumerate(truncated) if t]
+        if cut:
+            import logging
+            logging.getLogger(__name__).warning("%s: chunk(s) %s of %d reached the speech-token budget without an end-of-speech token and are cut "
+                                                "off; use a smaller max_chars (now %d)", who, cut, len(truncated), max_chars)
 
     def _run_long(self, text, a, tokenize, samp, return_segments, fmt=None, loud=None):
         """generate_long behind its validation: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), run the jobs of long_plan (_run_jobs), concatenate
@@ -635,30 +718,60 @@ class _TTS(_Finish):
         _finish (host -> device -> host; no converter state travels through the joined pieces on the device), and the segments' start / stop become output samples,
         ceil(s U / D), so the last stop is the length; src_start / src_stop stay 24 kHz samples.  loud (a LUFS target or None): the engine jobs do not carry it
         either -- the concatenated waveform is measured and gained as ONE signal in _finish, ahead of the watermark, so the chunks keep their relative level."""
-        chunks = split_text(text, a["max_chars"])
-        tokens = [tokenize(c) for c, _ in chunks]
-        plan = long_plan(chunks, int(self.max_batch or self.engine.t3.MAX_BATCH), a)
-        t3, gen = self.conds.t3.as_dict(), self.conds.gen
-        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join") if k in p}) for p in plan]
+        chunks, plan, jobs = self._long_work(text, a, tokenize, samp)
         pieces, segments, base = [], [], 0
         for p, (piece, st) in zip(plan, self._run_jobs(jobs, self._synth_kw())):
             pieces.append(piece["wav"].detach().float().cpu())
             assert pieces[-1].numel() == piece["total"], "a joined piece and its layout record disagree"
-            for r, k in enumerate(p["chunks"]):
-                a0, b0 = piece["edges"][r]
-                segments.append(dict(text=chunks[k][0], start=base + piece["offsets"][r], stop=base + piece["offsets"][r] + (b0 - a0), src_start=a0, src_stop=b0,
-                                     tokens=None if st is None else st[r], truncated=bool(piece["truncated"][r])))
+            segments += self._long_segments(chunks, p, piece, st, base)
             base += piece["total"]
-        cut = [k for k, s in enumerate(segments) if s["truncated"]]
-        if cut:
-            import logging
-            logging.getLogger(__name__).warning("generate_long: chunk(s) %s of %d reached the speech-token budget without an end-of-speech token and are cut "
-                                                "off; use a smaller max_chars (now %d)", cut, len(segments), a["max_chars"])
+        self._warn_truncated("generate_long", [s["truncated"] for s in segments], a["max_chars"])
         wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=loud)
         if fmt is not None:
             for seg in segments:
                 seg.update(start=ops.formatted_len(seg["start"], fmt["sample_rate"]), stop=ops.formatted_len(seg["stop"], fmt["sample_rate"]))
         return (wav, segments) if return_segments else wav
+
+    def _stream_long(self, chunks, plan, jobs, a, return_segments, fmt=None, loud=None):
+        """generate_long_stream behind its validation, a generator: the jobs run through _run_jobs -- while the consumer holds piece k the throughput schedule has
+        the T3 of pieces k + 1 and k + 2 in flight --, and every joined piece is finished and yielded as it leaves the device.  Per piece, in this order:
+        loudness (loud: upload, ONE ops.WaveLoudnessStream held here measures pieces 0 .. k, ops.wave_gain with its gain, ceiling 1.0; engine.last_loudness = the
+        latest stats), the watermark if a watermarker is loaded, the format (ONE ops.WaveFormatStream held here, final on the last piece; the engine jobs do not
+        carry it).  With neither a piece costs what generate_long's costs: one copy to the host.  Closing the generator closes _run_jobs, and with it the
+        engine's synthesize_pipelined (its `finally` returns the T3 engines)."""
+        dev, scope = self._device_scope()
+        run = self._run_jobs(jobs, self._synth_kw())
+        meter = conv = None
+        base, truncated = 0, []
+        try:
+            for g, (p, (piece, st)) in enumerate(zip(plan, run)):
+                wav = piece["wav"].detach().float().cpu()
+                assert wav.numel() == piece["total"], "a joined piece and its layout record disagree"
+                segments = self._long_segments(chunks, p, piece, st, base)
+                base += piece["total"]
+                truncated += [s["truncated"] for s in segments]
+                on_dev = None  # the piece on the device, while the host copy `wav` is the same samples
+                if loud is not None and wav.numel():
+                    with scope:
+                        on_dev = wav.to(dev).contiguous()
+                        meter = meter or ops.WaveLoudnessStream(1, dev)
+                        stats, gain = meter.push([on_dev], [float(loud)], 1.0)
+                        ops.wave_gain([on_dev], gain)
+                        self.engine.last_loudness = stats
+                        wav = on_dev.cpu()
+                if self.watermarker is not None and wav.numel():
+                    wav, on_dev = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr)), None
+                if fmt is not None:
+                    with scope:
+                        conv = conv or ops.WaveFormatStream(1, fmt, dev)
+                        wav = conv.push([wav.to(dev) if on_dev is None else on_dev], [g == len(plan) - 1])[0].cpu()
+                    for seg in segments:
+                        seg.update(start=ops.formatted_len(seg["start"], fmt["sample_rate"]), stop=ops.formatted_len(seg["stop"], fmt["sample_rate"]))
+                if wav.numel() or (return_segments and segments):
+                    yield (wav.unsqueeze(0), segments) if return_segments else wav.unsqueeze(0)
+        finally:
+            run.close()
+            self._warn_truncated("generate_long_stream", truncated, a["max_chars"])
 
 
 class _LlamaTTS(_TTS):
@@ -767,6 +880,32 @@ class ChatterboxTTS(_LlamaTTS):
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
+    def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
+                             max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
+                             sample_rate=None, encoding=None, loudness=None, first_batch=1, batch_growth=2.0):
+        """generate_long() in pieces: a generator of (1, n) CPU tensors, one per device batch as it leaves the device (empty pieces left out); concatenated along
+        dim 1 they are the long-form result.  Every argument of generate_long with its meaning and default, plus the ramp of the device batches:
+        first_batch (None, or an int >= 1) and batch_growth (a finite number >= 1): the batches hold s_0 = min(first_batch, step) chunks, then
+        s_(g+1) = min(step, max(s_g, ceil(s_g * batch_growth))), step = min(max_batch, 64) (long_stream_plan), so the first piece is one chunk's work and the
+        later ones fill the device.  first_batch=None is generate_long's own plan: the pieces then concatenate to generate_long bit for bit (same seed).  The
+        defaults 1 / 2.0 are UNMEASURED choices.  Everything is validated, and the voice prepared, when this method is CALLED, not at the first next().
+        While the consumer holds piece k the throughput schedule has the T3 of the next two batches in flight; closing the generator early returns the engines at
+        once.  The truncation warning is issued once, when the stream ends.
+        return_segments=True: (wav, segments) per piece, `segments` the records of that piece's chunks with generate_long's keys; start / stop count samples of the
+        whole stream.
+        loudness: piece k is multiplied by the gain the one-shot meter gives for pieces 0 .. k of the ungained signal, limited to a sample peak of 1.0 -- the
+        "integrated so far" reading of a live meter (ops.WaveLoudnessStream: bit for bit ops.wave_loudness of the concatenation).  The step between two gains falls
+        at a piece boundary, where the join left a pause of zeros followed by a fade-in, so it makes no click; with pause=0 or join_fade=0 it DOES fall on signal.
+        A first piece under 0.4 s, or a silent one, gets gain 1.  The result is not generate_long(loudness=)'s, which knows the whole signal -- except for a text of
+        one piece.  The watermarker, if loaded, is applied per piece, as generate_stream does.
+        sample_rate, encoding: every piece goes through ONE ops.WaveFormatStream, so the pieces add up to the conversion of the whole bit for bit.  A piece that is
+        not the last holds the resampling filter's tail back: a segment's last samples may arrive with the NEXT piece."""
+        fmt = ops.check_format(sample_rate, encoding)
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
+        ramp = _long_stream_args(first_batch, batch_growth)
+        samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
+
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
                        min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
@@ -865,6 +1004,17 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
+
+    def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
+                             top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
+                             return_segments=False, sample_rate=None, encoding=None, loudness=None, first_batch=1, batch_growth=2.0):
+        """ChatterboxTTS.generate_long_stream with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
+        fmt = ops.check_format(sample_rate, encoding)
+        lid = _language(language_id)
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
+        ramp = _long_stream_args(first_batch, batch_growth)
+        samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):
@@ -978,6 +1128,18 @@ class ChatterboxTurboTTS(_TTS):
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), fmt,
                                    loudness, norm_loudness=norm_loudness)
+
+    def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
+                             top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None,
+                             speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, first_batch=1, batch_growth=2.0):
+        """ChatterboxTTS.generate_long_stream on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other, so a piece is
+        yielded before the next batch starts)."""
+        fmt = ops.check_format(sample_rate, encoding)
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
+        ramp = _long_stream_args(first_batch, batch_growth)
+        samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), fmt,
+                                   loudness, ramp, norm_loudness=norm_loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
                        top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None):

@@ -25,6 +25,13 @@
 //
 // Gain: workgroups (x, r) multiply row r by gain[r] in place: 16-byte accesses counted from the 16-byte boundary at or below the row's first sample, 4-byte
 // accesses at the ragged ends; nothing outside the rows is touched.
+//
+// The running meter (cbx_wave_loudness_push_f32): the same meter fed piece by piece.  Per row a record on the device -- the cascade's state on entry to the first
+// segment that is not complete, the running peak, the table of the E_s -- and the t = n0 mod hop samples of that segment in a tail buffer (two, ping-pong).  The
+// whole segments of tail ++ piece go through the SAME per-segment code as above (wl_segment, a template over where sample i comes from: -ffp-contract=on fuses per
+// source expression, so one source is one arithmetic), the chain starts from the record's state instead of zero, and the row step reads the record's table: after
+// any sequence of pushes the numbers are bit for bit the one-shot meter's over the concatenation.  One workgroup per row also takes max |piece| into the running
+// peak and copies the (t + L) mod hop left-over samples to the other tail buffer.
 #include <math.h>
 
 #include "cbx_common.h"
@@ -48,6 +55,22 @@ struct wl_pow_t {
 struct wl_target_t {
     double t[WL_MAX_ROWS];
 };
+struct wl_n0_t {
+    long v[WL_MAX_ROWS];  // samples a running meter has consumed, per row
+};
+constexpr int WL_REC = 8;  // doubles of a running meter's record ahead of its E table: state[4], peak, three zeros
+
+// where sample i of a segment pass comes from: a row of the batch, or the virtual signal tail[0, t) ++ piece of a running meter
+struct wl_src_row_t {
+    const float* p;
+    __device__ __forceinline__ float operator()(long i) const { return p[i]; }
+};
+struct wl_src_cat_t {
+    const float* tail;
+    const float* p;
+    long t;
+    __device__ __forceinline__ float operator()(long i) const { return i < t ? tail[i] : p[i - t]; }
+};
 
 __device__ __forceinline__ bool wl_finite(double v) { return fabs(v) < INFINITY; }
 
@@ -69,22 +92,21 @@ __device__ __forceinline__ void wl_mac(const double* M, const double* t, double*
 
 // Workspace, in doubles, ld = segments of the longest row: [0, 4 R ld) the segment states (r ld + s) * 4 + q -- the zero-state end state v_s after pass 0, the
 // incoming state s_s after the chain --, then E at 4 R ld + r ld + s and the segments' peaks at 5 R ld + r ld + s.
-// grid (ceil(segments / 4), R) x 256: wave w of workgroup (x, r) owns segment 4 x + w of row r.  fin = 0: v_s of every whole segment; fin = 1: E_s and the peak
-__global__ __launch_bounds__(256) void wave_loud_seg_kernel(const float* __restrict__ wav, wl_rows_t rows, int R, wl_coef_t k, wl_pow_t pw, int hop, int fin,
-                                                            double* __restrict__ ws, long ld) {
-    const int r = blockIdx.y, lane = threadIdx.x & 63;
-    const long s = (long)blockIdx.x * 4 + (long)(threadIdx.x >> 6);
-    const long n = rows.n[r], s0 = s * hop;
+// One WAVE on segment s of the n samples x(0 .. n): fin = 0: v_s of a whole segment -> state; fin = 1: entered at `state`, E_s -> *e_out and the segment's peak ->
+// *p_out (p_out NULL: no peaks are kept, and an incomplete segment is nobody's business)
+template <class Src>
+__device__ __forceinline__ void wl_segment(const Src& x, long n, long s, const wl_coef_t& k, const wl_pow_t& pw, int hop, int fin, double* state, double* e_out,
+                                           double* p_out) {
+    const int lane = threadIdx.x & 63;
+    const long s0 = s * hop;
     if (s0 >= n) return;  // (wave-uniform, as every branch below that holds a lane exchange)
     const long cnt = n - s0 < hop ? n - s0 : (long)hop;
     const bool whole = cnt == hop;
-    if (!fin && !whole) return;
-    const float* p = wav + rows.off[r];
+    if (!whole && (!fin || !p_out)) return;
     const long c = (hop + 63) / 64;
     long a = s0 + lane * c, b = a + c;
     b = b < s0 + cnt ? b : s0 + cnt;
     a = a < b ? a : b;
-    double* state = ws + ((long)r * ld + s) * 4;
     double e = 0.0;
     float pk = 0.0f;
     int bad = 0;
@@ -93,7 +115,7 @@ __global__ __launch_bounds__(256) void wave_loud_seg_kernel(const float* __restr
         if (fin && lane == 0)
             for (int q = 0; q < 4; ++q) in[q] = state[q];
         for (int q = 0; q < 4; ++q) v[q] = in[q];
-        for (long i = a; i < b; ++i) wl_step(k, v, (double)p[i]);
+        for (long i = a; i < b; ++i) wl_step(k, v, (double)x(i));
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             for (int q = 0; q < 4; ++q) t[q] = __shfl_up(v[q], 1u << i);
@@ -104,23 +126,23 @@ __global__ __launch_bounds__(256) void wave_loud_seg_kernel(const float* __restr
             for (int q = 0; q < 4; ++q) in[q] = t[q];
         if (!fin) {
             if (lane == (int)((hop - 1) / c)) {  // the last lane with samples: the segment's end state
-                for (long i = a; i < b; ++i) wl_step(k, in, (double)p[i]);
+                for (long i = a; i < b; ++i) wl_step(k, in, (double)x(i));
                 for (int q = 0; q < 4; ++q) state[q] = in[q];
             }
             return;
         }
         for (long i = a; i < b; ++i) {
-            const float x = p[i];
-            const double y = wl_step(k, in, (double)x);
+            const float xi = x(i);
+            const double y = wl_step(k, in, (double)xi);
             e += y * y;
-            pk = fmaxf(pk, fabsf(x));
-            bad |= !(x == x);
+            pk = fmaxf(pk, fabsf(xi));
+            bad |= !(xi == xi);
         }
     } else {  // the incomplete segment at the end of a row belongs to no block: its peak only
         for (long i = a; i < b; ++i) {
-            const float x = p[i];
-            pk = fmaxf(pk, fabsf(x));
-            bad |= !(x == x);
+            const float xi = x(i);
+            pk = fmaxf(pk, fabsf(xi));
+            bad |= !(xi == xi);
         }
     }
     for (int m = 32; m >= 1; m >>= 1) {
@@ -129,18 +151,34 @@ __global__ __launch_bounds__(256) void wave_loud_seg_kernel(const float* __restr
         bad |= __shfl_xor(bad, m);
     }
     if (lane == 0) {
-        ws[(4l * R + r) * ld + s] = e;
-        ws[(5l * R + r) * ld + s] = bad ? (double)NAN : (double)pk;
+        *e_out = e;
+        if (p_out) *p_out = bad ? (double)NAN : (double)pk;
     }
 }
 
-// grid R x 256: v_s -> the incoming state s_s of every whole segment of row r, in place: s_0 = 0, s_(k+1) = A^hop s_k + v_k
-__global__ __launch_bounds__(256) void wave_loud_chain_kernel(wl_rows_t rows, wl_pow_t pw, int hop, double* __restrict__ ws, long ld) {
-    __shared__ double sm[4 * WL_CHAIN];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const long S = rows.n[r] / hop;
-    double* st = ws + (long)r * ld * 4;
-    double cur[4] = {0.0, 0.0, 0.0, 0.0};  // (lane 0's)
+// grid (ceil(segments / 4), R) x 256: wave w of workgroup (x, r) owns segment 4 x + w of row r.  fin = 0: v_s of every whole segment; fin = 1: E_s and the peak
+__global__ __launch_bounds__(256) void wave_loud_seg_kernel(const float* __restrict__ wav, wl_rows_t rows, int R, wl_coef_t k, wl_pow_t pw, int hop, int fin,
+                                                            double* __restrict__ ws, long ld) {
+    const int r = blockIdx.y;
+    const long s = (long)blockIdx.x * 4 + (long)(threadIdx.x >> 6);
+    wl_segment(wl_src_row_t{wav + rows.off[r]}, (long)rows.n[r], s, k, pw, hop, fin, ws + ((long)r * ld + s) * 4, ws + (4l * R + r) * ld + s, ws + (5l * R + r) * ld + s);
+}
+
+// The running meter's launch of the same: grid (ceil(K_max / 4), R) x 256 over the K_r whole segments of tail_r[0, t_r) ++ piece_r.  ws: the segment states alone,
+// (r ld + s) * 4 + q, ld = K_max; E_(S0 + s) goes to the row's record rec + r rec_ld
+__global__ __launch_bounds__(256) void wave_loud_push_seg_kernel(const float* __restrict__ wav, wl_rows_t rows, wl_n0_t n0, const float* __restrict__ tail, wl_coef_t k,
+                                                                 wl_pow_t pw, int hop, int fin, double* __restrict__ ws, long ld, double* __restrict__ rec, long rec_ld) {
+    const int r = blockIdx.y;
+    const long s = (long)blockIdx.x * 4 + (long)(threadIdx.x >> 6);
+    const long t = n0.v[r] % hop, S0 = n0.v[r] / hop, n = t + rows.n[r];
+    if (s >= n / hop) return;  // (wave-uniform) whole segments only: s < K_r <= ld, S0 + s < seg_cap
+    wl_segment(wl_src_cat_t{tail + (long)r * hop, wav + rows.off[r], t}, n, s, k, pw, hop, fin, ws + ((long)r * ld + s) * 4, rec + (long)r * rec_ld + WL_REC + S0 + s,
+               (double*)nullptr);
+}
+
+// v_s -> the incoming state s_s of the S segments at st, in place: s_0 = cur (thread 0's), s_(k+1) = A^hop s_k + v_k; cur leaves as s_S
+__device__ __forceinline__ void wl_chain(double* sm, double* st, long S, const wl_pow_t& pw, double* cur) {
+    const int tid = threadIdx.x;
     for (long k0 = 0; k0 < S; k0 += WL_CHAIN) {
         const int m = S - k0 < WL_CHAIN ? (int)(S - k0) : WL_CHAIN;
         for (int i = tid; i < 4 * m; i += 256) sm[i] = st[4 * k0 + i];
@@ -159,6 +197,56 @@ __global__ __launch_bounds__(256) void wave_loud_chain_kernel(wl_rows_t rows, wl
     }
 }
 
+// grid R x 256: the chain over every whole segment of row r, from zero state
+__global__ __launch_bounds__(256) void wave_loud_chain_kernel(wl_rows_t rows, wl_pow_t pw, int hop, double* __restrict__ ws, long ld) {
+    __shared__ double sm[4 * WL_CHAIN];
+    const int r = blockIdx.x;
+    double cur[4] = {0.0, 0.0, 0.0, 0.0};  // (lane 0's)
+    wl_chain(sm, ws + (long)r * ld * 4, rows.n[r] / hop, pw, cur);
+}
+
+// grid R x 256, the running meter's row r: the chain over its K new segments from the record's state, which becomes the state on entry to segment S0 + K; the
+// running peak takes max |piece| (NaN once a NaN was seen); the (t + L) mod hop samples behind the last whole segment go to the OTHER tail buffer
+__global__ __launch_bounds__(256) void wave_loud_push_chain_kernel(const float* __restrict__ wav, wl_rows_t rows, wl_n0_t n0, const float* __restrict__ tail_in,
+                                                                   float* __restrict__ tail_out, wl_pow_t pw, int hop, double* __restrict__ ws, long ld,
+                                                                   double* __restrict__ rec, long rec_ld) {
+    __shared__ double sm[4 * WL_CHAIN];
+    __shared__ float s_pk[256];
+    __shared__ int s_nan[256];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const long t = n0.v[r] % hop, L = rows.n[r], K = (t + L) / hop;
+    const float* p = wav + rows.off[r];
+    double* R0 = rec + (long)r * rec_ld;
+    double cur[4] = {0.0, 0.0, 0.0, 0.0};
+    if (tid == 0)
+        for (int q = 0; q < 4; ++q) cur[q] = R0[q];
+    wl_chain(sm, ws + (long)r * ld * 4, K, pw, cur);
+    if (tid == 0 && K > 0)
+        for (int q = 0; q < 4; ++q) R0[q] = cur[q];
+    float pk = 0.0f;
+    int bad = 0;
+    for (long i = tid; i < L; i += 256) {
+        const float x = p[i];
+        pk = fmaxf(pk, fabsf(x));
+        bad |= !(x == x);
+    }
+    s_pk[tid] = pk, s_nan[tid] = bad;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if (tid < s) s_pk[tid] = fmaxf(s_pk[tid], s_pk[tid + s]), s_nan[tid] |= s_nan[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0 && L > 0) {
+        const double old = R0[4];
+        R0[4] = (s_nan[0] || !(old == old)) ? (double)NAN : fmax(old, (double)s_pk[0]);
+    }
+    const long rem = t + L - K * hop;  // (< hop)
+    for (long j = tid; j < rem; j += 256) {
+        const long i = K * hop + j;
+        tail_out[(long)r * hop + j] = i < t ? tail_in[(long)r * hop + i] : p[i - t];
+    }
+}
+
 // sum of v over the workgroup in a fixed order; every thread gets it
 __device__ __forceinline__ double wl_block_sum(double* sm, int tid, double v) {
     __syncthreads();
@@ -171,21 +259,23 @@ __device__ __forceinline__ double wl_block_sum(double* sm, int tid, double v) {
     return sm[0];
 }
 
-// grid R x 256: blocks, gates, L, peak and gain of row r
+// grid R x 256: blocks, gates, L, peak and gain of row r.  PUSH (the running meter): ws is the records, ld their stride, rows.n[r] the SEGMENTS of row r so far,
+// and the peak is the record's
+template <bool PUSH>
 __global__ __launch_bounds__(256) void wave_loud_row_kernel(wl_rows_t rows, int R, int hop, wl_target_t target, double ceiling, const double* __restrict__ ws, long ld,
                                                             double* __restrict__ stats, float* __restrict__ gain) {
     __shared__ double sm[256];
     __shared__ int s_bad[256], s_nan[256];
     const int r = blockIdx.x, tid = threadIdx.x;
     const long n = rows.n[r];
-    const long S = n / hop, nseg = (n + hop - 1) / hop;
-    const double* E = ws + (4l * R + r) * ld;
-    const double* P = ws + (5l * R + r) * ld;
+    const long S = PUSH ? n : n / hop, nseg = PUSH ? n : (n + hop - 1) / hop;
+    const double* E = PUSH ? ws + (long)r * ld + WL_REC : ws + (4l * R + r) * ld;
+    const double* P = ws + (5l * R + r) * ld;  // (not read by PUSH)
     double pk = 0.0;
     int pnan = 0;
     long bad = S;  // the first segment whose E is not finite
     for (long s = tid; s < nseg; s += 256) {
-        const double v = P[s];
+        const double v = PUSH ? 0.0 : P[s];
         pnan |= !(v == v);
         pk = fmax(pk, v);
         if (s < S && !wl_finite(E[s])) bad = s < bad ? s : bad;
@@ -200,7 +290,7 @@ __global__ __launch_bounds__(256) void wave_loud_row_kernel(wl_rows_t rows, int 
         }
         __syncthreads();
     }
-    const double peak = s_nan[0] ? (double)NAN : sm[0];
+    const double peak = PUSH ? ws[(long)r * ld + 4] : (s_nan[0] ? (double)NAN : sm[0]);
     bad = s_bad[0];
     const long nb = S >= 4 ? S - 3 : 0;
     const double den = 4.0 * (double)hop;
@@ -293,6 +383,29 @@ void wl_matpow(const double* a, long e, double* o) {
     }
 }
 
+// the caller's coefficients, all finite -> *k
+int wl_coefs(const char* who, const double* coef, wl_coef_t* k) {
+    for (int i = 0; i < 10; ++i) {
+        CBX_REQUIRE(fabs(coef[i]) < INFINITY, "%s: coefficient %d is not finite", who, i);
+        k->c[i] = coef[i];
+    }
+    return 0;
+}
+
+// the powers of the cascade's transition matrix the kernels take by value
+void wl_powers(const wl_coef_t& k, int hop, wl_pow_t* pw) {
+    double A[16];
+    for (int j = 0; j < 4; ++j) {  // column j of A: one step of the cascade on unit vector j with a zero sample
+        double st[4] = {0.0, 0.0, 0.0, 0.0};
+        st[j] = 1.0;
+        wl_step(k, st, 0.0);
+        for (int q = 0; q < 4; ++q) A[4 * q + j] = st[q];
+    }
+    wl_matpow(A, (hop + 63) / 64, pw->m[0]);
+    for (int i = 1; i < 6; ++i) wl_matmul(pw->m[i - 1], pw->m[i - 1], pw->m[i]);
+    wl_matpow(A, hop, pw->m[6]);
+}
+
 }  // namespace
 
 extern "C" int cbx_wave_loudness_f32(const float* wav, const long* row_off, const int* row_len, int R, const double* coef, int hop, const double* target,
@@ -304,10 +417,7 @@ extern "C" int cbx_wave_loudness_f32(const float* wav, const long* row_off, cons
     CBX_REQUIRE(wav && coef && target && stats && gain && ws, "wave_loudness: null pointer");
     CBX_REQUIRE(hop >= 1, "wave_loudness: hop = %d (a tenth of a second in samples, at least 1)", hop);
     wl_coef_t k;
-    for (int i = 0; i < 10; ++i) {
-        CBX_REQUIRE(fabs(coef[i]) < INFINITY, "wave_loudness: coefficient %d is not finite", i);
-        k.c[i] = coef[i];
-    }
+    if (const int e = wl_coefs("wave_loudness", coef, &k)) return e;
     const long nseg = (n_max + hop - 1) / hop;
     CBX_REQUIRE(ws_cap >= 6l * R * nseg, "wave_loudness: workspace of %ld doubles, %d rows of %ld segments need %ld", ws_cap, R, nseg, 6l * R * nseg);
     wl_target_t tg;
@@ -316,16 +426,7 @@ extern "C" int cbx_wave_loudness_f32(const float* wav, const long* row_off, cons
         const long gx = (nseg + 3) / 4;
         CBX_REQUIRE(gx <= 0x7fffffffl, "wave_loudness: a row of %ld samples is too long for one launch", n_max);
         wl_pow_t pw;
-        double A[16];
-        for (int j = 0; j < 4; ++j) {  // column j of A: one step of the cascade on unit vector j with a zero sample
-            double st[4] = {0.0, 0.0, 0.0, 0.0};
-            st[j] = 1.0;
-            wl_step(k, st, 0.0);
-            for (int q = 0; q < 4; ++q) A[4 * q + j] = st[q];
-        }
-        wl_matpow(A, (hop + 63) / 64, pw.m[0]);
-        for (int i = 1; i < 6; ++i) wl_matmul(pw.m[i - 1], pw.m[i - 1], pw.m[i]);
-        wl_matpow(A, hop, pw.m[6]);
+        wl_powers(k, hop, &pw);
         hipLaunchKernelGGL(wave_loud_seg_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, R, k, pw, hop, 0, ws, nseg);
         int e = cbx_check_launch("wave_loudness");
         if (e) return e;
@@ -334,8 +435,54 @@ extern "C" int cbx_wave_loudness_f32(const float* wav, const long* row_off, cons
         hipLaunchKernelGGL(wave_loud_seg_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, R, k, pw, hop, 1, ws, nseg);
         if ((e = cbx_check_launch("wave_loudness"))) return e;
     }
-    hipLaunchKernelGGL(wave_loud_row_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, R, hop, tg, ceiling, (const double*)ws, nseg, stats, gain);
+    hipLaunchKernelGGL(wave_loud_row_kernel<false>, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, R, hop, tg, ceiling, (const double*)ws, nseg, stats, gain);
     return cbx_check_launch("wave_loudness");
+}
+
+extern "C" int cbx_wave_loudness_push_f32(const float* wav, const long* row_off, const int* row_len, const long* n0, int R, const double* coef, int hop,
+                                          const double* target, double ceiling, double* rec, long seg_cap, const float* tail_in, float* tail_out, double* stats,
+                                          float* gain, double* ws, long ws_cap, void* stream) {
+    wl_rows_t rows;
+    long n_max;
+    const int rc = wl_rows("wave_loudness_push", row_off, row_len, R, &rows, &n_max);
+    if (rc) return rc;
+    CBX_REQUIRE(wav && n0 && coef && target && rec && tail_in && tail_out && stats && gain && ws, "wave_loudness_push: null pointer");
+    CBX_REQUIRE(tail_in != tail_out, "wave_loudness_push: tail_out is tail_in (the two tail buffers alternate)");
+    CBX_REQUIRE(hop >= 1, "wave_loudness_push: hop = %d (a tenth of a second in samples, at least 1)", hop);
+    wl_coef_t k;
+    if (const int e = wl_coefs("wave_loudness_push", coef, &k)) return e;
+    wl_n0_t at;
+    wl_rows_t segs = rows;  // n[r]: the segments of row r after this push
+    long k_max = 0;
+    for (int r = 0; r < WL_MAX_ROWS; ++r) at.v[r] = 0;
+    for (int r = 0; r < R; ++r) {
+        CBX_REQUIRE(n0[r] >= 0, "wave_loudness_push: row %d has consumed %ld samples", r, n0[r]);
+        const long K = (n0[r] % hop + row_len[r]) / hop, S1 = n0[r] / hop + K;
+        CBX_REQUIRE(S1 <= seg_cap && S1 <= 0x7fffffffl, "wave_loudness_push: row %d reaches %ld segments, the record holds %ld", r, S1, seg_cap);
+        at.v[r] = n0[r], segs.n[r] = (int)S1;
+        k_max = K > k_max ? K : k_max;
+    }
+    CBX_REQUIRE(ws_cap >= 4l * R * k_max, "wave_loudness_push: workspace of %ld doubles, %d rows of %ld new segments need %ld", ws_cap, R, k_max, 4l * R * k_max);
+    wl_target_t tg;
+    for (int r = 0; r < WL_MAX_ROWS; ++r) tg.t[r] = r < R ? target[r] : (double)NAN;
+    const long rec_ld = WL_REC + seg_cap, gx = (k_max + 3) / 4;
+    wl_pow_t pw = {};
+    int e;
+    if (k_max > 0) {
+        wl_powers(k, hop, &pw);
+        hipLaunchKernelGGL(wave_loud_push_seg_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, at, tail_in, k, pw, hop, 0, ws, k_max,
+                           rec, rec_ld);
+        if ((e = cbx_check_launch("wave_loudness_push"))) return e;
+    }
+    hipLaunchKernelGGL(wave_loud_push_chain_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, at, tail_in, tail_out, pw, hop, ws, k_max, rec, rec_ld);
+    if ((e = cbx_check_launch("wave_loudness_push"))) return e;
+    if (k_max > 0) {
+        hipLaunchKernelGGL(wave_loud_push_seg_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, at, tail_in, k, pw, hop, 1, ws, k_max,
+                           rec, rec_ld);
+        if ((e = cbx_check_launch("wave_loudness_push"))) return e;
+    }
+    hipLaunchKernelGGL(wave_loud_row_kernel<true>, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, segs, R, hop, tg, ceiling, (const double*)rec, rec_ld, stats, gain);
+    return cbx_check_launch("wave_loudness_push");
 }
 
 extern "C" int cbx_wave_gain_f32(float* wav, const long* row_off, const int* row_len, int R, const float* gain, void* stream) {

@@ -1345,6 +1345,68 @@ def wave_loudness(rows, target=None, ceiling=1.0, fs=WAVE_IN_RATE):
     return stats, gain
 
 
+def wave_loudness_push(meter, rows, target=None, ceiling=1.0):
+    """cbx_wave_loudness_push_f32 on the current stream: the rows' new pieces (_wave_rows: R 1-D fp32 views of ONE allocation; an empty row: nothing new) enter
+    `meter` (a WaveLoudnessStream of R rows, which owns the records, the two tails, n0 and the workspace and is advanced here).  target, ceiling: wave_loudness's.
+    Returns (stats, gain) on the device as wave_loudness does -- bit for bit what wave_loudness gives for each row's pieces so far, concatenated.  Nothing is
+    synchronised.  A push that would pass the meter's seg_cap is refused by the entry (-22): WaveLoudnessStream.push grows the record first."""
+    base, offs, lens = _wave_rows(rows, "wave_loudness_push")
+    R, dev, f = len(lens), rows[0].device, meter.f
+    if R != meter.R:
+        raise ValueError(f"wave_loudness_push: {R} rows for a meter of {meter.R}")
+    if target is None or not isinstance(target, (list, tuple)):
+        target = [target] * R
+    if len(target) != R:
+        raise ValueError(f"wave_loudness_push: {len(target)} targets for {R} rows")
+    tg = (ctypes.c_double * R)(*[float("nan") if t is None else float(t) for t in target])
+    coef = (ctypes.c_double * 10)(*f["coef"].tolist())
+    n0 = (ctypes.c_long * R)(*meter.n0)
+    k_max = max((a % f["hop"] + int(n)) // f["hop"] for a, n in zip(meter.n0, lens))
+    if meter.ws.numel() < 4 * R * k_max:
+        meter.ws = torch.empty(4 * R * k_max, dtype=torch.float64, device=dev)
+    stats = torch.empty(R, 4, dtype=torch.float64, device=dev)
+    gain = torch.empty(R, dtype=torch.float32, device=dev)
+    check(lib.cbx_wave_loudness_push_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(n0), R, ctypes.addressof(coef), f["hop"],
+                                         ctypes.addressof(tg), 0.0 if ceiling is None else float(ceiling), _p(meter.rec), meter.seg_cap, _p(meter.tail[meter.cur]),
+                                         _p(meter.tail[1 - meter.cur]), _p(stats), _p(gain), _p(meter.ws), meter.ws.numel(), _stream()), "cbx_wave_loudness_push_f32")
+    meter.cur = 1 - meter.cur
+    meter.n0 = [a + int(n) for a, n in zip(meter.n0, lens)]
+    return stats, gain
+
+
+class WaveLoudnessStream:
+    """cbx_wave_loudness_push_f32 over the pieces of R signals that arrive one after the other: a running BS.1770-4 meter.  Per row a device record of 8 + seg_cap
+    doubles (the K-weighting's state on entry to the unfinished 100 ms segment, the running peak, the table of segment energies), two (R, hop) tail buffers
+    (ping-pong) with the unfinished segment's samples, the samples consumed (n0, on the host) and the workspace.  push(rows, target, ceiling) measures in at most
+    four launches; after ANY sequence of pushes its (stats, gain) are bit for bit wave_loudness of each row's concatenated pieces -- the "integrated so far"
+    reading of a live meter.  The record grows by a device copy when a push would pass seg_cap (4096 segments are 6.8 minutes; one hour is 36 000)."""
+
+    def __init__(self, R, device, fs=WAVE_IN_RATE, seg_cap=4096):
+        self.R, self.dev, self.f, self.seg_cap = int(R), torch.device(device), loudness_filter(fs), max(1, int(seg_cap))
+        if not 1 <= self.R <= WAVE_JOIN_MAX_ROWS:
+            raise ValueError(f"WaveLoudnessStream: {self.R} rows (1 .. {WAVE_JOIN_MAX_ROWS})")
+        self.rec = torch.zeros(self.R, 8 + self.seg_cap, dtype=torch.float64, device=self.dev)
+        self.tail = [torch.zeros(self.R, self.f["hop"], device=self.dev) for _ in range(2)]
+        self.ws = torch.empty(4 * self.R, dtype=torch.float64, device=self.dev)
+        self.n0, self.cur = [0] * self.R, 0
+
+    def push(self, rows, target=None, ceiling=1.0):
+        """rows: R 1-D fp32 tensors on the device, views of ONE allocation (None or an empty tensor: nothing new for that row).  Returns wave_loudness_push's
+        (stats, gain)."""
+        rows = list(rows)
+        if len(rows) != self.R:
+            raise ValueError(f"WaveLoudnessStream.push: {len(rows)} rows for {self.R} signals")
+        anchor = next((w for w in rows if w is not None and w.numel()), self.tail[0].view(-1))  # (an empty tensor may have no allocation at all)
+        rows = [anchor[:0] if (w is None or not w.numel()) else w for w in rows]
+        need = max((a + int(w.numel())) // self.f["hop"] for a, w in zip(self.n0, rows))
+        if need > self.seg_cap:
+            cap = max(need, 2 * self.seg_cap)
+            rec = torch.zeros(self.R, 8 + cap, dtype=torch.float64, device=self.dev)
+            rec[:, : 8 + self.seg_cap].copy_(self.rec)
+            self.rec, self.seg_cap = rec, cap
+        return wave_loudness_push(self, rows, target, ceiling)
+
+
 def wave_gain(rows, gain):
     """cbx_wave_gain_f32 on the current stream: row r times gain[r] (an (R,) fp32 device tensor), in place, one launch.  Returns rows."""
     base, offs, lens = _wave_rows(rows, "wave_gain")

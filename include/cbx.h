@@ -906,6 +906,30 @@ int cbx_wave_format_f32(const float* wav, const long* row_off, const int* row_le
  * -22 before any launch: a null pointer, R outside [1, 64], a negative length or offset, hop < 1, a coefficient that is not finite, a workspace that is too small. */
 int cbx_wave_loudness_f32(const float* wav, const long* row_off, const int* row_len, int R, const double* coef, int hop, const double* target, double ceiling,
                           double* stats, float* gain, double* ws, long ws_cap, void* stream);
+/* cbx_wave_loudness_push_f32: the same meter fed piece by piece (a running / streaming loudness; new function, no version step).  The reference has no counterpart:
+ * it levels only Turbo's voice prompt, on the host (tts_turbo.py:223-239).
+ * State of a meter of R rows, R in [1, 64], all of it on the device and owned by the caller:
+ *   rec: R records of 8 + seg_cap doubles: [0..3] the cascade's state on entry to the first segment that is not yet complete, [4] the running sample peak (NaN once
+ *     a NaN was seen), [5..7] zero, then E_0 .. E_(seg_cap-1).  A new meter is all zeros.
+ *   tail_in / tail_out: two buffers of R x hop floats that alternate from push to push (as the histories of cbx_wave_format_f32); row r's n0[r] mod hop samples of
+ *     the unfinished segment are at tail + r hop.  tail_in is only read.
+ *   n0: R HOST longs, the samples row r has consumed so far (the sum of its earlier piece lengths), by value like row_off / row_len.
+ * A push over pieces of L_r = row_len[r] >= 0 samples at wav + row_off[r] (0: nothing new).  With t = n0 mod hop, S0 = n0 div hop and the virtual signal
+ * v = tail_in[0, t) ++ piece[0, L): the K = (t + L) div hop whole segments of v get E_(S0 + k) by the three phases and the per-lane partition of
+ * cbx_wave_loudness_f32 (lane l owns samples [l c, (l + 1) c) of its segment, c = ceil(hop / 64); the zero-state pass; the chain s_(k+1) = A^hop s_k + v_k, which
+ * starts from rec[0..3] instead of 0; the true-state pass with the same xor butterfly) -- one source for both entries, so one arithmetic.  rec[0..3] becomes the state
+ * on entry to segment S0 + K, the last (t + L) mod hop samples of v go to tail_out, rec[4] becomes max(rec[4], max |piece|).  Then the row step of
+ * cbx_wave_loudness_f32 (blocks, both gates, L, gain, ceiling) runs over E_0 .. E_(S0 + K - 1) with the running peak and writes stats (R, 4) and gain (R) as there; a
+ * NaN target is measure only, gain 1.
+ * CONTRACT: after any sequence of pushes, stats, gain and the E table are bit for bit those of cbx_wave_loudness_f32 over each row's concatenated pieces (same
+ * coefficients, target and ceiling).  No floating-point atomics, a fixed order whatever the grid and the rows' alignment, 4-byte accesses at ragged ends; nothing
+ * outside the records, tail_out, stats, gain and the workspace is written.  Four launches (two when no row completes a segment), nothing synchronises the host.
+ * ws: device workspace of ws_cap >= 4 * R * max_r K_r doubles (not NULL; K_r the whole segments this push completes in row r).
+ * -22 before any launch, nothing written: a null pointer, tail_out == tail_in, R outside [1, 64], a negative length, offset or n0, hop < 1, a coefficient that is
+ * not finite, S0 + K > seg_cap for any row, a workspace that is too small. */
+int cbx_wave_loudness_push_f32(const float* wav, const long* row_off, const int* row_len, const long* n0, int R, const double* coef, int hop, const double* target,
+                               double ceiling, double* rec, long seg_cap, const float* tail_in, float* tail_out, double* stats, float* gain, double* ws, long ws_cap,
+                               void* stream);
 /* cbx_wave_gain_f32: wav_r[i] = wav_r[i] * gain[r] for i < n_r, ONE launch (none when every row is empty); gain: R device floats (cbx_wave_loudness_f32's).
  * 16-byte accesses inside a row where alignment allows, 4-byte accesses at the ragged ends; nothing outside the rows is touched.
  * -22 before any launch: a null pointer, R outside [1, 64], a negative length or offset. */
