@@ -173,7 +173,24 @@ int wj_rows(const char* who, const long* row_off, const int* row_len, const int*
     return 0;
 }
 
+// the frame pass of a call: m_f of every frame of every row -> ws[r * nf + f]
+int wj_frame_pass(const char* who, const float* wav, const wj_rows_t& rows, int R, long n_max, long nf, double* ws, void* stream) {
+    const long gx = (nf + 3) / 4;
+    CBX_REQUIRE(gx <= 0x7fffffffl, "%s: a row of %ld samples is too long for one launch", who, n_max);
+    hipLaunchKernelGGL(wave_frame_ms_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, ws, nf);
+    return cbx_check_launch(who);
+}
+
 }  // namespace
+
+// The same frame pass for the pause control (wave_squeeze.hip; declared in cbx_common.h): ONE kernel, so its m_f are those of cbx_wave_edges_f32 bit for bit.
+// The caller has checked the rows (R in [1, 64], lengths and offsets >= 0) and that ws holds R * nf doubles, nf = ceil(max n / 480) > 0.
+int cbx_wave_frame_ms(const char* who, const float* wav, const long* row_off, const int* row_len, int R, long nf, double* ws, void* stream) {
+    wj_rows_t rows;
+    long n_max, n_sum;
+    const int rc = wj_rows(who, row_off, row_len, nullptr, R, &rows, &n_max, &n_sum);
+    return rc ? rc : wj_frame_pass(who, wav, rows, R, n_max, nf, ws, stream);
+}
 
 extern "C" int cbx_wave_edges_f32(const float* wav, const long* row_off, const int* row_len, int R, double ratio, int pad, int* edges, double* ws, long ws_cap,
                                   void* stream) {
@@ -186,10 +203,7 @@ extern "C" int cbx_wave_edges_f32(const float* wav, const long* row_off, const i
     const long nf = (n_max + WJ_FRAME - 1) / WJ_FRAME;
     CBX_REQUIRE(ws_cap >= (long)R * nf, "wave_edges: workspace of %ld doubles, %d rows of %ld frames need %ld", ws_cap, R, nf, (long)R * nf);
     if (nf > 0) {
-        const long gx = (nf + 3) / 4;
-        CBX_REQUIRE(gx <= 0x7fffffffl, "wave_edges: a row of %ld samples is too long for one launch", n_max);
-        hipLaunchKernelGGL(wave_frame_ms_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, ws, nf);
-        const int e = cbx_check_launch("wave_edges");
+        const int e = wj_frame_pass("wave_edges", wav, rows, R, n_max, nf, ws, stream);
         if (e) return e;
     }
     hipLaunchKernelGGL(wave_edges_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, (const double*)ws, nf, ratio, pad, edges);

@@ -72,10 +72,14 @@ def _valid_tokens(toks):
 def _checked_job(job):
     """A job of synthesize_pipelined with its optional keys checked as synthesize checks its arguments: seeds (ops.request_seeds; not together with the job's
     generator), speed (ops.check_speed), join (ops.check_join), format (ops.check_format_arg), loudness (ops.check_loudness; not together with a join).  A join of
-    None is dropped: from here on `"join" in job` says whether the job is joined; likewise a format that is None or the default (24 kHz fp32) and a loudness that
-    normalises no utterance."""
+    None is dropped: from here on `"join" in job` says whether the job is joined; likewise a format that is None or the default (24 kHz fp32), a loudness that
+    normalises no utterance and pauses (ops.check_pauses) that shorten no utterance."""
     n = len(job["text_tokens"])
-    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness") or v is not None}
+    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness", "pauses") or v is not None}
+    if "pauses" in job:
+        job["pauses"] = ops.check_pauses(job["pauses"], n)
+        if job["pauses"] is None:
+            del job["pauses"]
     if "loudness" in job:
         job["loudness"] = ops.check_loudness(job["loudness"], n)
         if job["loudness"] is None:
@@ -110,11 +114,12 @@ class S3GenEngine:
         self.hift = HiFTEngine(s3gen_sd, self.dev)
         self.last_timing = {}
         self.last_loudness = None  # the (B, 4) float64 device tensor {L, peak, gain, blocks used} of the last call with loudness=; not synchronised
+        self.last_pauses = None  # the (B, 4) int32 device tensor {n', pauses cut, frames removed, n} of the last call with pauses=; not synchronised
 
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None):
+               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
@@ -142,7 +147,16 @@ class S3GenEngine:
         speed stretch has shaped it) is measured and the waveform multiplied in place by the gain that brings it to its target, limited so that no sample exceeds
         1.0; a None entry, a silent utterance and one shorter than 0.4 s keep their samples.  It runs ahead of the format launch, whose s16 / G.711 store therefore
         sees the normalised signal and does not clip.  The stats {L, peak, gain, blocks used} of the call stay on the device as self.last_loudness; nothing is
-        synchronised.  Not together with a join (ValueError): a long text is normalised as a whole."""
+        synchronised.  Not together with a join (ValueError): a long text is normalised as a whole.
+        pauses (None, or no utterance with a keep: this call, launch for launch; else ops.check_pauses' dict(keep=[B ints], db=, fade=)): the pause control --
+        ops.wave_squeeze (cbx_wave_squeeze_f32) on the stream that owns the waveforms, behind the loudness step (which measures and gains the unshortened rows) and
+        ahead of the join and / or the format launch: of every silence inside utterance b that is longer than keep[b] frames of 480 samples, keep[b] remain.  The
+        new lengths n' exist on the device only (self.last_pauses keeps the record {n', pauses cut, frames removed, n}; not synchronised).  Without a join: with
+        sync=True the record is read (one small copy) and the returned waveforms are cut to n' -- formatted ones to ops.formatted_len(n', rate): the conversion
+        of a zero-tailed row is, in that range, the conversion of the exact-length row --; with sync=False the call returns dict(rows=, pauses=, format=) on the
+        device, the rows still n long with zero tails, for ops.cut_pauses once the record is on the host.  With a join the three launches run in the order edges
+        (on the original rows), squeeze (which maps the edge table), join (ops.wave_join(squeeze=)); the piece gains `pauses`, and its layout is in delivered
+        samples already."""
         B = len(speech_tokens)
         seeds = ops.request_seeds(seeds, B, generator)
         speed = ops.check_speed(speed, B)
@@ -151,6 +165,7 @@ class S3GenEngine:
         loud = ops.check_loudness(loudness, B)
         if loud is not None and join is not None:
             raise ValueError(LOUDNESS_JOIN)
+        pz = ops.check_pauses(pauses, B)
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
         tok = torch.zeros(B, Nmax, dtype=torch.long)
@@ -201,6 +216,19 @@ class S3GenEngine:
         if loud is not None:
             with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
                 self.last_loudness = ops.wave_normalize(out, loud)
+        if pz is not None:
+            with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
+                if join is not None:
+                    cap = sum(int(w.numel()) for w in out) + sum(join["gaps"])
+                    piece = ops.wave_join(out, squeeze=pz, **({} if fmt is None else dict(out=torch.zeros(max(1, cap), device=wav.device))), **join)
+                    self.last_pauses = piece["pauses"]
+                    return (piece if fmt is None else dict(piece, formatted=ops.wave_format([piece["out"]], fmt)[0], format=fmt)), mel
+                sq = ops.wave_squeeze(out, pz["keep"], pz["db"], pz["fade"])
+                self.last_pauses = sq["stats"]
+                rows = sq["rows"] if fmt is None else ops.wave_format(sq["rows"], fmt)
+                if not sync:
+                    return dict(rows=rows, pauses=sq["stats"], format=fmt), mel
+                return ops.cut_pauses(rows, sq["stats"].cpu(), fmt), mel
         if join is not None and fmt is None:
             if hift_stream is not None:
                 with torch.cuda.stream(hift_stream):
@@ -286,7 +314,7 @@ class ChatterboxEngine(S3GenEngine):
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None):
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
@@ -296,7 +324,9 @@ class ChatterboxEngine(S3GenEngine):
         ops.piece_on_host's dict (wav = the joined piece on the device, offsets, total, edges, n) plus truncated = [B bools: T3 spent its budget without EOS].
         format: None, or vocode(format=)'s dict -- the waveforms (the joined piece's `wav`) come back at that sample rate in that encoding.
         loudness: None, a number or B numbers / Nones in [-50, -5] LUFS -- vocode(loudness=): every utterance with a target is brought to it on the device (sample
-        peak limited to 1.0); not together with a join."""
+        peak limited to 1.0); not together with a join.
+        pauses: None, or vocode(pauses=)'s dict / list -- silences inside an utterance longer than its keep are shortened on the device; the waveforms come back cut
+        to their new lengths, a joined piece gains `pauses` = the record {n', pauses cut, frames removed, n} per chunk as lists."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
         join = ops.check_join(join, len(text_tokens))
@@ -304,6 +334,7 @@ class ChatterboxEngine(S3GenEngine):
         loud = ops.check_loudness(loudness, len(text_tokens))
         if loud is not None and join is not None:
             raise ValueError(LOUDNESS_JOIN)
+        pz = ops.check_pauses(pauses, len(text_tokens))
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
@@ -314,9 +345,10 @@ class ChatterboxEngine(S3GenEngine):
         st = _valid_tokens(toks)
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
                               drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)),
-                              **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)))
+                              **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)), **({} if pz is None else dict(pauses=pz)))
         if join is not None:  # (the record's copy waits for the two launches behind the vocoder)
-            wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks))
+            wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks),
+                        **({} if pz is None else dict(pauses=wavs["pauses"].tolist())))
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
@@ -334,6 +366,8 @@ class ChatterboxEngine(S3GenEngine):
         every draw of the job that is not injected, as synthesize(seeds=); not together with a generator), or `speed` (a number or one per utterance: vocode(speed=)),
         or `format` (vocode(format=)'s dict: the job's audio is converted on the device ahead of its copies, which then carry the encoded samples),
         or `loudness` (vocode(loudness=): a number or one number / None per utterance; the meter and the gain run behind the vocoder on its stream; not with a join),
+        or `pauses` (vocode(pauses=)'s dict / list: the squeeze runs behind the vocoder on its stream; its record of the new lengths travels to the host as one more
+        small pinned copy behind the same event, and the waveforms are cut after it: no host synchronisation is added),
         or `join` (vocode(join=)'s dict: the job's utterances are consecutive chunks of one text; `wavs` is then synthesize(join=)'s piece dict with `wav` on the host.
         The two launches run behind the vocoder on its stream, the piece leaves the device as ONE pinned copy plus one of its small records where a job without
         it makes one copy per utterance, and it is sliced after the event this schedule waits for anyway: no host synchronisation is added).
@@ -377,7 +411,7 @@ class ChatterboxEngine(S3GenEngine):
             is called exactly as before there was one)"""
             wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
                                   speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10), drop_last_token=kw.get("drop_last_token", True), sync=False,
-                                  **({k: job[k] for k in ("join", "format", "loudness") if k in job}))
+                                  **({k: job[k] for k in ("join", "format", "loudness", "pauses") if k in job}))
             return wavs
 
         def to_host(job, wavs, pinned):
@@ -386,13 +420,18 @@ class ChatterboxEngine(S3GenEngine):
             ops.piece_on_host), any other job one copy per utterance."""
             copy = (lambda w: torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True)) if pinned else (lambda w: w.cpu())
             if "join" in job:
-                return copy(wavs.get("formatted", wavs["out"])), copy(wavs["rec"]), wavs["n"], job.get("format")
+                host = copy(wavs.get("formatted", wavs["out"])), copy(wavs["rec"]), wavs["n"], job.get("format")
+                return host + (copy(wavs["pauses"]),) if "pauses" in job else host
+            if "pauses" in job:  # (the rows are still n long; the record that cuts them travels the same way)
+                return [copy(w) for w in wavs["rows"]], copy(wavs["pauses"]), wavs["format"]
             return [copy(w) for w in wavs]
 
         def result_of(job, host, toks):
             """What a job yields as `wavs` once `host` is readable: the waveforms, or the joined piece as its record lays it out, which also says which chunks spent
             T3's budget without EOS"""
-            return dict(ops.piece_on_host(*host), truncated=self._truncated(toks)) if "join" in job else host
+            if "join" in job:
+                return dict(ops.piece_on_host(*host[:4]), truncated=self._truncated(toks), **({} if "pauses" not in job else dict(pauses=host[4].tolist())))
+            return ops.cut_pauses(*host) if "pauses" in job else host
 
         if not host_threads:  # round 4's form: one host thread enqueues T3(k + 1), then flow + vocoder(k)
             try:
@@ -988,11 +1027,12 @@ class TurboEngine(S3GenEngine):
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
         for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=);
         speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=); join: None, or vocode(join=)'s dict -- the call then returns
-        ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict; loudness: None, or vocode(loudness=)'s targets (not with a join)."""
+        ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict; loudness: None, or vocode(loudness=)'s targets (not with a join);
+        pauses: None, or vocode(pauses=)'s dict / list, as ChatterboxEngine.synthesize(pauses=) returns its results."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
         join = ops.check_join(join, len(text_tokens))
@@ -1000,6 +1040,7 @@ class TurboEngine(S3GenEngine):
         loud = ops.check_loudness(loudness, len(text_tokens))
         if loud is not None and join is not None:
             raise ValueError(LOUDNESS_JOIN)
+        pz = ops.check_pauses(pauses, len(text_tokens))
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                 repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
@@ -1008,9 +1049,11 @@ class TurboEngine(S3GenEngine):
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed,
-                              **({} if join is None else dict(join=join)), **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)))
+                              **({} if join is None else dict(join=join)), **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)),
+                              **({} if pz is None else dict(pauses=pz)))
         if join is not None:
-            wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks, max_gen_len))
+            wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks, max_gen_len),
+                        **({} if pz is None else dict(pauses=wavs["pauses"].tolist())))
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 

@@ -1076,11 +1076,14 @@ def wave_edges(rows, trim_db, pad_frames=2, edges=None):
     return edges
 
 
-def wave_join(rows, gaps, trim_db=None, pad_frames=2, fade=240, first=True, last=True, out=None):
+def wave_join(rows, gaps, trim_db=None, pad_frames=2, fade=240, first=True, last=True, out=None, squeeze=None):
     """cbx_wave_edges_f32 (unless trim_db is None) + cbx_wave_join_f32 on the current stream: the rows' kept parts laid out in ONE buffer with their gaps and
     fades (include/cbx.h states the layout).  rows: _wave_rows; gaps: R ints.  Returns the piece, everything on the device and nothing synchronised:
     dict(out=(capacity,) fp32 of which [0, total) is the piece -- capacity = sum of the lengths and gaps; the rest is NOT written --, rec=(3 R + 1,) int32 = the
-    layout record off_0 .. off_(R-1), total followed by the edge table, layout / edges = views of rec, n = the R row lengths)."""
+    layout record off_0 .. off_(R-1), total followed by the edge table, layout / edges = views of rec, n = the R row lengths).
+    squeeze (None: this call, launch for launch; else check_pauses' dict): the pause control between the two -- edges on the ORIGINAL rows, then wave_squeeze,
+    which shortens the rows and maps the table, then the join over the shortened rows with the host-side lengths n_r and the mapped table (a caller-written
+    {0, n_r} has become {0, n'_r}: the zero tail never reaches the piece).  The piece gains `pauses`, wave_squeeze's stats."""
     base, offs, lens = _wave_rows(rows, "wave_join")
     R, dev = len(lens), rows[0].device
     n = [int(v) for v in lens]
@@ -1098,10 +1101,99 @@ def wave_join(rows, gaps, trim_db=None, pad_frames=2, fade=240, first=True, last
         edges.view(-1).copy_(host.pin_memory() if dev.type == "cuda" else host, non_blocking=True)
     else:
         wave_edges(rows, trim_db, pad_frames, edges=edges)
+    pauses = None
+    if squeeze is not None:
+        sq = wave_squeeze(rows, squeeze["keep"], squeeze["db"], squeeze["fade"], edges=edges)
+        pauses = sq["stats"]
+        base, offs, lens = _wave_rows(sq["rows"], "wave_join")
     g = (ctypes.c_int * R)(*gaps)
     check(lib.cbx_wave_join_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(g), R, _p(edges), _p(join_ramp(fade, dev)), int(fade),
                                 int(bool(first)), int(bool(last)), _p(_f32(out, "out")), out.numel(), _p(layout), _stream()), "cbx_wave_join_f32")
-    return dict(out=out, rec=rec, layout=layout, edges=edges, n=n)
+    piece = dict(out=out, rec=rec, layout=layout, edges=edges, n=n)
+    return piece if pauses is None else dict(piece, pauses=pauses)
+
+
+# ----------------------------------------------------------------------------- pause control: shorten long silences inside the rows (wave_squeeze.hip)
+WAVE_SQUEEZE_TILE = 256          # frames per step of the plan kernel's scans (WS_TILE): a pause may start in one tile and end in a later one
+WAVE_SQUEEZE_MAX_KEEP = 3000     # 60 s of 480-sample frames
+PAUSES_KEYS = ("keep", "db", "fade")
+
+
+def check_pauses(value, B, name="pauses"):
+    """A `pauses` argument of the engines as dict(keep=[B ints], db=float, fade=int), or None.  value: None; a dict(keep=, db=, fade=) whose keep is an int (every
+    row) or a list of B ints / Nones; or a per-request list of B ints / Nones (the keeps, db and fade at their defaults).  keep[b]: 0 or None -- row b is left as it
+    is --, else the frames (of 480 samples) that remain of every longer pause, an int in [2, 3000].  db: a finite number >= 0, decibels below the row's loudest
+    frame at or under which a frame is silent (default 40).  fade: the seam's cross-fade in samples, an int in [0, 480] (default 240).  A value with no keep on
+    any row is None: the call is then the call without the argument.  TypeError / ValueError before anything is launched."""
+    import math
+    import numbers
+    if value is None:
+        return None
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    if isinstance(value, dict):
+        extra = set(value) - set(PAUSES_KEYS)
+        if extra or "keep" not in value:
+            raise ValueError(f"{name}: keys {sorted(value)}: `keep` is required, the others are {PAUSES_KEYS[1:]}")
+        keep, db, fade = value["keep"], value.get("db", 40.0), value.get("fade", 240)
+    elif isinstance(value, (list, tuple)):
+        keep, db, fade = value, 40.0, 240
+    else:
+        raise TypeError(f"{name}: expected None, a dict with {PAUSES_KEYS} or a list of {B} ints / Nones, got {type(value).__name__}")
+    if is_int(keep):
+        keep = [keep] * B
+    if not isinstance(keep, (list, tuple)) or not all(k is None or is_int(k) for k in keep):
+        raise TypeError(f"{name}['keep']: expected an int or a list of {B} ints / Nones")
+    if len(keep) != B or not 1 <= B <= WAVE_JOIN_MAX_ROWS:
+        raise ValueError(f"{name}['keep']: {len(keep)} entries for {B} rows (1 .. {WAVE_JOIN_MAX_ROWS} rows)")
+    keep = [0 if k is None else int(k) for k in keep]
+    if any(k != 0 and not 2 <= k <= WAVE_SQUEEZE_MAX_KEEP for k in keep):
+        raise ValueError(f"{name}['keep'] = {keep}: 0 / None (the row is left alone) or an int in [2, {WAVE_SQUEEZE_MAX_KEEP}] frames")
+    if not isinstance(db, numbers.Real) or isinstance(db, bool):
+        raise TypeError(f"{name}['db']: expected a number, got {type(db).__name__}")
+    db = float(db)
+    if not math.isfinite(db) or db < 0.0:
+        raise ValueError(f"{name}['db'] = {db}: a finite number >= 0 (decibels below the loudest frame)")
+    if not is_int(fade):
+        raise TypeError(f"{name}['fade']: expected an int, got {type(fade).__name__}")
+    if not 0 <= fade <= WAVE_FRAME:
+        raise ValueError(f"{name}['fade'] = {fade}: expected an int in [0, {WAVE_FRAME}]")
+    return dict(keep=keep, db=db, fade=fade) if any(keep) else None
+
+
+def wave_squeeze(rows, keep, db=40.0, fade=240, edges=None, out=None):
+    """cbx_wave_squeeze_f32 on the current stream: of every pause (a run of silent 480-sample frames between two non-silent ones; silent = mean square at or under
+    the row's loudest frame's times 10^(-db / 10)) longer than keep[r] frames only keep[r] remain, the cut cross-faded over `fade` samples (include/cbx.h states
+    the definition).  rows: _wave_rows; keep: R ints, 0 = the row is copied.  edges: None, or an (R, 2) int32 device table {start, stop} on the ORIGINAL rows, which
+    is rewritten in place for the shortened ones.  out: None, or the buffer to write into (row r at the offset it has in its own allocation; not that allocation).
+    Returns dict(rows = views of a NEW buffer with the rows' layout, each still n_r long: [0, n'_r) the shortened
+    row, [n'_r, n_r) zeros; stats = (R, 4) int32 device tensor {n', pauses cut, frames removed, n}; edges = the table or None; n = the R lengths).  Everything
+    stays on the device and nothing is synchronised: n' is known to the host once `stats` has been copied."""
+    base, offs, lens = _wave_rows(rows, "wave_squeeze")
+    R, dev = len(lens), rows[0].device
+    keep = [int(k) for k in keep]
+    if len(keep) != R:
+        raise ValueError(f"wave_squeeze: {len(keep)} keeps for {R} rows")
+    n = [int(v) for v in lens]
+    span = max(int(o) + k for o, k in zip(offs, n))
+    if out is None:
+        out = torch.empty(max(1, span), device=dev)
+    assert out.dim() == 1 and out.is_contiguous() and out.device == dev, "wave_squeeze: out is a contiguous 1-D fp32 tensor on the rows' device"
+    stats = torch.empty(R, 4, dtype=torch.int32, device=dev)
+    if edges is not None:
+        assert edges.dtype == torch.int32 and edges.numel() == 2 * R and edges.is_contiguous() and edges.device == dev, "wave_squeeze: edges is (R, 2) int32 on the rows' device"
+    ws = torch.empty(max(1, 2 * R * -(-max(n) // WAVE_FRAME)), dtype=torch.float64, device=dev)  # 16 bytes per frame
+    kp = (ctypes.c_int * R)(*keep)
+    check(lib.cbx_wave_squeeze_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(kp), R, 10.0 ** (-float(db) / 10.0), _p(join_ramp(fade, dev)),
+                                   int(fade), _p(_f32(out, "out")), out.numel(), _p(edges), _p(stats), _p(ws), 8 * ws.numel(), _stream()), "cbx_wave_squeeze_f32")
+    return dict(rows=[out[int(o): int(o) + k] for o, k in zip(offs, n)], stats=stats, edges=edges, n=n)
+
+
+def cut_pauses(rows, stats, fmt=None):
+    """The rows of wave_squeeze (or their conversion by wave_format to `fmt`) cut to their new lengths once `stats` is readable on the host: row r keeps n'_r
+    samples, a converted row formatted_len(n'_r, rate) -- the conversion of a zero-tailed row is, in that range, bit for bit the conversion of the exact-length
+    row: an output past it would be the first to read no sample of the row at all."""
+    new = [int(s[0]) for s in stats.tolist()]
+    return [w[: k if fmt is None else formatted_len(k, fmt["sample_rate"])] for w, k in zip(rows, new)]
 
 
 def piece_on_host(out, rec, n, fmt=None):

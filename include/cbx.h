@@ -857,6 +857,37 @@ int cbx_wave_edges_f32(const float* wav, const long* row_off, const int* row_len
 int cbx_wave_join_f32(const float* wav, const long* row_off, const int* row_len, const int* gaps, int R, const int* edges, const float* ramp, int fade, int first,
                       int last, float* out, long out_cap, int* layout, void* stream);
 
+/* ---- pause control: shorten long silences INSIDE the rows of a batch on the device (added after ABI v16 without a version step: a new function only).  The
+ * reference returns the waveform with whatever holes T3 sampled (tts.py:272, mtl_tts.py:352, tts_turbo.py:320, vc.py:104) and has no such step.  Rows as
+ * cbx_wave_join_f32 takes them: R in [1, 64] rows of row_len[r] floats at wav + row_off[r]; row_off, row_len and keep are HOST arrays (by value).  Row r has n samples x.
+ * Frames: frame f covers [480 f, min(480 (f + 1), n)); m_f = its mean square in fp64, computed by the frame kernel of cbx_wave_edges_f32 itself (one source: the
+ *   same bits); peak = max_f m_f as that entry takes it (fmax from 0: a NaN frame is ignored by the peak).
+ * Silent: frame f is silent iff m_f <= peak * ratio or m_f == 0 (ratio = 10^(-pause_db / 10), computed by the caller in fp64).  A frame whose m_f is NaN is NOT
+ *   silent and is never removed -- this differs from cbx_wave_edges_f32, where a NaN frame is not live (there NaN counts as silence, here as signal).
+ * Runs: f0 / f1 = the first / last non-silent frame; none: nothing is removed.  A pause is a maximal run [a, b) of silent frames with f0 < a and b <= f1, P = b - a
+ *   frames long.  Leading and trailing silence is not a pause (cbx_wave_edges_f32 trims that).
+ * Cut: K = keep[r]; 0: row r is copied unchanged; else K >= 2, and of every pause with P > K the frames [a + h, b - t) are removed, h = K - K / 2, t = K / 2 (integer
+ *   division): in samples [c0, c1) = [480 (a + h), 480 (b - t)).  Only whole frames are removed; the row's partial last frame is never removed and is never the
+ *   frame ahead of a cut.
+ * Output: row r of the result lives at out + row_off[r] (same layout, another buffer; out overlapping wav is refused).  n' = n - 480 sum (P - K); y[0, n') = the
+ *   kept samples in order, y[n', n) is written as zeros, nothing outside [0, n) of the row is written.
+ * Seam: with F = fade in [0, 480] and ramp[i] = (2 i + 1) / (2 fade) by convention (`fade` device floats; NULL when fade = 0), for each cut with q = map(c0), i < F:
+ *   y[q - F + i] = fmaf(ramp[i], x[c1 - F + i] - x[c0 - F + i], x[c0 - F + i]) -- one fp32 subtraction and one fmaf.  Both operands lie in silent frames of the
+ *   same run (the kept head frame a + h - 1, the removed frame b - t - 1); no sample is blended twice.
+ * Map: map(p) = the number of kept samples in [0, p), p in [0, n].  edges (NULL, or an (R, 2) int32 device table, in / out): each entry {start, stop} is cut into
+ *   [0, n] as the join cuts it and rewritten as {map(start), map(stop)} -- the table cbx_wave_edges_f32 wrote for the ORIGINAL rows, or {0, n} written by the
+ *   caller (which becomes {0, n'}), so that cbx_wave_join_f32 over the result, with the host-side lengths n, never sees the zero tail: no host round trip.
+ * Record: stats = (R, 4) int32 device table {n', pauses cut, frames removed, n}.
+ * Three launches (the frame pass, one workgroup per row that plans, one wave per output frame that gathers); integer scans in a fixed order, no atomics: the
+ * result does not depend on the grid or on a row's alignment; 16-byte accesses where a row's addresses allow, 4-byte accesses elsewhere; positions are 64-bit.
+ * ws: device workspace of ws_cap BYTES on an 8-byte boundary, ws_cap >= 16 * R * ceil(max_r n_r / 480): per frame one double (m_f) and two ints (the next
+ * non-silent frame; the source frame of each output frame).  out_cap: floats in `out`, at least max_r (row_off[r] + n_r).
+ * -22 before any launch, nothing written: a null pointer (edges may be NULL), R outside [1, 64], a negative length or offset, keep[r] = 1 or negative, ratio
+ * negative / not finite, fade outside [0, 480], fade > 0 without a ramp, out overlapping wav, out_cap short of the furthest row end, a workspace that is too
+ * small. */
+int cbx_wave_squeeze_f32(const float* wav, const long* row_off, const int* row_len, const int* keep, int R, double ratio, const float* ramp, int fade, float* out,
+                         long out_cap, int* edges, int* stats, void* ws, long ws_cap, void* stream);
+
 /* ---- output formats: resample 24 kHz fp32 to the delivery rate and encode it, one launch for the rows of a batch or of a stream's round (added after ABI v16
  * without a version step: a new function only).  The reference returns 24 kHz fp32 and leaves this to its caller (tts.py:272, mtl_tts.py:352, tts_turbo.py:320,
  * vc.py:104).  Rows as cbx_wave_join_f32 takes them: R in [1, 64] pieces of row_len[r] floats at wav + row_off[r] (HOST arrays; 4-byte alignment is enough).
