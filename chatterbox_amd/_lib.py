@@ -289,6 +289,7 @@ _SIGS = {
     "cbx_wave_edges_f32": ([c_f, c_f, c_f, c_int, ctypes.c_double, c_int, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_join_f32": ([c_f, c_f, c_f, c_f, c_int, c_f, c_f, c_int, c_int, c_int, c_f, c_long, c_f, c_f], c_int),
     "cbx_wave_squeeze_f32": ([c_f, c_f, c_f, c_f, c_int, ctypes.c_double, c_f, c_int, c_f, c_long, c_f, c_f, c_f, c_long, c_f], c_int),
+    "cbx_wave_pitch_f32": ([c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_int, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_format_f32": ([c_f, c_f, c_f, c_int, c_int, c_int, c_f, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_loudness_f32": ([c_f, c_f, c_f, c_int, c_f, c_int, c_f, ctypes.c_double, c_f, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_loudness_push_f32": ([c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_f, ctypes.c_double, c_f, c_long, c_f, c_f, c_f, c_f, c_f, c_long, c_f], c_int),

@@ -273,6 +273,22 @@ def _pause_kw(max_pause, pause_db):
     return {} if pz is None else dict(pauses=pz)
 
 
+def _one_pitch(speed, pitch):
+    """The `pitch` of a method that takes ONE request: None (also for 0), or the semitones as a float in [-12, 12] (ops.check_pitch; a sequence is a TypeError),
+    checked against the call's `speed` (ops.check_speed_pitch: speed / 2^(pitch / 12) in [0.5, 2.0], else a ValueError naming both) before anything is launched"""
+    if isinstance(pitch, (list, tuple)):
+        raise TypeError(f"pitch: expected None or a number of semitones, got a {type(pitch).__name__}")
+    p = ops.check_pitch(pitch, 1)
+    ops.check_speed_pitch(speed, p, 1)
+    return None if p is None else p[0]
+
+
+def _pitch_kw(speed, pitch):
+    """generate's `pitch` as the engines' pitch= keyword ({} for None / 0: the engine call is then exactly the one without it)"""
+    p = _one_pitch(speed, pitch)
+    return {} if p is None else dict(pitch=[p])
+
+
 def _stream_speed_kw(speed):
     """generate_stream's `speed` as the engines' speed= keyword: ONE number in [0.5, 2.0] for the stream ({} at 1.0 / None).  TypeError / ValueError
     (engine.check_stream_speed) before anything is launched."""
@@ -417,6 +433,8 @@ def _long_jobs(chunks, max_batch, a, sizes=None):
             job["speed"] = [a["speed"]] * len(idx)
         if a.get("pauses") is not None:
             job["pauses"] = dict(a["pauses"], keep=a["pauses"]["keep"] * len(idx))
+        if a.get("pitch") is not None:
+            job["pitch"] = [a["pitch"]] * len(idx)
         jobs.append(job)
     return jobs
 
@@ -424,7 +442,8 @@ def _long_jobs(chunks, max_batch, a, sizes=None):
 def long_plan(chunks, max_batch, a):
     """The jobs of a generate_long call, WITHOUT their tokens and voices: chunks = split_text's list, a = _long_args' dict.  Chunks keep the text's order (no length
     sort: a piece is a run of consecutive chunks) and are cut into consecutive device batches of at most max_batch (and at most 64, the join's row limit).  Per job:
-    dict(chunks=[indices], join=the engines' join dict, seeds=[...] if seeded, speed=[...] if not 1.0, pauses=the engines' pauses dict if a["pauses"]).  The gap behind a chunk is round(pause * 24000 / speed)
+    dict(chunks=[indices], join=the engines' join dict, seeds=[...] if seeded, speed=[...] if not 1.0, pauses=the engines' pauses dict if a["pauses"],
+    pitch=[...] if a["pitch"]).  The gap behind a chunk is round(pause * 24000 / speed)
     samples, paragraph_pause behind a paragraph's last chunk; the first job carries first=True, the last one last=True."""
     return _long_jobs(chunks, max_batch, a)
 
@@ -662,7 +681,7 @@ class _TTS(_Finish):
             args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
             yield self.engine.synthesize(*args, **synth_kw, **job)
 
-    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, loudness=None, pauses=None, **analyse_kw):
+    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, loudness=None, pauses=None, pitch=None, **analyse_kw):
         """generate_batch behind its signature: validation of every per-request argument (seeds and speed first), then the voices, then tokenisation, then the
         device work.  samp: the sampling arguments the engine takes; unsampled: those it does not -- exaggeration, which picks the voice's cond dict, and what the
         backbone ignores."""
@@ -673,23 +692,26 @@ class _TTS(_Finish):
         speed = ops.check_speed(speed, B)
         loud = ops.check_loudness(loudness, B)
         pz = None if pauses is None else _pauses(*pauses, B)
+        pit = ops.check_pitch(pitch, B)
+        ops.check_speed_pitch(speed, pit, B)
         langs = self._languages(language_ids, B)
         samp = _sampling_lists(B, **samp)
         unsampled = _sampling_lists(B, **unsampled)
         self._warn_ignored(*(v for vals in unsampled.values() for v in vals))
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, unsampled["exaggeration"], **analyse_kw)
         tokens = [self._engine_tokens(self._text_ids(t, lid)) for t, lid in zip(texts, langs)]
-        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt, loud, pz)
+        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt, loud, pz, pit)
 
     def _languages(self, language_ids, B):
         return [None] * B
 
-    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None, loud=None, pz=None):
+    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None, loud=None, pz=None, pit=None):
         """Sub-batches of at most max_batch requests in order of text length (_run_jobs: one runs the serial schedule, several the throughput schedule).  Returns the
         finished waveforms in the caller's order.  seeds (B ints or None) travel with their requests: a request's draws do not depend on the sub-batch or the row
         it lands in.  speed (B floats or None) travels the same way.  fmt (one format for the call, or None): every job carries it as `format` unless a
         watermarker is loaded (_engine_format).  loud (B LUFS targets / Nones, or None) travels with its requests like speed: a job carries `loudness` only when
-        one of its requests has a target.  pz (_pauses' dict or None) the same: a job carries `pauses`, with its requests' keeps, only when one of them has one."""
+        one of its requests has a target.  pz (_pauses' dict or None) the same: a job carries `pauses`, with its requests' keeps, only when one of them has one.  pit (B semitones or None) the same: a job
+        carries `pitch` only when one of its requests is transposed."""
         dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
         plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
         jobs = []
@@ -707,6 +729,8 @@ class _TTS(_Finish):
                 job["loudness"] = _pick(loud, idx)
             if pz is not None and any(_pick(pz["keep"], idx)):
                 job["pauses"] = dict(pz, keep=_pick(pz["keep"], idx))
+            if pit is not None and any(_pick(pit, idx)):
+                job["pitch"] = _pick(pit, idx)
             job.update(self._engine_format(fmt))
             jobs.append(job)
         out = [None] * len(tokens)
@@ -738,7 +762,7 @@ class _TTS(_Finish):
         max_batch = int(self.max_batch or self.engine.t3.MAX_BATCH)
         plan = long_plan(chunks, max_batch, a) if ramp is None else long_stream_plan(chunks, max_batch, a, *ramp)
         t3, gen = self.conds.t3.as_dict(), self.conds.gen
-        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join", "pauses") if k in p}) for p in plan]
+        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join", "pauses", "pitch") if k in p}) for p in plan]
         return chunks, plan, jobs
 
     @staticmethod
@@ -882,7 +906,7 @@ class ChatterboxTTS(_LlamaTTS):
         return self.tokenizer.text_to_tokens(punc_norm_en(text))
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
-                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
         alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
         speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
@@ -904,16 +928,23 @@ class ChatterboxTTS(_LlamaTTS):
         UNMEASURED choice.  generate_batch: max_pause is a number or one number / None per request and travels with its request like speed; pause_db is one number
         for the call.  generate_long: every chunk is shortened ahead of the join; a segment's [start, stop) holds the chunk's kept, shortened samples, and
         [src_start, src_stop) count samples of the shortened chunk.  generate_stream does not take the arguments: a pause's end is not known inside a round.
-        This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause` and `pause_db` for every method of every class of this module;
-        the others say only what differs."""
+        pitch (None, or semitones in [-12, 12]; 0 is None): pitch control.  With r = 2^(pitch / 12) the mel is stretched at speed / r instead of speed -- that
+        rate must lie in [0.5, 2.0], else a ValueError that names both arguments --, the vocoder runs on it, and one launch on the device (ops.wave_pitch) reads the
+        waveform back at a step of r samples, ahead of the loudness step, the pauses, the format conversion and the only copy to the host: the result has exactly
+        the length of the call without `pitch`, every frequency multiplied by r.  The formants move WITH the pitch (varispeed with the duration restored): two or
+        three semitones keep the voice, an octave does not.  The range and the filter are UNMEASURED choices.  generate_batch: a number or
+        one number / None per request, travelling with its request like speed.  generate_long: every chunk is transposed ahead of the join; the gaps do not
+        change.  generate_stream does not take the argument.
+        This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db` and `pitch` for every method of every class of this
+        module; the others say only what differs."""
         fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text), fmt, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
                               top_p=top_p, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """generate() for a text of ANY length: the reference stops at 1000 speech tokens (40 s) and cuts a longer text off.  The text is split into chunks of at
         most max_chars characters at paragraph, sentence and clause boundaries (text.split_text), the chunks are synthesised in text order as device batches
         (one: synthesize; several: the throughput schedule where the engine has it), and each batch's waveforms are trimmed of their leading / trailing silence and
@@ -933,13 +964,13 @@ class ChatterboxTTS(_LlamaTTS):
         all of it, limited to a sample peak of 1.0, applied on the device ahead of the watermark and the conversion."""
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"] = _pauses(max_pause, pause_db, 1, one=True)
+        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                              max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
-                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, first_batch=1, batch_growth=2.0):
+                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, first_batch=1, batch_growth=2.0):
         """generate_long() in pieces: a generator of (1, n) CPU tensors, one per device batch as it leaves the device (empty pieces left out); concatenated along
         dim 1 they are the long-form result.  Every argument of generate_long with its meaning and default, plus the ramp of the device batches:
         first_batch (None, or an int >= 1) and batch_growth (a finite number >= 1): the batches hold s_0 = min(first_batch, step) chunks, then
@@ -959,13 +990,13 @@ class ChatterboxTTS(_LlamaTTS):
         not the last holds the resampling filter's tail back: a segment's last samples may arrive with the NEXT piece."""
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"] = _pauses(max_pause, pause_db, 1, one=True)
+        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
         ramp = _long_stream_args(first_batch, batch_growth)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
-                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
         request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
         neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
@@ -981,7 +1012,7 @@ class ChatterboxTTS(_LlamaTTS):
         This is the contract of generate_batch of every class of this module; the others say only what differs."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db))
+                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                         cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, sample_rate=None, encoding=None, speed=1.0):
@@ -1043,11 +1074,11 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
         return [_language(lid, f" (request {k})") for k, lid in enumerate(langs)]
 
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
         token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness: as there."""
         fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text, lid), fmt, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
@@ -1055,34 +1086,34 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         fmt = ops.check_format(sample_rate, encoding)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
-        a["pauses"] = _pauses(max_pause, pause_db, 1, one=True)
+        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
     def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                              top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                             return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, first_batch=1, batch_growth=2.0):
+                             return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         fmt = ops.check_format(sample_rate, encoding)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
-        a["pauses"] = _pauses(max_pause, pause_db, 1, one=True)
+        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
         ramp = _long_stream_args(first_batch, batch_growth)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
         speed, before the sampling arguments)."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db))
+                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch)
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
@@ -1170,46 +1201,46 @@ class ChatterboxTurboTTS(_TTS):
         return dict(max_gen_len=1000) if batch else {}
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
-                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed, sample_rate, encoding, loudness: as
         ChatterboxTTS.generate."""
         fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
         self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
         self._warn_ignored(cfg_weight, exaggeration, min_p)
         return self._generate(self._text_ids(text), fmt, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                       top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """ChatterboxTTS.generate_long on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other)."""
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"] = _pauses(max_pause, pause_db, 1, one=True)
+        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), fmt,
                                    loudness, norm_loudness=norm_loudness)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                              top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None,
-                             speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, first_batch=1, batch_growth=2.0):
+                             speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other, so a piece is
         yielded before the next batch starts)."""
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"] = _pauses(max_pause, pause_db, 1, one=True)
+        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
         ramp = _long_stream_args(first_batch, batch_growth)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), fmt,
                                    loudness, ramp, norm_loudness=norm_loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
-                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
         of B).  CFG, min_p and exaggeration are ignored with generate()'s warning.  Sub-batches run one after the other."""
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), norm_loudness=norm_loudness)
+                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, norm_loudness=norm_loudness)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
                         temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
@@ -1294,13 +1325,13 @@ class ChatterboxVC(_Finish):
             s3_tokens = self._tokens_of(audio)
         return torch.as_tensor(s3_tokens).view(-1).long().cpu()
 
-    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """reference vc.py:83-104.  audio: a WAV path, a (waveform, sample_rate) pair or raw samples (data, sample_rate, encoding[, channels]) -- bytes or a uint8 /
         int16 / int32 / float32 array of interleaved frames in one of ops.WAVE_IN_ENCODINGS; with self.audio_in = "device" it is decoded and resampled on the device
         (a path then opens G.711 and 24-bit WAVs too).  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
         are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding, loudness: as there."""
         fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
         wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **seed_kw, **self._engine_format(fmt))
         return self._finish(wavs[0], fmt)
 
@@ -1334,7 +1365,7 @@ class ChatterboxVC(_Finish):
 
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 
-    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0):
+    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """generate() for B conversions in one call: `audios` (WAV paths, (waveform, sample_rate) pairs or raw (data, sample_rate, encoding[, channels]) tuples; with
         audio_in = "device" the sources of one (rate, encoding, channels) are uploaded and converted together) or `s3_tokens` (B id sequences); target voice per
         request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
@@ -1352,6 +1383,8 @@ class ChatterboxVC(_Finish):
         speed = ops.check_speed(speed, B)
         loud = ops.check_loudness(loudness, B)
         pz = _pauses(max_pause, pause_db, B)
+        pit = ops.check_pitch(pitch, B)
+        ops.check_speed_pitch(speed, pit, B)
         if target_voice_paths is not None and ref_dicts is not None:
             raise ValueError("give target_voice_paths or ref_dicts, not both")
         if target_voice_paths is not None:
@@ -1372,7 +1405,8 @@ class ChatterboxVC(_Finish):
             wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **({} if seeds is None else dict(seeds=_pick(seeds, idx))),
                                          **({} if speed is None else dict(speed=_pick(speed, idx))), **self._engine_format(fmt),
                                          **({} if loud is None or all(v is None for v in _pick(loud, idx)) else dict(loudness=_pick(loud, idx))),
-                                         **({} if pz is None or not any(_pick(pz["keep"], idx)) else dict(pauses=dict(pz, keep=_pick(pz["keep"], idx)))))
+                                         **({} if pz is None or not any(_pick(pz["keep"], idx)) else dict(pauses=dict(pz, keep=_pick(pz["keep"], idx)))),
+                                         **({} if pit is None or not any(_pick(pit, idx)) else dict(pitch=_pick(pit, idx))))
             for i, w in zip(idx, wavs):
                 out[i] = self._finish(w, fmt)
         return out

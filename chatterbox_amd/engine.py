@@ -73,9 +73,16 @@ def _checked_job(job):
     """A job of synthesize_pipelined with its optional keys checked as synthesize checks its arguments: seeds (ops.request_seeds; not together with the job's
     generator), speed (ops.check_speed), join (ops.check_join), format (ops.check_format_arg), loudness (ops.check_loudness; not together with a join).  A join of
     None is dropped: from here on `"join" in job` says whether the job is joined; likewise a format that is None or the default (24 kHz fp32), a loudness that
-    normalises no utterance and pauses (ops.check_pauses) that shorten no utterance."""
+    normalises no utterance, pauses (ops.check_pauses) that shorten no utterance and a pitch (ops.check_pitch; with the job's speed: ops.check_speed_pitch) that
+    transposes no utterance."""
     n = len(job["text_tokens"])
-    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness", "pauses") or v is not None}
+    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness", "pauses", "pitch") or v is not None}
+    if "pitch" in job:
+        job["pitch"] = ops.check_pitch(job["pitch"], n)
+        if job["pitch"] is None:
+            del job["pitch"]
+        else:
+            ops.check_speed_pitch(job.get("speed"), job["pitch"], n)
     if "pauses" in job:
         job["pauses"] = ops.check_pauses(job["pauses"], n)
         if job["pauses"] is None:
@@ -119,7 +126,7 @@ class S3GenEngine:
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None):
+               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
@@ -156,7 +163,14 @@ class S3GenEngine:
         of a zero-tailed row is, in that range, the conversion of the exact-length row --; with sync=False the call returns dict(rows=, pauses=, format=) on the
         device, the rows still n long with zero tails, for ops.cut_pauses once the record is on the host.  With a join the three launches run in the order edges
         (on the original rows), squeeze (which maps the edge table), join (ops.wave_join(squeeze=)); the piece gains `pauses`, and its layout is in delivered
-        samples already."""
+        samples already.
+        pitch (None, or every entry None / 0: this call, launch for launch; else a number or B numbers / Nones in [-12, 12] semitones, ops.check_pitch): the pitch
+        control.  With r_b = ops.pitch_ratio(pitch[b]) the ONE ops.mel_time_scale launch stretches row b at s_eff = speed[b] / r_b (ops.check_speed_pitch: in
+        [0.5, 2.0], else a ValueError naming both arguments; a row without a pitch at its plain speed), the vocoder runs on that mel -- noise, phase and seeded
+        draws sized from it exactly as speed= sizes them --, and ONE ops.wave_pitch launch (cbx_wave_pitch_f32) on the stream that owns the waveforms reads the
+        cut rows, 480 scaled_len(K_b, s_eff) samples, at a step of r_b into 480 scaled_len(K_b, speed[b]) samples: the length of the call without a pitch,
+        every frequency multiplied by r_b.  The formants move with the pitch.  The launch runs ahead of the loudness step, the pauses, the join and the format
+        launch, which see its rows (views of one packed buffer; a row without a pitch is copied)."""
         B = len(speech_tokens)
         seeds = ops.request_seeds(seeds, B, generator)
         speed = ops.check_speed(speed, B)
@@ -166,6 +180,11 @@ class S3GenEngine:
         if loud is not None and join is not None:
             raise ValueError(LOUDNESS_JOIN)
         pz = ops.check_pauses(pauses, B)
+        pitch = ops.check_pitch(pitch, B)
+        rates = speed  # at which the mel is stretched
+        if pitch is not None:
+            eff = ops.check_speed_pitch(speed, pitch, B)
+            rates = None if all(e == 1.0 for e in eff) else eff
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
         tok = torch.zeros(B, Nmax, dtype=torch.long)
@@ -184,10 +203,10 @@ class S3GenEngine:
                 torch.cuda.synchronize()
             t1 = time.perf_counter()
             # short_b > 0 only when the prompt mel has an odd frame more than 2 * prompt tokens (flow.py:170-195); per voice when the batch mixes voices
-            if speed is None:
+            if rates is None:
                 vmel, mel_lens = mel, None if same and len(set(shorts)) == 1 else (2 * lens - torch.tensor(shorts, dtype=torch.int32)).to(self.dev)
             else:  # the vocoder's input is the stretched mel; lens always: the rows differ
-                vmel, mel_lens = ops.mel_time_scale(mel, speed, in_lens=[2 * n - sh for n, sh in zip(ns, shorts)])
+                vmel, mel_lens = ops.mel_time_scale(mel, rates, in_lens=[2 * n - sh for n, sh in zip(ns, shorts)])
             if hift_stream is not None:
                 ev = torch.cuda.Event()
                 ev.record()
@@ -206,13 +225,18 @@ class S3GenEngine:
             return wav, mel
 
         wav, mel = _range_checked(self, run, check=sync)
-        out = []
+        out, plain = [], []
         for b, n in enumerate(ns):
             keep = max(1, n - 1) if drop_last_token else n
             frames = min(2 * keep, 2 * n - shorts[b])  # K_b: what the unscaled call returns, in mel frames of 480 samples
-            if speed is not None:
-                frames = ops.scaled_len(frames, speed[b])
+            if pitch is not None:
+                plain.append(ops.scaled_len(frames, speed[b]) if speed is not None else frames)
+            if rates is not None:
+                frames = ops.scaled_len(frames, rates[b])
             out.append(wav[b, : frames * (SAMPLES_PER_TOKEN // 2)])
+        if pitch is not None:  # the source rows, read at a step of r_b into the lengths of the call without a pitch
+            with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
+                out = ops.wave_pitch(out, [ops.pitch_ratio(p) for p in pitch], [k * (SAMPLES_PER_TOKEN // 2) for k in plain])
         if loud is not None:
             with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
                 self.last_loudness = ops.wave_normalize(out, loud)
@@ -314,7 +338,7 @@ class ChatterboxEngine(S3GenEngine):
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None):
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
@@ -326,9 +350,13 @@ class ChatterboxEngine(S3GenEngine):
         loudness: None, a number or B numbers / Nones in [-50, -5] LUFS -- vocode(loudness=): every utterance with a target is brought to it on the device (sample
         peak limited to 1.0); not together with a join.
         pauses: None, or vocode(pauses=)'s dict / list -- silences inside an utterance longer than its keep are shortened on the device; the waveforms come back cut
-        to their new lengths, a joined piece gains `pauses` = the record {n', pauses cut, frames removed, n} per chunk as lists."""
+        to their new lengths, a joined piece gains `pauses` = the record {n', pauses cut, frames removed, n} per chunk as lists.
+        pitch: None, a number or B numbers / Nones in [-12, 12] semitones -- vocode(pitch=): utterance b comes back transposed by pitch[b] at the length speed[b]
+        alone gives it; T3 and its tokens do not depend on it.  speed / 2^(pitch / 12) outside [0.5, 2.0] is a ValueError before anything is launched."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
+        pitch = ops.check_pitch(pitch, len(text_tokens))
+        ops.check_speed_pitch(speed, pitch, len(text_tokens))
         join = ops.check_join(join, len(text_tokens))
         fmt = ops.check_format_arg(format)
         loud = ops.check_loudness(loudness, len(text_tokens))
@@ -345,7 +373,8 @@ class ChatterboxEngine(S3GenEngine):
         st = _valid_tokens(toks)
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
                               drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)),
-                              **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)), **({} if pz is None else dict(pauses=pz)))
+                              **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)), **({} if pz is None else dict(pauses=pz)),
+                              **({} if pitch is None else dict(pitch=pitch)))
         if join is not None:  # (the record's copy waits for the two launches behind the vocoder)
             wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks),
                         **({} if pz is None else dict(pauses=wavs["pauses"].tolist())))
@@ -366,6 +395,7 @@ class ChatterboxEngine(S3GenEngine):
         every draw of the job that is not injected, as synthesize(seeds=); not together with a generator), or `speed` (a number or one per utterance: vocode(speed=)),
         or `format` (vocode(format=)'s dict: the job's audio is converted on the device ahead of its copies, which then carry the encoded samples),
         or `loudness` (vocode(loudness=): a number or one number / None per utterance; the meter and the gain run behind the vocoder on its stream; not with a join),
+        or `pitch` (vocode(pitch=): a number or one number / None per utterance, semitones; the launch runs behind the vocoder on its stream),
         or `pauses` (vocode(pauses=)'s dict / list: the squeeze runs behind the vocoder on its stream; its record of the new lengths travels to the host as one more
         small pinned copy behind the same event, and the waveforms are cut after it: no host synchronisation is added),
         or `join` (vocode(join=)'s dict: the job's utterances are consecutive chunks of one text; `wavs` is then synthesize(join=)'s piece dict with `wav` on the host.
@@ -411,7 +441,7 @@ class ChatterboxEngine(S3GenEngine):
             is called exactly as before there was one)"""
             wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
                                   speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10), drop_last_token=kw.get("drop_last_token", True), sync=False,
-                                  **({k: job[k] for k in ("join", "format", "loudness", "pauses") if k in job}))
+                                  **({k: job[k] for k in ("join", "format", "loudness", "pauses", "pitch") if k in job}))
             return wavs
 
         def to_host(job, wavs, pinned):
@@ -1027,14 +1057,17 @@ class TurboEngine(S3GenEngine):
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
         for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=);
         speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=); join: None, or vocode(join=)'s dict -- the call then returns
         ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict; loudness: None, or vocode(loudness=)'s targets (not with a join);
-        pauses: None, or vocode(pauses=)'s dict / list, as ChatterboxEngine.synthesize(pauses=) returns its results."""
+        pauses: None, or vocode(pauses=)'s dict / list, as ChatterboxEngine.synthesize(pauses=) returns its results; pitch: None, or vocode(pitch=)'s semitones,
+        checked against speed before anything is launched as ChatterboxEngine.synthesize(pitch=) does."""
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
+        pitch = ops.check_pitch(pitch, len(text_tokens))
+        ops.check_speed_pitch(speed, pitch, len(text_tokens))
         join = ops.check_join(join, len(text_tokens))
         fmt = ops.check_format_arg(format)
         loud = ops.check_loudness(loudness, len(text_tokens))
@@ -1050,7 +1083,7 @@ class TurboEngine(S3GenEngine):
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed,
                               **({} if join is None else dict(join=join)), **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)),
-                              **({} if pz is None else dict(pauses=pz)))
+                              **({} if pz is None else dict(pauses=pz)), **({} if pitch is None else dict(pitch=pitch)))
         if join is not None:
             wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks, max_gen_len),
                         **({} if pz is None else dict(pauses=wavs["pauses"].tolist())))

@@ -1206,6 +1206,111 @@ def piece_on_host(out, rec, n, fmt=None):
     return piece if fmt is None else dict(piece, wav=out[: formatted_len(rec[R], fmt["sample_rate"])], format=fmt)
 
 
+# ----------------------------------------------------------------------------- pitch control: the waveform read back at a real step (wave_pitch.hip)
+PITCH_MIN, PITCH_MAX = -12.0, 12.0               # semitones a caller may ask for
+PITCH_Z, PITCH_L, PITCH_BETA = 16, 256, 9.0      # zero crossings per side, table steps per crossing, Kaiser beta: UNMEASURED choices
+_PITCH_FILTER, _PITCH_TABLES = {}, {}
+
+
+def pitch_ratio(p):
+    """The frequency ratio of `p` semitones: 2.0 ** (p / 12.0) in Python floats.  THE definition: the mel's stretch and the kernel's step come from here."""
+    return 2.0 ** (float(p) / 12.0)
+
+
+def check_pitch(value, B, name="pitch"):
+    """A `pitch` argument as a list of B floats (semitones; a None entry is 0.0), or None when no request is transposed (None, or every entry None or 0).  A
+    number serves every request; anything else must be a list or tuple of exactly B numbers / Nones in [-12, 12].  A bool or a non-number is a TypeError; a
+    non-finite or out-of-range value and a wrong length are ValueErrors -- raised before anything is launched."""
+    import math
+    import numbers
+    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    if value is None:
+        return None
+    if one(value):
+        value = [value] * B
+    elif not isinstance(value, (list, tuple)):
+        raise TypeError(f"{name}: expected None, a number or a list of {B} numbers, got {type(value).__name__}")
+    if len(value) != B:
+        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
+    out = []
+    for k, v in enumerate(value):
+        if v is None:
+            v = 0.0
+        if not one(v):
+            raise TypeError(f"{name}[{k}]: expected None or a number, got {type(v).__name__}")
+        v = float(v)
+        if not math.isfinite(v) or not PITCH_MIN <= v <= PITCH_MAX:
+            raise ValueError(f"{name}[{k}] = {v}: a pitch is a finite number of semitones in [{PITCH_MIN}, {PITCH_MAX}]")
+        out.append(v)
+    return None if all(v == 0.0 for v in out) else out
+
+
+def check_speed_pitch(speed, pitch, B):
+    """The rates at which the mel is stretched when `speed` and `pitch` (as check_speed / check_pitch take them) meet: None without a pitch -- the call is then
+    the one with `speed` alone --, else B floats s_eff[b] = speed[b] / pitch_ratio(pitch[b]), a request without a pitch at exactly its speed.  The vocoder's
+    source is 480 scaled_len(K, s_eff) samples, read at a step of pitch_ratio into 480 scaled_len(K, speed).  Every s_eff must lie in [0.5, 2.0], where the mel's
+    stretch is defined: otherwise a ValueError that names both arguments, before anything is launched."""
+    speed, pitch = check_speed(speed, B), check_pitch(pitch, B)
+    if pitch is None:
+        return None
+    speed = [1.0] * B if speed is None else speed
+    eff = [s if p == 0.0 else s / pitch_ratio(p) for s, p in zip(speed, pitch)]
+    for k, (s, p, e) in enumerate(zip(speed, pitch, eff)):
+        if not SPEED_MIN <= e <= SPEED_MAX:
+            raise ValueError(f"speed[{k}] = {s} with pitch[{k}] = {p}: the mel would be stretched at speed / 2^(pitch / 12) = {e:.4f}, outside [{SPEED_MIN}, {SPEED_MAX}]")
+    return eff
+
+
+def pitch_filter():
+    """The interpolation filter of the pitch step, built once in NumPy fp64: h(t) = sinc(t) I0(beta sqrt(1 - (t / Z)^2)) / I0(beta) for |t| < Z, else 0 -- a
+    Kaiser-windowed sinc of Z = 16 zero crossings per side, beta = 9.0 -- as the fp32 table tab[k] = h(k / L), k = 0 .. Z L + 1, L = 256 steps per crossing (4098
+    floats, 16 KiB).  tab[0] = 1; tab[k] = 0 exactly at every other multiple of L and for k >= Z L: a step of 1 then returns the input's bits."""
+    import numpy as np
+    if not _PITCH_FILTER:
+        Z, L, beta = PITCH_Z, PITCH_L, PITCH_BETA
+        t = np.arange(Z * L + 2, dtype=np.float64) / L
+        h = np.sinc(t) * np.i0(beta * np.sqrt(np.maximum(0.0, 1.0 - (t / Z) ** 2))) / np.i0(beta)
+        h[0] = 1.0
+        h[L::L] = 0.0
+        h[Z * L:] = 0.0
+        _PITCH_FILTER.update(Z=Z, L=L, beta=beta, h=h, tab=np.ascontiguousarray(h.astype(np.float32)))
+    return _PITCH_FILTER
+
+
+def _pitch_table(device):
+    """pitch_filter's table on `device`, uploaded once per device"""
+    key = str(device)
+    if key not in _PITCH_TABLES:
+        _PITCH_TABLES[key] = torch.from_numpy(pitch_filter()["tab"]).to(device)
+    return _PITCH_TABLES[key]
+
+
+def wave_pitch(rows, steps, out_lens):
+    """cbx_wave_pitch_f32 on the current stream: row r (_wave_rows: 1 .. 64 1-D fp32 views of ONE allocation) read at a step of steps[r] source samples per output
+    sample (R Python floats in [0.5, 2.0]) into out_lens[r] samples, through pitch_filter's windowed sinc with its cutoff at min(1, 1 / step) of the source's Nyquist
+    rate, in ONE launch (include/cbx.h states the definition).  Samples outside a row read as zeros; a step of 1 copies the row.  Returns R 1-D fp32 tensors that
+    are views of one packed device buffer, each beginning on a 16-byte boundary of it.  No host synchronisation."""
+    rows = list(rows)
+    steps, out_lens = [float(s) for s in steps], [int(n) for n in out_lens]
+    if len(steps) != len(rows) or len(out_lens) != len(rows):
+        raise ValueError(f"wave_pitch: {len(steps)} steps and {len(out_lens)} lengths for {len(rows)} rows")
+    if any(n < 0 for n in out_lens):
+        raise ValueError(f"wave_pitch: out_lens {out_lens}")
+    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: every tap reads outside its row)
+        return [torch.zeros(n, device=w.device) for w, n in zip(rows, out_lens)]
+    base, offs, lens = _wave_rows(rows, "wave_pitch")
+    R, dev, f = len(lens), rows[0].device, pitch_filter()
+    starts, pos = [], 0
+    for n in out_lens:
+        starts.append(pos)
+        pos += -(-n // 4) * 4
+    packed = torch.empty(max(1, pos), device=dev)
+    st, ol, o = (ctypes.c_double * R)(*steps), (ctypes.c_int * R)(*out_lens), (ctypes.c_long * R)(*starts)
+    check(lib.cbx_wave_pitch_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(st), ctypes.addressof(ol), R, _p(_pitch_table(dev)), f["Z"], f["L"],
+                                 _p(packed), ctypes.addressof(o), packed.numel(), _stream()), "cbx_wave_pitch_f32")
+    return [packed[a: a + n] for a, n in zip(starts, out_lens)]
+
+
 # ----------------------------------------------------------------------------- output formats: resample + encode ahead of the copy to the host (wave_format.hip)
 WAVE_IN_RATE = 24000
 WAVE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)

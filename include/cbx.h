@@ -888,6 +888,33 @@ int cbx_wave_join_f32(const float* wav, const long* row_off, const int* row_len,
 int cbx_wave_squeeze_f32(const float* wav, const long* row_off, const int* row_len, const int* keep, int R, double ratio, const float* ramp, int fade, float* out,
                          long out_cap, int* edges, int* stats, void* ws, long ws_cap, void* stream);
 
+/* ---- pitch control: read the rows of a batch back at an arbitrary real step, one launch (added after ABI v16 without a version step: a new function only).  The
+ * reference vocodes the flow's mel as it is (models/s3gen/s3gen.py:289) and returns the result (tts.py:272, mtl_tts.py:352, tts_turbo.py:320, vc.py:104); it has
+ * no transpose.  Here a pitch of p semitones, p in [-12, 12], is the ratio r = 2^(p / 12): with the speaking rate s the mel is stretched at s_eff = s / r
+ * (cbx_mel_time_scale_f32; s_eff in [0.5, 2]), the vocoder runs on the stretched mel, and this entry reads its cut row -- the source, n_src = 480 scaled_len(K,
+ * s_eff) samples for the K frames of the unscaled call -- at step = r into N = 480 scaled_len(K, s) samples: exactly the length of the call without a pitch, every
+ * frequency multiplied by r.  The formants move with the pitch (varispeed with the duration restored); nothing here preserves them.
+ * Rows as cbx_wave_format_f32 takes them: R in [1, 64] rows of row_len[r] floats at wav + row_off[r]; row_off, row_len, step, out_len and out_off are HOST arrays
+ * (by value; 4-byte alignment of a row is enough).  step[r]: source samples per output sample, a finite double in [0.5, 2]; c = min(1.0, 1.0 / step), computed
+ * here in fp64: the cutoff relative to the source's Nyquist rate, and the gain.
+ * Filter: Z zero crossings per side, L table steps per crossing, h(t) = sinc(t) I0(beta sqrt(1 - (t / Z)^2)) / I0(beta) for |t| < Z, else 0 (the project uses Z = 16,
+ *   L = 256, Kaiser beta = 9.0).  tab: Z L + 2 device floats built by the CALLER in fp64, tab[k] = h(k / L); tab[0] = 1, and tab[k] = 0 exactly at every other
+ *   multiple of L and for k >= Z L.
+ * Output j < out_len[r] of a row x of n = row_len[r] samples:
+ *   x_j = j * step in fp64; for i ascending over max(0, ceil(x_j - Z / c)) .. min(n - 1, floor(x_j + Z / c)):
+ *     u = |x_j - i| * c * L in fp64; the tap is skipped if u >= Z L; k = (long)u, a = (float)(u - k);
+ *     w = fmaf(a, tab[k + 1] - tab[k], tab[k]); acc = fmaf(w, x[i], acc) starting from 0;
+ *   y[j] = (float)c * acc.
+ *   Taps outside the row read nothing: an output whose taps all lie outside [0, n) is 0.  At most floor(2 Z / c) + 2 taps per output (66 at step 2).  step = 1
+ *   returns the input's bits for finite samples (a -0 comes back as +0); h is continuous, so how the compiler rounds x_j - i does not matter beyond the bound.
+ * out: ONE buffer of out_cap floats; row r's outputs go to out + out_off[r].  Nothing else is written.  One workgroup per 256 outputs of a row; the result does not
+ * depend on the grid or on a row's alignment; 16-byte loads where a row's addresses allow, 4-byte accesses elsewhere; positions are 64-bit.
+ * -22 before any launch, nothing written: a null pointer, R outside [1, 64], a negative length or offset, a step that is not finite or outside [0.5, 2], Z or L < 1
+ * or Z L + 2 > 4098 (or a reach 2 Z / c beyond the kernel's staging), a row that would write outside [0, out_cap), out_cap below the sum of the rows' outputs, out
+ * overlapping wav. */
+int cbx_wave_pitch_f32(const float* wav, const long* row_off, const int* row_len, const double* step, const int* out_len, int R, const float* tab, int Z, int L,
+                       float* out, const long* out_off, long out_cap, void* stream);
+
 /* ---- output formats: resample 24 kHz fp32 to the delivery rate and encode it, one launch for the rows of a batch or of a stream's round (added after ABI v16
  * without a version step: a new function only).  The reference returns 24 kHz fp32 and leaves this to its caller (tts.py:272, mtl_tts.py:352, tts_turbo.py:320,
  * vc.py:104).  Rows as cbx_wave_join_f32 takes them: R in [1, 64] pieces of row_len[r] floats at wav + row_off[r] (HOST arrays; 4-byte alignment is enough).
