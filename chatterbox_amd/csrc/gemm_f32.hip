@@ -350,6 +350,9 @@ extern "C" int cbx_gemm_f32(const cbx_gemm_t* pp, void* stream) {
     CBX_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
     CBX_REQUIRE(p.K == p.taps * p.Cin, "gemm: K=%d != taps*Cin=%d*%d", p.K, p.taps, p.Cin);
     CBX_REQUIRE(p.taps == 1 || p.Cin % 16 == 0, "gemm: conv needs Cin %% 16 == 0 (Cin=%d)", p.Cin);
+    // every loader walks K in float4 units and guards a unit by its FIRST column only: with W in [N][K] layout a K tail would multiply the
+    // 1 .. 3 columns behind K of both operands in (strided views: whatever lies there)
+    CBX_REQUIRE(p.w_kn || p.K % 4 == 0, "gemm: K %% 4 == 0 is required unless w_kn (K=%d): pad K with zero columns", p.K);
     CBX_REQUIRE(p.lda % 4 == 0 && p.a_s1 % 4 == 0 && p.a_s2 % 4 == 0 && ((uintptr_t)p.A & 15) == 0,
                 "gemm: A must be 16-byte aligned (lda=%ld)", p.lda);
     CBX_REQUIRE(p.ldw % 4 == 0 && p.w_s1 % 4 == 0 && p.w_s2 % 4 == 0 && ((uintptr_t)p.W & 15) == 0,

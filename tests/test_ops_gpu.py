@@ -16,8 +16,10 @@ def _close(got, ref, tol, what=""):
     got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
     err = (got - ref).abs()
     lim = tol * (1.0 + ref.abs())
-    bad = err > lim
-    assert not bad.any(), f"{what}: max err {err.max():.3e} (ref max {ref.abs().max():.3e}), {int(bad.sum())} / {bad.numel()} over tol {tol}"
+    bad = ~(err <= lim)  # a NaN anywhere (err is NaN) is a failure
+    nonfinite = int((~torch.isfinite(got)).sum())
+    assert not bad.any(), (f"{what}: max err {torch.nan_to_num(err, nan=0.0).max():.3e} (ref max {ref.abs().max():.3e}), {int(bad.sum())} / {bad.numel()} over tol {tol}, "
+                           f"{nonfinite} non-finite in the output")
 
 
 def _r(shape, seed, scale=1.0):

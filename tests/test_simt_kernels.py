@@ -236,6 +236,33 @@ def test_vocoder_edge_bodies_on_the_emulator(emu, name, args):
     getattr(V, name)(ops, CPU, *args)
 
 
+# tests/test_smallest_shapes_gpu.py (smallest_shapes_common.py: the pipelined kernels where their prologues and drains run) -- a reduced matrix that keeps every branch:
+# K walks of 1, 2, 3 K tiles at BK = 32 and BK = 64 (and 4, 6: the full Linear shape list) on the dispatcher's choice, a symmetric three-stage form of each K tile width
+# (12, 45), loader-wave forms with one and four loaders (21, 33), the four-stage rings (25, 34), both deferred-epilogue forms with both df_kinds on tile walks (the
+# `nk < PKT` arm) and one tile per workgroup (the drain), the LayerNorm epilogue at nk = 1, 2, 3, the conv and the transposed column range on a symmetric and a
+# loader-wave form, every attention version at T = 7, 65, 129 (one, two and three KV tiles), the fp32-operand GEMMs in full, the K % 4 contract.
+def _smallest_shape_cases():
+    import smallest_shapes_common as S
+    cases = [("check_linear_tile", (t, p)) for t, p in ((0, 2), (12, 2), (12, 0), (45, 2), (21, 2), (21, 0), (33, 2), (25, 2), (34, 0))]
+    cases += [("check_deferred_epilogue", (t, pl, p, M, N)) for t, pl in ((41, 32), (42, 35)) for p, M, N in ((2, 300, 640), (0, 65, 512))]
+    cases += [("check_layernorm_epilogue", (32, 2)), ("check_layernorm_epilogue", (64, 0)), ("check_layernorm_epilogue", (96, 2))]
+    cases += [("check_conv_tile", (12, 2)), ("check_conv_tile", (21, 2)), ("check_conv_tile", (33, 0)), ("check_conv_tile", (43, 2))]
+    cases += [("check_transposed_tile", (9, 2)), ("check_transposed_tile", (14, 2)), ("check_transposed_tile", (21, 0))]
+    cases += [("check_attention", (v, (7, 65, 129))) for v in range(7)]
+    cases += [("check_f32_linear", (1, S.F32_P1_M, S.F32_P1_N, S.F32_P1_K))] + [("check_f32_linear", (p, S.F32_SPLIT_M, S.F32_SPLIT_N, S.F32_SPLIT_K)) for p in (3, 6, 16)]
+    cases += [("check_f32_layernorm_fold", ())] + [("check_k_multiple_of_4_contract", (p, M)) for p in (1, 16) for M in (1, 33)]
+    return cases
+
+
+_SMALLSHAPE = _smallest_shape_cases()
+
+
+@pytest.mark.parametrize("name,args", _SMALLSHAPE, ids=["-".join([n] + [str(a).replace(" ", "") for a in args]) for n, args in _SMALLSHAPE])
+def test_smallest_shape_bodies_on_the_emulator(emu, name, args):
+    import smallest_shapes_common as S
+    getattr(S, name)(CPU, *args)
+
+
 @pytest.mark.parametrize("tile,persist", [(0, 1), (1, 0), (3, 8), (7, 1), (12, 0), (15, 8), (21, 1), (24, 8), (26, 0), (28, 1), (31, 8), (32, 1), (33, 0), (34, 8), (36, 1)])
 def test_gemm_planes_tiles_small(emu, tile, persist):
     """tests/test_planes_gpu.py::test_gemm_planes_linear_tiles at emulator-sized shapes: symmetric, loader-wave (21+) and 16-wave (26+) tile
@@ -631,7 +658,8 @@ def _rerun(env, select):
     return r.returncode, (r.stdout + r.stderr)[-1500:]
 
 
-_DMA_TESTS = "gemm_planes_tiles_small or flash_attn_planes_small or conv_and_transposed_columns or transposed_walk or layernorm_epilogue or deferred_epilogue"
+_DMA_TESTS = ("gemm_planes_tiles_small or flash_attn_planes_small or conv_and_transposed_columns or transposed_walk or layernorm_epilogue or deferred_epilogue "
+              "or smallest_shape")
 
 
 def test_counted_waits_of_the_lds_dma_pipelines_are_sufficient(emu):
@@ -644,6 +672,10 @@ def test_counted_waits_of_the_lds_dma_pipelines_are_sufficient(emu):
     assert rc == 0, out
     rc, out = _rerun({"CBX_EMU_DMA": "deferred", "CBX_EMU_DMA_SLACK": "1"}, "gemm_planes_tiles_small and 21-1")
     assert rc != 0, "weakened waits went unnoticed: the deferred-DMA mode is not effective\n" + out
+    # ... and the short K walks notice it too (nk = 1 .. 3 against a three-stage ring; a loader-wave form)
+    for sel in ("smallest_shape and check_linear_tile-12-2", "smallest_shape and check_linear_tile-21-2"):
+        rc, out = _rerun({"CBX_EMU_DMA": "deferred", "CBX_EMU_DMA_SLACK": "1"}, sel)
+        assert rc != 0, f"weakened waits went unnoticed by the short-walk cases ({sel})\n" + out
 
 
 def test_results_do_not_depend_on_the_lane_schedule(emu):
@@ -652,7 +684,8 @@ def test_results_do_not_depend_on_the_lane_schedule(emu):
     The workgroups of a launch run in a shuffled order too (the split-context decode attention must merge in split order whoever arrives last).
     Self-check: with the first barrier of every thread dropped (CBX_EMU_DROP_BARRIER=0) the same selection must fail."""
     sel = ("test_sampler or test_layernorm_rmsnorm or test_flash_attn or decode_attn_rope_fused or split_context or test_hift or (gemm_planes_tiles_small and 21-1) "
-           "or (gemm_planes_tiles_small and 3-8) or (gemm_planes_tiles_small and 32-1) or (test_gemv_packed_rms_fused and False) or flash_attn_planes_small or layernorm_epilogue")
+           "or (gemm_planes_tiles_small and 3-8) or (gemm_planes_tiles_small and 32-1) or (test_gemv_packed_rms_fused and False) or flash_attn_planes_small or layernorm_epilogue "
+           "or (smallest_shape and (check_deferred_epilogue or check_linear_tile-21 or check_linear_tile-33 or check_linear_tile-25))")  # DF and loader-wave forms on short K walks
     rc, out = _rerun({"CBX_EMU_SCHED": "random:5"}, sel)
     assert rc == 0, out
     rc, out = _rerun({"CBX_EMU_SCHED": "random:5", "CBX_EMU_DROP_BARRIER": "0"}, "test_gemv_decode or test_linear")  # the K-slice reduction through LDS
