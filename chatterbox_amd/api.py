@@ -20,8 +20,8 @@ from typing import Optional
 import torch
 
 from . import ops, synth
-from .engine import ChatterboxEngine, S3GenEngine, TurboEngine
-from .text import CJK_LANGUAGES, EnTokenizer, MTLTokenizer, default_max_chars, punc_norm, punc_norm_en, punc_norm_turbo, split_text
+from .engine import ChatterboxEngine, S3GenEngine, TurboEngine, frame_sample
+from .text import CJK_LANGUAGES, EnTokenizer, MTLTokenizer, default_max_chars, punc_norm, punc_norm_en, punc_norm_turbo, split_text, word_groups
 
 S3GEN_SR, S3_SR = 24000, 16000
 REPO_ID = "ResembleAI/chatterbox"
@@ -528,6 +528,31 @@ def _analysed_once(requests, analyse):
 _NO_VOICE = "Please `prepare_conditionals` first or specify `audio_prompt_path`"
 
 
+WORD_TIMES_PAUSE = ("max_pause together with word_times: the pause step's cut map is data on the device, and mapping word boundaries through it is not built "
+                    "-- ask for one of the two")
+
+
+def _word_times(word_times, max_pause=None):
+    """word_times of generate / generate_batch / generate_long -> None (False / None: the call without the argument), "words" (True / "words") or "tokens"."""
+    if word_times is None or word_times is False:
+        return None
+    mode = "words" if word_times is True else word_times
+    if mode not in ("words", "tokens"):
+        raise ValueError(f'word_times: expected False, True, "words" or "tokens", got {word_times!r}')
+    pauses = max_pause if isinstance(max_pause, (list, tuple)) else [max_pause]
+    if any(v is not None for v in pauses):
+        raise ValueError(WORD_TIMES_PAUSE)
+    return mode
+
+
+def _no_word_times(method, word_times):
+    """generate_long_stream lists word_times only because its signature is generate_long's plus the ramp; anything but False / None is refused as an argument the
+    method does not take"""
+    if word_times is not None and word_times is not False:
+        raise TypeError(f"{method}() does not take word_times: a stream has no finished token sequence for the alignment pass to read -- use generate_long("
+                        "return_segments=True, word_times=...)")
+
+
 class _Finish:
     """The epilogue of every public method that returns audio, and the `audio_in` switch of every method that takes audio."""
     sr = S3GEN_SR
@@ -620,6 +645,7 @@ class _TTS(_Finish):
     PROMPT_LEN = 150    # T3Config.speech_cond_prompt_len
     ANALYSIS_KW = {}    # further keywords of the voice-prompt analysis (_prepare_conditionals)
     max_batch = None    # utterances per device batch of generate_batch / generate_long (None: the T3 engine's MAX_BATCH)
+    align_heads = None  # (layer, head) pairs the alignment pass of word_times= reads (None: T3Engine.ALIGN_HEADS, an UNMEASURED default)
 
     def __init__(self, engine, tokenizer, device, conds: Optional[Conditionals] = None, analyzer=None):
         self.engine, self.tokenizer, self.device, self.conds = engine, tokenizer, device, conds
@@ -654,11 +680,55 @@ class _TTS(_Finish):
         assert all(c is not None for c in out), _NO_VOICE
         return out
 
+    # ------------------------------------------------------------------------------------------------------------ word timestamps
+    def _word_mode(self, word_times, max_pause=None):
+        """_word_times, and what the mode needs from this model: "words" a tokenizer with pieces(ids) (text.MTLTokenizer.pieces)"""
+        mode = _word_times(word_times, max_pause)
+        if mode == "words" and not hasattr(self.tokenizer, "pieces"):
+            raise ValueError('word_times="words" needs a tokenizer with pieces(ids) to group text tokens into words; word_times="tokens" does not')
+        return mode
+
+    def _long_word_mode(self, word_times, max_pause, return_segments):
+        mode = self._word_mode(word_times, max_pause)
+        if mode is not None and not return_segments:
+            raise ValueError("word_times without return_segments: the words of generate_long travel in its segments")
+        return mode
+
+    def _word_kw(self, mode):
+        return {} if mode is None else dict(words=dict(heads=self.align_heads))
+
+    def _words_of(self, mode, tokens, al, place):
+        """The words of one utterance: dict(text, start, stop, tokens=(a, b), frames=(f0, f1)) in text order.  tokens: the engine's 1-D text ids; al: its entry of
+        synthesize(words=)'s alignment; place(s): a 24 kHz sample of the utterance's own waveform -> a sample of what the caller receives (clipping included).
+        A word begins where its first token's frames begin and ends where the next word begins -- frames of spaces and control tokens go to the word in front
+        of them --, the last one where its last token's frames end: start / stop are nondecreasing and stop of one word is start of the next.
+        mode "tokens": every text token is a word (text: its piece, or its id where the tokenizer has no pieces)."""
+        ids = [int(i) for i in tokens.view(-1).tolist()]
+        pieces = self.tokenizer.pieces(ids) if hasattr(self.tokenizer, "pieces") else [str(i) for i in ids]
+        space = getattr(self.tokenizer, "SPACE", "[SPACE]")
+        groups = [(i, i + 1) for i in range(len(ids))] if mode == "tokens" else word_groups(pieces, space)
+        if not groups:
+            return []
+        fr = al["frames"]
+        at = lambda f: int(place(frame_sample(f, al["speed"], al["pitch"])))
+        starts = [at(fr[a][0]) for a, _ in groups]
+        stops = starts[1:] + [max(starts[-1], at(fr[groups[-1][1] - 1][1]))]
+        return [dict(text="".join(pieces[a:b]).replace(space, " ").strip() if mode == "words" else pieces[a], start=s0, stop=s1, tokens=(a, b),
+                     frames=(fr[a][0], fr[b - 1][1])) for (a, b), s0, s1 in zip(groups, starts, stops)]
+
+    @staticmethod
+    def _place(n_out, fmt):
+        """_words_of's place for a waveform returned whole: through the format's rate (ops.formatted_len, as segments go), clipped to its n_out samples"""
+        return lambda s: min(n_out, s if fmt is None else ops.formatted_len(s, fmt["sample_rate"]))
+
     # ------------------------------------------------------------------------------------------------------------ one utterance
-    def _generate(self, text_ids, fmt=None, **kw):
-        """generate() behind its argument handling: tokenizer ids -> the finished waveform.  kw: sampling arguments, and _synth_kw's if they are to differ."""
-        wavs, _ = self.engine.synthesize([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw), **self._engine_format(fmt))
-        return self._finish(wavs[0], fmt)
+    def _generate(self, text_ids, fmt=None, word_mode=None, **kw):
+        """generate() behind its argument handling: tokenizer ids -> the finished waveform (word_mode: and its words).  kw: sampling arguments, and _synth_kw's if
+        they are to differ."""
+        tokens = self._engine_tokens(text_ids)
+        res = self.engine.synthesize([tokens], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw), **self._engine_format(fmt), **self._word_kw(word_mode))
+        wav = self._finish(res[0][0], fmt)
+        return wav if word_mode is None else (wav, self._words_of(word_mode, tokens, res[2][0], self._place(wav.shape[-1], fmt)))
 
     def _generate_stream(self, text_ids, stream_kw, fmt=None, **samp):
         return self._stream_pieces(self.engine.synthesize_stream([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **self._synth_kw(), **stream_kw,
@@ -667,8 +737,10 @@ class _TTS(_Finish):
     # ------------------------------------------------------------------------------------------------------------ device batches
     def _run_jobs(self, jobs, synth_kw):
         """(wavs or joined piece, speech tokens) of every job, in order: several jobs run the throughput schedule (synthesize_pipelined) where the engine has one;
-        one job, or an engine without it, the serial schedule (synthesize), one job after the other."""
-        if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined"):
+        one job, or an engine without it, the serial schedule (synthesize), one job after the other -- also a call whose jobs carry `words` (word timestamps:
+        the alignment pass runs between T3 and the vocoder of the serial schedule; such a call gives up the T3 / flow overlap), whose results are synthesize's
+        3-tuples."""
+        if len(jobs) > 1 and hasattr(self.engine, "synthesize_pipelined") and not any(job.get("words") is not None for job in jobs):
             results = self.engine.synthesize_pipelined(jobs, **synth_kw)
             try:
                 for r in results:
@@ -681,13 +753,15 @@ class _TTS(_Finish):
             args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
             yield self.engine.synthesize(*args, **synth_kw, **job)
 
-    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, loudness=None, pauses=None, pitch=None, **analyse_kw):
+    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, loudness=None, pauses=None, pitch=None, word_times=False,
+                        **analyse_kw):
         """generate_batch behind its signature: validation of every per-request argument (seeds and speed first), then the voices, then tokenisation, then the
         device work.  samp: the sampling arguments the engine takes; unsampled: those it does not -- exaggeration, which picks the voice's cond dict, and what the
         backbone ignores."""
         texts = [texts] if isinstance(texts, str) else list(texts)
         B = len(texts)
         assert B >= 1, "empty batch"
+        word_mode = self._word_mode(word_times, None if pauses is None else pauses[0])
         seeds = _batch_seeds(seeds, B, generator)
         speed = ops.check_speed(speed, B)
         loud = ops.check_loudness(loudness, B)
@@ -700,18 +774,19 @@ class _TTS(_Finish):
         self._warn_ignored(*(v for vals in unsampled.values() for v in vals))
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, unsampled["exaggeration"], **analyse_kw)
         tokens = [self._engine_tokens(self._text_ids(t, lid)) for t, lid in zip(texts, langs)]
-        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt, loud, pz, pit)
+        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt, loud, pz, pit, word_mode)
 
     def _languages(self, language_ids, B):
         return [None] * B
 
-    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None, loud=None, pz=None, pit=None):
+    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None, loud=None, pz=None, pit=None, word_mode=None):
         """Sub-batches of at most max_batch requests in order of text length (_run_jobs: one runs the serial schedule, several the throughput schedule).  Returns the
         finished waveforms in the caller's order.  seeds (B ints or None) travel with their requests: a request's draws do not depend on the sub-batch or the row
         it lands in.  speed (B floats or None) travels the same way.  fmt (one format for the call, or None): every job carries it as `format` unless a
         watermarker is loaded (_engine_format).  loud (B LUFS targets / Nones, or None) travels with its requests like speed: a job carries `loudness` only when
         one of its requests has a target.  pz (_pauses' dict or None) the same: a job carries `pauses`, with its requests' keeps, only when one of them has one.  pit (B semitones or None) the same: a job
-        carries `pitch` only when one of its requests is transposed."""
+        carries `pitch` only when one of its requests is transposed.  word_mode (_word_mode's): every job carries `words`, the sub-batches then run the serial
+        schedule one after the other (_run_jobs), and the result is a list of (waveform, words)."""
         dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
         plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
         jobs = []
@@ -732,11 +807,14 @@ class _TTS(_Finish):
             if pit is not None and any(_pick(pit, idx)):
                 job["pitch"] = _pick(pit, idx)
             job.update(self._engine_format(fmt))
+            job.update(self._word_kw(word_mode))
             jobs.append(job)
         out = [None] * len(tokens)
-        for idx, (wavs, _) in zip(plan, self._run_jobs(jobs, self._synth_kw(batch=True))):
-            for i, w in zip(idx, wavs):
+        for idx, res in zip(plan, self._run_jobs(jobs, self._synth_kw(batch=True))):
+            for r, (i, w) in enumerate(zip(idx, res[0])):
                 out[i] = self._finish(w, fmt)
+                if word_mode is not None:
+                    out[i] = (out[i], self._words_of(word_mode, tokens[i], res[2][r], self._place(out[i].shape[-1], fmt)))
         return out
 
     def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, fmt=None, loudness=None, ramp=None, **prepare_kw):
@@ -762,7 +840,8 @@ class _TTS(_Finish):
         max_batch = int(self.max_batch or self.engine.t3.MAX_BATCH)
         plan = long_plan(chunks, max_batch, a) if ramp is None else long_stream_plan(chunks, max_batch, a, *ramp)
         t3, gen = self.conds.t3.as_dict(), self.conds.gen
-        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join", "pauses", "pitch") if k in p}) for p in plan]
+        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join", "pauses", "pitch") if k in p},
+                     **self._word_kw(a.get("words"))) for p in plan]
         return chunks, plan, jobs
 
     @staticmethod
@@ -791,10 +870,17 @@ class _TTS(_Finish):
         either -- the concatenated waveform is measured and gained as ONE signal in _finish, ahead of the watermark, so the chunks keep their relative level."""
         chunks, plan, jobs = self._long_work(text, a, tokenize, samp)
         pieces, segments, base = [], [], 0
-        for p, (piece, st) in zip(plan, self._run_jobs(jobs, self._synth_kw())):
+        fl = (lambda v: v) if fmt is None else (lambda v: ops.formatted_len(v, fmt["sample_rate"]))
+        for p, job, res in zip(plan, jobs, self._run_jobs(jobs, self._synth_kw())):
+            piece, st = res[0], res[1]
             pieces.append(piece["wav"].detach().float().cpu())
             assert pieces[-1].numel() == piece["total"], "a joined piece and its layout record disagree"
-            segments += self._long_segments(chunks, p, piece, st, base)
+            segs = self._long_segments(chunks, p, piece, st, base)
+            if a.get("words") is not None:  # a word of chunk r: its samples clipped to the kept part [src_start, src_stop), shifted to the segment's start
+                for r, seg in enumerate(segs):
+                    place = lambda v, seg=seg: fl(seg["start"] + min(max(v, seg["src_start"]), seg["src_stop"]) - seg["src_start"])
+                    seg["words"] = self._words_of(a["words"], job["text_tokens"][r], res[2][r], place)
+            segments += segs
             base += piece["total"]
         self._warn_truncated("generate_long", [s["truncated"] for s in segments], a["max_chars"])
         wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=loud)
@@ -906,7 +992,8 @@ class ChatterboxTTS(_LlamaTTS):
         return self.tokenizer.text_to_tokens(punc_norm_en(text))
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
-                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                 cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
+                 word_times=False):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
         alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
         speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
@@ -935,16 +1022,28 @@ class ChatterboxTTS(_LlamaTTS):
         three semitones keep the voice, an octave does not.  The range and the filter are UNMEASURED choices.  generate_batch: a number or
         one number / None per request, travelling with its request like speed.  generate_long: every chunk is transposed ahead of the join; the gaps do not
         change.  generate_stream does not take the argument.
-        This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db` and `pitch` for every method of every class of this
-        module; the others say only what differs."""
+        word_times (False; True or "words"; "tokens"): word timestamps.  The call returns (wav, words), words a list of dict(text, start, stop, tokens=(a, b),
+        frames=(f0, f1)) in text order: the word is text tokens [a, b) of the request (start / end-of-text included in the count), spoken over the speech tokens
+        [f0, f1) and the samples [start, stop) of the returned waveform -- nondecreasing, stop of one word is start of the next, everything clipped to the
+        waveform's length; with `speed`, `pitch` and `sample_rate` the boundaries are mapped as the audio is.  "tokens": one entry per text token, no grouping.
+        The times come from T3's own attention: after the tokens are sampled, one teacher-forced pass over the request reads how much attention a few heads
+        (align_heads; T3Engine.ALIGN_HEADS) put on each text token while each speech token was sampled, and a monotonic path through that is cut at the word
+        boundaries (T3Engine.align).  WHICH heads align is an UNMEASURED default taken from the reference project's analyser: nobody has
+        checked it on trained weights here.  Not together with max_pause (ValueError).  generate_batch: one flag for the call, a list of (wav, words); the
+        sub-batches of such a call run one after the other, without the T3 / flow overlap.  generate_long: with return_segments=True every segment gains `words`
+        in samples of the joined result, clipped to the segment.  generate_stream, generate_long_stream, ChatterboxTurboTTS and ChatterboxVC do not take it.
+        This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db`, `pitch` and `word_times` for every method of every
+        class of this module; the others say only what differs."""
         fmt = ops.check_format(sample_rate, encoding)
+        word_mode = self._word_mode(word_times, max_pause)
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate(self._text_ids(text), fmt, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
+        return self._generate(self._text_ids(text), fmt, word_mode, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
                               top_p=top_p, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                      max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
+                      word_times=False):
         """generate() for a text of ANY length: the reference stops at 1000 speech tokens (40 s) and cuts a longer text off.  The text is split into chunks of at
         most max_chars characters at paragraph, sentence and clause boundaries (text.split_text), the chunks are synthesised in text order as device batches
         (one: synthesize; several: the throughput schedule where the engine has it), and each batch's waveforms are trimmed of their leading / trailing silence and
@@ -961,16 +1060,19 @@ class ChatterboxTTS(_LlamaTTS):
         sample_rate, encoding: generate()'s; the whole waveform is converted once, after the watermark, and the segments' [start, stop) are then samples of the
         converted result (ceil(s U / D)) while [src_start, src_stop) stay 24 kHz samples.
         loudness: generate()'s, of the WHOLE assembled waveform measured as one signal (pauses included), so the chunks keep their relative level: one gain for
-        all of it, limited to a sample peak of 1.0, applied on the device ahead of the watermark and the conversion."""
+        all of it, limited to a sample peak of 1.0, applied on the device ahead of the watermark and the conversion.
+        word_times: generate()'s, with return_segments=True (without: ValueError): every segment gains `words`, its chunk's words shifted into the joined result
+        through the segment's start / src_start and clipped to [start, stop); the device batches of such a call run one after the other."""
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
+        a["words"] = self._long_word_mode(word_times, max_pause, return_segments)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                              max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
-                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, first_batch=1, batch_growth=2.0):
+                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, first_batch=1, batch_growth=2.0):
         """generate_long() in pieces: a generator of (1, n) CPU tensors, one per device batch as it leaves the device (empty pieces left out); concatenated along
         dim 1 they are the long-form result.  Every argument of generate_long with its meaning and default, plus the ramp of the device batches:
         first_batch (None, or an int >= 1) and batch_growth (a finite number >= 1): the batches hold s_0 = min(first_batch, step) chunks, then
@@ -987,7 +1089,10 @@ class ChatterboxTTS(_LlamaTTS):
         A first piece under 0.4 s, or a silent one, gets gain 1.  The result is not generate_long(loudness=)'s, which knows the whole signal -- except for a text of
         one piece.  The watermarker, if loaded, is applied per piece, as generate_stream does.
         sample_rate, encoding: every piece goes through ONE ops.WaveFormatStream, so the pieces add up to the conversion of the whole bit for bit.  A piece that is
-        not the last holds the resampling filter's tail back: a segment's last samples may arrive with the NEXT piece."""
+        not the last holds the resampling filter's tail back: a segment's last samples may arrive with the NEXT piece.
+        word_times: NOT taken -- it stands in the signature only because that is generate_long's plus the ramp; anything but False is a TypeError: a stream has
+        no finished token sequence for the alignment pass."""
+        _no_word_times("generate_long_stream", word_times)
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
@@ -996,7 +1101,8 @@ class ChatterboxTTS(_LlamaTTS):
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
-                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                       min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
+                       word_times=False):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
         request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
         neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
@@ -1012,7 +1118,7 @@ class ChatterboxTTS(_LlamaTTS):
         This is the contract of generate_batch of every class of this module; the others say only what differs."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch)
+                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, word_times)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                         cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, sample_rate=None, encoding=None, speed=1.0):
@@ -1074,31 +1180,36 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
         return [_language(lid, f" (request {k})") for k, lid in enumerate(langs)]
 
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                 repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
+                 word_times=False):
         """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
-        token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness: as there."""
+        token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness, word_times: as there."""
         fmt = ops.check_format(sample_rate, encoding)
+        word_mode = self._word_mode(word_times, max_pause)
         seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate(self._text_ids(text, lid), fmt, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
+        return self._generate(self._text_ids(text, lid), fmt, word_mode, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
                               top_p=top_p, **seed_kw)
 
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         fmt = ops.check_format(sample_rate, encoding)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
         a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
+        a["words"] = self._long_word_mode(word_times, max_pause, return_segments)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
     def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                              top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                             return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, first_batch=1, batch_growth=2.0):
+                             return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, first_batch=1,
+                             batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
+        _no_word_times("generate_long_stream", word_times)
         fmt = ops.check_format(sample_rate, encoding)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
@@ -1108,12 +1219,13 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
         return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                       repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
+                       word_times=False):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
         speed, before the sampling arguments)."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch)
+                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, word_times)
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,

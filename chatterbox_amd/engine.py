@@ -76,7 +76,9 @@ def _checked_job(job):
     normalises no utterance, pauses (ops.check_pauses) that shorten no utterance and a pitch (ops.check_pitch; with the job's speed: ops.check_speed_pitch) that
     transposes no utterance."""
     n = len(job["text_tokens"])
-    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness", "pauses", "pitch") or v is not None}
+    if job.get("words") is not None:
+        raise ValueError(WORDS_PIPELINED)
+    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness", "pauses", "pitch", "words") or v is not None}
     if "pitch" in job:
         job["pitch"] = ops.check_pitch(job["pitch"], n)
         if job["pitch"] is None:
@@ -104,6 +106,46 @@ def _checked_job(job):
     if "join" in job:
         job["join"] = ops.check_join(job["join"], n)
     return job
+
+
+WORDS_PIPELINED = ("words: the alignment pass runs between T3 and the vocoder of the serial schedule only -- call synthesize(words=) per job "
+                   "(synthesize_pipelined keeps two T3 states in flight; the pass inside that overlap is not built)")
+WORDS_PAUSES = ("max_pause (pauses) together with word_times (words): the cut map of the pause step is data on the device; mapping word boundaries "
+                "through it is not built")
+
+
+def check_words(words):
+    """synthesize's words= argument: None, or dict(heads=None or a sequence of (layer, head) pairs) -> None or dict(heads=...)"""
+    if words is None:
+        return None
+    if not isinstance(words, dict) or set(words) - {"heads"}:
+        raise ValueError(f"words: expected None or dict(heads=...), got {words!r}")
+    return dict(heads=words.get("heads"))
+
+
+def valid_frame_counts(toks):
+    """c[i] = how many of the sampled tokens toks[:i] the flow receives (drop_invalid_tokens), i = 0 .. len(toks): frame boundary i of the alignment -- which
+    counts every sampled token -- is boundary c[i] of the waveform's tokens.  An invalid id in the middle shifts what follows."""
+    x = toks.view(-1)
+    sos, eos = (x == START_SPEECH).nonzero(), (x == STOP_SPEECH).nonzero()
+    s = int(sos[0]) + 1 if len(sos) else 0
+    e = int(eos[0]) if len(eos) else len(x)
+    keep = (x < SPEECH_VOCAB)
+    keep[:s] = False
+    keep[e:] = False
+    return [0] + torch.cumsum(keep.long(), 0).tolist()
+
+
+def frame_sample(f, speed=None, pitch=None):
+    """The 24 kHz sample at which token frame f (a count of valid speech tokens; 2 mel frames, 960 samples each at speed 1) begins in the waveform vocode(speed=,
+    pitch=) returns: the first stretched mel frame j whose position x_j = stretch_position(j, s_eff) is at or beyond mel frame 2 f (s_eff = speed / 2^(pitch /
+    12), the rate the mel is stretched at), times 480 -- and under a pitch, which reads that waveform back at a step of r = 2^(pitch / 12), divided by r.  Not
+    clipped to the waveform's length: the caller does that."""
+    s, r = float(speed or 1.0), (1.0 if not pitch else ops.pitch_ratio(pitch))
+    s_eff = s / r
+    j = 2 * int(f) if s_eff == 1.0 else _first_frame_at(2.0 * int(f), s_eff)
+    pos = (SAMPLES_PER_TOKEN // 2) * j
+    return pos if r == 1.0 else int(math.floor(pos / r + 0.5))
 
 
 LOUDNESS_JOIN = "loudness together with join: a long text is normalised as a whole, after its pieces are assembled (generate_long(loudness=))"
@@ -338,7 +380,8 @@ class ChatterboxEngine(S3GenEngine):
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
-                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None):
+                   noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None,
+                   words=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
@@ -352,7 +395,19 @@ class ChatterboxEngine(S3GenEngine):
         pauses: None, or vocode(pauses=)'s dict / list -- silences inside an utterance longer than its keep are shortened on the device; the waveforms come back cut
         to their new lengths, a joined piece gains `pauses` = the record {n', pauses cut, frames removed, n} per chunk as lists.
         pitch: None, a number or B numbers / Nones in [-12, 12] semitones -- vocode(pitch=): utterance b comes back transposed by pitch[b] at the length speed[b]
-        alone gives it; T3 and its tokens do not depend on it.  speed / 2^(pitch / 12) outside [0.5, 2.0] is a ValueError before anything is launched."""
+        alone gives it; T3 and its tokens do not depend on it.  speed / 2^(pitch / 12) outside [0.5, 2.0] is a ValueError before anything is launched.
+        words: None, or dict(heads=None or (layer, head) pairs) -- word timestamps: T3Engine.align runs between T3 and the vocoder, on the state the tokens came
+        from, and the call returns (wavs, speech_tokens, alignment): per utterance dict(frames = [(f0, f1) per text token]: the token is spoken over the valid
+        speech tokens [f0, f1) (valid_frame_counts: the tokens the flow receives; 960 samples each at speed 1), n_frames, speed, pitch -- what frame_sample needs
+        to turn a frame into a sample of wavs[b]).  Not together with pauses; at most T3Engine.MAX_BATCH utterances.  Without it the call is launch for launch
+        the one it always was."""
+        words = check_words(words)
+        if words is not None:
+            if pauses is not None and ops.check_pauses(pauses, len(text_tokens)) is not None:
+                raise ValueError(WORDS_PAUSES)
+            if len(text_tokens) > self.t3.MAX_BATCH:
+                raise ValueError(f"words: {len(text_tokens)} utterances (at most {self.t3.MAX_BATCH}: the pass runs on the state of ONE device batch)")
+            self.t3.check_align_heads(words["heads"])
         seeds = ops.request_seeds(seeds, len(text_tokens), generator)
         speed = ops.check_speed(speed, len(text_tokens))
         pitch = ops.check_pitch(pitch, len(text_tokens))
@@ -371,6 +426,16 @@ class ChatterboxEngine(S3GenEngine):
         torch.cuda.synchronize()
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         st = _valid_tokens(toks)
+        alignment = None
+        if words is not None:
+            t1 = time.perf_counter()
+            spans = self.t3.align(text_tokens, toks, align_heads=words["heads"])
+            alignment = []
+            for b, (sp, t) in enumerate(zip(spans, toks)):
+                c = valid_frame_counts(t)
+                alignment.append(dict(frames=[(c[f0], c[f1]) for f0, f1 in sp.tolist()], n_frames=c[-1], speed=None if speed is None else speed[b],
+                                      pitch=None if pitch is None else pitch[b]))
+            self.last_timing["align_s"] = time.perf_counter() - t1
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
                               drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)),
                               **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)), **({} if pz is None else dict(pauses=pz)),
@@ -379,7 +444,7 @@ class ChatterboxEngine(S3GenEngine):
             wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks),
                         **({} if pz is None else dict(pauses=wavs["pauses"].tolist())))
         self.last_timing["total_s"] = time.perf_counter() - t0
-        return wavs, st
+        return (wavs, st) if alignment is None else (wavs, st, alignment)
 
     @staticmethod
     def _truncated(toks):

@@ -515,6 +515,45 @@ def flash_attn(q, k, v, out, scale, key_lens=None, causal=False):
     return out
 
 
+def attn_text_mass(q, k, mass, heads, q_len, ctx0, t0, t_len, scale, weight=1.0, accumulate=False, q0=None):
+    """cbx_attn_text_mass_f32 on the current stream: mass[z, i, t] (+)= weight * sum over `heads` (in list order; ints of THIS layer, 1 .. 16 of them) of the
+    attention probability query i of row z puts on key t0[z] + t, the softmax taken over every visible key j <= ctx0[z] + i.  q (Z, Tq, H, 64) and k (Z, Tk, H,
+    64): strided views with unit inner stride, q's head stride 64, k's free (a view of the KV cache); mass (Z, >= max q_len, >= max t_len) fp32 with unit inner
+    stride.  q_len, ctx0, t0, t_len: Z Python ints each; q0 (None: zeros): query i of row z is q[z, q0[z] + i].  Elements outside [q_len) x [t_len) keep what they hold.  No host synchronisation."""
+    Z, Tq, H, D = q.shape
+    heads, q_len, ctx0, t0, t_len, q0 = ([int(v) for v in a] for a in (heads, q_len, ctx0, t0, t_len, [0] * Z if q0 is None else q0))
+    assert D == 64 and k.shape[0] == Z and k.shape[2] == H and k.shape[3] == 64 and q.stride(3) == 1 and q.stride(2) == 64 and k.stride(3) == 1
+    assert mass.dim() == 3 and mass.shape[0] == Z and mass.stride(2) == 1 and all(len(a) == Z for a in (q_len, ctx0, t0, t_len, q0))
+    assert all(0 <= n <= mass.shape[1] and 0 <= a and a + n <= Tq for n, a in zip(q_len, q0)) and all(n <= mass.shape[2] for n in t_len), "attn_text_mass: a row outside q / mass"
+    assert all(n == 0 or c + n <= k.shape[1] for n, c in zip(q_len, ctx0)), "attn_text_mass: a context beyond k"
+    ia = lambda a: (ctypes.c_int * len(a))(*a)
+    hs, ql, c0, ts, tn, qs = ia(heads), ia(q_len), ia(ctx0), ia(t0), ia(t_len), ia(q0)
+    args = (_p(_f32(q, "q")), _p(_f32(k, "k")), _p(_f32(mass, "mass")), ctypes.addressof(hs), len(heads), H, ctypes.addressof(qs), ctypes.addressof(ql), ctypes.addressof(c0),
+            ctypes.addressof(ts), ctypes.addressof(tn), Z, q.stride(0), q.stride(1), k.stride(0), k.stride(1), k.stride(2), mass.stride(0), mass.stride(1),
+            float(scale), float(weight), int(bool(accumulate)))
+    _timed("attn_text_mass", 2.0 * len(heads) * 64 * sum(n * (c + n) for n, c in zip(q_len, ctx0)), 4.0 * len(heads) * 64 * sum(c + n for n, c in zip(q_len, ctx0)),
+           lambda: check(lib.cbx_attn_text_mass_f32(*args, _stream()), "cbx_attn_text_mass_f32"))
+    return mass
+
+
+def align_path(score, n, m):
+    """cbx_align_path_f32 on the current stream: the best monotonic path through score[z, :n[z], :m[z]] (Z, N, M) fp32 with unit inner stride -- include/cbx.h
+    states the recurrence.  n, m: Z Python ints each.  Returns (spans (Z, M, 2) int32: first frame and last frame + 1 of every text token, frame_tok (Z, N) int32)
+    on the device; entries beyond m[z] / n[z] are zero.  Allocates the move-bit workspace.  No host synchronisation."""
+    Z, N, M = score.shape
+    n, m = [int(v) for v in n], [int(v) for v in m]
+    assert score.stride(2) == 1 and len(n) == Z and len(m) == Z and all(1 <= v <= N for v in n) and all(1 <= v <= M for v in m), "align_path: a row outside score"
+    dev = score.device
+    spans = torch.zeros(Z, M, 2, dtype=torch.int32, device=dev)
+    frame_tok = torch.zeros(Z, N, dtype=torch.int32, device=dev)
+    ws = torch.empty(Z * max(n) * (-(-max(m) // 64)), dtype=torch.int64, device=dev)
+    na, ma = (ctypes.c_int * Z)(*n), (ctypes.c_int * Z)(*m)
+    _timed("align_path", 2.0 * sum(a * b for a, b in zip(n, m)), 4.0 * sum(a * b for a, b in zip(n, m)),
+           lambda: check(lib.cbx_align_path_f32(_p(_f32(score, "score")), score.stride(0), score.stride(1), ctypes.addressof(na), ctypes.addressof(ma), Z, _p(spans),
+                                                spans.stride(0), _p(frame_tok), frame_tok.stride(0), _p(ws), 8 * ws.numel(), _stream()), "cbx_align_path_f32"))
+    return spans, frame_tok
+
+
 def flash_relpos(q4, pp, out, scale, key_lens=None):
     """Conformer rel-pos attention without materialised scores.  q4 (Z,T,4,H,64): the fused [q + u | q + v | k | v] projection (any batch /
     token strides, unit inner strides); pp (2T-1, H*64) = linear_pos(pos_emb); out (Z,T,H,64) view."""

@@ -544,12 +544,15 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
     # ------------------------------------------------------------------ the conditioning prefix of a voice (round 6: VoicePrefixCache)
     # Later prefills with the SAME conditioning tensors run over the text positions only (a third fewer rows in every prefill GEMM at 64 text tokens) and read the
     # prefix keys from the cache (cbx_flash_attn_kv_f32).
-    def _layer_prefill_text(self, lw, x, ws, St, S, rows, kc, vc, pos, crow):
-        """_layer_prefill over the text positions alone: queries from the q | k | v workspace, keys / values [cached prefix | text] from the KV cache."""
+    def _layer_prefill_text(self, lw, x, ws, St, S, rows, kc, vc, pos, crow, after_rope=None):
+        """_layer_prefill over the text positions alone: queries from the q | k | v workspace, keys / values [cached prefix | text] from the KV cache.
+        after_rope(q4, kc): called once the layer's rotated q is in the workspace and its k in the cache (the alignment pass reads both there)."""
         ops.layernorm(x, lw["ln1"], None, ws["h"], 1e-5, rms=True)
         ops.linear(ws["h"], lw["wqkv"], ws["qkv"])
         ops.rope_kv(ws["qkv"], pos, self.cos, self.sin, kc, vc, self.H, cache_rows=crow)
         q4 = ws["qkv"].view(rows, St, 3, self.H, 64)
+        if after_rope is not None:
+            after_rope(q4, kc)
         ops.flash_attn(q4[:, :, 0], kc[:rows, :, :S].permute(0, 2, 1, 3), vc[:rows, :, :S].permute(0, 2, 1, 3), ws["att"].view(rows, St, self.H, 64), 0.125,
                        causal=True)
         ops.linear(ws["att"], lw["wo"], x, residual=x)
@@ -863,3 +866,91 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         if debug_logits:
             return out, torch.stack(step_logits)  # (steps, 2B, V)
         return (out, prefill_logits) if return_prefill_logits else out
+
+    # ------------------------------------------------------------------ word timestamps: the alignment pass
+    # (layer, head) pairs whose attention follows the text token being spoken: the set the reference project's later alignment analyser reads on the 30-layer
+    # multilingual T3.  NOT measured on this project's kernels with trained weights for either checkpoint.
+    ALIGN_HEADS = ((9, 2), (12, 15), (13, 11))
+    last_alignment = None  # what the last align() call left on the device
+
+    def check_align_heads(self, align_heads=None):
+        """align_heads (None: ALIGN_HEADS) as a tuple of (layer, head) int pairs; a pair that does not exist in the loaded model is a ValueError."""
+        heads = tuple((int(l), int(h)) for l, h in (self.ALIGN_HEADS if align_heads is None else align_heads))
+        if not heads:
+            raise ValueError("align_heads: no (layer, head) pair")
+        for l, h in heads:
+            if not (0 <= l < self.L and 0 <= h < self.H):
+                raise ValueError(f"align_heads: (layer {l}, head {h}) does not exist in a model of {self.L} layers of {self.H} heads")
+        by_layer = {}
+        for l, h in heads:
+            by_layer.setdefault(l, []).append(h)
+        if any(len(v) > 16 for v in by_layer.values()):
+            raise ValueError("align_heads: more than 16 heads of one layer")
+        return heads
+
+    @ops.on_device
+    @torch.inference_mode()
+    def align(self, text_tokens, tokens, align_heads=None, slot=0):
+        """Which text token is being spoken at every speech token (frame) of a finished generate() call: right after generate() has collected the tokens, on the
+        same state (`slot`), before anything else uses it.  text_tokens: the B 1-D id tensors generate() took; tokens: the B 1-D tensors it returned.
+        A teacher-forced prefill of the conditional rows (cache rows 0 .. B - 1) over [text | BOS BOS | tok_0 .. tok_(n-2)] behind the voice prefix that is already
+        in the cache, layer by layer through the launches of _layer_prefill_text, up to the highest layer align_heads names; at each named layer ONE
+        ops.attn_text_mass launch adds that layer's heads -- frame i of utterance b is the query at position s0_b - 1 + i, the position whose logits sampled
+        tok_i; the text columns are [34, 34 + tl_b); weight 1 / (number of heads) --, then ONE ops.align_path launch for the batch.  K / V of the text and speech
+        positions of the conditional rows are overwritten: the request is finished.  Returns the host spans (list of B (tl_b, 2) int tensors: first frame, last
+        frame + 1 per text token) and keeps last_alignment = dict(mass (B, N, M), spans (B, M, 2), frame_tok (B, N) on the device; n, m host lists; tokens: the
+        sampled tokens the pass was forced with)."""
+        heads = self.check_align_heads(align_heads)
+        dev, B = self.dev, len(text_tokens)
+        sts = [s for k, s in self._state.items() if k[3] == slot]
+        if len(sts) != 1 or sts[0]["B"] != B or len(tokens) != B:
+            raise ValueError(f"align: slot {slot} holds no finished request of {B} utterances")
+        st = sts[0]
+        tl, n = [int(t.numel()) for t in text_tokens], [int(t.numel()) for t in tokens]
+        if min(tl) < 1 or min(n) < 1:
+            raise ValueError(f"align: every utterance needs a text token and a sampled token (text {tl}, sampled {n})")
+        if max(tl) > 1024:
+            raise ValueError(f"align: {max(tl)} text tokens (at most 1024)")
+        q0 = [t + 1 for t in tl]  # frame 0 is the second BOS: index tl + 1 of the block [text | BOS BOS | speech]
+        Sx = max(a + m_ for a, m_ in zip(q0, n))
+        S = 34 + Sx
+        assert S <= st["max_ctx"], "align: the request does not fit its own KV cache"
+        # ---- embeddings: what the prefill and the decode step use -- [text | BOS BOS] by cbx_prefill_embed, speech token i (the input behind tok_i) as
+        # speech_emb[tok_i] + speech_pos[i + 1], the next_pos_ids of the sampler -- ragged ends are zeros, hidden from every real query by the causal mask
+        xt, _, _, _ = ops.prefill_embed(text_tokens, text_emb=self.text_emb, text_pos=self.text_pos, speech_emb=self.speech_emb, speech_pos=self.speech_pos,
+                                        bos_id=START_SPEECH, n_bos=2, cfg=False, abs_pos=False, cond_lens=[34] * B, cond=None, pos0=34)
+        x = torch.zeros(B, Sx, self.D, device=dev)
+        x[:, : xt.shape[1]] = xt
+        for b in range(B):
+            if n[b] > 1:
+                ids = tokens[b][: n[b] - 1].to(dev, torch.int64)
+                ops.embed(ids, self.speech_emb, x[b, q0[b] + 1: q0[b] + n[b]], table2=self.speech_pos,
+                          ids2=torch.arange(1, n[b], dtype=torch.int32, device=dev))
+        pos = (34 + torch.arange(Sx, dtype=torch.int32, device=dev)).repeat(B)
+        crow = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(Sx)
+        xf = x.view(B * Sx, self.D)
+        pws = dict(h=torch.empty(B * Sx, self.D, device=dev), qkv=torch.empty(B * Sx, 3 * self.D, device=dev),
+                   att=torch.empty(B * Sx, self.D, device=dev), g=torch.empty(B * Sx, self.F, device=dev))
+        mass = torch.zeros(B, max(n), max(tl), device=dev)
+        by_layer = {}
+        for l, h in heads:
+            by_layer.setdefault(l, []).append(h)
+        ctx0 = [34 + a for a in q0]  # frame i sees the keys j <= s0 - 1 + i
+        launched = [0]
+
+        def text_mass(hs):
+            def run(q4, kc):
+                ops.attn_text_mass(q4[:, :, 0], kc[:B, :, :S].permute(0, 2, 1, 3), mass, hs, n, ctx0, [34] * B, tl, 0.125, weight=1.0 / len(heads),
+                                   accumulate=launched[0] > 0, q0=q0)
+                launched[0] += 1
+            return run
+
+        prec = self.tune.get("prefill_prec") or 0
+        with ops.gemm_precision(prec if prec in (0, 1) else 0):  # (attention over the cache's K / V is exact fp32 only)
+            for i in range(max(by_layer) + 1):
+                self._layer_prefill_text(self.layers[i], xf, pws, Sx, S, B, st["kc"][i], st["vc"][i], pos, crow,
+                                         after_rope=text_mass(by_layer[i]) if i in by_layer else None)
+        spans, frame_tok = ops.align_path(mass, n, tl)
+        self.last_alignment = dict(mass=mass, spans=spans, frame_tok=frame_tok, n=n, m=tl, tokens=[t.detach().cpu() for t in tokens])
+        host = spans.cpu()
+        return [host[b, : tl[b]] for b in range(B)]

@@ -82,10 +82,41 @@ class MTLTokenizer:
     def text_to_tokens(self, text, language_id=None, **kw):
         return torch.IntTensor(self.encode(text, language_id=language_id, **kw)).unsqueeze(0)
 
+    def pieces(self, ids):
+        """The vocabulary strings of token ids, one per id (word_groups' input); an id outside the vocabulary is the empty string"""
+        return [self.tokenizer.id_to_token(int(i)) or "" for i in ids]
+
 
 class EnTokenizer(MTLTokenizer):
     def encode(self, txt, language_id=None, **kw):
         return self.tokenizer.encode(txt.replace(" ", self.SPACE)).ids
+
+
+# ---------------------------------------------------------------------------------------------------------------- word timestamps: text tokens -> words
+def _is_special(piece):
+    """[START], [STOP], a language tag: a bracketed name is a control token, not text"""
+    return len(piece) > 2 and piece[0] == "[" and piece[-1] == "]"
+
+
+def _is_punctuation(piece):
+    return bool(piece) and all(unicodedata.category(c)[0] == "P" for c in piece)
+
+
+def word_groups(pieces, space="[SPACE]"):
+    """Group the text-token strings of one utterance into words: a list of (a, b), word k = pieces[a:b], in text order.  A `space` token ends a word and belongs
+    to none; neither do control tokens (bracketed names: [START], [STOP], a language tag) or empty strings.  A piece that is only punctuation attaches to the
+    word before it, also across a space ("hello , world": the comma joins "hello", whose range then spans the space); with no word before it, it starts one.
+    A text without spaces is one word.  Pure host function: no tokenizer, no tensors."""
+    groups, open_ = [], False
+    for i, p in enumerate(pieces):
+        if p == space or not p or _is_special(p):
+            open_ = False
+        elif open_ or (groups and _is_punctuation(p)):
+            groups[-1] = (groups[-1][0], i + 1)
+        else:
+            groups.append((i, i + 1))
+            open_ = True
+    return groups
 
 
 # ---------------------------------------------------------------------------------------------------------------- long-form synthesis: text -> chunks

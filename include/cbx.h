@@ -916,6 +916,46 @@ int cbx_wave_squeeze_f32(const float* wav, const long* row_off, const int* row_l
 int cbx_wave_pitch_f32(const float* wav, const long* row_off, const int* row_len, const double* step, const int* out_len, int R, const float* tab, int Z, int L,
                        float* out, const long* out_off, long out_cap, void* stream);
 
+/* ---- word timestamps: the attention mass selected heads put on the text columns, and the monotonic path through it (added after ABI v16 without a version
+ * step: new functions only).  The reference returns a waveform and nothing about when a word is spoken (tts.py:272, mtl_tts.py:352); its later alignment analyser
+ * reads a few heads of T3 -- a decoder over [34 conditioning | text | BOS BOS | speech ..] -- through forward hooks that materialise whole attention rows.  Here
+ * the rows never exist.  Plain C++ kernels: no inline assembly, no atomics, every output element written by exactly one thread per launch in a fixed summation
+ * order.
+ * cbx_attn_text_mass_f32: attention probability restricted to a column range, summed over selected heads.  q, k addressed as cbx_flash_attn_kv_f32 addresses them
+ * (head_dim 64): q = base + z q_sb + (q0[z] + i) q_st + head 64 (q0: the row's first query in its q block; NULL = zeros), k = base + z k_sb + j k_st + head k_sh -- T3's KV cache [row][head][max_ctx][64] has k_st = 64, k_sh =
+ * max_ctx 64; both read with 16-byte loads (pointers on 16-byte boundaries, strides multiples of 4 floats).  HOST arrays, by value to the kernel: heads[n_sel],
+ * 1 <= n_sel <= 16, each in [0, n_heads), the heads of THIS layer (a repeated head counts twice); per row z < nz, nz in [1, 64]: q0[z], q_len[z] valid queries (0: the
+ * row writes nothing), ctx0[z] (query i sees the keys j <= ctx0 + i), t0[z] / t_len[z] (the text columns [t0, t0 + t_len), t0 + t_len <= ctx0 + 1: visible to
+ * every query).
+ *   s_h[i][j] = scale * sum_(d = 0 .. 63) q_i[d] k_j[d], by fmaf in the order d = 0 .. 63 from 0;
+ *   p_h[i][j] = expf(s_h[i][j] - M) / L with M = max_j s_h[i][j] and L = sum_j expf(s_h[i][j] - M) over ALL visible keys j <= ctx0 + i: the normaliser covers
+ *     the whole causal row, not the text columns alone (running maximum and sum per lane over the keys j = lane mod 64, joined by the xor butterfly 32 .. 1);
+ *   mass[z][i][t] = (accumulate ? mass[z][i][t] : 0) + weight * sum_(h in heads, in list order) p_h[i][t0 + t],   mass = base + z m_sb + i m_si + t, fp32.
+ * Elements with i >= q_len[z] or t >= t_len[z] are not written.  A key beyond ctx0 + i never reaches query i's result, whatever the cache holds there (NaN
+ * included), and no key beyond ctx0 + q_len - 1 is loaded.  One launch (none when no row has a query and a text column): one wave per 4 queries of a row.
+ * Caps: ctx0 + q_len <= 4608 (the RoPE table), t_len <= 1024.
+ * -22 before any launch, nothing written: a null pointer, nz outside [1, 64], n_sel outside [1, 16], a head outside [0, n_heads), a negative length, offset or
+ * stride, a context or text range over the caps, t0 + t_len > ctx0 + 1, q / k not 16-byte addressable, m_si < t_len or (nz > 1) m_sb < q_len m_si. */
+int cbx_attn_text_mass_f32(const float* q, const float* k, float* mass, const int* heads, int n_sel, int n_heads, const int* q0, const int* q_len, const int* ctx0,
+                           const int* t0, const int* t_len, int nz, long q_sb, long q_st, long k_sb, long k_st, long k_sh, long m_sb, long m_si, float scale, float weight,
+                           int accumulate, void* stream);
+/* cbx_align_path_f32: the best monotonic path through a score matrix, on the LINEAR scores (as DTW over attention weights is usually done: no log is taken);
+ * exact: fp32 adds and compares only.  score = base + z s_sb + i s_si + t, any finite fp32; n[z] frames (1 .. 4096) and m[z] text tokens (1 .. 1024) per row
+ * z < nz, nz in [1, 64] (HOST arrays, by value).
+ *   D[0][0] = score[0][0]; D[0][t > 0] = -inf
+ *   D[i][t] = score[i][t] + max(D[i-1][t], D[i-1][t-1]) (t = 0: D[i-1][0] only); move[i][t] = (D[i-1][t-1] > D[i-1][t]) -- a tie stays
+ *   end e = m - 1 if n >= m, else the lowest t <= n - 1 with the largest D[n-1][t]
+ *   walk back from (n - 1, e): frame_tok[i] = t; t -= move[i][t]
+ *   spans[t] = (first frame, last frame + 1) of the frames with frame_tok == t for t <= e; (n, n) for t > e (never reached)
+ * The path starts at token 0 and moves by 0 or 1 per frame; when n >= m it ends at m - 1 and every span is non-empty.
+ * spans: int32 pairs at base + z sp_sb + 2 t (sp_sb in ints); frame_tok: int32 at base + z ft_sb + i.  Nothing beyond m[z] pairs / n[z] frames of a row is
+ * written.  One launch for the rows of a batch: one workgroup per row, thread t owns column t, one barrier per frame, one thread walks back.
+ * ws: device workspace of ws_cap BYTES on an 8-byte boundary for the move bits, ws_cap >= 8 * nz * max_z n[z] * ceil(max_z m[z] / 64).
+ * -22 before any launch, nothing written: a null pointer, nz outside [1, 64], n outside [1, 4096], m outside [1, 1024], s_si < m, (nz > 1) a row stride
+ * short of the row (s_sb < n s_si, sp_sb < 2 m, ft_sb < n), a workspace that is misaligned or too small. */
+int cbx_align_path_f32(const float* score, long s_sb, long s_si, const int* n, const int* m, int nz, int* spans, long sp_sb, int* frame_tok, long ft_sb, void* ws,
+                       long ws_cap, void* stream);
+
 /* ---- output formats: resample 24 kHz fp32 to the delivery rate and encode it, one launch for the rows of a batch or of a stream's round (added after ABI v16
  * without a version step: a new function only).  The reference returns 24 kHz fp32 and leaves this to its caller (tts.py:272, mtl_tts.py:352, tts_turbo.py:320,
  * vc.py:104).  Rows as cbx_wave_join_f32 takes them: R in [1, 64] pieces of row_len[r] floats at wav + row_off[r] (HOST arrays; 4-byte alignment is enough).
