@@ -292,6 +292,9 @@ _SIGS = {
     "cbx_wave_pitch_f32": ([c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_int, c_f, c_f, c_long, c_f], c_int),
     "cbx_attn_text_mass_f32": ([c_f, c_f, c_f, c_f, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_int] + [c_long] * 7 + [c_float, c_float, c_int, c_f], c_int),
     "cbx_align_path_f32": ([c_f, c_long, c_long, c_f, c_f, c_int, c_f, c_long, c_f, c_long, c_f, c_long, c_f], c_int),
+    "cbx_guard_text_mass_f32": ([c_f, c_long, c_int, c_long, c_f, c_int, c_float, c_f, c_f, c_f, c_f, c_long, c_long, c_int, c_f, c_int, c_int, c_int, c_f, c_f, c_int, c_int,
+                                 c_float, c_f, c_long, c_long, c_f], c_int),
+    "cbx_guard_update_f32": ([c_f, c_long, c_long, c_int, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_long, c_long, c_f, c_f, c_f, c_f, c_long, c_int, c_int, c_int, c_f, c_f], c_int),
     "cbx_wave_format_f32": ([c_f, c_f, c_f, c_int, c_int, c_int, c_f, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_loudness_f32": ([c_f, c_f, c_f, c_int, c_f, c_int, c_f, ctypes.c_double, c_f, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_loudness_push_f32": ([c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_f, ctypes.c_double, c_f, c_long, c_f, c_f, c_f, c_f, c_f, c_long, c_f], c_int),

@@ -721,12 +721,42 @@ class _TTS(_Finish):
         """_words_of's place for a waveform returned whole: through the format's rate (ops.formatted_len, as segments go), clipped to its n_out samples"""
         return lambda s: min(n_out, s if fmt is None else ops.formatted_len(s, fmt["sample_rate"]))
 
+    # ------------------------------------------------------------------------------------------------------------ the alignment guard
+    last_guard = None  # per request of the last guarded call, in the caller's order: T3Engine.collect's report
+
+    def _guard_kw(self, guard):
+        """guard= of generate / generate_batch / generate_long / generate_long_stream -> {} (None / False: the call without the argument) or dict(guard=the
+        engine's dict): True is T3Engine.GUARD_DEFAULTS with this model's align_heads, a dict overrides single keys; an unknown key is a ValueError.  The values
+        are checked by the engine, before anything is launched."""
+        if guard is None or guard is False:
+            return {}
+        from .t3 import T3Engine
+        if guard is not True and not isinstance(guard, dict):
+            raise ValueError(f"guard: expected None, True or a dict of {sorted(T3Engine.GUARD_DEFAULTS)}, got {guard!r}")
+        over = {} if guard is True else dict(guard)
+        if set(over) - set(T3Engine.GUARD_DEFAULTS):
+            raise ValueError(f"guard: unknown key(s) {sorted(set(over) - set(T3Engine.GUARD_DEFAULTS))} (known: {sorted(T3Engine.GUARD_DEFAULTS)})")
+        g = dict(T3Engine.GUARD_DEFAULTS, heads=self.align_heads, **over) if "heads" not in over else dict(T3Engine.GUARD_DEFAULTS, **over)
+        check = getattr(getattr(self.engine, "t3", None), "check_guard", None)
+        return dict(guard=g if check is None else check(g))
+
+    def _take_guard(self, reports, who):
+        """model.last_guard = the reports in the caller's order; one UserWarning names the requests that did not end by a sampled end-of-speech token"""
+        self.last_guard = reports
+        odd = [(i, r["reason"]) for i, r in enumerate(reports) if r is not None and r["reason"] != "eos"]
+        if odd:
+            import warnings
+            warnings.warn(f"{who}: the alignment guard ended request(s) " + ", ".join(f"{i} by {why!r}" for i, why in odd) + " (tail / repeat / run: end of speech "
+                          "was forced; length: the speech-token budget was spent)", UserWarning, stacklevel=3)
+
     # ------------------------------------------------------------------------------------------------------------ one utterance
     def _generate(self, text_ids, fmt=None, word_mode=None, **kw):
         """generate() behind its argument handling: tokenizer ids -> the finished waveform (word_mode: and its words).  kw: sampling arguments, and _synth_kw's if
-        they are to differ."""
+        they are to differ; guard (_guard_kw's dict) among them: last_guard is then the request's report."""
         tokens = self._engine_tokens(text_ids)
         res = self.engine.synthesize([tokens], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw), **self._engine_format(fmt), **self._word_kw(word_mode))
+        if kw.get("guard") is not None:
+            self._take_guard(list(self.engine.last_guard), "generate")
         wav = self._finish(res[0][0], fmt)
         return wav if word_mode is None else (wav, self._words_of(word_mode, tokens, res[2][0], self._place(wav.shape[-1], fmt)))
 
@@ -754,7 +784,7 @@ class _TTS(_Finish):
             yield self.engine.synthesize(*args, **synth_kw, **job)
 
     def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, loudness=None, pauses=None, pitch=None, word_times=False,
-                        **analyse_kw):
+                        guard=None, **analyse_kw):
         """generate_batch behind its signature: validation of every per-request argument (seeds and speed first), then the voices, then tokenisation, then the
         device work.  samp: the sampling arguments the engine takes; unsampled: those it does not -- exaggeration, which picks the voice's cond dict, and what the
         backbone ignores."""
@@ -762,6 +792,7 @@ class _TTS(_Finish):
         B = len(texts)
         assert B >= 1, "empty batch"
         word_mode = self._word_mode(word_times, None if pauses is None else pauses[0])
+        guard_kw = self._guard_kw(guard)
         seeds = _batch_seeds(seeds, B, generator)
         speed = ops.check_speed(speed, B)
         loud = ops.check_loudness(loudness, B)
@@ -774,19 +805,20 @@ class _TTS(_Finish):
         self._warn_ignored(*(v for vals in unsampled.values() for v in vals))
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, unsampled["exaggeration"], **analyse_kw)
         tokens = [self._engine_tokens(self._text_ids(t, lid)) for t, lid in zip(texts, langs)]
-        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt, loud, pz, pit, word_mode)
+        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt, loud, pz, pit, word_mode, guard_kw)
 
     def _languages(self, language_ids, B):
         return [None] * B
 
-    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None, loud=None, pz=None, pit=None, word_mode=None):
+    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None, loud=None, pz=None, pit=None, word_mode=None, guard_kw=None):
         """Sub-batches of at most max_batch requests in order of text length (_run_jobs: one runs the serial schedule, several the throughput schedule).  Returns the
         finished waveforms in the caller's order.  seeds (B ints or None) travel with their requests: a request's draws do not depend on the sub-batch or the row
         it lands in.  speed (B floats or None) travels the same way.  fmt (one format for the call, or None): every job carries it as `format` unless a
         watermarker is loaded (_engine_format).  loud (B LUFS targets / Nones, or None) travels with its requests like speed: a job carries `loudness` only when
         one of its requests has a target.  pz (_pauses' dict or None) the same: a job carries `pauses`, with its requests' keeps, only when one of them has one.  pit (B semitones or None) the same: a job
         carries `pitch` only when one of its requests is transposed.  word_mode (_word_mode's): every job carries `words`, the sub-batches then run the serial
-        schedule one after the other (_run_jobs), and the result is a list of (waveform, words)."""
+        schedule one after the other (_run_jobs), and the result is a list of (waveform, words).  guard_kw (_guard_kw's): every job carries `guard`, one setting
+        for the call; last_guard holds the reports in the caller's order."""
         dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
         plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
         jobs = []
@@ -808,13 +840,19 @@ class _TTS(_Finish):
                 job["pitch"] = _pick(pit, idx)
             job.update(self._engine_format(fmt))
             job.update(self._word_kw(word_mode))
+            job.update(guard_kw or {})
             jobs.append(job)
-        out = [None] * len(tokens)
+        out, reports = [None] * len(tokens), [None] * len(tokens)
         for idx, res in zip(plan, self._run_jobs(jobs, self._synth_kw(batch=True))):
+            if guard_kw:
+                for i, r in zip(idx, self.engine.last_guard):
+                    reports[i] = r
             for r, (i, w) in enumerate(zip(idx, res[0])):
                 out[i] = self._finish(w, fmt)
                 if word_mode is not None:
                     out[i] = (out[i], self._words_of(word_mode, tokens[i], res[2][r], self._place(out[i].shape[-1], fmt)))
+        if guard_kw:
+            self._take_guard(reports, "generate_batch")
         return out
 
     def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, fmt=None, loudness=None, ramp=None, **prepare_kw):
@@ -841,7 +879,7 @@ class _TTS(_Finish):
         plan = long_plan(chunks, max_batch, a) if ramp is None else long_stream_plan(chunks, max_batch, a, *ramp)
         t3, gen = self.conds.t3.as_dict(), self.conds.gen
         jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join", "pauses", "pitch") if k in p},
-                     **self._word_kw(a.get("words"))) for p in plan]
+                     **self._word_kw(a.get("words")), **(a.get("guard") or {})) for p in plan]
         return chunks, plan, jobs
 
     @staticmethod
@@ -876,6 +914,9 @@ class _TTS(_Finish):
             pieces.append(piece["wav"].detach().float().cpu())
             assert pieces[-1].numel() == piece["total"], "a joined piece and its layout record disagree"
             segs = self._long_segments(chunks, p, piece, st, base)
+            if a.get("guard"):  # the alignment guard's report of every chunk travels in its segment
+                for seg, r in zip(segs, self.engine.last_guard):
+                    seg["guard"] = r
             if a.get("words") is not None:  # a word of chunk r: its samples clipped to the kept part [src_start, src_stop), shifted to the segment's start
                 for r, seg in enumerate(segs):
                     place = lambda v, seg=seg: fl(seg["start"] + min(max(v, seg["src_start"]), seg["src_stop"]) - seg["src_start"])
@@ -883,6 +924,8 @@ class _TTS(_Finish):
             segments += segs
             base += piece["total"]
         self._warn_truncated("generate_long", [s["truncated"] for s in segments], a["max_chars"])
+        if a.get("guard"):
+            self._take_guard([s["guard"] for s in segments], "generate_long")
         wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=loud)
         if fmt is not None:
             for seg in segments:
@@ -899,12 +942,16 @@ class _TTS(_Finish):
         dev, scope = self._device_scope()
         run = self._run_jobs(jobs, self._synth_kw())
         meter = conv = None
-        base, truncated = 0, []
+        base, truncated, reports = 0, [], []
         try:
             for g, (p, (piece, st)) in enumerate(zip(plan, run)):
                 wav = piece["wav"].detach().float().cpu()
                 assert wav.numel() == piece["total"], "a joined piece and its layout record disagree"
                 segments = self._long_segments(chunks, p, piece, st, base)
+                if a.get("guard"):  # the reports so far, in text order; a piece's own travel in its segments
+                    for seg, r in zip(segments, self.engine.last_guard):
+                        seg["guard"] = r
+                    reports += [s["guard"] for s in segments]
                 base += piece["total"]
                 truncated += [s["truncated"] for s in segments]
                 on_dev = None  # the piece on the device, while the host copy `wav` is the same samples
@@ -929,6 +976,8 @@ class _TTS(_Finish):
         finally:
             run.close()
             self._warn_truncated("generate_long_stream", truncated, a["max_chars"])
+            if a.get("guard"):
+                self._take_guard(reports, "generate_long_stream")
 
 
 class _LlamaTTS(_TTS):
@@ -993,7 +1042,7 @@ class ChatterboxTTS(_LlamaTTS):
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                  cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                 word_times=False):
+                 word_times=False, guard=None):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
         alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
         speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
@@ -1032,18 +1081,31 @@ class ChatterboxTTS(_LlamaTTS):
         checked it on trained weights here.  Not together with max_pause (ValueError).  generate_batch: one flag for the call, a list of (wav, words); the
         sub-batches of such a call run one after the other, without the T3 / flow overlap.  generate_long: with return_segments=True every segment gains `words`
         in samples of the joined result, clipped to the segment.  generate_stream, generate_long_stream, ChatterboxTurboTTS and ChatterboxVC do not take it.
-        This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db`, `pitch` and `word_times` for every method of every
-        class of this module; the others say only what differs."""
+        guard (None; True, or a dict that overrides single keys of T3Engine.GUARD_DEFAULTS -- heads, back, ahead, end_tokens, tail, repeat, repeat_skip,
+        token_run, hold_eos, min_text; an unknown key is a ValueError): the alignment guard, a bound on how the request ENDS.  T3 sometimes never samples its
+        end-of-speech token -- it trails off into noise, repeats a phrase, sits on one token -- or samples it in the middle of the sentence.  With the guard, every
+        token step also reads, on the device, how much attention a few heads (`heads`; default align_heads / T3Engine.ALIGN_HEADS) put on each text token,
+        follows the text position, bans end-of-speech until the position has reached the last end_tokens text tokens (hold_eos, for texts of min_text tokens or
+        more), and forces it once the attention has stayed on the last tokens (`tail`), has gone back to earlier text (`repeat`) or the last token_run sampled
+        tokens are one token (`run`) (include/cbx.h cbx_guard_update_f32).  last_guard is then the list of reports, dict(reason: "eos",
+        "tail", "repeat", "run" or "length"; tokens, fired_at, completed_at, position, text_tokens) per request in the caller's order, and one UserWarning names
+        the requests that did not end by a sampled end-of-speech token.  The defaults follow what is publicly described of the reference project's analyser and are
+        UNMEASURED here: nobody has run them on trained weights with these kernels, and with the wrong heads hold_eos can itself keep a request running to the
+        token budget.  Opt-in; None is the call without the argument, launch for launch.  generate_batch: one setting for the call.  generate_long /
+        generate_long_stream: every chunk is guarded, with return_segments its report travels in its segment as `guard`.  generate_stream, ChatterboxTurboTTS and
+        ChatterboxVC do not take the argument: round streams and the GPT-2 backbone are not built.
+        This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db`, `pitch`, `word_times` and `guard` for every method
+        of every class of this module; the others say only what differs."""
         fmt = ops.check_format(sample_rate, encoding)
         word_mode = self._word_mode(word_times, max_pause)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch), **self._guard_kw(guard))
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text), fmt, word_mode, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
                               top_p=top_p, **seed_kw)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                       max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                      word_times=False):
+                      word_times=False, guard=None):
         """generate() for a text of ANY length: the reference stops at 1000 speech tokens (40 s) and cuts a longer text off.  The text is split into chunks of at
         most max_chars characters at paragraph, sentence and clause boundaries (text.split_text), the chunks are synthesised in text order as device batches
         (one: synthesize; several: the throughput schedule where the engine has it), and each batch's waveforms are trimmed of their leading / trailing silence and
@@ -1066,13 +1128,14 @@ class ChatterboxTTS(_LlamaTTS):
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
-        a["words"] = self._long_word_mode(word_times, max_pause, return_segments)
+        a["words"], a["guard"] = self._long_word_mode(word_times, max_pause, return_segments), self._guard_kw(guard)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                              max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
-                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, first_batch=1, batch_growth=2.0):
+                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None, first_batch=1,
+                             batch_growth=2.0):
         """generate_long() in pieces: a generator of (1, n) CPU tensors, one per device batch as it leaves the device (empty pieces left out); concatenated along
         dim 1 they are the long-form result.  Every argument of generate_long with its meaning and default, plus the ramp of the device batches:
         first_batch (None, or an int >= 1) and batch_growth (a finite number >= 1): the batches hold s_0 = min(first_batch, step) chunks, then
@@ -1095,14 +1158,14 @@ class ChatterboxTTS(_LlamaTTS):
         _no_word_times("generate_long_stream", word_times)
         fmt = ops.check_format(sample_rate, encoding)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
+        a["pauses"], a["pitch"], a["guard"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch), self._guard_kw(guard)
         ramp = _long_stream_args(first_batch, batch_growth)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
                        min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                       word_times=False):
+                       word_times=False, guard=None):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
         request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
         neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
@@ -1118,7 +1181,7 @@ class ChatterboxTTS(_LlamaTTS):
         This is the contract of generate_batch of every class of this module; the others say only what differs."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, word_times)
+                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, word_times, guard)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                         cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, sample_rate=None, encoding=None, speed=1.0):
@@ -1181,12 +1244,12 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                  repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                 word_times=False):
+                 word_times=False, guard=None):
         """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
-        token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness, word_times: as there."""
+        token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness, word_times, guard: as there."""
         fmt = ops.check_format(sample_rate, encoding)
         word_mode = self._word_mode(word_times, max_pause)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
+        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch), **self._guard_kw(guard))
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text, lid), fmt, word_mode, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
@@ -1194,38 +1257,39 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False):
+                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False,
+                      guard=None):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         fmt = ops.check_format(sample_rate, encoding)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
         a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
-        a["words"] = self._long_word_mode(word_times, max_pause, return_segments)
+        a["words"], a["guard"] = self._long_word_mode(word_times, max_pause, return_segments), self._guard_kw(guard)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
 
     def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                              top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                             return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, first_batch=1,
-                             batch_growth=2.0):
+                             return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None,
+                             first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         _no_word_times("generate_long_stream", word_times)
         fmt = ops.check_format(sample_rate, encoding)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
-        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
+        a["pauses"], a["pitch"], a["guard"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch), self._guard_kw(guard)
         ramp = _long_stream_args(first_batch, batch_growth)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                       word_times=False):
+                       word_times=False, guard=None):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
         speed, before the sampling arguments)."""
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, word_times)
+                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, word_times, guard)
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,

@@ -36,6 +36,8 @@ class DecodeRuntime:
     weight_dtype = "fp32"
     # what one token step writes: saved around a capture, whose warm-up run must not leak into the real sequence
     _STEP_STATE = ("seen", "step", "done", "n_generated", "out_tokens", "next_ids", "next_pos_ids", "positions", "ctx_lens", "logits")
+    # ... and what the step of a GUARDED request writes besides (T3Engine.generate(guard=)): the guard's buffers in st["guard"], and the sampler's parameters
+    _GUARD_STATE = ("p", "mass", "state", "sums", "trace")
 
     # ------------------------------------------------------------------ packed decode images of the current tune
     def _half_tiles(self):
@@ -111,18 +113,33 @@ class DecodeRuntime:
         return bool(self.c_loop and self._use_c_step(st) and self.dev.type == "cuda")
 
     # ------------------------------------------------------------------ the step captured by torch
+    @staticmethod
+    def _graph_slot(st):
+        """(dict, key) under which the torch-captured graph of the state's CURRENT step form lives: st["graph"] for the plain step; a guarded request
+        (st["guard_on"], T3Engine.generate(guard=)) replays a step with the guard's launches in it, kept beside the plain one in st["guard_graphs"], one per set of
+        heads -- neither evicts the other."""
+        g = st.get("guard_on")
+        return (st, "graph") if g is None else (st.setdefault("guard_graphs", {}), g["heads"])
+
+    def _step_graph(self, st):
+        d, k = self._graph_slot(st)
+        return d.get(k)
+
     @torch.inference_mode()
     def _capture(self, st, thread_local=None):
-        """torch-captured graph of one token step, as st["graph"]."""
+        """torch-captured graph of one token step, as st["graph"] (a guarded state: _graph_slot)."""
         thread_local = self._CAPTURE_THREAD_LOCAL if thread_local is None else thread_local
         torch.cuda.synchronize()
-        saved = {k: st[k].clone() for k in self._STEP_STATE}
+        saved = [(st[k], st[k].clone()) for k in self._STEP_STATE]
+        if st.get("guard_on") is not None:  # the guarded step also writes the guard's buffers and the ban column of the sampler's parameters
+            saved += [(st["guard"][k], st["guard"][k].clone()) for k in self._GUARD_STATE] + [(st["samp_dev"], st["samp_dev"].clone())]
         gr = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gr, capture_error_mode="thread_local" if thread_local else "global"):
             self._decode_step(st)
-        for k, v in saved.items():
-            st[k].copy_(v)
-        st["graph"] = gr
+        for t, v in saved:
+            t.copy_(v)
+        d, k = self._graph_slot(st)
+        d[k] = gr
 
     # ------------------------------------------------------------------ one request
     @staticmethod
@@ -157,7 +174,7 @@ class DecodeRuntime:
         if self._ONE_SHOT_C_LOOP and self._c_loop_serves(st):
             self._c_loop(st)
             return True
-        if st["graph"] is None:
+        if self._step_graph(st) is None:
             self._capture(st)
         return False
 
@@ -173,10 +190,11 @@ class DecodeRuntime:
         ran = 0
         if c_loop and n_steps > 0:
             ran = self._run_c_loop(st, n_steps, poll_every)
+        graph = self._step_graph(st) if use_graph else None
         for i in range(1, 1 if c_loop else n_steps + 1):
             ran += 1
-            if use_graph and st["graph"] is not None:
-                st["graph"].replay()
+            if graph is not None:
+                graph.replay()
             elif step_logits is not None:
                 self._forward(st)
                 step_logits.append(st["logits"].clone())
@@ -196,6 +214,9 @@ class DecodeRuntime:
         """Enqueue up to `n_steps` further token steps of an async generate() (finished utterances are no-ops inside the sampler).  Returns the number of
         steps enqueued.  No host synchronisation (the C loop runs with poll_every = 0)."""
         st = handle["st"]
+        if handle.get("guard") is not None:
+            raise ValueError("advance() on a guarded handle: the guard covers one-shot requests (generate(guard=) to the end, or async_mode + collect); round "
+                             "streams are not built")
         n = max(0, min(int(n_steps), handle["max_new_tokens"] - handle["next_i"]))
         c_loop = self._c_loop_serves(st) and not (self._ADVANCE_KEEPS_GRAPH and st["graph"] is not None)
         if n and not c_loop and self._ADVANCE_CAPTURES and self.dev.type == "cuda" and st["graph"] is None:

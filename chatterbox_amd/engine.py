@@ -78,7 +78,7 @@ def _checked_job(job):
     n = len(job["text_tokens"])
     if job.get("words") is not None:
         raise ValueError(WORDS_PIPELINED)
-    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness", "pauses", "pitch", "words") or v is not None}
+    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness", "pauses", "pitch", "words", "guard") or v is not None}
     if "pitch" in job:
         job["pitch"] = ops.check_pitch(job["pitch"], n)
         if job["pitch"] is None:
@@ -112,6 +112,9 @@ WORDS_PIPELINED = ("words: the alignment pass runs between T3 and the vocoder of
                    "(synthesize_pipelined keeps two T3 states in flight; the pass inside that overlap is not built)")
 WORDS_PAUSES = ("max_pause (pauses) together with word_times (words): the cut map of the pause step is data on the device; mapping word boundaries "
                 "through it is not built")
+
+
+GUARD_BANS = "guard together with ban_eos / ban_from: both ban the end-of-speech token the guard must be able to force"
 
 
 def check_words(words):
@@ -351,6 +354,8 @@ class S3GenEngine:
 
 
 class ChatterboxEngine(S3GenEngine):
+    last_guard = None  # the alignment guard's per-utterance report of the last guarded synthesize() call / synthesize_pipelined job yielded
+
     def __init__(self, t3_sd, s3gen_sd, device="cuda", n_t3_layers=None, meanflow=False, t3_weights=None):
         self.dev = torch.device(device)
         self.t3_weights = t3_weights  # None / "fp32" (parity path) or "bf16" (opt-in: decode weight images rounded to bf16)
@@ -381,7 +386,7 @@ class ChatterboxEngine(S3GenEngine):
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
                    noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None,
-                   words=None):
+                   words=None, guard=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
@@ -400,7 +405,13 @@ class ChatterboxEngine(S3GenEngine):
         from, and the call returns (wavs, speech_tokens, alignment): per utterance dict(frames = [(f0, f1) per text token]: the token is spoken over the valid
         speech tokens [f0, f1) (valid_frame_counts: the tokens the flow receives; 960 samples each at speed 1), n_frames, speed, pitch -- what frame_sample needs
         to turn a frame into a sample of wavs[b]).  Not together with pauses; at most T3Engine.MAX_BATCH utterances.  Without it the call is launch for launch
-        the one it always was."""
+        the one it always was.
+        guard: None, or T3Engine.generate(guard=)'s dict -- the alignment guard inside the token step (it holds EOS back until the text has been spoken and
+        forces it when the alignment says the utterance is over); last_guard is then the per-utterance report (T3Engine.collect).  Not with ban_eos / ban_from."""
+        if guard is not None:
+            guard = self.t3.check_guard(guard)
+            if ban_eos or ban_from > 0:
+                raise ValueError(GUARD_BANS)
         words = check_words(words)
         if words is not None:
             if pauses is not None and ops.check_pauses(pauses, len(text_tokens)) is not None:
@@ -422,7 +433,8 @@ class ChatterboxEngine(S3GenEngine):
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
                    min_p=min_p, repetition_penalty=repetition_penalty, cfg_weight=cfg_weight, uniforms=uniforms,
-                   ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
+                   ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds, **({} if guard is None else dict(guard=guard)))
+        self.last_guard = None if guard is None else self.t3.last_guard
         torch.cuda.synchronize()
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         st = _valid_tokens(toks)
@@ -461,6 +473,8 @@ class ChatterboxEngine(S3GenEngine):
         or `format` (vocode(format=)'s dict: the job's audio is converted on the device ahead of its copies, which then carry the encoded samples),
         or `loudness` (vocode(loudness=): a number or one number / None per utterance; the meter and the gain run behind the vocoder on its stream; not with a join),
         or `pitch` (vocode(pitch=): a number or one number / None per utterance, semitones; the launch runs behind the vocoder on its stream),
+        or `guard` (T3Engine.generate(guard=)'s dict: the job's T3 runs with the alignment guard inside its token step, in whichever of the two T3 states it
+        lands; engine.last_guard is the job's report while the job is the one just yielded; not with ban_eos / ban_from),
         or `pauses` (vocode(pauses=)'s dict / list: the squeeze runs behind the vocoder on its stream; its record of the new lengths travels to the host as one more
         small pinned copy behind the same event, and the waveforms are cut after it: no host synchronisation is added),
         or `join` (vocode(join=)'s dict: the job's utterances are consecutive chunks of one text; `wavs` is then synthesize(join=)'s piece dict with `wav` on the host.
@@ -478,11 +492,16 @@ class ChatterboxEngine(S3GenEngine):
             calls of the C stage seams release the GIL)."""
         import threading
         jobs = [_checked_job(job) for job in jobs]
+        for job in jobs:  # `guard` (T3Engine.generate(guard=)'s dict): the job's T3 runs guarded, in either slot; engine.last_guard is its report when the job is yielded
+            if "guard" in job:
+                job["guard"] = self.t3.check_guard(job["guard"])
+                if kw.get("ban_eos") or kw.get("ban_from", 0) > 0:
+                    raise ValueError(GUARD_BANS)
         torch.cuda.set_device(self.dev)  # a generator cannot hold a device guard across yields: pin the device for the caller
         self._pipeline_streams(stream_priorities)
         t3_kw = {k: kw[k] for k in ("max_new_tokens", "temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight", "ban_eos",
                                     "ban_from") if k in kw}
-        job_kw = lambda job: dict(t3_kw, **{k: job[k] for k in ("temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight") if k in job})
+        job_kw = lambda job: dict(t3_kw, **{k: job[k] for k in ("temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight", "guard") if k in job})
         self.co_resident(bool(co_resident))
         # ... and the flow + vocoder stream carries the co-resident ATTRIBUTE: its LayerNorm / split-GEMM launches (encoder, vocoder) keep to one or two
         # workgroups per CU as well (cbx_set_stream_coresident; no effect on results)
@@ -539,15 +558,16 @@ class ChatterboxEngine(S3GenEngine):
                         if "error" in box:
                             raise box["error"]
                     if pending is not None:
-                        job, st, t0, raw = pending
+                        job, st, t0, raw, rep = pending
                         with torch.cuda.stream(self._s_voc):  # (the copies block: this returns when the batch's audio is on the host)
                             host = _range_checked(self, lambda: to_host(job, vocode_job(job, st), pinned=False))
+                        self.last_guard = rep
                         yield result_of(job, host, raw), st, time.perf_counter() - t0
                     pending = None
                     if "handle" in box:
                         with torch.cuda.stream(self._s_t3):
                             raw = self.t3.collect(box["handle"])
-                        pending = (jobs[k], _valid_tokens(raw), t_start, raw)
+                        pending = (jobs[k], _valid_tokens(raw), t_start, raw, self.t3.last_guard if "guard" in jobs[k] else None)
             finally:
                 torch.cuda.synchronize()
                 self.co_resident(False)
@@ -593,7 +613,8 @@ class ChatterboxEngine(S3GenEngine):
                 ev.record()
             return host, ev
 
-        def finish(job, st, t0, host, ev, which, raw):
+        def finish(job, st, t0, host, ev, which, raw, rep):
+            self.last_guard = rep  # (the guard's report of THIS job, taken when its tokens were collected)
             ev.synchronize()
             if 16 in (self.flow.precision, self.hift.precision) and ops.range_flag_tripped(self.dev, which):
                 with _repeat_at_bf16x6(self, " of this batch"), torch.cuda.stream(self._s_voc):
@@ -611,10 +632,11 @@ class ChatterboxEngine(S3GenEngine):
                 with torch.cuda.stream(self._s_voc):
                     self._s_voc.wait_event(ev)
                     toks = self.t3.collect(h)  # blocks this thread until T3(k) is done; T3(k + 1) is already enqueued behind it
+                    rep = self.t3.last_guard if "guard" in job else None
                 slot_free[k % n_slots].release()
                 st = _valid_tokens(toks)
                 host, evv = start_voc(job, st, k % 2)
-                inflight.append((job, st, t0, host, evv, k % 2, toks))
+                inflight.append((job, st, t0, host, evv, k % 2, toks, rep))
                 yield finish(*inflight.popleft())
             while inflight:
                 yield finish(*inflight.popleft())

@@ -554,6 +554,49 @@ def align_path(score, n, m):
     return spans, frame_tok
 
 
+def guard_text_mass(qkv, positions, cos_t, sin_t, kc, heads, done, t_len, t0, scale, p, qkv_ssq=None, rms_dim=0, rms_eps=1e-5, max_ctx=None):
+    """cbx_guard_text_mass_f32 on the current stream, right after decode_attn_rope of the same layer and with its operands: p[s, b, t] = the attention probability
+    the CURRENT query of conditional row b (head heads[s] of this layer; ints, 1 .. 16 of them) puts on key t0 + t, t < t_len[b], the softmax over every key
+    j <= positions[b].  qkv (rows, 3*H*64) or (nparts, rows, 3*H*64) with qkv_ssq (nparts, 16) and rms_dim; kc (rows, H, max, 64) one layer of the cache;
+    positions (rows,), done (B,), t_len (B,) int32 on the device; p (>= len(heads), B, t_cap) fp32 with unit inner stride (a view at the layer's first slot).
+    Rows that are done, and columns beyond t_len, keep what they hold.  No host array changes from step to step: the launch can be captured."""
+    H, B = kc.shape[1], p.shape[1]
+    heads = [int(h) for h in heads]
+    nparts = qkv.shape[0] if qkv.dim() == 3 else 0
+    assert kc.dim() == 4 and kc.shape[3] == 64 and kc.stride(3) == 1 and kc.stride(2) == 64 and kc.shape[0] >= B and qkv.shape[-2] >= B and qkv.stride(-1) == 1
+    assert p.dim() == 3 and p.stride(2) == 1 and p.shape[0] >= len(heads) and done.numel() >= B and t_len.numel() >= B and positions.numel() >= B
+    assert all(t.dtype == torch.int32 for t in (positions, done, t_len)), "guard_text_mass: positions, done and t_len are int32"
+    assert nparts == 0 or (qkv_ssq is not None and tuple(qkv_ssq.shape) == (nparts, 16) and rms_dim > 0)
+    hs = (ctypes.c_int * len(heads))(*heads)
+    args = (_p(_f32(qkv, "qkv")), qkv.stride(-2), nparts, qkv.stride(0) if nparts else 0, _p(qkv_ssq), int(rms_dim), float(rms_eps), _p(positions), _p(cos_t), _p(sin_t),
+            _p(_f32(kc, "kc")), kc.stride(0), kc.stride(1), int(kc.shape[2] if max_ctx is None else max_ctx), ctypes.addressof(hs), len(heads), H, B, _p(done), _p(t_len),
+            int(t0), p.shape[2], float(scale), _p(_f32(p, "p")), p.stride(0), p.stride(1))
+    _timed("guard_text_mass", 2.0 * len(heads) * B * 64 * kc.shape[2], 4.0 * len(heads) * B * 64 * kc.shape[2],
+           lambda: check(lib.cbx_guard_text_mass_f32(*args, _stream()), "cbx_guard_text_mass_f32"))
+    return p
+
+
+GUARD_NTHR = 8  # thresholds per utterance of cbx_guard_update_f32: back, ahead, end_tokens, tail, repeat, repeat_skip, token_run, hold_min
+
+
+def guard_update(p, t_len, step, done, thresholds, out_tokens, mass, state, sums, trace, logits, V, eos, dev_params, n_sel=None):
+    """cbx_guard_update_f32 on the current stream, between the head GEMV and t3_sample (include/cbx.h states the eight steps).  p (n_sel, B, t_cap) the slots
+    guard_text_mass filled in this step; thresholds (B, 8) fp32; out_tokens (B, max_steps) int64; mass (B, max_steps, ld) the history; state (B, 8) int32, sums
+    (B, 4) fp32, trace (B, max_steps) int32; logits (>= 2 B, >= V); dev_params (B, 8) the sampler's per-utterance parameters: column 6 is written.  All on the device."""
+    n_sel = p.shape[0] if n_sel is None else int(n_sel)
+    B, max_steps = out_tokens.shape
+    assert p.dim() == 3 and p.stride(2) == 1 and p.shape[0] >= n_sel and p.shape[1] == B and mass.shape[:2] == (B, max_steps) and mass.stride(2) == 1
+    assert out_tokens.dtype == torch.int64 and out_tokens.is_contiguous() and trace.dtype == torch.int32 and trace.shape == (B, max_steps) and trace.is_contiguous()
+    assert state.dtype == torch.int32 and state.shape == (B, 8) and state.is_contiguous() and sums.shape == (B, 4) and sums.is_contiguous()
+    assert thresholds.shape == (B, GUARD_NTHR) and thresholds.is_contiguous() and dev_params.shape == (B, 8) and dev_params.is_contiguous()
+    assert all(t.dtype == torch.int32 and t.numel() >= B for t in (t_len, step, done)) and logits.shape[0] >= 2 * B and logits.stride(1) == 1 and logits.shape[1] >= V
+    assert mass.stride(1) <= p.shape[2], "guard_update: a text the history row holds must fit a slot of p (the kernel follows t_len <= the history's row stride)"
+    args = (_p(_f32(p, "p")), p.stride(0), p.stride(1), n_sel, _p(t_len), _p(step), _p(done), _p(_f32(thresholds, "thresholds")), _p(out_tokens), max_steps,
+            _p(_f32(mass, "mass")), mass.stride(0), mass.stride(1), _p(state), _p(_f32(sums, "sums")), _p(trace), _p(_f32(logits, "logits")), logits.stride(0), int(V), B,
+            int(eos), _p(_f32(dev_params, "dev_params")))
+    check(lib.cbx_guard_update_f32(*args, _stream()), "cbx_guard_update_f32")
+
+
 def flash_relpos(q4, pp, out, scale, key_lens=None):
     """Conformer rel-pos attention without materialised scores.  q4 (Z,T,4,H,64): the fused [q + u | q + v | k | v] projection (any batch /
     token strides, unit inner strides); pp (2T-1, H*64) = linear_pos(pos_emb); out (Z,T,H,64) view."""

@@ -332,7 +332,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
             # the captured graph / C step descriptor of a state are kept PER GEOMETRY (alternating synthesize() and synthesize_pipelined()
             # re-captured the decode graph on every switch); they reference the state's own buffers and the weight images, which both outlive the switch
             cache = st.setdefault("geom_cache", {})
-            cache[old_key] = {k: st.pop(k) for k in ("graph", "cstep", "cloop") if k in st}
+            cache[old_key] = {k: st.pop(k) for k in ("graph", "cstep", "cloop", "guard_graphs") if k in st}
             st["graph"] = None
             st.update(cache.pop(new_key, {}))
             self._sync_geom(st)
@@ -623,6 +623,8 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
             ops.add_rmsnorm(x, part, lw["ln1"], h)
             ops.gemv(h, lw["wqkv"], qkv, nw=tn["qkv_nw"])
             ops.decode_attn_rope(qkv, st["positions"], self.cos, self.sin, st["kc"][i], st["vc"][i], att, 0.125, geom=st["da"])
+            if st.get("guard_on") is not None:
+                self._guard_mass(st, i, qkv)
             ops.gemv(att, lw["wo"], po, ksplit=tn["o_ks"], nw=4)
             ops.add_rmsnorm(x, po, lw["ln2"], h)
             ops.gemv(h, lw["wgu"], g, swiglu=True, nw=tn["gu_nw"])
@@ -659,6 +661,8 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
                                      qkv_ssq=sq, rms_dim=self.D, rms_eps=1e-5)
             else:
                 ops.decode_attn_rope(qkv, st["positions"], self.cos, self.sin, st["kc"][i], st["vc"][i], att, 0.125, out_packed=True, geom=st["da"])
+            if st.get("guard_on") is not None:  # the alignment guard reads the same q and this layer's K, the new position included
+                self._guard_mass(st, i, qp if qks > 1 else qkv, sq if qks > 1 else None)
             ops.gemv(att, self._image(lw, "wo", odtc), cur, N=self.D, K=self.D, nw=tn["o_nw2"], res=cur, out_packed=True, half_tile=ot, **pk)
             ops.gemv(cur, lw["wgu_pk"], g, N=self.F, K=self.D, swiglu=True, nw=tn["gu_nw"], norm_w=lw["ln2"], out_packed=True, **pk)
             if dks > 1:
@@ -672,8 +676,11 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
 
     def _forward(self, st):
         if self.decode_mode == "v2" and st["rows"] <= 16:  # (17 .. 64 rows on this 5-launch layer: measured -4.5 % at 32 rows, +2.4 % at 64 -- profiles/r06_wide_rows_decode_ab.jsonl -- not adopted)
-            return self._forward_decode_v2(st)
-        self._forward_decode(st)
+            self._forward_decode_v2(st)
+        else:
+            self._forward_decode(st)
+        if st.get("guard_on") is not None:  # between the head GEMV and the sampler
+            self._guard_update(st)
 
     def _decode_step(self, st):
         if self._use_c_step(st):
@@ -682,7 +689,8 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         self._sample(st)
 
     def _use_c_step(self, st):
-        return self.c_step and self.decode_mode == "v2" and st["rows"] <= 16 and self.tune["d_ks2"] in (1, 2, 4)
+        # (a guarded request takes the Python-sequenced step: the C step has no descriptor for the guard's launches)
+        return self.c_step and self.decode_mode == "v2" and st["rows"] <= 16 and self.tune["d_ks2"] in (1, 2, 4) and st.get("guard_on") is None
 
     def _c_step_desc(self, st):
         """Build (once per state and geometry) the cbx_t3_step_t of this state: st["cstep"] = (descriptor, layers, sampler).  One call of it enqueues the
@@ -726,6 +734,8 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
     def _get_state(self, B, max_ctx, max_steps, slot=0):
         key = (B, max_ctx, max_steps, slot)
         if key in self._state:
+            # whoever takes the state starts unguarded: generate() sets the flag for ITS request right after; measure_decode / probe_decode never do
+            self._state[key]["guard_on"] = None
             return self._state[key]
         for k in [k for k in self._state if k[3] == slot]:  # one live configuration per slot (the KV cache dominates memory)
             del self._state[k]
@@ -761,7 +771,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
     @torch.inference_mode()
     def generate(self, conds, text_tokens, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                  repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16,
-                 return_prefill_logits=False, debug_logits=False, async_mode=False, slot=0, run_steps=None, generator=None, seeds=None):
+                 return_prefill_logits=False, debug_logits=False, async_mode=False, slot=0, run_steps=None, generator=None, seeds=None, guard=None):
         """conds: one T3 cond dict (shared voice) or a list of B; text_tokens: list of B 1-D LongTensors that already
         carry SOT/EOT (mtl_tts.py:319-322).  Returns a list of B 1-D LongTensors (EOS included if it was sampled).
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar, or a sequence of B (one row of cbx_sampler_t.dev_params per utterance).
@@ -770,9 +780,22 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         RNG_T3_UNIFORMS stream (ops.rng_fill), whatever its row and the batch around it; injected `uniforms` win; not together with a generator.
         `slot` selects an independent set of workspaces / KV cache / decode graph (pipelined serving keeps two alive).
         Chunked use (streaming synthesis): `async_mode=True, run_steps=k` samples only the first k tokens and returns a handle;
-        `advance(handle, n)` enqueues n more decode steps and `peek(handle)` fetches the tokens sampled so far."""
+        `advance(handle, n)` enqueues n more decode steps and `peek(handle)` fetches the tokens sampled so far.
+        guard: None, or a dict of check_guard's keys (missing ones take GUARD_DEFAULTS) -- the alignment guard: inside every token step, the attention mass
+        the named heads put on the text columns (ops.guard_text_mass, after decode_attn_rope of their layers) drives a state machine per utterance
+        (ops.guard_update, ahead of the sampler; include/cbx.h states it) that bans EOS until the text position has reached the last end_tokens text tokens and
+        forces EOS once the mass stays on the last tokens (`tail`), goes back to earlier text (`repeat`) or the last token_run sampled tokens are one token
+        (`run`).  Such a request takes the Python-sequenced step, replayed as a torch-captured graph kept beside the unguarded one.  Afterwards last_guard is the
+        per-utterance report and last_guard_device the device tensors (mass history (B, max_steps, ld), trace, state, sums).  Not with ban_eos / ban_from, which
+        ban the EOS the guard must be able to force; advance() refuses such a handle.  None: the call is launch for launch the one it always was."""
         dev, B = self.dev, len(text_tokens)
         assert B >= 1, "empty batch"
+        guard = self.check_guard(guard)
+        if guard is not None:
+            if ban_eos or ban_from > 0:
+                raise ValueError("guard together with ban_eos / ban_from: both ban the end-of-speech token the guard must be able to force")
+            if max(int(t.numel()) for t in text_tokens) > 1024:
+                raise ValueError(f"guard: {max(int(t.numel()) for t in text_tokens)} text tokens (at most 1024)")
         seeds = ops.request_seeds(seeds, B, generator)
         uniforms = self._uniform_rows(uniforms, B, max_new_tokens, f"max_new_tokens={max_new_tokens}")
         # {cfg_weight, temperature, min_p, top_p, rep_penalty, top_k, ban_token, ban_from} per utterance (cbx_sampler_t.dev_params); a wrong length raises here
@@ -781,15 +804,19 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
                                 ("ban_from", float(ban_from))))
         if B > self.MAX_BATCH:  # rows = 2B feeds the decode GEMV (M <= 64): larger batches run as consecutive sub-batches
             assert not (async_mode or debug_logits or return_prefill_logits), "sub-batching is only defined for the plain token path"
-            out = []
+            out, reports = [], []
             for lo in range(0, B, self.MAX_BATCH):
                 hi = min(B, lo + self.MAX_BATCH)
+                if lo and guard is not None:
+                    reports += self.last_guard
                 out += self.generate(conds if isinstance(conds, dict) else conds[lo:hi], text_tokens[lo:hi], max_new_tokens=max_new_tokens,
                                      temperature=_slice_param(temperature, lo, hi), top_p=_slice_param(top_p, lo, hi), min_p=_slice_param(min_p, lo, hi),
                                      repetition_penalty=_slice_param(repetition_penalty, lo, hi), cfg_weight=_slice_param(cfg_weight, lo, hi),
                                      uniforms=None if uniforms is None else uniforms[lo:hi], ban_eos=ban_eos,
                                      ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, slot=slot, generator=generator,
-                                     seeds=None if seeds is None else seeds[lo:hi])
+                                     seeds=None if seeds is None else seeds[lo:hi], guard=guard)
+            if guard is not None:
+                self.last_guard = reports + self.last_guard
             return out
         rows = 2 * B
         prec = self.tune.get("prefill_prec") or 0
@@ -806,6 +833,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         assert max_ctx <= self.max_pos, "context exceeds the RoPE table"
         st = self._get_state(B, max_ctx, max_new_tokens, slot)
         self._prepare_tune()
+        st["guard_on"] = None if guard is None else self._begin_guard(st, guard, tl, samp)  # (also: the first EOS ban into the request's sampler row)
         self._begin_request(st, samp, uniforms, max_new_tokens, generator, seeds)
 
         # ---- the missing prefixes of a mixed-voice batch: [conditioning] alone through the layers, once per distinct voice, into cache rows 0 .. n - 1
@@ -861,8 +889,8 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         # EOS is polled every `poll_every` steps unless the caller wants no synchronisation
         ran = self._replay(st, last - 1, 0 if (ban_eos or async_mode) else poll_every, c_loop, use_graph, step_logits, event_tag=(list(s0), rows))
         if async_mode:  # everything is enqueued on the current stream; no host synchronisation happened
-            return dict(st=st, B=B, next_i=1 + ran, max_new_tokens=max_new_tokens)
-        out = self.collect(dict(st=st, B=B))
+            return dict(st=st, B=B, next_i=1 + ran, max_new_tokens=max_new_tokens, guard=st["guard_on"])
+        out = self.collect(dict(st=st, B=B, guard=st["guard_on"]))
         if debug_logits:
             return out, torch.stack(step_logits)  # (steps, 2B, V)
         return (out, prefill_logits) if return_prefill_logits else out
@@ -887,6 +915,107 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         if any(len(v) > 16 for v in by_layer.values()):
             raise ValueError("align_heads: more than 16 heads of one layer")
         return heads
+
+    # ------------------------------------------------------------------ the alignment guard (generate(guard=); include/cbx.h)
+    # What is publicly described of the reference project's later analyser, with ALIGN_HEADS for the heads.  UNMEASURED here: nobody has run these numbers on
+    # trained weights with these kernels, and with the wrong heads hold_eos can itself keep a request running to max_new_tokens.  Opt-in.
+    GUARD_DEFAULTS = dict(heads=None, back=3, ahead=6, end_tokens=3, tail=5.0, repeat=5.0, repeat_skip=5, token_run=3, hold_eos=True, min_text=6)
+    last_guard = None         # per-utterance reports of the last guarded generate() / collect()
+    last_guard_device = None  # ... and the device tensors behind them
+
+    def check_guard(self, guard):
+        """generate's guard= argument -> None, or the complete dict: heads a tuple of (layer, head) pairs that exist (check_align_heads; None: ALIGN_HEADS), back,
+        ahead, repeat_skip, token_run, min_text ints >= 0 (token_run not 1: that would hold at every step), end_tokens in 1 .. 3, tail and repeat floats >= 0 (inf: the rule is off), hold_eos a bool.  ValueError
+        before anything is launched."""
+        if guard is None:
+            return None
+        if not isinstance(guard, dict) or set(guard) - set(self.GUARD_DEFAULTS):
+            raise ValueError(f"guard: expected None or a dict of {sorted(self.GUARD_DEFAULTS)}, got {guard!r}")
+        g = dict(self.GUARD_DEFAULTS, **guard)
+        g["heads"] = self.check_align_heads(g["heads"])
+        for k in ("back", "ahead", "end_tokens", "repeat_skip", "token_run", "min_text"):
+            if isinstance(g[k], bool) or not isinstance(g[k], (int, float)) or g[k] != g[k] or g[k] in (float("inf"), float("-inf")) or int(g[k]) != g[k] or g[k] < 0:
+                raise ValueError(f"guard: {k} = {g[k]!r} (an int >= 0)")
+            g[k] = int(g[k])
+        if g["token_run"] == 1:
+            raise ValueError("guard: token_run = 1 holds at every step (one token is always a run of one): 0 switches the rule off, 2 or more is a run")
+        if not 1 <= g["end_tokens"] <= 3:
+            raise ValueError(f"guard: end_tokens = {g['end_tokens']} outside 1 .. 3 (the device keeps three tail sums)")
+        for k in ("tail", "repeat"):
+            g[k] = float(g[k])
+            if not g[k] >= 0.0:
+                raise ValueError(f"guard: a negative threshold ({k} = {g[k]!r})")
+        g["hold_eos"] = bool(g["hold_eos"])
+        return g
+
+    def _begin_guard(self, st, guard, tl, samp):
+        """The guard's side of _begin_request: buffers (state, scratch, history, trace -- allocated with the state when a guarded request first needs them),
+        thresholds and text lengths into device memory, state zeroed; samp (the host image of the sampler's rows) gets the ban frame 0 is sampled under.
+        Returns st["guard_on"]: the settings plus the launch plan -- runs of consecutive heads of one layer, in list order, each with its first scratch slot."""
+        B, dev, heads = st["B"], self.dev, guard["heads"]
+        buf = st.get("guard")
+        if buf is None or buf["p"].shape[0] < len(heads):
+            # a text of this state has at most max_ctx - max_steps - 36 tokens (generate: max_ctx covers 34 + text + 2 BOS + max_new_tokens)
+            ld = max(4, min(1024, (st["max_ctx"] - st["max_steps"] - 36 + 3) // 4 * 4))
+            i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+            buf = st["guard"] = dict(p=torch.zeros(max(16, len(heads)), B, ld, device=dev), mass=torch.zeros(B, st["max_steps"], ld, device=dev), state=i32(B, 8),
+                                     sums=torch.zeros(B, 4, device=dev), trace=i32(B, st["max_steps"]), thr=torch.zeros(B, ops.GUARD_NTHR, device=dev), t_len=i32(B))
+            st.pop("guard_graphs", None)  # (a captured guarded step holds the old buffers: also those parked with another geometry)
+            for parked in st.get("geom_cache", {}).values():
+                parked.pop("guard_graphs", None)
+        assert max(tl) <= buf["mass"].shape[2], "guard: the text does not fit the history of this state"
+        row = [guard["back"], guard["ahead"], guard["end_tokens"], guard["tail"], guard["repeat"], guard["repeat_skip"], guard["token_run"],
+               guard["min_text"] if guard["hold_eos"] else -1]
+        buf["thr"].copy_(torch.tensor([row] * B, dtype=torch.float32))
+        buf["t_len"].copy_(torch.tensor(tl, dtype=torch.int32))
+        for k in ("state", "sums", "trace"):
+            buf[k].zero_()
+        for b in range(B):  # frame 0 passes no step: pos = 0, complete iff 0 >= m - end_tokens
+            hold = guard["hold_eos"] and tl[b] >= guard["min_text"] and tl[b] > guard["end_tokens"]
+            samp[b, 6] = float(STOP_SPEECH if hold else -1)
+        runs = []
+        for slot, (l, h) in enumerate(heads):
+            if runs and runs[-1][0] == l:  # (check_align_heads admits at most 16 heads of one layer: a run fits one launch)
+                runs[-1][2].append(h)
+            else:
+                runs.append((l, slot, [h]))
+        by_layer = {}
+        for l, slot, hs in runs:
+            by_layer.setdefault(l, []).append((slot, hs))
+        return dict(guard, by_layer=by_layer, n_sel=len(heads), text_tokens=list(tl))
+
+    def _guard_mass(self, st, layer, qkv, ssq=None):
+        """After decode_attn_rope of `layer`: the text mass of every conditional row's new query for the guard's heads of this layer, into their scratch slots."""
+        buf = st["guard"]
+        for slot, hs in st["guard_on"]["by_layer"].get(layer, ()):
+            ops.guard_text_mass(qkv, st["positions"], self.cos, self.sin, st["kc"][layer], hs, st["done"], buf["t_len"], 34, 0.125, buf["p"][slot:], qkv_ssq=ssq,
+                                rms_dim=self.D if ssq is not None else 0, rms_eps=1e-5, max_ctx=st["max_ctx"])
+
+    def _guard_update(self, st):
+        buf = st["guard"]
+        ops.guard_update(buf["p"], buf["t_len"], st["step"], st["done"], buf["thr"], st["out_tokens"], buf["mass"], buf["state"], buf["sums"], buf["trace"],
+                         st["logits"], self.V, STOP_SPEECH, st["samp_dev"], n_sel=st["guard_on"]["n_sel"])
+
+    GUARD_REASONS = ("eos", "tail", "repeat", "run", "length")
+
+    @ops.on_device
+    def collect(self, handle):
+        """DecodeRuntime.collect; a guarded handle also leaves last_guard -- per utterance dict(reason: "eos" (sampled), "tail" / "repeat" / "run" (forced by
+        that rule) or "length" (max_new_tokens reached), tokens, fired_at, completed_at (None: never), position, text_tokens) -- from one small copy beside the
+        token copy, and last_guard_device."""
+        out = super().collect(handle)
+        g = handle.get("guard")
+        if g is not None:
+            buf = handle["st"]["guard"]
+            rep = []
+            for b, (row, toks) in enumerate(zip(buf["state"].cpu().tolist(), out)):
+                pos, complete, completed_at, fired, fired_at = row[:5]
+                reason = self.GUARD_REASONS[fired] if fired else "eos" if len(toks) and int(toks[-1]) == STOP_SPEECH else "length"
+                rep.append(dict(reason=reason, tokens=int(len(toks)), fired_at=fired_at if fired else None, completed_at=completed_at if complete else None,
+                                position=pos, text_tokens=g["text_tokens"][b]))
+            self.last_guard = rep
+            self.last_guard_device = dict(buf, heads=g["heads"])
+        return out
 
     @ops.on_device
     @torch.inference_mode()

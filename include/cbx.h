@@ -956,6 +956,60 @@ int cbx_attn_text_mass_f32(const float* q, const float* k, float* mass, const in
 int cbx_align_path_f32(const float* score, long s_sb, long s_si, const int* n, const int* m, int nz, int* spans, long sp_sb, int* frame_tok, long ft_sb, void* ws,
                        long ws_cap, void* stream);
 
+/* ---- alignment guard: the text mass of the CURRENT decode query and a per-utterance state machine on it, both inside the captured token step (added after ABI
+ * v16 without a version step: new functions only; no existing struct changes).  T3 sometimes never samples its end-of-speech token, or samples it too early; the
+ * reference project's later alignment analyser watches a few heads for that on the host.  Here the two launches ride in the step: nothing is allocated, nothing
+ * synchronises, and everything that varies per step or per request is read from DEVICE memory (positions, step, done, t_len, thresholds), so a new request replays
+ * the same captured graph.  Plain C++ kernels: no inline assembly, no atomics, every output element written by exactly one thread in a fixed summation order; two
+ * runs are bit-identical.
+ * cbx_guard_text_mass_f32: launched right after the cbx_decode_attn_rope launch of one layer (the new position's K is in the cache, the step's q/k/v buffer still
+ * live), for the conditional rows b < B and the heads[n_sel] of THAT layer (HOST array, by value; 1 <= n_sel <= 16, each in [0, n_heads), a repeated head is
+ * computed twice).
+ *   q: as the attention launch sees it (cbx_decode_attn_t): qkv + b ld_qkv + head 64 + d; qkv_nparts 2 or 4: the parts at multiples of qkv_part_stride added in part
+ *     order, times rsqrtf(ssq / rms_dim + rms_eps) with ssq = sum over parts, in part order, of qkv_ssq[part 16 + b] (then B <= 16); qkv_nparts 0 or 1: the row as it
+ *     is, qkv_ssq may be NULL and parts beyond qkv_nparts are never read; rotated by cos_t / sin_t ([pos][64]) at pos = positions[b]: q[d] cos[d] -/+ q[d ^ 32]
+ *     sin[d] (- for d < 32); cos_t = sin_t = NULL: no rotation.
+ *   k_j = kc + b k_row_stride + head k_head_stride + j 64 (one layer of T3's KV cache; 16-byte loads).
+ *   s[j] = scale * sum_(d = 0 .. 63) q[d] k_j[d], by fmaf in the order d = 0 .. 63 from 0, over ALL visible keys j <= positions[b];
+ *   p[j] = expf(s[j] - M) / L, M = max_j s[j], L = sum_j expf(s[j] - M): the normaliser covers the whole causal row (a thread adds its keys j = tid mod 256 in
+ *     order, a wave's 64 lanes by the xor butterfly 32 .. 1, the 4 waves in wave order);
+ *   stored: p[t0 + t] for t < t_len[b] at p + s p_ss + b p_sb + t, s the head's index in `heads` (the caller offsets p by the slots of earlier layers).
+ * A key beyond positions[b] is never loaded.  A row with done[b] != 0 writes nothing; neither does a row outside the caps, which are checked on the device because
+ * the numbers live there: t_len[b] in [1, t_cap], positions[b] in [0, max_ctx), t0 + t_len[b] <= positions[b] + 1.  Columns t >= t_len[b] are not written.
+ * Caps: max_ctx <= 4608 (the RoPE table; also the keys a head of kc holds), t_cap <= 1024, n_sel <= 16, B <= 64.
+ * One launch: one workgroup of 256 threads per (row, selected head), that head's K streamed once, the row's scores kept in LDS.
+ * -22 before any launch, nothing written: a null pointer (cos_t / sin_t: one without the other), B outside [1, 64], n_sel outside [1, 16], a head outside
+ * [0, n_heads), qkv_nparts not 0, 1, 2 or 4 (or > 1 without qkv_ssq, rms_dim > 0, B <= 16), ld_qkv < 64 n_heads, a negative stride, kc not 16-byte addressable,
+ * max_ctx outside [1, 4608] or beyond k_head_stride, t0 < 0, t_cap outside [1, 1024], p_sb < t_cap or (n_sel > 1) p_ss short of B rows. */
+int cbx_guard_text_mass_f32(const float* qkv, long ld_qkv, int qkv_nparts, long qkv_part_stride, const float* qkv_ssq, int rms_dim, float rms_eps, const int* positions,
+                            const float* cos_t, const float* sin_t, const float* kc, long k_row_stride, long k_head_stride, int max_ctx, const int* heads, int n_sel,
+                            int n_heads, int B, const int* done, const int* t_len, int t0, int t_cap, float scale, float* p, long p_ss, long p_sb, void* stream);
+/* cbx_guard_update_f32: once per step, between the head GEMV and cbx_t3_sample; one workgroup (1024 threads, thread t owns text column t) per utterance b < B.
+ * Device state per utterance: state[b][8] int32 = {pos, complete, completed_at, fired, fired_at, 0, 0, 0}, sums[b][4] fp32 = {tail_sum[3], rep_sum}, all zero at
+ * the start of a request.  thresholds[b][8] fp32 = {back, ahead, end_tokens, tail, repeat, repeat_skip, token_run, hold_min}; end_tokens is clamped to 1 .. 3
+ * (tail_sum has three entries); hold_min: hold the end token back for texts of at least hold_min tokens, < 0: never.
+ * A row with done[b] != 0 or fired != 0 does nothing; neither does one with m = t_len[b] outside [1, min(1024, m_si)] or i = step[b] outside [0, max_steps).
+ * Otherwise, with p_h[s][b][t] = p[s p_ss + b p_sb + t] the slots the mass launches of this step filled:
+ *   1. a[t] = weight * sum_(s = 0 .. n_sel-1, in order) p_h[s][b][t], weight = 1.0f / n_sel, stored to mass[b m_sb + i m_si + t] (the history), t < m.
+ *   2. cur = the lowest t with the largest a[t]; if -back <= cur - pos <= ahead then pos = cur (a jump outside the window is ignored).
+ *   3. if not complete and pos >= m - end_tokens: complete = 1, completed_at = i.
+ *   4. if complete (the latching step included): tail_sum[j] += a[max(0, m - end_tokens) + j] for j < min(end_tokens, m) -- the last min(end_tokens, m) columns --;
+ *      rep_sum += max_(t < m - repeat_skip) a[t], or 0 when there is no such column.  fp32 adds in step order.
+ *   5. run = token_run > 0 and i >= token_run and out_tokens[b max_steps + i-1 .. i-token_run] are all equal.
+ *   6. reason = the first that holds: 1 (tail) complete and max_(j < min(end_tokens, m)) tail_sum[j] >= tail; 2 (repeat) complete and rep_sum >= repeat; 3 (run);
+ *      else 0.  The two sums exist once complete (they are 0 before: `complete` matters for a threshold of 0 alone, which then means "at completion").
+ *   7. reason != 0: fired = reason, fired_at = i; logits[b ld_logits + v] and logits[(B + b) ld_logits + v], v < V, become 0 and 32768 at v = eos -- the sampler's
+ *      c + w (c - u) is then this pattern for every w, every processor order leaves probability 1 on eos for every uniform, and cbx_t3_sample itself writes the
+ *      token, sets done and stops the row --; dev_params[b][6] (the sampler's ban token) = -1.  Columns v >= V of a padded row are not touched.
+ *      reason == 0: dev_params[b][6] = eos when hold_min >= 0 and m >= hold_min and not complete, else -1 (the sampler's existing per-utterance ban).
+ *   8. trace[b max_steps + i] = pos | complete << 16 | ban << 17 | reason << 18 (ban: 1 when dev_params[b][6] was set to eos).
+ * Frame 0 is sampled from the prefill logits and passes no step: the first call sees i = 1 and pos = 0; the host writes the first ban into dev_params.
+ * -22 before any launch, nothing written: a null pointer, B outside [1, 64], n_sel outside [1, 1024], max_steps < 1, V < 1, eos outside [0, V), ld_logits < V, a
+ * negative stride of p, m_si < 1, (B > 1) m_sb < max_steps m_si. */
+int cbx_guard_update_f32(const float* p, long p_ss, long p_sb, int n_sel, const int* t_len, const int* step, const int* done, const float* thresholds,
+                         const long long* out_tokens, int max_steps, float* mass, long m_sb, long m_si, int* state, float* sums, int* trace, float* logits, long ld_logits,
+                         int V, int B, int eos, float* dev_params, void* stream);
+
 /* ---- output formats: resample 24 kHz fp32 to the delivery rate and encode it, one launch for the rows of a batch or of a stream's round (added after ABI v16
  * without a version step: a new function only).  The reference returns 24 kHz fp32 and leaves this to its caller (tts.py:272, mtl_tts.py:352, tts_turbo.py:320,
  * vc.py:104).  Rows as cbx_wave_join_f32 takes them: R in [1, 64] pieces of row_len[r] floats at wav + row_off[r] (HOST arrays; 4-byte alignment is enough).
