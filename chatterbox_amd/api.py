@@ -217,20 +217,6 @@ def _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, windo
                 window=check_stream_window(window, fade, speed_kw.get("speed")), **speed_kw)
 
 
-def _one_loudness(loudness):
-    """The `loudness` of a method that takes ONE request: None, or the LUFS target as a float (ops.check_loudness; a sequence is a TypeError)"""
-    if isinstance(loudness, (list, tuple)):
-        raise TypeError(f"loudness: expected None or a number, got a {type(loudness).__name__}")
-    loud = ops.check_loudness(loudness, 1)
-    return None if loud is None else loud[0]
-
-
-def _loudness_kw(loudness):
-    """generate's `loudness` as the engines' loudness= keyword ({} for None: the engine call is then exactly the one without it)"""
-    loud = _one_loudness(loudness)
-    return {} if loud is None else dict(loudness=loud)
-
-
 PAUSE_FADE = 240  # samples of cross-fade over a shortened pause: fixed
 
 
@@ -267,26 +253,70 @@ def _pauses(max_pause, pause_db, B=1, one=False):
     return dict(keep=keep, db=float(pause_db), fade=PAUSE_FADE) if any(keep) else None
 
 
-def _pause_kw(max_pause, pause_db):
-    """generate's `max_pause` / `pause_db` as the engines' pauses= keyword ({} for None: the engine call is then exactly the one without it)"""
-    pz = _pauses(max_pause, pause_db, 1, one=True)
-    return {} if pz is None else dict(pauses=pz)
+def _request_seeds(seed, B=1, one=True, generator=None):
+    """`seed` of a method that takes ONE request (None or an int in [0, 2^64)) or `seeds` of generate_batch (None, an int for every request or a sequence of B ints;
+    not together with a generator) -> a list of B ints, or None.  TypeError / ValueError before anything is launched."""
+    if not one:
+        return ops.request_seeds(seed, B, generator)
+    if seed is None:
+        return None
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError(f"seed: expected an int, got {type(seed).__name__}")
+    return ops.check_seeds(seed, 1, "seed")
 
 
-def _one_pitch(speed, pitch):
-    """The `pitch` of a method that takes ONE request: None (also for 0), or the semitones as a float in [-12, 12] (ops.check_pitch; a sequence is a TypeError),
-    checked against the call's `speed` (ops.check_speed_pitch: speed / 2^(pitch / 12) in [0.5, 2.0], else a ValueError naming both) before anything is launched"""
-    if isinstance(pitch, (list, tuple)):
-        raise TypeError(f"pitch: expected None or a number of semitones, got a {type(pitch).__name__}")
-    p = ops.check_pitch(pitch, 1)
-    ops.check_speed_pitch(speed, p, 1)
-    return None if p is None else p[0]
+class _Options:
+    """The delivery options of ONE public call for its B requests, built from the public arguments and validated when the method is CALLED, generators included --
+    in one order for every method: the format (sample_rate, encoding), word_times, seed / seeds (with the generator), speed, loudness, max_pause / pause_db, pitch
+    with the speed x pitch rule (ops.check_speed_pitch), guard.  one=True: the method serves one request (generate, generate_long, ...): a sequence for
+    loudness, max_pause or pitch is then a TypeError.  segments=False (generate_long without return_segments): word_times is refused, its words travel in the
+    segments.  Holds fmt (ops.check_format's dict), words (_word_times' mode), seeds, speed, loud, pitch (B entries each), pz (_pauses' dict), guard (the
+    engines' dict) -- each None when no request uses it -- and the generator; kw(idx) turns them into the engines' keywords."""
 
+    def __init__(self, model, B=1, one=True, *, seeds=None, generator=None, speed=None, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0,
+                 pitch=None, word_times=False, guard=None, segments=True):
+        self.model, self.one, self.generator = model, one, generator
+        self.fmt = ops.check_format(sample_rate, encoding)
+        self.words = None if word_times is None or word_times is False else model._word_mode(word_times, max_pause)
+        if self.words is not None and not segments:
+            raise ValueError("word_times without return_segments: the words of generate_long travel in its segments")
+        self.seeds = _request_seeds(seeds, B, one, generator)
+        self.speed = ops.check_speed(speed, B)
+        if one and isinstance(loudness, (list, tuple)):
+            raise TypeError(f"loudness: expected None or a number, got a {type(loudness).__name__}")
+        self.loud = ops.check_loudness(loudness, B)
+        self.pz = _pauses(max_pause, pause_db, B, one)
+        if one and isinstance(pitch, (list, tuple)):
+            raise TypeError(f"pitch: expected None or a number of semitones, got a {type(pitch).__name__}")
+        self.pitch = ops.check_pitch(pitch, B)
+        ops.check_speed_pitch(self.speed, self.pitch, B)
+        self.guard = None if guard is None or guard is False else model._guard(guard)
 
-def _pitch_kw(speed, pitch):
-    """generate's `pitch` as the engines' pitch= keyword ({} for None / 0: the engine call is then exactly the one without it)"""
-    p = _one_pitch(speed, pitch)
-    return {} if p is None else dict(pitch=[p])
+    def kw(self, idx, chunks=False):
+        """The engines' keywords of a call or job over the requests `idx`, the call without an option being exactly the call before there was one: seeds and speed
+        are present when given at all; loudness, pauses and pitch only when a request in idx uses them; the format unless a watermarker is loaded (it works on the
+        24 kHz fp32 waveform: the conversion then follows it, in _finish); words and guard, one setting for the call, with the model's align_heads.
+        chunks=True (long form): idx are chunks of the ONE request.  Every chunk carries the request's options, chunk k the seed chunk_seed(seed, k); loudness and
+        the format are held back from the jobs -- the assembled whole is normalised and converted once."""
+        rows = (lambda v: [v[0]] * len(idx)) if chunks else (lambda v: _pick(v, idx))
+        kw = {}
+        if self.seeds is not None:
+            kw["seeds"] = [chunk_seed(self.seeds[0], k) for k in idx] if chunks else rows(self.seeds)
+        if self.speed is not None:
+            kw["speed"] = rows(self.speed)
+        if self.loud is not None and not chunks and any(v is not None for v in rows(self.loud)):
+            kw["loudness"] = self.loud[0] if self.one else rows(self.loud)
+        if self.pz is not None and any(rows(self.pz["keep"])):
+            kw["pauses"] = dict(self.pz, keep=rows(self.pz["keep"]))
+        if self.pitch is not None and any(rows(self.pitch)):
+            kw["pitch"] = rows(self.pitch)
+        if self.fmt is not None and not chunks and self.model.watermarker is None:
+            kw["format"] = self.fmt
+        if self.words is not None:
+            kw["words"] = dict(heads=self.model.align_heads)
+        if self.guard is not None:
+            kw["guard"] = self.guard
+        return kw
 
 
 def _stream_speed_kw(speed):
@@ -313,28 +343,6 @@ def _per_request(value, B, name, one):
 
 
 _PATH = (str, bytes, os.PathLike)
-
-
-def _batch_seeds(seeds, B, generator=None):
-    """generate_batch's `seeds` as a list of B ints, or None: an int serves every request, else a list or tuple of exactly B ints in [0, 2^64) (TypeError /
-    ValueError before anything is launched); not together with a generator."""
-    return ops.request_seeds(seeds, B, generator)
-
-
-def _seed_kw(seed):
-    """generate's `seed` as the engines' seeds= keyword ({} without one: the call is then exactly the unseeded one)."""
-    if seed is None:
-        return {}
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise TypeError(f"seed: expected an int, got {type(seed).__name__}")
-    return dict(seeds=ops.check_seeds(seed, 1, "seed"))
-
-
-def _speed_kw(speed, B=1):
-    """`speed` as the engines' speed= keyword ({} at 1.0 / None: the call is then exactly the one without it).  generate: one number; generate_batch: a number
-    or a sequence of B (entries may be None: 1.0).  TypeError / ValueError (ops.check_speed: numbers in [0.5, 2.0]) before anything is launched."""
-    speed = ops.check_speed(speed, B)
-    return {} if speed is None else dict(speed=speed)
 
 
 # ---------------------------------------------------------------------------------------------------------------- generate_long: host-side plumbing
@@ -376,10 +384,9 @@ def _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, 
             raise TypeError(f"{name}: expected an int, got {type(v).__name__}")
         if not 0 <= v <= 1 << 20:
             raise ValueError(f"{name} = {v}: expected an int in [0, 2^20]")
-    seed = _seed_kw(seed).get("seeds", [None])[0]
-    speed = ops.check_speed(speed, 1)
-    return dict(max_chars=max_chars, pause=float(pause), paragraph_pause=float(paragraph_pause), trim_db=trim_db, trim_pad=trim_pad, join_fade=join_fade, seed=seed,
-                speed=None if speed is None else speed[0])
+    seed, speed = _request_seeds(seed), ops.check_speed(speed, 1)
+    return dict(max_chars=max_chars, pause=float(pause), paragraph_pause=float(paragraph_pause), trim_db=trim_db, trim_pad=trim_pad, join_fade=join_fade,
+                seed=None if seed is None else seed[0], speed=None if speed is None else speed[0])
 
 
 def _long_numbers(**params):
@@ -431,10 +438,6 @@ def _long_jobs(chunks, max_batch, a, sizes=None):
             job["seeds"] = [chunk_seed(a["seed"], k) for k in idx]
         if a["speed"] is not None:
             job["speed"] = [a["speed"]] * len(idx)
-        if a.get("pauses") is not None:
-            job["pauses"] = dict(a["pauses"], keep=a["pauses"]["keep"] * len(idx))
-        if a.get("pitch") is not None:
-            job["pitch"] = [a["pitch"]] * len(idx)
         jobs.append(job)
     return jobs
 
@@ -442,8 +445,8 @@ def _long_jobs(chunks, max_batch, a, sizes=None):
 def long_plan(chunks, max_batch, a):
     """The jobs of a generate_long call, WITHOUT their tokens and voices: chunks = split_text's list, a = _long_args' dict.  Chunks keep the text's order (no length
     sort: a piece is a run of consecutive chunks) and are cut into consecutive device batches of at most max_batch (and at most 64, the join's row limit).  Per job:
-    dict(chunks=[indices], join=the engines' join dict, seeds=[...] if seeded, speed=[...] if not 1.0, pauses=the engines' pauses dict if a["pauses"],
-    pitch=[...] if a["pitch"]).  The gap behind a chunk is round(pause * 24000 / speed)
+    dict(chunks=[indices], join=the engines' join dict, seeds=[...] if seeded, speed=[...] if not 1.0) -- the seeds and speeds _Options.kw(chunks=True) gives the
+    engine jobs, next to the other options.  The gap behind a chunk is round(pause * 24000 / speed)
     samples, paragraph_pause behind a paragraph's last chunk; the first job carries first=True, the last one last=True."""
     return _long_jobs(chunks, max_batch, a)
 
@@ -492,6 +495,13 @@ def batch_plan(lengths, max_batch):
     assert max_batch >= 1
     order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
     return [order[lo:lo + max_batch] for lo in range(0, len(order), max_batch)]
+
+
+def _batch_of(texts):
+    """generate_batch's texts as a list of B >= 1: one str is a batch of one"""
+    texts = [texts] if isinstance(texts, str) else list(texts)
+    assert len(texts) >= 1, "empty batch"
+    return texts
 
 
 def _sampling_lists(B, **params):
@@ -607,11 +617,6 @@ class _Finish:
             self.engine.last_loudness = ops.wave_normalize([w], [float(target)])
             return w.cpu()
 
-    def _engine_format(self, fmt):
-        """The engines' format= keyword: {} for the default format (the engine call is then exactly the one without it) and when a watermarker is loaded (it works
-        on the 24 kHz fp32 waveform: the conversion then follows it, in _finish)."""
-        return {} if fmt is None or self.watermarker is not None else dict(format=fmt)
-
     def _stream_pieces(self, rounds, fmt):
         """The pieces of generate_stream from an engine stream's rounds: (1, n) CPU tensors, empty ones left out.  With a format and a watermarker every piece is
         watermarked as 24 kHz fp32 and then goes through an ops.WaveFormatStream held here, so the pieces add up to the conversion of the whole."""
@@ -688,15 +693,6 @@ class _TTS(_Finish):
             raise ValueError('word_times="words" needs a tokenizer with pieces(ids) to group text tokens into words; word_times="tokens" does not')
         return mode
 
-    def _long_word_mode(self, word_times, max_pause, return_segments):
-        mode = self._word_mode(word_times, max_pause)
-        if mode is not None and not return_segments:
-            raise ValueError("word_times without return_segments: the words of generate_long travel in its segments")
-        return mode
-
-    def _word_kw(self, mode):
-        return {} if mode is None else dict(words=dict(heads=self.align_heads))
-
     def _words_of(self, mode, tokens, al, place):
         """The words of one utterance: dict(text, start, stop, tokens=(a, b), frames=(f0, f1)) in text order.  tokens: the engine's 1-D text ids; al: its entry of
         synthesize(words=)'s alignment; place(s): a 24 kHz sample of the utterance's own waveform -> a sample of what the caller receives (clipping included).
@@ -724,12 +720,10 @@ class _TTS(_Finish):
     # ------------------------------------------------------------------------------------------------------------ the alignment guard
     last_guard = None  # per request of the last guarded call, in the caller's order: T3Engine.collect's report
 
-    def _guard_kw(self, guard):
-        """guard= of generate / generate_batch / generate_long / generate_long_stream -> {} (None / False: the call without the argument) or dict(guard=the
-        engine's dict): True is T3Engine.GUARD_DEFAULTS with this model's align_heads, a dict overrides single keys; an unknown key is a ValueError.  The values
+    def _guard(self, guard):
+        """guard= of generate / generate_batch / generate_long / generate_long_stream (None / False, the call without the argument, never gets here) -> the
+        engine's dict: True is T3Engine.GUARD_DEFAULTS with this model's align_heads, a dict overrides single keys; an unknown key is a ValueError.  The values
         are checked by the engine, before anything is launched."""
-        if guard is None or guard is False:
-            return {}
         from .t3 import T3Engine
         if guard is not True and not isinstance(guard, dict):
             raise ValueError(f"guard: expected None, True or a dict of {sorted(T3Engine.GUARD_DEFAULTS)}, got {guard!r}")
@@ -738,7 +732,7 @@ class _TTS(_Finish):
             raise ValueError(f"guard: unknown key(s) {sorted(set(over) - set(T3Engine.GUARD_DEFAULTS))} (known: {sorted(T3Engine.GUARD_DEFAULTS)})")
         g = dict(T3Engine.GUARD_DEFAULTS, heads=self.align_heads, **over) if "heads" not in over else dict(T3Engine.GUARD_DEFAULTS, **over)
         check = getattr(getattr(self.engine, "t3", None), "check_guard", None)
-        return dict(guard=g if check is None else check(g))
+        return g if check is None else check(g)
 
     def _take_guard(self, reports, who):
         """model.last_guard = the reports in the caller's order; one UserWarning names the requests that did not end by a sampled end-of-speech token"""
@@ -750,19 +744,21 @@ class _TTS(_Finish):
                           "was forced; length: the speech-token budget was spent)", UserWarning, stacklevel=3)
 
     # ------------------------------------------------------------------------------------------------------------ one utterance
-    def _generate(self, text_ids, fmt=None, word_mode=None, **kw):
-        """generate() behind its argument handling: tokenizer ids -> the finished waveform (word_mode: and its words).  kw: sampling arguments, and _synth_kw's if
-        they are to differ; guard (_guard_kw's dict) among them: last_guard is then the request's report."""
+    def _generate(self, text_ids, opts=None, **kw):
+        """generate() behind its argument handling: tokenizer ids -> the finished waveform (opts.words: and its words).  opts: the call's _Options (None: no
+        option); kw: sampling arguments, and _synth_kw's if they are to differ.  With a guard last_guard is the request's report."""
+        opts = opts or _Options(self)
         tokens = self._engine_tokens(text_ids)
-        res = self.engine.synthesize([tokens], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw), **self._engine_format(fmt), **self._word_kw(word_mode))
-        if kw.get("guard") is not None:
+        res = self.engine.synthesize([tokens], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw), **opts.kw([0]))
+        if opts.guard is not None:
             self._take_guard(list(self.engine.last_guard), "generate")
-        wav = self._finish(res[0][0], fmt)
-        return wav if word_mode is None else (wav, self._words_of(word_mode, tokens, res[2][0], self._place(wav.shape[-1], fmt)))
+        wav = self._finish(res[0][0], opts.fmt)
+        return wav if opts.words is None else (wav, self._words_of(opts.words, tokens, res[2][0], self._place(wav.shape[-1], opts.fmt)))
 
-    def _generate_stream(self, text_ids, stream_kw, fmt=None, **samp):
+    def _generate_stream(self, text_ids, stream_kw, opts, **samp):
+        """generate_stream() behind its argument handling; of opts a stream takes the seed and the format, its speed travels in stream_kw (_stream_kw)"""
         return self._stream_pieces(self.engine.synthesize_stream([self._engine_tokens(text_ids)], self.conds.t3.as_dict(), self.conds.gen, **self._synth_kw(), **stream_kw,
-                                                                 **samp, **self._engine_format(fmt)), fmt)
+                                                                 **samp, **opts.kw([0])), opts.fmt)
 
     # ------------------------------------------------------------------------------------------------------------ device batches
     def _run_jobs(self, jobs, synth_kw):
@@ -783,103 +779,74 @@ class _TTS(_Finish):
             args = [job.pop(k) for k in ("text_tokens", "t3_conds", "gen_ref")]
             yield self.engine.synthesize(*args, **synth_kw, **job)
 
-    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, unsampled, fmt=None, loudness=None, pauses=None, pitch=None, word_times=False,
-                        guard=None, **analyse_kw):
-        """generate_batch behind its signature: validation of every per-request argument (seeds and speed first), then the voices, then tokenisation, then the
+    def _generate_batch(self, texts, language_ids, audio_prompt_paths, conds, samp, unsampled, opts, **analyse_kw):
+        """generate_batch behind its signature and its _Options: validation of the other per-request arguments, then the voices, then tokenisation, then the
         device work.  samp: the sampling arguments the engine takes; unsampled: those it does not -- exaggeration, which picks the voice's cond dict, and what the
         backbone ignores."""
-        texts = [texts] if isinstance(texts, str) else list(texts)
         B = len(texts)
-        assert B >= 1, "empty batch"
-        word_mode = self._word_mode(word_times, None if pauses is None else pauses[0])
-        guard_kw = self._guard_kw(guard)
-        seeds = _batch_seeds(seeds, B, generator)
-        speed = ops.check_speed(speed, B)
-        loud = ops.check_loudness(loudness, B)
-        pz = None if pauses is None else _pauses(*pauses, B)
-        pit = ops.check_pitch(pitch, B)
-        ops.check_speed_pitch(speed, pit, B)
         langs = self._languages(language_ids, B)
         samp = _sampling_lists(B, **samp)
         unsampled = _sampling_lists(B, **unsampled)
         self._warn_ignored(*(v for vals in unsampled.values() for v in vals))
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, unsampled["exaggeration"], **analyse_kw)
         tokens = [self._engine_tokens(self._text_ids(t, lid)) for t, lid in zip(texts, langs)]
-        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, generator, seeds, speed, fmt, loud, pz, pit, word_mode, guard_kw)
+        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, opts)
 
     def _languages(self, language_ids, B):
         return [None] * B
 
-    def _run_batch(self, tokens, voices, exaggeration, samp, generator, seeds=None, speed=None, fmt=None, loud=None, pz=None, pit=None, word_mode=None, guard_kw=None):
+    def _run_batch(self, tokens, voices, exaggeration, samp, opts):
         """Sub-batches of at most max_batch requests in order of text length (_run_jobs: one runs the serial schedule, several the throughput schedule).  Returns the
-        finished waveforms in the caller's order.  seeds (B ints or None) travel with their requests: a request's draws do not depend on the sub-batch or the row
-        it lands in.  speed (B floats or None) travels the same way.  fmt (one format for the call, or None): every job carries it as `format` unless a
-        watermarker is loaded (_engine_format).  loud (B LUFS targets / Nones, or None) travels with its requests like speed: a job carries `loudness` only when
-        one of its requests has a target.  pz (_pauses' dict or None) the same: a job carries `pauses`, with its requests' keeps, only when one of them has one.  pit (B semitones or None) the same: a job
-        carries `pitch` only when one of its requests is transposed.  word_mode (_word_mode's): every job carries `words`, the sub-batches then run the serial
-        schedule one after the other (_run_jobs), and the result is a list of (waveform, words).  guard_kw (_guard_kw's): every job carries `guard`, one setting
-        for the call; last_guard holds the reports in the caller's order."""
+        finished waveforms in the caller's order.  Every option travels with its request (opts.kw(idx): a request's draws, rate, level, pauses and pitch do not
+        depend on the sub-batch or the row it lands in, and a job carries an option only when one of its requests uses it).  With word_times every job carries
+        `words`, the sub-batches then run the serial schedule one after the other (_run_jobs), and the result is a list of (waveform, words).  With a guard every
+        job carries it, one setting for the call; last_guard holds the reports in the caller's order."""
         dicts = [_t3_dict(c.t3, ex) for c, ex in zip(voices, exaggeration)]
         plan = batch_plan([int(t.numel()) for t in tokens], int(self.max_batch or self.engine.t3.MAX_BATCH))
         jobs = []
         for idx in plan:
             job = dict(text_tokens=_pick(tokens, idx), t3_conds=_one_or_list(_pick(dicts, idx)), gen_ref=_one_or_list([voices[i].gen for i in idx]),
                        **{k: _pick(v, idx) for k, v in samp.items()})
-            if generator is not None:  # repeatable: the sampling draws of every sub-batch come from the generator, in execution order
-                job["uniforms"] = torch.rand(len(idx), self.N_DRAWS, device=self.engine.dev, generator=generator)
-                job["generator"] = generator
-            if seeds is not None:
-                job["seeds"] = _pick(seeds, idx)
-            if speed is not None:
-                job["speed"] = _pick(speed, idx)
-            if loud is not None and any(v is not None for v in _pick(loud, idx)):
-                job["loudness"] = _pick(loud, idx)
-            if pz is not None and any(_pick(pz["keep"], idx)):
-                job["pauses"] = dict(pz, keep=_pick(pz["keep"], idx))
-            if pit is not None and any(_pick(pit, idx)):
-                job["pitch"] = _pick(pit, idx)
-            job.update(self._engine_format(fmt))
-            job.update(self._word_kw(word_mode))
-            job.update(guard_kw or {})
-            jobs.append(job)
+            if opts.generator is not None:  # repeatable: the sampling draws of every sub-batch come from the generator, in execution order
+                job["uniforms"] = torch.rand(len(idx), self.N_DRAWS, device=self.engine.dev, generator=opts.generator)
+                job["generator"] = opts.generator
+            jobs.append(dict(job, **opts.kw(idx)))
         out, reports = [None] * len(tokens), [None] * len(tokens)
         for idx, res in zip(plan, self._run_jobs(jobs, self._synth_kw(batch=True))):
-            if guard_kw:
+            if opts.guard is not None:
                 for i, r in zip(idx, self.engine.last_guard):
                     reports[i] = r
             for r, (i, w) in enumerate(zip(idx, res[0])):
-                out[i] = self._finish(w, fmt)
-                if word_mode is not None:
-                    out[i] = (out[i], self._words_of(word_mode, tokens[i], res[2][r], self._place(out[i].shape[-1], fmt)))
-        if guard_kw:
+                out[i] = self._finish(w, opts.fmt)
+                if opts.words is not None:
+                    out[i] = (out[i], self._words_of(opts.words, tokens[i], res[2][r], self._place(out[i].shape[-1], opts.fmt)))
+        if opts.guard is not None:
             self._take_guard(reports, "generate_batch")
         return out
 
-    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, fmt=None, loudness=None, ramp=None, **prepare_kw):
-        """generate_long behind its signature and _long_args: the remaining checks, the voice as generate() prepares it, then _run_long.  samp / unsampled: as
-        _generate_batch takes them, one number each.  ramp (_long_stream_args' pair): generate_long_stream -- the same checks and the same voice, all of it when
-        the method is CALLED, then the generator of _stream_long."""
+    def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, opts, ramp=None, **prepare_kw):
+        """generate_long behind its signature, its _Options and _long_args: the remaining checks, the voice as generate() prepares it, then _run_long.  samp /
+        unsampled: as _generate_batch takes them, one number each.  ramp (_long_stream_args' pair): generate_long_stream -- the same checks and the same voice,
+        all of it when the method is CALLED, then the generator of _stream_long."""
         if not isinstance(text, str):
             raise TypeError(f"text: expected a str, got {type(text).__name__}")
         _long_numbers(**unsampled, **samp)
-        loud = _one_loudness(loudness)
         self._use_voice(audio_prompt_path, unsampled["exaggeration"], **prepare_kw)
         self._warn_ignored(*unsampled.values())
         tokenize = lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id))
         if ramp is not None:
-            return self._stream_long(*self._long_work(text, a, tokenize, samp, ramp), a, return_segments, fmt, loud)
-        return self._run_long(text, a, tokenize, samp, return_segments, fmt, loud)
+            return self._stream_long(*self._long_work(text, a, tokenize, samp, opts, ramp), a, return_segments, opts)
+        return self._run_long(text, a, tokenize, samp, return_segments, opts)
 
-    def _long_work(self, text, a, tokenize, samp, ramp=None):
+    def _long_work(self, text, a, tokenize, samp, opts, ramp=None):
         """(chunks, plan, engine jobs) of a long-form call: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), long_plan -- long_stream_plan with
-        a ramp (first_batch, batch_growth)"""
+        a ramp (first_batch, batch_growth); a job carries its chunks' options (opts.kw(chunks=True): loudness and the format are held back for the whole)"""
         chunks = split_text(text, a["max_chars"])
         tokens = [tokenize(c) for c, _ in chunks]
         max_batch = int(self.max_batch or self.engine.t3.MAX_BATCH)
         plan = long_plan(chunks, max_batch, a) if ramp is None else long_stream_plan(chunks, max_batch, a, *ramp)
         t3, gen = self.conds.t3.as_dict(), self.conds.gen
-        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, **{k: p[k] for k in ("seeds", "speed", "join", "pauses", "pitch") if k in p},
-                     **self._word_kw(a.get("words")), **(a.get("guard") or {})) for p in plan]
+        jobs = [dict(text_tokens=_pick(tokens, p["chunks"]), t3_conds=t3, gen_ref=gen, **samp, join=p["join"], **opts.kw(p["chunks"], chunks=True)) for p in plan]
         return chunks, plan, jobs
 
     @staticmethod
@@ -900,47 +867,48 @@ class _TTS(_Finish):
             logging.getLogger(__name__).warning("%s: chunk(s) %s of %d reached the speech-token budget without an end-of-speech token and are cut "
                                                 "off; use a smaller max_chars (now %d)", who, cut, len(truncated), max_chars)
 
-    def _run_long(self, text, a, tokenize, samp, return_segments, fmt=None, loud=None):
+    def _run_long(self, text, a, tokenize, samp, return_segments, opts):
         """generate_long behind its validation: split, tokenise (`tokenize(chunk)` -> the engine's 1-D id tensor), run the jobs of long_plan (_run_jobs), concatenate
-        the joined pieces on the host, watermark the whole once.  fmt: the engine jobs do not carry it -- the concatenated 24 kHz waveform is converted once, in
+        the joined pieces on the host, watermark the whole once.  opts.fmt: the engine jobs do not carry it -- the concatenated 24 kHz waveform is converted once, in
         _finish (host -> device -> host; no converter state travels through the joined pieces on the device), and the segments' start / stop become output samples,
-        ceil(s U / D), so the last stop is the length; src_start / src_stop stay 24 kHz samples.  loud (a LUFS target or None): the engine jobs do not carry it
+        ceil(s U / D), so the last stop is the length; src_start / src_stop stay 24 kHz samples.  opts.loud (the LUFS target or None): the engine jobs do not carry it
         either -- the concatenated waveform is measured and gained as ONE signal in _finish, ahead of the watermark, so the chunks keep their relative level."""
-        chunks, plan, jobs = self._long_work(text, a, tokenize, samp)
-        pieces, segments, base = [], [], 0
+        chunks, plan, jobs = self._long_work(text, a, tokenize, samp, opts)
+        fmt, pieces, segments, base = opts.fmt, [], [], 0
         fl = (lambda v: v) if fmt is None else (lambda v: ops.formatted_len(v, fmt["sample_rate"]))
         for p, job, res in zip(plan, jobs, self._run_jobs(jobs, self._synth_kw())):
             piece, st = res[0], res[1]
             pieces.append(piece["wav"].detach().float().cpu())
             assert pieces[-1].numel() == piece["total"], "a joined piece and its layout record disagree"
             segs = self._long_segments(chunks, p, piece, st, base)
-            if a.get("guard"):  # the alignment guard's report of every chunk travels in its segment
+            if opts.guard is not None:  # the alignment guard's report of every chunk travels in its segment
                 for seg, r in zip(segs, self.engine.last_guard):
                     seg["guard"] = r
-            if a.get("words") is not None:  # a word of chunk r: its samples clipped to the kept part [src_start, src_stop), shifted to the segment's start
+            if opts.words is not None:  # a word of chunk r: its samples clipped to the kept part [src_start, src_stop), shifted to the segment's start
                 for r, seg in enumerate(segs):
                     place = lambda v, seg=seg: fl(seg["start"] + min(max(v, seg["src_start"]), seg["src_stop"]) - seg["src_start"])
-                    seg["words"] = self._words_of(a["words"], job["text_tokens"][r], res[2][r], place)
+                    seg["words"] = self._words_of(opts.words, job["text_tokens"][r], res[2][r], place)
             segments += segs
             base += piece["total"]
         self._warn_truncated("generate_long", [s["truncated"] for s in segments], a["max_chars"])
-        if a.get("guard"):
+        if opts.guard is not None:
             self._take_guard([s["guard"] for s in segments], "generate_long")
-        wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=loud)
+        wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=None if opts.loud is None else opts.loud[0])
         if fmt is not None:
             for seg in segments:
                 seg.update(start=ops.formatted_len(seg["start"], fmt["sample_rate"]), stop=ops.formatted_len(seg["stop"], fmt["sample_rate"]))
         return (wav, segments) if return_segments else wav
 
-    def _stream_long(self, chunks, plan, jobs, a, return_segments, fmt=None, loud=None):
+    def _stream_long(self, chunks, plan, jobs, a, return_segments, opts):
         """generate_long_stream behind its validation, a generator: the jobs run through _run_jobs -- while the consumer holds piece k the throughput schedule has
         the T3 of pieces k + 1 and k + 2 in flight --, and every joined piece is finished and yielded as it leaves the device.  Per piece, in this order:
-        loudness (loud: upload, ONE ops.WaveLoudnessStream held here measures pieces 0 .. k, ops.wave_gain with its gain, ceiling 1.0; engine.last_loudness = the
+        loudness (opts.loud: upload, ONE ops.WaveLoudnessStream held here measures pieces 0 .. k, ops.wave_gain with its gain, ceiling 1.0; engine.last_loudness = the
         latest stats), the watermark if a watermarker is loaded, the format (ONE ops.WaveFormatStream held here, final on the last piece; the engine jobs do not
         carry it).  With neither a piece costs what generate_long's costs: one copy to the host.  Closing the generator closes _run_jobs, and with it the
         engine's synthesize_pipelined (its `finally` returns the T3 engines)."""
         dev, scope = self._device_scope()
         run = self._run_jobs(jobs, self._synth_kw())
+        fmt, loud = opts.fmt, None if opts.loud is None else opts.loud[0]
         meter = conv = None
         base, truncated, reports = 0, [], []
         try:
@@ -948,7 +916,7 @@ class _TTS(_Finish):
                 wav = piece["wav"].detach().float().cpu()
                 assert wav.numel() == piece["total"], "a joined piece and its layout record disagree"
                 segments = self._long_segments(chunks, p, piece, st, base)
-                if a.get("guard"):  # the reports so far, in text order; a piece's own travel in its segments
+                if opts.guard is not None:  # the reports so far, in text order; a piece's own travel in its segments
                     for seg, r in zip(segments, self.engine.last_guard):
                         seg["guard"] = r
                     reports += [s["guard"] for s in segments]
@@ -976,7 +944,7 @@ class _TTS(_Finish):
         finally:
             run.close()
             self._warn_truncated("generate_long_stream", truncated, a["max_chars"])
-            if a.get("guard"):
+            if opts.guard is not None:
                 self._take_guard(reports, "generate_long_stream")
 
 
@@ -1096,12 +1064,9 @@ class ChatterboxTTS(_LlamaTTS):
         ChatterboxVC do not take the argument: round streams and the GPT-2 backbone are not built.
         This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db`, `pitch`, `word_times` and `guard` for every method
         of every class of this module; the others say only what differs."""
-        fmt = ops.check_format(sample_rate, encoding)
-        word_mode = self._word_mode(word_times, max_pause)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch), **self._guard_kw(guard))
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard)
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate(self._text_ids(text), fmt, word_mode, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
-                              top_p=top_p, **seed_kw)
+        return self._generate(self._text_ids(text), opts, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                       max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
@@ -1125,12 +1090,10 @@ class ChatterboxTTS(_LlamaTTS):
         all of it, limited to a sample peak of 1.0, applied on the device ahead of the watermark and the conversion.
         word_times: generate()'s, with return_segments=True (without: ValueError): every segment gains `words`, its chunk's words shifted into the joined result
         through the segment's start / src_start and clipped to [start, stop); the device batches of such a call run one after the other."""
-        fmt = ops.check_format(sample_rate, encoding)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
-        a["words"], a["guard"] = self._long_word_mode(word_times, max_pause, return_segments), self._guard_kw(guard)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                              max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
@@ -1156,12 +1119,11 @@ class ChatterboxTTS(_LlamaTTS):
         word_times: NOT taken -- it stands in the signature only because that is generate_long's plus the ramp; anything but False is a TypeError: a stream has
         no finished token sequence for the alignment pass."""
         _no_word_times("generate_long_stream", word_times)
-        fmt = ops.check_format(sample_rate, encoding)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, guard=guard)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"], a["pitch"], a["guard"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch), self._guard_kw(guard)
         ramp = _long_stream_args(first_batch, batch_growth)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), opts, ramp)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
                        min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
@@ -1179,9 +1141,10 @@ class ChatterboxTTS(_LlamaTTS):
         loudness (None, a number for every request, or a sequence of B numbers / Nones in [-50, -5]): request b's LUFS target, generate(loudness=)'s; a None entry
         leaves that request as it is; it travels with its request through the sub-batches like its speed.
         This is the contract of generate_batch of every class of this module; the others say only what differs."""
+        texts = _batch_of(texts)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, word_times, guard)
+        return self._generate_batch(texts, None, audio_prompt_paths, conds, samp, dict(exaggeration=exaggeration), opts)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                         cfg_weight=0.5, temperature=0.8, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None, seed=None, sample_rate=None, encoding=None, speed=1.0):
@@ -1192,11 +1155,10 @@ class ChatterboxTTS(_LlamaTTS):
         checked, with the window it asks for (engine.check_stream_window), when this is called.  sample_rate, encoding: generate()'s -- every round's new samples
         are converted ahead of the round's copy to the host (one ops.WaveFormatStream for the stream); the pieces add up to the conversion of the whole utterance.
         This is the contract of generate_stream of the three TTS classes; the others say only what differs."""
-        fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = _seed_kw(seed)
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding)
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), fmt, temperature=temperature,
-                                     cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
+        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), opts, temperature=temperature,
+                                     cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
 
 def _language(language_id, request=""):
@@ -1247,26 +1209,21 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
                  word_times=False, guard=None):
         """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
         token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness, word_times, guard: as there."""
-        fmt = ops.check_format(sample_rate, encoding)
-        word_mode = self._word_mode(word_times, max_pause)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch), **self._guard_kw(guard))
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard)
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate(self._text_ids(text, lid), fmt, word_mode, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p,
-                              top_p=top_p, **seed_kw)
+        return self._generate(self._text_ids(text, lid), opts, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                       return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False,
                       guard=None):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
-        fmt = ops.check_format(sample_rate, encoding)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
-        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
-        a["words"], a["guard"] = self._long_word_mode(word_times, max_pause, return_segments), self._guard_kw(guard)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness)
+        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
 
     def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                              top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
@@ -1274,33 +1231,32 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
                              first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         _no_word_times("generate_long_stream", word_times)
-        fmt = ops.check_format(sample_rate, encoding)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, guard=guard)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
-        a["pauses"], a["pitch"], a["guard"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch), self._guard_kw(guard)
         ramp = _long_stream_args(first_batch, batch_growth)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), fmt, loudness, ramp)
+        return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), opts, ramp)
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
                        word_times=False, guard=None):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
         speed, before the sampling arguments)."""
+        texts = _batch_of(texts)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(exaggeration=exaggeration),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, word_times, guard)
+        return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, samp, dict(exaggeration=exaggeration), opts)
 
     def generate_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                         repetition_penalty=1.2, min_p=0.05, top_p=1.0, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
                         seed=None, sample_rate=None, encoding=None, speed=1.0):
         """ChatterboxTTS.generate_stream with generate()'s language_id."""
-        fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = _seed_kw(seed)
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding)
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
-        return self._generate_stream(self._text_ids(text, lid), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), fmt,
-                                     temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p, **seed_kw)
+        return self._generate_stream(self._text_ids(text, lid), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), opts,
+                                     temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
 
 class ChatterboxTurboTTS(_TTS):
@@ -1380,54 +1336,52 @@ class ChatterboxTurboTTS(_TTS):
                  temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed, sample_rate, encoding, loudness: as
         ChatterboxTTS.generate."""
-        fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
         self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
         self._warn_ignored(cfg_weight, exaggeration, min_p)
-        return self._generate(self._text_ids(text), fmt, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
+        return self._generate(self._text_ids(text), opts, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                       top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                       return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """ChatterboxTTS.generate_long on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other)."""
-        fmt = ops.check_format(sample_rate, encoding)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
-        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), fmt,
-                                   loudness, norm_loudness=norm_loudness)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), opts,
+                                   norm_loudness=norm_loudness)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                              top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None,
                              speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other, so a piece is
         yielded before the next batch starts)."""
-        fmt = ops.check_format(sample_rate, encoding)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
-        a["pauses"], a["pitch"] = _pauses(max_pause, pause_db, 1, one=True), _one_pitch(speed, pitch)
         ramp = _long_stream_args(first_batch, batch_growth)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
-        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), fmt,
-                                   loudness, ramp, norm_loudness=norm_loudness)
+        return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), opts,
+                                   ramp, norm_loudness=norm_loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
                        top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
         """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
         of B).  CFG, min_p and exaggeration are ignored with generate()'s warning.  Sub-batches run one after the other."""
+        texts = _batch_of(texts)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
-        return self._generate_batch(texts, None, audio_prompt_paths, conds, generator, seeds, speed, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
-                                    ops.check_format(sample_rate, encoding), loudness, (max_pause, pause_db), pitch, norm_loudness=norm_loudness)
+        return self._generate_batch(texts, None, audio_prompt_paths, conds, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), opts,
+                                    norm_loudness=norm_loudness)
 
     def generate_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
                         temperature=0.8, top_k=1000, norm_loudness=True, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, overlap=True, window=None,
                         seed=None, sample_rate=None, encoding=None, speed=1.0):
         """ChatterboxTTS.generate_stream on the Turbo / Nano backbone (TurboEngine.synthesize_stream; generate()'s sampling arguments)."""
-        fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = _seed_kw(seed)
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding)
         self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
         self._warn_ignored(cfg_weight, exaggeration, min_p)
-        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), fmt, temperature=temperature,
-                                     top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, **seed_kw)
+        return self._generate_stream(self._text_ids(text), _stream_kw(first_chunk, chunk, chunk_growth, lookahead, fade, overlap, window, speed), opts, temperature=temperature,
+                                     top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
 
 
 class ChatterboxVC(_Finish):
@@ -1506,10 +1460,9 @@ class ChatterboxVC(_Finish):
         int16 / int32 / float32 array of interleaved frames in one of ops.WAVE_IN_ENCODINGS; with self.audio_in = "device" it is decoded and resampled on the device
         (a path then opens G.711 and 24-bit WAVs too).  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
         are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding, loudness: as there."""
-        fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_speed_kw(speed), **_loudness_kw(loudness), **_pause_kw(max_pause, pause_db), **_pitch_kw(speed, pitch))
-        wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **seed_kw, **self._engine_format(fmt))
-        return self._finish(wavs[0], fmt)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
+        wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **opts.kw([0]))
+        return self._finish(wavs[0], opts.fmt)
 
     def generate_stream(self, audio=None, target_voice_path=None, s3_tokens=None, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=200, seed=None, sample_rate=None, encoding=None, speed=1.0):
         """generate() in pieces (the engine's vocode_stream): a generator of CPU float32 tensors (1, n) at `.sr`, the first after `first_chunk` tokens of
@@ -1521,8 +1474,8 @@ class ChatterboxVC(_Finish):
         speed (a number in [0.5, 2.0]): generate(speed=)'s speaking rate at the bounded cost of a windowed round; the pieces add up to generate(speed=)'s length.
         sample_rate, encoding: as ChatterboxTTS.generate_stream."""
         from .engine import check_stream_window
-        fmt = ops.check_format(sample_rate, encoding)
-        seed_kw = dict(_seed_kw(seed), **_stream_speed_kw(speed), **self._engine_format(fmt))
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding)
+        seed_kw = dict(opts.kw([0]), **_stream_speed_kw(speed))
         for name, v, lo in (("first_chunk", first_chunk, 1), ("chunk", chunk, 1), ("lookahead", lookahead, 0), ("fade", fade, 0)):
             if isinstance(v, bool) or not isinstance(v, int) or v < lo:
                 raise ValueError(f"{name}={v!r}: expected an int >= {lo}")
@@ -1537,7 +1490,7 @@ class ChatterboxVC(_Finish):
         ref = self.ref_dict  # (the voice of THIS call: a later set_target_voice does not reach into a running stream)
 
         return self._stream_pieces(self.engine.vocode_stream([toks], ref, first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead,
-                                                             fade=fade, window=window, **seed_kw), fmt)
+                                                             fade=fade, window=window, **seed_kw), opts.fmt)
 
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 
@@ -1549,18 +1502,12 @@ class ChatterboxVC(_Finish):
         Never overwrites self.ref_dict.  seeds, speed: per request as ChatterboxTTS.generate_batch states them -- request b's noise is that of
         generate(seed=seeds[b]), its speaking rate generate(speed=speed[b])'s; sample_rate, encoding: one format for the call; loudness: a LUFS target for every
         request or one number / None per request, as there."""
-        fmt = ops.check_format(sample_rate, encoding)
         src = s3_tokens if s3_tokens is not None else audios
         assert src is not None, "give audios or s3_tokens"
         src = [src] if (isinstance(src, _PATH) or (torch.is_tensor(src) and src.dim() <= 1)) else list(src)
         B = len(src)
         assert B >= 1, "empty batch"
-        seeds = _batch_seeds(seeds, B)
-        speed = ops.check_speed(speed, B)
-        loud = ops.check_loudness(loudness, B)
-        pz = _pauses(max_pause, pause_db, B)
-        pit = ops.check_pitch(pitch, B)
-        ops.check_speed_pitch(speed, pit, B)
+        opts = _Options(self, B, False, seeds=seeds, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
         if target_voice_paths is not None and ref_dicts is not None:
             raise ValueError("give target_voice_paths or ref_dicts, not both")
         if target_voice_paths is not None:
@@ -1578,11 +1525,7 @@ class ChatterboxVC(_Finish):
         toks = [torch.as_tensor(t).view(-1).long().cpu() for t in src]
         out = [None] * B
         for idx in batch_plan([int(t.numel()) for t in toks], int(self.MAX_BATCH)):
-            wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **({} if seeds is None else dict(seeds=_pick(seeds, idx))),
-                                         **({} if speed is None else dict(speed=_pick(speed, idx))), **self._engine_format(fmt),
-                                         **({} if loud is None or all(v is None for v in _pick(loud, idx)) else dict(loudness=_pick(loud, idx))),
-                                         **({} if pz is None or not any(_pick(pz["keep"], idx)) else dict(pauses=dict(pz, keep=_pick(pz["keep"], idx)))),
-                                         **({} if pit is None or not any(_pick(pit, idx)) else dict(pitch=_pick(pit, idx))))
+            wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **opts.kw(idx))
             for i, w in zip(idx, wavs):
-                out[i] = self._finish(w, fmt)
+                out[i] = self._finish(w, opts.fmt)
         return out

@@ -10,6 +10,8 @@ import math
 import os
 import time
 import warnings
+from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -70,41 +72,18 @@ def _valid_tokens(toks):
 
 
 def _checked_job(job):
-    """A job of synthesize_pipelined with its optional keys checked as synthesize checks its arguments: seeds (ops.request_seeds; not together with the job's
-    generator), speed (ops.check_speed), join (ops.check_join), format (ops.check_format_arg), loudness (ops.check_loudness; not together with a join).  A join of
-    None is dropped: from here on `"join" in job` says whether the job is joined; likewise a format that is None or the default (24 kHz fp32), a loudness that
-    normalises no utterance, pauses (ops.check_pauses) that shorten no utterance and a pitch (ops.check_pitch; with the job's speed: ops.check_speed_pitch) that
-    transposes no utterance."""
-    n = len(job["text_tokens"])
+    """A job of synthesize_pipelined with its optional keys checked as synthesize checks its arguments (check_delivery: seeds not together with the job's
+    generator, loudness not together with a join, speed x pitch).  A join of None is dropped: from here on `"join" in job` says whether the job is joined;
+    likewise a format that is None or the default (24 kHz fp32), a loudness that normalises no utterance, pauses that shorten no utterance, a pitch that
+    transposes no utterance and a guard of None.  seeds and speed keep their key when the job has one."""
     if job.get("words") is not None:
         raise ValueError(WORDS_PIPELINED)
-    job = {k: v for k, v in job.items() if k not in ("join", "format", "loudness", "pauses", "pitch", "words", "guard") or v is not None}
-    if "pitch" in job:
-        job["pitch"] = ops.check_pitch(job["pitch"], n)
-        if job["pitch"] is None:
-            del job["pitch"]
-        else:
-            ops.check_speed_pitch(job.get("speed"), job["pitch"], n)
-    if "pauses" in job:
-        job["pauses"] = ops.check_pauses(job["pauses"], n)
-        if job["pauses"] is None:
-            del job["pauses"]
-    if "loudness" in job:
-        job["loudness"] = ops.check_loudness(job["loudness"], n)
-        if job["loudness"] is None:
-            del job["loudness"]
-        elif "join" in job:
-            raise ValueError(LOUDNESS_JOIN)
-    if "format" in job:
-        job["format"] = ops.check_format_arg(job["format"])
-        if job["format"] is None:
-            del job["format"]
-    if job.get("seeds") is not None:
-        job["seeds"] = ops.request_seeds(job["seeds"], n, job.get("generator"))
-    if job.get("speed") is not None:
-        job["speed"] = ops.check_speed(job["speed"], n)
-    if "join" in job:
-        job["join"] = ops.check_join(job["join"], n)
+    d = check_delivery(len(job["text_tokens"]), **{k: job.get(k) for k in ("seeds", "generator", "speed") + Delivery.OPTIONS})
+    job = {k: v for k, v in job.items() if k not in Delivery.OPTIONS + ("words",) and not (k == "guard" and v is None)}
+    job.update(d.kw())
+    for k, v in (("seeds", d.seeds), ("speed", d.speed)):
+        if job.get(k) is not None:
+            job[k] = v
     return job
 
 
@@ -152,6 +131,51 @@ def frame_sample(f, speed=None, pitch=None):
 
 
 LOUDNESS_JOIN = "loudness together with join: a long text is normalised as a whole, after its pieces are assembled (generate_long(loudness=))"
+
+
+@dataclass(frozen=True)
+class Delivery:
+    """The delivery options of one engine call for B utterances, checked and normalised (check_delivery): seeds (B ints), speed (B floats), pitch (B semitones),
+    rates (the B rates at which the mel is stretched: speed, or speed / 2^(pitch / 12) under a pitch), join (ops.check_join's dict), fmt (ops.check_format's
+    dict), loud (B LUFS targets / Nones), pz (ops.check_pauses' dict).  Each is None when the option is off for every utterance -- the call is then, launch for
+    launch, the call without it."""
+    seeds: Optional[list] = None
+    speed: Optional[list] = None
+    pitch: Optional[list] = None
+    rates: Optional[list] = None
+    join: Optional[dict] = None
+    fmt: Optional[dict] = None
+    loud: Optional[list] = None
+    pz: Optional[dict] = None
+    OPTIONS = ("pitch", "join", "format", "loudness", "pauses")  # the keywords a call carries only when the option is on
+
+    def kw(self):
+        """The OPTIONS as the keywords of a downstream call (vocode, a job of synthesize_pipelined): a key is present only when its option is on.  seeds and speed
+        are not among them: they travel as they were given."""
+        return {k: v for k, v in zip(self.OPTIONS, (self.pitch, self.join, self.fmt, self.loud, self.pz)) if v is not None}
+
+
+def check_delivery(B, *, seeds=None, generator=None, speed=None, pitch=None, join=None, format=None, loudness=None, pauses=None):
+    """The one place where an engine entry (vocode, both synthesize methods, a job of synthesize_pipelined) checks its delivery options -> Delivery.  In this
+    order: seeds (ops.request_seeds; not together with a generator), speed, pitch with the speed x pitch rule (ops.check_speed_pitch), join, format, loudness
+    (not together with a join: LOUDNESS_JOIN), pauses.  TypeError / ValueError before anything is launched; a checked value passes unchanged."""
+    seeds = ops.request_seeds(seeds, B, generator)
+    speed = ops.check_speed(speed, B)
+    pitch = ops.check_pitch(pitch, B)
+    eff = ops.check_speed_pitch(speed, pitch, B)
+    join = ops.check_join(join, B)
+    fmt = ops.check_format_arg(format)
+    loud = ops.check_loudness(loudness, B)
+    if loud is not None and join is not None:
+        raise ValueError(LOUDNESS_JOIN)
+    rates = speed if eff is None else (None if all(e == 1.0 for e in eff) else eff)
+    return Delivery(seeds, speed, pitch, rates, join, fmt, loud, ops.check_pauses(pauses, B))
+
+
+def _joined_on_host(out, rec, n, fmt, pauses, truncated):
+    """What synthesize(join=) and a joined job of synthesize_pipelined return once the piece is readable on the host: ops.piece_on_host's dict, plus truncated and,
+    with pauses, the record {n', pauses cut, frames removed, n} per chunk as lists"""
+    return dict(ops.piece_on_host(out, rec, n, fmt), truncated=truncated, **({} if pauses is None else dict(pauses=pauses.tolist())))
 
 
 class S3GenEngine:
@@ -217,19 +241,8 @@ class S3GenEngine:
         every frequency multiplied by r_b.  The formants move with the pitch.  The launch runs ahead of the loudness step, the pauses, the join and the format
         launch, which see its rows (views of one packed buffer; a row without a pitch is copied)."""
         B = len(speech_tokens)
-        seeds = ops.request_seeds(seeds, B, generator)
-        speed = ops.check_speed(speed, B)
-        join = ops.check_join(join, B)
-        fmt = ops.check_format_arg(format)
-        loud = ops.check_loudness(loudness, B)
-        if loud is not None and join is not None:
-            raise ValueError(LOUDNESS_JOIN)
-        pz = ops.check_pauses(pauses, B)
-        pitch = ops.check_pitch(pitch, B)
-        rates = speed  # at which the mel is stretched
-        if pitch is not None:
-            eff = ops.check_speed_pitch(speed, pitch, B)
-            rates = None if all(e == 1.0 for e in eff) else eff
+        d = check_delivery(B, seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses)
+        seeds, rates = d.seeds, d.rates
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
         tok = torch.zeros(B, Nmax, dtype=torch.long)
@@ -270,47 +283,47 @@ class S3GenEngine:
             return wav, mel
 
         wav, mel = _range_checked(self, run, check=sync)
+        return self._deliver(wav, ns, shorts, d, drop_last_token, sync, hift_stream), mel
+
+    def _deliver(self, wav, ns, shorts, d, drop_last_token, sync, hift_stream):
+        """The chain behind the vocoder, in the one order vocode's docstring states: cut the rows of the padded batch `wav`, pitch, loudness, then either edges +
+        squeeze + join (ONE ops.wave_join call) or the squeeze alone, then the format.  Every launch lands on the stream that owns the waveforms: ONE stream
+        scope, entered only when a step is on.  Returns the rows; the formatted views; with pauses the rows cut through ops.cut_pauses (sync=True) or
+        dict(rows=, pauses=, format=) for the caller to cut (sync=False); with a join the piece dict, with `formatted` / `format` under a format."""
+        HALF = SAMPLES_PER_TOKEN // 2
         out, plain = [], []
         for b, n in enumerate(ns):
             keep = max(1, n - 1) if drop_last_token else n
             frames = min(2 * keep, 2 * n - shorts[b])  # K_b: what the unscaled call returns, in mel frames of 480 samples
-            if pitch is not None:
-                plain.append(ops.scaled_len(frames, speed[b]) if speed is not None else frames)
-            if rates is not None:
-                frames = ops.scaled_len(frames, rates[b])
-            out.append(wav[b, : frames * (SAMPLES_PER_TOKEN // 2)])
-        if pitch is not None:  # the source rows, read at a step of r_b into the lengths of the call without a pitch
-            with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
-                out = ops.wave_pitch(out, [ops.pitch_ratio(p) for p in pitch], [k * (SAMPLES_PER_TOKEN // 2) for k in plain])
-        if loud is not None:
-            with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
-                self.last_loudness = ops.wave_normalize(out, loud)
-        if pz is not None:
-            with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
-                if join is not None:
-                    cap = sum(int(w.numel()) for w in out) + sum(join["gaps"])
-                    piece = ops.wave_join(out, squeeze=pz, **({} if fmt is None else dict(out=torch.zeros(max(1, cap), device=wav.device))), **join)
+            if d.pitch is not None:
+                plain.append(ops.scaled_len(frames, d.speed[b]) if d.speed is not None else frames)
+            if d.rates is not None:
+                frames = ops.scaled_len(frames, d.rates[b])
+            out.append(wav[b, : frames * HALF])
+        if not d.kw():
+            return out
+        with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
+            if d.pitch is not None:  # the source rows, read at a step of r_b into the lengths of the call without a pitch
+                out = ops.wave_pitch(out, [ops.pitch_ratio(p) for p in d.pitch], [k * HALF for k in plain])
+            if d.loud is not None:
+                self.last_loudness = ops.wave_normalize(out, d.loud)
+            if d.join is not None:  # (a join that will be formatted writes into a zeroed buffer: converting all of it converts the piece)
+                cap = sum(int(w.numel()) for w in out) + sum(d.join["gaps"])
+                piece = ops.wave_join(out, **({} if d.pz is None else dict(squeeze=d.pz)), **({} if d.fmt is None else dict(out=torch.zeros(max(1, cap), device=wav.device))),
+                                      **d.join)
+                if d.pz is not None:
                     self.last_pauses = piece["pauses"]
-                    return (piece if fmt is None else dict(piece, formatted=ops.wave_format([piece["out"]], fmt)[0], format=fmt)), mel
-                sq = ops.wave_squeeze(out, pz["keep"], pz["db"], pz["fade"])
-                self.last_pauses = sq["stats"]
-                rows = sq["rows"] if fmt is None else ops.wave_format(sq["rows"], fmt)
-                if not sync:
-                    return dict(rows=rows, pauses=sq["stats"], format=fmt), mel
-                return ops.cut_pauses(rows, sq["stats"].cpu(), fmt), mel
-        if join is not None and fmt is None:
-            if hift_stream is not None:
-                with torch.cuda.stream(hift_stream):
-                    return ops.wave_join(out, **join), mel
-            return ops.wave_join(out, **join), mel
-        if fmt is not None:
-            with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
-                if join is None:
-                    return ops.wave_format(out, fmt), mel
-                cap = sum(int(w.numel()) for w in out) + sum(join["gaps"])
-                piece = ops.wave_join(out, out=torch.zeros(max(1, cap), device=wav.device), **join)
-                return dict(piece, formatted=ops.wave_format([piece["out"]], fmt)[0], format=fmt), mel
-        return out, mel
+                return piece if d.fmt is None else dict(piece, formatted=ops.wave_format([piece["out"]], d.fmt)[0], format=d.fmt)
+            stats = None
+            if d.pz is not None:
+                sq = ops.wave_squeeze(out, d.pz["keep"], d.pz["db"], d.pz["fade"])
+                out, stats = sq["rows"], sq["stats"]
+                self.last_pauses = stats
+            if d.fmt is not None:
+                out = ops.wave_format(out, d.fmt)
+            if stats is None:
+                return out
+            return ops.cut_pauses(out, stats.cpu(), d.fmt) if sync else dict(rows=out, pauses=stats, format=d.fmt)
 
     def co_resident(self, on):
         """Both stages on (or off) the kernel forms whose workgroups can share a CU with the other stage's (T3Engine.co_resident, FlowEngine.co_resident)."""
@@ -419,16 +432,8 @@ class ChatterboxEngine(S3GenEngine):
             if len(text_tokens) > self.t3.MAX_BATCH:
                 raise ValueError(f"words: {len(text_tokens)} utterances (at most {self.t3.MAX_BATCH}: the pass runs on the state of ONE device batch)")
             self.t3.check_align_heads(words["heads"])
-        seeds = ops.request_seeds(seeds, len(text_tokens), generator)
-        speed = ops.check_speed(speed, len(text_tokens))
-        pitch = ops.check_pitch(pitch, len(text_tokens))
-        ops.check_speed_pitch(speed, pitch, len(text_tokens))
-        join = ops.check_join(join, len(text_tokens))
-        fmt = ops.check_format_arg(format)
-        loud = ops.check_loudness(loudness, len(text_tokens))
-        if loud is not None and join is not None:
-            raise ValueError(LOUDNESS_JOIN)
-        pz = ops.check_pauses(pauses, len(text_tokens))
+        d = check_delivery(len(text_tokens), seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses)
+        seeds = d.seeds
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_new_tokens=max_new_tokens, temperature=temperature, top_p=top_p,
@@ -445,16 +450,13 @@ class ChatterboxEngine(S3GenEngine):
             alignment = []
             for b, (sp, t) in enumerate(zip(spans, toks)):
                 c = valid_frame_counts(t)
-                alignment.append(dict(frames=[(c[f0], c[f1]) for f0, f1 in sp.tolist()], n_frames=c[-1], speed=None if speed is None else speed[b],
-                                      pitch=None if pitch is None else pitch[b]))
+                alignment.append(dict(frames=[(c[f0], c[f1]) for f0, f1 in sp.tolist()], n_frames=c[-1], speed=None if d.speed is None else d.speed[b],
+                                      pitch=None if d.pitch is None else d.pitch[b]))
             self.last_timing["align_s"] = time.perf_counter() - t1
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
-                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=speed, **({} if join is None else dict(join=join)),
-                              **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)), **({} if pz is None else dict(pauses=pz)),
-                              **({} if pitch is None else dict(pitch=pitch)))
-        if join is not None:  # (the record's copy waits for the two launches behind the vocoder)
-            wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks),
-                        **({} if pz is None else dict(pauses=wavs["pauses"].tolist())))
+                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=d.speed, **d.kw())
+        if d.join is not None:  # (the record's copy waits for the two launches behind the vocoder)
+            wavs = _joined_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], d.fmt, wavs.get("pauses"), self._truncated(toks))
         self.last_timing["total_s"] = time.perf_counter() - t0
         return (wavs, st) if alignment is None else (wavs, st, alignment)
 
@@ -534,8 +536,7 @@ class ChatterboxEngine(S3GenEngine):
             ops.piece_on_host), any other job one copy per utterance."""
             copy = (lambda w: torch.empty(w.shape, dtype=w.dtype, pin_memory=True).copy_(w, non_blocking=True)) if pinned else (lambda w: w.cpu())
             if "join" in job:
-                host = copy(wavs.get("formatted", wavs["out"])), copy(wavs["rec"]), wavs["n"], job.get("format")
-                return host + (copy(wavs["pauses"]),) if "pauses" in job else host
+                return copy(wavs.get("formatted", wavs["out"])), copy(wavs["rec"]), wavs["n"], job.get("format"), copy(wavs["pauses"]) if "pauses" in job else None
             if "pauses" in job:  # (the rows are still n long; the record that cuts them travels the same way)
                 return [copy(w) for w in wavs["rows"]], copy(wavs["pauses"]), wavs["format"]
             return [copy(w) for w in wavs]
@@ -544,7 +545,7 @@ class ChatterboxEngine(S3GenEngine):
             """What a job yields as `wavs` once `host` is readable: the waveforms, or the joined piece as its record lays it out, which also says which chunks spent
             T3's budget without EOS"""
             if "join" in job:
-                return dict(ops.piece_on_host(*host[:4]), truncated=self._truncated(toks), **({} if "pauses" not in job else dict(pauses=host[4].tolist())))
+                return _joined_on_host(*host, self._truncated(toks))
             return ops.cut_pauses(*host) if "pauses" in job else host
 
         if not host_threads:  # round 4's form: one host thread enqueues T3(k + 1), then flow + vocoder(k)
@@ -1151,16 +1152,8 @@ class TurboEngine(S3GenEngine):
         ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict; loudness: None, or vocode(loudness=)'s targets (not with a join);
         pauses: None, or vocode(pauses=)'s dict / list, as ChatterboxEngine.synthesize(pauses=) returns its results; pitch: None, or vocode(pitch=)'s semitones,
         checked against speed before anything is launched as ChatterboxEngine.synthesize(pitch=) does."""
-        seeds = ops.request_seeds(seeds, len(text_tokens), generator)
-        speed = ops.check_speed(speed, len(text_tokens))
-        pitch = ops.check_pitch(pitch, len(text_tokens))
-        ops.check_speed_pitch(speed, pitch, len(text_tokens))
-        join = ops.check_join(join, len(text_tokens))
-        fmt = ops.check_format_arg(format)
-        loud = ops.check_loudness(loudness, len(text_tokens))
-        if loud is not None and join is not None:
-            raise ValueError(LOUDNESS_JOIN)
-        pz = ops.check_pauses(pauses, len(text_tokens))
+        d = check_delivery(len(text_tokens), seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses)
+        seeds = d.seeds
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,
                                 repetition_penalty=repetition_penalty, uniforms=uniforms, ban_eos=ban_eos, ban_from=ban_from, generator=generator, seeds=seeds)
@@ -1168,12 +1161,10 @@ class TurboEngine(S3GenEngine):
         self.last_timing = dict(t3_s=time.perf_counter() - t0)
         sil = torch.full((3,), S3GEN_SIL, dtype=torch.long)
         st = [torch.cat([t[t < SPEECH_VOCAB], sil]) for t in toks]
-        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=speed,
-                              **({} if join is None else dict(join=join)), **({} if fmt is None else dict(format=fmt)), **({} if loud is None else dict(loudness=loud)),
-                              **({} if pz is None else dict(pauses=pz)), **({} if pitch is None else dict(pitch=pitch)))
-        if join is not None:
-            wavs = dict(ops.piece_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], fmt), truncated=self._truncated(toks, max_gen_len),
-                        **({} if pz is None else dict(pauses=wavs["pauses"].tolist())))
+        wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=2, drop_last_token=False, generator=generator, seeds=seeds, speed=d.speed,
+                              **d.kw())
+        if d.join is not None:
+            wavs = _joined_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], d.fmt, wavs.get("pauses"), self._truncated(toks, max_gen_len))
         self.last_timing["total_s"] = time.perf_counter() - t0
         return wavs, st
 
