@@ -285,6 +285,7 @@ _SIGS = {
     "cbx_stream_emit_f32": ([c_f, c_long, c_long, c_f, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_long, c_f, c_int, c_f], c_int),
     "cbx_rng_fill_f32": ([c_f, c_long, c_f, c_int, c_long, ctypes.c_ulonglong, c_int, c_f], c_int),
     "cbx_mel_time_scale_f32": ([c_f, c_long, c_long, c_int, c_f, c_f, c_f, c_long, c_long, c_int, c_f, c_int, c_int, c_f], c_int),
+    "cbx_mel_time_warp_f32": ([c_f, c_long, c_long, c_int, c_f, c_f, c_int, c_f, c_f, c_f, c_f, c_long, c_long, c_int, c_f, c_int, c_int, c_f], c_int),
     "cbx_mel_time_scale_win_f32": ([c_f, c_long, c_long, c_int, c_f, ctypes.c_double, c_long, c_long, c_f, c_long, c_long, c_int, c_f, c_int, c_int, c_f], c_int),
     "cbx_wave_edges_f32": ([c_f, c_f, c_f, c_int, ctypes.c_double, c_int, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_join_f32": ([c_f, c_f, c_f, c_f, c_int, c_f, c_f, c_int, c_int, c_int, c_f, c_long, c_f, c_f], c_int),

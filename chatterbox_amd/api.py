@@ -12,6 +12,7 @@ Turbo's `norm_loudness` needs `pyloudnorm` and is skipped with a warning when th
 project's own meter instead.
 """
 import contextlib
+import math
 import os
 from dataclasses import dataclass
 from pathlib import Path
@@ -271,10 +272,14 @@ class _Options:
     with the speed x pitch rule (ops.check_speed_pitch), guard.  one=True: the method serves one request (generate, generate_long, ...): a sequence for
     loudness, max_pause or pitch is then a TypeError.  segments=False (generate_long without return_segments): word_times is refused, its words travel in the
     segments.  Holds fmt (ops.check_format's dict), words (_word_times' mode), seeds, speed, loud, pitch (B entries each), pz (_pauses' dict), guard (the
-    engines' dict) -- each None when no request uses it -- and the generator; kw(idx) turns them into the engines' keywords."""
+    engines' dict) -- each None when no request uses it -- and the generator; kw(idx) turns them into the engines' keywords.
+    duration / timing (the timing control; checked last): dur holds ops.check_duration's B target lengths in frames / Nones, timing ops.check_timing's B lists of
+    word starts in frames / Nones; either is refused together with speed, pitch or max_pause (ValueError naming both).  timing needs the text: bind(tokens) --
+    called by the model once the requests are tokenised, before anything is launched -- checks the number of entries against the words of each request
+    (_TTS._word_groups) and turns them into one start per text token (`starts`), which kw(idx) hands to the engine."""
 
     def __init__(self, model, B=1, one=True, *, seeds=None, generator=None, speed=None, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0,
-                 pitch=None, word_times=False, guard=None, segments=True):
+                 pitch=None, word_times=False, guard=None, segments=True, duration=None, timing=None):
         self.model, self.one, self.generator = model, one, generator
         self.fmt = ops.check_format(sample_rate, encoding)
         self.words = None if word_times is None or word_times is False else model._word_mode(word_times, max_pause)
@@ -291,6 +296,53 @@ class _Options:
         self.pitch = ops.check_pitch(pitch, B)
         ops.check_speed_pitch(self.speed, self.pitch, B)
         self.guard = None if guard is None or guard is False else model._guard(guard)
+        if one and isinstance(duration, (list, tuple)):
+            raise TypeError(f"duration: expected None or a number of seconds, got a {type(duration).__name__}")
+        self.dur = ops.check_duration(duration, B)
+        self.timing = ops.check_timing([timing] if one and timing is not None else timing, B)
+        self.starts = None
+        if self.timing is not None and not hasattr(getattr(model, "tokenizer", None), "pieces"):
+            raise ValueError("timing needs a tokenizer with pieces(ids) to group text tokens into words (model.words(text) names them)")
+        for mine, on in (("duration", self.dur), ("timing", self.timing)):
+            for other, v in (("speed", self.speed), ("pitch", self.pitch), ("max_pause", self.pz)):
+                if on is not None and v is not None:
+                    raise ValueError(f"{mine} together with {other}: the time map fixes when things happen; combining it with {other} is not built -- give one of the two")
+
+    @property
+    def warped(self):
+        return self.dur is not None or self.timing is not None
+
+    def bind(self, tokens):
+        """The requests' engine tokens (B 1-D id tensors) -> self, with timing turned into `starts`: per request None or one output frame / None per TEXT TOKEN
+        (word i's start at its first token).  A wrong number of entries is a ValueError -- before anything is launched."""
+        if self.timing is None:
+            return self
+        self.starts = []
+        for b, (row, tok) in enumerate(zip(self.timing, tokens)):
+            if row is None:
+                self.starts.append(None)
+                continue
+            groups, texts = self.model._word_groups(tok)
+            if len(row) != len(groups):
+                raise ValueError(f"timing{'' if self.one else f'[{b}]'}: {len(row)} entries for {len(groups)} words {texts!r} (model.words(text) lists them)")
+            per_token = [None] * int(tok.numel())
+            for (a, _), t in zip(groups, row):
+                per_token[a] = t
+            self.starts.append(None if all(t is None for t in row) else per_token)
+        if all(st is None for st in self.starts):  # no word of any request has a time: the call without the argument
+            self.timing = self.starts = None
+        return self
+
+    def warp_kw(self, idx):
+        """The engines' warp= list over the requests `idx`, or None when none of them is warped"""
+        if not self.warped:
+            return None
+        assert self.timing is None or self.starts is not None, "timing: bind(tokens) comes first"
+        out = []
+        for i in idx:
+            d, st = None if self.dur is None else self.dur[i], None if self.starts is None else self.starts[i]
+            out.append(dict(starts=st, end=d) if st is not None else (None if d is None else dict(frames=d)))
+        return None if all(w is None for w in out) else out
 
     def kw(self, idx, chunks=False):
         """The engines' keywords of a call or job over the requests `idx`, the call without an option being exactly the call before there was one: seeds and speed
@@ -312,10 +364,12 @@ class _Options:
             kw["pitch"] = rows(self.pitch)
         if self.fmt is not None and not chunks and self.model.watermarker is None:
             kw["format"] = self.fmt
-        if self.words is not None:
+        if self.words is not None or self.timing is not None:  # (timing implies the alignment pass: one setting for the call)
             kw["words"] = dict(heads=self.model.align_heads)
         if self.guard is not None:
             kw["guard"] = self.guard
+        if not chunks and self.warp_kw(idx) is not None:
+            kw["warp"] = self.warp_kw(idx)
         return kw
 
 
@@ -566,6 +620,16 @@ def _no_word_times(method, word_times):
 class _Finish:
     """The epilogue of every public method that returns audio, and the `audio_in` switch of every method that takes audio."""
     sr = S3GEN_SR
+    last_fit = None  # per request of the last call with duration= / timing=, in the caller's order: None (a plain request) or the engine's fit report
+
+    def _take_fit(self, reports, who):
+        """model.last_fit = the engine's fit reports (engine._fit_report) in the caller's order; one UserWarning names the requests whose targets were not met"""
+        self.last_fit = reports
+        odd = [(i, r) for i, r in enumerate(reports) if r is not None and r["clamped"]]
+        if odd:
+            import warnings
+            warnings.warn(f"{who}: the time map of request(s) " + ", ".join(f"{i} (asked {r['target']} frames, got {r['frames']}; missed: {r['clamped']})" for i, r in odd)
+                          + " was clamped to rates in [0.5, 2.0]: nothing is padded or cut (model.last_fit has the plan)", UserWarning, stacklevel=3)
 
     @property
     def audio_in(self):
@@ -706,11 +770,29 @@ class _TTS(_Finish):
         if not groups:
             return []
         fr = al["frames"]
-        at = lambda f: int(place(frame_sample(f, al["speed"], al["pitch"])))
+        if al.get("table") is not None:  # a warped utterance: token frame f is mel frame 2 f, which the map places (exactly on the target at an anchor)
+            at = lambda f: int(place(int(math.floor(ops.warp_place(al["table"], 2 * f) * 480 + 0.5))))
+        else:
+            at = lambda f: int(place(frame_sample(f, al["speed"], al["pitch"])))
         starts = [at(fr[a][0]) for a, _ in groups]
         stops = starts[1:] + [max(starts[-1], at(fr[groups[-1][1] - 1][1]))]
         return [dict(text="".join(pieces[a:b]).replace(space, " ").strip() if mode == "words" else pieces[a], start=s0, stop=s1, tokens=(a, b),
                      frames=(fr[a][0], fr[b - 1][1])) for (a, b), s0, s1 in zip(groups, starts, stops)]
+
+    def _word_groups(self, tokens):
+        """The engine's 1-D text ids -> ([(a, b) token range per word], [the word strings]) exactly as word_times="words" groups and names them"""
+        ids = [int(i) for i in tokens.view(-1).tolist()]
+        pieces = self.tokenizer.pieces(ids)
+        space = getattr(self.tokenizer, "SPACE", "[SPACE]")
+        groups = word_groups(pieces, space)
+        return groups, ["".join(pieces[a:b]).replace(space, " ").strip() for a, b in groups]
+
+    def words(self, text, language_id=None):
+        """The words of `text` as word_times="words" groups them (text.word_groups over the tokenizer's pieces), as strings in text order: what `timing=` takes one
+        entry for.  Nothing is launched."""
+        if not hasattr(self.tokenizer, "pieces"):
+            raise ValueError("words() needs a tokenizer with pieces(ids)")
+        return self._word_groups(self._engine_tokens(self._text_ids(text, language_id)))[1]
 
     @staticmethod
     def _place(n_out, fmt):
@@ -749,9 +831,12 @@ class _TTS(_Finish):
         option); kw: sampling arguments, and _synth_kw's if they are to differ.  With a guard last_guard is the request's report."""
         opts = opts or _Options(self)
         tokens = self._engine_tokens(text_ids)
+        opts.bind([tokens])
         res = self.engine.synthesize([tokens], self.conds.t3.as_dict(), self.conds.gen, **dict(self._synth_kw(), **kw), **opts.kw([0]))
         if opts.guard is not None:
             self._take_guard(list(self.engine.last_guard), "generate")
+        if opts.warped:
+            self._take_fit(list(getattr(self.engine, "last_fit", None) or [None]), "generate")
         wav = self._finish(res[0][0], opts.fmt)
         return wav if opts.words is None else (wav, self._words_of(opts.words, tokens, res[2][0], self._place(wav.shape[-1], opts.fmt)))
 
@@ -790,7 +875,7 @@ class _TTS(_Finish):
         self._warn_ignored(*(v for vals in unsampled.values() for v in vals))
         voices = self._voices_of_batch(B, audio_prompt_paths, conds, unsampled["exaggeration"], **analyse_kw)
         tokens = [self._engine_tokens(self._text_ids(t, lid)) for t, lid in zip(texts, langs)]
-        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, opts)
+        return self._run_batch(tokens, voices, unsampled["exaggeration"], samp, opts.bind(tokens))
 
     def _languages(self, language_ids, B):
         return [None] * B
@@ -811,17 +896,22 @@ class _TTS(_Finish):
                 job["uniforms"] = torch.rand(len(idx), self.N_DRAWS, device=self.engine.dev, generator=opts.generator)
                 job["generator"] = opts.generator
             jobs.append(dict(job, **opts.kw(idx)))
-        out, reports = [None] * len(tokens), [None] * len(tokens)
+        out, reports, fits = [None] * len(tokens), [None] * len(tokens), [None] * len(tokens)
         for idx, res in zip(plan, self._run_jobs(jobs, self._synth_kw(batch=True))):
             if opts.guard is not None:
                 for i, r in zip(idx, self.engine.last_guard):
                     reports[i] = r
+            if opts.warp_kw(idx) is not None:
+                for i, r in zip(idx, getattr(self.engine, "last_fit", None) or [None] * len(idx)):
+                    fits[i] = r
             for r, (i, w) in enumerate(zip(idx, res[0])):
                 out[i] = self._finish(w, opts.fmt)
                 if opts.words is not None:
                     out[i] = (out[i], self._words_of(opts.words, tokens[i], res[2][r], self._place(out[i].shape[-1], opts.fmt)))
         if opts.guard is not None:
             self._take_guard(reports, "generate_batch")
+        if opts.warped:
+            self._take_fit(fits, "generate_batch")
         return out
 
     def _generate_long(self, text, language_id, audio_prompt_path, a, return_segments, samp, unsampled, opts, ramp=None, **prepare_kw):
@@ -1010,7 +1100,7 @@ class ChatterboxTTS(_LlamaTTS):
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                  cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                 word_times=False, guard=None):
+                 word_times=False, guard=None, duration=None, timing=None):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
         alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
         speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
@@ -1062,9 +1152,25 @@ class ChatterboxTTS(_LlamaTTS):
         token budget.  Opt-in; None is the call without the argument, launch for launch.  generate_batch: one setting for the call.  generate_long /
         generate_long_stream: every chunk is guarded, with return_segments its report travels in its segment as `guard`.  generate_stream, ChatterboxTurboTTS and
         ChatterboxVC do not take the argument: round streams and the GPT-2 backbone are not built.
-        This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db`, `pitch`, `word_times` and `guard` for every method
+        duration (None, or seconds in [0.02, 80]): timing control, the length.  The number of speech tokens is known before the flow runs, so the K mel frames
+        the plain call would return are fitted into O = floor(50 duration + 0.5) frames by ONE launch between the flow and the vocoder (ops.mel_time_warp,
+        cbx_mel_time_warp_f32) that stretches the mel at rate K / O; the F0 predictor runs on the stretched mel, so the pitch is kept, and T3 and its tokens do
+        not depend on it.  The result has exactly O * 480 samples at 24 kHz whenever K / O lies in [0.5, 2.0] (then through sample_rate= / encoding= as ever);
+        otherwise the rate is held at the bound, the result has the length that gives -- nothing is padded or cut --, a UserWarning names the request and
+        model.last_fit[b] = dict(target, frames, rate=(min, max), clamped, table) says so.  Not together with speed, pitch or max_pause (ValueError); not on the
+        streams or generate_long.  generate_batch: a number, or one number / None per request.
+        timing (None, or a list with one entry per word of the text -- model.words(text) lists them --, each None or the word's START in seconds, nondecreasing):
+        timing control, the words.  Honoured on the 20 ms frame grid: after T3 the alignment pass of word_times= says at which mel frame x_i word i begins, and the
+        anchors (x_i, floor(50 t_i + 0.5)) become a piecewise-linear time map (ops.warp_plan) applied by the same one launch; every segment's rate is held in
+        [0.5, 2.0], so a target that needs more is met as closely as the bound allows (UserWarning, last_fit[b]["clamped"] / ["achieved"]) and a later word still
+        aims at its own target.  A word that begins at frame 0 cannot be moved (there is nothing in front of it to stretch: no lead-in silence is inserted).
+        duration= may be given with it and fixes the end.  It implies the alignment pass, so the call runs the serial schedule, and it inherits that pass's
+        UNMEASURED default ALIGN_HEADS exactly as word_times= does: nobody has checked on trained weights here that those heads track the words.  With word_times=
+        in the same call the returned words are the achieved ones, mapped through the time map (ops.warp_place).  A wrong number of entries is a ValueError
+        before anything is launched.  generate_batch: a list of such lists / Nones.  Not on Turbo (its GPT-2 backbone has no alignment pass) or voice conversion.
+        This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db`, `pitch`, `word_times`, `guard`, `duration` and `timing` for every method
         of every class of this module; the others say only what differs."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text), opts, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
@@ -1127,7 +1233,7 @@ class ChatterboxTTS(_LlamaTTS):
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
                        min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                       word_times=False, guard=None):
+                       word_times=False, guard=None, duration=None, timing=None):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
         request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
         neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
@@ -1142,7 +1248,7 @@ class ChatterboxTTS(_LlamaTTS):
         leaves that request as it is; it travels with its request through the sub-batches like its speed.
         This is the contract of generate_batch of every class of this module; the others say only what differs."""
         texts = _batch_of(texts)
-        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, samp, dict(exaggeration=exaggeration), opts)
 
@@ -1206,10 +1312,10 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                  repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                 word_times=False, guard=None):
+                 word_times=False, guard=None, duration=None, timing=None):
         """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
         token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness, word_times, guard: as there."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text, lid), opts, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
@@ -1240,11 +1346,11 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                       word_times=False, guard=None):
+                       word_times=False, guard=None, duration=None, timing=None):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
         speed, before the sampling arguments)."""
         texts = _batch_of(texts)
-        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, samp, dict(exaggeration=exaggeration), opts)
 
@@ -1333,10 +1439,10 @@ class ChatterboxTurboTTS(_TTS):
         return dict(max_gen_len=1000) if batch else {}
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
-                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None):
         """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed, sample_rate, encoding, loudness: as
         ChatterboxTTS.generate."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
         self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
         self._warn_ignored(cfg_weight, exaggeration, min_p)
         return self._generate(self._text_ids(text), opts, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
@@ -1364,11 +1470,11 @@ class ChatterboxTurboTTS(_TTS):
                                    ramp, norm_loudness=norm_loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
-                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None):
         """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
         of B).  CFG, min_p and exaggeration are ignored with generate()'s warning.  Sub-batches run one after the other."""
         texts = _batch_of(texts)
-        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), opts,
                                     norm_loudness=norm_loudness)
@@ -1455,13 +1561,17 @@ class ChatterboxVC(_Finish):
             s3_tokens = self._tokens_of(audio)
         return torch.as_tensor(s3_tokens).view(-1).long().cpu()
 
-    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None):
         """reference vc.py:83-104.  audio: a WAV path, a (waveform, sample_rate) pair or raw samples (data, sample_rate, encoding[, channels]) -- bytes or a uint8 /
         int16 / int32 / float32 array of interleaved frames in one of ops.WAVE_IN_ENCODINGS; with self.audio_in = "device" it is decoded and resampled on the device
         (a path then opens G.711 and 24-bit WAVs too).  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
-        are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding, loudness: as there."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
+        are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding, loudness: as there.
+        duration (None, or seconds in [0.02, 80]): ChatterboxTTS.generate(duration=)'s -- the conversion is fitted into that length; not with speed, pitch or
+        max_pause; model.last_fit has the plan."""
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
         wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **opts.kw([0]))
+        if opts.warped:
+            self._take_fit(list(self.engine.last_fit), "generate")
         return self._finish(wavs[0], opts.fmt)
 
     def generate_stream(self, audio=None, target_voice_path=None, s3_tokens=None, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, window=200, seed=None, sample_rate=None, encoding=None, speed=1.0):
@@ -1494,7 +1604,7 @@ class ChatterboxVC(_Finish):
 
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 
-    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None):
         """generate() for B conversions in one call: `audios` (WAV paths, (waveform, sample_rate) pairs or raw (data, sample_rate, encoding[, channels]) tuples; with
         audio_in = "device" the sources of one (rate, encoding, channels) are uploaded and converted together) or `s3_tokens` (B id sequences); target voice per
         request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
@@ -1507,7 +1617,7 @@ class ChatterboxVC(_Finish):
         src = [src] if (isinstance(src, _PATH) or (torch.is_tensor(src) and src.dim() <= 1)) else list(src)
         B = len(src)
         assert B >= 1, "empty batch"
-        opts = _Options(self, B, False, seeds=seeds, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
+        opts = _Options(self, B, False, seeds=seeds, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
         if target_voice_paths is not None and ref_dicts is not None:
             raise ValueError("give target_voice_paths or ref_dicts, not both")
         if target_voice_paths is not None:
@@ -1523,9 +1633,14 @@ class ChatterboxVC(_Finish):
             else:
                 src = [self._tokens_of(a) for a in src]
         toks = [torch.as_tensor(t).view(-1).long().cpu() for t in src]
-        out = [None] * B
+        out, fits = [None] * B, [None] * B
         for idx in batch_plan([int(t.numel()) for t in toks], int(self.MAX_BATCH)):
             wavs, _ = self.engine.vocode(_pick(toks, idx), _one_or_list(_pick(refs, idx)), **opts.kw(idx))
             for i, w in zip(idx, wavs):
                 out[i] = self._finish(w, opts.fmt)
+            if opts.warp_kw(idx) is not None:
+                for i, r in zip(idx, self.engine.last_fit):
+                    fits[i] = r
+        if opts.warped:
+            self._take_fit(fits, "generate_batch")
         return out

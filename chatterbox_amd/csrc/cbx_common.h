@@ -187,6 +187,41 @@ __device__ __forceinline__ float cbx_act(float v, int act, float slope, float pa
     }
 }
 
+// The mel interpolation of mel_speed.hip (one rate per row, and a window of that map) and mel_warp.hip (a piecewise-linear map): ONE tap rule and ONE blend,
+// shared so that a one-segment warp reproduces the plain stretch bit for bit.  Each file evaluates its own position x -- (j + 0.5) s - 0.5 as one contracted fp64
+// multiply-add, in mel_warp.hip relative to the segment's edges -- and hands it over.
+// cbx_mel_taps_at: the taps of position x >= 0 (absolute) in an input whose frame 0 is absolute frame i_org and which holds M >= 1 frames: i0 / i1 are indices INTO
+// the input, clamped to [0, M - 1] whatever x and i_org are (a NaN x compares false everywhere and lands on M - 1 with l = 0); l is cut to [0, 1].
+struct cbx_mel_taps_t {
+    int i0, i1;
+    float l;
+};
+__device__ __forceinline__ cbx_mel_taps_t cbx_mel_taps_at(double x, long i_org, int M) {
+    const double r = floor(x) - (double)i_org;  // exact: both are integers far below 2^53
+    cbx_mel_taps_t t;
+    t.i0 = r < (double)(M - 1) ? (r > 0.0 ? (int)r : 0) : M - 1;
+    t.i1 = t.i0 + 1 < M ? t.i0 + 1 : M - 1;
+    t.l = (float)fmin(fmax(x - (double)((long)t.i0 + i_org), 0.0), 1.0);
+    return t;
+}
+// (1 - l) a + l b: 1 - l, l b and the fma round once each
+__device__ __forceinline__ float cbx_mel_blend(float a, float b, float l) { return fmaf(1.0f - l, a, l * b); }
+// out[o] = (1 - l) r0 + l r1 over VEC channels (4: one 16-byte access each; 1: a float), or zeros when r0 is null
+template <int VEC>
+__device__ __forceinline__ void cbx_mel_blend_store(float* o, const float* r0, const float* r1, float l) {
+    if (VEC == 4) {
+        if (!r0) {
+            *reinterpret_cast<f32x4*>(o) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            return;
+        }
+        const f32x4 a = *reinterpret_cast<const f32x4*>(r0), bb = *reinterpret_cast<const f32x4*>(r1);
+        *reinterpret_cast<f32x4*>(o) =
+            f32x4{cbx_mel_blend(a[0], bb[0], l), cbx_mel_blend(a[1], bb[1], l), cbx_mel_blend(a[2], bb[2], l), cbx_mel_blend(a[3], bb[3], l)};
+    } else {
+        *o = r0 ? cbx_mel_blend(*r0, *r1, l) : 0.0f;
+    }
+}
+
 // x of lane (l ^ MASK), MASK a power of two < 64, WITHOUT the LDS crossbar: hipcc lowers __shfl_xor to ds_bpermute_b32 (an LDS round trip, ~100
 // cycles each; a 6-step butterfly is a dependent chain of six) -- here 1 / 2 are quad_perm DPP moves, 4 is a row_shl:4 / row_shr:4 pair under
 // bank masks, 8 is row_ror:8 (a rotation by half a 16-lane row IS the xor), 16 / 32 are v_permlane16_swap / v_permlane32_swap (gfx950).  Same

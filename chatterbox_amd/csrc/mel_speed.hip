@@ -20,39 +20,18 @@
 
 namespace {
 
-// (1 - l) a + l b: 1 - l, l b and the fma round once each
-__device__ __forceinline__ float blend(float a, float b, float l) { return fmaf(1.0f - l, a, l * b); }
-
 // The taps of ABSOLUTE output frame j at rate s, for an input whose frame 0 is absolute frame i_org and which holds M frames: THE position expression of both
 // kernels -- x = max(0, (j + 0.5) s - 0.5) as one contracted fp64 multiply-add -- so a window of the map (mel_time_scale_win_kernel) reproduces the whole map's
-// bits.  i0 / i1 are indices INTO the input, clamped to [0, M - 1] whatever j, s and i_org are (M >= 1); l is cut to [0, 1].
-struct mel_taps_t {
-    int i0, i1;
-    float l;
-};
+// bits.  The tap rule and the blend live in cbx_common.h, where mel_warp.hip (a piecewise-linear map) shares them.
+typedef cbx_mel_taps_t mel_taps_t;
 __device__ __forceinline__ mel_taps_t mel_taps(long j, double s, long i_org, int M) {
-    const double x = fmax(0.0, ((double)j + 0.5) * s - 0.5);  // (a NaN rate gives 0; an infinite one is cut by the min below)
-    const double r = floor(x) - (double)i_org;                // exact: both are integers far below 2^53
-    mel_taps_t t;
-    t.i0 = r < (double)(M - 1) ? (r > 0.0 ? (int)r : 0) : M - 1;
-    t.i1 = t.i0 + 1 < M ? t.i0 + 1 : M - 1;
-    t.l = (float)fmin(fmax(x - (double)((long)t.i0 + i_org), 0.0), 1.0);
-    return t;
+    const double x = fmax(0.0, ((double)j + 0.5) * s - 0.5);  // (a NaN rate gives 0; an infinite one is cut by the clamp of the taps)
+    return cbx_mel_taps_at(x, i_org, M);
 }
 
-// out[o] = (1 - l) r0 + l r1 over VEC channels, or zeros when r0 is null
 template <int VEC>
 __device__ __forceinline__ void blend_store(float* o, const float* r0, const float* r1, float l) {
-    if (VEC == 4) {
-        if (!r0) {
-            *reinterpret_cast<f32x4*>(o) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            return;
-        }
-        const f32x4 a = *reinterpret_cast<const f32x4*>(r0), bb = *reinterpret_cast<const f32x4*>(r1);
-        *reinterpret_cast<f32x4*>(o) = f32x4{blend(a[0], bb[0], l), blend(a[1], bb[1], l), blend(a[2], bb[2], l), blend(a[3], bb[3], l)};
-    } else {
-        *o = r0 ? blend(*r0, *r1, l) : 0.0f;
-    }
+    cbx_mel_blend_store<VEC>(o, r0, r1, l);
 }
 
 // grid (ceil(T_out * CV / 256), B): thread = (output frame j, channel group c) of batch row blockIdx.y; CV = C / VEC channel groups of VEC floats

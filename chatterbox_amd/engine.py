@@ -79,6 +79,8 @@ def _checked_job(job):
     if job.get("words") is not None:
         raise ValueError(WORDS_PIPELINED)
     d = check_delivery(len(job["text_tokens"]), **{k: job.get(k) for k in ("seeds", "generator", "speed") + Delivery.OPTIONS})
+    if d.warp is not None and any(w is not None and "anchors" in w for w in d.warp):
+        raise ValueError(WARP_PIPELINED)
     job = {k: v for k, v in job.items() if k not in Delivery.OPTIONS + ("words",) and not (k == "guard" and v is None)}
     job.update(d.kw())
     for k, v in (("seeds", d.seeds), ("speed", d.speed)):
@@ -91,6 +93,12 @@ WORDS_PIPELINED = ("words: the alignment pass runs between T3 and the vocoder of
                    "(synthesize_pipelined keeps two T3 states in flight; the pass inside that overlap is not built)")
 WORDS_PAUSES = ("max_pause (pauses) together with word_times (words): the cut map of the pause step is data on the device; mapping word boundaries "
                 "through it is not built")
+
+
+WARP_PIPELINED = ("warp with anchors (timing): the anchors come from the alignment pass, which runs on the serial schedule only -- call synthesize(words=, warp=) "
+                  "per job; a job of synthesize_pipelined takes a warp of the duration kind, dict(frames=)")
+WARP_WITH = ("{0} together with duration / timing (warp): the time map fixes when things happen; combining it with {0} is not built -- "
+             "give one of the two")
 
 
 GUARD_BANS = "guard together with ban_eos / ban_from: both ban the end-of-speech token the guard must be able to force"
@@ -130,6 +138,44 @@ def frame_sample(f, speed=None, pitch=None):
     return pos if r == 1.0 else int(math.floor(pos / r + 0.5))
 
 
+def check_warp(warp, B):
+    """The `warp` option of an engine call for B utterances: None, or a list / tuple of B entries, each None (a plain row), dict(frames=O) -- fit the row into O >= 1
+    mel frames of 480 samples (the duration kind) -- or dict(anchors=[(x, t), ...], end=O or None): input mel frame x (nondecreasing, >= 0) lands on output frame t,
+    and the row ends at frame `end` (ops.warp_plan's arguments; x beyond the row's K frames is cut to K when the plan is made).  -> the list with every entry
+    normalised, or None when no row is warped.  TypeError / ValueError before anything is launched."""
+    import numbers
+    if warp is None:
+        return None
+    if not isinstance(warp, (list, tuple)):
+        raise TypeError(f"warp: expected None or a list of {B} entries (None, dict(frames=) or dict(anchors=, end=)), got {type(warp).__name__}")
+    if len(warp) != B:
+        raise ValueError(f"warp: {len(warp)} entries for {B} utterances")
+    integer = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    out = []
+    for b, w in enumerate(warp):
+        if w is None:
+            out.append(None)
+            continue
+        if not isinstance(w, dict) or set(w) not in ({"frames"}, {"anchors"}, {"anchors", "end"}):
+            raise ValueError(f"warp[{b}]: expected None, dict(frames=) or dict(anchors=, end=), got {w!r}")
+        end = w.get("frames", w.get("end"))
+        if "frames" in w and end is None or end is not None and not (integer(end) and 1 <= end <= 2 * 4000):
+            raise ValueError(f"warp[{b}]: a length of {end!r} frames (an int in [1, 8000])")
+        if "frames" in w:
+            out.append(dict(frames=int(end)))
+            continue
+        anchors, last = [], (0, 0)
+        for k, a in enumerate(w["anchors"]):
+            if not (isinstance(a, (list, tuple)) and len(a) == 2 and integer(a[0]) and integer(a[1])):
+                raise TypeError(f"warp[{b}]: anchor {k} = {a!r}: expected (input frame, output frame) as two ints")
+            if a[0] < last[0] or a[1] < last[1]:
+                raise ValueError(f"warp[{b}]: anchor {k} = {tuple(a)} after {last}: both frames are nondecreasing and not negative")
+            last = (int(a[0]), int(a[1]))
+            anchors.append(last)
+        out.append(dict(anchors=anchors, end=None if end is None else int(end)))
+    return None if all(w is None for w in out) else out
+
+
 LOUDNESS_JOIN = "loudness together with join: a long text is normalised as a whole, after its pieces are assembled (generate_long(loudness=))"
 
 
@@ -147,18 +193,20 @@ class Delivery:
     fmt: Optional[dict] = None
     loud: Optional[list] = None
     pz: Optional[dict] = None
-    OPTIONS = ("pitch", "join", "format", "loudness", "pauses")  # the keywords a call carries only when the option is on
+    warp: Optional[list] = None  # check_warp's list: per utterance None, dict(frames=) or dict(anchors=, end=)
+    OPTIONS = ("pitch", "join", "format", "loudness", "pauses", "warp")  # the keywords a call carries only when the option is on
 
     def kw(self):
         """The OPTIONS as the keywords of a downstream call (vocode, a job of synthesize_pipelined): a key is present only when its option is on.  seeds and speed
         are not among them: they travel as they were given."""
-        return {k: v for k, v in zip(self.OPTIONS, (self.pitch, self.join, self.fmt, self.loud, self.pz)) if v is not None}
+        return {k: v for k, v in zip(self.OPTIONS, (self.pitch, self.join, self.fmt, self.loud, self.pz, self.warp)) if v is not None}
 
 
-def check_delivery(B, *, seeds=None, generator=None, speed=None, pitch=None, join=None, format=None, loudness=None, pauses=None):
+def check_delivery(B, *, seeds=None, generator=None, speed=None, pitch=None, join=None, format=None, loudness=None, pauses=None, warp=None):
     """The one place where an engine entry (vocode, both synthesize methods, a job of synthesize_pipelined) checks its delivery options -> Delivery.  In this
     order: seeds (ops.request_seeds; not together with a generator), speed, pitch with the speed x pitch rule (ops.check_speed_pitch), join, format, loudness
-    (not together with a join: LOUDNESS_JOIN), pauses.  TypeError / ValueError before anything is launched; a checked value passes unchanged."""
+    (not together with a join: LOUDNESS_JOIN), pauses, warp (check_warp; not together with speed, pitch, pauses or a join: WARP_WITH).  TypeError / ValueError
+    before anything is launched; a checked value passes unchanged."""
     seeds = ops.request_seeds(seeds, B, generator)
     speed = ops.check_speed(speed, B)
     pitch = ops.check_pitch(pitch, B)
@@ -169,7 +217,13 @@ def check_delivery(B, *, seeds=None, generator=None, speed=None, pitch=None, joi
     if loud is not None and join is not None:
         raise ValueError(LOUDNESS_JOIN)
     rates = speed if eff is None else (None if all(e == 1.0 for e in eff) else eff)
-    return Delivery(seeds, speed, pitch, rates, join, fmt, loud, ops.check_pauses(pauses, B))
+    pz = ops.check_pauses(pauses, B)
+    warp = check_warp(warp, B)
+    if warp is not None:
+        for name, on in (("speed", speed), ("pitch", pitch), ("max_pause (pauses)", pz), ("join", join)):
+            if on is not None:
+                raise ValueError(WARP_WITH.format(name))
+    return Delivery(seeds, speed, pitch, rates, join, fmt, loud, pz, warp)
 
 
 def _joined_on_host(out, rec, n, fmt, pauses, truncated):
@@ -178,11 +232,23 @@ def _joined_on_host(out, rec, n, fmt, pauses, truncated):
     return dict(ops.piece_on_host(out, rec, n, fmt), truncated=truncated, **({} if pauses is None else dict(pauses=pauses.tolist())))
 
 
+def _fit_report(w, plan):
+    """What last_fit keeps for a warped row: target (the frames asked for: dict(frames=)'s O, or `end` of an anchored row, None when that was left open), frames
+    (the output length), rate = (min, max) over the plan's segments, clamped (ops.warp_plan's: the anchors that missed their frame, "end" for a missed length),
+    table (the map itself, mel_time_warp's row), and for an anchored row achieved (the output frame of every anchor) and dropped."""
+    rates = [s for _, _, s in plan["table"]]
+    rep = dict(target=w.get("frames", w.get("end")), frames=plan["frames"], rate=(min(rates), max(rates)), clamped=list(plan["clamped"]), table=list(plan["table"]))
+    if "anchors" in w:
+        rep.update(achieved=list(plan["achieved"]), dropped=list(plan["dropped"]))
+    return rep
+
+
 class S3GenEngine:
     """The S3Gen half of every engine -- flow matching (FlowEngine) and vocoder (HiFTEngine) of one checkpoint on one device -- and what is built on the two alone:
     vocode, vocode_stream and the streams and kernel forms of the overlapped schedules.  On its own it is the engine of voice conversion (no T3);
     ChatterboxEngine and TurboEngine put their T3 in front of it."""
     t3 = None
+    last_fit = None  # per utterance of the last vocode(warp=) call: None (a plain row) or _fit_report's dict; None after a call without warp
 
     def __init__(self, s3gen_sd, device="cuda", meanflow=False):
         self.dev = torch.device(device)
@@ -195,7 +261,7 @@ class S3GenEngine:
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None):
+               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None, warp=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
@@ -239,9 +305,16 @@ class S3GenEngine:
         draws sized from it exactly as speed= sizes them --, and ONE ops.wave_pitch launch (cbx_wave_pitch_f32) on the stream that owns the waveforms reads the
         cut rows, 480 scaled_len(K_b, s_eff) samples, at a step of r_b into 480 scaled_len(K_b, speed[b]) samples: the length of the call without a pitch,
         every frequency multiplied by r_b.  The formants move with the pitch.  The launch runs ahead of the loudness step, the pauses, the join and the format
-        launch, which see its rows (views of one packed buffer; a row without a pitch is copied)."""
+        launch, which see its rows (views of one packed buffer; a row without a pitch is copied).
+        warp (None, or no utterance with an entry: this call, launch for launch; else check_warp's list): the timing control.  Row b's entry is None, dict(frames=O)
+        -- fit the K_b frames the plain call returns into O -- or dict(anchors=[(x, t), ...], end=O or None) -- mel frame x lands on output frame t.  ops.warp_plan
+        turns it into a piecewise-linear map whose every rate lies in [0.5, 2.0] (a target that needs more is met as far as the bound allows: nothing is padded or
+        cut), ONE ops.mel_time_warp launch (cbx_mel_time_warp_f32) in the place of the ops.mel_time_scale launch warps the flow's mel -- a plain row of the batch
+        rides along on the one-segment rate-1 table, which copies it --, the vocoder runs on the warped mel with lens = frames, noise, phase and seeded draws sized
+        from it as speed= sizes them, and row b comes back with frames_b * 480 samples.  self.last_fit keeps the plans (_fit_report).  Not together with speed,
+        pitch, pauses or a join (ValueError naming both).  The returned mel stays the flow's."""
         B = len(speech_tokens)
-        d = check_delivery(B, seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses)
+        d = check_delivery(B, seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses, warp=warp)
         seeds, rates = d.seeds, d.rates
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
@@ -253,6 +326,8 @@ class S3GenEngine:
         refs = list(gen_ref) if isinstance(gen_ref, (list, tuple)) else [gen_ref] * B  # one voice for all, or one per utterance (s3gen.py:173-229)
         assert len(refs) == B, f"{len(refs)} voices for {B} utterances"
         shorts = [int(r["prompt_feat"].reshape(-1, 80).shape[0]) - 2 * int(r["prompt_token"].numel()) for r in refs]
+        plans = None if d.warp is None else self._warp_plans(d.warp, ns, shorts, drop_last_token)
+        self.last_fit = None if plans is None else [None if p is None else _fit_report(w, p) for w, p in zip(d.warp, plans)]
 
         def run():
             t0 = time.perf_counter()
@@ -261,7 +336,11 @@ class S3GenEngine:
                 torch.cuda.synchronize()
             t1 = time.perf_counter()
             # short_b > 0 only when the prompt mel has an odd frame more than 2 * prompt tokens (flow.py:170-195); per voice when the batch mixes voices
-            if rates is None:
+            if plans is not None:  # ONE launch: warped rows by their plans over the M_b valid frames, plain rows copied by the rate-1 table
+                M = [2 * n - sh for n, sh in zip(ns, shorts)]
+                vmel, mel_lens = ops.mel_time_warp(mel, [[(0, 0.0, 1.0)] if p is None else p["table"] for p in plans], in_lens=M,
+                                                   out_lens=[m if p is None else p["frames"] for m, p in zip(M, plans)])
+            elif rates is None:
                 vmel, mel_lens = mel, None if same and len(set(shorts)) == 1 else (2 * lens - torch.tensor(shorts, dtype=torch.int32)).to(self.dev)
             else:  # the vocoder's input is the stretched mel; lens always: the rows differ
                 vmel, mel_lens = ops.mel_time_scale(mel, rates, in_lens=[2 * n - sh for n, sh in zip(ns, shorts)])
@@ -283,9 +362,24 @@ class S3GenEngine:
             return wav, mel
 
         wav, mel = _range_checked(self, run, check=sync)
-        return self._deliver(wav, ns, shorts, d, drop_last_token, sync, hift_stream), mel
+        return self._deliver(wav, ns, shorts, d, drop_last_token, sync, hift_stream, plans), mel
 
-    def _deliver(self, wav, ns, shorts, d, drop_last_token, sync, hift_stream):
+    @staticmethod
+    def _warp_plans(warp, ns, shorts, drop_last_token):
+        """ops.warp_plan per warped row over K_b, the frames the plain call returns for it (the rule of _deliver); an anchor beyond K_b is cut to K_b"""
+        plans = []
+        for w, n, sh in zip(warp, ns, shorts):
+            if w is None:
+                plans.append(None)
+                continue
+            K = min(2 * (max(1, n - 1) if drop_last_token else n), 2 * n - sh)
+            if "frames" in w:
+                plans.append(ops.warp_plan(K, [], end=w["frames"]))
+            else:
+                plans.append(ops.warp_plan(K, [(min(x, K), t) for x, t in w["anchors"]], end=w["end"]))
+        return plans
+
+    def _deliver(self, wav, ns, shorts, d, drop_last_token, sync, hift_stream, plans=None):
         """The chain behind the vocoder, in the one order vocode's docstring states: cut the rows of the padded batch `wav`, pitch, loudness, then either edges +
         squeeze + join (ONE ops.wave_join call) or the squeeze alone, then the format.  Every launch lands on the stream that owns the waveforms: ONE stream
         scope, entered only when a step is on.  Returns the rows; the formatted views; with pauses the rows cut through ops.cut_pauses (sync=True) or
@@ -299,6 +393,8 @@ class S3GenEngine:
                 plain.append(ops.scaled_len(frames, d.speed[b]) if d.speed is not None else frames)
             if d.rates is not None:
                 frames = ops.scaled_len(frames, d.rates[b])
+            if plans is not None and plans[b] is not None:
+                frames = plans[b]["frames"]
             out.append(wav[b, : frames * HALF])
         if not d.kw():
             return out
@@ -399,7 +495,7 @@ class ChatterboxEngine(S3GenEngine):
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
                    noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None,
-                   words=None, guard=None):
+                   words=None, guard=None, warp=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
@@ -420,7 +516,22 @@ class ChatterboxEngine(S3GenEngine):
         to turn a frame into a sample of wavs[b]).  Not together with pauses; at most T3Engine.MAX_BATCH utterances.  Without it the call is launch for launch
         the one it always was.
         guard: None, or T3Engine.generate(guard=)'s dict -- the alignment guard inside the token step (it holds EOS back until the text has been spoken and
-        forces it when the alignment says the utterance is over); last_guard is then the per-utterance report (T3Engine.collect).  Not with ban_eos / ban_from."""
+        forces it when the alignment says the utterance is over); last_guard is then the per-utterance report (T3Engine.collect).  Not with ban_eos / ban_from.
+        warp: None, or vocode(warp=)'s list -- the timing control; T3 and its tokens do not depend on it.  An entry dict(frames=O) fits the utterance into O mel
+        frames.  With words= an entry may instead be dict(starts=[one output frame or None per TEXT TOKEN], end=O or None): once t3.align has said where every
+        text token begins, token i with a start becomes the anchor (2 c[f0_i], starts[i]) -- its first mel frame lands on that output frame --, and the
+        alignment entry of the utterance gains `table`, the map its boundaries go through (ops.warp_place); without words= such an entry is a ValueError.
+        last_fit is vocode's."""
+        starts = None
+        if warp is not None and isinstance(warp, (list, tuple)) and any(isinstance(w, dict) and "starts" in w for w in warp):
+            if words is None:
+                raise ValueError("warp with starts: the anchors come from the alignment pass -- give words= as well")
+            starts = [w if isinstance(w, dict) and "starts" in w else None for w in warp]
+            for b, w in enumerate(starts):
+                if w is not None and (set(w) - {"starts", "end"} or len(w["starts"]) != int(text_tokens[b].numel())):
+                    raise ValueError(f"warp[{b}]: dict(starts=, end=) with one start / None per text token ({int(text_tokens[b].numel())}), got {w!r}")
+            # checked as anchors at the frames they will at least have (x is known only after the alignment): the targets alone
+            warp = [w if s is None else dict(anchors=[(0, t) for t in s["starts"] if t is not None], end=s.get("end")) for w, s in zip(warp, starts)]
         if guard is not None:
             guard = self.t3.check_guard(guard)
             if ban_eos or ban_from > 0:
@@ -432,7 +543,8 @@ class ChatterboxEngine(S3GenEngine):
             if len(text_tokens) > self.t3.MAX_BATCH:
                 raise ValueError(f"words: {len(text_tokens)} utterances (at most {self.t3.MAX_BATCH}: the pass runs on the state of ONE device batch)")
             self.t3.check_align_heads(words["heads"])
-        d = check_delivery(len(text_tokens), seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses)
+        d = check_delivery(len(text_tokens), seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses,
+                           warp=warp)
         seeds = d.seeds
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
@@ -453,8 +565,16 @@ class ChatterboxEngine(S3GenEngine):
                 alignment.append(dict(frames=[(c[f0], c[f1]) for f0, f1 in sp.tolist()], n_frames=c[-1], speed=None if d.speed is None else d.speed[b],
                                       pitch=None if d.pitch is None else d.pitch[b]))
             self.last_timing["align_s"] = time.perf_counter() - t1
+        vkw = d.kw()
+        if starts is not None:  # word i's first mel frame, 2 c[f0_i], lands on its target
+            vkw["warp"] = [w if s is None else dict(anchors=[(2 * f[0], t) for f, t in zip(a["frames"], s["starts"]) if t is not None], end=s.get("end"))
+                           for w, s, a in zip(d.warp, starts, alignment)]
         wavs, _ = self.vocode(st, gen_ref, z=z, phase=phase, noise=noise, n_cfm_timesteps=n_cfm_timesteps,
-                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=d.speed, **d.kw())
+                              drop_last_token=drop_last_token, generator=generator, seeds=seeds, speed=d.speed, **vkw)
+        if alignment is not None and self.last_fit is not None:
+            for a, fit in zip(alignment, self.last_fit):
+                if fit is not None:
+                    a["table"] = fit["table"]  # (frame_sample is for unwarped rows: a warped row's boundaries go through ops.warp_place(table, 2 f) * 480)
         if d.join is not None:  # (the record's copy waits for the two launches behind the vocoder)
             wavs = _joined_on_host(wavs.get("formatted", wavs["out"]), wavs["rec"], wavs["n"], d.fmt, wavs.get("pauses"), self._truncated(toks))
         self.last_timing["total_s"] = time.perf_counter() - t0
@@ -475,6 +595,8 @@ class ChatterboxEngine(S3GenEngine):
         or `format` (vocode(format=)'s dict: the job's audio is converted on the device ahead of its copies, which then carry the encoded samples),
         or `loudness` (vocode(loudness=): a number or one number / None per utterance; the meter and the gain run behind the vocoder on its stream; not with a join),
         or `pitch` (vocode(pitch=): a number or one number / None per utterance, semitones; the launch runs behind the vocoder on its stream),
+        or `warp` (vocode(warp=)'s list, entries of the duration kind -- None or dict(frames=) -- only: anchors need the alignment pass of the serial schedule,
+        WARP_PIPELINED; engine.last_fit is the job's report while the job is the one just yielded),
         or `guard` (T3Engine.generate(guard=)'s dict: the job's T3 runs with the alignment guard inside its token step, in whichever of the two T3 states it
         lands; engine.last_guard is the job's report while the job is the one just yielded; not with ban_eos / ban_from),
         or `pauses` (vocode(pauses=)'s dict / list: the squeeze runs behind the vocoder on its stream; its record of the new lengths travels to the host as one more
@@ -527,7 +649,9 @@ class ChatterboxEngine(S3GenEngine):
             is called exactly as before there was one)"""
             wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
                                   speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10), drop_last_token=kw.get("drop_last_token", True), sync=False,
-                                  **({k: job[k] for k in ("join", "format", "loudness", "pauses", "pitch") if k in job}))
+                                  **({k: job[k] for k in ("join", "format", "loudness", "pauses", "pitch", "warp") if k in job}))
+            if "warp" in job:
+                job["_fit"] = self.last_fit  # (the job's own dict, _checked_job's copy: the report travels with it to the yield)
             return wavs
 
         def to_host(job, wavs, pinned):
@@ -562,7 +686,7 @@ class ChatterboxEngine(S3GenEngine):
                         job, st, t0, raw, rep = pending
                         with torch.cuda.stream(self._s_voc):  # (the copies block: this returns when the batch's audio is on the host)
                             host = _range_checked(self, lambda: to_host(job, vocode_job(job, st), pinned=False))
-                        self.last_guard = rep
+                        self.last_guard, self.last_fit = rep, job.get("_fit")
                         yield result_of(job, host, raw), st, time.perf_counter() - t0
                     pending = None
                     if "handle" in box:
@@ -620,6 +744,7 @@ class ChatterboxEngine(S3GenEngine):
             if 16 in (self.flow.precision, self.hift.precision) and ops.range_flag_tripped(self.dev, which):
                 with _repeat_at_bf16x6(self, " of this batch"), torch.cuda.stream(self._s_voc):
                     host = to_host(job, vocode_job(job, st), pinned=False)  # (the repeat repeats the join)
+            self.last_fit = job.get("_fit")  # (the fit report of THIS job: the vocoder of the next one may have been enqueued since)
             return result_of(job, host, raw), st, time.perf_counter() - t0
 
         th = threading.Thread(target=worker, name="cbx-t3-enqueue", daemon=True)
@@ -1145,14 +1270,18 @@ class TurboEngine(S3GenEngine):
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None, warp=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
         for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=);
         speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=); join: None, or vocode(join=)'s dict -- the call then returns
         ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict; loudness: None, or vocode(loudness=)'s targets (not with a join);
         pauses: None, or vocode(pauses=)'s dict / list, as ChatterboxEngine.synthesize(pauses=) returns its results; pitch: None, or vocode(pitch=)'s semitones,
-        checked against speed before anything is launched as ChatterboxEngine.synthesize(pitch=) does."""
-        d = check_delivery(len(text_tokens), seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses)
+        checked against speed before anything is launched as ChatterboxEngine.synthesize(pitch=) does; warp: None, or vocode(warp=)'s list with entries of the
+        duration kind (None or dict(frames=)): anchors need an alignment pass, which the GPT-2 backbone does not have."""
+        d = check_delivery(len(text_tokens), seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses,
+                           warp=warp)
+        if d.warp is not None and any(w is not None and "anchors" in w for w in d.warp):
+            raise ValueError("warp with anchors (timing) on the Turbo engine: the alignment pass on the GPT-2 backbone is not built -- dict(frames=) only")
         seeds = d.seeds
         t0 = time.perf_counter()
         toks = self.t3.generate(t3_conds, text_tokens, max_gen_len=max_gen_len, temperature=temperature, top_k=top_k, top_p=top_p,

@@ -1063,6 +1063,194 @@ def mel_time_scale_window(mel, rate, j0, i_org, in_lens, out_lens, out=None):
     return out, args[B:]
 
 
+# ----------------------------------------------------------------------------- timing control: a piecewise-linear time map of the mel (cbx_mel_time_warp_f32)
+MEL_WARP_MAX_ROWS = 64            # seg_off travels to the kernel by value
+DURATION_MIN, DURATION_MAX = 0.02, 80.0   # seconds: one 20 ms frame .. twice the 40 s budget (1000 tokens) at rate 0.5
+MEL_FRAMES_PER_S = 50
+
+
+def seconds_to_frames(t):
+    """Seconds -> 20 ms mel frames, floor(50 t + 0.5): half-way cases go up (Python's round sends them to the even neighbour)"""
+    import math
+    return int(math.floor(MEL_FRAMES_PER_S * float(t) + 0.5))
+
+
+def warp_plan(K, anchors, end=None, lo=SPEED_MIN, hi=SPEED_MAX):
+    """THE definition of the timing control, pure host arithmetic: the piecewise-linear map that takes the K mel frames the unwarped call returns for a row to a
+    chosen number of output frames, through `anchors` = [(x, t), ...]: input frame x (a number in [0, K], nondecreasing) should land on output frame t (an int).
+    The plan starts at (x, o) = (0, 0).  Anchor k with L = x_k - x_{k-1} > 0 gets n_k = min(max(t_k - o_{k-1}, ceil(L / hi), 1), floor(L / lo)) output frames,
+    o_k = o_{k-1} + n_k, and the segment's rate is L / n_k -- in [lo, hi] by construction; a later anchor still aims at its absolute target, so a clamp does not
+    accumulate.  An anchor whose x is 0 or equals an earlier anchor's x has no input to stretch: it is dropped (`dropped`), achieved[k] is the output frame its x
+    already has, and it counts as clamped when that is not its target.  The last segment runs to x = K with target `end` (None: o_last + (K - x_last), rate 1); an
+    anchor at x = K closes the plan itself, and `end` is then not honoured unless it agrees.
+    -> dict(table=[(o, a, s), ...] (segment starts at output frame o, where input position a lies, and runs at rate s: mel_time_warp's row), frames = the output
+    length, achieved = [o_k per anchor], clamped = [k with o_k != t_k] plus "end" when `end` was given and frames != end, dropped = [k])."""
+    import math
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"warp_plan: K = {K}: a row has at least one frame")
+    table, achieved, clamped, dropped = [], [], [], []
+    x0, o0 = 0, 0
+
+    def fit(L, want):
+        return int(min(max(int(want), int(math.ceil(L / hi)), 1), int(math.floor(L / lo))))
+    for k, (x, t) in enumerate(anchors):
+        if not x0 <= x <= K:
+            raise ValueError(f"warp_plan: anchor {k} at x = {x}: positions are nondecreasing in [0, {K}]")
+        L = x - x0
+        if L > 0:
+            n = fit(L, int(t) - o0)
+            table.append((o0, float(x0), L / n))
+            x0, o0 = x, o0 + n
+        else:
+            dropped.append(k)
+        achieved.append(o0)
+        if o0 != int(t):
+            clamped.append(k)
+    L = K - x0
+    if L > 0:
+        n = fit(L, L if end is None else int(end) - o0)
+        table.append((o0, float(x0), L / n))
+        o0 += n
+    if end is not None and o0 != int(end):
+        clamped.append("end")
+    return dict(table=table, frames=o0, achieved=achieved, clamped=clamped, dropped=dropped)
+
+
+def warp_place(table, x):
+    """The inverse of a row's map: input frame position x -> its output position o_k + (x - a_k) / s_k in frames, k the last segment with a_k <= x (the first
+    when there is none).  At an anchor -- x = a_k -- that is exactly o_k.  The word boundaries of word_times= go through here."""
+    k = 0
+    for i, (_, a, _) in enumerate(table):
+        if a <= x:
+            k = i
+    o, a, s = table[k]
+    return o + (x - a) / s
+
+
+def check_duration(value, B, name="duration"):
+    """A `duration` argument as a list of B target lengths in FRAMES (seconds_to_frames) / Nones, or None when no request has one.  A number serves every
+    request; anything else is a list or tuple of exactly B numbers / Nones in [0.02, 80] seconds.  A bool or a non-number is a TypeError; a non-finite or
+    out-of-range value and a wrong length are ValueErrors -- raised before anything is launched."""
+    import math
+    import numbers
+    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    if value is None:
+        return None
+    if one(value):
+        value = [value] * B
+    elif not isinstance(value, (list, tuple)):
+        raise TypeError(f"{name}: expected a number of seconds or a list of {B} numbers / Nones, got {type(value).__name__}")
+    if len(value) != B:
+        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
+    out = []
+    for k, v in enumerate(value):
+        if v is None:
+            out.append(None)
+            continue
+        if not one(v):
+            raise TypeError(f"{name}[{k}]: expected a number of seconds or None, got {type(v).__name__}")
+        v = float(v)
+        if not math.isfinite(v) or not DURATION_MIN <= v <= DURATION_MAX:
+            raise ValueError(f"{name}[{k}] = {v}: a duration is a finite number of seconds in [{DURATION_MIN}, {DURATION_MAX}]")
+        out.append(seconds_to_frames(v))
+    return None if all(v is None for v in out) else out
+
+
+def check_timing(value, B, name="timing"):
+    """A `timing` argument as a list of B entries, each None or the list of its request's word starts in FRAMES (seconds_to_frames) / Nones, or None when no
+    request has one.  value: None, or a list / tuple of exactly B entries, each None or a list / tuple with one entry per word: None (the word falls where it
+    falls) or its start in seconds, in [0, 80] and nondecreasing over the words that have one.  A bool or a non-number is a TypeError; a non-finite, negative,
+    too large or decreasing value and a wrong length are ValueErrors.  (The number of words is checked by the caller, who knows the text; a list without a
+    single time is kept for that check.)"""
+    import math
+    import numbers
+    if value is None:
+        return None
+    if not isinstance(value, (list, tuple)):
+        raise TypeError(f"{name}: expected a list of {B} lists of word starts / Nones, got {type(value).__name__}")
+    if len(value) != B:
+        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
+    out = []
+    for b, row in enumerate(value):
+        if row is None:
+            out.append(None)
+            continue
+        if not isinstance(row, (list, tuple)):
+            raise TypeError(f"{name}[{b}]: expected a list with one start in seconds / None per word, got {type(row).__name__}")
+        frames, last = [], None
+        for k, v in enumerate(row):
+            if v is None:
+                frames.append(None)
+                continue
+            if not isinstance(v, numbers.Real) or isinstance(v, bool):
+                raise TypeError(f"{name}[{b}][{k}]: expected a number of seconds or None, got {type(v).__name__}")
+            v = float(v)
+            if not math.isfinite(v) or not 0.0 <= v <= DURATION_MAX:
+                raise ValueError(f"{name}[{b}][{k}] = {v}: a word start is a finite number of seconds in [0, {DURATION_MAX}]")
+            if last is not None and v < last:
+                raise ValueError(f"{name}[{b}][{k}] = {v} after {last}: word starts are nondecreasing")
+            last = v
+            frames.append(seconds_to_frames(v))
+        out.append(frames)  # (kept even when no word has a time: the caller still checks the number of entries against the text)
+    return None if all(r is None for r in out) else out
+
+
+def mel_time_warp(mel, tables, in_lens=None, out=None, out_lens=None):
+    """cbx_mel_time_warp_f32: mel (B, T_in, C) fp32 channel-last (any batch / row stride, unit channel stride; B <= 64) warped along time, row b by tables[b] =
+    [(o, a, s), ...] (warp_plan's `table`: the segment starts at output frame o, where input position a lies, and runs at rate s) over its in_lens[b] valid frames
+    (B ints on the host; None: T_in) -> (out, out_lens) as mel_time_scale returns them.  out_lens: B host ints, or None: the last segment runs to the row's end,
+    o + max(1, floor((in_lens[b] - a) / s + 0.5)) -- what warp_plan's `frames` is for a plan over K = in_lens[b].  A one-segment table (0, 0.0, s) gives
+    mel_time_scale's bits at rate s.  out: as in mel_time_scale."""
+    import ctypes
+    import math
+    assert mel.dim() == 3 and mel.shape[2] >= 1 and (mel.shape[2] == 1 or mel.stride(2) == 1), "mel_time_warp: mel is (B, T_in, C) with unit channel stride"
+    B, T_in, C = mel.shape
+    M = [T_in] * B if in_lens is None else [int(v) for v in in_lens]
+    tables = [[(int(o), float(a), float(s)) for o, a, s in tb] for tb in tables]
+    if len(tables) != B or len(M) != B or not 1 <= B <= MEL_WARP_MAX_ROWS:
+        raise ValueError(f"mel_time_warp: {len(tables)} tables and {len(M)} lengths for {B} rows (at most {MEL_WARP_MAX_ROWS})")
+    if not all(0 <= m <= T_in for m in M):
+        raise ValueError(f"mel_time_warp: in_lens {M} outside [0, {T_in}]")
+    if not all(len(tb) >= 1 for tb in tables):
+        raise ValueError("mel_time_warp: every row needs at least one segment")
+    if out_lens is None:
+        O = []
+        for m, tb in zip(M, tables):
+            o, a, s = tb[-1]
+            n = (m - a) / s if s > 0 and math.isfinite(s) and math.isfinite(a) else 0.0
+            O.append(o + max(1, int(math.floor(n + 0.5))))
+    else:
+        O = [int(v) for v in out_lens]
+    if len(O) != B or min(O) < 0:
+        raise ValueError(f"mel_time_warp: out_lens {O} for {B} rows")
+    if out is None:
+        out = torch.empty(B, max(O), C, device=mel.device)
+    assert out.dim() == 3 and out.shape[0] == B and out.shape[2] == C and (C == 1 or out.stride(2) == 1) and out.device == mel.device, "mel_time_warp: out is (B, T_out, C)"
+    T_out = out.shape[1]
+    if max(O) > T_out:
+        raise ValueError(f"mel_time_warp: out holds {T_out} frames, the longest row needs {max(O)}")
+    # the table (S doubles seg_a, S doubles seg_s, S ints seg_o), in_lens and out_lens travel as ONE pinned buffer and one asynchronous copy (mel_time_scale);
+    # seg_off stays on the host: the entry checks it and passes it by value
+    S = sum(len(tb) for tb in tables)
+    off = [0]
+    for tb in tables:
+        off.append(off[-1] + len(tb))
+    dev = mel.device
+    host = torch.empty(5 * S + 2 * B, dtype=torch.int32, pin_memory=dev.type == "cuda")
+    host[: 4 * S].view(torch.float64).copy_(torch.tensor([a for tb in tables for _, a, _ in tb] + [s for tb in tables for _, _, s in tb], dtype=torch.float64))
+    host[4 * S:].copy_(torch.tensor([o for tb in tables for o, _, _ in tb] + M + O, dtype=torch.int32))
+    args = host.to(dev, non_blocking=True)
+    p = args.data_ptr()
+    seg_off = (ctypes.c_int * (B + 1))(*off)
+    sb = lambda t, T: t.stride(0) if B > 1 else max(t.stride(0), T * t.stride(1), C)  # (the stride of a dimension of size 1 is arbitrary)
+    check(lib.cbx_mel_time_warp_f32(_p(_f32(mel, "mel")), sb(mel, T_in), mel.stride(1) if T_in > 1 else max(mel.stride(1), C), T_in,
+                                    None if in_lens is None else p + 4 * (5 * S), ctypes.addressof(seg_off), S, p + 4 * (4 * S), p, p + 8 * S,
+                                    _p(_f32(out, "out")), sb(out, T_out), out.stride(1) if T_out > 1 else max(out.stride(1), C), T_out, p + 4 * (5 * S + B), B, C,
+                                    _stream()), "cbx_mel_time_warp_f32")
+    return out, args[5 * S + B:]
+
+
 # ----------------------------------------------------------------------------- long-form synthesis: trim + join the waveforms of a sub-batch (wave_join.hip)
 WAVE_FRAME, WAVE_JOIN_MAX_ROWS = 480, 64
 JOIN_KEYS = ("gaps", "trim_db", "pad_frames", "fade", "first", "last")

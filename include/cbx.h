@@ -837,6 +837,21 @@ int cbx_mel_time_scale_f32(const float* in, long in_sb, long in_ld, int T_in, co
  * [out_lens[b], T_out) are written as zeros, columns [C, out_ld) are not touched.  rate must be finite and > 0, j0 and i_org in [0, 2^40): else -22 before a launch. */
 int cbx_mel_time_scale_win_f32(const float* in, long in_sb, long in_ld, int T_in, const int* in_lens, double rate, long j0, long i_org, float* out, long out_sb,
                                long out_ld, int T_out, const int* out_lens, int B, int C, void* stream);
+/* ---- timing control: a PIECEWISE-LINEAR time map of the mel, in the place of cbx_mel_time_scale_f32 (added after ABI v16 without a version step: a new function
+ * only; the reference has no time map at all, models/s3gen/s3gen.py:289).  The layout arguments are those of cbx_mel_time_scale_f32.  Row b owns segments
+ * [seg_off[b], seg_off[b + 1]) of a packed table of n_seg segments: seg_off is a HOST array of B + 1 ints (it travels by value: B <= 64), seg_o (int32: the first
+ * output frame of each segment, increasing, the row's first 0), seg_a (fp64: the input position that output EDGE seg_o maps to) and seg_s (fp64: the rate inside the
+ * segment) are DEVICE arrays of n_seg entries, in_lens / out_lens device arrays as ever.  Output frame j < out_lens[b], in the last segment k of its row with
+ * seg_o[k] <= j (the row's first when there is none), samples the input at, in fp64,
+ *   x = max(0, seg_a[k] + (((j - seg_o[k]) + 0.5) seg_s[k] - 0.5))
+ * with the taps of cbx_mel_time_scale_f32: i0 = min(floor(x), M - 1), i1 = min(i0 + 1, M - 1), l = x - i0 cut to [0, 1], out = (1 - l) in[i0] + l in[i1] in fp32.
+ * The product term is the same contracted multiply-add: a one-segment table (0, 0.0, s) reproduces cbx_mel_time_scale_f32 at rate s bit for bit.  The map is
+ * continuous when seg_a[k + 1] = seg_a[k] + (seg_o[k + 1] - seg_o[k]) seg_s[k].  Memory safety does not depend on the table: the taps are clamped into [0, M - 1]
+ * whatever it holds and the search stays inside the row's range.  Frames [out_lens[b], T_out) are written as zeros (out_lens[b] is cut to T_out), columns
+ * [C, out_ld) are not touched, input frames from in_lens[b] on are never read.  A null pointer, C <= 0, a stride below C, B outside [0, 64], a negative T_in /
+ * T_out / n_seg / seg_off[0], or a row without a segment inside the table (seg_off[b + 1] <= seg_off[b] or > n_seg): -22 before any launch. */
+int cbx_mel_time_warp_f32(const float* in, long in_sb, long in_ld, int T_in, const int* in_lens, const int* seg_off, int n_seg, const int* seg_o,
+                          const double* seg_a, const double* seg_s, float* out, long out_sb, long out_ld, int T_out, const int* out_lens, int B, int C, void* stream);
 
 /* ---- long-form synthesis: trim and join the waveforms of one sub-batch of text chunks on the device (added after ABI v16 without a version step: new functions
  * only).  The reference stops at 1000 speech tokens (tts.py:249, mtl_tts.py:328) and has no chunking.  Rows: R in [1, 64] waveforms in text order, row r = the
