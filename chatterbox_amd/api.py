@@ -268,10 +268,10 @@ def _request_seeds(seed, B=1, one=True, generator=None):
 
 class _Options:
     """The delivery options of ONE public call for its B requests, built from the public arguments and validated when the method is CALLED, generators included --
-    in one order for every method: the format (sample_rate, encoding), word_times, seed / seeds (with the generator), speed, loudness, max_pause / pause_db, pitch
+    in one order for every method: the format (sample_rate, encoding), word_times, seed / seeds (with the generator), speed, loudness, true_peak, max_pause / pause_db, pitch
     with the speed x pitch rule (ops.check_speed_pitch), guard.  one=True: the method serves one request (generate, generate_long, ...): a sequence for
-    loudness, max_pause or pitch is then a TypeError.  segments=False (generate_long without return_segments): word_times is refused, its words travel in the
-    segments.  Holds fmt (ops.check_format's dict), words (_word_times' mode), seeds, speed, loud, pitch (B entries each), pz (_pauses' dict), guard (the
+    loudness, true_peak, max_pause or pitch is then a TypeError.  segments=False (generate_long without return_segments): word_times is refused, its words travel in the
+    segments.  Holds fmt (ops.check_format's dict), words (_word_times' mode), seeds, speed, loud, peak (ops.check_true_peak's dBTP ceilings), pitch (B entries each), pz (_pauses' dict), guard (the
     engines' dict) -- each None when no request uses it -- and the generator; kw(idx) turns them into the engines' keywords.
     duration / timing (the timing control; checked last): dur holds ops.check_duration's B target lengths in frames / Nones, timing ops.check_timing's B lists of
     word starts in frames / Nones; either is refused together with speed, pitch or max_pause (ValueError naming both).  timing needs the text: bind(tokens) --
@@ -279,7 +279,7 @@ class _Options:
     (_TTS._word_groups) and turns them into one start per text token (`starts`), which kw(idx) hands to the engine."""
 
     def __init__(self, model, B=1, one=True, *, seeds=None, generator=None, speed=None, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0,
-                 pitch=None, word_times=False, guard=None, segments=True, duration=None, timing=None):
+                 pitch=None, word_times=False, guard=None, segments=True, duration=None, timing=None, true_peak=None):
         self.model, self.one, self.generator = model, one, generator
         self.fmt = ops.check_format(sample_rate, encoding)
         self.words = None if word_times is None or word_times is False else model._word_mode(word_times, max_pause)
@@ -290,6 +290,9 @@ class _Options:
         if one and isinstance(loudness, (list, tuple)):
             raise TypeError(f"loudness: expected None or a number, got a {type(loudness).__name__}")
         self.loud = ops.check_loudness(loudness, B)
+        if one and isinstance(true_peak, (list, tuple)):
+            raise TypeError(f"true_peak: expected None or a number of dBTP, got a {type(true_peak).__name__}")
+        self.peak = ops.check_true_peak(true_peak, B)
         self.pz = _pauses(max_pause, pause_db, B, one)
         if one and isinstance(pitch, (list, tuple)):
             raise TypeError(f"pitch: expected None or a number of semitones, got a {type(pitch).__name__}")
@@ -346,10 +349,10 @@ class _Options:
 
     def kw(self, idx, chunks=False):
         """The engines' keywords of a call or job over the requests `idx`, the call without an option being exactly the call before there was one: seeds and speed
-        are present when given at all; loudness, pauses and pitch only when a request in idx uses them; the format unless a watermarker is loaded (it works on the
+        are present when given at all; loudness, true_peak, pauses and pitch only when a request in idx uses them; the format unless a watermarker is loaded (it works on the
         24 kHz fp32 waveform: the conversion then follows it, in _finish); words and guard, one setting for the call, with the model's align_heads.
-        chunks=True (long form): idx are chunks of the ONE request.  Every chunk carries the request's options, chunk k the seed chunk_seed(seed, k); loudness and
-        the format are held back from the jobs -- the assembled whole is normalised and converted once."""
+        chunks=True (long form): idx are chunks of the ONE request.  Every chunk carries the request's options, chunk k the seed chunk_seed(seed, k); loudness,
+        true_peak and the format are held back from the jobs -- the assembled whole is normalised, limited and converted once."""
         rows = (lambda v: [v[0]] * len(idx)) if chunks else (lambda v: _pick(v, idx))
         kw = {}
         if self.seeds is not None:
@@ -358,6 +361,8 @@ class _Options:
             kw["speed"] = rows(self.speed)
         if self.loud is not None and not chunks and any(v is not None for v in rows(self.loud)):
             kw["loudness"] = self.loud[0] if self.one else rows(self.loud)
+        if self.peak is not None and not chunks and any(v is not None for v in rows(self.peak)):
+            kw["true_peak"] = self.peak[0] if self.one else rows(self.peak)
         if self.pz is not None and any(rows(self.pz["keep"])):
             kw["pauses"] = dict(self.pz, keep=rows(self.pz["keep"]))
         if self.pitch is not None and any(rows(self.pitch)):
@@ -609,6 +614,14 @@ def _word_times(word_times, max_pause=None):
     return mode
 
 
+def _no_true_peak(method, true_peak):
+    """generate_long_stream lists true_peak only because its signature is generate_long's plus the ramp; anything but None is refused as an argument the method
+    does not take"""
+    if true_peak is not None:
+        raise TypeError(f"{method}() does not take true_peak: a running limiter needs a look-ahead carried from piece to piece, which is not built -- use "
+                        "generate_long(true_peak=...)")
+
+
 def _no_word_times(method, word_times):
     """generate_long_stream lists word_times only because its signature is generate_long's plus the ramp; anything but False / None is refused as an argument the
     method does not take"""
@@ -646,17 +659,19 @@ class _Finish:
         else:
             self._audio_in = value
 
-    def _finish(self, wav, fmt=None, converted=True, loud=None):
+    def _finish(self, wav, fmt=None, converted=True, loud=None, peak=None):
         """A device waveform as the reference returns it: CPU float32 (1, n), watermarked if a watermarker is loaded.
         fmt (ops.check_format's dict; None: exactly the above): the (1, n) CPU tensor at fmt's rate in fmt's encoding.  Without a watermarker the engine was given the
         format and `wav` is the converted audio already (converted=True): one copy to the host.  With one -- or when the caller kept the format from the engine
         (converted=False: generate_long) -- `wav` is 24 kHz fp32: it is watermarked on the host as ever, then converted on the device (_to_format).
         loud (a LUFS target; generate_long): the 24 kHz waveform is normalised as ONE signal first (_to_loudness); the watermark follows the gain, the conversion
-        the watermark."""
+        the watermark.  peak (a ceiling in dBTP; generate_long): the true-peak limiter follows that gain in the same visit to the device (_to_loudness)."""
         if fmt is not None and converted and self.watermarker is None:
             return wav.detach().cpu().unsqueeze(0)
         wav = wav.detach().float().cpu()
-        if loud is not None:
+        if peak is not None:
+            wav = self._to_loudness(wav, loud, peak)
+        elif loud is not None:
             wav = self._to_loudness(wav, loud)
         if self.watermarker is not None:
             wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
@@ -672,12 +687,19 @@ class _Finish:
         with scope:
             return ops.wave_format([wav.to(dev)], fmt)[0].cpu()
 
-    def _to_loudness(self, wav, target):
+    def _to_loudness(self, wav, target, peak=None):
         """A 24 kHz fp32 waveform on the host -> the device, ops.wave_normalize to `target` LUFS (sample peak limited to 1.0), back to the host (1-D); the stats stay
-        on the device as engine.last_loudness"""
+        on the device as engine.last_loudness.  peak (dBTP): one upload, the meter with the FULL gain to the target (none when target is None), ops.wave_limit
+        with that gain to the ceiling, one download; engine.last_limit keeps the limiter's stats."""
         dev, scope = self._device_scope()
         with scope:
             w = wav.to(dev).contiguous()
+            if peak is not None:
+                gain = None
+                if target is not None:
+                    self.engine.last_loudness, gain = ops.wave_loudness([w], [float(target)], None)
+                out, self.engine.last_limit = ops.wave_limit([w], [float(peak)], gain=gain)
+                return out[0].cpu()
             self.engine.last_loudness = ops.wave_normalize([w], [float(target)])
             return w.cpu()
 
@@ -962,7 +984,8 @@ class _TTS(_Finish):
         the joined pieces on the host, watermark the whole once.  opts.fmt: the engine jobs do not carry it -- the concatenated 24 kHz waveform is converted once, in
         _finish (host -> device -> host; no converter state travels through the joined pieces on the device), and the segments' start / stop become output samples,
         ceil(s U / D), so the last stop is the length; src_start / src_stop stay 24 kHz samples.  opts.loud (the LUFS target or None): the engine jobs do not carry it
-        either -- the concatenated waveform is measured and gained as ONE signal in _finish, ahead of the watermark, so the chunks keep their relative level."""
+        either -- the concatenated waveform is measured and gained as ONE signal in _finish, ahead of the watermark, so the chunks keep their relative level; opts.peak
+        (the dBTP ceiling or None) likewise: the whole is limited once, behind that gain."""
         chunks, plan, jobs = self._long_work(text, a, tokenize, samp, opts)
         fmt, pieces, segments, base = opts.fmt, [], [], 0
         fl = (lambda v: v) if fmt is None else (lambda v: ops.formatted_len(v, fmt["sample_rate"]))
@@ -983,7 +1006,7 @@ class _TTS(_Finish):
         self._warn_truncated("generate_long", [s["truncated"] for s in segments], a["max_chars"])
         if opts.guard is not None:
             self._take_guard([s["guard"] for s in segments], "generate_long")
-        wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=None if opts.loud is None else opts.loud[0])
+        wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=None if opts.loud is None else opts.loud[0], peak=None if opts.peak is None else opts.peak[0])
         if fmt is not None:
             for seg in segments:
                 seg.update(start=ops.formatted_len(seg["start"], fmt["sample_rate"]), stop=ops.formatted_len(seg["stop"], fmt["sample_rate"]))
@@ -1100,7 +1123,7 @@ class ChatterboxTTS(_LlamaTTS):
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5,
                  cfg_weight=0.5, temperature=0.8, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                 word_times=False, guard=None, duration=None, timing=None):
+                 word_times=False, guard=None, duration=None, timing=None, true_peak=None):
         """seed (None, or an int in [0, 2^64)): every random draw of this request -- sampling, flow noise, vocoder phase and noise -- is a function of the seed
         alone (no torch RNG is consumed), and is the one generate_batch(seeds=) gives the request in any batch.
         speed (a number in [0.5, 2.0]): the speaking rate, 1.25 = 25 % faster, at unchanged pitch -- the mel is interpolated along time between the flow decoder and
@@ -1114,6 +1137,17 @@ class ChatterboxTTS(_LlamaTTS):
         waveform is measured and multiplied by the gain that brings it to the target on the device, behind the vocoder and ahead of the format conversion and the
         only copy to the host (ops.wave_normalize); the gain is limited so that no sample exceeds a peak of 1.0, so a quiet target is met exactly and a loud one
         may fall short.  A silent result and one shorter than 0.4 s are returned as they are.  None is the call without the argument.
+        true_peak (None, or a ceiling in [-20, 0] dBTP, e.g. -1 for EBU R 128 and the streaming platforms): the true-peak limiter.  The peak of the 4-times
+        oversampled waveform -- the values between the samples that a D/A converter or a rate conversion reconstructs -- is held under the ceiling by a
+        look-ahead gain envelope of 5 ms on the device (ops.wave_limit), behind the loudness step and ahead of the pauses, the format conversion and the only
+        copy to the host.  Together with `loudness` the gain to the target is applied in full (the sample-peak limit of 1.0 gives way to the limiter), so a loud
+        target is met up to what the limiter removes: the loudness is not measured again and can end slightly below the target.  It changes no length: word
+        times and segments are untouched.  The ceiling holds for the 24 kHz fp32 signal; a later rate conversion or a host watermark can move peaks slightly --
+        that is what the headroom below 0 dBTP is for.  engine.last_limit keeps {true peak before, least gain, samples gained down, samples over the ceiling}.
+        generate_batch: a number or one number / None per request, travelling with its request like loudness.  generate_long: the assembled whole is limited
+        once, behind its loudness step.  The streams do not take the argument: a running limiter needs a carried look-ahead (generate_long_stream lists it, as it
+        lists word_times, because its signature is generate_long's plus the ramp, and refuses anything but None with a TypeError).  The look-ahead and the window are
+        UNMEASURED choices.  None is the call without the argument.
         max_pause (None, or seconds in [0.04, 60]) and pause_db (a finite number >= 0, default 40): pause control.  A silence INSIDE the utterance -- a run of
         480-sample frames whose mean square is pause_db decibels or more below the loudest frame's, between two frames that are not -- that is longer than
         round(max_pause * 50) frames is shortened to that many, on the device (ops.wave_squeeze), behind the loudness step and ahead of the format conversion and
@@ -1170,13 +1204,13 @@ class ChatterboxTTS(_LlamaTTS):
         before anything is launched.  generate_batch: a list of such lists / Nones.  Not on Turbo (its GPT-2 backbone has no alignment pass) or voice conversion.
         This is the statement of `seed`, `speed`, `sample_rate`, `encoding`, `loudness`, `max_pause`, `pause_db`, `pitch`, `word_times`, `guard`, `duration` and `timing` for every method
         of every class of this module; the others say only what differs."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text), opts, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                       max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                      word_times=False, guard=None):
+                      word_times=False, guard=None, true_peak=None):
         """generate() for a text of ANY length: the reference stops at 1000 speech tokens (40 s) and cuts a longer text off.  The text is split into chunks of at
         most max_chars characters at paragraph, sentence and clause boundaries (text.split_text), the chunks are synthesised in text order as device batches
         (one: synthesize; several: the throughput schedule where the engine has it), and each batch's waveforms are trimmed of their leading / trailing silence and
@@ -1196,15 +1230,15 @@ class ChatterboxTTS(_LlamaTTS):
         all of it, limited to a sample peak of 1.0, applied on the device ahead of the watermark and the conversion.
         word_times: generate()'s, with return_segments=True (without: ValueError): every segment gains `words`, its chunk's words shifted into the joined result
         through the segment's start / src_start and clipped to [start, stop); the device batches of such a call run one after the other."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                              max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
-                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None, first_batch=1,
-                             batch_growth=2.0):
+                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None, true_peak=None,
+                             first_batch=1, batch_growth=2.0):
         """generate_long() in pieces: a generator of (1, n) CPU tensors, one per device batch as it leaves the device (empty pieces left out); concatenated along
         dim 1 they are the long-form result.  Every argument of generate_long with its meaning and default, plus the ramp of the device batches:
         first_batch (None, or an int >= 1) and batch_growth (a finite number >= 1): the batches hold s_0 = min(first_batch, step) chunks, then
@@ -1225,6 +1259,7 @@ class ChatterboxTTS(_LlamaTTS):
         word_times: NOT taken -- it stands in the signature only because that is generate_long's plus the ramp; anything but False is a TypeError: a stream has
         no finished token sequence for the alignment pass."""
         _no_word_times("generate_long_stream", word_times)
+        _no_true_peak("generate_long_stream", true_peak)
         opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, guard=guard)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         ramp = _long_stream_args(first_batch, batch_growth)
@@ -1233,7 +1268,7 @@ class ChatterboxTTS(_LlamaTTS):
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2,
                        min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                       word_times=False, guard=None, duration=None, timing=None):
+                       word_times=False, guard=None, duration=None, timing=None, true_peak=None):
         """generate() for B requests in one call: a list of B CPU float32 tensors (1, n_b) at `.sr`, in the caller's order, each what generate() returns for that
         request.  Voice per request: `audio_prompt_paths` (one, or a list of B; equal paths are analysed once) or `conds` (one Conditionals, or a list of B);
         neither: self.conds.  exaggeration .. top_p: a float or a sequence of B (a wrong length raises ValueError before anything is launched).  generator: a
@@ -1248,7 +1283,7 @@ class ChatterboxTTS(_LlamaTTS):
         leaves that request as it is; it travels with its request through the sub-batches like its speed.
         This is the contract of generate_batch of every class of this module; the others say only what differs."""
         texts = _batch_of(texts)
-        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, samp, dict(exaggeration=exaggeration), opts)
 
@@ -1312,10 +1347,10 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                  repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                 word_times=False, guard=None, duration=None, timing=None):
+                 word_times=False, guard=None, duration=None, timing=None, true_peak=None):
         """ChatterboxTTS.generate in the language `language_id` (ValueError for one that is not in SUPPORTED_LANGUAGES; None: no language token); the last
         token's 40 ms are dropped as the reference does.  seed, speed, sample_rate, encoding, loudness, word_times, guard: as there."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
         lid = _language(language_id)
         self._use_voice(audio_prompt_path, exaggeration)
         return self._generate(self._text_ids(text, lid), opts, temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
@@ -1323,9 +1358,9 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                       return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False,
-                      guard=None):
+                      guard=None, true_peak=None):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
@@ -1334,9 +1369,10 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
     def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                              top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                              return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None,
-                             first_batch=1, batch_growth=2.0):
+                             true_peak=None, first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         _no_word_times("generate_long_stream", word_times)
+        _no_true_peak("generate_long_stream", true_peak)
         opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, guard=guard)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
@@ -1346,11 +1382,11 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate_batch(self, texts, language_ids, audio_prompt_paths=None, conds=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                        repetition_penalty=1.2, min_p=0.05, top_p=1.0, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                       word_times=False, guard=None, duration=None, timing=None):
+                       word_times=False, guard=None, duration=None, timing=None, true_peak=None):
         """ChatterboxTTS.generate_batch with a language per request: `language_ids` one id or a list of B, each validated as generate() does (after seeds and
         speed, before the sampling arguments)."""
         texts = _batch_of(texts)
-        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, duration=duration, timing=timing)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_batch(texts, language_ids, audio_prompt_paths, conds, samp, dict(exaggeration=exaggeration), opts)
 
@@ -1439,19 +1475,19 @@ class ChatterboxTurboTTS(_TTS):
         return dict(max_gen_len=1000) if batch else {}
 
     def generate(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0,
-                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None):
+                 temperature=0.8, top_k=1000, norm_loudness=True, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None, true_peak=None):
         """reference tts_turbo.py:272-320.  norm_loudness: prepare_conditionals' (used with an audio_prompt_path).  seed, speed, sample_rate, encoding, loudness: as
         ChatterboxTTS.generate."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
         self._use_voice(audio_prompt_path, exaggeration, norm_loudness=norm_loudness)
         self._warn_ignored(cfg_weight, exaggeration, min_p)
         return self._generate(self._text_ids(text), opts, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                       top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None):
+                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, true_peak=None):
         """ChatterboxTTS.generate_long on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other)."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), opts,
@@ -1459,9 +1495,10 @@ class ChatterboxTurboTTS(_TTS):
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                              top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None,
-                             speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, first_batch=1, batch_growth=2.0):
+                             speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, true_peak=None, first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other, so a piece is
         yielded before the next batch starts)."""
+        _no_true_peak("generate_long_stream", true_peak)
         opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         ramp = _long_stream_args(first_batch, batch_growth)
@@ -1470,11 +1507,11 @@ class ChatterboxTurboTTS(_TTS):
                                    ramp, norm_loudness=norm_loudness)
 
     def generate_batch(self, texts, audio_prompt_paths=None, conds=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8, repetition_penalty=1.2, min_p=0.00,
-                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None):
+                       top_p=0.95, top_k=1000, norm_loudness=True, generator=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None, true_peak=None):
         """generate() for B requests in one call (the contract of ChatterboxTTS.generate_batch; temperature, repetition_penalty, top_p, top_k: a number or a sequence
         of B).  CFG, min_p and exaggeration are ignored with generate()'s warning.  Sub-batches run one after the other."""
         texts = _batch_of(texts)
-        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
+        opts = _Options(self, len(texts), False, seeds=seeds, generator=generator, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_batch(texts, None, audio_prompt_paths, conds, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), opts,
                                     norm_loudness=norm_loudness)
@@ -1561,14 +1598,14 @@ class ChatterboxVC(_Finish):
             s3_tokens = self._tokens_of(audio)
         return torch.as_tensor(s3_tokens).view(-1).long().cpu()
 
-    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None):
+    def generate(self, audio=None, target_voice_path=None, s3_tokens=None, seed=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None, true_peak=None):
         """reference vc.py:83-104.  audio: a WAV path, a (waveform, sample_rate) pair or raw samples (data, sample_rate, encoding[, channels]) -- bytes or a uint8 /
         int16 / int32 / float32 array of interleaved frames in one of ops.WAVE_IN_ENCODINGS; with self.audio_in = "device" it is decoded and resampled on the device
         (a path then opens G.711 and 24-bit WAVs too).  seed, speed: as ChatterboxTTS.generate, where the draws of a conversion
         are the flow noise and the vocoder's phase and noise (there is no sampling), and the tokens are the source's.  sample_rate, encoding, loudness: as there.
         duration (None, or seconds in [0.02, 80]): ChatterboxTTS.generate(duration=)'s -- the conversion is fitted into that length; not with speed, pitch or
         max_pause; model.last_fit has the plan."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
         wavs, _ = self.engine.vocode([self._source_tokens(audio, target_voice_path, s3_tokens)], self.ref_dict, **opts.kw([0]))
         if opts.warped:
             self._take_fit(list(self.engine.last_fit), "generate")
@@ -1604,7 +1641,7 @@ class ChatterboxVC(_Finish):
 
     MAX_BATCH = 8  # utterances per device batch of generate_batch (flow + vocoder activations grow with batch x length)
 
-    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None):
+    def generate_batch(self, audios=None, target_voice_paths=None, ref_dicts=None, s3_tokens=None, seeds=None, speed=1.0, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, duration=None, true_peak=None):
         """generate() for B conversions in one call: `audios` (WAV paths, (waveform, sample_rate) pairs or raw (data, sample_rate, encoding[, channels]) tuples; with
         audio_in = "device" the sources of one (rate, encoding, channels) are uploaded and converted together) or `s3_tokens` (B id sequences); target voice per
         request from `target_voice_paths` (one, or a list of B; equal paths are analysed once) or `ref_dicts` (one S3Gen reference dict, or a list of B), neither:
@@ -1617,7 +1654,7 @@ class ChatterboxVC(_Finish):
         src = [src] if (isinstance(src, _PATH) or (torch.is_tensor(src) and src.dim() <= 1)) else list(src)
         B = len(src)
         assert B >= 1, "empty batch"
-        opts = _Options(self, B, False, seeds=seeds, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
+        opts = _Options(self, B, False, seeds=seeds, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, duration=duration)
         if target_voice_paths is not None and ref_dicts is not None:
             raise ValueError("give target_voice_paths or ref_dicts, not both")
         if target_voice_paths is not None:

@@ -73,7 +73,7 @@ def _valid_tokens(toks):
 
 def _checked_job(job):
     """A job of synthesize_pipelined with its optional keys checked as synthesize checks its arguments (check_delivery: seeds not together with the job's
-    generator, loudness not together with a join, speed x pitch).  A join of None is dropped: from here on `"join" in job` says whether the job is joined;
+    generator, loudness and true_peak not together with a join, speed x pitch).  A join of None is dropped: from here on `"join" in job` says whether the job is joined;
     likewise a format that is None or the default (24 kHz fp32), a loudness that normalises no utterance, pauses that shorten no utterance, a pitch that
     transposes no utterance and a guard of None.  seeds and speed keep their key when the job has one."""
     if job.get("words") is not None:
@@ -177,13 +177,14 @@ def check_warp(warp, B):
 
 
 LOUDNESS_JOIN = "loudness together with join: a long text is normalised as a whole, after its pieces are assembled (generate_long(loudness=))"
+TRUE_PEAK_JOIN = "true_peak together with join: a long text is limited as a whole, after its pieces are assembled (generate_long(true_peak=))"
 
 
 @dataclass(frozen=True)
 class Delivery:
     """The delivery options of one engine call for B utterances, checked and normalised (check_delivery): seeds (B ints), speed (B floats), pitch (B semitones),
     rates (the B rates at which the mel is stretched: speed, or speed / 2^(pitch / 12) under a pitch), join (ops.check_join's dict), fmt (ops.check_format's
-    dict), loud (B LUFS targets / Nones), pz (ops.check_pauses' dict).  Each is None when the option is off for every utterance -- the call is then, launch for
+    dict), loud (B LUFS targets / Nones), pz (ops.check_pauses' dict), peak (B true-peak ceilings in dBTP / Nones).  Each is None when the option is off for every utterance -- the call is then, launch for
     launch, the call without it."""
     seeds: Optional[list] = None
     speed: Optional[list] = None
@@ -193,19 +194,20 @@ class Delivery:
     fmt: Optional[dict] = None
     loud: Optional[list] = None
     pz: Optional[dict] = None
+    peak: Optional[list] = None  # ops.check_true_peak's list: per utterance None or a ceiling in dBTP
     warp: Optional[list] = None  # check_warp's list: per utterance None, dict(frames=) or dict(anchors=, end=)
-    OPTIONS = ("pitch", "join", "format", "loudness", "pauses", "warp")  # the keywords a call carries only when the option is on
+    OPTIONS = ("pitch", "join", "format", "loudness", "pauses", "true_peak", "warp")  # the keywords a call carries only when the option is on
 
     def kw(self):
         """The OPTIONS as the keywords of a downstream call (vocode, a job of synthesize_pipelined): a key is present only when its option is on.  seeds and speed
         are not among them: they travel as they were given."""
-        return {k: v for k, v in zip(self.OPTIONS, (self.pitch, self.join, self.fmt, self.loud, self.pz, self.warp)) if v is not None}
+        return {k: v for k, v in zip(self.OPTIONS, (self.pitch, self.join, self.fmt, self.loud, self.pz, self.peak, self.warp)) if v is not None}
 
 
-def check_delivery(B, *, seeds=None, generator=None, speed=None, pitch=None, join=None, format=None, loudness=None, pauses=None, warp=None):
+def check_delivery(B, *, seeds=None, generator=None, speed=None, pitch=None, join=None, format=None, loudness=None, pauses=None, true_peak=None, warp=None):
     """The one place where an engine entry (vocode, both synthesize methods, a job of synthesize_pipelined) checks its delivery options -> Delivery.  In this
     order: seeds (ops.request_seeds; not together with a generator), speed, pitch with the speed x pitch rule (ops.check_speed_pitch), join, format, loudness
-    (not together with a join: LOUDNESS_JOIN), pauses, warp (check_warp; not together with speed, pitch, pauses or a join: WARP_WITH).  TypeError / ValueError
+    (not together with a join: LOUDNESS_JOIN), true_peak (ops.check_true_peak; not together with a join: TRUE_PEAK_JOIN), pauses, warp (check_warp; not together with speed, pitch, pauses or a join: WARP_WITH).  TypeError / ValueError
     before anything is launched; a checked value passes unchanged."""
     seeds = ops.request_seeds(seeds, B, generator)
     speed = ops.check_speed(speed, B)
@@ -216,6 +218,9 @@ def check_delivery(B, *, seeds=None, generator=None, speed=None, pitch=None, joi
     loud = ops.check_loudness(loudness, B)
     if loud is not None and join is not None:
         raise ValueError(LOUDNESS_JOIN)
+    peak = ops.check_true_peak(true_peak, B)
+    if peak is not None and join is not None:
+        raise ValueError(TRUE_PEAK_JOIN)
     rates = speed if eff is None else (None if all(e == 1.0 for e in eff) else eff)
     pz = ops.check_pauses(pauses, B)
     warp = check_warp(warp, B)
@@ -223,7 +228,7 @@ def check_delivery(B, *, seeds=None, generator=None, speed=None, pitch=None, joi
         for name, on in (("speed", speed), ("pitch", pitch), ("max_pause (pauses)", pz), ("join", join)):
             if on is not None:
                 raise ValueError(WARP_WITH.format(name))
-    return Delivery(seeds, speed, pitch, rates, join, fmt, loud, pz, warp)
+    return Delivery(seeds, speed, pitch, rates, join, fmt, loud, pz, peak, warp)
 
 
 def _joined_on_host(out, rec, n, fmt, pauses, truncated):
@@ -248,6 +253,7 @@ class S3GenEngine:
     vocode, vocode_stream and the streams and kernel forms of the overlapped schedules.  On its own it is the engine of voice conversion (no T3);
     ChatterboxEngine and TurboEngine put their T3 in front of it."""
     t3 = None
+    last_limit = None  # set by a call with true_peak= (S3GenEngine.__init__ states the layout)
     last_fit = None  # per utterance of the last vocode(warp=) call: None (a plain row) or _fit_report's dict; None after a call without warp
 
     def __init__(self, s3gen_sd, device="cuda", meanflow=False):
@@ -256,12 +262,13 @@ class S3GenEngine:
         self.hift = HiFTEngine(s3gen_sd, self.dev)
         self.last_timing = {}
         self.last_loudness = None  # the (B, 4) float64 device tensor {L, peak, gain, blocks used} of the last call with loudness=; not synchronised
+        self.last_limit = None  # the (B, 4) float64 device tensor {true peak, min g, samples with g < 1, samples over the ceiling} of the last call with true_peak=; not synchronised
         self.last_pauses = None  # the (B, 4) int32 device tensor {n', pauses cut, frames removed, n} of the last call with pauses=; not synchronised
 
     @ops.on_device
     @torch.inference_mode()
     def vocode(self, speech_tokens, gen_ref, z=None, phase=None, noise=None, n_cfm_timesteps=10, drop_last_token=False, sync=True, hift_stream=None,
-               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None, warp=None):
+               generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None, warp=None, true_peak=None):
         """S3Gen.inference for a list of 1-D token tensors (already valid ids).  Returns (list of 1-D wav tensors on
         device, mel (B, 2Nmax, 80) channel-last).  hift_stream (synthesize_pipelined): the vocoder runs on THAT stream behind an event, so the flow
         stream is free for the next batch's encoder + CFM; the returned waveforms belong to it.  generator: a torch.Generator on the engine's device for the flow / vocoder noise
@@ -290,6 +297,14 @@ class S3GenEngine:
         1.0; a None entry, a silent utterance and one shorter than 0.4 s keep their samples.  It runs ahead of the format launch, whose s16 / G.711 store therefore
         sees the normalised signal and does not clip.  The stats {L, peak, gain, blocks used} of the call stay on the device as self.last_loudness; nothing is
         synchronised.  Not together with a join (ValueError): a long text is normalised as a whole.
+        true_peak (None, or no utterance with a ceiling: this call, launch for launch; else ops.check_true_peak's list -- a number or B numbers / Nones in [-20, 0]
+        dBTP): the true-peak limiter -- ONE ops.wave_limit call (cbx_wave_limit_f32, two launches) behind pitch and loudness, on the stream that owns the
+        waveforms, ahead of the pauses and the format launch, whose s16 / G.711 store therefore sees the limited signal: the 4-times oversampled peak of every row
+        with a ceiling is held under it by a look-ahead gain envelope (include/cbx.h states the definition).  A row with a loudness target AND a ceiling gets the
+        full gain to its target -- the sample-peak cap of 1.0 is the limiter's job there --; what the limiter removes is not measured again, so its loudness can
+        end below the target.  A row without a ceiling is what the call without true_peak returns, bit for bit.  The stats {true peak, min g, samples with
+        g < 1, samples over the ceiling} stay on the device as self.last_limit; nothing is synchronised.  It changes no length.  Not together with a join
+        (ValueError): a long text is limited as a whole.
         pauses (None, or no utterance with a keep: this call, launch for launch; else ops.check_pauses' dict(keep=[B ints], db=, fade=)): the pause control --
         ops.wave_squeeze (cbx_wave_squeeze_f32) on the stream that owns the waveforms, behind the loudness step (which measures and gains the unshortened rows) and
         ahead of the join and / or the format launch: of every silence inside utterance b that is longer than keep[b] frames of 480 samples, keep[b] remain.  The
@@ -314,7 +329,7 @@ class S3GenEngine:
         from it as speed= sizes them, and row b comes back with frames_b * 480 samples.  self.last_fit keeps the plans (_fit_report).  Not together with speed,
         pitch, pauses or a join (ValueError naming both).  The returned mel stays the flow's."""
         B = len(speech_tokens)
-        d = check_delivery(B, seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses, warp=warp)
+        d = check_delivery(B, seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses, warp=warp, true_peak=true_peak)
         seeds, rates = d.seeds, d.rates
         ns = [int(t.numel()) for t in speech_tokens]
         Nmax = max(ns)
@@ -381,7 +396,7 @@ class S3GenEngine:
 
     def _deliver(self, wav, ns, shorts, d, drop_last_token, sync, hift_stream, plans=None):
         """The chain behind the vocoder, in the one order vocode's docstring states: cut the rows of the padded batch `wav`, pitch, loudness, then either edges +
-        squeeze + join (ONE ops.wave_join call) or the squeeze alone, then the format.  Every launch lands on the stream that owns the waveforms: ONE stream
+        squeeze + join (ONE ops.wave_join call) or the squeeze alone, then the format; with a true_peak the loudness step and the limiter are _limit's.  Every launch lands on the stream that owns the waveforms: ONE stream
         scope, entered only when a step is on.  Returns the rows; the formatted views; with pauses the rows cut through ops.cut_pauses (sync=True) or
         dict(rows=, pauses=, format=) for the caller to cut (sync=False); with a join the piece dict, with `formatted` / `format` under a format."""
         HALF = SAMPLES_PER_TOKEN // 2
@@ -401,7 +416,9 @@ class S3GenEngine:
         with (torch.cuda.stream(hift_stream) if hift_stream is not None else contextlib.nullcontext()):
             if d.pitch is not None:  # the source rows, read at a step of r_b into the lengths of the call without a pitch
                 out = ops.wave_pitch(out, [ops.pitch_ratio(p) for p in d.pitch], [k * HALF for k in plain])
-            if d.loud is not None:
+            if d.peak is not None:
+                out = self._limit(out, d)
+            elif d.loud is not None:
                 self.last_loudness = ops.wave_normalize(out, d.loud)
             if d.join is not None:  # (a join that will be formatted writes into a zeroed buffer: converting all of it converts the piece)
                 cap = sum(int(w.numel()) for w in out) + sum(d.join["gaps"])
@@ -420,6 +437,30 @@ class S3GenEngine:
             if stats is None:
                 return out
             return ops.cut_pauses(out, stats.cpu(), d.fmt) if sync else dict(rows=out, pauses=stats, format=d.fmt)
+
+    def _limit(self, out, d):
+        """The loudness step and the true-peak limiter of a batch in which a row has a ceiling.  A row with a target AND a ceiling gets the FULL gain to its target
+        (the meter runs for it with ceiling=None; the limiter holds the peaks); a row with a target and no ceiling keeps the sample-peak cap of 1.0, and so the
+        bits of the call without true_peak.  The meter runs once per kind of row that is present (ops.wave_loudness per group); its gain vector goes into the ONE
+        limiter launch as the pre-gain, which every row of the batch passes -- a row without a ceiling is copied as x * gain, ops.wave_gain's bits, so
+        ops.wave_gain is not launched.  last_loudness / last_limit keep the stats on the device."""
+        gain = None
+        if d.loud is not None:
+            B = len(out)
+            capped = [b for b in range(B) if d.loud[b] is not None and d.peak[b] is None]
+            free = [b for b in range(B) if b not in capped]
+            if not capped:
+                self.last_loudness, gain = ops.wave_loudness(out, d.loud, None)
+            else:
+                self.last_loudness = torch.empty(B, 4, dtype=torch.float64, device=out[0].device)
+                gain = torch.empty(B, dtype=torch.float32, device=out[0].device)
+                for idx, ceiling in ((capped, 1.0), (free, None)):
+                    if idx:
+                        st, g = ops.wave_loudness([out[b] for b in idx], [d.loud[b] for b in idx], ceiling)
+                        at = torch.tensor(idx, device=g.device)
+                        self.last_loudness[at], gain[at] = st, g
+        out, self.last_limit = ops.wave_limit(out, d.peak, gain=gain)
+        return out
 
     def co_resident(self, on):
         """Both stages on (or off) the kernel forms whose workgroups can share a CU with the other stage's (T3Engine.co_resident, FlowEngine.co_resident)."""
@@ -495,7 +536,7 @@ class ChatterboxEngine(S3GenEngine):
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                    repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None,
                    noise=None, n_cfm_timesteps=10, drop_last_token=True, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None,
-                   words=None, guard=None, warp=None):
+                   words=None, guard=None, warp=None, true_peak=None):
         """Full hot path for B utterances.  Returns (wavs: list of 1-D device tensors, speech_tokens: list).  t3_conds / gen_ref: one voice or a list of B;
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar or a sequence of B; generator: torch.Generator (device) for every draw that is not injected.
         seeds: None, or B ints in [0, 2^64) (an int: the same for every utterance): every draw of utterance b that is not injected depends on seeds[b] alone
@@ -506,6 +547,8 @@ class ChatterboxEngine(S3GenEngine):
         format: None, or vocode(format=)'s dict -- the waveforms (the joined piece's `wav`) come back at that sample rate in that encoding.
         loudness: None, a number or B numbers / Nones in [-50, -5] LUFS -- vocode(loudness=): every utterance with a target is brought to it on the device (sample
         peak limited to 1.0); not together with a join.
+        true_peak: None, a number or B numbers / Nones in [-20, 0] dBTP -- vocode(true_peak=): every utterance with a ceiling is limited to it on the device, behind
+        the loudness step (which then applies its full gain); not together with a join.
         pauses: None, or vocode(pauses=)'s dict / list -- silences inside an utterance longer than its keep are shortened on the device; the waveforms come back cut
         to their new lengths, a joined piece gains `pauses` = the record {n', pauses cut, frames removed, n} per chunk as lists.
         pitch: None, a number or B numbers / Nones in [-12, 12] semitones -- vocode(pitch=): utterance b comes back transposed by pitch[b] at the length speed[b]
@@ -544,7 +587,7 @@ class ChatterboxEngine(S3GenEngine):
                 raise ValueError(f"words: {len(text_tokens)} utterances (at most {self.t3.MAX_BATCH}: the pass runs on the state of ONE device batch)")
             self.t3.check_align_heads(words["heads"])
         d = check_delivery(len(text_tokens), seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses,
-                           warp=warp)
+                           warp=warp, true_peak=true_peak)
         seeds = d.seeds
         self.co_resident(False)  # the serial schedule runs every kernel on its fastest-alone form (a no-op unless synthesize_pipelined ran before)
         t0 = time.perf_counter()
@@ -595,6 +638,7 @@ class ChatterboxEngine(S3GenEngine):
         or `format` (vocode(format=)'s dict: the job's audio is converted on the device ahead of its copies, which then carry the encoded samples),
         or `loudness` (vocode(loudness=): a number or one number / None per utterance; the meter and the gain run behind the vocoder on its stream; not with a join),
         or `pitch` (vocode(pitch=): a number or one number / None per utterance, semitones; the launch runs behind the vocoder on its stream),
+        or `true_peak` (vocode(true_peak=): a number or one number / None per utterance, dBTP; the limiter runs behind the vocoder on its stream; not with a join),
         or `warp` (vocode(warp=)'s list, entries of the duration kind -- None or dict(frames=) -- only: anchors need the alignment pass of the serial schedule,
         WARP_PIPELINED; engine.last_fit is the job's report while the job is the one just yielded),
         or `guard` (T3Engine.generate(guard=)'s dict: the job's T3 runs with the alignment guard inside its token step, in whichever of the two T3 states it
@@ -649,7 +693,7 @@ class ChatterboxEngine(S3GenEngine):
             is called exactly as before there was one)"""
             wavs, _ = self.vocode(st, job["gen_ref"], z=job.get("z"), phase=job.get("phase"), noise=job.get("noise"), generator=job.get("generator"), seeds=job.get("seeds"),
                                   speed=job.get("speed"), n_cfm_timesteps=kw.get("n_cfm_timesteps", 10), drop_last_token=kw.get("drop_last_token", True), sync=False,
-                                  **({k: job[k] for k in ("join", "format", "loudness", "pauses", "pitch", "warp") if k in job}))
+                                  **({k: job[k] for k in ("join", "format", "loudness", "pauses", "pitch", "warp", "true_peak") if k in job}))
             if "warp" in job:
                 job["_fit"] = self.last_fit  # (the job's own dict, _checked_job's copy: the report travels with it to the yield)
             return wavs
@@ -1270,16 +1314,17 @@ class TurboEngine(S3GenEngine):
     @ops.on_device
     @torch.inference_mode()
     def synthesize(self, text_tokens, t3_conds, gen_ref, *, max_gen_len=1000, temperature=0.8, top_k=1000, top_p=0.95,
-                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None, warp=None):
+                   repetition_penalty=1.2, uniforms=None, ban_eos=False, ban_from=0, z=None, phase=None, noise=None, generator=None, seeds=None, speed=None, join=None, format=None, loudness=None, pauses=None, pitch=None, warp=None, true_peak=None):
         """t3_conds / gen_ref: one voice or a list of B; temperature, top_k, top_p, repetition_penalty: a scalar or a sequence of B; generator: torch.Generator (device)
         for every draw that is not injected; seeds: None, an int or B ints in [0, 2^64) -- the per-utterance draws of ChatterboxEngine.synthesize(seeds=);
         speed: None, a number or B numbers in [0.5, 2.0] -- the speaking rate of vocode(speed=); join: None, or vocode(join=)'s dict -- the call then returns
         ChatterboxEngine.synthesize(join=)'s piece (truncated: T3 sampled all max_gen_len + 1 tokens without EOS); format: None, or vocode(format=)'s dict; loudness: None, or vocode(loudness=)'s targets (not with a join);
         pauses: None, or vocode(pauses=)'s dict / list, as ChatterboxEngine.synthesize(pauses=) returns its results; pitch: None, or vocode(pitch=)'s semitones,
         checked against speed before anything is launched as ChatterboxEngine.synthesize(pitch=) does; warp: None, or vocode(warp=)'s list with entries of the
-        duration kind (None or dict(frames=)): anchors need an alignment pass, which the GPT-2 backbone does not have."""
+        duration kind (None or dict(frames=)): anchors need an alignment pass, which the GPT-2 backbone does not have; true_peak: None, or vocode(true_peak=)'s
+        ceilings in dBTP (not with a join)."""
         d = check_delivery(len(text_tokens), seeds=seeds, generator=generator, speed=speed, pitch=pitch, join=join, format=format, loudness=loudness, pauses=pauses,
-                           warp=warp)
+                           warp=warp, true_peak=true_peak)
         if d.warp is not None and any(w is not None and "anchors" in w for w in d.warp):
             raise ValueError("warp with anchors (timing) on the Turbo engine: the alignment pass on the GPT-2 backbone is not built -- dict(frames=) only")
         seeds = d.seeds

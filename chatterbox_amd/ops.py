@@ -1894,6 +1894,142 @@ def wave_normalize(rows, target, ceiling=1.0, fs=WAVE_IN_RATE):
     return stats
 
 
+# ----------------------------------------------------------------------------- true-peak limiter: a dBTP ceiling with look-ahead (wave_limit.hip)
+TRUE_PEAK_MIN, TRUE_PEAK_MAX = -20.0, 0.0   # dBTP ceilings a caller may ask for
+LIMIT_OVERSAMPLE = 4                        # U: the true peak is read on the 4-times oversampled signal (ITU-R BS.1770-4 annex 2 asks for at least 4 at 48 kHz)
+LIMIT_LOOK = 120                            # H: look-ahead and release, samples at 24 kHz (5 ms).  UNMEASURED choice
+LIMIT_LOOK_MAX = 480
+_LIMIT_FILTER, _LIMIT_WINDOWS, _LIMIT_TABLES = [], {}, {}
+
+
+def true_peak_filter():
+    """The oversampler of the true-peak meter, wave_filter's design (scipy.signal.resample_poly's, restated in NumPy fp64): U = 4, hl = 10 U = 40,
+    h = U firwin(2 hl + 1, 1 / U, window=("kaiser", 5.0)), tab (U, T) fp32 = h[p + j U] (zero past 2 hl), T = ceil((2 hl + 1) / U) = 21.  Built once."""
+    import numpy as np
+    if not _LIMIT_FILTER:
+        U = LIMIT_OVERSAMPLE
+        hl, cutoff = 10 * U, 1.0 / U
+        i = np.arange(2 * hl + 1, dtype=np.float64) - hl
+        h = cutoff * np.sinc(cutoff * i) * np.kaiser(2 * hl + 1, 5.0)
+        h = U * (h / h.sum())
+        T = -(-(2 * hl + 1) // U)
+        pad = np.zeros(U * T)
+        pad[: 2 * hl + 1] = h
+        _LIMIT_FILTER.append(dict(U=U, hl=hl, T=T, h=h, tab=np.ascontiguousarray(pad.reshape(T, U).T.astype(np.float32))))
+    return _LIMIT_FILTER[0]
+
+
+def limit_window(H=LIMIT_LOOK):
+    """The limiter's smoothing window for a look-ahead of H samples (1 .. 480): w_k ~ 0.5 (1 + cos(pi k / (H + 1))), k = -H .. H, normalised to sum 1 in fp64,
+    as 2 H + 1 float32 (cbx_wave_limit_f32's `win`).  Built once per H."""
+    import numpy as np
+    if isinstance(H, bool) or not isinstance(H, int):
+        raise TypeError(f"limit_window: H: expected an int, got {type(H).__name__}")
+    if not 1 <= H <= LIMIT_LOOK_MAX:
+        raise ValueError(f"limit_window: H = {H} outside [1, {LIMIT_LOOK_MAX}]")
+    if H not in _LIMIT_WINDOWS:
+        w = 0.5 * (1.0 + np.cos(np.pi * np.arange(-H, H + 1, dtype=np.float64) / (H + 1)))
+        _LIMIT_WINDOWS[H] = (w / w.sum()).astype(np.float32)
+    return _LIMIT_WINDOWS[H]
+
+
+def _limit_tables(H, device):
+    """(phase table, window) on `device`, uploaded once per (device, H)"""
+    key = (str(device), H)
+    if key not in _LIMIT_TABLES:
+        _LIMIT_TABLES[key] = (torch.from_numpy(true_peak_filter()["tab"]).to(device), torch.from_numpy(limit_window(H)).to(device))
+    return _LIMIT_TABLES[key]
+
+
+def check_true_peak(value, B, name="true_peak"):
+    """A `true_peak` argument as a list of B entries -- a float (the ceiling of that request in dBTP) or None (that request is not limited) --, or None when no
+    request is limited.  A number serves every request; anything else must be a list or tuple of exactly B numbers or Nones, each number finite and in [-20, 0].
+    A bool or a non-number is a TypeError; a non-finite or out-of-range value and a wrong length are ValueErrors -- raised before anything is launched."""
+    import math
+    import numbers
+    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+    if value is None:
+        return None
+    if one(value):
+        value = [value] * B
+    elif not isinstance(value, (list, tuple)):
+        raise TypeError(f"{name}: expected None, a number or a list of {B} numbers, got {type(value).__name__}")
+    if len(value) != B:
+        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
+    out = []
+    for k, v in enumerate(value):
+        if v is not None:
+            if not one(v):
+                raise TypeError(f"{name}[{k}]: expected None or a number, got {type(v).__name__}")
+            v = float(v)
+            if not math.isfinite(v) or not TRUE_PEAK_MIN <= v <= TRUE_PEAK_MAX:
+                raise ValueError(f"{name}[{k}] = {v}: a true-peak ceiling is a finite number of dBTP in [{TRUE_PEAK_MIN}, {TRUE_PEAK_MAX}]")
+        out.append(v)
+    return None if all(v is None for v in out) else out
+
+
+def _wave_limit_launch(rows, ceilings, gain, look, out):
+    """One cbx_wave_limit_f32 call on the current stream.  ceilings: R linear ceilings / Nones; out: None (measure only) or R rows of the lengths of `rows`, views
+    of ONE allocation that is not the rows'.  Returns the (R, 4) stats on the device."""
+    base, offs, lens = _wave_rows(rows, "wave_limit")
+    R, dev, f = len(lens), rows[0].device, true_peak_filter()
+    if len(ceilings) != R:
+        raise ValueError(f"wave_limit: {len(ceilings)} ceilings for {R} rows")
+    tab, win = _limit_tables(look, dev)
+    ceil = (ctypes.c_double * R)(*[float("nan") if c is None else float(c) for c in ceilings])
+    if gain is not None:
+        assert gain.dtype == torch.float32 and gain.numel() == R and gain.is_contiguous() and gain.device == dev, "wave_limit: gain is (R,) fp32 on the rows' device"
+    obase, ooffs, cap = None, None, 0
+    if out is not None:
+        obase, o, olens = _wave_rows(out, "wave_limit: out")
+        if list(olens) != list(lens):
+            raise ValueError("wave_limit: the rows of out have other lengths than the rows")
+        ooffs, cap = ctypes.addressof(o), max((a + n for a, n in zip(o, olens)), default=0)
+    stats = torch.empty(R, 4, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, 4 * R * -(-max(lens) // 1024)), dtype=torch.float64, device=dev)
+    check(lib.cbx_wave_limit_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, _p(gain), ctypes.addressof(ceil), _p(tab), f["U"], f["T"], _p(win), look,
+                                 obase, ooffs, cap, _p(stats), _p(ws), ws.numel(), _stream()), "cbx_wave_limit_f32")
+    return stats
+
+
+def _empty_limit_stats(rows):
+    return torch.tensor([[0.0, 1.0, 0.0, 0.0]] * len(rows), dtype=torch.float64).to(rows[0].device)
+
+
+def wave_true_peak(rows):
+    """cbx_wave_limit_f32 as a meter, on the current stream: the true peak (4-times oversampled, linear) of every row (_wave_rows: 1 .. 64 1-D fp32 views of ONE
+    allocation at 24 kHz).  Returns the (R, 4) float64 stats {true peak (NaN for a row with a NaN), 1, 0, 0} on the device; nothing is written but them, nothing is
+    synchronised."""
+    rows = list(rows)
+    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+        return _empty_limit_stats(rows)
+    return _wave_limit_launch(rows, [None] * len(rows), None, LIMIT_LOOK, None)
+
+
+def wave_limit(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None):
+    """cbx_wave_limit_f32 on the current stream: every row (_wave_rows: 1 .. 64 1-D fp32 views of ONE allocation at 24 kHz) times gain[r] (an (R,) fp32 device
+    tensor, wave_loudness's; None: 1) and held under its true-peak ceiling by a look-ahead limiter of `look` samples (include/cbx.h states the definition).
+    ceilings_db: a number of dBTP, or R numbers / Nones (None: the row is not limited and comes back as x * gain, wave_gain's bits); no range is imposed here
+    (check_true_peak is the public arguments' check).  Returns (out_rows, stats): out_rows are views of ONE new allocation in the layout of `rows` (out: R rows of
+    the same lengths in an allocation of the caller's instead), stats (R, 4) float64 {true peak of x * gain, min g, samples with g < 1, samples over the ceiling} on
+    the device.  Two launches, nothing is synchronised."""
+    rows = list(rows)
+    if ceilings_db is None or not isinstance(ceilings_db, (list, tuple)):
+        ceilings_db = [ceilings_db] * len(rows)
+    ceil = [None if c is None else 10.0 ** (float(c) / 20.0) for c in ceilings_db]
+    limit_window(look)
+    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+        return (list(out) if out is not None else [torch.empty(0, dtype=torch.float32, device=w.device) for w in rows]), _empty_limit_stats(rows)
+    if out is None:
+        base, offs, lens = _wave_rows(rows, "wave_limit")
+        lo = min(a for a, n in zip(offs, lens) if n)
+        buf = torch.empty(max(a + n for a, n in zip(offs, lens) if n) - lo, dtype=torch.float32, device=rows[0].device)
+        out = [buf[a - lo: a - lo + n] if n else buf[:0] for a, n in zip(offs, lens)]
+    else:
+        out = list(out)
+    return out, _wave_limit_launch(rows, ceil, gain, look, out)
+
+
 # ----------------------------------------------------------------------------- audio in: decode + mixdown + resample, trim edges (wave_ingest.hip)
 WAVE_IN_ENCODINGS = ("u8", "s16", "s24", "s32", "f32", "mulaw", "alaw")   # cbx_wave_ingest's encoding 0 .. 6 (CBX_WAVE_IN_*)
 WAVE_IN_SAMPLE_BYTES = dict(u8=1, s16=2, s24=3, s32=4, f32=4, mulaw=1, alaw=1)

@@ -1103,6 +1103,42 @@ int cbx_wave_loudness_push_f32(const float* wav, const long* row_off, const int*
  * -22 before any launch: a null pointer, R outside [1, 64], a negative length or offset. */
 int cbx_wave_gain_f32(float* wav, const long* row_off, const int* row_len, int R, const float* gain, void* stream);
 
+/* ---- true-peak limiter: hold the rows of a batch under a dBTP ceiling (added after ABI v16 without a version step: new function only).  The reference has no
+ * counterpart: it returns the vocoder's output as is (tts.py:272, mtl_tts.py:352, tts_turbo.py:320, vc.py:104).  Rows as cbx_wave_gain_f32 takes them: R in
+ * [1, 64] rows of row_len[r] floats at wav + row_off[r] (HOST arrays; 4-byte alignment is enough).
+ * Inputs per row r: x, n fp32 samples; a pre-gain gamma = gain[r] (R device floats; NULL: 1); a linear ceiling C = ceiling[r] > 0 (R HOST doubles; NaN: the row
+ * is not limited), used as C32 = (float)C.  Two tables built by the CALLER in fp64, in device memory:
+ *   tab: the oversampler.  hl = 10 U, h = U firwin(2 hl + 1, 1 / U, window = ("kaiser", 5.0)) -- cbx_wave_format_f32's design --, tab[p * T + j] = h[p + j U] (zero
+ *     past 2 hl), T = ceil((2 hl + 1) / U).  The product uses U = 4, T = 21.
+ *   win: the smoothing window, 2 H + 1 floats w_k proportional to 0.5 (1 + cos(pi k / (H + 1))), k = -H .. H, normalised to sum 1 in fp64 (win[k + H]).  H is the
+ *     look-ahead in samples; the product uses H = 120 (5 ms at 24 kHz).
+ * Definition, in fp32:
+ *   1. u[i] = x[i] * gamma: one multiply, the bits cbx_wave_gain_f32 would store.
+ *   2. y[k] = sum_i u[i] h[k - U i + hl] for k = 0 .. U n - 1 (scipy.signal.resample_poly's alignment: y[U i] is centred on u[i]); samples outside [0, n) are 0.
+ *      With k = U i + p: y[k] = sum_(j = 0 .. T - 1) tab[p][j] u[i + 10 - j], by fmaf in the order j = 0 .. T - 1 from 0 (the taps of h ascending).
+ *   3. m[i] = max(|u[i]|, |y[U i]|, .., |y[U i + U - 1]|); NaN when one of them is.
+ *   4. c[i] = C32 / m[i] (one IEEE division) where m[i] is finite and > C32, else 1; c = 1 outside [0, n).
+ *   5. a[i] = min over |j - i| <= H of c[j], for i in [-H, n + H).
+ *   6. s[i] = sum_(k = -H .. H) w_k (1 - a[i + k]), 1 - a rounded once, then fmaf in the order k = -H .. H from 0; g[i] = min(1 - s[i], c[i]).
+ *   7. out[i] = u[i] * g[i].
+ * Properties: |out[i]| <= C32 up to the two roundings of steps 4 and 7, at the samples and at the U - 1 oversampled points between them of u c; every a[i + k] of
+ * step 6 has i inside its window, so 1 - s[i] <= c[i] holds in exact arithmetic and the min only absorbs rounding.  A row with m <= C32 everywhere returns u bit for
+ * bit: every term of s is exactly 0.  A row with C = NaN likewise returns u (the bits cbx_wave_gain_f32 gives), so a batch that mixes limited and other rows needs no
+ * launch of cbx_wave_gain_f32.  The result does not depend on the grid, the tile a sample falls into or the row's alignment, bit for bit.
+ * stats: (R, 4) device doubles {the true peak of u = max_i m[i] (NaN when an m is NaN; 0 for an empty row), min_i g[i], the samples with g < 1, the samples with
+ * m > C32 (an infinite m counts)}.  out: one fp32 buffer of out_cap floats, row r's n_r outputs at out + out_off[r] (HOST array); NULL (out_off may then be NULL):
+ * measure only, stats alone are written.  wav is only read; out must not overlap it; nothing outside the rows of out is written.  16-byte loads and stores inside a
+ * row where alignment allows, 4-byte accesses at the ragged ends.
+ * One workgroup per tile of 1024 outputs of a row (wave_limit.hip): u over tile +- 2 H plus the filter's reach in LDS, the sliding minimum by doubling passes, the
+ * smoothing sum in the order above.  Per-tile partial stats go to ws; a second launch folds them per row (max, min and integer counts: exact in any order).  No
+ * floating-point atomics.  Two launches; ONE, the fold, when every row is empty: it writes {0, 1, 0, 0} per row.  Nothing synchronises the host.
+ * ws: device workspace of ws_cap >= 4 * R * ceil(max_r n_r / 1024) doubles (not NULL).
+ * -22 before any launch, nothing written: a null pointer other than gain / out (out_off may be NULL only with out), R outside [1, 64], a negative length or
+ * offset, U outside [1, 8], T < 1 or U T > 1024, H outside [1, 480], a ceiling that is <= 0 or infinite (or whose float is), a row that would write outside
+ * [0, out_cap), out overlapping wav, a workspace that is too small. */
+int cbx_wave_limit_f32(const float* wav, const long* row_off, const int* row_len, int R, const float* gain, const double* ceiling, const float* tab, int U, int T,
+                       const float* win, int H, float* out, const long* out_off, long out_cap, double* stats, double* ws, long ws_cap, void* stream);
+
 /* ---- audio in: decode, mix down and resample the raw sample bytes of voice prompts and conversion sources, and find the silence at their ends, on the device
  * (added after ABI v16 without a version step: new functions only).  The mirror image of cbx_wave_format_f32.  It replaces frontend.load_wav / resample /
  * trim_silence (NumPy / SciPy on the host), which restate librosa.load, librosa.resample and librosa.effects.trim of the reference (tts.py:184-187,
