@@ -102,6 +102,24 @@ def test_gemv_epilogue_prefetch_on_the_emulator(emu, name, args, monkeypatch):
     test_zz_abi_v9_gpu.test_gemv_epilogue_prefetch_equals_plain(CPU, name, args, monkeypatch)
 
 
+# tests/test_wide_batch_decode_gpu.py (wide_batch_common.py: the decode forms above 16 rows): the kernel bodies in full (under a second each), and the Turbo engine
+# body on both sides of the 16-row seam -- B = 17 is the 7-launch form, B = 16 the packed layer (11 s each; the larger batches are left to the GPU)
+def _wide_batch_cases():
+    import wide_batch_common as W
+    cases = [("check_gemv_wide_rows_packed_weight", (M, *s)) for M in W.GEMV_M for s in W.GEMV_SHAPES]
+    cases += [("check_add_norm_layernorm_wide", c) for c in W.ADD_NORM_CASES]
+    return cases + [("check_turbo_engine_vs_oracle", (17,)), ("check_turbo_engine_vs_oracle", (16,))]
+
+
+_WIDE = _wide_batch_cases()
+
+
+@pytest.mark.parametrize("name,args", _WIDE, ids=[f"{n}{list(a)}" for n, a in _WIDE])
+def test_wide_batch_decode_bodies_on_the_emulator(emu, name, args):
+    import wide_batch_common as W
+    getattr(W, name)(CPU, *args)
+
+
 # tests/test_sampler_gpu.py and tests/test_frontend_ops_gpu.py at emulator sizes (the sampler: 10 utterances per launch, one seed, a reduced matrix that keeps both
 # orders, cfg 0 / 1, dev_params, V < 1024, V not a multiple of 1024, the ties and the state machine)
 _SAMPLER = [("test_sampler_matrix", (0, 10, 1, True)), ("test_sampler_matrix", (1, 10, 1, True)),
