@@ -740,6 +740,10 @@ class _TTS(_Finish):
 
     def __init__(self, engine, tokenizer, device, conds: Optional[Conditionals] = None, analyzer=None):
         self.engine, self.tokenizer, self.device, self.conds = engine, tokenizer, device, conds
+        # the sub-batches of generate_batch / generate_long stay ONE T3 call and one vocoder call each (engine.synthesize_pipelined pairs the T3 of consecutive
+        # jobs by default): a request's draws, reports and first audio are defined per sub-batch here, and a pair would make the first sub-batch wait for the second
+        if getattr(engine, "t3_pair", False):
+            engine.t3_pair = False
         self.analyzer = analyzer  # frontend.PromptAnalyzer (S3 tokenizer + CAMPPlus + voice encoder + 24 kHz mel) or None
         self.t3, self.s3gen, self.ve = engine.t3, engine, (analyzer.ve if analyzer is not None else None)
         self.watermarker = _watermarker()

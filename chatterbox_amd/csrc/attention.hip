@@ -573,12 +573,14 @@ __global__ __launch_bounds__(256) void decode_attn_rope_kernel(const float* __re
         float qv = qp[lane], kn0 = qp[(long)n_heads * 64 + lane], vn0 = qp[(long)n_heads * 128 + lane];
         if (qkv_nparts > 1) {  // uniform (kernel argument): qkv holds split-K partial sums of the RMSNorm-folded projection (cbx_gemv_t.col_tiles,
             // ksplit > 1): added in fixed order, then rstd[row] of the projection's input.  Loads unconditional (clamped part index), one round trip
+            // qkv_ssq is [part][rows padded to whole 16-row tiles] (gemv_ct_kernel: 16 floats per part up to 16 rows, 32 up to 32 rows)
+            const int ssq_ld = ((int)gridDim.y + 15) & ~15;
             float sq = qkv_ssq[row];
 #pragma unroll
             for (int j = 1; j < 4; ++j) {
                 const bool onj = j < qkv_nparts;
                 const float* qj = qp + (onj ? j : 0) * qkv_part_stride;
-                const float a = qj[lane], b = qj[(long)n_heads * 64 + lane], cc = qj[(long)n_heads * 128 + lane], sj = qkv_ssq[(onj ? j : 0) * 16 + row];
+                const float a = qj[lane], b = qj[(long)n_heads * 64 + lane], cc = qj[(long)n_heads * 128 + lane], sj = qkv_ssq[(onj ? j : 0) * ssq_ld + row];
                 if (onj) qv += a, kn0 += b, vn0 += cc, sq += sj;
             }
             const float rstd = rsqrtf(sq / rms_dim + rms_eps);  // the expression of gemv_kernel / gemv_ct_kernel with ksplit == 1
@@ -871,8 +873,8 @@ extern "C" int cbx_decode_attn_rope(const cbx_decode_attn_t* pd, void* stream) {
     CBX_REQUIRE(a.unroll == 0 || a.unroll == 4 || a.unroll == 8 || a.unroll == 16, "decode_attn_rope: unroll must be 0 (= 4), 4, 8 or 16");
     CBX_REQUIRE(a.pipeline >= 0 && a.pipeline <= 7 && a.split_min >= 0, "decode_attn_rope: pipeline in 0 .. 7, split_min >= 0");
     CBX_REQUIRE(!(a.pipeline & 4) || a.cache_head_stride >= 64 * 64, "decode_attn_rope: the speculative first step needs 64 cache positions per (row, head)");
-    CBX_REQUIRE(a.qkv_nparts >= 0 && a.qkv_nparts <= 4 && (a.qkv_nparts <= 1 || (a.qkv_ssq && a.rms_dim > 0 && a.rows <= 16 && a.qkv_part_stride % 4 == 0)),
-                "decode_attn_rope: qkv_nparts in 0 .. 4; partial sums need qkv_ssq, rms_dim and rows <= 16");
+    CBX_REQUIRE(a.qkv_nparts >= 0 && a.qkv_nparts <= 4 && (a.qkv_nparts <= 1 || (a.qkv_ssq && a.rms_dim > 0 && a.rows <= 32 && a.qkv_part_stride % 4 == 0)),
+                "decode_attn_rope: qkv_nparts in 0 .. 4; partial sums need qkv_ssq, rms_dim and rows <= 32");
     const int nparts = a.qkv_nparts > 1 ? a.qkv_nparts : 1;
     const float inv_dim = a.rms_dim > 0 ? (float)a.rms_dim : 1.f;  // (passed as the dimension itself)
     // contexts shorter than this are walked by one workgroup even on a split grid (the hand-off costs more than it saves below ~3 round trips)

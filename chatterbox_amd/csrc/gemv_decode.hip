@@ -29,7 +29,7 @@ CBX_TRC_TU
 // c[m] = the median of channels 0, K/2 and K - 1 of the (summed) row (gemv_ln_pivot): a value of the row itself, so x - c is exact
 // wherever the row's spread is small against its offset, and one outlier channel cannot become the pivot.  The form is a template
 // parameter (LN): the RMSNorm kernels carry none of it.
-// NP > 0 (RMS variants, <= 16 rows): the x operand is x + sum_{j < NP} xpart[j] -- the split-K partial images of the PRODUCING
+// NP > 0 (RMS variants, <= 32 rows = one or two row tiles): the x operand is x + sum_{j < NP} xpart[j] -- the split-K partial images of the PRODUCING
 // projection are reduced (fixed order) on the way to the MFMA instead of by a separate kernel; workgroup 0 also writes the sum
 // (the new residual stream) to x_out.  Every workgroup re-reads the NP + 1 images from L2: NP * 64 KiB extra per workgroup,
 // which is cheaper than a dependent launch (~1.8 us boundary + a cross-XCD round trip) only for small NP.
@@ -69,7 +69,7 @@ __device__ __forceinline__ float gemv_ln_pivot(const float* __restrict__ x, cons
 template <int MT, int NW, bool SWIGLU, bool PK, bool XPK, bool RMS, int NP, bool WB = false, bool D8 = false, bool D2 = false, bool LN = false>
 __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
     __builtin_amdgcn_s_setprio(3);  // decode-step kernels are latency-bound and issue little: beside a co-resident workgroup of another stream (the throughput schedule, profiles/r05_overlap_*) their waves go first at the SIMD's issue arbiter; alone on the CU it changes nothing
-    static_assert(NP == 0 || (RMS && MT == 1), "partial-sum operand: RMS variant, one row tile");
+    static_assert(NP == 0 || (RMS && MT <= 2), "partial-sum operand: RMS variant, one or two row tiles");
     static_assert(!WB || (PK && XPK), "bf16 weights: packed operands only");
     static_assert(!LN || (RMS && !SWIGLU), "LayerNorm form: the norm-folded packed kernel, no swiglu");
     __shared__ __attribute__((aligned(16))) float red[(SWIGLU ? 2 : 1) * NW * MT * 256];
@@ -199,13 +199,16 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
             for (int j = 0; j < EIT; ++j) e_cw[j] = p.ln_cw[e_n[j]], e_cb[j] = p.ln_cb[e_n[j]];
         }
     }
-    constexpr int DEPTH = D8 ? 8 : (MT == 1 && !D2) ? 4 : 2;  // K blocks (2 KiB of W per wave each) issued before the first MFMA
+    // K blocks (2 KiB of W per wave each) issued before the first MFMA.  Two row tiles (17 .. 32 rows: the paired batches of the throughput schedule) keep the
+    // one-tile depth where the register file allows it: not with partial images folded in (NP > 0: 4 blocks x 2 tiles x (1 + NP) images would need > 256
+    // VGPRs); the 16-wave form fits its 128 at depth 4 (124).  The depth only groups the loads: every row's products and their order are the one-tile form's.
+    constexpr int DEPTH = D8 ? 8 : D2 ? 2 : MT == 1 ? 4 : (MT == 2 && NP == 0) ? 4 : 2;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // Loads are UNCONDITIONAL (out-of-range lanes / K blocks re-read a valid address and are zeroed by a select): a predicated
     // load makes hipcc join all of them behind one vmcnt(0); unconditional ones get counted waits, so the MFMAs of K block d
     // start while blocks d+1.. are still in flight.
     for (int it0 = 0; it0 < nit; it0 += DEPTH) {
-        f32x4 wv[DEPTH][2], uv[DEPTH][2], xv[DEPTH][MT][2], nv[DEPTH][2], pv[DEPTH][NP > 0 ? NP : 1][2];
+        f32x4 wv[DEPTH][2], uv[DEPTH][2], xv[DEPTH][MT][2], nv[DEPTH][2], pv[DEPTH][NP > 0 ? NP : 1][NP > 0 ? MT : 1][2];
         bool on[DEPTH];
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d) {
@@ -230,11 +233,13 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
             }
             if constexpr (NP > 0) {
 #pragma unroll
-                for (int j = 0; j < NP; ++j) {
-                    const float* pp = p.xpart + (long)j * p.xpart_stride + (xp[0] - p.x);
-                    pv[d][j][0] = *reinterpret_cast<const f32x4*>(pp + xoff);
-                    pv[d][j][1] = *reinterpret_cast<const f32x4*>(pp + xoff + 256);
-                }
+                for (int j = 0; j < NP; ++j)
+#pragma unroll
+                    for (int t = 0; t < MT; ++t) {  // (a partial image is laid out as x is: tile t at the same offset)
+                        const float* pp = p.xpart + (long)j * p.xpart_stride + (xp[t] - p.x);
+                        pv[d][j][t][0] = *reinterpret_cast<const f32x4*>(pp + xoff);
+                        pv[d][j][t][1] = *reinterpret_cast<const f32x4*>(pp + xoff + 256);
+                    }
             }
             __builtin_amdgcn_sched_barrier(0);  // keep the issue order block by block, so block d's wait is vmcnt(later blocks)
         }
@@ -259,9 +264,9 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
                     f32x4 xq = xv[d][t][h];
                     if constexpr (NP > 0) {
 #pragma unroll
-                        for (int j = 0; j < NP; ++j) xq += pv[d][j][h];
-                        if (p.x_out && blockIdx.x == 0 && on[d] && xok[0])  // the reduced residual stream, same packed address as x (pad rows stay as allocated: zero)
-                            cbx_store_out4(p.x_out + (xp[0] - p.x) + (it0 + d) * 512 + h * 256, xq);
+                        for (int j = 0; j < NP; ++j) xq += pv[d][j][t][h];
+                        if (p.x_out && blockIdx.x == 0 && on[d] && xok[t])  // the reduced residual stream, same packed address as x (pad rows stay as allocated: zero)
+                            cbx_store_out4(p.x_out + (xp[t] - p.x) + (it0 + d) * 512 + h * 256, xq);
                     }
                     if constexpr (LN) xq -= piv[t];  // after x_out took the unshifted sum
                     xq = (on[d] && xok[t]) ? xq : zero4;
@@ -378,13 +383,17 @@ __global__ __launch_bounds__(NW * 64) void gemv_kernel(const cbx_gemv_t p) {
 // ssq_out[ks][m] (written by column group 0): rstd factors out of the contraction, so the CONSUMER -- the decode attention, which reads 192
 // values per workgroup -- adds the ksplit partials in fixed order and applies rstd = rsqrt(sum_ks ssq / K + eps).  ksplit == 1: rstd in the
 // epilogue as above.  Same MFMA, same fixed-order LDS reduction over the 8 waves; deterministic.
-template <int CT, int NP, int DEPTH, bool LN = false>
+// MT = 2 (17 .. 32 rows: two batches of the throughput schedule decoded as one chain): a wave requests each weight K block ONCE and issues one MFMA per row
+// tile with it.  The tiles share the weight registers and nothing else -- waves, K slice per wave, ksplit, MFMA order, the order of the LDS reduction and of
+// every fold are the one-tile launch's, so every row is bit for bit what a one-tile launch on its 16-row image gives.  x, x_out and the partial images hold two
+// whole tiles (pad rows zero); ssq_out is [ksplit][16 * MT].
+template <int CT, int NP, int DEPTH, bool LN = false, int MT = 1>
 __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
     __builtin_amdgcn_s_setprio(3);  // decode-step kernels are latency-bound and issue little: beside a co-resident workgroup of another stream (the throughput schedule, profiles/r05_overlap_*) their waves go first at the SIMD's issue arbiter; alone on the CU it changes nothing
     constexpr int NW = 8;
-    __shared__ __attribute__((aligned(16))) float red[NW * CT * 256];
-    __shared__ float ssq[NW * 16];
-    __shared__ float ssx[LN ? NW * 16 : 1];  // row sums (LayerNorm form: ln_cw / ln_cb, ksplit == 1)
+    __shared__ __attribute__((aligned(16))) float red[NW * MT * CT * 256];
+    __shared__ float ssq[NW * MT * 16];
+    __shared__ float ssx[LN ? NW * MT * 16 : 1];  // row sums (LayerNorm form: ln_cw / ln_cb, ksplit == 1)
     CBX_TRC_DECL;
     CBX_TRC_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -401,22 +410,30 @@ __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
         wok[c] = tile0 + c < ntiles;
         wp[c] = p.W + ((long)(wok[c] ? tile0 + c : tile0) * KB + kb0) * 512 + lane * 4;  // [tile][K/32][2][64][4]; a tile past N re-reads tile0
     }
-    const bool xok = (lane & 15) < p.M;
-    const long xo = kb0 * 512 + (xok ? lane : (lane & 48)) * 4;  // packed x: [K/32][2][64][4] (one 16-row tile); rows past M read row 0's bytes (gemv_kernel)
-    const float* nwp = p.norm_w + kb0 * 32 + 8 * (lane >> 4);
-    f32x4 acc[CT];
+    bool xok[MT];
+    long xo[MT];
 #pragma unroll
-    for (int c = 0; c < CT; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float ss = 0.f;
-    [[maybe_unused]] float sx = 0.f;  // row sum (LayerNorm form)
+    for (int t = 0; t < MT; ++t) {
+        xok[t] = t * 16 + (lane & 15) < p.M;
+        xo[t] = ((long)t * KB + kb0) * 512 + (xok[t] ? lane : (lane & 48)) * 4;  // packed x: [row tile][K/32][2][64][4]; rows past M read row 0's bytes of their tile (gemv_kernel)
+    }
+    const float* nwp = p.norm_w + kb0 * 32 + 8 * (lane >> 4);
+    f32x4 acc[MT][CT];
+    float ss[MT];
+    [[maybe_unused]] float sx[MT];  // row sums (LayerNorm form)
+    [[maybe_unused]] float piv[MT];  // LayerNorm form: this lane's row pivots, the expression of gemv_kernel
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        ss[t] = 0.f, sx[t] = 0.f, piv[t] = 0.f;
+        if constexpr (LN) piv[t] = gemv_ln_pivot<NP>(p.x + (long)t * KB * 512, NP > 0 ? p.xpart + (long)t * KB * 512 : nullptr, p.xpart_stride, p.K, xok[t] ? (lane & 15) : 0);
+    }
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    // LayerNorm form: this lane's row pivot, the expression of gemv_kernel
-    [[maybe_unused]] float piv = 0.f;
-    if constexpr (LN) piv = gemv_ln_pivot<NP>(p.x, p.xpart, p.xpart_stride, p.K, xok ? (lane & 15) : 0);
     // DEPTH = K blocks requested per batch (picked by the host so that it divides the wave's block count: an idle slot would re-read a block,
     // i.e. spend the very per-CU bytes this form saves; registers: DEPTH * 2 * (CT + NP + 2) float4)
     for (int it0 = 0; it0 < nit; it0 += DEPTH) {
-        f32x4 wv[DEPTH][CT][2], xv[DEPTH][2], nv[DEPTH][2], pv[DEPTH][NP > 0 ? NP : 1][2];
+        f32x4 wv[DEPTH][CT][2], xv[DEPTH][MT][2], nv[DEPTH][2], pv[DEPTH][NP > 0 ? NP : 1][NP > 0 ? MT : 1][2];
         bool on[DEPTH];
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d) {
@@ -427,17 +444,22 @@ __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
                 wv[d][c][0] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(wp[c] + blk * 512));
                 wv[d][c][1] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(wp[c] + blk * 512 + 256));
             }
-            xv[d][0] = *reinterpret_cast<const f32x4*>(p.x + xo + blk * 512);
-            xv[d][1] = *reinterpret_cast<const f32x4*>(p.x + xo + blk * 512 + 256);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                xv[d][t][0] = *reinterpret_cast<const f32x4*>(p.x + xo[t] + blk * 512);
+                xv[d][t][1] = *reinterpret_cast<const f32x4*>(p.x + xo[t] + blk * 512 + 256);
+            }
             nv[d][0] = *reinterpret_cast<const f32x4*>(nwp + blk * 32);
             nv[d][1] = *reinterpret_cast<const f32x4*>(nwp + blk * 32 + 4);
             if constexpr (NP > 0) {
 #pragma unroll
-                for (int j = 0; j < NP; ++j) {
-                    const float* pp = p.xpart + (long)j * p.xpart_stride + xo + blk * 512;
-                    pv[d][j][0] = *reinterpret_cast<const f32x4*>(pp);
-                    pv[d][j][1] = *reinterpret_cast<const f32x4*>(pp + 256);
-                }
+                for (int j = 0; j < NP; ++j)
+#pragma unroll
+                    for (int t = 0; t < MT; ++t) {
+                        const float* pp = p.xpart + (long)j * p.xpart_stride + xo[t] + blk * 512;
+                        pv[d][j][t][0] = *reinterpret_cast<const f32x4*>(pp);
+                        pv[d][j][t][1] = *reinterpret_cast<const f32x4*>(pp + 256);
+                    }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -448,78 +470,84 @@ __global__ __launch_bounds__(512) void gemv_ct_kernel(const cbx_gemv_t p) {
         for (int d = 0; d < DEPTH; ++d) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                f32x4 xq = xv[d][h];
-                if constexpr (NP > 0) {
 #pragma unroll
-                    for (int j = 0; j < NP; ++j) xq += pv[d][j][h];
-                    if (p.x_out && blockIdx.x == 0 && on[d] && xok)  // the reduced residual stream (this wave's K slice), same packed address as x; pad rows stay zero
-                        cbx_store_out4(p.x_out + xo + (it0 + d) * 512 + h * 256, xq);
-                }
-                if constexpr (LN) xq -= piv;  // after x_out took the unshifted sum
-                xq = (on[d] && xok) ? xq : zero4;
-                ss += (xq[0] * xq[0] + xq[1] * xq[1]) + (xq[2] * xq[2] + xq[3] * xq[3]);
-                if constexpr (LN) sx += (xq[0] + xq[1]) + (xq[2] + xq[3]);
-                xq *= nv[d][h];
+                for (int t = 0; t < MT; ++t) {
+                    f32x4 xq = xv[d][t][h];
+                    if constexpr (NP > 0) {
 #pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    const f32x4 wq = (on[d] && wok[c]) ? wv[d][c][h] : zero4;
+                        for (int j = 0; j < NP; ++j) xq += pv[d][j][t][h];
+                        if (p.x_out && blockIdx.x == 0 && on[d] && xok[t])  // the reduced residual stream (this wave's K slice), same packed address as x; pad rows stay zero
+                            cbx_store_out4(p.x_out + xo[t] + (it0 + d) * 512 + h * 256, xq);
+                    }
+                    if constexpr (LN) xq -= piv[t];  // after x_out took the unshifted sum
+                    xq = (on[d] && xok[t]) ? xq : zero4;
+                    ss[t] += (xq[0] * xq[0] + xq[1] * xq[1]) + (xq[2] * xq[2] + xq[3] * xq[3]);
+                    if constexpr (LN) sx[t] += (xq[0] + xq[1]) + (xq[2] + xq[3]);
+                    xq *= nv[d][h];
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(xq[s], wq[s], acc[c], 0, 0, 0);
+                    for (int c = 0; c < CT; ++c) {
+                        const f32x4 wq = (on[d] && wok[c]) ? wv[d][c][h] : zero4;  // the weight registers: requested once, one MFMA per row tile
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) acc[t][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(xq[s], wq[s], acc[t][c], 0, 0, 0);
+                    }
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
 #ifdef CBX_TRACE
             if (it0 == 0 && d == 0) {
-                asm volatile("s_nop 0" ::"v"(acc[0][0]));
+                asm volatile("s_nop 0" ::"v"(acc[0][0][0]));
                 CBX_TRC_STAMP(2);
             }
 #endif
         }
     }
 #ifdef CBX_TRACE
-    asm volatile("s_nop 0" ::"v"(acc[0][0]));
+    asm volatile("s_nop 0" ::"v"(acc[0][0][0]));
     CBX_TRC_STAMP(3);
 #endif
     // fixed-order reduction over the 8 K slices of this workgroup.  D map of the MFMA: row = q*4 + r, col = c16
     const int c16 = lane & 15, q = lane >> 4;
 #pragma unroll
-    for (int c = 0; c < CT; ++c)
+    for (int t = 0; t < MT; ++t) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) red[(w * CT + c) * 256 + (q * 4 + r) * 16 + c16] = acc[c][r];
-    {
-        float v = ss;
+        for (int c = 0; c < CT; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[((w * MT + t) * CT + c) * 256 + (q * 4 + r) * 16 + c16] = acc[t][c][r];
+        float v = ss[t];
         v += cbx_xor_lane<16>(v);
         v += cbx_xor_lane<32>(v);
-        if (q == 0) ssq[w * 16 + c16] = v;
+        if (q == 0) ssq[(w * MT + t) * 16 + c16] = v;
         if constexpr (LN) {
-            float u = sx;
+            float u = sx[t];
             u += cbx_xor_lane<16>(u);
             u += cbx_xor_lane<32>(u);
-            if (q == 0) ssx[w * 16 + c16] = u;
+            if (q == 0) ssx[(w * MT + t) * 16 + c16] = u;
         }
     }
     __syncthreads();
     CBX_TRC_STAMP(4);
-    for (int e = tid; e < CT * 256; e += NW * 64) {
-        const int c = e >> 8, rc = e & 255, row = rc >> 4, col = rc & 15;
+    for (int e = tid; e < MT * CT * 256; e += NW * 64) {
+        const int t = e / (CT * 256), ec = e - t * (CT * 256);
+        const int c = ec >> 8, rc = ec & 255, r16 = rc >> 4, col = rc & 15;
+        const int row = t * 16 + r16;  // row of the launch; r16: its row in tile t
         const int n = (tile0 + c) * 16 + col;
         if (row >= p.M || n >= p.N) continue;
         float v = 0.f, sq = 0.f;
 #pragma unroll
-        for (int ww = 0; ww < NW; ++ww) v += red[(ww * CT + c) * 256 + rc];
+        for (int ww = 0; ww < NW; ++ww) v += red[((ww * MT + t) * CT + c) * 256 + rc];
 #pragma unroll
-        for (int ww = 0; ww < NW; ++ww) sq += ssq[ww * 16 + row];
+        for (int ww = 0; ww < NW; ++ww) sq += ssq[(ww * MT + t) * 16 + r16];
         if constexpr (LN) {  // LayerNorm form (GPT-2 ln_f + head; ksplit == 1) on the shifted row: the expression of gemv_kernel
             float su = 0.f;
 #pragma unroll
-            for (int ww = 0; ww < NW; ++ww) su += ssx[ww * 16 + row];
+            for (int ww = 0; ww < NW; ++ww) su += ssx[(ww * MT + t) * 16 + r16];
             const float mean = su / (float)p.K;
             const float rstd = rsqrtf(fmaxf(sq / (float)p.K - mean * mean, 0.f) + p.eps);
             v = rstd * (v - mean * p.ln_cw[n]) + p.ln_cb[n];
         } else if (p.ksplit == 1) {
             v *= rsqrtf(sq / (float)p.K + p.eps);
         } else if (blockIdx.x == 0 && c == 0 && col == 0) {
-            cbx_store_out(p.ssq_out + ks * 16 + row, sq);  // this K slice's sum of squares of row `row` (identical in every column group: group 0 writes it)
+            cbx_store_out(p.ssq_out + ks * (16 * MT) + row, sq);  // this K slice's sum of squares of row `row` (identical in every column group: group 0 writes it)
         }
         cbx_store_out(p.out + (long)ks * p.part_stride + (long)row * p.ldo + n, v);
     }
@@ -536,6 +564,21 @@ int launch_ct_np(const cbx_gemv_t& p, hipStream_t st) {
     const int ntiles = (p.N + 15) / 16;
     dim3 grid((ntiles + CT - 1) / CT, p.ksplit);
     const int nit = p.K / (32 * p.ksplit * 8);  // K blocks per wave
+    if (p.M > 16) {  // two row tiles (checked: M <= 32, col_tiles <= 3, no LayerNorm form).  The one-tile depth of two K blocks per batch, except with FOUR
+        // partial images folded in: 2 blocks x 2 tiles x 5 images x 2 float4 = 160 registers of activations alone beside the weights' 48 do not fit 256 VGPRs,
+        // so that form requests one block per batch (every row's arithmetic is unchanged; its K loop pays one dependent round trip more per block)
+        if constexpr (CT <= 3) {
+            if constexpr (NP < 4) {
+                if (nit % 2 == 0) {
+                    hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 2, false, 2>), grid, dim3(512), 0, st, p);
+                    return cbx_check_launch("gemv (column tiles, two row tiles)");
+                }
+            }
+            hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 1, false, 2>), grid, dim3(512), 0, st, p);
+            return cbx_check_launch("gemv (column tiles, two row tiles)");
+        }
+        return cbx_set_error(CBX_EINVAL, "gemv: col_tiles=4 serves M <= 16");
+    }
     if (p.ln_cw) {  // LayerNorm form (checked: ksplit == 1)
         if (nit % 2 == 0) hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 2, true>), grid, dim3(512), 0, st, p);
         else hipLaunchKernelGGL((gemv_ct_kernel<CT, NP, 1, true>), grid, dim3(512), 0, st, p);
@@ -557,7 +600,7 @@ int g_gemv_pre_epi = 0;  // cbx_set_gemv_epilogue_prefetch
 
 template <int MT, bool SWIGLU, bool PK, bool XPK, bool RMS, int NP = 0, bool WB = false, bool LN = false>
 int launch_nw(const cbx_gemv_t& p, hipStream_t st) {
-    if constexpr (RMS && !SWIGLU && !LN) {
+    if constexpr (RMS && !SWIGLU && !LN && !(MT == 2 && NP > 0)) {
         if (p.ln_cw) return launch_nw<MT, false, PK, XPK, true, NP, WB, true>(p, st);  // LayerNorm form: the kernels with the pivot shift
     }
     const int tc = PK ? gemv_tile_cols(p.half_tile) : 16;
@@ -575,9 +618,17 @@ int launch_nw(const cbx_gemv_t& p, hipStream_t st) {
             return cbx_check_launch("gemv");
         }
     }
-    if constexpr (MT == 1 && SWIGLU && PK && XPK && RMS && NP == 0 && !WB) {
+    if constexpr (MT <= 2 && SWIGLU && PK && XPK && RMS && NP == 0 && !WB) {
         if ((p.flags & CBX_GEMV_SHALLOW) && p.nw >= 8) {
-            hipLaunchKernelGGL((gemv_kernel<1, 8, true, true, true, true, 0, false, false, true>), grid, dim3(512), 0, st, p);
+            hipLaunchKernelGGL((gemv_kernel<MT, 8, true, true, true, true, 0, false, false, true>), grid, dim3(512), 0, st, p);
+            return cbx_check_launch("gemv");
+        }
+    }
+    // Two row tiles on packed operands (17 .. 32 rows of the five-launch decode layer): the workgroup geometry of the one-tile launch -- 16 K slices where it
+    // takes 16 -- so that every row is reduced exactly as its one-tile launch reduces it.  (CBX_GEMV_DEEP only regroups the loads: the two-tile form ignores it.)
+    if constexpr (MT == 2 && !SWIGLU && !RMS && PK && XPK && !WB) {
+        if (p.nw == 16) {
+            hipLaunchKernelGGL((gemv_kernel<2, 16, false, true, true, false, 0, false>), grid, dim3(1024), 0, st, p);
             return cbx_check_launch("gemv");
         }
     }
@@ -608,6 +659,10 @@ int launch_pk(const cbx_gemv_t& p, hipStream_t st) {
             if (p.n_xpart == 2) return launch_nw<1, SWIGLU, true, true, true, 2>(p, st);
             if constexpr (!SWIGLU)  // (the swiglu form would need > 256 VGPRs with 4 partial images in flight)
                 if (p.n_xpart == 4) return launch_nw<1, false, true, true, true, 4>(p, st);
+        }
+        if constexpr (MT == 2 && !SWIGLU) {  // two row tiles: the RMSNorm form only (checked: no ln_cw with xpart above 16 rows)
+            if (p.n_xpart == 2) return launch_nw<2, false, true, true, true, 2>(p, st);
+            if (p.n_xpart == 4) return launch_nw<2, false, true, true, true, 4>(p, st);
         }
         return launch_nw<MT, SWIGLU, true, true, true>(p, st);
     }
@@ -837,14 +892,16 @@ extern "C" int cbx_gemv_f32(const cbx_gemv_t* pp, void* stream) {
     CBX_REQUIRE(!p.norm_w || (p.w_packed && p.x_packed && (p.ksplit == 1 || p.col_tiles > 0)), "gemv: norm_w needs w_packed, x_packed and ksplit == 1 (or col_tiles)");
     CBX_REQUIRE(!p.res || p.ksplit == 1, "gemv: res needs ksplit == 1");
     CBX_REQUIRE(!p.ln_cw || (p.norm_w && p.ln_cb && !p.swiglu && !p.bias), "gemv: the LayerNorm form needs norm_w, ln_cb, no swiglu, bias folded into ln_cb");
-    CBX_REQUIRE(p.n_xpart == 0 || p.col_tiles > 0 || (p.norm_w && p.xpart && p.M <= 16 && (p.n_xpart == 2 || (p.n_xpart == 4 && !p.swiglu)) && p.nw == 8 && p.x_out != p.x),
-                "gemv: xpart needs norm_w, M <= 16, n_xpart in {2, 4}, nw == 8 and x_out != x");
+    CBX_REQUIRE(p.n_xpart == 0 || p.col_tiles > 0 || (p.norm_w && p.xpart && p.M <= 32 && (p.n_xpart == 2 || (p.n_xpart == 4 && !p.swiglu)) && p.nw == 8 && p.x_out != p.x),
+                "gemv: xpart needs norm_w, M <= 32, n_xpart in {2, 4}, nw == 8 and x_out != x");
+    CBX_REQUIRE(p.n_xpart == 0 || p.M <= 16 || (!p.swiglu && !p.ln_cw && !p.w_bf16), "gemv: xpart at 17 .. 32 rows serves the plain RMSNorm-folded fp32 form");
     CBX_REQUIRE(!p.out_packed || p.N % 32 == 0, "gemv: out_packed needs N %% 32 == 0");
     CBX_REQUIRE(!(p.w_packed || p.x_packed) || p.K % 32 == 0, "gemv: packed operands need K %% 32 == 0");
     if (p.col_tiles > 0) {  // column-tile / split-K form of the RMSNorm-folded packed GEMV (gemv_ct_kernel)
         CBX_REQUIRE(p.col_tiles <= 4 && p.norm_w && p.w_packed && p.x_packed && !p.w_bf16 && !p.swiglu && !p.bias && !p.res && !p.act && !p.out_packed &&
-                        p.half_tile == 0 && p.M <= 16 && (!p.ln_cw || (p.ln_cb && p.ksplit == 1)),
-                    "gemv: col_tiles serves the plain RMSNorm- / LayerNorm-folded packed fp32 form (M <= 16, 16-column image, no bias / residual / activation; LayerNorm form: ksplit == 1)");
+                        p.half_tile == 0 && p.M <= 32 && (!p.ln_cw || (p.ln_cb && p.ksplit == 1)),
+                    "gemv: col_tiles serves the plain RMSNorm- / LayerNorm-folded packed fp32 form (M <= 32, 16-column image, no bias / residual / activation; LayerNorm form: ksplit == 1)");
+        CBX_REQUIRE(p.M <= 16 || (p.col_tiles <= 3 && !p.ln_cw), "gemv: col_tiles at 17 .. 32 rows: at most 3 column tiles, RMSNorm form");
         CBX_REQUIRE(p.K % (256 * p.ksplit) == 0 && (p.ksplit == 1 || p.ssq_out), "gemv: col_tiles needs K %% (256 * ksplit) == 0, and ssq_out with ksplit > 1");
         CBX_REQUIRE(p.n_xpart == 0 || ((p.n_xpart == 2 || p.n_xpart == 4) && p.xpart && p.x_out != p.x), "gemv: col_tiles with xpart: 2 or 4 images, x_out != x");
         hipStream_t st = (hipStream_t)stream;

@@ -24,7 +24,8 @@ extern "C" int cbx_trace_set(unsigned long long* buf, unsigned* cnt, unsigned ca
 
 extern "C" int cbx_t3_decode_step(const cbx_t3_step_t* d, void* stream) {
     CBX_REQUIRE(d && d->layers && d->n_layers > 0, "t3_decode_step: null descriptor");
-    CBX_REQUIRE(d->rows >= 1 && d->rows <= 16, "t3_decode_step: rows=%d (this entry point serves the packed <= 16-row path)", d->rows);
+    CBX_REQUIRE(d->rows >= 1 && d->rows <= 32, "t3_decode_step: rows=%d (this entry point serves the packed <= 32-row path)", d->rows);
+    CBX_REQUIRE(d->rows <= 16 || (!d->w_bf16 && d->qkv_ct <= 3 && d->head_ct <= 3), "t3_decode_step: 17 .. 32 rows need fp32 images and at most 3 column tiles per workgroup");
     CBX_REQUIRE(d->d_ksplit == 1 || d->d_ksplit == 2 || d->d_ksplit == 4, "t3_decode_step: d_ksplit must be 1, 2 or 4");
     const int qks = d->qkv_ksplit > 1 ? d->qkv_ksplit : 1;  // ABI v11: the q/k/v projection as split-K partial sums folded by the attention launch
     CBX_REQUIRE(qks == 1 || ((qks == 2 || qks == 4) && d->dim % (256 * qks) == 0 && d->qkv_ct >= 1 && d->qkv_ct <= 4 && d->qkv_ssq && d->qkv_tile == 0 && !d->w_bf16),

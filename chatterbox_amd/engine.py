@@ -505,6 +505,7 @@ class S3GenEngine:
 
 class ChatterboxEngine(S3GenEngine):
     last_guard = None  # the alignment guard's per-utterance report of the last guarded synthesize() call / synthesize_pipelined job yielded
+    t3_pair = True     # synthesize_pipelined(t3_pair=None): pair the T3 of jobs 2p and 2p + 1 (the public classes of api.py switch it off for their sub-batches)
 
     def __init__(self, t3_sd, s3gen_sd, device="cuda", n_t3_layers=None, meanflow=False, t3_weights=None):
         self.dev = torch.device(device)
@@ -628,7 +629,7 @@ class ChatterboxEngine(S3GenEngine):
         """Per utterance of a joined piece: T3 spent its budget without sampling an end-of-speech token (generate keeps a sampled one in `toks`)."""
         return [not bool((t == STOP_SPEECH).any()) for t in toks]
     @torch.inference_mode()
-    def synthesize_pipelined(self, jobs, co_resident=True, host_threads=True, t3_in_flight=2, stream_priorities=(-1, 0), **kw):
+    def synthesize_pipelined(self, jobs, co_resident=True, host_threads=True, t3_in_flight=2, stream_priorities=(-1, 0), t3_pair=None, **kw):
         """Throughput mode for a stream of batches: T3 of batch k+1 runs on a high-priority HIP stream WHILE the flow
         matching + vocoder of batch k run on a second stream.  jobs: list of dicts(text_tokens=[...], t3_conds=..., gen_ref=...); yields
         (wavs, tokens, latency_s) per job in order.  Results are identical to synthesize() called per job.  A job may carry sampling parameters of its own
@@ -657,7 +658,14 @@ class ChatterboxEngine(S3GenEngine):
           * host_threads: the decode loop is 250 hipGraph launches of 153 kernel nodes -- ~0.6 ms of HOST time each, invisible in the serial schedule
             (the GPU needs 1.1 ms per token) but 150-180 ms per batch in front of the flow's own ~130 ms of launches when one thread enqueues both
             (scripts/overlap_probe.py: the flow started 180 ms late).  The T3 enqueue runs on a second host thread (graph launches and the ctypes
-            calls of the C stage seams release the GIL)."""
+            calls of the C stage seams release the GIL).
+        t3_pair (host_threads only; None: the engine's t3_pair attribute -- True --, unless CBX_T3_PAIR=0 in the environment): jobs 2p and 2p + 1 decode as ONE T3Engine.generate call of up to 32 rows --
+        two row tiles per launch, every decode launch streams its weights once for both jobs and each row is bit for bit what its own 16-row launch gives
+        (T3Engine._packed_rows); t3_in_flight such calls are in flight.  A pair forms when the two jobs' rows sum to <= 32, neither
+        carries a guard, and both inject uniforms, or neither does and both or neither carry seeds; sampling parameters, uniforms and seeds reach the rows of their
+        own job.  The pair's tokens are split per job: flow + vocoder of job 2p, then of job 2p + 1, beside the next pair's T3.  Any other job, and the last of an
+        odd count, runs alone as before; the yield order, the per-job results, last_guard and last_fit are unchanged (the first audio of job 2p waits for the
+        pair's T3).  False: today's schedule, call for call."""
         import threading
         jobs = [_checked_job(job) for job in jobs]
         for job in jobs:  # `guard` (T3Engine.generate(guard=)'s dict): the job's T3 runs guarded, in either slot; engine.last_guard is its report when the job is yielded
@@ -751,17 +759,34 @@ class ChatterboxEngine(S3GenEngine):
         q, stop = queue.Queue(), threading.Event()
         n_slots = max(2, n_t3)
         slot_free = [threading.Semaphore(1) for _ in range(n_slots)]
+        if t3_pair is None:
+            t3_pair = bool(self.t3_pair) and os.environ.get("CBX_T3_PAIR", "1") != "0"
+        # units of T3 work: [k] (a job alone: generate() exactly as before) or [2p, 2p + 1] (one paired call)
+        units, k = [], 0
+        while k < len(jobs):
+            pair = None
+            if t3_pair and k % 2 == 0 and k + 1 < len(jobs):
+                pair = _paired_t3_call(jobs[k], jobs[k + 1], job_kw(jobs[k]), job_kw(jobs[k + 1]), int(kw.get("max_new_tokens", 1000)))
+            units.append(([k, k + 1], pair) if pair is not None else ([k], None))
+            k += len(units[-1][0])
+        # (paired calls keep the t3_in_flight chains: measured on one MI355X, headline command, two 32-row chains 249.8 audio-s/wall-s against 231.2 for the
+        # unpaired schedule and 233.8 for ONE 32-row chain beside the flow with the co-resident stream attribute on -- profiles/r07_pair_schedule_ab.jsonl)
 
         def worker():
             try:
                 torch.cuda.set_device(self.dev)
-                for k, job in enumerate(jobs):
-                    slot_free[k % n_slots].acquire()
+                for u, (ks, pair) in enumerate(units):
+                    slot_free[u % n_slots].acquire()
                     if stop.is_set():
                         return
                     t_start = time.perf_counter()
-                    with torch.inference_mode(), torch.cuda.stream(self._s_t3x[k % n_t3]):
-                        h = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), seeds=job.get("seeds"), slot=k % n_slots, **job_kw(job))
+                    job = jobs[ks[0]]
+                    with torch.inference_mode(), torch.cuda.stream(self._s_t3x[u % n_t3]):
+                        if pair is None:
+                            h = self.t3.generate(job["t3_conds"], job["text_tokens"], async_mode=True, uniforms=job.get("uniforms"), seeds=job.get("seeds"), slot=u % n_slots, **job_kw(job))
+                        else:
+                            pkw = dict(pair)
+                            h = self.t3.generate(pkw.pop("conds"), pkw.pop("text_tokens"), async_mode=True, slot=u % n_slots, two_tile=True, **pkw)
                         ev = torch.cuda.Event()
                         ev.record()
                     q.put((h, ev, t_start))
@@ -794,20 +819,25 @@ class ChatterboxEngine(S3GenEngine):
         th = threading.Thread(target=worker, name="cbx-t3-enqueue", daemon=True)
         th.start()
         try:
-            for k, job in enumerate(jobs):
+            for u, (ks, pair) in enumerate(units):
                 item = q.get()
                 if isinstance(item, BaseException):
                     raise item
                 h, ev, t0 = item
                 with torch.cuda.stream(self._s_voc):
                     self._s_voc.wait_event(ev)
-                    toks = self.t3.collect(h)  # blocks this thread until T3(k) is done; T3(k + 1) is already enqueued behind it
-                    rep = self.t3.last_guard if "guard" in job else None
-                slot_free[k % n_slots].release()
-                st = _valid_tokens(toks)
-                host, evv = start_voc(job, st, k % 2)
-                inflight.append((job, st, t0, host, evv, k % 2, toks, rep))
-                yield finish(*inflight.popleft())
+                    toks_u = self.t3.collect(h)  # blocks this thread until this unit's T3 is done; the next unit's is already enqueued behind it
+                    rep = self.t3.last_guard if "guard" in jobs[ks[0]] else None  # (a guarded job is never paired)
+                slot_free[u % n_slots].release()
+                lo = 0
+                for k in ks:  # the pair's tokens go back to their jobs, in order
+                    job = jobs[k]
+                    toks = toks_u[lo:lo + len(job["text_tokens"])]
+                    lo += len(job["text_tokens"])
+                    st = _valid_tokens(toks)
+                    host, evv = start_voc(job, st, k % 2)
+                    inflight.append((job, st, t0, host, evv, k % 2, toks, rep))
+                    yield finish(*inflight.popleft())
             while inflight:
                 yield finish(*inflight.popleft())
         finally:
@@ -861,6 +891,44 @@ class ChatterboxEngine(S3GenEngine):
                                       first_chunk=first_chunk, chunk=chunk, chunk_growth=chunk_growth, lookahead=lookahead, fade=fade, z=z, phase=phase,
                                       noise=noise, n_cfm_timesteps=n_cfm_timesteps, drop_last_token=drop_last_token, overlap=overlap, first_alone=first_alone,
                                       run_ahead=run_ahead, window=window, seeds=seeds, speed=speed, format=format)
+
+
+_T3_SAMPLING_DEFAULTS = dict(temperature=0.8, top_p=1.0, min_p=0.05, repetition_penalty=1.2, cfg_weight=0.5)  # T3Engine.generate's
+
+
+def _paired_t3_call(job_a, job_b, kw_a, kw_b, max_new_tokens):
+    """The keyword arguments of ONE T3Engine.generate call that decodes two jobs of synthesize_pipelined(t3_pair=True) -- utterances of job_a first --, or None when
+    the two cannot share a call: more than 32 rows, a guard, or draws that one call cannot express (uniforms in one job only; seeds in one job only).  kw_a / kw_b:
+    each job's own T3 keywords (the call's, overridden by the job's).  Everything that differs between the jobs travels per utterance."""
+    na, nb = len(job_a["text_tokens"]), len(job_b["text_tokens"])
+    if 2 * (na + nb) > 32 or "guard" in kw_a or "guard" in kw_b:
+        return None
+    ua, ub = job_a.get("uniforms"), job_b.get("uniforms")
+    sa, sb = job_a.get("seeds"), job_b.get("seeds")
+    if (ua is None) != (ub is None) or (ua is None and (sa is None) != (sb is None)):
+        return None
+    out = {k: v for k, v in kw_a.items() if k not in _T3_SAMPLING_DEFAULTS}
+    if out != {k: v for k, v in kw_b.items() if k not in _T3_SAMPLING_DEFAULTS}:
+        return None
+    per_utt = lambda v, n: [float(x) for x in v] if isinstance(v, (list, tuple)) or torch.is_tensor(v) else [float(v)] * n
+    for key, default in _T3_SAMPLING_DEFAULTS.items():
+        if key in kw_a or key in kw_b:
+            va, vb = per_utt(kw_a.get(key, default), na), per_utt(kw_b.get(key, default), nb)
+            if len(va) != na or len(vb) != nb:
+                return None  # (a wrong length: let the job's own call raise as it always did)
+            out[key] = va + vb
+    conds = lambda job, n: list(job["t3_conds"]) if isinstance(job["t3_conds"], (list, tuple)) else [job["t3_conds"]] * n
+    out["conds"], out["text_tokens"] = conds(job_a, na) + conds(job_b, nb), list(job_a["text_tokens"]) + list(job_b["text_tokens"])
+    if ua is not None:
+        rows = lambda u, n: torch.as_tensor(u, dtype=torch.float32).reshape(n, -1)
+        ua, ub = rows(ua, na), rows(ub, nb)
+        if min(ua.shape[1], ub.shape[1]) < max_new_tokens:
+            return None
+        out["uniforms"] = torch.cat([ua[:, :max_new_tokens], ub[:, :max_new_tokens].to(ua.device)])
+    elif sa is not None:
+        ints = lambda v, n: [int(x) for x in v] if isinstance(v, (list, tuple)) or torch.is_tensor(v) else [int(v)] * n
+        out["seeds"] = ints(sa, na) + ints(sb, nb)
+    return out
 
 
 def _stream_plan(n_tokens, done, exhausted, lookahead):

@@ -658,11 +658,11 @@ def decode_attn_rope(qkv, positions, cos_t, sin_t, kc, vc, out, scale, out_packe
     """Fused RoPE + KV append + decode attention: qkv (rows, 3*H*64), caches (rows,H,max,64), out (rows, H*64)
     [out_packed: the packed operand image of the o-projection gemv, (ceil(rows/16)*16, H*64)].
     geom: a DecodeAttnGeom (the engines: geometry and workspace per call); None = the positional entry point on the process-wide test hooks.
-    qkv (nparts, rows, 3*H*64) + qkv_ssq (nparts, 16) + rms_dim: split-K partial sums of the RMSNorm-folded projection (gemv(col_tiles=..., ksplit > 1))."""
+    qkv (nparts, rows, 3*H*64) + qkv_ssq (nparts, rows padded to 16; rows <= 32) + rms_dim: split-K partial sums of the RMSNorm-folded projection (gemv(col_tiles=..., ksplit > 1))."""
     rows, H = kc.shape[0], kc.shape[1]
     nparts = 0
     if qkv.dim() == 3:
-        assert geom is not None and qkv_ssq is not None and rms_dim > 0 and qkv.shape[0] <= 4 and qkv_ssq.shape == (qkv.shape[0], 16)
+        assert geom is not None and qkv_ssq is not None and rms_dim > 0 and qkv.shape[0] <= 4 and qkv_ssq.shape == (qkv.shape[0], max(16, (rows + 15) // 16 * 16))
         nparts = qkv.shape[0]
     if geom is None:
         check(lib.cbx_decode_attn_rope_f32(_p(qkv), _p(positions), _p(cos_t), _p(sin_t), _p(kc), _p(vc), _p(out), rows, H,

@@ -361,10 +361,11 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
 
     @ops.on_device
     @torch.inference_mode()
-    def measure_decode(self, B=8, ctx=224, steps=24, reps=2, use_graph=True, slot=7):
+    def measure_decode(self, B=8, ctx=224, steps=24, reps=2, use_graph=True, slot=7, two_tile=False):
         """(ms per token step, logits after ONE step) of the current geometry on a seeded synthetic decode state: 2 B rows that hold `ctx`
         cached positions each.  The step is the one generate() replays (embedding .. sampler, one hipGraph); time = HIP events around
-        `steps` replays, best of `reps`.  The logits are a pure function of the seed, so two geometries can be compared bit for bit."""
+        `steps` replays, best of `reps`.  The logits are a pure function of the seed, so two geometries can be compared bit for bit.
+        two_tile: 17 .. 32 rows on the packed five-launch layer (generate(two_tile=True))."""
         import time
         rows = 2 * B
         total = 4 + reps * steps
@@ -375,6 +376,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         st["graph"] = None
         self._drop_c_step(st)
         st.pop("geom_cache", None)
+        st["two_tile"] = bool(two_tile)
         gen = torch.Generator(device=self.dev).manual_seed(20240229)
         for k in ("kc", "vc"):
             st[k].normal_(0.0, 0.5, generator=gen)
@@ -674,8 +676,20 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
             red["x_out"] = None
         ops.gemv(cur, self.head_pk, st["logits"], N=self.V, K=self.D, nw=8, norm_w=self.norm, col_tiles=hct, **red, **pk)
 
+    def _packed_rows(self, st):
+        """Does this state's token step run on the packed five-launch layer?  Up to 16 rows always.  17 .. 32 rows (two row tiles: every launch streams its weights
+        once for both tiles, each row bit for bit what its 16-row launch gives -- csrc/gemv_decode.hip) where the state asks for it (generate(two_tile=True): the
+        paired batches of engine.synthesize_pipelined), on fp32 images, with at most 3 column tiles per workgroup, unguarded (the guard's launches read 16-row
+        q/k/v partial sums).  33 .. 64 rows, and 17 .. 32 without the switch: the 9-launch step (DESIGN.md section 4 has both measured)."""
+        if self.decode_mode != "v2":
+            return False
+        if st["rows"] <= 16:
+            return True
+        return bool(st.get("two_tile")) and st["rows"] <= 32 and self.weight_dtype == "fp32" and st.get("guard_on") is None \
+            and int(self.tune.get("qkv_ct") or 3) <= 3 and self._hct() <= 3 and not self.tune.get("qkv_tc")
+
     def _forward(self, st):
-        if self.decode_mode == "v2" and st["rows"] <= 16:  # (17 .. 64 rows on this 5-launch layer: measured -4.5 % at 32 rows, +2.4 % at 64 -- profiles/r06_wide_rows_decode_ab.jsonl -- not adopted)
+        if self._packed_rows(st):
             self._forward_decode_v2(st)
         else:
             self._forward_decode(st)
@@ -690,7 +704,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
 
     def _use_c_step(self, st):
         # (a guarded request takes the Python-sequenced step: the C step has no descriptor for the guard's launches)
-        return self.c_step and self.decode_mode == "v2" and st["rows"] <= 16 and self.tune["d_ks2"] in (1, 2, 4) and st.get("guard_on") is None
+        return self.c_step and self._packed_rows(st) and self.tune["d_ks2"] in (1, 2, 4) and st.get("guard_on") is None
 
     def _c_step_desc(self, st):
         """Build (once per state and geometry) the cbx_t3_step_t of this state: st["cstep"] = (descriptor, layers, sampler).  One call of it enqueues the
@@ -758,7 +772,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
                            pd_pk=torch.zeros(4, (rows + 15) // 16 * 16, self.D, device=dev),
                            g_pk=torch.zeros((rows + 15) // 16 * 16, self.F, device=dev),
                            # split-K partial sums of the q/k/v projection + their sums of squares (tune qkv_ks, ABI v11)
-                           qkv_parts=torch.zeros(4, rows, 3 * self.D, device=dev), qkv_ssq=torch.zeros(4, 16, device=dev)),
+                           qkv_parts=torch.zeros(4, rows, 3 * self.D, device=dev), qkv_ssq=torch.zeros(4, (rows + 15) // 16 * 16 if rows <= 32 else 16, device=dev)),
                   graph=None, samp_dev=torch.zeros(B, 8, device=dev),
                   # geometry + split-context workspace of this state's attention launches (a state = one stream of launches; two slots may be in flight)
                   da=ops.DecodeAttnGeom(dev, split=rows * self.H < 128))
@@ -771,7 +785,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
     @torch.inference_mode()
     def generate(self, conds, text_tokens, max_new_tokens=1000, temperature=0.8, top_p=1.0, min_p=0.05,
                  repetition_penalty=1.2, cfg_weight=0.5, uniforms=None, ban_eos=False, ban_from=0, use_graph=True, poll_every=16,
-                 return_prefill_logits=False, debug_logits=False, async_mode=False, slot=0, run_steps=None, generator=None, seeds=None, guard=None):
+                 return_prefill_logits=False, debug_logits=False, async_mode=False, slot=0, run_steps=None, generator=None, seeds=None, guard=None, two_tile=False):
         """conds: one T3 cond dict (shared voice) or a list of B; text_tokens: list of B 1-D LongTensors that already
         carry SOT/EOT (mtl_tts.py:319-322).  Returns a list of B 1-D LongTensors (EOS included if it was sampled).
         temperature, top_p, min_p, repetition_penalty, cfg_weight: a scalar, or a sequence of B (one row of cbx_sampler_t.dev_params per utterance).
@@ -787,7 +801,9 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         forces EOS once the mass stays on the last tokens (`tail`), goes back to earlier text (`repeat`) or the last token_run sampled tokens are one token
         (`run`).  Such a request takes the Python-sequenced step, replayed as a torch-captured graph kept beside the unguarded one.  Afterwards last_guard is the
         per-utterance report and last_guard_device the device tensors (mass history (B, max_steps, ld), trace, state, sums).  Not with ban_eos / ban_from, which
-        ban the EOS the guard must be able to force; advance() refuses such a handle.  None: the call is launch for launch the one it always was."""
+        ban the EOS the guard must be able to force; advance() refuses such a handle.  None: the call is launch for launch the one it always was.
+        two_tile: a batch of 9 .. 16 utterances (17 .. 32 rows) decodes on the packed five-launch layer and the C step, two row tiles per launch (_packed_rows);
+        every logit of every step is bit for bit the one the same utterance gets in a batch of at most 8.  False: the 9-launch step, as before."""
         dev, B = self.dev, len(text_tokens)
         assert B >= 1, "empty batch"
         guard = self.check_guard(guard)
@@ -814,7 +830,7 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
                                      repetition_penalty=_slice_param(repetition_penalty, lo, hi), cfg_weight=_slice_param(cfg_weight, lo, hi),
                                      uniforms=None if uniforms is None else uniforms[lo:hi], ban_eos=ban_eos,
                                      ban_from=ban_from, use_graph=use_graph, poll_every=poll_every, slot=slot, generator=generator,
-                                     seeds=None if seeds is None else seeds[lo:hi], guard=guard)
+                                     seeds=None if seeds is None else seeds[lo:hi], guard=guard, two_tile=two_tile)
             if guard is not None:
                 self.last_guard = reports + self.last_guard
             return out
@@ -833,6 +849,10 @@ class T3Engine(DecodeRuntime, VoicePrefixCache):
         assert max_ctx <= self.max_pos, "context exceeds the RoPE table"
         st = self._get_state(B, max_ctx, max_new_tokens, slot)
         self._prepare_tune()
+        if bool(st.get("two_tile")) != bool(two_tile):  # the captured step bakes its form in
+            self._drop_c_step(st)
+            st["graph"] = None
+            st["two_tile"] = bool(two_tile)
         st["guard_on"] = None if guard is None else self._begin_guard(st, guard, tl, samp)  # (also: the first EOS ban into the request's sampler row)
         self._begin_request(st, samp, uniforms, max_new_tokens, generator, seeds)
 

@@ -200,7 +200,8 @@ typedef struct cbx_gemv_t {
     const float* res;    /* or NULL: out = res + x W^T, res in the same layout as out (in place allowed); ksplit == 1 */
     float eps;           /* RMSNorm epsilon */
     int n_xpart;         /* 0, 2 or 4: the x operand is x + sum_j xpart[j] (split-K partial images of the producing projection, packed
-                            layout, reduced in fixed order on the way to the MFMA); needs norm_w, M <= 16, nw == 8 */
+                            layout, reduced in fixed order on the way to the MFMA); needs norm_w, nw == 8, M <= 16 -- or M <= 32 (two whole row tiles per
+                            image, pad rows zero) in the plain RMSNorm fp32 form: no swiglu, ln_cw or w_bf16 */
     const float* xpart;  /* [n_xpart] images, xpart_stride floats apart */
     long xpart_stride;
     float* x_out;        /* or NULL: receives x + sum_j xpart[j] (packed; must not alias x: other workgroups still read it).  Since ABI v11 rows >= M of
@@ -213,11 +214,12 @@ typedef struct cbx_gemv_t {
                          /* out[m][n] = rstd[m] (sum_k x' w W - mean'[m] ln_cw[n]) + ln_cb[n], then `act`, on the SHIFTED row x' = x - c[m], c[m] = the */
                          /* median of channels 0, K/2, K - 1 of the (summed) row: mean' = sum_k x' / K, rstd = rsqrt(sum_k x'^2 / K - mean'^2 + eps) -- */
                          /* the one-pass variance and the mean term do not cancel when |mean| >> std; x_out still receives the unshifted row */
-    /* ABI v11 -- column-tile / split-K form of the RMSNorm-folded packed GEMV (norm_w, packed fp32 operands in the 16-column image, M <= 16, no
+    /* ABI v11 -- column-tile / split-K form of the RMSNorm-folded packed GEMV (norm_w, packed fp32 operands in the 16-column image, M <= 16 -- or M <= 32 with
+     * col_tiles <= 3 and no ln_cw: two row tiles share every weight register, each row bit for bit what a launch on its own 16-row image gives --, no
      * bias / residual / activation; xpart / x_out as above).  col_tiles = 1 .. 4: a workgroup owns that many 16-column tiles, which share every x
      * register (activation : weight bytes per workgroup = 1 : col_tiles instead of 1 : 1 -- the decode GEMVs are bound by the bytes a CU moves,
      * profiles/r04_decode_launch_timeline.txt), and 1 / ksplit of K on 8 waves (K % (256 ksplit) == 0).  ksplit == 1: out = RMSNorm(x) W^T as
-     * before.  ksplit > 1: out[ks] (part_stride floats apart) holds the UN-normalised partial sums of K slice ks and ssq_out[ks * 16 + m] the
+     * before.  ksplit > 1: out[ks] (part_stride floats apart) holds the UN-normalised partial sums of K slice ks and ssq_out[ks * 16 * ceil(M / 16) + m] the
      * slice's sum of squares of row m: the consumer adds the partials in fixed order and applies rstd = rsqrt(sum_ks ssq / K + eps)
      * (cbx_decode_attn_t.qkv_nparts does).  0 = the one-tile form above. */
     int col_tiles;
@@ -347,8 +349,8 @@ typedef struct cbx_decode_attn_t {
     int unroll, pipeline, split_min;
     float* split_ws; int* split_cnt; long split_pairs;
     /* ABI v11: qkv_nparts = 2 .. 4: `qkv` holds that many UN-normalised split-K partial sums of the fused q/k/v row (cbx_gemv_t.col_tiles with
-     * ksplit > 1), qkv_part_stride floats apart; the kernel adds them in fixed order and multiplies by rstd[row] = rsqrt(sum_p qkv_ssq[p * 16 + row]
-     * / rms_dim + rms_eps) (LlamaRMSNorm of the projection's input, folded through the contraction); rows <= 16.  0 / 1: qkv is the finished row. */
+     * ksplit > 1), qkv_part_stride floats apart; the kernel adds them in fixed order and multiplies by rstd[row] = rsqrt(sum_p qkv_ssq[p * 16 * ceil(rows / 16) + row]
+     * / rms_dim + rms_eps) (LlamaRMSNorm of the projection's input, folded through the contraction); rows <= 32.  0 / 1: qkv is the finished row. */
     int qkv_nparts; long qkv_part_stride; const float* qkv_ssq; int rms_dim; float rms_eps;
 } cbx_decode_attn_t;
 int cbx_decode_attn_rope(const cbx_decode_attn_t* p, void* stream);
@@ -476,7 +478,7 @@ int cbx_t3_sample(const cbx_sampler_t* p, void* stream);
 
 /* ---- stage-level entry point: ONE token step of T3.inference's loop for every row (t3.py:338-386) ----
  * Sequences the kernel-level entry points above on `stream` (embedding gather, n_layers x 5 launches, head, sampler): no allocation,
- * no synchronisation, hipGraph-capturable.  rows <= 16 (the packed-operand path); all weights are cbx_pack_gemv_weight_f32 images
+ * no synchronisation, hipGraph-capturable.  rows <= 32 (the packed-operand path: one or two 16-row tiles; 17 .. 32 rows need fp32 images and qkv_ct, head_ct <= 3); all weights are cbx_pack_gemv_weight_f32 images
  * (wgu with swiglu = 1), all buffers caller-owned device memory. */
 typedef struct cbx_t3_layer_t {
     const float *ln1, *ln2;               /* [dim] RMSNorm weights (input_layernorm, post_attention_layernorm) */
@@ -506,7 +508,7 @@ typedef struct cbx_t3_step_t {
     int da_unroll, da_pipeline, da_split_min, gemv_flags;
     float* da_ws; int* da_cnt; long da_pairs;
     /* ABI v11: qkv_ksplit = 2 or 4 (dim % (256 qkv_ksplit) == 0; with qkv_ct = column tiles per workgroup, qkv_tile = 0): the q/k/v projection in the split-K column-tile form --
-     * qkv then holds [qkv_ksplit][rows][3*dim] partial sums and qkv_ssq [qkv_ksplit][16] sums of squares, which the attention launch folds;
+     * qkv then holds [qkv_ksplit][rows][3*dim] partial sums and qkv_ssq [qkv_ksplit][16 * ceil(rows / 16)] sums of squares, which the attention launch folds;
      * head_ct > 0: the speech head in the column-tile form (ksplit 1).  0 = the one-tile forms. */
     int qkv_ksplit, qkv_ct, head_ct;
     float* qkv_ssq;
