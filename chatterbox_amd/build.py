@@ -22,9 +22,13 @@ def _sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
+def _headers():
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+
+
 def _digest():
     h = hashlib.sha256()
-    for f in _sources() + [os.path.join(CSRC, "cbx_common.h"), os.path.join(HERE, "..", "include", "cbx.h")]:
+    for f in _sources() + _headers() + [os.path.join(HERE, "..", "include", "cbx.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join(FLAGS).encode())

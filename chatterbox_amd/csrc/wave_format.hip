@@ -14,21 +14,20 @@
 #include <math.h>
 
 #include "cbx_common.h"
+#include "../../chatterbox_amd/csrc/wave_common.h"  // (by its path from the root: the header says why)
 
 namespace {
 
-constexpr int WF_MAX_ROWS = 64, WF_TILE = 256;
+constexpr int WF_TILE = 256;
 constexpr int WF_SPAN = 1024;       // LDS floats of a tile's input span (the entry checks 255 D / U + T + 8 against it)
 constexpr int WF_TAB = 147 * 23;    // LDS floats of the phase table at its padded stride: U <= 147 phases of T <= 22 taps there, 61 taps at U = 1
 constexpr int WF_IN_RATE = 24000;
 
-struct wf_rows_t {
-    long off[WF_MAX_ROWS];      // first sample of the piece, floats from `wav`
-    long out_off[WF_MAX_ROWS];  // first output of the launch, elements from `out`
-    long n0[WF_MAX_ROWS];       // inputs consumed before this piece
-    long m0[WF_MAX_ROWS];       // outputs produced before this launch
-    int len[WF_MAX_ROWS];       // L: samples of the piece
-    int cnt[WF_MAX_ROWS];       // outputs of this launch: m0 <= m < m0 + cnt
+struct wf_rows_t : cbx_wave_rows_t {       // (the core: the pieces, L = n[r] samples each)
+    long out_off[CBX_WAVE_MAX_ROWS];  // first output of the launch, elements from `out`
+    long n0[CBX_WAVE_MAX_ROWS];       // inputs consumed before this piece
+    long m0[CBX_WAVE_MAX_ROWS];       // outputs produced before this launch
+    int cnt[CBX_WAVE_MAX_ROWS];       // outputs of this launch: m0 <= m < m0 + cnt
 };
 
 // clamp(rintf(y * 32768), -32768, 32767), ties to even, NaN -> 0
@@ -71,7 +70,7 @@ __global__ __launch_bounds__(256) void wave_format_kernel(const float* __restric
     __shared__ float s_x[WF_SPAN];
     __shared__ float s_tab[WF_TAB];
     const int r = blockIdx.y, tid = threadIdx.x;
-    const long n0 = rows.n0[r], L = rows.len[r], cnt = rows.cnt[r];
+    const long n0 = rows.n0[r], L = rows.n[r], cnt = rows.cnt[r];
     const float* piece = wav + rows.off[r];
     const float* hist = hist_in ? hist_in + (long)r * H : nullptr;
     if (blockIdx.x == 0 && hist_out && tid < H) hist_out[(long)r * H + tid] = wf_sample(piece, hist, n0, L, H, n0 + L - H + tid);
@@ -132,7 +131,7 @@ extern "C" int cbx_wave_format_f32(const float* wav, const long* row_off, const 
                                    const long* n0, const long* m0, const int* fin, const float* hist_in, float* hist_out, void* out, const long* out_off,
                                    long out_cap, void* stream) {
     CBX_REQUIRE(wav && row_off && row_len && out && out_off, "wave_format: null pointer");
-    CBX_REQUIRE(R >= 1 && R <= WF_MAX_ROWS, "wave_format: R = %d outside [1, %d]", R, WF_MAX_ROWS);
+    if (const int e = cbx_wave_count("wave_format", row_off, row_len, R)) return e;
     CBX_REQUIRE(encoding >= 0 && encoding <= 3, "wave_format: unknown encoding %d (0 f32, 1 s16, 2 mulaw, 3 alaw)", encoding);
     const wf_rate_t* rt = nullptr;
     for (const wf_rate_t& c : WF_RATES)
@@ -147,15 +146,15 @@ extern "C" int cbx_wave_format_f32(const float* wav, const long* row_off, const 
     CBX_REQUIRE((WF_TILE - 1l) * rt->D / rt->U + T + 8 <= WF_SPAN && rt->U * (T | 1) <= WF_TAB, "wave_format: the rate %d does not fit the kernel's LDS", rate);
     CBX_REQUIRE((n0 && m0 && fin) || (!n0 && !m0 && !fin), "wave_format: n0, m0 and final go together (all NULL: the one-shot call)");
     CBX_REQUIRE(!hist_out || hist_out != hist_in, "wave_format: the next history needs a buffer of its own");
-    wf_rows_t rows;
-    for (int r = 0; r < WF_MAX_ROWS; ++r) rows.off[r] = rows.out_off[r] = rows.n0[r] = rows.m0[r] = 0, rows.len[r] = rows.cnt[r] = 0;
-    long sum = 0, cnt_max = 0;
+    wf_rows_t rows = {};
+    cbx_wave_span_t sp;
+    if (const int e = cbx_wave_rows("wave_format", row_off, row_len, R, &rows, &sp)) return e;
+    long cnt[CBX_WAVE_MAX_ROWS];
     for (int r = 0; r < R; ++r) {
-        const long a = n0 ? n0[r] : 0, b = m0 ? m0[r] : 0, L = row_len[r];
-        CBX_REQUIRE(L >= 0 && row_off[r] >= 0, "wave_format: row %d has length %ld at offset %ld", r, L, row_off[r]);
+        const long a = n0 ? n0[r] : 0, b = m0 ? m0[r] : 0;
         CBX_REQUIRE(a >= 0 && b >= 0 && a < (1l << 48) && b < (1l << 48), "wave_format: row %d continues at n0 = %ld, m0 = %ld", r, a, b);
         CBX_REQUIRE(a == 0 || hist_in || H == 0, "wave_format: row %d continues at n0 = %ld without a history", r, a);
-        const long N = a + L;
+        const long N = a + row_len[r];
         long m1;
         if (!fin || fin[r]) {
             m1 = (N * rt->U + rt->D - 1) / rt->D;
@@ -163,14 +162,13 @@ extern "C" int cbx_wave_format_f32(const float* wav, const long* row_off, const 
             const long num = (N - 1) * rt->U - hl;
             m1 = num < 0 ? 0 : num / rt->D + 1;
         }
-        const long cnt = m1 > b ? m1 - b : 0;
-        CBX_REQUIRE(cnt <= 0x7fffffffl, "wave_format: row %d would produce %ld outputs in one launch", r, cnt);
-        CBX_REQUIRE(out_off[r] >= 0 && out_off[r] + cnt <= out_cap, "wave_format: row %d writes [%ld, %ld) of an output of %ld", r, out_off[r], out_off[r] + cnt, out_cap);
-        rows.off[r] = row_off[r], rows.out_off[r] = out_off[r], rows.n0[r] = a, rows.m0[r] = b, rows.len[r] = (int)L, rows.cnt[r] = (int)cnt;
-        sum += cnt;
-        cnt_max = cnt > cnt_max ? cnt : cnt_max;
+        cnt[r] = m1 > b ? m1 - b : 0;
+        CBX_REQUIRE(cnt[r] <= 0x7fffffffl, "wave_format: row %d would produce %ld outputs in one launch", r, cnt[r]);
+        rows.out_off[r] = out_off[r], rows.n0[r] = a, rows.m0[r] = b, rows.cnt[r] = (int)cnt[r];
     }
-    CBX_REQUIRE(sum <= out_cap, "wave_format: out holds %ld elements, the rows produce %ld", out_cap, sum);
+    cbx_wave_span_t to;
+    if (const int e = cbx_wave_packed("wave_format", out_off, cnt, R, out_cap, "elements", &to)) return e;
+    const long cnt_max = to.n_max;
     const bool carry = hist_out && H > 0;
     if (cnt_max == 0 && !carry) return 0;
     const long gx = cnt_max > 0 ? (cnt_max + WF_TILE - 1) / WF_TILE : 1;

@@ -15,19 +15,21 @@
 #include <math.h>
 
 #include "cbx_common.h"
+#include "../../chatterbox_amd/csrc/wave_common.h"  // (by its path from the root: the header says why)
 
 namespace {
 
-constexpr int WI_MAX_ROWS = 64, WI_TILE = 256;
+constexpr int WI_TILE = 256;
 constexpr int WI_SPAN = CBX_WAVE_INGEST_MAX_SPAN;  // LDS floats of a tile's decoded span
 constexpr int WI_TAB = 3456;                       // LDS floats of a staged phase table at its padded stride (larger tables are read from global memory)
 constexpr int WI_RAW = 16384;                      // LDS bytes of one piece of a span's raw frames
 constexpr int WT_FRAME = 2048, WT_HOP = 512;
 
+// (not cbx_wave_rows_t: an ingest row is counted in bytes and in `long` frames)
 struct wi_rows_t {
-    long off[WI_MAX_ROWS];      // first byte of the row, from `raw`
-    long out_off[WI_MAX_ROWS];  // first output, floats from `out`
-    long n[WI_MAX_ROWS];        // frames of the row
+    long off[CBX_WAVE_MAX_ROWS];      // first byte of the row, from `raw`
+    long out_off[CBX_WAVE_MAX_ROWS];  // first output, floats from `out`
+    long n[CBX_WAVE_MAX_ROWS];        // frames of the row
 };
 
 // ITU-T G.711 expansion of a code word to the 16-bit sample
@@ -134,39 +136,6 @@ __global__ __launch_bounds__(256) void wave_ingest_kernel(const unsigned char* _
     out[rows.out_off[r] + mb + tid] = acc;
 }
 
-struct wt_rows_t {
-    long off[WI_MAX_ROWS];
-    int n[WI_MAX_ROWS];
-};
-
-// grid (ceil(max blocks / 4), R) x 256: wave w of workgroup (x, r) owns block 4 x + w of row r, the samples [512 b, 512 (b + 1)) cut at n
-__global__ __launch_bounds__(256) void wave_trim_blocks_kernel(const float* __restrict__ wav, wt_rows_t rows, double* __restrict__ ws, long ws_ld) {
-    const int r = blockIdx.y, lane = threadIdx.x & 63;
-    const int b = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    const int n = rows.n[r];
-    const long s0 = (long)b * WT_HOP;
-    if (s0 >= n) return;  // (wave-uniform)
-    const int cnt = n - s0 < WT_HOP ? (int)(n - s0) : WT_HOP;
-    const float* p = wav + rows.off[r] + s0;
-    const bool aligned = ((uintptr_t)p & 15) == 0;
-    double acc = 0.0;
-    for (int q = lane; q < WT_HOP / 4; q += 64) {
-        const int e = 4 * q;
-        if (e >= cnt) break;
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // (elements beyond the row add an exact zero)
-        if (aligned && e + 4 <= cnt) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(p + e);
-            v[0] = t[0], v[1] = t[1], v[2] = t[2], v[3] = t[3];
-        } else {
-            for (int k = 0; k < 4; ++k)
-                if (e + k < cnt) v[k] = p[e + k];
-        }
-        for (int k = 0; k < 4; ++k) acc += (double)v[k] * (double)v[k];
-    }
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
-    if (lane == 0) ws[(long)r * ws_ld + b] = acc;
-}
-
 // mean square of frame f (the row padded by 1024 zeros on either side: the blocks f - 2 .. f + 1), floored at 1e-20 as trim_silence floors the RMS at 1e-10
 __device__ __forceinline__ double wt_frame(const double* m, int nb, int f) {
     double s = 0.0;
@@ -175,43 +144,18 @@ __device__ __forceinline__ double wt_frame(const double* m, int nb, int f) {
 }
 
 // grid R x 256: the kept part of row r
-__global__ __launch_bounds__(256) void wave_trim_edges_kernel(wt_rows_t rows, const double* __restrict__ ws, long ws_ld, double ratio, int* __restrict__ edges) {
-    __shared__ double s_pk[256];
-    __shared__ int s_lo[256], s_hi[256];
-    const int r = blockIdx.x, tid = threadIdx.x;
+__global__ __launch_bounds__(256) void wave_trim_edges_kernel(cbx_wave_rows_t rows, const double* __restrict__ ws, long ws_ld, double ratio, int* __restrict__ edges) {
+    const int r = blockIdx.x;
     const int n = rows.n[r];
     const int nb = (n + WT_HOP - 1) / WT_HOP, nf = 1 + n / WT_HOP;
     const double* m = ws + (long)r * ws_ld;
-    double pk = 0.0;
-    for (int f = tid; f < nf; f += 256) pk = fmax(pk, wt_frame(m, nb, f));
-    s_pk[tid] = pk;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (tid < s) s_pk[tid] = fmax(s_pk[tid], s_pk[tid + s]);
-        __syncthreads();
-    }
-    const double thr = s_pk[0] * ratio;
-    int lo = 0x7fffffff, hi = -1;
-    for (int f = tid; f < nf; f += 256) {
-        if (wt_frame(m, nb, f) > thr) {
-            lo = f < lo ? f : lo;
-            hi = f > hi ? f : hi;
-        }
-    }
-    s_lo[tid] = lo, s_hi[tid] = hi;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (tid < s) {
-            s_lo[tid] = s_lo[tid + s] < s_lo[tid] ? s_lo[tid + s] : s_lo[tid];
-            s_hi[tid] = s_hi[tid + s] > s_hi[tid] ? s_hi[tid + s] : s_hi[tid];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
+    int lo, hi;
+    cbx_wave_peak_edges(nf, ratio, [=](int f) { return wt_frame(m, nb, f); }, [](double v, double thr) { return v > thr; }, &lo, &hi);
+    if (threadIdx.x == 0) {
         int start = 0, stop = 0;
-        if (s_hi[0] >= 0) {
-            const long e1 = ((long)s_hi[0] + 1) * WT_HOP;
-            start = s_lo[0] * WT_HOP;
+        if (hi >= 0) {
+            const long e1 = ((long)hi + 1) * WT_HOP;
+            start = lo * WT_HOP;
             stop = (int)(e1 < n ? e1 : n);
         }
         edges[2 * r] = start;
@@ -232,7 +176,7 @@ long wi_gcd(long a, long b) {
 extern "C" int cbx_wave_ingest(const void* raw, const long* row_off, const long* row_frames, int R, int encoding, int channels, const float* tab, int U, int D, int T,
                                float* out, const long* out_off, long out_cap, void* stream) {
     CBX_REQUIRE(raw && row_off && row_frames && out && out_off, "wave_ingest: null pointer");
-    CBX_REQUIRE(R >= 1 && R <= WI_MAX_ROWS, "wave_ingest: R = %d outside [1, %d]", R, WI_MAX_ROWS);
+    CBX_REQUIRE(R >= 1 && R <= CBX_WAVE_MAX_ROWS, "wave_ingest: R = %d outside [1, %d]", R, CBX_WAVE_MAX_ROWS);
     CBX_REQUIRE(encoding >= CBX_WAVE_IN_U8 && encoding <= CBX_WAVE_IN_ALAW, "wave_ingest: unknown encoding %d (0 u8, 1 s16, 2 s24, 3 s32, 4 f32, 5 mulaw, 6 alaw)", encoding);
     CBX_REQUIRE(channels >= 1 && channels <= 8, "wave_ingest: %d channels outside [1, 8]", channels);
     CBX_REQUIRE(U >= 1 && D >= 1 && U <= (1 << 20) && D <= (1 << 20) && wi_gcd(U, D) == 1, "wave_ingest: U / D = %d / %d is not a reduced ratio", U, D);
@@ -247,21 +191,20 @@ extern "C" int cbx_wave_ingest(const void* raw, const long* row_off, const long*
     const int ss = wi_sample_size(encoding);
     const int al = ss == 3 ? 1 : ss;  // packed 24-bit samples are read byte by byte
     CBX_REQUIRE((uintptr_t)raw % al == 0, "wave_ingest: the buffer is not aligned to the sample size %d", al);
-    wi_rows_t rows;
-    for (int r = 0; r < WI_MAX_ROWS; ++r) rows.off[r] = rows.out_off[r] = rows.n[r] = 0;
-    long sum = 0, cnt_max = 0;
+    // the rows are counted in bytes and `long` frames and aligned to their sample size: a loop of its own, not cbx_wave_rows
+    wi_rows_t rows = {};
+    long cnt[CBX_WAVE_MAX_ROWS];
     for (int r = 0; r < R; ++r) {
         const long n = row_frames[r];
         CBX_REQUIRE(n >= 0 && row_off[r] >= 0 && n < (1l << 40), "wave_ingest: row %d has %ld frames at byte %ld", r, n, row_off[r]);
         CBX_REQUIRE(row_off[r] % al == 0, "wave_ingest: row %d begins at byte %ld, not a multiple of the sample size %d", r, row_off[r], al);
-        const long cnt = (n * U + D - 1) / D;
-        CBX_REQUIRE(cnt <= 0x7fffffffl, "wave_ingest: row %d would produce %ld outputs in one launch", r, cnt);
-        CBX_REQUIRE(out_off[r] >= 0 && out_off[r] + cnt <= out_cap, "wave_ingest: row %d writes [%ld, %ld) of an output of %ld", r, out_off[r], out_off[r] + cnt, out_cap);
+        cnt[r] = (n * U + D - 1) / D;
+        CBX_REQUIRE(cnt[r] <= 0x7fffffffl, "wave_ingest: row %d would produce %ld outputs in one launch", r, cnt[r]);
         rows.off[r] = row_off[r], rows.out_off[r] = out_off[r], rows.n[r] = n;
-        sum += cnt;
-        cnt_max = cnt > cnt_max ? cnt : cnt_max;
     }
-    CBX_REQUIRE(sum <= out_cap, "wave_ingest: out holds %ld floats, the rows produce %ld", out_cap, sum);
+    cbx_wave_span_t to;
+    if (const int e = cbx_wave_packed("wave_ingest", out_off, cnt, R, out_cap, "floats", &to)) return e;
+    const long cnt_max = to.n_max;
     if (cnt_max == 0) return 0;
     const long gx = (cnt_max + WI_TILE - 1) / WI_TILE;
     const int staged = filter && U * (T | 1) <= WI_TAB;
@@ -272,21 +215,15 @@ extern "C" int cbx_wave_ingest(const void* raw, const long* row_off, const long*
 
 extern "C" int cbx_wave_trim_edges_f32(const float* wav, const long* row_off, const int* row_len, int R, double ratio, int* edges, double* ws, long ws_cap, void* stream) {
     CBX_REQUIRE(wav && row_off && row_len && edges && ws, "wave_trim_edges: null pointer");
-    CBX_REQUIRE(R >= 1 && R <= WI_MAX_ROWS, "wave_trim_edges: R = %d outside [1, %d]", R, WI_MAX_ROWS);
+    if (const int e = cbx_wave_count("wave_trim_edges", row_off, row_len, R)) return e;
     CBX_REQUIRE(ratio >= 0.0 && ratio < INFINITY, "wave_trim_edges: bad threshold (ratio %g)", ratio);
-    wt_rows_t rows;
-    for (int r = 0; r < WI_MAX_ROWS; ++r) rows.off[r] = 0, rows.n[r] = 0;
-    long n_max = 0;
-    for (int r = 0; r < R; ++r) {
-        CBX_REQUIRE(row_len[r] >= 0 && row_off[r] >= 0, "wave_trim_edges: row %d has length %d at offset %ld", r, row_len[r], row_off[r]);
-        rows.off[r] = row_off[r], rows.n[r] = row_len[r];
-        n_max = row_len[r] > n_max ? row_len[r] : n_max;
-    }
-    const long nb = (n_max + WT_HOP - 1) / WT_HOP;
+    cbx_wave_rows_t rows;
+    cbx_wave_span_t sp;
+    if (const int e = cbx_wave_rows("wave_trim_edges", row_off, row_len, R, &rows, &sp)) return e;
+    const long nb = (sp.n_max + WT_HOP - 1) / WT_HOP;
     CBX_REQUIRE(ws_cap >= (long)R * nb, "wave_trim_edges: workspace of %ld doubles, %d rows of %ld blocks need %ld", ws_cap, R, nb, (long)R * nb);
     if (nb > 0) {
-        hipLaunchKernelGGL(wave_trim_blocks_kernel, dim3((unsigned)((nb + 3) / 4), (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, ws, nb);
-        const int e = cbx_check_launch("wave_trim_edges");
+        const int e = cbx_wave_block_pass<WT_HOP, false>("wave_trim_edges", wav, rows, R, sp.n_max, nb, ws, stream);
         if (e) return e;
     }
     hipLaunchKernelGGL(wave_trim_edges_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, (const double*)ws, nb, ratio, edges);

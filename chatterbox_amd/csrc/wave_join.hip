@@ -17,84 +17,29 @@
 #include <math.h>
 
 #include "cbx_common.h"
+#include "../../chatterbox_amd/csrc/wave_common.h"  // (by its path from the root: the header says why)
 
 namespace {
 
-constexpr int WJ_MAX_ROWS = 64, WJ_FRAME = 480;
+constexpr int WJ_FRAME = 480;
 constexpr int WJ_TILE = 4096;  // output samples of one join workgroup: 256 threads x 4 quads
 
-struct wj_rows_t {
-    long off[WJ_MAX_ROWS];
-    int n[WJ_MAX_ROWS];
-    int gap[WJ_MAX_ROWS];
+struct wj_rows_t : cbx_wave_rows_t {
+    int gap[CBX_WAVE_MAX_ROWS];
 };
 
-// grid (ceil(max frames / 4), R) x 256: wave w of workgroup (x, r) owns frame 4 x + w of row r
-__global__ __launch_bounds__(256) void wave_frame_ms_kernel(const float* __restrict__ wav, wj_rows_t rows, double* __restrict__ ws, long ws_ld) {
-    const int r = blockIdx.y, lane = threadIdx.x & 63;
-    const int f = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    const int n = rows.n[r];
-    const long s0 = (long)f * WJ_FRAME;
-    if (s0 >= n) return;  // (wave-uniform)
-    const int cnt = n - s0 < WJ_FRAME ? (int)(n - s0) : WJ_FRAME;
-    const float* p = wav + rows.off[r] + s0;
-    const bool aligned = ((uintptr_t)p & 15) == 0;
-    double acc = 0.0;
-    for (int q = lane; q < WJ_FRAME / 4; q += 64) {
-        const int e = 4 * q;
-        if (e >= cnt) break;
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // (elements beyond the row add an exact zero)
-        if (aligned && e + 4 <= cnt) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(p + e);
-            v[0] = t[0], v[1] = t[1], v[2] = t[2], v[3] = t[3];
-        } else {
-            for (int k = 0; k < 4; ++k)
-                if (e + k < cnt) v[k] = p[e + k];
-        }
-        for (int k = 0; k < 4; ++k) acc += (double)v[k] * (double)v[k];
-    }
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
-    if (lane == 0) ws[(long)r * ws_ld + f] = acc / (double)cnt;
-}
-
 // grid R x 256: the kept part of row r from its frames' mean squares
-__global__ __launch_bounds__(256) void wave_edges_kernel(wj_rows_t rows, const double* __restrict__ ws, long ws_ld, double ratio, int pad, int* __restrict__ edges) {
-    __shared__ double s_pk[256];
-    __shared__ int s_lo[256], s_hi[256];
-    const int r = blockIdx.x, tid = threadIdx.x;
+__global__ __launch_bounds__(256) void wave_edges_kernel(cbx_wave_rows_t rows, const double* __restrict__ ws, long ws_ld, double ratio, int pad, int* __restrict__ edges) {
+    const int r = blockIdx.x;
     const int n = rows.n[r];
     const int nf = (int)(((long)n + WJ_FRAME - 1) / WJ_FRAME);
     const double* m = ws + (long)r * ws_ld;
-    double pk = 0.0;
-    for (int f = tid; f < nf; f += 256) pk = fmax(pk, m[f]);
-    s_pk[tid] = pk;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (tid < s) s_pk[tid] = fmax(s_pk[tid], s_pk[tid + s]);
-        __syncthreads();
-    }
-    const double thr = s_pk[0] * ratio;
-    int lo = 0x7fffffff, hi = -1;
-    for (int f = tid; f < nf; f += 256) {
-        const double v = m[f];
-        if (v > thr && v > 0.0) {
-            lo = f < lo ? f : lo;
-            hi = f > hi ? f : hi;
-        }
-    }
-    s_lo[tid] = lo, s_hi[tid] = hi;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (tid < s) {
-            s_lo[tid] = s_lo[tid + s] < s_lo[tid] ? s_lo[tid + s] : s_lo[tid];
-            s_hi[tid] = s_hi[tid + s] > s_hi[tid] ? s_hi[tid + s] : s_hi[tid];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
+    int lo, hi;
+    cbx_wave_peak_edges(nf, ratio, [=](int f) { return m[f]; }, [](double v, double thr) { return v > thr && v > 0.0; }, &lo, &hi);
+    if (threadIdx.x == 0) {
         int start = 0, stop = 0;
-        if (s_hi[0] >= 0) {
-            const long f0 = (long)s_lo[0] - pad, e1 = ((long)s_hi[0] + 1 + pad) * WJ_FRAME;
+        if (hi >= 0) {
+            const long f0 = (long)lo - pad, e1 = ((long)hi + 1 + pad) * WJ_FRAME;
             start = (int)((f0 > 0 ? f0 : 0) * WJ_FRAME);
             stop = (int)(e1 < n ? e1 : n);
         }
@@ -157,53 +102,29 @@ __global__ __launch_bounds__(256) void wave_join_kernel(const float* __restrict_
     }
 }
 
-// the host arrays of a call -> the by-value descriptor; returns the longest row through *n_max, the sum of the lengths through *n_sum
-int wj_rows(const char* who, const long* row_off, const int* row_len, const int* gaps, int R, wj_rows_t* rows, long* n_max, long* n_sum) {
-    CBX_REQUIRE(row_off && row_len, "%s: null pointer", who);
-    CBX_REQUIRE(R >= 1 && R <= WJ_MAX_ROWS, "%s: R = %d outside [1, %d]", who, R, WJ_MAX_ROWS);
-    *n_max = *n_sum = 0;
-    for (int r = 0; r < WJ_MAX_ROWS; ++r) rows->off[r] = 0, rows->n[r] = 0, rows->gap[r] = 0;
-    for (int r = 0; r < R; ++r) {
-        CBX_REQUIRE(row_len[r] >= 0 && row_off[r] >= 0, "%s: row %d has length %d at offset %ld", who, r, row_len[r], row_off[r]);
-        CBX_REQUIRE(!gaps || gaps[r] >= 0, "%s: row %d has gap %d", who, r, gaps ? gaps[r] : 0);
-        rows->off[r] = row_off[r], rows->n[r] = row_len[r], rows->gap[r] = gaps ? gaps[r] : 0;
-        *n_max = row_len[r] > *n_max ? row_len[r] : *n_max;
-        *n_sum += (long)row_len[r] + rows->gap[r];
-    }
-    return 0;
-}
-
-// the frame pass of a call: m_f of every frame of every row -> ws[r * nf + f]
-int wj_frame_pass(const char* who, const float* wav, const wj_rows_t& rows, int R, long n_max, long nf, double* ws, void* stream) {
-    const long gx = (nf + 3) / 4;
-    CBX_REQUIRE(gx <= 0x7fffffffl, "%s: a row of %ld samples is too long for one launch", who, n_max);
-    hipLaunchKernelGGL(wave_frame_ms_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, ws, nf);
-    return cbx_check_launch(who);
-}
-
 }  // namespace
 
 // The same frame pass for the pause control (wave_squeeze.hip; declared in cbx_common.h): ONE kernel, so its m_f are those of cbx_wave_edges_f32 bit for bit.
-// The caller has checked the rows (R in [1, 64], lengths and offsets >= 0) and that ws holds R * nf doubles, nf = ceil(max n / 480) > 0.
+// ws holds R * nf doubles, nf = ceil(max n / 480) > 0.
 int cbx_wave_frame_ms(const char* who, const float* wav, const long* row_off, const int* row_len, int R, long nf, double* ws, void* stream) {
-    wj_rows_t rows;
-    long n_max, n_sum;
-    const int rc = wj_rows(who, row_off, row_len, nullptr, R, &rows, &n_max, &n_sum);
-    return rc ? rc : wj_frame_pass(who, wav, rows, R, n_max, nf, ws, stream);
+    cbx_wave_rows_t rows;
+    cbx_wave_span_t sp;
+    const int rc = cbx_wave_rows(who, row_off, row_len, R, &rows, &sp);
+    return rc ? rc : cbx_wave_block_pass<WJ_FRAME, true>(who, wav, rows, R, sp.n_max, nf, ws, stream);
 }
 
 extern "C" int cbx_wave_edges_f32(const float* wav, const long* row_off, const int* row_len, int R, double ratio, int pad, int* edges, double* ws, long ws_cap,
                                   void* stream) {
-    wj_rows_t rows;
-    long n_max, n_sum;
-    const int rc = wj_rows("wave_edges", row_off, row_len, nullptr, R, &rows, &n_max, &n_sum);
+    cbx_wave_rows_t rows;
+    cbx_wave_span_t sp;
+    const int rc = cbx_wave_rows("wave_edges", row_off, row_len, R, &rows, &sp);
     if (rc) return rc;
     CBX_REQUIRE(wav && edges && ws, "wave_edges: null pointer");
     CBX_REQUIRE(ratio >= 0.0 && ratio < INFINITY && pad >= 0 && pad <= (1 << 20), "wave_edges: bad threshold (ratio %g, pad %d)", ratio, pad);
-    const long nf = (n_max + WJ_FRAME - 1) / WJ_FRAME;
+    const long nf = (sp.n_max + WJ_FRAME - 1) / WJ_FRAME;
     CBX_REQUIRE(ws_cap >= (long)R * nf, "wave_edges: workspace of %ld doubles, %d rows of %ld frames need %ld", ws_cap, R, nf, (long)R * nf);
     if (nf > 0) {
-        const int e = wj_frame_pass("wave_edges", wav, rows, R, n_max, nf, ws, stream);
+        const int e = cbx_wave_block_pass<WJ_FRAME, true>("wave_edges", wav, rows, R, sp.n_max, nf, ws, stream);
         if (e) return e;
     }
     hipLaunchKernelGGL(wave_edges_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, (const double*)ws, nf, ratio, pad, edges);
@@ -212,17 +133,22 @@ extern "C" int cbx_wave_edges_f32(const float* wav, const long* row_off, const i
 
 extern "C" int cbx_wave_join_f32(const float* wav, const long* row_off, const int* row_len, const int* gaps, int R, const int* edges, const float* ramp, int fade,
                                  int first, int last, float* out, long out_cap, int* layout, void* stream) {
-    wj_rows_t rows;
-    long n_max, n_sum;
+    wj_rows_t rows = {};
+    cbx_wave_span_t sp;
     CBX_REQUIRE(gaps, "wave_join: null pointer");
-    const int rc = wj_rows("wave_join", row_off, row_len, gaps, R, &rows, &n_max, &n_sum);
+    const int rc = cbx_wave_rows("wave_join", row_off, row_len, R, &rows, &sp);
     if (rc) return rc;
+    long n_sum = sp.n_sum, span = 0;  // the rows with their gaps: all of them, and the longest
+    for (int r = 0; r < R; ++r) {
+        CBX_REQUIRE(gaps[r] >= 0, "wave_join: row %d has gap %d", r, gaps[r]);
+        rows.gap[r] = gaps[r];
+        n_sum += gaps[r];
+        span = (long)rows.n[r] + gaps[r] > span ? (long)rows.n[r] + gaps[r] : span;
+    }
     CBX_REQUIRE(wav && edges && out && layout, "wave_join: null pointer");
     CBX_REQUIRE(fade >= 0 && (fade == 0 || ramp), "wave_join: fade = %d%s", fade, fade > 0 ? " without a ramp" : "");
     CBX_REQUIRE(n_sum <= 0x7fffffffl, "wave_join: %ld samples do not fit the int32 layout record", n_sum);
     CBX_REQUIRE(out_cap >= n_sum, "wave_join: out holds %ld samples, the rows and their gaps may need %ld", out_cap, n_sum);
-    long span = 0;
-    for (int r = 0; r < R; ++r) span = (long)rows.n[r] + rows.gap[r] > span ? (long)rows.n[r] + rows.gap[r] : span;
     const long gx = (span + 3 + WJ_TILE - 1) / WJ_TILE;  // (+ 3: the span may begin up to three samples into its first quad; >= 1: the layout record is always written)
     hipLaunchKernelGGL(wave_join_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, R, edges, ramp, fade, first != 0, last != 0, out,
                        layout);

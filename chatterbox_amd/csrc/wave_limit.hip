@@ -20,10 +20,10 @@
 #include <math.h>
 
 #include "cbx_common.h"
+#include "../../chatterbox_amd/csrc/wave_common.h"  // (by its path from the root: the header says why)
 
 namespace {
 
-constexpr int LM_MAX_ROWS = 64;
 constexpr int LM_TILE = 1024;                        // outputs of one workgroup: 256 threads x 4
 constexpr int LM_HMAX = 480;                         // the largest look-ahead
 constexpr int LM_TAB = 1024;                         // floats of the phase table, U T
@@ -32,11 +32,9 @@ constexpr int LM_NC = LM_TILE + 4 * LM_HMAX;         // c over tile +- 2 H
 constexpr int LM_SPAN = LM_NC + LM_TAB + 16;         // u over that, plus the filter's reach and the alignment slack
 constexpr int LM_WIN = 2 * LM_HMAX + 1;
 
-struct lm_rows_t {
-    long off[LM_MAX_ROWS];      // first sample of the row, floats from `wav`
-    long out_off[LM_MAX_ROWS];  // first output of the row, floats from `out`
-    int n[LM_MAX_ROWS];
-    float ceil[LM_MAX_ROWS];    // (float)C; NaN: the row is not limited
+struct lm_rows_t : cbx_wave_rows_t {
+    long out_off[CBX_WAVE_MAX_ROWS];  // first output of the row, floats from `out`
+    float ceil[CBX_WAVE_MAX_ROWS];    // (float)C; NaN: the row is not limited
 };
 
 // sample i of the row times the pre-gain, zero outside [0, n)
@@ -224,26 +222,25 @@ extern "C" int cbx_wave_limit_f32(const float* wav, const long* row_off, const i
                                   void* stream) {
     CBX_REQUIRE(wav && row_off && row_len && ceiling && tab && win && stats && ws, "wave_limit: null pointer");
     CBX_REQUIRE(!out || out_off, "wave_limit: null pointer (out_off may be NULL only with out)");
-    CBX_REQUIRE(R >= 1 && R <= LM_MAX_ROWS, "wave_limit: R = %d outside [1, %d]", R, LM_MAX_ROWS);
+    int rc = cbx_wave_count("wave_limit", row_off, row_len, R);
+    if (rc) return rc;
     CBX_REQUIRE(U >= 1 && U <= 8, "wave_limit: U = %d outside [1, 8]", U);
     CBX_REQUIRE(T >= 1 && U * (long)T <= LM_TAB, "wave_limit: T = %d: a table of U T = %ld floats (1 .. %d)", T, U * (long)T, LM_TAB);
     CBX_REQUIRE(H >= 1 && H <= LM_HMAX, "wave_limit: H = %d outside [1, %d]", H, LM_HMAX);
-    lm_rows_t rows;
-    for (int r = 0; r < LM_MAX_ROWS; ++r) rows.off[r] = rows.out_off[r] = 0, rows.n[r] = 0, rows.ceil[r] = NAN;
-    long n_max = 0;
+    lm_rows_t rows = {};  // (entries behind R stay zero: the grids end at R, no kernel reads them)
+    cbx_wave_span_t sp, to;
+    if ((rc = cbx_wave_rows("wave_limit", row_off, row_len, R, &rows, &sp))) return rc;
+    long cnt[CBX_WAVE_MAX_ROWS];
     for (int r = 0; r < R; ++r) {
-        CBX_REQUIRE(row_len[r] >= 0 && row_off[r] >= 0, "wave_limit: row %d has length %d at offset %ld", r, row_len[r], row_off[r]);
         const double c = ceiling[r];
         CBX_REQUIRE(!(c == c) || (c > 0.0 && c < INFINITY), "wave_limit: row %d has the ceiling %g (a positive finite number, or NaN for a row that is not limited)", r, c);
-        rows.off[r] = row_off[r], rows.n[r] = row_len[r], rows.ceil[r] = (float)c;
+        rows.ceil[r] = (float)c;
         CBX_REQUIRE(!(c == c) || (rows.ceil[r] > 0.0f && rows.ceil[r] < INFINITY), "wave_limit: row %d has the ceiling %g, which is no positive finite float", r, c);
-        if (out) {
-            CBX_REQUIRE(out_off[r] >= 0 && out_off[r] + row_len[r] <= out_cap, "wave_limit: row %d writes [%ld, %ld) of an output of %ld", r, out_off[r],
-                        out_off[r] + row_len[r], out_cap);
-            rows.out_off[r] = out_off[r];
-        }
-        n_max = row_len[r] > n_max ? row_len[r] : n_max;
+        if (out) rows.out_off[r] = out_off[r];
+        cnt[r] = row_len[r];
     }
+    if (out && (rc = cbx_wave_packed("wave_limit", out_off, cnt, R, out_cap, nullptr, &to))) return rc;  // (the rows' own layout: no sum)
+    const long n_max = sp.n_max;
     if (out)
         for (int a = 0; a < R; ++a)
             for (int b = 0; b < R; ++b) {

@@ -35,17 +35,13 @@
 #include <math.h>
 
 #include "cbx_common.h"
+#include "../../chatterbox_amd/csrc/wave_common.h"  // (by its path from the root: the header says why)
 
 namespace {
 
-constexpr int WL_MAX_ROWS = 64;
 constexpr int WL_CHAIN = 1024;  // segments of one LDS tile of the chain
 constexpr int WL_TILE = 4096;  // samples of one gain workgroup: 256 threads x 4 quads
 
-struct wl_rows_t {
-    long off[WL_MAX_ROWS];
-    int n[WL_MAX_ROWS];
-};
 struct wl_coef_t {
     double c[10];  // b0 b1 b2 a1 a2 of the shelf, then of the high pass
 };
@@ -53,10 +49,10 @@ struct wl_pow_t {
     double m[7][16];  // row-major 4 x 4: A^(c 2^i) for i = 0 .. 5, then A^hop
 };
 struct wl_target_t {
-    double t[WL_MAX_ROWS];
+    double t[CBX_WAVE_MAX_ROWS];
 };
 struct wl_n0_t {
-    long v[WL_MAX_ROWS];  // samples a running meter has consumed, per row
+    long v[CBX_WAVE_MAX_ROWS];  // samples a running meter has consumed, per row
 };
 constexpr int WL_REC = 8;  // doubles of a running meter's record ahead of its E table: state[4], peak, three zeros
 
@@ -157,7 +153,7 @@ __device__ __forceinline__ void wl_segment(const Src& x, long n, long s, const w
 }
 
 // grid (ceil(segments / 4), R) x 256: wave w of workgroup (x, r) owns segment 4 x + w of row r.  fin = 0: v_s of every whole segment; fin = 1: E_s and the peak
-__global__ __launch_bounds__(256) void wave_loud_seg_kernel(const float* __restrict__ wav, wl_rows_t rows, int R, wl_coef_t k, wl_pow_t pw, int hop, int fin,
+__global__ __launch_bounds__(256) void wave_loud_seg_kernel(const float* __restrict__ wav, cbx_wave_rows_t rows, int R, wl_coef_t k, wl_pow_t pw, int hop, int fin,
                                                             double* __restrict__ ws, long ld) {
     const int r = blockIdx.y;
     const long s = (long)blockIdx.x * 4 + (long)(threadIdx.x >> 6);
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(256) void wave_loud_seg_kernel(const float* __restr
 
 // The running meter's launch of the same: grid (ceil(K_max / 4), R) x 256 over the K_r whole segments of tail_r[0, t_r) ++ piece_r.  ws: the segment states alone,
 // (r ld + s) * 4 + q, ld = K_max; E_(S0 + s) goes to the row's record rec + r rec_ld
-__global__ __launch_bounds__(256) void wave_loud_push_seg_kernel(const float* __restrict__ wav, wl_rows_t rows, wl_n0_t n0, const float* __restrict__ tail, wl_coef_t k,
+__global__ __launch_bounds__(256) void wave_loud_push_seg_kernel(const float* __restrict__ wav, cbx_wave_rows_t rows, wl_n0_t n0, const float* __restrict__ tail, wl_coef_t k,
                                                                  wl_pow_t pw, int hop, int fin, double* __restrict__ ws, long ld, double* __restrict__ rec, long rec_ld) {
     const int r = blockIdx.y;
     const long s = (long)blockIdx.x * 4 + (long)(threadIdx.x >> 6);
@@ -198,7 +194,7 @@ __device__ __forceinline__ void wl_chain(double* sm, double* st, long S, const w
 }
 
 // grid R x 256: the chain over every whole segment of row r, from zero state
-__global__ __launch_bounds__(256) void wave_loud_chain_kernel(wl_rows_t rows, wl_pow_t pw, int hop, double* __restrict__ ws, long ld) {
+__global__ __launch_bounds__(256) void wave_loud_chain_kernel(cbx_wave_rows_t rows, wl_pow_t pw, int hop, double* __restrict__ ws, long ld) {
     __shared__ double sm[4 * WL_CHAIN];
     const int r = blockIdx.x;
     double cur[4] = {0.0, 0.0, 0.0, 0.0};  // (lane 0's)
@@ -207,7 +203,7 @@ __global__ __launch_bounds__(256) void wave_loud_chain_kernel(wl_rows_t rows, wl
 
 // grid R x 256, the running meter's row r: the chain over its K new segments from the record's state, which becomes the state on entry to segment S0 + K; the
 // running peak takes max |piece| (NaN once a NaN was seen); the (t + L) mod hop samples behind the last whole segment go to the OTHER tail buffer
-__global__ __launch_bounds__(256) void wave_loud_push_chain_kernel(const float* __restrict__ wav, wl_rows_t rows, wl_n0_t n0, const float* __restrict__ tail_in,
+__global__ __launch_bounds__(256) void wave_loud_push_chain_kernel(const float* __restrict__ wav, cbx_wave_rows_t rows, wl_n0_t n0, const float* __restrict__ tail_in,
                                                                    float* __restrict__ tail_out, wl_pow_t pw, int hop, double* __restrict__ ws, long ld,
                                                                    double* __restrict__ rec, long rec_ld) {
     __shared__ double sm[4 * WL_CHAIN];
@@ -262,7 +258,7 @@ __device__ __forceinline__ double wl_block_sum(double* sm, int tid, double v) {
 // grid R x 256: blocks, gates, L, peak and gain of row r.  PUSH (the running meter): ws is the records, ld their stride, rows.n[r] the SEGMENTS of row r so far,
 // and the peak is the record's
 template <bool PUSH>
-__global__ __launch_bounds__(256) void wave_loud_row_kernel(wl_rows_t rows, int R, int hop, wl_target_t target, double ceiling, const double* __restrict__ ws, long ld,
+__global__ __launch_bounds__(256) void wave_loud_row_kernel(cbx_wave_rows_t rows, int R, int hop, wl_target_t target, double ceiling, const double* __restrict__ ws, long ld,
                                                             double* __restrict__ stats, float* __restrict__ gain) {
     __shared__ double sm[256];
     __shared__ int s_bad[256], s_nan[256];
@@ -330,7 +326,7 @@ __global__ __launch_bounds__(256) void wave_loud_row_kernel(wl_rows_t rows, int 
 }
 
 // grid (ceil((max n + 3) / WL_TILE), R) x 256: workgroup (x, r) owns quads [1024 x, 1024 (x + 1)) of row r, counted from the 16-byte boundary at or below its start
-__global__ __launch_bounds__(256) void wave_gain_kernel(float* __restrict__ wav, wl_rows_t rows, const float* __restrict__ gain) {
+__global__ __launch_bounds__(256) void wave_gain_kernel(float* __restrict__ wav, cbx_wave_rows_t rows, const float* __restrict__ gain) {
     const int r = blockIdx.y;
     const long n = rows.n[r];
     float* p = wav + rows.off[r];
@@ -347,20 +343,6 @@ __global__ __launch_bounds__(256) void wave_gain_kernel(float* __restrict__ wav,
                 if (i0 + e >= 0 && i0 + e < n) p[i0 + e] = p[i0 + e] * g;
         }
     }
-}
-
-// the host arrays of a call -> the by-value descriptor; the longest row through *n_max
-int wl_rows(const char* who, const long* row_off, const int* row_len, int R, wl_rows_t* rows, long* n_max) {
-    CBX_REQUIRE(row_off && row_len, "%s: null pointer", who);
-    CBX_REQUIRE(R >= 1 && R <= WL_MAX_ROWS, "%s: R = %d outside [1, %d]", who, R, WL_MAX_ROWS);
-    *n_max = 0;
-    for (int r = 0; r < WL_MAX_ROWS; ++r) rows->off[r] = 0, rows->n[r] = 0;
-    for (int r = 0; r < R; ++r) {
-        CBX_REQUIRE(row_len[r] >= 0 && row_off[r] >= 0, "%s: row %d has length %d at offset %ld", who, r, row_len[r], row_off[r]);
-        rows->off[r] = row_off[r], rows->n[r] = row_len[r];
-        *n_max = row_len[r] > *n_max ? row_len[r] : *n_max;
-    }
-    return 0;
 }
 
 // o = a b, 4 x 4 row-major (o is neither a nor b)
@@ -410,21 +392,21 @@ void wl_powers(const wl_coef_t& k, int hop, wl_pow_t* pw) {
 
 extern "C" int cbx_wave_loudness_f32(const float* wav, const long* row_off, const int* row_len, int R, const double* coef, int hop, const double* target,
                                      double ceiling, double* stats, float* gain, double* ws, long ws_cap, void* stream) {
-    wl_rows_t rows;
-    long n_max;
-    const int rc = wl_rows("wave_loudness", row_off, row_len, R, &rows, &n_max);
+    cbx_wave_rows_t rows;
+    cbx_wave_span_t sp;
+    const int rc = cbx_wave_rows("wave_loudness", row_off, row_len, R, &rows, &sp);
     if (rc) return rc;
     CBX_REQUIRE(wav && coef && target && stats && gain && ws, "wave_loudness: null pointer");
     CBX_REQUIRE(hop >= 1, "wave_loudness: hop = %d (a tenth of a second in samples, at least 1)", hop);
     wl_coef_t k;
     if (const int e = wl_coefs("wave_loudness", coef, &k)) return e;
-    const long nseg = (n_max + hop - 1) / hop;
+    const long nseg = (sp.n_max + hop - 1) / hop;
     CBX_REQUIRE(ws_cap >= 6l * R * nseg, "wave_loudness: workspace of %ld doubles, %d rows of %ld segments need %ld", ws_cap, R, nseg, 6l * R * nseg);
     wl_target_t tg;
-    for (int r = 0; r < WL_MAX_ROWS; ++r) tg.t[r] = r < R ? target[r] : (double)NAN;
+    for (int r = 0; r < CBX_WAVE_MAX_ROWS; ++r) tg.t[r] = r < R ? target[r] : (double)NAN;
     if (nseg > 0) {
         const long gx = (nseg + 3) / 4;
-        CBX_REQUIRE(gx <= 0x7fffffffl, "wave_loudness: a row of %ld samples is too long for one launch", n_max);
+        CBX_REQUIRE(gx <= 0x7fffffffl, "wave_loudness: a row of %ld samples is too long for one launch", sp.n_max);
         wl_pow_t pw;
         wl_powers(k, hop, &pw);
         hipLaunchKernelGGL(wave_loud_seg_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, R, k, pw, hop, 0, ws, nseg);
@@ -442,9 +424,9 @@ extern "C" int cbx_wave_loudness_f32(const float* wav, const long* row_off, cons
 extern "C" int cbx_wave_loudness_push_f32(const float* wav, const long* row_off, const int* row_len, const long* n0, int R, const double* coef, int hop,
                                           const double* target, double ceiling, double* rec, long seg_cap, const float* tail_in, float* tail_out, double* stats,
                                           float* gain, double* ws, long ws_cap, void* stream) {
-    wl_rows_t rows;
-    long n_max;
-    const int rc = wl_rows("wave_loudness_push", row_off, row_len, R, &rows, &n_max);
+    cbx_wave_rows_t rows;
+    cbx_wave_span_t sp;
+    const int rc = cbx_wave_rows("wave_loudness_push", row_off, row_len, R, &rows, &sp);
     if (rc) return rc;
     CBX_REQUIRE(wav && n0 && coef && target && rec && tail_in && tail_out && stats && gain && ws, "wave_loudness_push: null pointer");
     CBX_REQUIRE(tail_in != tail_out, "wave_loudness_push: tail_out is tail_in (the two tail buffers alternate)");
@@ -452,9 +434,9 @@ extern "C" int cbx_wave_loudness_push_f32(const float* wav, const long* row_off,
     wl_coef_t k;
     if (const int e = wl_coefs("wave_loudness_push", coef, &k)) return e;
     wl_n0_t at;
-    wl_rows_t segs = rows;  // n[r]: the segments of row r after this push
+    cbx_wave_rows_t segs = rows;  // n[r]: the segments of row r after this push
     long k_max = 0;
-    for (int r = 0; r < WL_MAX_ROWS; ++r) at.v[r] = 0;
+    for (int r = 0; r < CBX_WAVE_MAX_ROWS; ++r) at.v[r] = 0;
     for (int r = 0; r < R; ++r) {
         CBX_REQUIRE(n0[r] >= 0, "wave_loudness_push: row %d has consumed %ld samples", r, n0[r]);
         const long K = (n0[r] % hop + row_len[r]) / hop, S1 = n0[r] / hop + K;
@@ -464,7 +446,7 @@ extern "C" int cbx_wave_loudness_push_f32(const float* wav, const long* row_off,
     }
     CBX_REQUIRE(ws_cap >= 4l * R * k_max, "wave_loudness_push: workspace of %ld doubles, %d rows of %ld new segments need %ld", ws_cap, R, k_max, 4l * R * k_max);
     wl_target_t tg;
-    for (int r = 0; r < WL_MAX_ROWS; ++r) tg.t[r] = r < R ? target[r] : (double)NAN;
+    for (int r = 0; r < CBX_WAVE_MAX_ROWS; ++r) tg.t[r] = r < R ? target[r] : (double)NAN;
     const long rec_ld = WL_REC + seg_cap, gx = (k_max + 3) / 4;
     wl_pow_t pw = {};
     int e;
@@ -486,13 +468,13 @@ extern "C" int cbx_wave_loudness_push_f32(const float* wav, const long* row_off,
 }
 
 extern "C" int cbx_wave_gain_f32(float* wav, const long* row_off, const int* row_len, int R, const float* gain, void* stream) {
-    wl_rows_t rows;
-    long n_max;
-    const int rc = wl_rows("wave_gain", row_off, row_len, R, &rows, &n_max);
+    cbx_wave_rows_t rows;
+    cbx_wave_span_t sp;
+    const int rc = cbx_wave_rows("wave_gain", row_off, row_len, R, &rows, &sp);
     if (rc) return rc;
     CBX_REQUIRE(wav && gain, "wave_gain: null pointer");
-    if (n_max == 0) return 0;
-    const long gx = (n_max + 3 + WL_TILE - 1) / WL_TILE;  // (+ 3: a row may begin up to three samples into its first quad)
+    if (sp.n_max == 0) return 0;
+    const long gx = (sp.n_max + 3 + WL_TILE - 1) / WL_TILE;  // (+ 3: a row may begin up to three samples into its first quad)
     hipLaunchKernelGGL(wave_gain_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, gain);
     return cbx_check_launch("wave_gain");
 }

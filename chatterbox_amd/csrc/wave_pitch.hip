@@ -17,21 +17,20 @@
 #include <math.h>
 
 #include "cbx_common.h"
+#include "../../chatterbox_amd/csrc/wave_common.h"  // (by its path from the root: the header says why)
 
 namespace {
 
-constexpr int WP_MAX_ROWS = 64, WP_TILE = 256;
+constexpr int WP_TILE = 256;
 constexpr int WP_SPAN = 640;    // LDS floats of a tile's input span (the entry checks ceil(255 step + 2 Z / c) + 8 against it)
 constexpr int WP_TAB = 4098;    // LDS floats of the table: Z L + 2 <= 4098
 
-struct wp_rows_t {
-    long off[WP_MAX_ROWS];      // first sample of the row, floats from `wav`
-    long out_off[WP_MAX_ROWS];  // first output of the row, floats from `out`
-    double step[WP_MAX_ROWS];   // source samples per output sample
-    double c[WP_MAX_ROWS];      // min(1, 1 / step): the filter's cutoff, relative to the source's Nyquist rate, and its gain
-    double half[WP_MAX_ROWS];   // Z / c: the filter's reach to either side, in source samples
-    int len[WP_MAX_ROWS];       // n: samples of the row
-    int cnt[WP_MAX_ROWS];       // N: outputs of the row
+struct wp_rows_t : cbx_wave_rows_t {       // (3 KiB with the core)
+    long out_off[CBX_WAVE_MAX_ROWS];  // first output of the row, floats from `out`
+    double step[CBX_WAVE_MAX_ROWS];   // source samples per output sample
+    double c[CBX_WAVE_MAX_ROWS];      // min(1, 1 / step): the filter's cutoff, relative to the source's Nyquist rate, and its gain
+    double half[CBX_WAVE_MAX_ROWS];   // Z / c: the filter's reach to either side, in source samples
+    int cnt[CBX_WAVE_MAX_ROWS];       // N: outputs of the row
 };
 
 // the first / last source sample output j may read: max(0, ceil(j step - half)) / min(n - 1, floor(j step + half)); x is a statement of its own, so that the
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(256) void wave_pitch_kernel(const float* __restrict
     __shared__ float s_x[WP_SPAN];
     __shared__ float s_tab[WP_TAB];
     const int r = blockIdx.y, tid = threadIdx.x;
-    const long n = rows.len[r], cnt = rows.cnt[r];
+    const long n = rows.n[r], cnt = rows.cnt[r];
     const long jb = (long)blockIdx.x * WP_TILE;
     if (jb >= cnt) return;  // (uniform over the workgroup, ahead of its barrier)
     const int nt = cnt - jb < WP_TILE ? (int)(cnt - jb) : WP_TILE;
@@ -110,36 +109,24 @@ __global__ __launch_bounds__(256) void wave_pitch_kernel(const float* __restrict
 extern "C" int cbx_wave_pitch_f32(const float* wav, const long* row_off, const int* row_len, const double* step, const int* out_len, int R, const float* tab, int Z,
                                   int L, float* out, const long* out_off, long out_cap, void* stream) {
     CBX_REQUIRE(wav && row_off && row_len && step && out_len && tab && out && out_off, "wave_pitch: null pointer");
-    CBX_REQUIRE(R >= 1 && R <= WP_MAX_ROWS, "wave_pitch: R = %d outside [1, %d]", R, WP_MAX_ROWS);
+    int rc = cbx_wave_count("wave_pitch", row_off, row_len, R);
+    if (rc) return rc;
     CBX_REQUIRE(Z >= 1 && L >= 1 && (long)Z * L + 2 <= WP_TAB, "wave_pitch: a table of Z = %d crossings of L = %d steps (Z, L >= 1, Z L + 2 <= %d)", Z, L, WP_TAB);
-    wp_rows_t rows;
-    for (int r = 0; r < WP_MAX_ROWS; ++r) rows.off[r] = rows.out_off[r] = 0, rows.step[r] = rows.c[r] = 1.0, rows.half[r] = 0.0, rows.len[r] = rows.cnt[r] = 0;
-    long sum = 0, cnt_max = 0, lo = -1, hi = 0, olo = -1, ohi = 0;  // the rows span [lo, hi) of wav, their outputs [olo, ohi) of out
+    wp_rows_t rows = {};     // (entries behind R stay zero: the grid ends at R, the kernel does not read them)
+    cbx_wave_span_t in, to;  // the rows span [lo, hi) of wav, their outputs [lo, hi) of out
+    if ((rc = cbx_wave_rows("wave_pitch", row_off, row_len, R, &rows, &in))) return rc;
+    long cnt[CBX_WAVE_MAX_ROWS];
     for (int r = 0; r < R; ++r) {
-        const long n = row_len[r], N = out_len[r];
         const double s = step[r];
-        CBX_REQUIRE(n >= 0 && row_off[r] >= 0, "wave_pitch: row %d has length %ld at offset %ld", r, n, row_off[r]);
         CBX_REQUIRE(s >= 0.5 && s <= 2.0, "wave_pitch: row %d has step %g (a finite number in [0.5, 2])", r, s);  // (NaN fails both comparisons)
-        CBX_REQUIRE(N >= 0 && out_off[r] >= 0 && out_off[r] + N <= out_cap, "wave_pitch: row %d writes [%ld, %ld) of an output of %ld", r, out_off[r], out_off[r] + N, out_cap);
         const double c = s > 1.0 ? 1.0 / s : 1.0, half = (double)Z / c;
         CBX_REQUIRE(ceil((WP_TILE - 1) * s + 2.0 * half) + 8.0 <= WP_SPAN, "wave_pitch: Z = %d at step %g does not fit the kernel's LDS", Z, s);
-        rows.off[r] = row_off[r], rows.out_off[r] = out_off[r], rows.step[r] = s, rows.c[r] = c, rows.half[r] = half, rows.len[r] = (int)n, rows.cnt[r] = (int)N;
-        sum += N;
-        cnt_max = N > cnt_max ? N : cnt_max;
-        if (n > 0) {
-            lo = lo < 0 || row_off[r] < lo ? row_off[r] : lo;
-            hi = row_off[r] + n > hi ? row_off[r] + n : hi;
-        }
-        if (N > 0) {
-            olo = olo < 0 || out_off[r] < olo ? out_off[r] : olo;
-            ohi = out_off[r] + N > ohi ? out_off[r] + N : ohi;
-        }
+        rows.out_off[r] = out_off[r], rows.step[r] = s, rows.c[r] = c, rows.half[r] = half, rows.cnt[r] = out_len[r];
+        cnt[r] = out_len[r];
     }
-    CBX_REQUIRE(sum <= out_cap, "wave_pitch: out holds %ld samples, the rows produce %ld", out_cap, sum);
-    if (lo >= 0 && olo >= 0) {
-        const uintptr_t a0 = (uintptr_t)(wav + lo), a1 = (uintptr_t)(wav + hi), b0 = (uintptr_t)(out + olo), b1 = (uintptr_t)(out + ohi);
-        CBX_REQUIRE(a1 <= b0 || b1 <= a0, "wave_pitch: out overlaps wav (an output reads samples on either side of its position)");
-    }
+    if ((rc = cbx_wave_packed("wave_pitch", out_off, cnt, R, out_cap, "samples", &to))) return rc;
+    if ((rc = cbx_wave_apart("wave_pitch", wav, in, out, to, "an output reads samples on either side of its position"))) return rc;
+    const long cnt_max = to.n_max;
     if (cnt_max == 0) return 0;
     hipLaunchKernelGGL(wave_pitch_kernel, dim3((unsigned)((cnt_max + WP_TILE - 1) / WP_TILE), (unsigned)R), dim3(WP_TILE), 0, (hipStream_t)stream, wav, rows,
                        tab, Z * L, (double)L, out);

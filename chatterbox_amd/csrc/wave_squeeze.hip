@@ -14,15 +14,14 @@
 #include <math.h>
 
 #include "cbx_common.h"
+#include "../../chatterbox_amd/csrc/wave_common.h"  // (by its path from the root: the header says why)
 
 namespace {
 
-constexpr int WS_MAX_ROWS = 64, WS_FRAME = 480, WS_TILE = 256, WS_NONE = 0x7fffffff;
+constexpr int WS_FRAME = 480, WS_TILE = 256, WS_NONE = 0x7fffffff;
 
-struct ws_rows_t {
-    long off[WS_MAX_ROWS];
-    int n[WS_MAX_ROWS];
-    int keep[WS_MAX_ROWS];
+struct ws_rows_t : cbx_wave_rows_t {
+    int keep[CBX_WAVE_MAX_ROWS];
 };
 
 template <int MASK>
@@ -204,29 +203,20 @@ __global__ __launch_bounds__(256) void wave_squeeze_gather_kernel(const float* _
 extern "C" int cbx_wave_squeeze_f32(const float* wav, const long* row_off, const int* row_len, const int* keep, int R, double ratio, const float* ramp, int fade,
                                     float* out, long out_cap, int* edges, int* stats, void* ws, long ws_cap, void* stream) {
     CBX_REQUIRE(wav && row_off && row_len && keep && out && stats && ws, "wave_squeeze: null pointer");
-    CBX_REQUIRE(R >= 1 && R <= WS_MAX_ROWS, "wave_squeeze: R = %d outside [1, %d]", R, WS_MAX_ROWS);
-    ws_rows_t rows;
-    for (int r = 0; r < WS_MAX_ROWS; ++r) rows.off[r] = 0, rows.n[r] = 0, rows.keep[r] = 0;
-    long n_max = 0, lo = -1, hi = 0;  // the rows span [lo, hi) of either buffer
+    ws_rows_t rows = {};
+    cbx_wave_span_t sp;  // the rows span [lo, hi) of either buffer
+    int rc = cbx_wave_rows("wave_squeeze", row_off, row_len, R, &rows, &sp);
+    if (rc) return rc;
     for (int r = 0; r < R; ++r) {
-        CBX_REQUIRE(row_len[r] >= 0 && row_off[r] >= 0, "wave_squeeze: row %d has length %d at offset %ld", r, row_len[r], row_off[r]);
         CBX_REQUIRE(keep[r] == 0 || keep[r] >= 2, "wave_squeeze: row %d keeps %d frames of a pause (0: the row is copied; else >= 2)", r, keep[r]);
-        rows.off[r] = row_off[r], rows.n[r] = row_len[r], rows.keep[r] = keep[r];
-        n_max = row_len[r] > n_max ? row_len[r] : n_max;
-        if (row_len[r] > 0) {
-            lo = lo < 0 || row_off[r] < lo ? row_off[r] : lo;
-            hi = row_off[r] + row_len[r] > hi ? row_off[r] + row_len[r] : hi;
-        }
+        rows.keep[r] = keep[r];
     }
     CBX_REQUIRE(ratio >= 0.0 && ratio < INFINITY, "wave_squeeze: bad threshold (ratio %g)", ratio);
     CBX_REQUIRE(fade >= 0 && fade <= WS_FRAME, "wave_squeeze: fade = %d outside [0, %d]", fade, WS_FRAME);
     CBX_REQUIRE(fade == 0 || ramp, "wave_squeeze: fade = %d without a ramp", fade);
-    CBX_REQUIRE(out_cap >= hi, "wave_squeeze: out holds %ld samples, the furthest row ends at %ld", out_cap, hi);
-    if (lo >= 0) {
-        const uintptr_t a0 = (uintptr_t)(wav + lo), a1 = (uintptr_t)(wav + hi), b0 = (uintptr_t)(out + lo), b1 = (uintptr_t)(out + hi);
-        CBX_REQUIRE(a1 <= b0 || b1 <= a0, "wave_squeeze: out overlaps wav (the rows are gathered, not moved in place)");
-    }
-    const long nf = (n_max + WS_FRAME - 1) / WS_FRAME;
+    CBX_REQUIRE(out_cap >= sp.hi, "wave_squeeze: out holds %ld samples, the furthest row ends at %ld", out_cap, sp.hi);
+    if ((rc = cbx_wave_apart("wave_squeeze", wav, sp, out, sp, "the rows are gathered, not moved in place"))) return rc;
+    const long nf = (sp.n_max + WS_FRAME - 1) / WS_FRAME;
     const long need = 16 * (long)R * nf;  // R * nf doubles (m_f), R * nf ints (next non-silent frame), R * nf ints (src)
     CBX_REQUIRE(ws_cap >= need && ((uintptr_t)ws & 7) == 0, "wave_squeeze: workspace of %ld bytes at %p, %d rows of %ld frames need %ld on an 8-byte boundary", ws_cap, ws,
                 R, nf, need);

@@ -968,10 +968,11 @@ def scaled_len(n, rate):
     return max(1, int(math.floor(int(n) / float(rate))))
 
 
-def check_speed(value, B, name="speed"):
-    """A `speed` argument as a list of B floats, or None when no request is scaled (None, or every entry 1.0 or None).  A number serves every request; anything
-    else must be a list or tuple of exactly B numbers (or None: 1.0) in [0.5, 2.0].  A bool or a non-number is a TypeError; a non-finite or out-of-range value and
-    a wrong length are ValueErrors -- raised before anything is launched."""
+def _per_request_numbers(value, B, name, lo, hi, what, *, scalar="None, a number", entry="None or a number", plural="numbers", none_as=None, finish=None):
+    """The one shape of the per-request number arguments (speed, pitch, loudness, true_peak, duration): None, a number that serves every request, or a list / tuple
+    of exactly B numbers / Nones, every number finite and in [lo, hi] -> B entries, a None as `none_as` and a number through `finish`, or None when every entry is
+    `none_as`.  A bool or a non-number is a TypeError, a non-finite or out-of-range value and a wrong length are ValueErrors; `what`, `scalar`, `entry` and
+    `plural` are the words in which the messages of the five arguments differ."""
     import math
     import numbers
     one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
@@ -980,20 +981,28 @@ def check_speed(value, B, name="speed"):
     if one(value):
         value = [value] * B
     elif not isinstance(value, (list, tuple)):
-        raise TypeError(f"{name}: expected a number or a list of {B} numbers, got {type(value).__name__}")
+        raise TypeError(f"{name}: expected {scalar} or a list of {B} {plural}, got {type(value).__name__}")
     if len(value) != B:
         raise ValueError(f"{name}: {len(value)} entries for {B} requests")
     out = []
     for k, v in enumerate(value):
         if v is None:
-            v = 1.0
+            out.append(none_as)
+            continue
         if not one(v):
-            raise TypeError(f"{name}[{k}]: expected a number, got {type(v).__name__}")
+            raise TypeError(f"{name}[{k}]: expected {entry}, got {type(v).__name__}")
         v = float(v)
-        if not math.isfinite(v) or not SPEED_MIN <= v <= SPEED_MAX:
-            raise ValueError(f"{name}[{k}] = {v}: a speed is a finite number in [{SPEED_MIN}, {SPEED_MAX}]")
-        out.append(v)
-    return None if all(v == 1.0 for v in out) else out
+        if not math.isfinite(v) or not lo <= v <= hi:
+            raise ValueError(f"{name}[{k}] = {v}: {what} in [{lo}, {hi}]")
+        out.append(finish(v) if finish else v)
+    return None if all(v == none_as for v in out) else out
+
+
+def check_speed(value, B, name="speed"):
+    """A `speed` argument as a list of B floats, or None when no request is scaled (None, or every entry 1.0 or None).  A number serves every request; anything
+    else must be a list or tuple of exactly B numbers (or None: 1.0) in [0.5, 2.0].  A bool or a non-number is a TypeError; a non-finite or out-of-range value and
+    a wrong length are ValueErrors -- raised before anything is launched."""
+    return _per_request_numbers(value, B, name, SPEED_MIN, SPEED_MAX, "a speed is a finite number", scalar="a number", entry="a number", none_as=1.0)
 
 
 def mel_time_scale(mel, rates, in_lens=None, out=None):
@@ -1132,29 +1141,8 @@ def check_duration(value, B, name="duration"):
     """A `duration` argument as a list of B target lengths in FRAMES (seconds_to_frames) / Nones, or None when no request has one.  A number serves every
     request; anything else is a list or tuple of exactly B numbers / Nones in [0.02, 80] seconds.  A bool or a non-number is a TypeError; a non-finite or
     out-of-range value and a wrong length are ValueErrors -- raised before anything is launched."""
-    import math
-    import numbers
-    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
-    if value is None:
-        return None
-    if one(value):
-        value = [value] * B
-    elif not isinstance(value, (list, tuple)):
-        raise TypeError(f"{name}: expected a number of seconds or a list of {B} numbers / Nones, got {type(value).__name__}")
-    if len(value) != B:
-        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
-    out = []
-    for k, v in enumerate(value):
-        if v is None:
-            out.append(None)
-            continue
-        if not one(v):
-            raise TypeError(f"{name}[{k}]: expected a number of seconds or None, got {type(v).__name__}")
-        v = float(v)
-        if not math.isfinite(v) or not DURATION_MIN <= v <= DURATION_MAX:
-            raise ValueError(f"{name}[{k}] = {v}: a duration is a finite number of seconds in [{DURATION_MIN}, {DURATION_MAX}]")
-        out.append(seconds_to_frames(v))
-    return None if all(v is None for v in out) else out
+    return _per_request_numbers(value, B, name, DURATION_MIN, DURATION_MAX, "a duration is a finite number of seconds", scalar="a number of seconds",
+                                entry="a number of seconds or None", plural="numbers / Nones", finish=seconds_to_frames)
 
 
 def check_timing(value, B, name="timing"):
@@ -1254,7 +1242,20 @@ def mel_time_warp(mel, tables, in_lens=None, out=None, out_lens=None):
 # ----------------------------------------------------------------------------- long-form synthesis: trim + join the waveforms of a sub-batch (wave_join.hip)
 WAVE_FRAME, WAVE_JOIN_MAX_ROWS = 480, 64
 JOIN_KEYS = ("gaps", "trim_db", "pad_frames", "fade", "first", "last")
-_JOIN_RAMPS = {}
+_DEVICE_TABLES = {}
+
+
+def _on_device(key, device, make):
+    """make() -- a NumPy array or a tensor, one of the delivery kernels' tables -- on `device`: built and uploaded once per (key, device)"""
+    key = (key, str(device))
+    if key not in _DEVICE_TABLES:
+        _DEVICE_TABLES[key] = torch.as_tensor(make()).to(device)
+    return _DEVICE_TABLES[key]
+
+
+def _all_empty(rows):
+    """every row is an empty tensor: such rows may have no allocation to point at, and there is nothing to launch"""
+    return bool(rows) and all(torch.is_tensor(w) and w.numel() == 0 for w in rows)
 
 
 def check_join(join, R, name="join"):
@@ -1305,10 +1306,7 @@ def join_ramp(fade, device):
     fade = int(fade)
     if fade == 0:
         return None
-    key = (fade, str(device))
-    if key not in _JOIN_RAMPS:
-        _JOIN_RAMPS[key] = ((2.0 * torch.arange(fade, dtype=torch.float64) + 1.0) / (2.0 * fade)).float().to(device)
-    return _JOIN_RAMPS[key]
+    return _on_device(("join_ramp", fade), device, lambda: ((2.0 * torch.arange(fade, dtype=torch.float64) + 1.0) / (2.0 * fade)).float())
 
 
 def _wave_rows(rows, who):
@@ -1479,7 +1477,7 @@ def piece_on_host(out, rec, n, fmt=None):
 # ----------------------------------------------------------------------------- pitch control: the waveform read back at a real step (wave_pitch.hip)
 PITCH_MIN, PITCH_MAX = -12.0, 12.0               # semitones a caller may ask for
 PITCH_Z, PITCH_L, PITCH_BETA = 16, 256, 9.0      # zero crossings per side, table steps per crossing, Kaiser beta: UNMEASURED choices
-_PITCH_FILTER, _PITCH_TABLES = {}, {}
+_PITCH_FILTER = {}
 
 
 def pitch_ratio(p):
@@ -1491,28 +1489,7 @@ def check_pitch(value, B, name="pitch"):
     """A `pitch` argument as a list of B floats (semitones; a None entry is 0.0), or None when no request is transposed (None, or every entry None or 0).  A
     number serves every request; anything else must be a list or tuple of exactly B numbers / Nones in [-12, 12].  A bool or a non-number is a TypeError; a
     non-finite or out-of-range value and a wrong length are ValueErrors -- raised before anything is launched."""
-    import math
-    import numbers
-    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
-    if value is None:
-        return None
-    if one(value):
-        value = [value] * B
-    elif not isinstance(value, (list, tuple)):
-        raise TypeError(f"{name}: expected None, a number or a list of {B} numbers, got {type(value).__name__}")
-    if len(value) != B:
-        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
-    out = []
-    for k, v in enumerate(value):
-        if v is None:
-            v = 0.0
-        if not one(v):
-            raise TypeError(f"{name}[{k}]: expected None or a number, got {type(v).__name__}")
-        v = float(v)
-        if not math.isfinite(v) or not PITCH_MIN <= v <= PITCH_MAX:
-            raise ValueError(f"{name}[{k}] = {v}: a pitch is a finite number of semitones in [{PITCH_MIN}, {PITCH_MAX}]")
-        out.append(v)
-    return None if all(v == 0.0 for v in out) else out
+    return _per_request_numbers(value, B, name, PITCH_MIN, PITCH_MAX, "a pitch is a finite number of semitones", none_as=0.0)
 
 
 def check_speed_pitch(speed, pitch, B):
@@ -1549,10 +1526,7 @@ def pitch_filter():
 
 def _pitch_table(device):
     """pitch_filter's table on `device`, uploaded once per device"""
-    key = str(device)
-    if key not in _PITCH_TABLES:
-        _PITCH_TABLES[key] = torch.from_numpy(pitch_filter()["tab"]).to(device)
-    return _PITCH_TABLES[key]
+    return _on_device("pitch", device, lambda: pitch_filter()["tab"])
 
 
 def wave_pitch(rows, steps, out_lens):
@@ -1566,7 +1540,7 @@ def wave_pitch(rows, steps, out_lens):
         raise ValueError(f"wave_pitch: {len(steps)} steps and {len(out_lens)} lengths for {len(rows)} rows")
     if any(n < 0 for n in out_lens):
         raise ValueError(f"wave_pitch: out_lens {out_lens}")
-    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: every tap reads outside its row)
+    if _all_empty(rows):  # (every tap reads outside its row)
         return [torch.zeros(n, device=w.device) for w, n in zip(rows, out_lens)]
     base, offs, lens = _wave_rows(rows, "wave_pitch")
     R, dev, f = len(lens), rows[0].device, pitch_filter()
@@ -1586,7 +1560,7 @@ WAVE_IN_RATE = 24000
 WAVE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
 WAVE_ENCODINGS = ("f32", "s16", "mulaw", "alaw")   # cbx_wave_format_f32's encoding 0 .. 3
 _WAVE_DTYPES = (torch.float32, torch.int16, torch.uint8, torch.uint8)
-_WAVE_FILTERS, _WAVE_TABLES = {}, {}
+_WAVE_FILTERS = {}
 
 
 def check_format(sample_rate=None, encoding=None, name="format"):
@@ -1625,39 +1599,40 @@ def _wave_fmt(fmt):
     return fmt["sample_rate"], WAVE_ENCODINGS.index(fmt["encoding"])
 
 
-def wave_filter(sample_rate):
-    """The resampler 24000 -> sample_rate as scipy.signal.resample_poly designs it, restated in NumPy fp64 (no SciPy in the product path): U / D the reduced
-    ratio, hl = 10 max(U, D), h = U firwin(2 hl + 1, 1 / max(U, D), window=("kaiser", 5.0)) -- the windowed sinc cutoff sinc(cutoff (i - hl)) times np.kaiser,
+def _poly_filter(U, D):
+    """THE resampler design of the delivery kernels, scipy.signal.resample_poly's for the reduced ratio U / D restated in NumPy fp64 (no SciPy in the product
+    path): hl = 10 max(U, D), h = U firwin(2 hl + 1, 1 / max(U, D), window=("kaiser", 5.0)) -- the windowed sinc cutoff sinc(cutoff (i - hl)) times np.kaiser,
     scaled to unit gain at 0 --, tab (U, T) fp32 = h[p + j U] (zero past 2 hl), T = ceil((2 hl + 1) / U) taps per output, H = ceil(2 hl / U) samples of history.
+    U == D: no filter (U = D = T = 1, hl = H = 0, tab = [[1]]).  -> a new dict(U, D, hl, T, H, h, tab)."""
+    import numpy as np
+    if U == D:
+        return dict(U=1, D=1, hl=0, T=1, H=0, h=np.ones(1), tab=np.ones((1, 1), np.float32))
+    hl, cutoff = 10 * max(U, D), 1.0 / max(U, D)
+    i = np.arange(2 * hl + 1, dtype=np.float64) - hl
+    h = cutoff * np.sinc(cutoff * i) * np.kaiser(2 * hl + 1, 5.0)
+    h = U * (h / h.sum())
+    T = -(-(2 * hl + 1) // U)
+    pad = np.zeros(U * T)
+    pad[: 2 * hl + 1] = h
+    return dict(U=U, D=D, hl=hl, T=T, H=-(-2 * hl // U), h=h, tab=np.ascontiguousarray(pad.reshape(T, U).T.astype(np.float32)))
+
+
+def wave_filter(sample_rate):
+    """The resampler 24000 -> sample_rate as scipy.signal.resample_poly designs it (_poly_filter states the design): U / D the reduced ratio, hl = 10 max(U, D),
+    h the fp64 taps, tab (U, T) fp32 = h[p + j U], T = ceil((2 hl + 1) / U) taps per output, H = ceil(2 hl / U) samples of history.
     24000: no filter (hl = H = 0, T = 1, tab = [[1]]).  Built once per rate."""
     import math
-    import numpy as np
     if sample_rate not in _WAVE_FILTERS:
         if sample_rate not in WAVE_RATES:
             raise ValueError(f"sample_rate = {sample_rate}: expected one of {WAVE_RATES}")
         g = math.gcd(sample_rate, WAVE_IN_RATE)
-        U, D = sample_rate // g, WAVE_IN_RATE // g
-        if U == D:
-            f = dict(U=1, D=1, hl=0, T=1, H=0, h=np.ones(1), tab=np.ones((1, 1), np.float32))
-        else:
-            hl, cutoff = 10 * max(U, D), 1.0 / max(U, D)
-            i = np.arange(2 * hl + 1, dtype=np.float64) - hl
-            h = cutoff * np.sinc(cutoff * i) * np.kaiser(2 * hl + 1, 5.0)
-            h = U * (h / h.sum())
-            T = -(-(2 * hl + 1) // U)
-            pad = np.zeros(U * T)
-            pad[: 2 * hl + 1] = h
-            f = dict(U=U, D=D, hl=hl, T=T, H=-(-2 * hl // U), h=h, tab=np.ascontiguousarray(pad.reshape(T, U).T.astype(np.float32)))
-        _WAVE_FILTERS[sample_rate] = f
+        _WAVE_FILTERS[sample_rate] = _poly_filter(sample_rate // g, WAVE_IN_RATE // g)
     return _WAVE_FILTERS[sample_rate]
 
 
 def _wave_table(sample_rate, device):
     """wave_filter's phase table on `device`, uploaded once per (device, rate)"""
-    key = (str(device), sample_rate)
-    if key not in _WAVE_TABLES:
-        _WAVE_TABLES[key] = torch.from_numpy(wave_filter(sample_rate)["tab"]).to(device)
-    return _WAVE_TABLES[key]
+    return _on_device(("wave", sample_rate), device, lambda: wave_filter(sample_rate)["tab"])
 
 
 def formatted_len(n, sample_rate):
@@ -1699,7 +1674,7 @@ def wave_format(rows, fmt):
     No host synchronisation."""
     rate, enc = _wave_fmt(fmt)
     rows = list(rows)
-    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+    if _all_empty(rows):
         return [torch.empty(0, dtype=_WAVE_DTYPES[enc], device=w.device) for w in rows]
     packed, spans = _wave_format_launch(rows, rate, enc)
     return [packed[a: a + c] for a, c in spans]
@@ -1767,27 +1742,7 @@ def check_loudness(value, B, name="loudness"):
     """A `loudness` argument as a list of B entries -- a float (the LUFS target of that request) or None (that request is left alone) --, or None when no request
     is normalised.  A number serves every request; anything else must be a list or tuple of exactly B numbers or Nones, each number finite and in [-50, -5].  A
     bool or a non-number is a TypeError; a non-finite or out-of-range value and a wrong length are ValueErrors -- raised before anything is launched."""
-    import math
-    import numbers
-    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
-    if value is None:
-        return None
-    if one(value):
-        value = [value] * B
-    elif not isinstance(value, (list, tuple)):
-        raise TypeError(f"{name}: expected None, a number or a list of {B} numbers, got {type(value).__name__}")
-    if len(value) != B:
-        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
-    out = []
-    for k, v in enumerate(value):
-        if v is not None:
-            if not one(v):
-                raise TypeError(f"{name}[{k}]: expected None or a number, got {type(v).__name__}")
-            v = float(v)
-            if not math.isfinite(v) or not LOUDNESS_MIN <= v <= LOUDNESS_MAX:
-                raise ValueError(f"{name}[{k}] = {v}: a loudness target is a finite number of LUFS in [{LOUDNESS_MIN}, {LOUDNESS_MAX}]")
-        out.append(v)
-    return None if all(v is None for v in out) else out
+    return _per_request_numbers(value, B, name, LOUDNESS_MIN, LOUDNESS_MAX, "a loudness target is a finite number of LUFS")
 
 
 def wave_loudness(rows, target=None, ceiling=1.0, fs=WAVE_IN_RATE):
@@ -1887,7 +1842,7 @@ def wave_normalize(rows, target, ceiling=1.0, fs=WAVE_IN_RATE):
     """wave_loudness + wave_gain: every row with a target is brought to it in place (limited to a sample peak of `ceiling`); rows whose target is None, silent rows
     and rows shorter than 0.4 s keep their samples.  Returns the (R, 4) stats.  Five launches, no host synchronisation."""
     rows = list(rows)
-    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+    if _all_empty(rows):
         return torch.tensor([[float("-inf"), 0.0, 1.0, 0.0]] * len(rows), dtype=torch.float64).to(rows[0].device)
     stats, gain = wave_loudness(rows, target, ceiling, fs)
     wave_gain(rows, gain)
@@ -1899,23 +1854,15 @@ TRUE_PEAK_MIN, TRUE_PEAK_MAX = -20.0, 0.0   # dBTP ceilings a caller may ask for
 LIMIT_OVERSAMPLE = 4                        # U: the true peak is read on the 4-times oversampled signal (ITU-R BS.1770-4 annex 2 asks for at least 4 at 48 kHz)
 LIMIT_LOOK = 120                            # H: look-ahead and release, samples at 24 kHz (5 ms).  UNMEASURED choice
 LIMIT_LOOK_MAX = 480
-_LIMIT_FILTER, _LIMIT_WINDOWS, _LIMIT_TABLES = [], {}, {}
+_LIMIT_FILTER, _LIMIT_WINDOWS = [], {}
 
 
 def true_peak_filter():
     """The oversampler of the true-peak meter, wave_filter's design (scipy.signal.resample_poly's, restated in NumPy fp64): U = 4, hl = 10 U = 40,
     h = U firwin(2 hl + 1, 1 / U, window=("kaiser", 5.0)), tab (U, T) fp32 = h[p + j U] (zero past 2 hl), T = ceil((2 hl + 1) / U) = 21.  Built once."""
-    import numpy as np
     if not _LIMIT_FILTER:
-        U = LIMIT_OVERSAMPLE
-        hl, cutoff = 10 * U, 1.0 / U
-        i = np.arange(2 * hl + 1, dtype=np.float64) - hl
-        h = cutoff * np.sinc(cutoff * i) * np.kaiser(2 * hl + 1, 5.0)
-        h = U * (h / h.sum())
-        T = -(-(2 * hl + 1) // U)
-        pad = np.zeros(U * T)
-        pad[: 2 * hl + 1] = h
-        _LIMIT_FILTER.append(dict(U=U, hl=hl, T=T, h=h, tab=np.ascontiguousarray(pad.reshape(T, U).T.astype(np.float32))))
+        f = _poly_filter(LIMIT_OVERSAMPLE, 1)
+        _LIMIT_FILTER.append({k: f[k] for k in ("U", "hl", "T", "h", "tab")})
     return _LIMIT_FILTER[0]
 
 
@@ -1934,38 +1881,15 @@ def limit_window(H=LIMIT_LOOK):
 
 
 def _limit_tables(H, device):
-    """(phase table, window) on `device`, uploaded once per (device, H)"""
-    key = (str(device), H)
-    if key not in _LIMIT_TABLES:
-        _LIMIT_TABLES[key] = (torch.from_numpy(true_peak_filter()["tab"]).to(device), torch.from_numpy(limit_window(H)).to(device))
-    return _LIMIT_TABLES[key]
+    """(phase table, window) on `device`, each uploaded once per device (the window per H)"""
+    return _on_device("true_peak", device, lambda: true_peak_filter()["tab"]), _on_device(("limit_window", H), device, lambda: limit_window(H))
 
 
 def check_true_peak(value, B, name="true_peak"):
     """A `true_peak` argument as a list of B entries -- a float (the ceiling of that request in dBTP) or None (that request is not limited) --, or None when no
     request is limited.  A number serves every request; anything else must be a list or tuple of exactly B numbers or Nones, each number finite and in [-20, 0].
     A bool or a non-number is a TypeError; a non-finite or out-of-range value and a wrong length are ValueErrors -- raised before anything is launched."""
-    import math
-    import numbers
-    one = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
-    if value is None:
-        return None
-    if one(value):
-        value = [value] * B
-    elif not isinstance(value, (list, tuple)):
-        raise TypeError(f"{name}: expected None, a number or a list of {B} numbers, got {type(value).__name__}")
-    if len(value) != B:
-        raise ValueError(f"{name}: {len(value)} entries for {B} requests")
-    out = []
-    for k, v in enumerate(value):
-        if v is not None:
-            if not one(v):
-                raise TypeError(f"{name}[{k}]: expected None or a number, got {type(v).__name__}")
-            v = float(v)
-            if not math.isfinite(v) or not TRUE_PEAK_MIN <= v <= TRUE_PEAK_MAX:
-                raise ValueError(f"{name}[{k}] = {v}: a true-peak ceiling is a finite number of dBTP in [{TRUE_PEAK_MIN}, {TRUE_PEAK_MAX}]")
-        out.append(v)
-    return None if all(v is None for v in out) else out
+    return _per_request_numbers(value, B, name, TRUE_PEAK_MIN, TRUE_PEAK_MAX, "a true-peak ceiling is a finite number of dBTP")
 
 
 def _wave_limit_launch(rows, ceilings, gain, look, out):
@@ -2001,7 +1925,7 @@ def wave_true_peak(rows):
     allocation at 24 kHz).  Returns the (R, 4) float64 stats {true peak (NaN for a row with a NaN), 1, 0, 0} on the device; nothing is written but them, nothing is
     synchronised."""
     rows = list(rows)
-    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+    if _all_empty(rows):
         return _empty_limit_stats(rows)
     return _wave_limit_launch(rows, [None] * len(rows), None, LIMIT_LOOK, None)
 
@@ -2018,7 +1942,7 @@ def wave_limit(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None):
         ceilings_db = [ceilings_db] * len(rows)
     ceil = [None if c is None else 10.0 ** (float(c) / 20.0) for c in ceilings_db]
     limit_window(look)
-    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+    if _all_empty(rows):
         return (list(out) if out is not None else [torch.empty(0, dtype=torch.float32, device=w.device) for w in rows]), _empty_limit_stats(rows)
     if out is None:
         base, offs, lens = _wave_rows(rows, "wave_limit")
@@ -2037,15 +1961,14 @@ WAVE_IN_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 8
 WAVE_INGEST_MAX_SPAN, WAVE_INGEST_MAX_TAB = 2048, 16384   # CBX_WAVE_INGEST_MAX_SPAN / _TAB of include/cbx.h
 WAVE_IN_MAX_CHANNELS = 8
 _WAVE_IN_DTYPES = {torch.uint8: None, torch.int16: "s16", torch.int32: "s32", torch.float32: "f32"}   # a typed row must hold its own encoding; uint8 rows hold any
-_RESAMPLE_FILTERS, _RESAMPLE_TABLES = {}, {}
+_RESAMPLE_FILTERS = {}
 
 
 def resample_filter(rate_in, rate_out):
-    """wave_filter for any pair of rates: the resampler rate_in -> rate_out as scipy.signal.resample_poly designs it (NumPy fp64; wave_filter states the design):
+    """wave_filter for any pair of rates: the resampler rate_in -> rate_out as scipy.signal.resample_poly designs it (NumPy fp64; _poly_filter states the design):
     dict(U, D, hl, T, h, tab (U, T) fp32).  Equal rates: no filter (U = D = T = 1, hl = 0).  Rates are positive ints (TypeError / ValueError); a pair whose reduced
     table or tile span is over cbx_wave_ingest's caps is a ValueError -- there is no host fallback.  Built once per pair."""
     import math
-    import numpy as np
     for name, v in (("rate_in", rate_in), ("rate_out", rate_out)):
         if isinstance(v, bool) or not isinstance(v, int):
             raise TypeError(f"{name}: expected an int, got {type(v).__name__}")
@@ -2055,31 +1978,19 @@ def resample_filter(rate_in, rate_out):
     if key not in _RESAMPLE_FILTERS:
         g = math.gcd(rate_in, rate_out)
         U, D = rate_out // g, rate_in // g
-        if U == D:
-            f = dict(U=1, D=1, hl=0, T=1, h=np.ones(1), tab=np.ones((1, 1), np.float32))
-        else:
-            hl = 10 * max(U, D)
-            T = -(-(2 * hl + 1) // U)
-            if U * T > WAVE_INGEST_MAX_TAB or 255 * D // U + T + 1 > WAVE_INGEST_MAX_SPAN:
-                raise ValueError(f"no conversion from {rate_in} to {rate_out} samples per second: U / D = {U} / {D} needs a table of {U * T} floats (cap "
-                                 f"{WAVE_INGEST_MAX_TAB}) and a span of {255 * D // U + T + 1} frames (cap {WAVE_INGEST_MAX_SPAN})")
-            cutoff = 1.0 / max(U, D)
-            i = np.arange(2 * hl + 1, dtype=np.float64) - hl
-            h = cutoff * np.sinc(cutoff * i) * np.kaiser(2 * hl + 1, 5.0)
-            h = U * (h / h.sum())
-            pad = np.zeros(U * T)
-            pad[: 2 * hl + 1] = h
-            f = dict(U=U, D=D, hl=hl, T=T, h=h, tab=np.ascontiguousarray(pad.reshape(T, U).T.astype(np.float32)))
+        T = -(-(20 * max(U, D) + 1) // U)  # (the caps are checked ahead of the design: a table over them is never built)
+        if U != D and (U * T > WAVE_INGEST_MAX_TAB or 255 * D // U + T + 1 > WAVE_INGEST_MAX_SPAN):
+            raise ValueError(f"no conversion from {rate_in} to {rate_out} samples per second: U / D = {U} / {D} needs a table of {U * T} floats (cap "
+                             f"{WAVE_INGEST_MAX_TAB}) and a span of {255 * D // U + T + 1} frames (cap {WAVE_INGEST_MAX_SPAN})")
+        f = _poly_filter(U, D)
+        del f["H"]
         _RESAMPLE_FILTERS[key] = f
     return _RESAMPLE_FILTERS[key]
 
 
 def _resample_table(rate_in, rate_out, device):
     """resample_filter's phase table on `device`, uploaded once per (device, pair)"""
-    key = (str(device), rate_in, rate_out)
-    if key not in _RESAMPLE_TABLES:
-        _RESAMPLE_TABLES[key] = torch.from_numpy(resample_filter(rate_in, rate_out)["tab"]).to(device)
-    return _RESAMPLE_TABLES[key]
+    return _on_device(("resample", rate_in, rate_out), device, lambda: resample_filter(rate_in, rate_out)["tab"])
 
 
 def resampled_len(n, rate_in, rate_out):
@@ -2173,7 +2084,7 @@ def wave_ingest(rows, encoding, channels, rate_in, rate_out):
         raise ValueError(f"wave_ingest: channels = {channels!r}: expected an int in 1 .. {WAVE_IN_MAX_CHANNELS}")
     f = resample_filter(rate_in, rate_out)
     rows = list(rows)
-    if rows and all(torch.is_tensor(w) and w.numel() == 0 for w in rows):  # (empty tensors may have no allocation to point at: nothing to launch)
+    if _all_empty(rows):
         return [torch.empty(0, dtype=torch.float32, device=w.device) for w in rows]
     base, offs, nfr, frames = _ingest_rows(rows, encoding, channels)
     R, dev = len(frames), rows[0].device

@@ -140,7 +140,8 @@ def transform(src, name):
     s = re.sub(r"extern\s+__shared__\s+(?:__attribute__\(\(aligned\(\d+\)\)\)\s+)?([A-Za-z_][\w ]*?)\s+(\w+)\[\];",
                lambda m: f"{m.group(1)}* {m.group(2)} = ({m.group(1)}*)simt::dyn_lds();", s)
     assert "extern __shared__" not in s, f"{name}: an extern __shared__ declaration was not rewritten"
-    return s
+    # a header of csrc named by its path from the root (wave_common.h) is the rewritten copy beside the generated source
+    return s.replace('"../../chatterbox_amd/csrc/', '"')
 
 
 def _digest(files):
@@ -154,7 +155,8 @@ def _digest(files):
 
 def build(force=False, verbose=False):
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
-    deps = srcs + [os.path.join(CSRC, "cbx_common.h"), os.path.join(ROOT, "include", "cbx.h"), os.path.join(HERE, "simt_emu.h"),
+    hdrs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    deps = srcs + hdrs + [os.path.join(ROOT, "include", "cbx.h"), os.path.join(HERE, "simt_emu.h"),
                    os.path.join(HERE, "simt_core.cpp"), os.path.abspath(__file__)]
     dig = _digest(deps)
     stamp = os.path.join(GEN, ".stamp")
@@ -166,9 +168,10 @@ def build(force=False, verbose=False):
     # keep the sources' relative include of ../../include/cbx.h working: _gen/csrc/x.hip -> _gen/../../include does not exist, so copy
     with open(os.path.join(ROOT, "include", "cbx.h")) as f:
         cbx_h = f.read()
-    gen_common = transform(open(os.path.join(CSRC, "cbx_common.h")).read(), "cbx_common.h").replace('"../../include/cbx.h"', '"cbx.h"')
-    with open(os.path.join(GEN, "csrc", "cbx_common.h"), "w") as f:
-        f.write(gen_common)
+    for hdr in hdrs:
+        name = os.path.basename(hdr)
+        with open(os.path.join(GEN, "csrc", name), "w") as f:
+            f.write(transform(open(hdr).read(), name).replace('"../../include/cbx.h"', '"cbx.h"'))
     with open(os.path.join(GEN, "csrc", "cbx.h"), "w") as f:
         f.write(cbx_h)
     objs, procs = [], []

@@ -629,3 +629,40 @@ def test_every_kernel_entry_point_is_named_by_a_kernel_level_test():
     assert not missing, f"entry points that launch kernels but that no kernel-level test names: {missing}"
     for e in ("cbx_axpby_f32", "cbx_dwconv1d_f32", "cbx_stats_pool_f32"):  # the scan itself: these are reached through their wrappers only
         assert e not in text and named(e)
+
+
+def test_the_per_request_number_checks_are_the_five_functions_they_replaced():
+    """ops.check_speed / check_pitch / check_loudness / check_true_peak / check_duration are calls of one helper; tests/golden/check_numbers.json holds what the five
+    separate functions returned or raised -- exception type and whole message -- over one list of inputs (tests/golden/make_golden_check_numbers.py wrote it from
+    them, before the change)."""
+    import json
+    from chatterbox_amd import ops
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_golden_check_numbers as G
+    finally:
+        sys.path.pop(0)
+    with open(os.path.join(ROOT, "tests", "golden", "check_numbers.json"), encoding="utf-8") as fh:
+        want = json.load(fh)
+    assert re.fullmatch(r"[0-9a-f]{7,40}", want.pop("_recorded_at_commit")), "the table names the commit whose functions it records"
+    assert sorted(want) == sorted(G.RANGES) and all(len(rows) >= 39 for rows in want.values())
+    for fn, rows in want.items():
+        kinds = {o.split(":")[0] for *_, o in rows}
+        assert {"TypeError", "ValueError", "None"} <= kinds and any(o.startswith("[") for *_, o in rows), fn
+        for expr, b, name, outcome in rows:
+            got = G.outcome(getattr(ops, fn), expr, b, **({} if name is None else dict(name=name)))
+            assert got == outcome, (fn, expr, b, name, got, outcome)
+
+
+def test_the_three_resamplers_share_one_design():
+    """the limiter's oversampler, the 1:4 resampler of the audio inputs and the table a 1:4 output format would take are the same bits, because they are one function"""
+    import numpy as np
+    from chatterbox_amd import ops
+    a, b, c = ops.true_peak_filter(), ops.resample_filter(1, 4), ops._poly_filter(4, 1)
+    assert a["tab"].dtype == b["tab"].dtype == c["tab"].dtype == np.float32 and a["tab"].shape == b["tab"].shape == c["tab"].shape == (4, 21)
+    assert a["tab"].tobytes() == b["tab"].tobytes() == c["tab"].tobytes() and a["h"].tobytes() == b["h"].tobytes() == c["h"].tobytes()
+    assert sorted(a) == ["T", "U", "h", "hl", "tab"] and sorted(b) == ["D", "T", "U", "h", "hl", "tab"] and sorted(ops.wave_filter(48000)) == sorted(c) == ["D", "H", "T", "U", "h", "hl", "tab"]
+    w = ops.wave_filter(48000)   # 24000 -> 48000 is 2:1: wave_filter itself goes through the same function
+    assert w["tab"].tobytes() == ops._poly_filter(2, 1)["tab"].tobytes() == ops.resample_filter(24000, 48000)["tab"].tobytes()
+    one = ops._poly_filter(3, 3)
+    assert (one["U"], one["D"], one["T"], one["hl"], one["H"]) == (1, 1, 1, 0, 0) and one["tab"].tolist() == [[1.0]] == ops.wave_filter(24000)["tab"].tolist()

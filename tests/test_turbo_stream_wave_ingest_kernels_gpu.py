@@ -73,3 +73,11 @@ def test_trim_edges_equal_the_host_rule_exactly(dev):
     with torch.cuda.device(dev):
         C.check_trim(ops, dev, sync=torch.cuda.synchronize)
         assert ops.wave_trim_edges([torch.zeros(3000, device=dev)], 0.0).cpu().tolist() == [[0, 0]]
+
+
+@pytest.mark.parametrize("lengths", C.TRIM_SEAMS, ids=lambda t: "-".join(map(str, t)))
+def test_trim_edges_at_the_block_seams(dev, lengths):
+    """rows of 0 .. 1025 samples on either side of the 480- and 512-sample block lengths, two of the three off the 16-byte grid: the host rule's edges"""
+    from chatterbox_amd import ops
+    with torch.cuda.device(dev):
+        C.check_trim_seams(ops, dev, lengths, sync=torch.cuda.synchronize)

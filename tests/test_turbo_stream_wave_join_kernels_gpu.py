@@ -29,6 +29,14 @@ def test_wave_join_equals_the_restatement_bitwise(dev, name, cfg):
         W.check_launch(ops, dev, name, cfg, sync=torch.cuda.synchronize)
 
 
+@pytest.mark.parametrize("lengths", W.SEAMS, ids=lambda t: "-".join(map(str, t)))
+def test_wave_edges_at_the_block_seams(dev, lengths):
+    """rows of 0 .. 1025 samples on either side of the 480- and 512-sample block lengths, two of the three off the 16-byte grid: the table is the restatement's"""
+    from chatterbox_amd import ops
+    with torch.cuda.device(dev):
+        W.check_seams(ops, dev, lengths, sync=torch.cuda.synchronize)
+
+
 def test_the_cases_the_shapes_are_chosen_for_are_what_they_claim():
     W.what_the_sets_cover()
 

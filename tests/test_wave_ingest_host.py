@@ -218,6 +218,12 @@ def test_trim_edges_on_the_emulator(emu):
     assert ops.wave_trim_edges([torch.zeros(3000)], 0.0).tolist() == [[0, 0]], "top_db = 0: no frame is above the loudest"
 
 
+@pytest.mark.parametrize("lengths", C.TRIM_SEAMS, ids=lambda t: "-".join(map(str, t)))
+def test_trim_edges_at_the_block_seams_on_the_emulator(emu, lengths):
+    from chatterbox_amd import ops
+    C.check_trim_seams(ops, CPU, lengths)
+
+
 # ----------------------------------------------------------------------------- the RIFF reader
 def _chunk(cid, body):
     return cid + struct.pack("<I", len(body)) + body + (b"\0" if len(body) & 1 else b"")

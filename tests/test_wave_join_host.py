@@ -121,6 +121,14 @@ def test_descriptor_errors_return_a_status_and_a_message():
     _descriptor_errors(_lib.lib)
 
 
+@pytest.mark.parametrize("case", W.ROW_REFUSALS)
+@pytest.mark.parametrize("entry", W.ROW_ENTRIES)
+def test_every_row_entry_refuses_bad_rows_under_its_own_name(entry, case):
+    """the product library on host buffers: the shared row check of wave_common.h carries the name of the entry that called it"""
+    from chatterbox_amd import _lib, ops
+    W.check_row_refusal(_lib.lib, ops, entry, case)
+
+
 # ----------------------------------------------------------------------------- the kernels on the SIMT emulator
 @pytest.fixture(scope="module")
 def emu():
@@ -136,6 +144,12 @@ def emu():
 def test_wave_join_on_the_emulator(emu, name, cfg):
     from chatterbox_amd import ops
     W.check_launch(ops, CPU, name, cfg)
+
+
+@pytest.mark.parametrize("lengths", W.SEAMS, ids=lambda t: "-".join(map(str, t)))
+def test_wave_edges_at_the_block_seams_on_the_emulator(emu, lengths):
+    from chatterbox_amd import ops
+    W.check_seams(ops, CPU, lengths)
 
 
 def test_the_cases_the_shapes_are_chosen_for_are_what_they_claim():

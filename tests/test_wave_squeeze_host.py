@@ -37,7 +37,8 @@ def test_entry_point_is_declared_exported_bound_and_documented():
                    "16 * R * ceil(max_r n_r / 480)", "out overlapping wav", "tts.py:272"):
         assert phrase in block, phrase
     src = open(os.path.join(ROOT, "chatterbox_amd", "csrc", "wave_squeeze.hip")).read()
-    assert "cbx_wave_frame_ms(" in src and "wave_frame_ms_kernel" not in src.replace("// ", ""), "the frame pass is wave_join.hip's kernel, not a copy"
+    assert "cbx_wave_frame_ms(" in src and "wave_frame_ms_kernel" not in src.replace("// ", "") and "wave_block_ms_kernel" not in src and "cbx_wave_block_pass" not in src, \
+        "the frame pass is wave_join.hip's instantiation, not one of its own"
     assert "asm" not in src and "__shfl" not in src and "cbx_xor_lane" in src
     assert ops.WAVE_SQUEEZE_TILE == S.TILE and f"WS_TILE = {S.TILE}" in src
 

@@ -289,6 +289,7 @@ def what_the_sets_cover():
 # ----------------------------------------------------------------------------- trim
 TRIM_DB = 20.0
 TRIM_CASES = ("bursts", "silent", "loud", "short")
+from wave_join_common import SEAMS as TRIM_SEAMS  # noqa: E402  (the lengths on either side of both block lengths of the shared block pass)
 
 
 def trim_case(kind):
@@ -337,6 +338,26 @@ def check_trim_rule(kind):
     else:
         assert (start, stop) == (0, len(y)), "silence throughout, noise throughout and less than a frame are kept whole (librosa's rule)"
     return y, (start, stop)
+
+
+def check_trim_seams(ops, dev, lengths, sync=lambda: None):
+    """cbx_wave_trim_edges_f32 on three rows of the lengths of one wave_join_common.SEAMS entry -- either side of the 480-sample frame of the join and of the
+    512-sample block here --, rows 1 and 2 off the 16-byte grid: blocks of loud and of faint noise (74 dB apart, every frame at least 0.01 dB from the
+    threshold), the edges are the host rule's exactly."""
+    import wave_join_common as J
+    from chatterbox_amd import frontend
+    rng = np.random.default_rng(sum(lengths))
+    rows = []
+    for r, n in enumerate(lengths):
+        amp = np.where((np.arange(n) // 512 + r) % 2 == 0, 0.5, 1e-4)
+        rows.append((amp * rng.uniform(-1.0, 1.0, n)).astype(np.float32))
+        assert n == 0 or trim_margin_db(rows[-1]) >= 0.01, (lengths, r)
+    want = [list(frontend.trim_edges_rule(y, TRIM_DB)) for y in rows]
+    got = ops.wave_trim_edges(J.seam_rows(rows, dev), TRIM_DB)
+    sync()
+    print(f"trim seams {lengths}: edges {got.cpu().tolist()}")
+    assert got.dtype == torch.int32 and got.cpu().tolist() == want, (lengths, got.cpu().tolist(), want)
+    return want
 
 
 def check_trim(ops, dev, sync=lambda: None):

@@ -137,8 +137,93 @@ def check_launch(ops, dev, name, cfg, sync=lambda: None, extra=7):
     return want_edges, total
 
 
+# Row lengths on either side of the two block lengths of the shared block pass (wave_common.h): the 480-sample frame here, the 512-sample block of the voice
+# trim (wave_ingest_common.check_trim_seams runs the same rows).  One call per triple; its first row is the one on the 16-byte grid (seam_rows), so it is not the empty one.
+SEAMS = [(479, 0, 1), (480, 481, 511), (512, 513, 1025)]
+
+
+def seam_rows(signals, dev):
+    """The rows of one call as views of ONE NaN-filled buffer: row r begins r floats behind a 16-byte boundary, so row 0 takes the block pass's 16-byte loads
+    and rows 1 and 2 its scalar loads, in the same launch."""
+    offs, pos = [], 0
+    for r, x in enumerate(signals):
+        pos = -(-pos // 4) * 4 + r
+        offs.append(pos)
+        pos += len(x) + 1
+    big = torch.full((pos + 4,), float("nan"))
+    for o, x in zip(offs, signals):
+        big[o: o + len(x)] = torch.from_numpy(x)
+    big = big.to(dev)
+    assert big.data_ptr() % 16 == 0 and [o % 4 for o in offs] == [0, 1, 2] and big.numel() < 4000
+    return [big[o: o + len(x)] for o, x in zip(offs, signals)]
+
+
+def check_seams(ops, dev, lengths, sync=lambda: None):
+    """cbx_wave_edges_f32 on three rows of the lengths of one SEAMS entry: frames of hum, speech and zeros, so that the last, partial frame of a row decides its
+    stop; the table equals the restatement's exactly, at both pads."""
+    rng = np.random.RandomState(sum(lengths))
+    rows = [make_row(n, "HSZ" if n > 2 * FRAME else "HS" if n % 2 else "SH", rng) for n in lengths]
+    views = seam_rows(rows, dev)
+    for pad in (0, 2):
+        want = [edges(r, 40.0, pad, check_margin=True) for r in rows]
+        got = ops.wave_edges(views, 40.0, pad_frames=pad)
+        sync()
+        print(f"seams {lengths} pad {pad}: edges {got.cpu().tolist()}")
+        assert got.dtype == torch.int32 and [tuple(e) for e in got.cpu().tolist()] == want, (lengths, pad, got.cpu().tolist(), want)
+    return want
+
+
+# The entries that take rows as (row_off, row_len, R) and check them with the one helper of wave_common.h, which is handed the entry's name.
+ROW_ENTRIES = ("cbx_wave_edges_f32", "cbx_wave_join_f32", "cbx_wave_squeeze_f32", "cbx_wave_pitch_f32", "cbx_wave_format_f32", "cbx_wave_loudness_f32",
+               "cbx_wave_loudness_push_f32", "cbx_wave_gain_f32", "cbx_wave_limit_f32", "cbx_wave_trim_edges_f32")
+ROW_REFUSALS = ("R0", "R65", "length", "offset")
+
+
+def check_row_refusal(lib, ops, entry, case):
+    """One bad row descriptor -- R = 0, R = 65, a negative length, a negative offset -- around otherwise good arguments of `entry`, all in host memory: -22, the
+    shared message under the ENTRY's name (the whole text: no other check fired first), and not a byte of any output written."""
+    import ctypes
+    who = entry[len("cbx_"):].replace("_f32", "")
+    N = 65
+    f32 = lambda v, n=4096: np.full(n, v, np.float32)
+    wav, out, gain, ramp, tail = f32(0.25, 2048), f32(7.0), f32(7.0, N), f32(1.0, 8), f32(7.0, 2 * N * 2400)
+    ints, stats, ws, rec = np.full(1024, 7, np.int32), np.full(1024, 7.0), np.full(4096, 7.0), np.full(N * 64, 7.0)
+    zeros, lens8, steps, nans = np.zeros(N, np.int32), np.full(N, 8, np.int32), np.ones(N), np.full(N, np.nan)
+    long0, out_off = np.zeros(N, np.int64), 16 * np.arange(N, dtype=np.int64)
+    off, n, R = np.array([0, 960] + [0] * (N - 2), np.int64), np.array([960, 960] + [0] * (N - 2), np.int32), 2
+    if case == "R0":
+        R, text = 0, f"{who}: R = 0 outside [1, 64]"
+    elif case == "R65":
+        R, text = 65, f"{who}: R = 65 outside [1, 64]"
+    elif case == "length":
+        n[1], text = -1, f"{who}: row 1 has length -1 at offset 960"
+    else:
+        off[1], text = -4, f"{who}: row 1 has length 960 at offset -4"
+    p = lambda a: a.ctypes.data
+    pf, tp, lf = ops.pitch_filter(), ops.true_peak_filter(), ops.loudness_filter()
+    win, coef = ops.limit_window(ops.LIMIT_LOOK), np.ascontiguousarray(lf["coef"])
+    rows = (p(wav), p(off), p(n))
+    args = {
+        "cbx_wave_edges_f32": (*rows, R, 1e-4, 2, p(ints), p(ws), ws.size, None),
+        "cbx_wave_join_f32": (*rows, p(zeros), R, p(ints), p(ramp), 8, 1, 1, p(out), out.size, p(ints) + 2048, None),
+        "cbx_wave_squeeze_f32": (*rows, p(zeros), R, 1e-4, p(ramp), 8, p(out), out.size, None, p(ints), p(ws), 8 * ws.size, None),
+        "cbx_wave_pitch_f32": (*rows, p(steps), p(lens8), R, p(pf["tab"]), pf["Z"], pf["L"], p(out), p(out_off), out.size, None),
+        "cbx_wave_format_f32": (*rows, R, 24000, 0, None, 1, 1, None, None, None, None, None, p(out), p(long0), out.size, None),
+        "cbx_wave_loudness_f32": (*rows, R, p(coef), lf["hop"], p(nans), 1.0, p(stats), p(gain), p(ws), ws.size, None),
+        "cbx_wave_loudness_push_f32": (*rows, p(long0), R, p(coef), lf["hop"], p(nans), 1.0, p(rec), 56, p(tail), p(tail) + 4 * N * 2400, p(stats), p(gain), p(ws),
+                                       ws.size, None),
+        "cbx_wave_gain_f32": (*rows, R, p(gain), None),
+        "cbx_wave_limit_f32": (*rows, R, None, p(nans), p(tp["tab"]), tp["U"], tp["T"], p(win), ops.LIMIT_LOOK, p(out), p(long0), out.size, p(stats), p(ws), ws.size, None),
+        "cbx_wave_trim_edges_f32": (*rows, R, 0.01, p(ints), p(ws), ws.size, None),
+    }[entry]
+    rc = getattr(lib, entry)(*args)
+    assert rc == -22 and lib.cbx_last_error().decode() == text, (entry, case, rc, lib.cbx_last_error())
+    assert all(bool((a == 7).all()) for a in (out, gain, tail, ints, stats, ws, rec)) and bool((wav == 0.25).all()), f"{entry}, {case}: a refusal writes nothing"
+
+
 def what_the_sets_cover():
     """Host arithmetic on the restatement: the inputs are what the shapes were chosen for."""
+    assert {n // FRAME for t in SEAMS for n in t} == {0, 1, 2} and {n % FRAME for t in SEAMS for n in t} >= {0, 1, 479} and {n % 512 for t in SEAMS for n in t} >= {0, 1, 511}
     rng = np.random.RandomState(0)
     a = [make_row(n, p, rng) for n, p in SETS["A"]]
     assert edges(a[0], 40.0, 0) == (960, 1920) and edges(a[0], 40.0, 2) == (0, 2879) and edges(a[1], 40.0, 2) == (0, 0) and edges(a[2], 40.0, 2) == (0, 0)
