@@ -301,6 +301,7 @@ _SIGS = {
     "cbx_wave_loudness_push_f32": ([c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_f, ctypes.c_double, c_f, c_long, c_f, c_f, c_f, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_gain_f32": ([c_f, c_f, c_f, c_int, c_f, c_f], c_int),
     "cbx_wave_limit_f32": ([c_f, c_f, c_f, c_int, c_f, c_f, c_f, c_int, c_int, c_f, c_int, c_f, c_f, c_long, c_f, c_f, c_long, c_f], c_int),
+    "cbx_wave_mix_f32": ([c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_f, c_f, c_int, c_f, c_long, c_int, c_f], c_int),
     "cbx_wave_ingest": ([c_f, c_f, c_f, c_int, c_int, c_int, c_f, c_int, c_int, c_int, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_trim_edges_f32": ([c_f, c_f, c_f, c_int, ctypes.c_double, c_f, c_f, c_long, c_f], c_int),
     "cbx_hift_stft_f32": ([c_f, c_f, c_f, c_int, c_long, c_long, c_f], c_int),

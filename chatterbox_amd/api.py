@@ -527,6 +527,127 @@ def long_stream_plan(chunks, max_batch, a, first_batch=1, batch_growth=2.0):
     return _long_jobs(chunks, max_batch, a, sizes())
 
 
+# ---------------------------------------------------------------------------------------------------------------- generate_dialogue: host-side plumbing
+DIALOGUE_TURN_PAUSE = 0.3   # seconds between two turns: an UNMEASURED default -- nobody has tuned it on trained weights
+DIALOGUE_BALANCE = -23.0    # balance=True: the LUFS level every voice is brought to (EBU R 128's programme level): an UNMEASURED default
+DIALOGUE_GAP = 60.0         # |gap| and |turn_pause| of a turn, seconds
+DIALOGUE_TURN_KEYS = ("voice", "text", "gap", "speed", "pitch", "exaggeration")
+DIALOGUE_MAX_VOICES = ops.WAVE_JOIN_MAX_ROWS   # the meter of balance= takes one row per voice
+
+
+def _dialogue_gap(v, name):
+    import numbers
+    if not isinstance(v, numbers.Real) or isinstance(v, bool):
+        raise TypeError(f"{name}: expected a number of seconds, got {type(v).__name__}")
+    if not math.isfinite(v) or not -DIALOGUE_GAP <= v <= DIALOGUE_GAP:
+        raise ValueError(f"{name} = {v}: expected a finite number of seconds in [-{DIALOGUE_GAP:g}, {DIALOGUE_GAP:g}] (negative: the turn starts that long before "
+                         "the front of the conversation)")
+    return float(v)
+
+
+def _dialogue_balance(balance):
+    """balance= of generate_dialogue -> None, or the LUFS level every voice is brought to (True: DIALOGUE_BALANCE)"""
+    if balance is None or balance is False:
+        return None
+    if balance is True:
+        return DIALOGUE_BALANCE
+    if isinstance(balance, (list, tuple)):
+        raise TypeError(f"balance: expected None, True or a number of LUFS, got a {type(balance).__name__}")
+    return ops.check_loudness(balance, 1, "balance")[0]
+
+
+def _dialogue_turns(turns, voices, turn_pause, exaggeration, language_id=None, multilingual=False):
+    """generate_dialogue's script, validated when the method is CALLED (TypeError: wrong types, unknown dict keys, a bool where a number belongs, `turns` not a
+    list; ValueError: values out of range or not finite, an unknown voice key, empty text) -> one dict(voice, text, gap, speed, pitch, exaggeration, language_id)
+    per turn: speed a float (1.0: none), pitch a float (0.0: none), language_id lower case or None."""
+    if not isinstance(turns, list):
+        raise TypeError(f"turns: expected a list of (voice, text) pairs or dicts, got {type(turns).__name__}")
+    if not turns:
+        raise ValueError("turns: expected at least one turn")
+    if voices is not None and not isinstance(voices, dict):
+        raise TypeError(f"voices: expected None or a dict of voice key -> Conditionals / voice prompt, got {type(voices).__name__}")
+    turn_pause = _dialogue_gap(turn_pause, "turn_pause")
+    keys = DIALOGUE_TURN_KEYS + (("language_id",) if multilingual else ())
+    out = []
+    for t, turn in enumerate(turns):
+        name = f"turns[{t}]"
+        if isinstance(turn, dict):
+            extra = set(turn) - set(keys)
+            if extra or "text" not in turn:
+                raise TypeError(f"{name}: keys {sorted(map(str, turn))}: `text` is required, the others are {[k for k in keys if k != 'text']}")
+            turn = dict(turn)
+        elif isinstance(turn, (tuple, list)) and len(turn) == 2:
+            turn = dict(voice=turn[0], text=turn[1])
+        else:
+            raise TypeError(f"{name}: expected a (voice, text) pair or a dict with {keys}, got {type(turn).__name__}")
+        voice, text = turn.get("voice"), turn["text"]
+        if not isinstance(text, str):
+            raise TypeError(f"{name}: text: expected a str, got {type(text).__name__}")
+        if not text.strip():
+            raise ValueError(f"{name}: text is empty")
+        if voice is not None:
+            try:
+                known = voices is not None and voice in voices
+            except TypeError:
+                raise TypeError(f"{name}: voice: expected None or a key of `voices`, got {type(voice).__name__}") from None
+            if not known:
+                raise ValueError(f"{name}: voice {voice!r} is not a key of `voices` ({sorted(map(repr, voices or {}))})")
+        gap = turn_pause if turn.get("gap") is None else _dialogue_gap(turn["gap"], f"{name}: gap")
+        for key in ("speed", "pitch"):
+            if isinstance(turn.get(key), (list, tuple)):
+                raise TypeError(f"{name}: {key}: expected None or a number, got a {type(turn[key]).__name__}")
+        speed, pitch = ops.check_speed(turn.get("speed"), 1, f"{name}: speed"), ops.check_pitch(turn.get("pitch"), 1, f"{name}: pitch")
+        try:
+            ops.check_speed_pitch(speed, pitch, 1)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        ex = exaggeration if turn.get("exaggeration") is None else turn["exaggeration"]
+        _long_numbers(**{f"{name}: exaggeration": ex})
+        lid = language_id
+        if multilingual and turn.get("language_id") is not None:
+            if not isinstance(turn["language_id"], str):
+                raise TypeError(f"{name}: language_id: expected a str, got {type(turn['language_id']).__name__}")
+            lid = _language(turn["language_id"], f" (turn {t})")
+        out.append(dict(voice=voice, text=text, gap=gap, speed=1.0 if speed is None else speed[0], pitch=0.0 if pitch is None else pitch[0], exaggeration=ex,
+                        language_id=lid))
+    return out
+
+
+def dialogue_plan(turns, max_batch, a):
+    """The rows and jobs of a generate_dialogue call, WITHOUT their tokens and voices.  turns: one dict(chunks=split_text's list of the turn's text, gap=seconds
+    before the turn, speed=, pitch=) per turn (speed / pitch may be missing: 1.0 / 0.0); a: _long_args' dict.  The rows are the chunks in script order; chunk k,
+    counted over the whole script, is seeded with chunk_seed(seed, k).  Returns dict(rows, jobs):
+    rows[k] = dict(turn, text, after): `after` is ops.mix_layout's signed count of samples behind the row -- round(pause * 24000 / speed) behind an inner chunk
+      of a turn (paragraph_pause behind a paragraph's last chunk; the turn's speed, as long_plan computes it), round(gap * 24000) of the NEXT turn behind a
+      turn's last chunk (not scaled by speed; negative: an overlap), 0 behind the last row of all;
+    jobs: the rows cut into consecutive device batches of at most max_batch (and at most 64), no length sort, as long_plan cuts them; per job dict(chunks=[row
+      indices], join=the engines' join dict, seeds=[...] if seeded, speed=[...] if any row of the SCRIPT is scaled, pitch=[...] if a row of the job is
+      transposed).  The join has zero gaps and no fade, first = last = True: a job's piece is its trimmed rows back to back, and the mixer places and fades them."""
+    rows = []
+    for t, turn in enumerate(turns):
+        rate = float(turn.get("speed") or 1.0)
+        for c, (text, para_end) in enumerate(turn["chunks"]):
+            if c + 1 < len(turn["chunks"]):
+                after = int(round((a["paragraph_pause"] if para_end else a["pause"]) * S3GEN_SR / rate))
+            else:
+                after = int(round(turns[t + 1]["gap"] * S3GEN_SR)) if t + 1 < len(turns) else 0
+            rows.append(dict(turn=t, text=text, after=after, speed=rate, pitch=float(turn.get("pitch") or 0.0)))
+    step = max(1, min(int(max_batch), ops.WAVE_JOIN_MAX_ROWS))
+    scaled = any(r["speed"] != 1.0 for r in rows)
+    jobs = []
+    for lo in range(0, len(rows), step):
+        idx = list(range(lo, min(lo + step, len(rows))))
+        job = dict(chunks=idx, join=dict(gaps=[0] * len(idx), trim_db=a["trim_db"], pad_frames=a["trim_pad"], fade=0, first=True, last=True))
+        if a["seed"] is not None:
+            job["seeds"] = [chunk_seed(a["seed"], k) for k in idx]
+        if scaled:
+            job["speed"] = [rows[k]["speed"] for k in idx]
+        if any(rows[k]["pitch"] for k in idx):
+            job["pitch"] = [rows[k]["pitch"] for k in idx]
+        jobs.append(job)
+    return dict(rows=[dict(turn=r["turn"], text=r["text"], after=r["after"]) for r in rows], jobs=jobs)
+
+
 # T3 cond dicts of a voice, kept while its T3Cond lives (generate_batch): id(T3Cond) -> [emotion tensor the entry was built from, its value, {exaggeration: dict}]
 _T3_DICTS = {}
 
@@ -1016,6 +1137,128 @@ class _TTS(_Finish):
                 seg.update(start=ops.formatted_len(seg["start"], fmt["sample_rate"]), stop=ops.formatted_len(seg["stop"], fmt["sample_rate"]))
         return (wav, segments) if return_segments else wav
 
+    # ------------------------------------------------------------------------------------------------------------ dialogue
+    last_balance = None  # per voice of the last generate_dialogue(balance=) call, in order of first appearance: dict(voice, lufs, peak, gain, blocks); else None
+
+    def _generate_dialogue(self, turns, voices, turn_pause, balance, a, return_segments, samp, unsampled, opts, language_id=None, multilingual=False, **analyse_kw):
+        """generate_dialogue behind its signature, its _Options (format, loudness, true_peak, guard: the finish and the guard) and _long_args: the script's
+        validation, the voices (each distinct prompt analysed once; self.conds is never written), the chunks of every turn, dialogue_plan's jobs through _run_jobs,
+        then _mix_dialogue.  samp / unsampled: as _generate_long takes them, one number each."""
+        ts = _dialogue_turns(turns, voices, turn_pause, unsampled["exaggeration"], language_id, multilingual)
+        level = _dialogue_balance(balance)
+        _long_numbers(**unsampled, **samp)
+        keys = list(dict.fromkeys(t["voice"] for t in ts))  # the distinct voices in order of first appearance (None: the model's own)
+        if level is not None and len(keys) > DIALOGUE_MAX_VOICES:
+            raise ValueError(f"balance: {len(keys)} distinct voices, the meter takes at most {DIALOGUE_MAX_VOICES}")
+        assert self.conds is not None or None not in keys, _NO_VOICE
+        self._warn_ignored(*unsampled.values(), *(t["exaggeration"] for t in ts))
+        given = [None if k is None else voices[k] for k in keys]
+        prompts = [(g, unsampled["exaggeration"]) for g in given if g is not None and not isinstance(g, Conditionals)]
+        analysed = iter(_analysed_once(prompts, lambda wav, ex: self._analyse(wav, ex, **analyse_kw)))
+        conds = [self.conds if g is None else (g if isinstance(g, Conditionals) else next(analysed)) for g in given]
+        for t in ts:
+            t["chunks"] = split_text(t["text"], a["max_chars"])
+        plan = dialogue_plan(ts, int(self.max_batch or self.engine.t3.MAX_BATCH), a)
+        turn_of = [r["turn"] for r in plan["rows"]]
+        tokens = [self._engine_tokens(self._text_ids(r["text"], ts[r["turn"]]["language_id"])) for r in plan["rows"]]
+        row_voice = [keys.index(ts[t]["voice"]) for t in turn_of]
+        dicts = [_t3_dict(conds[v].t3, ts[t]["exaggeration"]) for v, t in zip(row_voice, turn_of)]
+        jobs = []
+        for p in plan["jobs"]:
+            idx = p["chunks"]
+            job = dict(text_tokens=_pick(tokens, idx), t3_conds=_one_or_list(_pick(dicts, idx)), gen_ref=_one_or_list([conds[row_voice[k]].gen for k in idx]), **samp,
+                       **{k: v for k, v in p.items() if k != "chunks"})
+            if opts.guard is not None:
+                job["guard"] = opts.guard
+            jobs.append(job)
+        pieces, recs, truncated, reports = [], [], [], []
+        for p, res in zip(plan["jobs"], self._run_jobs(jobs, self._synth_kw())):
+            piece = res[0]
+            pieces.append(piece["wav"].detach().float().cpu())
+            assert pieces[-1].numel() == piece["total"], "a joined piece and its layout record disagree"
+            recs.append(piece)
+            truncated += [bool(v) for v in piece["truncated"]]
+            if opts.guard is not None:
+                reports += list(self.engine.last_guard)
+        self._warn_truncated("generate_dialogue", truncated, a["max_chars"])
+        if opts.guard is not None:
+            self._take_guard(reports, "generate_dialogue")
+        wav, starts, kept = self._mix_dialogue(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts)
+        if not return_segments:
+            return wav
+        fl = (lambda v: v) if opts.fmt is None else (lambda v: ops.formatted_len(v, opts.fmt["sample_rate"]))
+        segments = []
+        for k, (r, (a0, b0)) in enumerate(zip(plan["rows"], kept)):
+            seg = dict(turn=r["turn"], voice=ts[r["turn"]]["voice"], text=r["text"], start=fl(starts[k]), stop=fl(starts[k] + b0 - a0), src_start=a0, src_stop=b0,
+                       truncated=truncated[k])
+            if opts.guard is not None:
+                seg["guard"] = reports[k]
+            segments.append(seg)
+        return wav, segments
+
+    def _mix_dialogue(self, pieces, recs, after, row_voice, keys, level, fade, opts):
+        """The finish of generate_dialogue, ONE visit to the device for the whole conversation: the jobs' pieces (host tensors: each the job's trimmed rows back to
+        back; recs: their records of offsets and edges) are uploaded into ONE allocation, ops.mix_layout over the kept lengths places the rows, the meter of
+        balance= reads every voice's rows packed back to back (torch.cat: copies, no arithmetic; ONE ops.wave_loudness over the V voices, ceiling 1.0 -> the (V,)
+        gain vector the rows index through gain_idx), ops.wave_mix sums the rows into `out` -- ONE launch for up to 64 rows, whatever pieces they came in; a longer
+        script in launches of 64, the first writing every sample and the others accumulating --, then loudness over the mix as ONE signal, true_peak, the watermark
+        on the host if a watermarker is loaded, the format, and the one copy to the host -- the order of _finish / _to_loudness.  (One launch per PIECE would also
+        be the definition's values, but an accumulating launch adds to the +0.0 its predecessor left: a row that begins with -0.0 samples -- the vocoder's do --
+        would differ from generate_long's bits in the sign of those zeros.  With one allocation a script of up to 64 chunks is one launch and has no such seam.)
+        Every row fades in and out over `fade` samples except the very first row's start and the very last row's end where nothing was trimmed there (the join's
+        first / last rule).  Returns (the (1, n) CPU tensor, the rows' starts in 24 kHz samples, their kept (src_start, src_stop))."""
+        kept = [e for rec in recs for e in rec["edges"]]
+        lengths = [b0 - a0 for a0, b0 in kept]
+        starts, total = ops.mix_layout(lengths, after)
+        flags = [3] * len(kept)
+        if kept[0][0] == 0:
+            flags[0] &= ~1
+        if kept[-1][1] == recs[-1]["n"][-1]:
+            flags[-1] &= ~2
+        fmt, loud, peak = opts.fmt, None if opts.loud is None else opts.loud[0], None if opts.peak is None else opts.peak[0]
+        self.last_balance = None
+        if total == 0:
+            return self._finish(torch.zeros(0), fmt, converted=False), starts, kept
+        dev, scope = self._device_scope()
+        with scope:
+            # the upload: every piece into its slice of ONE allocation, so that a launch may take rows of several pieces
+            cuts = [0]
+            for w in pieces:
+                cuts.append(cuts[-1] + int(w.numel()))
+            up = torch.empty(max(1, cuts[-1]), dtype=torch.float32, device=dev)
+            for g, w in enumerate(pieces):
+                up[cuts[g]: cuts[g + 1]].copy_(w)
+            flat = [up[cuts[g] + off: cuts[g] + off + (b0 - a0)] for g, rec in enumerate(recs) for off, (a0, b0) in zip(rec["offsets"], rec["edges"])]
+            gain = stats = None
+            if level is not None:
+                order = [k for v in range(len(keys)) for k in range(len(flat)) if row_voice[k] == v]
+                packed = torch.cat([flat[k] for k in order])
+                ends = [sum(lengths[k] for k in order if row_voice[k] < v) for v in range(len(keys) + 1)]
+                stats, gain = ops.wave_loudness([packed[ends[v]: ends[v + 1]] for v in range(len(keys))], [level] * len(keys), 1.0)
+            out = torch.empty(total, dtype=torch.float32, device=dev)
+            for lo in range(0, len(flat), ops.WAVE_JOIN_MAX_ROWS):
+                hi = min(lo + ops.WAVE_JOIN_MAX_ROWS, len(flat))
+                ops.wave_mix(flat[lo:hi], starts[lo:hi], flags[lo:hi], out, gain=gain, gain_idx=None if gain is None else row_voice[lo:hi], fade=fade, accumulate=lo > 0)
+            w = out
+            if peak is not None:
+                pre = None
+                if loud is not None:
+                    self.engine.last_loudness, pre = ops.wave_loudness([w], [float(loud)], None)
+                o, self.engine.last_limit = ops.wave_limit([w], [float(peak)], gain=pre)
+                w = o[0]
+            elif loud is not None:
+                self.engine.last_loudness = ops.wave_normalize([w], [float(loud)])
+            if self.watermarker is not None:
+                w = torch.from_numpy(self.watermarker.apply_watermark(w.cpu().numpy(), sample_rate=self.sr))
+                if fmt is not None:
+                    w = w.to(dev)
+            if fmt is not None:
+                w = ops.wave_format([w], fmt)[0]
+            w = w.cpu()
+            if stats is not None:
+                self.last_balance = [dict(voice=k, lufs=s[0], peak=s[1], gain=s[2], blocks=int(s[3])) for k, s in zip(keys, stats.cpu().tolist())]
+        return w.unsqueeze(0), starts, kept
+
     def _stream_long(self, chunks, plan, jobs, a, return_segments, opts):
         """generate_long_stream behind its validation, a generator: the jobs run through _run_jobs -- while the consumer holds piece k the throughput schedule has
         the T3 of pieces k + 1 and k + 2 in flight --, and every joined piece is finished and yielded as it leaves the device.  Per piece, in this order:
@@ -1239,6 +1482,39 @@ class ChatterboxTTS(_LlamaTTS):
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
 
+    def generate_dialogue(self, turns, voices=None, *, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None, pause=0.15,
+                          paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, repetition_penalty=1.2, min_p=0.05, top_p=1.0, exaggeration=0.5,
+                          cfg_weight=0.5, temperature=0.8, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None):
+        """A conversation: a script whose turns are spoken by different voices, delivered as ONE waveform.  The reference has no counterpart: it returns one
+        utterance of one voice.  turns: a non-empty list of (voice, text) pairs or dicts dict(voice=, text=, gap=, speed=, pitch=, exaggeration=); voice is a key
+        of `voices` or None (the model's current conds); `voices` maps a key to a Conditionals or to anything audio_prompt_path= takes (each distinct prompt is
+        analysed once per call; self.conds is never written).  gap: seconds before this turn, a finite number in [-60, 60], default turn_pause; a NEGATIVE gap
+        starts the turn that long before the front of the conversation -- the next speaker comes in before the last one has finished, a "mm-hm" lies over the
+        other voice (clipped at the start of the conversation; the first turn's gap is not used; not scaled by speed).  speed, pitch, exaggeration: generate()'s,
+        per turn, travelling with the turn's chunks as generate_batch's per-request values do.
+        Every turn's text is split as generate_long splits it (max_chars; pause / paragraph_pause between a turn's own chunks, divided by the turn's speed); the
+        chunks run in script order as device batches of mixed voices (no length sort), chunk k of the whole script seeded with chunk_seed(seed, k); each batch is
+        trimmed on the device (trim_db, trim_pad) and leaves it as one piece.  The finish is ONE more visit to the device: the pieces are uploaded, every chunk is
+        placed (ops.mix_layout), faded over join_fade samples and SUMMED into the conversation by cbx_wave_mix_f32 (ops.wave_mix: rows that overlap are added in
+        script order, bit for bit reproducible), then loudness (the mix as ONE signal), true_peak, the watermark, sample_rate / encoding: generate_long's, in its
+        order.  A one-voice script with non-negative gaps is generate_long's result bit for bit.
+        balance (None; True: -23 LUFS; or a number in [-50, -5]): two cloned voices seldom have the same level -- every voice's chunks, packed back to back, are
+        measured by ONE launch of the BS.1770-4 meter and each voice gets the one gain that brings it to that level (sample peak limited to 1.0; a voice shorter
+        than 0.4 s keeps gain 1, the meter's own rule), applied inside the mixer.  More than 64 distinct voices with balance is a ValueError.  model.last_balance
+        then holds dict(voice, lufs, peak, gain, blocks) per voice in order of first appearance (else None).
+        return_segments=True: also one dict per chunk with turn, voice, text, start, stop, src_start, src_stop, truncated (and guard with a guard): [start, stop)
+        in samples of the returned waveform (through the format's rate as generate_long maps them; overlapping chunks overlap in these numbers), [src_start,
+        src_stop) the kept part of the chunk's own waveform.  Truncated chunks get generate_long's single warning.
+        Everything is validated when the method is called, before the engine or the voice analysis is touched: TypeError for wrong types, unknown dict keys, a
+        bool where a number belongs and `turns` not a list; ValueError for out-of-range or non-finite values, an unknown voice key and empty text.
+        turn_pause = 0.3 s and balance=True -> -23 LUFS are UNMEASURED defaults: nobody has tuned them with trained weights.  Not taken:
+        streaming, word_times, max_pause, duration / timing, stereo or panning, a background bed or ducking; ChatterboxVC has no such method.
+        This is the contract of generate_dialogue of the three TTS classes; the others say only what differs."""
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, guard=guard)
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, 1.0, False)
+        samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
+
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                              max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
                              sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None, true_peak=None,
@@ -1370,6 +1646,19 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, lid, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
 
+    def generate_dialogue(self, turns, voices=None, *, language_id=None, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None,
+                          pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
+                          repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None):
+        """ChatterboxTTS.generate_dialogue with generate()'s language_id for the call and, as a further key of a turn's dict, per turn (default: the call's);
+        max_chars=None is 100 when the call's language is zh / ja / ko and 300 otherwise."""
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, guard=guard)
+        if language_id is not None and not isinstance(language_id, str):
+            raise TypeError(f"language_id: expected None or a str, got {type(language_id).__name__}")
+        lid = _language(language_id)
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, 1.0, lid in CJK_LANGUAGES)
+        samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
+        return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(exaggeration=exaggeration), opts, lid, True)
+
     def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                              top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                              return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None,
@@ -1496,6 +1785,18 @@ class ChatterboxTurboTTS(_TTS):
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), opts,
                                    norm_loudness=norm_loudness)
+
+    def generate_dialogue(self, turns, voices=None, *, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None, pause=0.15,
+                          paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, repetition_penalty=1.2, min_p=0.00, top_p=0.95, exaggeration=0.0,
+                          cfg_weight=0.0, temperature=0.8, top_k=1000, norm_loudness=True, seed=None, sample_rate=None, encoding=None, loudness=None,
+                          true_peak=None):
+        """ChatterboxTTS.generate_dialogue on the Turbo / Nano backbone (generate()'s sampling arguments; norm_loudness: prepare_conditionals', for the prompts in
+        `voices`; the batches run one after the other; no guard on this backbone)."""
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak)
+        a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, 1.0, False)
+        samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
+        return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
+                                       opts, norm_loudness=norm_loudness)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                              top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None,

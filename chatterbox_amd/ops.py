@@ -1474,6 +1474,66 @@ def piece_on_host(out, rec, n, fmt=None):
     return piece if fmt is None else dict(piece, wav=out[: formatted_len(rec[R], fmt["sample_rate"])], format=fmt)
 
 
+# ----------------------------------------------------------------------------- dialogue: sum rows into one waveform, each at its own position (wave_mix.hip)
+WAVE_MIX_TILE = 4096             # output samples of one workgroup of cbx_wave_mix_f32 (WM_TILE)
+
+
+def mix_layout(lengths, after):
+    """Where the rows of a conversation start: (starts, total) as host ints.  after[r]: the signed count of samples between the front of the conversation (the
+    furthest end of any row so far) and the next non-empty row; negative: the next row comes in that many samples before the front.  The walk, with front = 0 and
+    pending = 0: an empty row gets start = front and changes nothing (the join drops an empty row's gap); otherwise start_r = max(0, front + pending),
+    front = max(front, start_r + n_r), pending = after[r].  total = front.  With every after >= 0 this is cbx_wave_join_f32's layout with last=True."""
+    lengths, after = [int(n) for n in lengths], [int(g) for g in after]
+    if len(lengths) != len(after):
+        raise ValueError(f"mix_layout: {len(after)} entries of `after` for {len(lengths)} rows")
+    if any(n < 0 for n in lengths):
+        raise ValueError(f"mix_layout: negative length in {lengths}")
+    starts, front, pending = [], 0, 0
+    for n, g in zip(lengths, after):
+        if n == 0:
+            starts.append(front)
+            continue
+        start = max(0, front + pending)
+        starts.append(start)
+        front, pending = max(front, start + n), g
+    return starts, front
+
+
+def wave_mix(rows, starts, flags, out, gain=None, gain_idx=None, fade=240, accumulate=False):
+    """cbx_wave_mix_f32 on the current stream: row r (_wave_rows: 1 .. 64 1-D fp32 views of ONE allocation) times its gain, with the join's fades, ADDED into
+    out[starts[r], starts[r] + n_r) -- rows that cover the same sample are summed in ascending r (include/cbx.h states the definition).  starts: R ints >= 0;
+    flags: R ints, bit 0 the row fades in, bit 1 it fades out, over min(fade, n_r / 2) samples of join_ramp(fade).  out: a contiguous 1-D fp32 tensor on the rows'
+    device, not the rows' allocation; every sample of it is written (+0.0 where no row is) unless accumulate, which adds to what it holds and leaves uncovered
+    samples alone.  gain: None (every row at 1, no multiply) or a (G,) fp32 device tensor; gain_idx: None (row r uses gain[r]) or R ints in [0, G).  One launch,
+    nothing is synchronised.  Returns out."""
+    rows = list(rows)
+    R = len(rows)
+    starts, flags = [int(s) for s in starts], [int(f) for f in flags]
+    if len(starts) != R or len(flags) != R:
+        raise ValueError(f"wave_mix: {len(starts)} starts and {len(flags)} flags for {R} rows")
+    if gain_idx is not None and len(gain_idx) != R:
+        raise ValueError(f"wave_mix: {len(gain_idx)} gain indices for {R} rows")
+    assert out.dim() == 1 and out.is_contiguous(), "wave_mix: out is a contiguous 1-D fp32 tensor on the rows' device"
+    _f32(out, "out")
+    if _all_empty(rows):  # (such rows may have no allocation to point at)
+        if not 1 <= R <= WAVE_JOIN_MAX_ROWS or any(not 0 <= s <= out.numel() for s in starts):
+            raise ValueError(f"wave_mix: {R} empty rows at {starts} of an output of {out.numel()}")
+        return out if accumulate else out.zero_()
+    base, offs, lens = _wave_rows(rows, "wave_mix")
+    dev = rows[0].device
+    assert out.device == dev, "wave_mix: out is a contiguous 1-D fp32 tensor on the rows' device"
+    G = 0
+    if gain is not None:
+        assert gain.dtype == torch.float32 and gain.dim() == 1 and gain.is_contiguous() and gain.device == dev, "wave_mix: gain is (G,) fp32 on the rows' device"
+        G = int(gain.numel())
+    st, fl = (ctypes.c_long * R)(*starts), (ctypes.c_int * R)(*flags)
+    gi = None if gain_idx is None else (ctypes.c_int * R)(*[int(g) for g in gain_idx])
+    check(lib.cbx_wave_mix_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(st), ctypes.addressof(fl), R, _p(gain), G,
+                               None if gi is None else ctypes.addressof(gi), _p(join_ramp(fade, dev)), int(fade), _p(out), out.numel(), int(bool(accumulate)), _stream()),
+          "cbx_wave_mix_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------- pitch control: the waveform read back at a real step (wave_pitch.hip)
 PITCH_MIN, PITCH_MAX = -12.0, 12.0               # semitones a caller may ask for
 PITCH_Z, PITCH_L, PITCH_BETA = 16, 256, 9.0      # zero crossings per side, table steps per crossing, Kaiser beta: UNMEASURED choices (DESIGN.md section 0)

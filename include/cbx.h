@@ -1141,6 +1141,38 @@ int cbx_wave_gain_f32(float* wav, const long* row_off, const int* row_len, int R
 int cbx_wave_limit_f32(const float* wav, const long* row_off, const int* row_len, int R, const float* gain, const double* ceiling, const float* tab, int U, int T,
                        const float* win, int H, float* out, const long* out_off, long out_cap, double* stats, double* ws, long ws_cap, void* stream);
 
+/* ---- dialogue: SUM the rows of a batch into one waveform, each at a position of its own (added after ABI v16 without a version step: new function only).  The
+ * reference has no counterpart: it returns one utterance of one voice (tts.py:272, mtl_tts.py:352, tts_turbo.py:320).  cbx_wave_join_f32 lays rows one after
+ * another; here two rows may sound at the same time -- the next speaker comes in before the last one has finished -- and every row has a gain.
+ * Rows as the other delivery entries take them: R in [1, 64] rows of row_len[r] >= 0 floats at wav + row_off[r]; row_off, row_len, start, flags and gain_idx are
+ * HOST arrays that travel to the kernel by value.  start[r] >= 0 is the output index of row r's first sample, start[r] + row_len[r] <= out_len.
+ * gain: G device floats, or NULL: every row at 1.  gain_idx[r] in [0, G): the gain row r uses (one per voice serves all of that voice's rows); NULL: r, G >= R.
+ * ramp: `fade` device floats, cbx_wave_join_f32's ramp[i] = (2 i + 1) / (2 fade); NULL only when fade == 0.  flags[r] bit 0: row r fades in over its first
+ * F_r = min(fade, n_r / 2) samples; bit 1: it fades out over its last F_r -- the rules of cbx_wave_join_f32.
+ * Definition, in fp32, for every p in [0, out_len), the rows that cover p (start_r <= p < start_r + n_r) taken in ASCENDING r -- the order of summation:
+ *   1. i = p - start_r; s_r = x_r[i] * g_r: one rounded multiply (no multiply at all when gain is NULL).
+ *   2. bit 0 set and i < F_r: s_r = s_r * ramp[i];
+ *   3. else bit 1 set and i >= n_r - F_r: s_r = s_r * ramp[n_r - 1 - i] (as in the join, the fade-in wins where the two meet).
+ *   4. acc = out[p] when `accumulate` is set, else the first covering row's s_r itself;
+ *   5. every further row: acc = acc + s_r, one rounded add each.  Products and sums are rounded separately: nothing is fused.
+ *   6. out[p] = acc.  A sample that no row covers is written as +0.0 when accumulate == 0 and is not written when accumulate == 1.
+ * Consequences: a sample covered by one row with a NULL gain holds exactly the bits cbx_wave_join_f32 would store.  Rows given in groups over several launches
+ * (the first with accumulate = 0, the others with 1) give the values of one launch over all of them; only the sign of a zero may differ, where the first launch
+ * covers nothing.  The result does not depend on the grid, the tile a sample falls into, or the alignment of wav, a row or out.  There are no atomics.  wav is
+ * only read, and out must not overlap it.  Nothing outside out[0, out_len) is written.
+ * Layout rule of a conversation (ops.mix_layout: the caller's, on the host): with front = pending = 0, an empty row gets start = front and changes nothing;
+ * otherwise start_r = max(0, front + pending), front = max(front, start_r + n_r), pending = after[r] (a signed count of samples; negative: an overlap);
+ * out_len = front.  With every after >= 0 this is cbx_wave_join_f32's layout with last = 1.
+ * One workgroup of 256 threads per tile of 4096 outputs (wave_mix.hip), counted from the 16-byte boundary at or below out: a uniform loop over the rows finds
+ * those that meet the tile, the sums are kept in registers in row order; 16-byte stores, 4-byte stores at the ragged ends; 16-byte loads where a row's source
+ * address allows, else 4-byte.  A tile that no row meets writes zeros when accumulate == 0 and returns when accumulate == 1.  One launch; none, rc 0, when
+ * out_len == 0.  Nothing synchronises the host.
+ * -22 before any launch, nothing written: a null wav / row_off / row_len / start / flags / out, R outside [1, 64], a negative length, offset or start,
+ * start + len > out_len, out_len < 0, fade < 0 or fade > 0 with ramp NULL, gain NULL with gain_idx given, G < 1 with gain given, an index outside [0, G), NULL
+ * gain_idx with G < R, flags outside 0 .. 3, accumulate outside {0, 1}, out overlapping a non-empty row. */
+int cbx_wave_mix_f32(const float* wav, const long* row_off, const int* row_len, const long* start, const int* flags, int R, const float* gain, int G,
+                     const int* gain_idx, const float* ramp, int fade, float* out, long out_len, int accumulate, void* stream);
+
 /* ---- audio in: decode, mix down and resample the raw sample bytes of voice prompts and conversion sources, and find the silence at their ends, on the device
  * (added after ABI v16 without a version step: new functions only).  The mirror image of cbx_wave_format_f32.  It replaces frontend.load_wav / resample /
  * trim_silence (NumPy / SciPy on the host), which restate librosa.load, librosa.resample and librosa.effects.trim of the reference (tts.py:184-187,
