@@ -170,7 +170,7 @@ class CfmStage(ctypes.Structure):  # cbx_cfm_stage_t
 
 
 class CfmSolve(ctypes.Structure):  # cbx_cfm_t
-    _fields_ = ([(k, c_int) for k in ("n_stages", "rows", "B", "n_steps", "cfg", "fused_qkv", "fused_ln")]
+    _fields_ = ([(k, c_int) for k in ("n_stages", "rows", "B", "n_steps", "cfg", "fused_qkv", "fused_ln", "b_split")]  # b_split: two chains, in T's alignment slot
                 + [("T", c_long), ("cfg_rate", c_float), ("dt", ctypes.POINTER(c_float)), ("stages", ctypes.POINTER(CfmStage)),
                    ("fin_c", PlanesRef), ("fin_proj", PlanesRef)]
                 + [(k, c_f) for k in ("fin_c_b", "fin_n_w", "fin_n_b", "fin_proj_b", "tbias", "lens", "xin")]
@@ -329,6 +329,8 @@ def _load():
         fn.restype = res
     if lib.cbx_abi_version() != ABI_VERSION:
         raise ImportError("libcbx_hip.so ABI version mismatch")
+    # (exported for tests/test_cfm_two_chains_*: calls of cbx_cfm_solve that forked.  Not part of include/cbx.h, hence not of _SIGS.)
+    lib.cbx_cfm_two_chain_solves.argtypes, lib.cbx_cfm_two_chain_solves.restype = [], c_long
     return lib
 
 

@@ -544,6 +544,11 @@ extern "C" int cbx_set_attn_planes_version(int v) {
     g_attn_pl_version = v;
     return 0;
 }
+// Does the AUTOMATIC choice (version 0) take the one-group kernel of version 1 for this launch?  (cbx_common.h: the only automatic choice that changes the bits --
+// versions 4 and 5 agree bit for bit, version 1 walks the keys in other tiles -- so a caller that splits a batch into row groups pins it for the parts.)
+bool cbx_attn_planes_short_seq(int Tq, int Tk, int n_heads, int nz1) {
+    return g_attn_pl_version == 0 && Tk <= 768 && (long)((Tq + 255) / 256) * n_heads * nz1 > 128;
+}
 
 extern "C" int cbx_flash_attn_planes_v(const void* q, const void* k, const void* vt, void* o, const int* key_lens, int nz1, int n_heads, int Tq,
                                        int Tk, long q_sb, long q_st, long q_lo, long k_sb, long k_st, long k_lo, long vt_sb, long vt_sd,
@@ -568,7 +573,7 @@ extern "C" int cbx_flash_attn_planes_v(const void* q, const void* k, const void*
     // automatic = version 4 (256 queries per workgroup, three stages); on small grids its 128-query twin (below); for SHORT key sequences on a filled chip the one-group
     // kernel of version 1 (128 queries, two workgroups per CU): the 9 - 12 KV tiles of T <= 768 do not amortise version 4's prologue and its last, part-filled query
     // tile -- 16 rows: T 530 59.3 -> 54.0 us, T 730 76.9 -> 72.4, T 1000 110.8 against 120.3 (profiles/r06_ag_plane_attention_short_sequences.log)
-    const bool short_seq = forced == 0 && Tk <= 768 && (long)((Tq + 255) / 256) * n_heads * nz1 > 128;
+    const bool short_seq = version == 0 && cbx_attn_planes_short_seq(Tq, Tk, n_heads, nz1);
     const int ver = forced ? forced : short_seq ? 1 : 4;
     const bool v2ok = !causal && k_st >= k_lo + 64 && (long)Tk * k_st * 2 < 0x7fffffffL && 64 * vt_sd * 2 < 0x7fffffffL && vt_sd >= vt_lo;
     if (ver >= 2 && v2ok) {

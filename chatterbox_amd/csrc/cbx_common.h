@@ -42,6 +42,7 @@ __device__ __forceinline__ void cbx_store_out4(float* p, f32x4 v) {
 }
 #define CBX_F16_LO_SCALE 2048.0f  /* scale of the second fp16 plane of the f16x3 forms (gemm_split.hip) */
 int* cbx_range_flag();            /* gemm_split.hip: device word of cbx_set_range_flag, or NULL */
+bool cbx_attn_planes_short_seq(int Tq, int Tk, int n_heads, int nz1); /* attention_planes.hip: the automatic version of this launch is the one-group kernel (1) */
 int cbx_wave_frame_ms(const char* who, const float* wav, const long* row_off, const int* row_len, int R, long nf, double* ws, void* stream); /* wave_join.hip: the 480-sample frame pass */
 #ifdef __HIPCC__
 // amax = max(amax, |v0..3|) in two instructions (fmaxf chains compile to one canonicalising v_max per operand)

@@ -4,7 +4,10 @@
 //   cbx_hift_decode -- HiFTGenerator.decode (models/s3gen/hifigan.py:412-444) between the STFT of the source and the iSTFT of conv_post.
 // Like cbx_t3_decode_step / cbx_t3_prefill they only SEQUENCE the kernel-level entry points of this library, with the arguments
 // chatterbox_amd/s3gen.py::FlowEngine.cfm / hift.py::HiFTEngine.decode pass one launch at a time (bit-identical results): caller-owned device memory,
-// no allocation, no synchronisation, one stream, hipGraph-capturable.
+// no allocation, no synchronisation, one stream, hipGraph-capturable.  (cbx_cfm_solve with cbx_cfm_t.b_split, outside a capture: the second half-batch
+// runs on a stream of the library's own between a fork and a join event; the caller's stream still orders everything.)
+#include <atomic>
+#include <mutex>
 #include "cbx_common.h"
 
 namespace {
@@ -134,6 +137,72 @@ struct CfmCtx {
     }
 };
 
+// Euler steps [k0, k1) of the batch `d` describes, on `stream`
+int cfm_step(const cbx_cfm_t& d, void* stream, int k0, int k1) {
+    CfmCtx c{&d, stream, d.rows, d.T, (long)d.rows * d.T};
+    for (int k = k0; k < k1; ++k) {
+        int rc;
+        // the packed estimator input [x | mu | spk | cond]: mu / spk / cond were split once by the caller, x after every Euler step
+        if (k && (rc = cbx_split_planes_f32(d.xin, d.xinP.p, c.M, 80, 320, d.xinP.ld, d.xinP.lo, stream))) return rc;
+        if ((rc = c.estimator(d.tbias + (long)k * d.n_stages * 256))) return rc;
+        if ((rc = cbx_cfm_euler_f32(d.xin, d.v, d.B, d.T, 80, 320, 80, d.T * 320, d.T * 80, d.dt[k], d.cfg_rate, d.cfg, stream))) return rc;
+    }
+    return 0;
+}
+
+// The half-batch of B utterances whose rows start at row r0 of `d`: the same descriptor over row slices of every operand and workspace (V^T: 512 rows per
+// row group); weights, tbias and the schedule are shared
+cbx_cfm_t cfm_half(const cbx_cfm_t& d, long r0, int B) {
+    cbx_cfm_t h = d;
+    const long m0 = r0 * d.T;
+    h.B = B, h.rows = d.cfg ? 2 * B : B, h.b_split = 0;
+    // every automatic form gives the bits of every other one (plane GEMM tiles, the 256- and 128-query attention), except the attention's one-group kernel for
+    // short sequences on a filled chip: where the whole batch takes it, its halves do
+    if (d.attn_version == 0 && cbx_attn_planes_short_seq((int)d.T, (int)d.T, 8, d.rows)) h.attn_version = 1;
+    if (h.lens) h.lens = d.lens + r0;
+    h.xin = d.xin + m0 * 320, h.ra = d.ra + m0 * 256, h.rb = d.rb + m0 * 256, h.x = d.x + m0 * 256, h.v = d.v + m0 * 80;
+    h.xinP = rows_from(d.xinP, m0), h.aP = rows_from(d.aP, m0), h.hP = rows_from(d.hP, m0), h.qkP = rows_from(d.qkP, m0), h.attP = rows_from(d.attP, m0);
+    h.ffP = rows_from(d.ffP, m0), h.xP = rows_from(d.xP, m0), h.yP = rows_from(d.yP, m0), h.catP = rows_from(d.catP, m0);
+    h.vtP = rows_from(d.vtP, r0 * 512);
+    return h;
+}
+
+std::atomic<long> g_two_chain_solves{0};
+
+#ifndef CBX_SIMT_EMU
+// The second chain's stream and the fork / join events: created once per (device, priority of the caller's stream) and kept for the life of the process
+struct CfmSide {
+    int dev, prio;
+    hipStream_t st;
+    hipEvent_t fork, join;
+    std::mutex busy;
+};
+int cfm_side(hipStream_t caller, CfmSide** out) {
+    static std::mutex table_lock;
+    static std::vector<CfmSide*> table;
+    int prio = 0;
+    hipError_t e = hipStreamGetPriority(caller, &prio);
+    if (e != hipSuccess) return cbx_set_error((int)e, "cfm_solve: hipStreamGetPriority: %s", hipGetErrorString(e));
+    const int dev = cbx_device();
+    std::lock_guard<std::mutex> lock(table_lock);
+    for (CfmSide* s : table)
+        if (s->dev == dev && s->prio == prio) return *out = s, 0;
+    CfmSide* s = new CfmSide();
+    s->dev = dev, s->prio = prio, s->st = nullptr, s->fork = s->join = nullptr;
+    const char* what = "hipStreamCreateWithPriority";
+    if ((e = hipStreamCreateWithPriority(&s->st, hipStreamNonBlocking, prio)) == hipSuccess) what = "hipEventCreateWithFlags", e = hipEventCreateWithFlags(&s->fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->join, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        if (s->fork) (void)hipEventDestroy(s->fork);
+        if (s->st) (void)hipStreamDestroy(s->st);
+        delete s;
+        return cbx_set_error((int)e, "cfm_solve: %s: %s", what, hipGetErrorString(e));
+    }
+    table.push_back(s);
+    return *out = s, 0;
+}
+#endif
+
 }  // namespace
 
 extern "C" int cbx_cfm_solve(const cbx_cfm_t* d, void* stream) {
@@ -146,16 +215,46 @@ extern "C" int cbx_cfm_solve(const cbx_cfm_t* d, void* stream) {
         CBX_REQUIRE(s.n_tb >= 1 && s.tb && s.cin % 32 == 0, "cfm_solve: stage %d needs transformer blocks and cin %% 32 == 0", k);
         CBX_REQUIRE((s.tail.p != nullptr) == (k == 0 || k == d->n_stages - 1), "cfm_solve: the down and the up stage (only) end in a conv");
     }
-    CfmCtx c{d, stream, d->rows, d->T, (long)d->rows * d->T};
-    for (int k = 0; k < d->n_steps; ++k) {
-        int rc;
-        // the packed estimator input [x | mu | spk | cond]: mu / spk / cond were split once by the caller, x after every Euler step
-        if (k && (rc = cbx_split_planes_f32(d->xin, d->xinP.p, c.M, 80, 320, d->xinP.ld, d->xinP.lo, stream))) return rc;
-        if ((rc = c.estimator(d->tbias + (long)k * d->n_stages * 256))) return rc;
-        if ((rc = cbx_cfm_euler_f32(d->xin, d->v, d->B, d->T, 80, 320, 80, d->T * 320, d->T * 80, d->dt[k], d->cfg_rate, d->cfg, stream))) return rc;
+    if (d->b_split == 0) return cfm_step(*d, stream, 0, d->n_steps);
+    // two chains (cbx_cfm_t.b_split): the half-batches share nothing but the weights and tbias for all n_steps
+    CBX_REQUIRE(d->b_split > 0 && d->b_split < d->B, "cfm_solve: b_split %d does not split %d utterances", d->b_split, d->B);
+    const int per = d->cfg ? 2 : 1;
+    const cbx_cfm_t h0 = cfm_half(*d, 0, d->b_split), h1 = cfm_half(*d, (long)per * d->b_split, d->B - d->b_split);
+    // (cbx_layernorm_f32 takes its narrow kernel from 64 rows on: a smaller half would not reproduce the whole batch's bits)
+    CBX_REQUIRE((long)h0.rows * d->T >= 64 && (long)h1.rows * d->T >= 64, "cfm_solve: each half-batch needs rows * T >= 64 of its own");
+    int rc = 0;
+#ifndef CBX_SIMT_EMU
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing((hipStream_t)stream, &cap);
+    if (e != hipSuccess) return cbx_set_error((int)e, "cfm_solve: hipStreamIsCapturing: %s", hipGetErrorString(e));
+    if (cap == hipStreamCaptureStatusNone) {
+        CfmSide* s = nullptr;
+        if ((rc = cfm_side((hipStream_t)stream, &s))) return rc;
+        std::lock_guard<std::mutex> lock(s->busy);  // one solve at a time between this side stream's fork and join
+        // the caller's co-resident attribute: the table is written only when the side stream's entry differs, and only under this lock
+        const int want = cbx_stream_coresident((hipStream_t)stream);
+        if (cbx_stream_coresident(s->st) != want && (rc = cbx_set_stream_coresident(s->st, want))) return rc;
+        const char* what = "hipEventRecord (fork)";
+        if ((e = hipEventRecord(s->fork, (hipStream_t)stream)) == hipSuccess) what = "hipStreamWaitEvent (fork)", e = hipStreamWaitEvent(s->st, s->fork, 0);
+        if (e != hipSuccess) return cbx_set_error((int)e, "cfm_solve: %s: %s", what, hipGetErrorString(e));
+        g_two_chain_solves.fetch_add(1);
+        // step by step, so that neither chain's launches wait in the host's queue behind all of the other's
+        for (int k = 0; !rc && k < d->n_steps; ++k)
+            if (!(rc = cfm_step(h0, stream, k, k + 1))) rc = cfm_step(h1, s->st, k, k + 1);
+        // the join is enqueued whatever the launches returned: the caller's stream orders everything the side stream was given
+        what = "hipEventRecord (join)";
+        if ((e = hipEventRecord(s->join, s->st)) == hipSuccess) what = "hipStreamWaitEvent (join)", e = hipStreamWaitEvent((hipStream_t)stream, s->join, 0);
+        if (!rc && e != hipSuccess) rc = cbx_set_error((int)e, "cfm_solve: %s: %s", what, hipGetErrorString(e));
+        return rc;
     }
-    return 0;
+#endif
+    // no fork inside a capture (the graph would have parallel branches) and none on the emulator: the halves one after the other on the caller's stream
+    if (!(rc = cfm_step(h0, stream, 0, d->n_steps))) rc = cfm_step(h1, stream, 0, d->n_steps);
+    return rc;
 }
+
+// Calls of cbx_cfm_solve that forked, for the tests of the fork / join: exported, but no entry point of include/cbx.h (it takes no descriptor and returns no status)
+extern "C" long cbx_cfm_two_chain_solves(void) { return g_two_chain_solves.load(); }
 
 // ------------------------------------------------------------------------------------------------------------------ HiFT decode
 namespace {

@@ -679,6 +679,9 @@ class ChatterboxEngine(S3GenEngine):
                                     "ban_from") if k in kw}
         job_kw = lambda job: dict(t3_kw, **{k: job[k] for k in ("temperature", "top_p", "min_p", "repetition_penalty", "cfg_weight", "guard") if k in job})
         self.co_resident(bool(co_resident))
+        # the CFM solve as two half-batch chains (FlowEngine.two_chain_schedule): measured in this form of the schedule only -- 320.3 -> 313.4 ms per batch,
+        # three alternating pairs (profiles/r09_cfm_two_chains_headline_ab.jsonl); alone the flow loses 2 % with it, so every other caller keeps one chain
+        self.flow.two_chain_schedule = bool(co_resident) and bool(host_threads)
         # ... and the flow + vocoder stream carries the co-resident ATTRIBUTE: its LayerNorm / split-GEMM launches (encoder, vocoder) keep to one or two
         # workgroups per CU as well (cbx_set_stream_coresident; no effect on results)
         from ._lib import check, lib
@@ -748,6 +751,7 @@ class ChatterboxEngine(S3GenEngine):
             finally:
                 torch.cuda.synchronize()
                 self.co_resident(False)
+                self.flow.two_chain_schedule = False
             return
 
         # ---- two host threads, two T3 states: the worker enqueues T3(k) into state k % 2 as soon as batch k - 2's tokens were collected, so the T3 stream
@@ -848,6 +852,7 @@ class ChatterboxEngine(S3GenEngine):
             ops.select_range_flag(self.dev, 0)
             torch.cuda.synchronize()
             self.co_resident(False)  # callers of vocode() / flow.inference() / synthesize_stream() get the fastest-alone forms back
+            self.flow.two_chain_schedule = False
 
     @torch.inference_mode()
     def synthesize_stream(self, text_tokens, t3_conds, gen_ref, *, first_chunk=25, chunk=50, chunk_growth=1.0, lookahead=3, fade=480, max_new_tokens=1000,

@@ -20,6 +20,34 @@ def _dev(t, dev):
     return t.float().contiguous().to(dev)
 
 
+# ---- row order of the CFM estimator's batch (cbx_cfm_t.b_split).  One chain: [cond 0..B) | uncond 0..B)] (no CFG: the B utterances).  Two chains: each
+# half-batch is contiguous, [cond h0 | uncond h0 | cond h1 | uncond h1], so that cbx_cfm_solve can run the halves as two independent solves over row slices.
+CFM_HALF_MIN_ROWS = 64  # rows * T a half-batch needs (cbx_cfm_solve): from 64 rows on LayerNorm takes the kernel it takes for the whole batch -- the same bits
+
+
+def cfm_halves(B, cfg, chains):
+    """The half-batches of a B-utterance solve as (first utterance, utterances, first row): two of ceil(B / 2) and floor(B / 2) utterances for chains = 2
+    and B >= 2, else the whole batch."""
+    per = 2 if cfg else 1
+    if chains != 2 or B < 2:
+        return [(0, B, 0)]
+    b0 = (B + 1) // 2
+    return [(0, b0, 0), (b0, B - b0, per * b0)]
+
+
+def cfm_row_order(B, cfg, chains):
+    """(utterance, is_uncond) of every estimator row, in row order."""
+    out = []
+    for u0, n, _ in cfm_halves(B, cfg, chains):
+        out += [(u0 + i, False) for i in range(n)] + ([(u0 + i, True) for i in range(n)] if cfg else [])
+    return out
+
+
+def cfm_result_rows(B, cfg, chains):
+    """The row that holds utterance b's mel after the solve (its cond row), for b in 0..B)."""
+    return [r0 + i for _, n, r0 in cfm_halves(B, cfg, chains) for i in range(n)]
+
+
 class FlowEngine:
     @ops.on_device
     def __init__(self, sd, device="cuda", meanflow=False, precision=None):
@@ -130,12 +158,26 @@ class FlowEngine:
         # launch geometry of the estimator's plane GEMMs / attention (cbx_gemm_pl_t.tile, cbx_flash_attn_planes_v: per call since ABI v13).  (0, 0) = the
         # library's measured defaults; co_resident(True) = the forms that leave half of every CU to another stream (engine.synthesize_pipelined)
         self.gemm_tile = self.attn_version = 0
+        # cfm_chains = 2: cbx_cfm_solve runs a batch of B >= 2 utterances as two independent half-batch solves, the second on a stream of the library's own
+        # (cbx_cfm_t.b_split; bit-identical mel).  1: one chain.  0 (default) = what was measured (profiles/r09_cfm_two_chains_*): two
+        # chains where the schedule asks for them (`two_chain_schedule`, set by engine.synthesize_pipelined alone: 320.3 -> 313.4 and 327.4 -> 320.4 ms per
+        # batch on two boxes, three alternating pairs each), one everywhere else -- the flow alone takes 176.5 ms with one chain and 180.3 with two.
+        # CBX_CFM_CHAINS (0, 1, 2) overrides.
+        self.cfm_chains = int(os.environ.get("CBX_CFM_CHAINS", "0"))
+        self.two_chain_schedule = False
+        self.chains()
 
     def co_resident(self, on):
         """The CFM estimator's kernels on their co-resident forms (one 8-wave / 4-wave workgroup per CU: profiles/r05_overlap_*) or back on the defaults.
         Same arithmetic, bit-identical mel."""
         from ._lib import ATTN_PL_CORESIDENT, PL_TILE_CORESIDENT
         self.gemm_tile, self.attn_version = (PL_TILE_CORESIDENT, ATTN_PL_CORESIDENT) if on else (0, 0)
+
+    def chains(self):
+        """The chains a cfm() call of two or more utterances runs as: cfm_chains, or for 0 two inside the schedule that set `two_chain_schedule`, else one."""
+        if self.cfm_chains not in (0, 1, 2):
+            raise ValueError(f"cfm_chains / CBX_CFM_CHAINS is 0 (automatic), 1 or 2, not {self.cfm_chains!r}")
+        return self.cfm_chains or (2 if self.two_chain_schedule else 1)
 
     # ------------------------------------------------------------------ conformer encoder
     def _rel_pos_table(self, T, dev=None, dm=512):
@@ -466,7 +508,7 @@ class FlowEngine:
             self._cfm_static = (d, stages, keep)
         return self._cfm_static[0]
 
-    def _cfm_solve_c(self, xin, xinP, lens_r, tb, t_span, ws, B, rows, T, n_steps, cfg, cfg_rate):
+    def _cfm_solve_c(self, xin, xinP, lens_r, tb, t_span, ws, B, rows, T, n_steps, cfg, cfg_rate, b_split=0):
         """solve_euler through cbx_cfm_solve: one ctypes call instead of ~4400 per utterance batch."""
         import ctypes
 
@@ -478,6 +520,7 @@ class FlowEngine:
         assert tb.is_contiguous() and tb.shape == (n_steps, len(self.stages), 256) and lens_r.dtype == torch.int32 and lens_r.numel() == rows
         d.rows, d.B, d.n_steps, d.cfg, d.fused_qkv, d.fused_ln, d.T = rows, B, n_steps, int(cfg), int(self.fused_qkv), int(self.fused_ln), T
         d.cfg_rate, d.dt = cfg_rate, dt
+        d.b_split = b_split  # > 0: the rows are laid out as two half-batches (cfm_halves) and solved as two chains
         d.gemm_tile, d.attn_version = int(self.gemm_tile), int(self.attn_version)
         d.tbias, d.lens, d.xin, d.xinP = ops._p(tb), ops._p(lens_r), ops._p(xin), ref(xinP)
         d.ra, d.rb, d.x, d.v = ops._p(ws["ra"]), ops._p(ws["rb"]), ops._p(ws["x"]), ops._p(ws["v"])
@@ -539,14 +582,25 @@ class FlowEngine:
                       cat=f(rows, T, 512),
                       h=f(rows * T, 256), qkv=f(rows * T, 1536), att=f(rows * T, 512), ff=f(rows * T, 1024), v=f(rows, T, 80),
                       stats=f(rows * T, 2))
+        # two chains (cfm_chains): only through the C seam, outside a capture (a fork would give the graph parallel branches), and where each half-batch is
+        # a plane-format solve of its own; anything else keeps today's row order and one chain
+        c_seam = planes and self.c_seam and not ops.TIMER
+        halves = cfm_halves(B, cfg, self.chains() if c_seam and not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()) else 1)
+        if min((2 if cfg else 1) * n * T for _, n, _ in halves) < CFM_HALF_MIN_ROWS:
+            halves = cfm_halves(B, cfg, 1)
         xin = torch.zeros(rows, T, 320, device=dev)
-        xin[:B, :, 0:80] = z
-        xin[:B, :, 80:160] = mu
-        xin[:B, :, 160:240] = spk[:, None, :]
-        xin[:B, :, 240:320] = cond
+        for u0, n, r0 in halves:  # [cond | uncond] of each half-batch: the uncond rows hold [x | 0 | 0 | 0]
+            u = slice(u0, u0 + n)
+            xin[r0:r0 + n, :, 0:80] = z[u]
+            xin[r0:r0 + n, :, 80:160] = mu[u]
+            xin[r0:r0 + n, :, 160:240] = spk[u, None, :]
+            xin[r0:r0 + n, :, 240:320] = cond[u]
+            if cfg:
+                xin[r0 + n:r0 + 2 * n, :, 0:80] = z[u]
         if cfg:
-            xin[B:, :, 0:80] = z
-        lens_r = torch.cat([lens, lens]).contiguous() if cfg else lens
+            lens_r = torch.cat([lens[u0:u0 + n] for u0, n, _ in halves for _ in range(2)]).contiguous()
+        else:
+            lens_r = lens
         t_span = torch.linspace(0, 1, n_steps + 1)
         if not self.meanflow:
             t_span = 1 - torch.cos(t_span * 0.5 * math.pi)
@@ -556,8 +610,10 @@ class FlowEngine:
         if planes:  # the packed estimator input in plane format: [mu | spk | cond] are split once, x after every Euler step
             xin2 = xin.view(rows * T, 320)
             xinP = ops.split_planes(xin2)
-        if planes and self.c_seam and not ops.TIMER:
-            self._cfm_solve_c(xin, xinP, lens_r, tb, t_span, ws, B, rows, T, n_steps, cfg, cfg_rate)
+        if c_seam:
+            self._cfm_solve_c(xin, xinP, lens_r, tb, t_span, ws, B, rows, T, n_steps, cfg, cfg_rate, b_split=halves[0][1] if len(halves) == 2 else 0)
+            if len(halves) == 2 and cfg:  # the cond rows of the two half-batches, back in utterance order
+                return torch.cat([xin[r0:r0 + n, :, :80] for _, n, r0 in halves])
             return xin[:B, :, :80]
         for k in range(n_steps):
             if planes:

@@ -683,6 +683,21 @@ typedef struct cbx_cfm_t {
     int n_stages, rows, B, n_steps, cfg, fused_qkv, fused_ln;    /* fused_ln (ABI v13; the slot of v12's fused_mlp): 1 = norm3 from the attention
                                                                   * out-projection's epilogue (cbx_gemm_pl_t.ln_w), 2 = also the next block's norm1
                                                                   * from ff2's; 0 = LayerNorm launches of their own */
+    int b_split;                          /* TWO CHAINS (in the alignment slot in front of T: size and every other offset unchanged, a zeroed descriptor is
+                                           * the one-chain call).  0 < b_split < B: the batch is two independent half-batches of b_split and B - b_split
+                                           * utterances, each CONTIGUOUS in the rows -- with CFG [cond h0 | uncond h0 | cond h1 | uncond h1], without
+                                           * [h0 | h1] -- and on return the mel of utterance b is row b (b < b_split) resp. row (cfg ? 2 : 1) * b_split +
+                                           * (b - b_split).  The first half is launched on `stream`, the second on a stream of the library's own (one per
+                                           * device and priority, the caller's priority and co-resident attribute) between ONE fork and ONE join event:
+                                           * after the call `stream` orders everything, as in the one-chain call.  Each half needs rows * T >= 64 of its
+                                           * own (below it a half's LayerNorm launches would take another kernel than the whole batch's).  While
+                                           * `stream` is capturing both halves are launched on it, one after the other (no fork: twice the launches of
+                                           * the one-chain call at half the rows; a caller that wants the one-chain launches in a capture passes 0).
+                                           * The side stream is shared by every caller stream of its device and priority: their second halves queue on
+                                           * it in call order, and the library holds a lock of its own from the fork to the join of a call (the whole
+                                           * enqueue, several thousand launches), so concurrent two-chain calls at one priority enqueue one after the
+                                           * other.  The field occupies bytes that were padding up to now: a descriptor MUST be zero-initialised
+                                           * (memset / `= {0}`) before it is filled. */
     long T;
     float cfg_rate;
     const float* dt;                      /* HOST [n_steps] */
