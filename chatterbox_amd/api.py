@@ -268,7 +268,7 @@ def _request_seeds(seed, B=1, one=True, generator=None):
 
 class _Options:
     """The delivery options of ONE public call for its B requests, built from the public arguments and validated when the method is CALLED, generators included --
-    in one order for every method: the format (sample_rate, encoding), word_times, seed / seeds (with the generator), speed, loudness, true_peak, max_pause / pause_db, pitch
+    in one order for every method: the format (sample_rate, encoding), word_times, seed / seeds (with the generator), speed, loudness, true_peak, bed, max_pause / pause_db, pitch
     with the speed x pitch rule (ops.check_speed_pitch), guard.  one=True: the method serves one request (generate, generate_long, ...): a sequence for
     loudness, true_peak, max_pause or pitch is then a TypeError.  segments=False (generate_long without return_segments): word_times is refused, its words travel in the
     segments.  Holds fmt (ops.check_format's dict), words (_word_times' mode), seeds, speed, loud, peak (ops.check_true_peak's dBTP ceilings), pitch (B entries each), pz (_pauses' dict), guard (the
@@ -279,7 +279,7 @@ class _Options:
     (_TTS._word_groups) and turns them into one start per text token (`starts`), which kw(idx) hands to the engine."""
 
     def __init__(self, model, B=1, one=True, *, seeds=None, generator=None, speed=None, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0,
-                 pitch=None, word_times=False, guard=None, segments=True, duration=None, timing=None, true_peak=None):
+                 pitch=None, word_times=False, guard=None, segments=True, duration=None, timing=None, true_peak=None, bed=None):
         self.model, self.one, self.generator = model, one, generator
         self.fmt = ops.check_format(sample_rate, encoding)
         self.words = None if word_times is None or word_times is False else model._word_mode(word_times, max_pause)
@@ -293,6 +293,7 @@ class _Options:
         if one and isinstance(true_peak, (list, tuple)):
             raise TypeError(f"true_peak: expected None or a number of dBTP, got a {type(true_peak).__name__}")
         self.peak = ops.check_true_peak(true_peak, B)
+        self.bed = ops.check_bed(bed)  # (generate_dialogue / generate_long: the plan of the music bed, or None; it never travels in a job)
         self.pz = _pauses(max_pause, pause_db, B, one)
         if one and isinstance(pitch, (list, tuple)):
             raise TypeError(f"pitch: expected None or a number of semitones, got a {type(pitch).__name__}")
@@ -743,6 +744,14 @@ def _no_true_peak(method, true_peak):
                         "generate_long(true_peak=...)")
 
 
+def _no_bed(method, bed):
+    """generate_long_stream lists bed only because its signature is generate_long's plus the ramp; anything but None is refused as an argument the method does
+    not take"""
+    if bed is not None:
+        raise TypeError(f"{method}() does not take bed: ducking looks ahead of every word over the WHOLE signal, and a running form carried from piece to piece "
+                        "is not built -- use generate_long(bed=...)")
+
+
 def _no_word_times(method, word_times):
     """generate_long_stream lists word_times only because its signature is generate_long's plus the ramp; anything but False / None is refused as an argument the
     method does not take"""
@@ -754,6 +763,7 @@ def _no_word_times(method, word_times):
 class _Finish:
     """The epilogue of every public method that returns audio, and the `audio_in` switch of every method that takes audio."""
     sr = S3GEN_SR
+    last_bed = None  # of the last generate_dialogue / generate_long call: None, or with bed= dict(gain, speech_lufs, bed_lufs, ducked, frames, peak)
     last_fit = None  # per request of the last call with duration= / timing=, in the caller's order: None (a plain request) or the engine's fit report
 
     def _take_fit(self, reports, who):
@@ -780,17 +790,21 @@ class _Finish:
         else:
             self._audio_in = value
 
-    def _finish(self, wav, fmt=None, converted=True, loud=None, peak=None):
+    def _finish(self, wav, fmt=None, converted=True, loud=None, peak=None, bed=None):
         """A device waveform as the reference returns it: CPU float32 (1, n), watermarked if a watermarker is loaded.
         fmt (ops.check_format's dict; None: exactly the above): the (1, n) CPU tensor at fmt's rate in fmt's encoding.  Without a watermarker the engine was given the
         format and `wav` is the converted audio already (converted=True): one copy to the host.  With one -- or when the caller kept the format from the engine
         (converted=False: generate_long) -- `wav` is 24 kHz fp32: it is watermarked on the host as ever, then converted on the device (_to_format).
         loud (a LUFS target; generate_long): the 24 kHz waveform is normalised as ONE signal first (_to_loudness); the watermark follows the gain, the conversion
-        the watermark.  peak (a ceiling in dBTP; generate_long): the true-peak limiter follows that gain in the same visit to the device (_to_loudness)."""
+        the watermark.  peak (a ceiling in dBTP; generate_long): the true-peak limiter follows that gain in the same visit to the device (_to_loudness).
+        bed ((plan, source) of _bed_source; generate_long): the music bed is laid under the waveform in that same visit, ahead of the meter: level and ceiling
+        hold for speech plus bed."""
         if fmt is not None and converted and self.watermarker is None:
             return wav.detach().cpu().unsqueeze(0)
         wav = wav.detach().float().cpu()
-        if peak is not None:
+        if bed is not None:
+            wav = self._to_loudness(wav, loud, peak, bed)
+        elif peak is not None:
             wav = self._to_loudness(wav, loud, peak)
         elif loud is not None:
             wav = self._to_loudness(wav, loud)
@@ -808,19 +822,70 @@ class _Finish:
         with scope:
             return ops.wave_format([wav.to(dev)], fmt)[0].cpu()
 
-    def _to_loudness(self, wav, target, peak=None):
+    def _bed_source(self, plan):
+        """The source of a music bed (plan: ops.check_bed's) at 24 kHz mono, brought there as a voice prompt is: a float32 host array (audio_in = "host":
+        _load_wave) or a 1-D fp32 device tensor (audio_in = "device": PromptAnalyzer.ingest, ops.wave_ingest).  Read when the method is called, before the engine
+        runs.  ValueError naming `bed` for an empty source and for one that cannot loop (no longer than twice the cross-fade)."""
+        import numpy as np
+        if self.audio_in == "device":
+            from types import SimpleNamespace
+            from .frontend import PromptAnalyzer
+            # (ingest reads its analyzer's device alone: a model built without the prompt networks lends it the engine's)
+            who = self.analyzer if self.analyzer is not None else SimpleNamespace(dev=torch.device(self.engine.dev), raw_form=PromptAnalyzer.raw_form)
+            src = PromptAnalyzer.ingest(who, [plan["audio"]], S3GEN_SR)[0]
+            nb = int(src.numel())
+        else:
+            src = np.ascontiguousarray(_load_wave(plan["audio"], S3GEN_SR), dtype=np.float32).reshape(-1)
+            nb = int(src.size)
+        if nb == 0:
+            raise ValueError("bed: the audio is empty")
+        if plan["loop"] and nb <= 2 * plan["xf"]:
+            raise ValueError(f"bed: a source of {nb} samples at 24 kHz cannot loop with a cross-fade of {plan['xf']} samples (loop_fade): it must be longer than twice that")
+        return src
+
+    def _lay_bed(self, w, plan, src):
+        """The bed step on the device, inside the caller's scope and visit: w (1-D fp32, the finished speech) -> speech over the ducked bed (ops.bed_len(n, plan)
+        samples).  Two measure-only ops.wave_loudness calls -- the speech as it is, the bed over its whole source -- feed ops.wave_duck_level, whose gain
+        ops.wave_duck applies.  Nothing is synchronised: the numbers of model.last_bed wait on the device (_take_bed)."""
+        b = src if torch.is_tensor(src) else torch.from_numpy(src).to(w.device)
+        silent = lambda: torch.tensor([[float("-inf"), 0.0, 1.0, 0.0]], dtype=torch.float64).to(w.device)
+        ss = ops.wave_loudness([w], None, None)[0] if w.numel() else silent()
+        sb = ops.wave_loudness([b], None, None)[0]
+        out, st = ops.wave_duck([w], [b], plan, gain=ops.wave_duck_level(ss, sb, plan["level"]))
+        self._bed_numbers = torch.cat([st.reshape(-1), ss[0, :1], sb[0, :1]])
+        return out[0]
+
+    def _take_bed(self):
+        """model.last_bed from the six numbers _lay_bed left on the device: one small copy beside the audio's"""
+        g, ducked, frames, peak, ls, lb = self._bed_numbers.cpu().tolist()
+        self._bed_numbers = None
+        self.last_bed = dict(gain=g, speech_lufs=ls, bed_lufs=lb, ducked=int(ducked), frames=int(frames), peak=peak)
+
+    def _to_loudness(self, wav, target, peak=None, bed=None):
         """A 24 kHz fp32 waveform on the host -> the device, ops.wave_normalize to `target` LUFS (sample peak limited to 1.0), back to the host (1-D); the stats stay
         on the device as engine.last_loudness.  peak (dBTP): one upload, the meter with the FULL gain to the target (none when target is None), ops.wave_limit
-        with that gain to the ceiling, one download; engine.last_limit keeps the limiter's stats."""
+        with that gain to the ceiling, one download; engine.last_limit keeps the limiter's stats.  bed ((plan, source)): _lay_bed first, on the same upload; the
+        meter and the limiter then see speech plus bed (neither a target nor a ceiling: the sum comes back as it is)."""
         dev, scope = self._device_scope()
         with scope:
             w = wav.to(dev).contiguous()
+            if bed is not None:
+                w = self._lay_bed(w, *bed)
+                if peak is None:
+                    if target is not None:
+                        self.engine.last_loudness = ops.wave_normalize([w], [float(target)])
+                    w = w.cpu()
+                    self._take_bed()
+                    return w
             if peak is not None:
                 gain = None
                 if target is not None:
                     self.engine.last_loudness, gain = ops.wave_loudness([w], [float(target)], None)
                 out, self.engine.last_limit = ops.wave_limit([w], [float(peak)], gain=gain)
-                return out[0].cpu()
+                res = out[0].cpu()
+                if bed is not None:
+                    self._take_bed()
+                return res
             self.engine.last_loudness = ops.wave_normalize([w], [float(target)])
             return w.cpu()
 
@@ -1068,6 +1133,9 @@ class _TTS(_Finish):
         if not isinstance(text, str):
             raise TypeError(f"text: expected a str, got {type(text).__name__}")
         _long_numbers(**unsampled, **samp)
+        if ramp is None:
+            self.last_bed = None
+            opts.bed_source = None if opts.bed is None else self._bed_source(opts.bed)  # (read ahead of the voice analysis: a bad source costs nothing)
         self._use_voice(audio_prompt_path, unsampled["exaggeration"], **prepare_kw)
         self._warn_ignored(*unsampled.values())
         tokenize = lambda chunk: self._engine_tokens(self._text_ids(chunk, language_id))
@@ -1110,9 +1178,11 @@ class _TTS(_Finish):
         _finish (host -> device -> host; no converter state travels through the joined pieces on the device), and the segments' start / stop become output samples,
         ceil(s U / D), so the last stop is the length; src_start / src_stop stay 24 kHz samples.  opts.loud (the LUFS target or None): the engine jobs do not carry it
         either -- the concatenated waveform is measured and gained as ONE signal in _finish, ahead of the watermark, so the chunks keep their relative level; opts.peak
-        (the dBTP ceiling or None) likewise: the whole is limited once, behind that gain."""
+        (the dBTP ceiling or None) likewise: the whole is limited once, behind that gain.  opts.bed (ops.check_bed's plan or None): its source was read before the
+        voice analysis (_generate_long: opts.bed_source), the bed is laid under the whole in _finish's visit ahead of the meter, and segments and words begin `lead` samples later."""
+        bed = None if opts.bed is None else (opts.bed, opts.bed_source)
         chunks, plan, jobs = self._long_work(text, a, tokenize, samp, opts)
-        fmt, pieces, segments, base = opts.fmt, [], [], 0
+        fmt, pieces, segments, base = opts.fmt, [], [], 0 if bed is None else opts.bed["lead"]  # (the speech begins `lead` samples into the result)
         fl = (lambda v: v) if fmt is None else (lambda v: ops.formatted_len(v, fmt["sample_rate"]))
         for p, job, res in zip(plan, jobs, self._run_jobs(jobs, self._synth_kw())):
             piece, st = res[0], res[1]
@@ -1131,7 +1201,7 @@ class _TTS(_Finish):
         self._warn_truncated("generate_long", [s["truncated"] for s in segments], a["max_chars"])
         if opts.guard is not None:
             self._take_guard([s["guard"] for s in segments], "generate_long")
-        wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=None if opts.loud is None else opts.loud[0], peak=None if opts.peak is None else opts.peak[0])
+        wav = self._finish(torch.cat(pieces), fmt, converted=False, loud=None if opts.loud is None else opts.loud[0], peak=None if opts.peak is None else opts.peak[0], bed=bed)
         if fmt is not None:
             for seg in segments:
                 seg.update(start=ops.formatted_len(seg["start"], fmt["sample_rate"]), stop=ops.formatted_len(seg["stop"], fmt["sample_rate"]))
@@ -1147,6 +1217,8 @@ class _TTS(_Finish):
         ts = _dialogue_turns(turns, voices, turn_pause, unsampled["exaggeration"], language_id, multilingual)
         level = _dialogue_balance(balance)
         _long_numbers(**unsampled, **samp)
+        self.last_bed = None
+        bed = None if opts.bed is None else (opts.bed, self._bed_source(opts.bed))
         keys = list(dict.fromkeys(t["voice"] for t in ts))  # the distinct voices in order of first appearance (None: the model's own)
         if level is not None and len(keys) > DIALOGUE_MAX_VOICES:
             raise ValueError(f"balance: {len(keys)} distinct voices, the meter takes at most {DIALOGUE_MAX_VOICES}")
@@ -1183,7 +1255,9 @@ class _TTS(_Finish):
         self._warn_truncated("generate_dialogue", truncated, a["max_chars"])
         if opts.guard is not None:
             self._take_guard(reports, "generate_dialogue")
-        wav, starts, kept = self._mix_dialogue(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts)
+        wav, starts, kept = self._mix_dialogue(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts, bed)
+        if bed is not None:  # the speech begins `lead` samples into the result
+            starts = [v + opts.bed["lead"] for v in starts]
         if not return_segments:
             return wav
         fl = (lambda v: v) if opts.fmt is None else (lambda v: ops.formatted_len(v, opts.fmt["sample_rate"]))
@@ -1196,12 +1270,13 @@ class _TTS(_Finish):
             segments.append(seg)
         return wav, segments
 
-    def _mix_dialogue(self, pieces, recs, after, row_voice, keys, level, fade, opts):
+    def _mix_dialogue(self, pieces, recs, after, row_voice, keys, level, fade, opts, bed=None):
         """The finish of generate_dialogue, ONE visit to the device for the whole conversation: the jobs' pieces (host tensors: each the job's trimmed rows back to
         back; recs: their records of offsets and edges) are uploaded into ONE allocation, ops.mix_layout over the kept lengths places the rows, the meter of
         balance= reads every voice's rows packed back to back (torch.cat: copies, no arithmetic; ONE ops.wave_loudness over the V voices, ceiling 1.0 -> the (V,)
         gain vector the rows index through gain_idx), ops.wave_mix sums the rows into `out` -- ONE launch for up to 64 rows, whatever pieces they came in; a longer
-        script in launches of 64, the first writing every sample and the others accumulating --, then loudness over the mix as ONE signal, true_peak, the watermark
+        script in launches of 64, the first writing every sample and the others accumulating --, then the music bed (bed: (plan, source) or None; _lay_bed: the
+        mix is measured before the bed, the bed over its whole source), then loudness over the result as ONE signal, true_peak, the watermark
         on the host if a watermarker is loaded, the format, and the one copy to the host -- the order of _finish / _to_loudness.  (One launch per PIECE would also
         be the definition's values, but an accumulating launch adds to the +0.0 its predecessor left: a row that begins with -0.0 samples -- the vocoder's do --
         would differ from generate_long's bits in the sign of those zeros.  With one allocation a script of up to 64 chunks is one launch and has no such seam.)
@@ -1217,7 +1292,7 @@ class _TTS(_Finish):
             flags[-1] &= ~2
         fmt, loud, peak = opts.fmt, None if opts.loud is None else opts.loud[0], None if opts.peak is None else opts.peak[0]
         self.last_balance = None
-        if total == 0:
+        if total == 0 and bed is None:
             return self._finish(torch.zeros(0), fmt, converted=False), starts, kept
         dev, scope = self._device_scope()
         with scope:
@@ -1238,8 +1313,9 @@ class _TTS(_Finish):
             out = torch.empty(total, dtype=torch.float32, device=dev)
             for lo in range(0, len(flat), ops.WAVE_JOIN_MAX_ROWS):
                 hi = min(lo + ops.WAVE_JOIN_MAX_ROWS, len(flat))
-                ops.wave_mix(flat[lo:hi], starts[lo:hi], flags[lo:hi], out, gain=gain, gain_idx=None if gain is None else row_voice[lo:hi], fade=fade, accumulate=lo > 0)
-            w = out
+                if total:
+                    ops.wave_mix(flat[lo:hi], starts[lo:hi], flags[lo:hi], out, gain=gain, gain_idx=None if gain is None else row_voice[lo:hi], fade=fade, accumulate=lo > 0)
+            w = out if bed is None else self._lay_bed(out, *bed)
             if peak is not None:
                 pre = None
                 if loud is not None:
@@ -1255,6 +1331,8 @@ class _TTS(_Finish):
             if fmt is not None:
                 w = ops.wave_format([w], fmt)[0]
             w = w.cpu()
+            if bed is not None:
+                self._take_bed()
             if stats is not None:
                 self.last_balance = [dict(voice=k, lufs=s[0], peak=s[1], gain=s[2], blocks=int(s[3])) for k, s in zip(keys, stats.cpu().tolist())]
         return w.unsqueeze(0), starts, kept
@@ -1457,7 +1535,7 @@ class ChatterboxTTS(_LlamaTTS):
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                       max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None,
-                      word_times=False, guard=None, true_peak=None):
+                      word_times=False, guard=None, true_peak=None, bed=None):
         """generate() for a text of ANY length: the reference stops at 1000 speech tokens (40 s) and cuts a longer text off.  The text is split into chunks of at
         most max_chars characters at paragraph, sentence and clause boundaries (text.split_text), the chunks are synthesised in text order as device batches
         (one: synthesize; several: the throughput schedule where the engine has it), and each batch's waveforms are trimmed of their leading / trailing silence and
@@ -1476,15 +1554,17 @@ class ChatterboxTTS(_LlamaTTS):
         loudness: generate()'s, of the WHOLE assembled waveform measured as one signal (pauses included), so the chunks keep their relative level: one gain for
         all of it, limited to a sample peak of 1.0, applied on the device ahead of the watermark and the conversion.
         word_times: generate()'s, with return_segments=True (without: ValueError): every segment gains `words`, its chunk's words shifted into the joined result
-        through the segment's start / src_start and clipped to [start, stop); the device batches of such a call run one after the other."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments)
+        through the segment's start / src_start and clipped to [start, stop); the device batches of such a call run one after the other.
+        bed: generate_dialogue()'s music bed under the whole assembled waveform, in the visit to the device that loudness and true_peak make; segments and words
+        begin `lead` seconds later."""
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments, bed=bed)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
 
     def generate_dialogue(self, turns, voices=None, *, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None, pause=0.15,
                           paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, repetition_penalty=1.2, min_p=0.05, top_p=1.0, exaggeration=0.5,
-                          cfg_weight=0.5, temperature=0.8, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None):
+                          cfg_weight=0.5, temperature=0.8, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None, bed=None):
         """A conversation: a script whose turns are spoken by different voices, delivered as ONE waveform.  The reference has no counterpart: it returns one
         utterance of one voice.  turns: a non-empty list of (voice, text) pairs or dicts dict(voice=, text=, gap=, speed=, pitch=, exaggeration=); voice is a key
         of `voices` or None (the model's current conds); `voices` maps a key to a Conditionals or to anything audio_prompt_path= takes (each distinct prompt is
@@ -1507,17 +1587,29 @@ class ChatterboxTTS(_LlamaTTS):
         src_stop) the kept part of the chunk's own waveform.  Truncated chunks get generate_long's single warning.
         Everything is validated when the method is called, before the engine or the voice analysis is touched: TypeError for wrong types, unknown dict keys, a
         bool where a number belongs and `turns` not a list; ValueError for out-of-range or non-finite values, an unknown voice key and empty text.
+        bed (None; an audio input -- whatever audio_prompt_path= takes: a path, a (waveform, sample_rate) pair or raw (data, rate, encoding[, channels]) --; or a
+        dict with `audio` plus overrides of ops.BED_DEFAULTS): background music or room tone under the conversation, pulled down while someone talks.  The source
+        is brought to 24 kHz mono as a voice prompt is (model.audio_in), looped with a cross-fade if it is shorter than the programme (loop, loop_fade), faded in
+        and out (fade_in, fade_out), and may play alone before and after the speech (lead, tail).  Its level is `level` LU relative to the speech (default -12:
+        two readings of the BS.1770-4 meter, the mix before the bed and the bed over its whole source); while a 10 ms frame of speech peaks above `threshold`
+        dBFS the bed is `duck` dB lower, from `pre` seconds before a word until `post` seconds after it, every transition taking `ramp` seconds -- the whole
+        signal is known, so the bed is down BEFORE the word (cbx_wave_duck_f32, ops.wave_duck; include/cbx.h states the definition).  Order of the finish: mix,
+        bed, loudness, true_peak, the watermark, sample_rate / encoding: meter and limiter see speech plus bed.  Without loudness= / true_peak= the sum is NOT
+        bounded -- speech near full scale plus the bed can pass 1.0 --: true_peak=-1 is recommended with a bed.  With return_segments the records begin `lead`
+        seconds later.  model.last_bed then holds dict(gain, speech_lufs, bed_lufs, ducked, frames, peak) -- the linear gain applied to the bed, the two
+        readings, the 10 ms frames the bed was down for, all frames, the sample peak of the sum (else None).  bed=None is the call without the argument.  Every
+        default of ops.BED_DEFAULTS is an UNMEASURED choice: nobody has tuned them by listening.
         turn_pause = 0.3 s and balance=True -> -23 LUFS are UNMEASURED defaults: nobody has tuned them with trained weights.  Not taken:
-        streaming, word_times, max_pause, duration / timing, stereo or panning, a background bed or ducking; ChatterboxVC has no such method.
+        streaming, word_times, max_pause, duration / timing, stereo or panning, more than one bed or a bed that changes per turn; ChatterboxVC has no such method.
         This is the contract of generate_dialogue of the three TTS classes; the others say only what differs."""
-        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, guard=guard)
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, guard=guard, bed=bed)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, 1.0, False)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
         return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                              max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
-                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None, true_peak=None,
+                             sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None, true_peak=None, bed=None,
                              first_batch=1, batch_growth=2.0):
         """generate_long() in pieces: a generator of (1, n) CPU tensors, one per device batch as it leaves the device (empty pieces left out); concatenated along
         dim 1 they are the long-form result.  Every argument of generate_long with its meaning and default, plus the ramp of the device batches:
@@ -1537,9 +1629,11 @@ class ChatterboxTTS(_LlamaTTS):
         sample_rate, encoding: every piece goes through ONE ops.WaveFormatStream, so the pieces add up to the conversion of the whole bit for bit.  A piece that is
         not the last holds the resampling filter's tail back: a segment's last samples may arrive with the NEXT piece.
         word_times: NOT taken -- it stands in the signature only because that is generate_long's plus the ramp; anything but False is a TypeError: a stream has
-        no finished token sequence for the alignment pass."""
+        no finished token sequence for the alignment pass.  true_peak and bed likewise: anything but None is a TypeError (a running limiter and a running bed
+        are not built)."""
         _no_word_times("generate_long_stream", word_times)
         _no_true_peak("generate_long_stream", true_peak)
+        _no_bed("generate_long_stream", bed)
         opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, guard=guard)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         ramp = _long_stream_args(first_batch, batch_growth)
@@ -1638,9 +1732,9 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
     def generate_long(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                       top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                       return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False,
-                      guard=None, true_peak=None):
+                      guard=None, true_peak=None, bed=None):
         """ChatterboxTTS.generate_long with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, word_times=word_times, guard=guard, segments=return_segments, bed=bed)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
@@ -1648,10 +1742,10 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate_dialogue(self, turns, voices=None, *, language_id=None, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None,
                           pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                          repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None):
+                          repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None, bed=None):
         """ChatterboxTTS.generate_dialogue with generate()'s language_id for the call and, as a further key of a turn's dict, per turn (default: the call's);
         max_chars=None is 100 when the call's language is zh / ja / ko and 300 otherwise."""
-        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, guard=guard)
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, guard=guard, bed=bed)
         if language_id is not None and not isinstance(language_id, str):
             raise TypeError(f"language_id: expected None or a str, got {type(language_id).__name__}")
         lid = _language(language_id)
@@ -1662,10 +1756,11 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
     def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                              top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
                              return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, word_times=False, guard=None,
-                             true_peak=None, first_batch=1, batch_growth=2.0):
+                             true_peak=None, bed=None, first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream with generate()'s language_id; max_chars=None is 100 for zh / ja / ko and 300 otherwise."""
         _no_word_times("generate_long_stream", word_times)
         _no_true_peak("generate_long_stream", true_peak)
+        _no_bed("generate_long_stream", bed)
         opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch, guard=guard)
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, lid in CJK_LANGUAGES)
@@ -1778,9 +1873,9 @@ class ChatterboxTurboTTS(_TTS):
 
     def generate_long(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                       top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
-                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, true_peak=None):
+                      return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, true_peak=None, bed=None):
         """ChatterboxTTS.generate_long on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other)."""
-        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
+        opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, max_pause=max_pause, pause_db=pause_db, pitch=pitch, bed=bed)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_long(text, None, audio_prompt_path, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p), opts,
@@ -1789,10 +1884,10 @@ class ChatterboxTurboTTS(_TTS):
     def generate_dialogue(self, turns, voices=None, *, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None, pause=0.15,
                           paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, repetition_penalty=1.2, min_p=0.00, top_p=0.95, exaggeration=0.0,
                           cfg_weight=0.0, temperature=0.8, top_k=1000, norm_loudness=True, seed=None, sample_rate=None, encoding=None, loudness=None,
-                          true_peak=None):
+                          true_peak=None, bed=None):
         """ChatterboxTTS.generate_dialogue on the Turbo / Nano backbone (generate()'s sampling arguments; norm_loudness: prepare_conditionals', for the prompts in
         `voices`; the batches run one after the other; no guard on this backbone)."""
-        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak)
+        opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, bed=bed)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, 1.0, False)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
@@ -1800,10 +1895,11 @@ class ChatterboxTurboTTS(_TTS):
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                              top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None,
-                             speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, true_peak=None, first_batch=1, batch_growth=2.0):
+                             speed=1.0, return_segments=False, sample_rate=None, encoding=None, loudness=None, max_pause=None, pause_db=40.0, pitch=None, true_peak=None, bed=None, first_batch=1, batch_growth=2.0):
         """ChatterboxTTS.generate_long_stream on the Turbo / Nano backbone (generate()'s sampling arguments; the batches run one after the other, so a piece is
         yielded before the next batch starts)."""
         _no_true_peak("generate_long_stream", true_peak)
+        _no_bed("generate_long_stream", bed)
         opts = _Options(self, seeds=seed, speed=speed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, max_pause=max_pause, pause_db=pause_db, pitch=pitch)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, speed, False)
         ramp = _long_stream_args(first_batch, batch_growth)

@@ -2014,8 +2014,145 @@ def wave_limit(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None):
     return out, _wave_limit_launch(rows, ceil, gain, look, out)
 
 
+# ----------------------------------------------------------------------------- music bed: speech over a background that ducks while someone talks (wave_duck.hip)
+BED_FRAME = 240                                                    # Q: samples of a control frame (10 ms at 24 kHz)
+BED_HOLD_MAX, BED_S_MAX, BED_FADE_MAX = 200, 100, 24000            # the entry's caps: pre / post and S in frames, xf / fi / fo in samples
+BED_DEFAULTS = dict(level=-12.0, duck=-9.0, threshold=-40.0, pre=0.10, post=0.30, ramp=0.25, lead=0.0, tail=0.0, fade_in=0.02, fade_out=0.5, loop=True, loop_fade=0.1)
+_BED_RANGES = dict(level=(-60.0, 20.0), duck=(-60.0, 0.0), threshold=(-100.0, 0.0), pre=(0.0, 2.0), post=(0.0, 2.0), ramp=(0.02, 2.0), lead=(0.0, 600.0), tail=(0.0, 600.0),
+                   fade_in=(0.0, 1.0), fade_out=(0.0, 1.0), loop_fade=(0.0, 1.0))
+
+
+def check_bed(value, name="bed"):
+    """A `bed` argument of generate_dialogue / generate_long -> None, or the plan ops.wave_duck takes.  value: None; an audio input (whatever audio_prompt_path=
+    takes: check_audio_in); or a dict with `audio` plus overrides of BED_DEFAULTS:
+      level      the bed's loudness in LU relative to the speech (BS.1770-4 over the whole of each), [-60, 20]                      default -12
+      duck       dB the bed goes down by while someone talks, [-60, 0] (0: no ducking)                                              default  -9
+      threshold  dBFS: a 10 ms frame whose speech peak is above it counts as talk, [-100, 0]                                        default -40
+      pre, post  seconds the bed is down before a word / stays down after it, [0, 2]                                                default 0.10 / 0.30
+      ramp       seconds a transition of the gain takes (the raised-cosine window: S = round(50 ramp) frames either side), [0.02, 2] default 0.25
+      lead, tail seconds of bed alone before / after the speech, [0, 600]                                                           default 0 / 0
+      fade_in, fade_out  seconds the bed fades in at the start / out at its end, [0, 1]                                             default 0.02 / 0.5
+      loop       bool: a source shorter than the programme repeats (False: it ends, with its fade-out)                              default True
+      loop_fade  seconds of cross-fade at the loop seam, [0, 1] (the source must be longer than twice that)                         default 0.1
+    Every default is an UNMEASURED choice: nobody has tuned them by listening.  A wrong type or an unknown key is a TypeError, a value out of
+    range or not finite a ValueError; both name `bed`.  The plan: dict(audio=the input as given (check_audio_in has passed it), level, duck, threshold (dB), lead, tail, fi, fo, xf (samples at
+    24 kHz), pre, post, S (frames of 10 ms), loop)."""
+    import math
+    import numbers
+    if value is None:
+        return None
+    if isinstance(value, dict):
+        extra = set(value) - set(BED_DEFAULTS) - {"audio"}
+        if extra or "audio" not in value:
+            raise TypeError(f"{name}: keys {sorted(value, key=str)}: `audio` is required, the others are {tuple(BED_DEFAULTS)}")
+        audio, given = value["audio"], {k: v for k, v in value.items() if k != "audio"}
+    else:
+        audio, given = value, {}
+    if audio is None or isinstance(audio, (bool, numbers.Number, dict)):
+        raise TypeError(f"{name}: expected None, an audio input or a dict with `audio`, got {type(audio).__name__}")
+    check_audio_in(audio, name=f"{name}: audio")
+    v = dict(BED_DEFAULTS, **given)
+    if not isinstance(v["loop"], bool):
+        raise TypeError(f"{name}['loop']: expected a bool, got {type(v['loop']).__name__}")
+    for key, (lo, hi) in _BED_RANGES.items():
+        x = v[key]
+        if isinstance(x, bool) or not isinstance(x, numbers.Real):
+            raise TypeError(f"{name}['{key}']: expected a number, got {type(x).__name__}")
+        x = float(x)
+        if not math.isfinite(x) or not lo <= x <= hi:
+            raise ValueError(f"{name}['{key}'] = {x}: a finite number in [{lo}, {hi}]")
+        v[key] = x
+    sec = lambda t: int(round(t * WAVE_IN_RATE))
+    fr = lambda t: int(round(t * WAVE_IN_RATE / BED_FRAME))
+    return dict(audio=audio, level=v["level"], duck=v["duck"], threshold=v["threshold"], lead=sec(v["lead"]), tail=sec(v["tail"]), fi=sec(v["fade_in"]), fo=sec(v["fade_out"]),
+                xf=sec(v["loop_fade"]), pre=fr(v["pre"]), post=fr(v["post"]), S=max(1, int(round(v["ramp"] * 50.0))), loop=v["loop"])
+
+
+def bed_len(n, plan):
+    """Samples of the output of wave_duck for n samples of speech: lead + n + tail"""
+    return int(plan["lead"]) + int(n) + int(plan["tail"])
+
+
+def wave_duck_level(stats_s, stats_b, level):
+    """cbx_wave_duck_level_f32 on the current stream: the bed gains (R,) fp32 on the device from two (R, 4) float64 stats blocks of wave_loudness in measure-only
+    mode (speech, bed): 10^((Ls + level - Lb) / 20), `level` (a number or R numbers) in LU relative to the speech; where a reading is not finite (silence, or
+    shorter than 0.4 s) 10^(level / 20).  One launch, nothing is synchronised."""
+    R, dev = int(stats_s.shape[0]), stats_s.device
+    for st in (stats_s, stats_b):
+        assert st.dtype == torch.float64 and tuple(st.shape) == (R, 4) and st.is_contiguous() and st.device == dev, "wave_duck_level: stats are (R, 4) float64 on one device"
+    if not isinstance(level, (list, tuple)):
+        level = [level] * R
+    if len(level) != R:
+        raise ValueError(f"wave_duck_level: {len(level)} levels for {R} rows")
+    lv = (ctypes.c_double * R)(*[float(x) for x in level])
+    gain = torch.empty(R, dtype=torch.float32, device=dev)
+    check(lib.cbx_wave_duck_level_f32(_p(stats_s), _p(stats_b), ctypes.addressof(lv), R, _p(gain), _stream()), "cbx_wave_duck_level_f32")
+    return gain
+
+
+def wave_duck(speech_rows, bed_rows, plan, gain=None, out=None):
+    """cbx_wave_duck_f32 on the current stream: every speech row (_wave_rows: 1 .. 64 1-D fp32 views of ONE allocation at 24 kHz; None or an empty tensor: no
+    speech) over its bed source (bed_rows: None -- no bed at all --, or R rows of ONE allocation, None / empty ones allowed) times gain[r] (an (R,) fp32 device
+    tensor, wave_duck_level's; None: 1), the bed pulled down by plan["duck"] dB around the frames where the speech peaks above plan["threshold"] dBFS
+    (include/cbx.h states the definition).  plan: check_bed's dict, of which duck, threshold, lead, tail, pre, post, S, loop, xf, fi, fo are read.  Returns
+    (out_rows, stats): out_rows of bed_len(n_r, plan) samples each, views of ONE new allocation, back to back (out: R rows of those lengths in an allocation of
+    the caller's instead, overlapping neither input); stats (R, 4) float64 {the gain as applied, frames ducked, frames, max |out| (NaN: the row holds one)} on the
+    device.  Three launches -- none when every output row is empty --, nothing is synchronised."""
+    speech_rows = list(speech_rows)
+    R = len(speech_rows)
+    bed_rows = [None] * R if bed_rows is None else list(bed_rows)
+    if len(bed_rows) != R:
+        raise ValueError(f"wave_duck: {len(bed_rows)} bed rows for {R} speech rows")
+
+    def anchored(rows, who):
+        anchor = next((w for w in rows if w is not None and w.numel()), None)
+        if anchor is None:
+            return None
+        return [anchor[:0] if (w is None or not w.numel()) else w for w in rows]
+    dev = next((w.device for w in speech_rows + bed_rows + list(out or []) if w is not None), None)
+    if gain is not None:
+        dev = gain.device if dev is None else dev
+        assert gain.dtype == torch.float32 and gain.numel() == R and gain.is_contiguous() and gain.device == dev, "wave_duck: gain is (R,) fp32 on the rows' device"
+    sp, bd = anchored(speech_rows, "speech"), anchored(bed_rows, "bed")
+    n = [0 if w is None else int(w.numel()) for w in speech_rows]
+    N = [bed_len(k, plan) for k in n]
+    win = limit_window(int(plan["S"]))  # (TypeError / ValueError for an S the window does not take; S <= 100 is the entry's own check)
+    if max(N, default=0) == 0:
+        if not 1 <= R <= WAVE_JOIN_MAX_ROWS:
+            raise ValueError(f"wave_duck: {R} rows (1 .. {WAVE_JOIN_MAX_ROWS})")
+        stats = torch.zeros(R, 4, dtype=torch.float64, device=dev)
+        stats[:, 0] = 1.0 if gain is None else gain.double()
+        return (list(out) if out is not None else [torch.empty(0, dtype=torch.float32, device=dev) for _ in range(R)]), stats
+    if out is None:
+        starts = [sum(N[:r]) for r in range(R)]
+        buf = torch.empty(max(1, sum(N)), dtype=torch.float32, device=dev)
+        out = [buf[a: a + k] for a, k in zip(starts, N)]
+    else:
+        out = list(out)
+    obase, ooffs, olens = _wave_rows(out, "wave_duck: out")
+    if list(olens) != N:
+        raise ValueError(f"wave_duck: the rows of out have the lengths {list(olens)}, the plan gives {N}")
+    cap = max((a + k for a, k in zip(ooffs, olens)), default=0)
+    zero_off, zero_len = (ctypes.c_long * R)(), (ctypes.c_int * R)()
+    if sp is None:  # (no speech at all: bed alone over lead + tail; the entry wants a pointer, and reads nothing through it)
+        sbase, soffs, slens = obase, zero_off, zero_len
+    else:
+        sbase, soffs, slens = _wave_rows(sp, "wave_duck: speech")
+    bbase, boffs, blens = (None, zero_off, zero_len) if bd is None else _wave_rows(bd, "wave_duck: bed")
+    xf = int(plan["xf"])
+    ramp = join_ramp(xf, dev) if plan["loop"] and xf > 0 else None
+    stats = torch.empty(R, 4, dtype=torch.float64, device=dev)
+    n_max = max(N)
+    ws = torch.empty(max(1, R * (-(-n_max // BED_FRAME) + 4 * -(-n_max // 1024))), dtype=torch.float32, device=dev)
+    check(lib.cbx_wave_duck_f32(sbase, ctypes.addressof(soffs), ctypes.addressof(slens), bbase, ctypes.addressof(boffs), ctypes.addressof(blens), R, _p(gain),
+                                int(plan["lead"]), int(plan["tail"]), 10.0 ** (float(plan["threshold"]) / 20.0), 10.0 ** (float(plan["duck"]) / 20.0), int(plan["pre"]),
+                                int(plan["post"]), int(plan["S"]), _p(_on_device(("limit_window", int(plan["S"])), dev, lambda: win)), int(bool(plan["loop"])), xf, _p(ramp),
+                                int(plan["fi"]), int(plan["fo"]), obase, ctypes.addressof(ooffs), cap, _p(stats), _p(ws), ws.numel(), _stream()), "cbx_wave_duck_f32")
+    return out, stats
+
+
 # ----------------------------------------------------------------------------- audio in: decode + mixdown + resample, trim edges (wave_ingest.hip)
-WAVE_IN_ENCODINGS = ("u8", "s16", "s24", "s32", "f32", "mulaw", "alaw")   # cbx_wave_ingest's encoding 0 .. 6 (CBX_WAVE_IN_*)
+WAVE_IN_ENCODINGS =("u8", "s16", "s24", "s32", "f32", "mulaw", "alaw")   # cbx_wave_ingest's encoding 0 .. 6 (CBX_WAVE_IN_*)
 WAVE_IN_SAMPLE_BYTES = dict(u8=1, s16=2, s24=3, s32=4, f32=4, mulaw=1, alaw=1)
 WAVE_IN_RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000)   # the source rates every analysis rate (16000, 24000) is tested at
 WAVE_INGEST_MAX_SPAN, WAVE_INGEST_MAX_TAB = 2048, 16384   # CBX_WAVE_INGEST_MAX_SPAN / _TAB of include/cbx.h

@@ -1188,6 +1188,54 @@ int cbx_wave_limit_f32(const float* wav, const long* row_off, const int* row_len
 int cbx_wave_mix_f32(const float* wav, const long* row_off, const int* row_len, const long* start, const int* flags, int R, const float* gain, int G,
                      const int* gain_idx, const float* ramp, int fade, float* out, long out_len, int accumulate, void* stream);
 
+/* ---- music bed: lay the finished speech over a background and pull the background down while someone talks (added after ABI v16 without a version step: new
+ * functions only).  The reference has no counterpart: it returns one utterance of one voice as the vocoder left it (tts.py:272, mtl_tts.py:352,
+ * tts_turbo.py:320).  All signals are 24 kHz mono fp32.  Rows: R in [1, 64]; speech row r = s_len[r] floats at speech + s_off[r], its bed source b_len[r] floats
+ * at bed + b_off[r], its output at out + out_off[r] (HOST arrays that travel to the kernels by value; 4-byte alignment is enough).  One set of control numbers
+ * serves the call.
+ * Inputs per row: s, n samples of speech; b, nb samples of bed source; lead, tail >= 0 samples of bed alone before and after the speech; L = gain[r], the bed
+ * gain (R device floats; NULL: 1); thr = (float)threshold, threshold = 10^(threshold_db / 20) > 0; d = (float)duck, duck = 10^(duck_db / 20) in (0, 1]; pre,
+ * post >= 0 control frames; S >= 1, the smoothing half-width in frames; loop (0 / 1) and xf, the cross-fade samples at the loop seam; fi, fo, the fade-in and
+ * fade-out samples.  Two tables built by the CALLER in device memory: win = cbx_wave_limit_f32's window for H = S (2 S + 1 floats, w_k at win[k + S]) and ramp =
+ * cbx_wave_join_f32's ramp[i] = (2 i + 1) / (2 xf), xf floats (NULL only when loop == 0 or xf == 0).
+ * Definition, in fp32.  The output has N = lead + n + tail samples; s'[i] = s[i - lead] inside the speech, else 0.
+ *   1. Control frames: Q = 240 samples (10 ms), F = ceil(N / Q).  p[f] = the max of |s'[i]| over frame f, NaN if the frame holds a NaN; act[f] = !(p[f] <= thr):
+ *      a NaN frame is active.  A comparison of exact values: the same decision in every implementation.
+ *   2. Hold: A[f] = the OR of act[j] for j in [f - post, f + pre], frames outside [0, F) inactive: the bed goes down pre frames before a word and stays down
+ *      post frames after it (the whole signal is known).
+ *   3. Smoothing: t[f] = d if A[f] else 1, and 1 outside [0, F); G[f] = 1 - sum_(k = -S .. S) w_k (1 - t[f + k]), 1 - t rounded once, then fmaf in the order
+ *      k = -S .. S from 0.
+ *   4. Per-sample gain: j = i - Q / 2, f0 = floor(j / Q), a = (float)(j - f0 Q) / 240.0f; g[i] = fmaf(a, G[f0 + 1] - G[f0], G[f0]) with G[-1] = G[0] and
+ *      G[F] = G[F - 1].
+ *   5. Bed read bed'(i): nb == 0: 0 (in either mode).  No loop: b[i] for i < nb, else 0; end = min(N, nb).  Loop: P = nb - xf, k = i / P, r = i % P; where
+ *      k > 0 and r < xf the value is fmaf(ramp[r], b[r] - b[P + r], b[P + r]), else b[r]; end = N.  (end = 0 when nb == 0.)
+ *   6. Envelope: up = i < fi ? (float)(i + 1) / (float)(fi + 1) : 1; dn = end - 1 - i < fo ? (float)(end - i) / (float)(fo + 1) : 1; e = up * dn, and 0 for
+ *      i >= end.
+ *   7. out[i] = fmaf((bed'(i) * e) * g[i], L, s'[i]): two rounded products, one fma.
+ * Properties: with duck == 1 (0 dB) every 1 - t is exactly 0, so G and g are exactly 1; for a row with no active frame likewise (as the limiter's g is 1 wherever
+ * nothing within its window is limited).  With L == 0 or nb == 0 the non-zero samples of out are s' bit for bit (a -0 may come back as +0).  Every value depends
+ * on the row's samples alone, not on the tile, the grid or the rows' alignment, bit for bit.
+ * stats: (R, 4) device doubles {L as applied, the frames with A[f], F, max |out| (NaN if the output row holds one; 0 for an empty row)}.
+ * speech and bed are only read; the output rows may overlap neither; nothing outside the rows of out is written.  16-byte loads and stores inside a row where
+ * the addresses allow, 4-byte accesses at the ragged ends; a quad that meets the loop seam is read sample by sample.
+ * Three launches (wave_duck.hip): frames -- one WAVE per control frame, the wave maximum by cbx_xor_lane butterflies, the activity as 1.0f / 0.0f in ws --, apply
+ * -- one workgroup of 256 threads per 1024 outputs of a row: the activity of the tile's frames +- 1 +- S and pre / post in LDS, then A, 1 - t and G for its <= 7
+ * frames in the order above, then the stream --, fold -- the tiles' {max |out|, NaN flag, frames with A} per row (max and integer counts: exact in any order).
+ * No floating-point atomics.  ONE launch, the fold, when every output row is empty.  Nothing synchronises the host.
+ * ws: device workspace of ws_cap >= R * (ceil(max_r N_r / 240) + 4 * ceil(max_r N_r / 1024)) floats (not NULL).
+ * -22 before any launch, nothing written: a null pointer other than gain / ramp / bed (bed may be NULL only when every bed row is empty, ramp only when loop == 0
+ * or xf == 0), R outside [1, 64], a negative length, offset, lead or tail, more than 2^31 - 1 outputs in a row, a threshold that is not a positive finite float,
+ * duck outside (0, 1], pre or post outside [0, 200], S outside [1, 100], xf, fi or fo outside [0, 24000], loop outside {0, 1}, a looped bed row with
+ * 0 < nb <= 2 xf, a row that would write outside [0, out_cap), an output row overlapping a speech or bed row, a workspace that is too small. */
+int cbx_wave_duck_f32(const float* speech, const long* s_off, const int* s_len, const float* bed, const long* b_off, const int* b_len, int R, const float* gain,
+                      long lead, long tail, double threshold, double duck, int pre, int post, int S, const float* win, int loop, int xf, const float* ramp, int fi,
+                      int fo, float* out, const long* out_off, long out_cap, double* stats, float* ws, long ws_cap, void* stream);
+/* cbx_wave_duck_level_f32: the bed gain from two readings of the BS.1770-4 meter.  stats_speech / stats_bed: two (R, 4) stats blocks of cbx_wave_loudness_f32 in
+ * measure-only mode (device doubles; column 0 = L in LUFS); level: R HOST doubles, the bed's level in LU relative to the speech (finite, within +- 200).
+ * gain[r] = (float)10^((Ls_r + level_r - Lb_r) / 20), evaluated in fp64; where Ls_r or Lb_r is not finite (silence, or shorter than 0.4 s) gain[r] =
+ * (float)10^(level_r / 20).  One small launch; nothing is synchronised.  -22 before the launch: a null pointer, R outside [1, 64], a level that is not finite. */
+int cbx_wave_duck_level_f32(const double* stats_speech, const double* stats_bed, const double* level, int R, float* gain, void* stream);
+
 /* ---- audio in: decode, mix down and resample the raw sample bytes of voice prompts and conversion sources, and find the silence at their ends, on the device
  * (added after ABI v16 without a version step: new functions only).  The mirror image of cbx_wave_format_f32.  It replaces frontend.load_wav / resample /
  * trim_silence (NumPy / SciPy on the host), which restate librosa.load, librosa.resample and librosa.effects.trim of the reference (tts.py:184-187,
