@@ -302,6 +302,9 @@ _SIGS = {
     "cbx_wave_gain_f32": ([c_f, c_f, c_f, c_int, c_f, c_f], c_int),
     "cbx_wave_limit_f32": ([c_f, c_f, c_f, c_int, c_f, c_f, c_f, c_int, c_int, c_f, c_int, c_f, c_f, c_long, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_mix_f32": ([c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_f, c_f, c_int, c_f, c_long, c_int, c_f], c_int),
+    "cbx_wave_pan_mix_f32": ([c_f, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_f, c_f, c_int, c_f, c_long, c_long, c_int, c_f], c_int),
+    "cbx_wave_loudness_ch_f32": ([c_f, c_f, c_f, c_int, c_int, c_f, c_int, c_f, ctypes.c_double, c_f, c_f, c_f, c_long, c_f], c_int),
+    "cbx_wave_limit_ch_f32": ([c_f, c_f, c_f, c_int, c_int, c_f, c_f, c_f, c_int, c_int, c_f, c_int, c_f, c_f, c_long, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_duck_f32": ([c_f] * 6 + [c_int, c_f, c_long, c_long, ctypes.c_double, ctypes.c_double, c_int, c_int, c_int, c_f, c_int, c_int, c_f, c_int, c_int, c_f, c_f,
                            c_long, c_f, c_f, c_long, c_f], c_int),
     "cbx_wave_duck_level_f32": ([c_f, c_f, c_f, c_int, c_f, c_f], c_int),

@@ -532,7 +532,8 @@ def long_stream_plan(chunks, max_batch, a, first_batch=1, batch_growth=2.0):
 DIALOGUE_TURN_PAUSE = 0.3   # seconds between two turns: an UNMEASURED default -- nobody has tuned it on trained weights
 DIALOGUE_BALANCE = -23.0    # balance=True: the LUFS level every voice is brought to (EBU R 128's programme level): an UNMEASURED default
 DIALOGUE_GAP = 60.0         # |gap| and |turn_pause| of a turn, seconds
-DIALOGUE_TURN_KEYS = ("voice", "text", "gap", "speed", "pitch", "exaggeration")
+DIALOGUE_TURN_KEYS = ("voice", "text", "gap", "speed", "pitch", "exaggeration", "pan")
+DIALOGUE_PAN_SPREAD = 0.3   # pan=True: the distinct voices are spread evenly over [-0.3, +0.3]: an UNMEASURED default -- nobody has tuned it by listening
 DIALOGUE_MAX_VOICES = ops.WAVE_JOIN_MAX_ROWS   # the meter of balance= takes one row per voice
 
 
@@ -555,6 +556,36 @@ def _dialogue_balance(balance):
     if isinstance(balance, (list, tuple)):
         raise TypeError(f"balance: expected None, True or a number of LUFS, got a {type(balance).__name__}")
     return ops.check_loudness(balance, 1, "balance")[0]
+
+
+def _dialogue_pan(pan, ts, keys, bed=None):
+    """pan= of generate_dialogue -> None (mono: today's call), or dict(voices=[position per distinct voice, in the order of `keys`], rows=[position per turn]).
+    pan: None; True (the distinct voices spread evenly over [-DIALOGUE_PAN_SPREAD, +DIALOGUE_PAN_SPREAD] in order of first appearance, one voice at 0); or a dict
+    voice key -> position in [-1, 1] (a voice not named sits at 0; a key that no turn uses is a ValueError).  A turn's own pan= overrides its voice's place for that
+    turn, and needs pan= on the call.  Raised when the method is called: TypeError for wrong types and bools where a number belongs, ValueError for the rest."""
+    if pan is None or pan is False:
+        for t, turn in enumerate(ts):
+            if turn["pan"] is not None:
+                raise ValueError(f"turns[{t}]: pan: a turn is placed only in a stereo call; pass pan=True or pan={{voice: position}} to generate_dialogue")
+        return None
+    if bed is not None:
+        raise ValueError("bed= together with pan= is not built: a stereo bed needs a linked ducking kernel and an ingest that keeps the channels")
+    if pan is True:
+        V = len(keys)
+        place = [0.0 if V == 1 else -DIALOGUE_PAN_SPREAD + 2.0 * DIALOGUE_PAN_SPREAD * v / (V - 1) for v in range(V)]
+    elif isinstance(pan, dict):
+        for k, v in pan.items():
+            try:
+                known = k in keys
+            except TypeError:
+                known = False
+            if not known:
+                raise ValueError(f"pan: voice {k!r} speaks no turn of the script ({sorted(map(repr, keys))})")
+            ops.check_pan(v, f"pan[{k!r}]")
+        place = [ops.check_pan(pan.get(k, 0.0), f"pan[{k!r}]") for k in keys]
+    else:
+        raise TypeError(f"pan: expected None, True or a dict of voice key -> position in [-1, 1], got {type(pan).__name__}")
+    return dict(voices=place, rows=[place[keys.index(t["voice"])] if t["pan"] is None else t["pan"] for t in ts])
 
 
 def _dialogue_turns(turns, voices, turn_pause, exaggeration, language_id=None, multilingual=False):
@@ -602,6 +633,7 @@ def _dialogue_turns(turns, voices, turn_pause, exaggeration, language_id=None, m
             ops.check_speed_pitch(speed, pitch, 1)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
+        place = None if turn.get("pan") is None else ops.check_pan(turn["pan"], f"{name}: pan")
         ex = exaggeration if turn.get("exaggeration") is None else turn["exaggeration"]
         _long_numbers(**{f"{name}: exaggeration": ex})
         lid = language_id
@@ -610,7 +642,7 @@ def _dialogue_turns(turns, voices, turn_pause, exaggeration, language_id=None, m
                 raise TypeError(f"{name}: language_id: expected a str, got {type(turn['language_id']).__name__}")
             lid = _language(turn["language_id"], f" (turn {t})")
         out.append(dict(voice=voice, text=text, gap=gap, speed=1.0 if speed is None else speed[0], pitch=0.0 if pitch is None else pitch[0], exaggeration=ex,
-                        language_id=lid))
+                        language_id=lid, pan=place))
     return out
 
 
@@ -1210,16 +1242,20 @@ class _TTS(_Finish):
     # ------------------------------------------------------------------------------------------------------------ dialogue
     last_balance = None  # per voice of the last generate_dialogue(balance=) call, in order of first appearance: dict(voice, lufs, peak, gain, blocks); else None
 
-    def _generate_dialogue(self, turns, voices, turn_pause, balance, a, return_segments, samp, unsampled, opts, language_id=None, multilingual=False, **analyse_kw):
+    last_pan = None      # per voice of the last generate_dialogue(pan=) call, in order of first appearance: dict(voice, position, left, right); else None
+
+    def _generate_dialogue(self, turns, voices, turn_pause, balance, a, return_segments, samp, unsampled, opts, language_id=None, multilingual=False, pan=None,
+                           **analyse_kw):
         """generate_dialogue behind its signature, its _Options (format, loudness, true_peak, guard: the finish and the guard) and _long_args: the script's
         validation, the voices (each distinct prompt analysed once; self.conds is never written), the chunks of every turn, dialogue_plan's jobs through _run_jobs,
         then _mix_dialogue.  samp / unsampled: as _generate_long takes them, one number each."""
         ts = _dialogue_turns(turns, voices, turn_pause, unsampled["exaggeration"], language_id, multilingual)
         level = _dialogue_balance(balance)
         _long_numbers(**unsampled, **samp)
-        self.last_bed = None
-        bed = None if opts.bed is None else (opts.bed, self._bed_source(opts.bed))
+        self.last_bed = self.last_pan = None
         keys = list(dict.fromkeys(t["voice"] for t in ts))  # the distinct voices in order of first appearance (None: the model's own)
+        place = _dialogue_pan(pan, ts, keys, opts.bed)
+        bed = None if opts.bed is None else (opts.bed, self._bed_source(opts.bed))
         if level is not None and len(keys) > DIALOGUE_MAX_VOICES:
             raise ValueError(f"balance: {len(keys)} distinct voices, the meter takes at most {DIALOGUE_MAX_VOICES}")
         assert self.conds is not None or None not in keys, _NO_VOICE
@@ -1255,7 +1291,12 @@ class _TTS(_Finish):
         self._warn_truncated("generate_dialogue", truncated, a["max_chars"])
         if opts.guard is not None:
             self._take_guard(reports, "generate_dialogue")
-        wav, starts, kept = self._mix_dialogue(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts, bed)
+        if place is not None:
+            wav, starts, kept = self._mix_dialogue_stereo(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts,
+                                                          [ops.pan_gains(place["rows"][t]) for t in turn_of])
+            self.last_pan = [dict(voice=k, position=p, left=g[0], right=g[1]) for k, p in zip(keys, place["voices"]) for g in [ops.pan_gains(p)]]
+        else:
+            wav, starts, kept = self._mix_dialogue(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts, bed)
         if bed is not None:  # the speech begins `lead` samples into the result
             starts = [v + opts.bed["lead"] for v in starts]
         if not return_segments:
@@ -1270,6 +1311,39 @@ class _TTS(_Finish):
             segments.append(seg)
         return wav, segments
 
+    @staticmethod
+    def _dialogue_layout(recs, after):
+        """The rows of a conversation from the jobs' records -> (kept (src_start, src_stop) per row, their lengths, ops.mix_layout's starts and total, the fade
+        flags: every row fades in and out except the very first row's start and the very last row's end where nothing was trimmed there)."""
+        kept = [e for rec in recs for e in rec["edges"]]
+        lengths = [b0 - a0 for a0, b0 in kept]
+        starts, total = ops.mix_layout(lengths, after)
+        flags = [3] * len(kept)
+        if kept[0][0] == 0:
+            flags[0] &= ~1
+        if kept[-1][1] == recs[-1]["n"][-1]:
+            flags[-1] &= ~2
+        return kept, lengths, starts, total, flags
+
+    @staticmethod
+    def _dialogue_upload(pieces, recs, lengths, row_voice, keys, level, dev):
+        """The upload of the finish: every piece into its slice of ONE allocation, so that a launch may take rows of several pieces -> (the rows as views of it,
+        and with a balance level the meter's (V, 4) stats and (V,) gains over every voice's rows packed back to back, else None, None)."""
+        cuts = [0]
+        for w in pieces:
+            cuts.append(cuts[-1] + int(w.numel()))
+        up = torch.empty(max(1, cuts[-1]), dtype=torch.float32, device=dev)
+        for g, w in enumerate(pieces):
+            up[cuts[g]: cuts[g + 1]].copy_(w)
+        flat = [up[cuts[g] + off: cuts[g] + off + (b0 - a0)] for g, rec in enumerate(recs) for off, (a0, b0) in zip(rec["offsets"], rec["edges"])]
+        gain = stats = None
+        if level is not None:
+            order = [k for v in range(len(keys)) for k in range(len(flat)) if row_voice[k] == v]
+            packed = torch.cat([flat[k] for k in order])
+            ends = [sum(lengths[k] for k in order if row_voice[k] < v) for v in range(len(keys) + 1)]
+            stats, gain = ops.wave_loudness([packed[ends[v]: ends[v + 1]] for v in range(len(keys))], [level] * len(keys), 1.0)
+        return flat, stats, gain
+
     def _mix_dialogue(self, pieces, recs, after, row_voice, keys, level, fade, opts, bed=None):
         """The finish of generate_dialogue, ONE visit to the device for the whole conversation: the jobs' pieces (host tensors: each the job's trimmed rows back to
         back; recs: their records of offsets and edges) are uploaded into ONE allocation, ops.mix_layout over the kept lengths places the rows, the meter of
@@ -1282,34 +1356,14 @@ class _TTS(_Finish):
         would differ from generate_long's bits in the sign of those zeros.  With one allocation a script of up to 64 chunks is one launch and has no such seam.)
         Every row fades in and out over `fade` samples except the very first row's start and the very last row's end where nothing was trimmed there (the join's
         first / last rule).  Returns (the (1, n) CPU tensor, the rows' starts in 24 kHz samples, their kept (src_start, src_stop))."""
-        kept = [e for rec in recs for e in rec["edges"]]
-        lengths = [b0 - a0 for a0, b0 in kept]
-        starts, total = ops.mix_layout(lengths, after)
-        flags = [3] * len(kept)
-        if kept[0][0] == 0:
-            flags[0] &= ~1
-        if kept[-1][1] == recs[-1]["n"][-1]:
-            flags[-1] &= ~2
+        kept, lengths, starts, total, flags = self._dialogue_layout(recs, after)
         fmt, loud, peak = opts.fmt, None if opts.loud is None else opts.loud[0], None if opts.peak is None else opts.peak[0]
         self.last_balance = None
         if total == 0 and bed is None:
             return self._finish(torch.zeros(0), fmt, converted=False), starts, kept
         dev, scope = self._device_scope()
         with scope:
-            # the upload: every piece into its slice of ONE allocation, so that a launch may take rows of several pieces
-            cuts = [0]
-            for w in pieces:
-                cuts.append(cuts[-1] + int(w.numel()))
-            up = torch.empty(max(1, cuts[-1]), dtype=torch.float32, device=dev)
-            for g, w in enumerate(pieces):
-                up[cuts[g]: cuts[g + 1]].copy_(w)
-            flat = [up[cuts[g] + off: cuts[g] + off + (b0 - a0)] for g, rec in enumerate(recs) for off, (a0, b0) in zip(rec["offsets"], rec["edges"])]
-            gain = stats = None
-            if level is not None:
-                order = [k for v in range(len(keys)) for k in range(len(flat)) if row_voice[k] == v]
-                packed = torch.cat([flat[k] for k in order])
-                ends = [sum(lengths[k] for k in order if row_voice[k] < v) for v in range(len(keys) + 1)]
-                stats, gain = ops.wave_loudness([packed[ends[v]: ends[v + 1]] for v in range(len(keys))], [level] * len(keys), 1.0)
+            flat, stats, gain = self._dialogue_upload(pieces, recs, lengths, row_voice, keys, level, dev)
             out = torch.empty(total, dtype=torch.float32, device=dev)
             for lo in range(0, len(flat), ops.WAVE_JOIN_MAX_ROWS):
                 hi = min(lo + ops.WAVE_JOIN_MAX_ROWS, len(flat))
@@ -1336,6 +1390,51 @@ class _TTS(_Finish):
             if stats is not None:
                 self.last_balance = [dict(voice=k, lufs=s[0], peak=s[1], gain=s[2], blocks=int(s[3])) for k, s in zip(keys, stats.cpu().tolist())]
         return w.unsqueeze(0), starts, kept
+
+    def _mix_dialogue_stereo(self, pieces, recs, after, row_voice, keys, level, fade, opts, pan):
+        """_mix_dialogue with pan=: the same ONE visit to the device, two planes.  pan: the (left, right) gains of every row (ops.pan_gains of its turn's place).
+        The upload, the layout, the flags and the meter of balance= (over every voice's MONO rows) are _mix_dialogue's; ops.wave_pan_mix sums the rows into a
+        (2, total) buffer in launches of 64 rows, the first writing both planes and the others accumulating; loudness= reads the two planes as ONE signal
+        (ops.wave_loudness_ch: the channels' summed block energies); true_peak= is the linked limiter (ops.wave_limit_ch) with the meter's gain as its pre-gain;
+        without a ceiling the loudness gain is limited to a sample peak of 1.0 over both channels and applied by ops.wave_gain with the one gain for both planes.
+        The watermark, if loaded, is applied per channel on the host; sample_rate= / encoding= are ONE ops.wave_format call with the planes as two rows; one copy
+        to the host.  Returns (the planar (2, n) CPU tensor, the rows' starts in 24 kHz samples, their kept (src_start, src_stop))."""
+        kept, lengths, starts, total, flags = self._dialogue_layout(recs, after)
+        fmt, loud, peak = opts.fmt, None if opts.loud is None else opts.loud[0], None if opts.peak is None else opts.peak[0]
+        self.last_balance = None
+        if total == 0:
+            w = self._finish(torch.zeros(0), fmt, converted=False)
+            return torch.cat([w, w]), starts, kept
+        dev, scope = self._device_scope()
+        with scope:
+            flat, stats, gain = self._dialogue_upload(pieces, recs, lengths, row_voice, keys, level, dev)
+            out = torch.empty(2, total, dtype=torch.float32, device=dev)
+            for lo in range(0, len(flat), ops.WAVE_JOIN_MAX_ROWS):
+                hi = min(lo + ops.WAVE_JOIN_MAX_ROWS, len(flat))
+                ops.wave_pan_mix(flat[lo:hi], starts[lo:hi], flags[lo:hi], pan[lo:hi], out, gain=gain, gain_idx=None if gain is None else row_voice[lo:hi], fade=fade,
+                                 accumulate=lo > 0)
+            w = out
+            if peak is not None:
+                pre = None
+                if loud is not None:
+                    self.engine.last_loudness, pre = ops.wave_loudness_ch([w[0], w[1]], [float(loud)], None)
+                lim = torch.empty_like(w)
+                _, self.engine.last_limit = ops.wave_limit_ch([w[0], w[1]], [float(peak)], gain=pre, out=[lim[0], lim[1]])
+                w = lim
+            elif loud is not None:
+                self.engine.last_loudness, g1 = ops.wave_loudness_ch([w[0], w[1]], [float(loud)], 1.0)
+                ops.wave_gain([w[0], w[1]], g1.repeat(2))
+            if self.watermarker is not None:
+                host = w.cpu().numpy()
+                w = torch.stack([torch.from_numpy(self.watermarker.apply_watermark(host[c], sample_rate=self.sr)) for c in range(2)])
+                if fmt is not None:
+                    w = w.to(dev)
+            if fmt is not None:
+                w = torch.stack(ops.wave_format([w[0], w[1]], fmt))
+            w = w.cpu()
+            if stats is not None:
+                self.last_balance = [dict(voice=k, lufs=s[0], peak=s[1], gain=s[2], blocks=int(s[3])) for k, s in zip(keys, stats.cpu().tolist())]
+        return w, starts, kept
 
     def _stream_long(self, chunks, plan, jobs, a, return_segments, opts):
         """generate_long_stream behind its validation, a generator: the jobs run through _run_jobs -- while the consumer holds piece k the throughput schedule has
@@ -1564,7 +1663,7 @@ class ChatterboxTTS(_LlamaTTS):
 
     def generate_dialogue(self, turns, voices=None, *, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None, pause=0.15,
                           paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, repetition_penalty=1.2, min_p=0.05, top_p=1.0, exaggeration=0.5,
-                          cfg_weight=0.5, temperature=0.8, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None, bed=None):
+                          cfg_weight=0.5, temperature=0.8, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None, bed=None, pan=None):
         """A conversation: a script whose turns are spoken by different voices, delivered as ONE waveform.  The reference has no counterpart: it returns one
         utterance of one voice.  turns: a non-empty list of (voice, text) pairs or dicts dict(voice=, text=, gap=, speed=, pitch=, exaggeration=); voice is a key
         of `voices` or None (the model's current conds); `voices` maps a key to a Conditionals or to anything audio_prompt_path= takes (each distinct prompt is
@@ -1599,13 +1698,25 @@ class ChatterboxTTS(_LlamaTTS):
         seconds later.  model.last_bed then holds dict(gain, speech_lufs, bed_lufs, ducked, frames, peak) -- the linear gain applied to the bed, the two
         readings, the 10 ms frames the bed was down for, all frames, the sample peak of the sum (else None).  bed=None is the call without the argument.  Every
         default of ops.BED_DEFAULTS is an UNMEASURED choice: nobody has tuned them by listening.
+        pan (None; True; or a dict voice key -> position in [-1, 1], -1 hard left, 0 the centre, +1 hard right): a STEREO programme, each voice at a place in the
+        image.  A voice the dict does not name sits at 0, a key that speaks no turn is a ValueError; True spreads the distinct voices evenly over
+        [-DIALOGUE_PAN_SPREAD, +DIALOGUE_PAN_SPREAD] = [-0.3, 0.3] in order of first appearance (one voice: 0); a turn's dict may carry pan= and overrides its
+        voice's place for that turn.  The constant-power law (ops.pan_gains: left = cos, right = sin of (p + 1) pi / 4) keeps a voice's power wherever it sits.
+        The finish stays ONE visit to the device: balance= still meters each voice's mono rows; cbx_wave_pan_mix_f32 sums the rows into two planes, reading every
+        sample once; loudness= reads the two planes as one signal (cbx_wave_loudness_ch_f32: BS.1770-4 gates on the SUM of the channels' block energies);
+        true_peak= is the LINKED limiter (cbx_wave_limit_ch_f32: one gain envelope for both channels, so a peak on one side does not move the image); the
+        watermark is applied per channel; sample_rate= / encoding= convert both planes in one launch.  The result is a planar (2, n) tensor in every encoding;
+        the segments' numbers are per-channel sample positions, those of the mono call.  model.last_pan then holds dict(voice, position, left, right) per voice
+        in order of first appearance (else None).  pan=None is the call without the argument, launch for launch.  bed= together with pan= is a ValueError: a
+        stereo bed is not built.  DIALOGUE_PAN_SPREAD = 0.3 is an UNMEASURED default: nobody has tuned it by listening.
         turn_pause = 0.3 s and balance=True -> -23 LUFS are UNMEASURED defaults: nobody has tuned them with trained weights.  Not taken:
-        streaming, word_times, max_pause, duration / timing, stereo or panning, more than one bed or a bed that changes per turn; ChatterboxVC has no such method.
+        streaming, word_times, max_pause, duration / timing, a stereo bed, more than two channels or interleaved output, more than one bed or a bed that changes
+        per turn; ChatterboxVC has no such method.
         This is the contract of generate_dialogue of the three TTS classes; the others say only what differs."""
         opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, guard=guard, bed=bed)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, 1.0, False)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(exaggeration=exaggeration), opts)
+        return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(exaggeration=exaggeration), opts, pan=pan)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.05, top_p=1.0, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
                              max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0, return_segments=False,
@@ -1742,7 +1853,8 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
 
     def generate_dialogue(self, turns, voices=None, *, language_id=None, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None,
                           pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, exaggeration=0.5, cfg_weight=0.5, temperature=0.8,
-                          repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None, bed=None):
+                          repetition_penalty=1.2, min_p=0.05, top_p=1.0, seed=None, sample_rate=None, encoding=None, loudness=None, true_peak=None, guard=None, bed=None,
+                          pan=None):
         """ChatterboxTTS.generate_dialogue with generate()'s language_id for the call and, as a further key of a turn's dict, per turn (default: the call's);
         max_chars=None is 100 when the call's language is zh / ja / ko and 300 otherwise."""
         opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, guard=guard, bed=bed)
@@ -1751,7 +1863,7 @@ class ChatterboxMultilingualTTS(_LlamaTTS):
         lid = _language(language_id)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, 1.0, lid in CJK_LANGUAGES)
         samp = dict(temperature=temperature, cfg_weight=cfg_weight, repetition_penalty=repetition_penalty, min_p=min_p, top_p=top_p)
-        return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(exaggeration=exaggeration), opts, lid, True)
+        return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(exaggeration=exaggeration), opts, lid, True, pan=pan)
 
     def generate_long_stream(self, text, language_id, audio_prompt_path=None, exaggeration=0.5, cfg_weight=0.5, temperature=0.8, repetition_penalty=1.2, min_p=0.05,
                              top_p=1.0, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None, speed=1.0,
@@ -1884,14 +1996,14 @@ class ChatterboxTurboTTS(_TTS):
     def generate_dialogue(self, turns, voices=None, *, turn_pause=DIALOGUE_TURN_PAUSE, balance=None, return_segments=False, max_chars=None, pause=0.15,
                           paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, repetition_penalty=1.2, min_p=0.00, top_p=0.95, exaggeration=0.0,
                           cfg_weight=0.0, temperature=0.8, top_k=1000, norm_loudness=True, seed=None, sample_rate=None, encoding=None, loudness=None,
-                          true_peak=None, bed=None):
+                          true_peak=None, bed=None, pan=None):
         """ChatterboxTTS.generate_dialogue on the Turbo / Nano backbone (generate()'s sampling arguments; norm_loudness: prepare_conditionals', for the prompts in
         `voices`; the batches run one after the other; no guard on this backbone)."""
         opts = _Options(self, seeds=seed, sample_rate=sample_rate, encoding=encoding, loudness=loudness, true_peak=true_peak, bed=bed)
         a = _long_args(max_chars, pause, paragraph_pause, trim_db, trim_pad, join_fade, seed, 1.0, False)
         samp = dict(temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty)
         return self._generate_dialogue(turns, voices, turn_pause, balance, a, return_segments, samp, dict(cfg_weight=cfg_weight, exaggeration=exaggeration, min_p=min_p),
-                                       opts, norm_loudness=norm_loudness)
+                                       opts, pan=pan, norm_loudness=norm_loudness)
 
     def generate_long_stream(self, text, repetition_penalty=1.2, min_p=0.00, top_p=0.95, audio_prompt_path=None, exaggeration=0.0, cfg_weight=0.0, temperature=0.8,
                              top_k=1000, norm_loudness=True, max_chars=None, pause=0.15, paragraph_pause=0.4, trim_db=40.0, trim_pad=2, join_fade=240, seed=None,

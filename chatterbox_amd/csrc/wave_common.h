@@ -71,6 +71,25 @@ static inline int cbx_wave_apart(const char* who, const float* wav, const cbx_wa
     return 0;
 }
 
+// The meter and the limiter behind their entries, with the channel count C in {1, 2} of a signal as an argument (wave_loudness.hip, wave_limit.hip): the mono
+// entries are the C = 1 calls, the linked entries of wave_stereo.hip check C and the groups' lengths and call the same code -- one source, one arithmetic.
+int cbx_wave_loudness_run(const char* who, const float* wav, const long* row_off, const int* row_len, int R, int C, const double* coef, int hop, const double* target,
+                          double ceiling, double* stats, float* gain, double* ws, long ws_cap, void* stream);
+int cbx_wave_limit_run(const char* who, const float* wav, const long* row_off, const int* row_len, int R, int C, const float* gain, const double* ceiling,
+                       const float* tab, int U, int T, const float* win, int H, float* out, const long* out_off, long out_cap, double* stats, double* ws, long ws_cap,
+                       void* stream);
+
+// the rows of a linked entry: C in {1, 2} and R a multiple of it, the C rows of every signal of one length
+static inline int cbx_wave_groups(const char* who, const long* row_off, const int* row_len, int R, int C) {
+    if (const int rc = cbx_wave_count(who, row_off, row_len, R)) return rc;
+    CBX_REQUIRE(C == 1 || C == 2, "%s: C = %d channels outside {1, 2}", who, C);
+    CBX_REQUIRE(R % C == 0, "%s: %d rows are no whole number of signals of %d channels", who, R, C);
+    for (int r = 0; r < R; r += C)
+        for (int c = 1; c < C; ++c)
+            CBX_REQUIRE(row_len[r + c] == row_len[r], "%s: rows %d and %d, channels of one signal, have the lengths %d and %d", who, r, r + c, row_len[r], row_len[r + c]);
+    return 0;
+}
+
 // Block b of row r covers [BLOCK b, min(BLOCK (b + 1), n)); ws[r ws_ld + b] = the fp64 sum of its squares, divided by its count where MEAN.  One WAVE per block:
 // lane l squares and adds elements [4 l, 4 l + 4) and [256 + 4 l, 256 + 4 l + 4) in that order (16-byte loads where the row allows them, the same order where it
 // does not), then a 6-step xor butterfly -- a fixed order per block whatever the grid or the row's alignment, no floating-point atomics.

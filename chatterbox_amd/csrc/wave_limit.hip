@@ -68,61 +68,86 @@ __device__ __forceinline__ float lm_peak(const float* x, const float* tabs, int 
     return m;
 }
 
-// grid (ceil(max n / 1024), R) x 256.  ws: 4 doubles per (row, tile) at (r ld + x) * 4
+// grid (ceil(max n / 1024), R / C) x 256: signal g = rows [g C, g C + C) of one length, the channels of one signal (C = 1: row g, cbx_wave_limit_f32).  The
+// channels are staged one after the other through s_u: each gives its m, the maximum over the channels so far waits in s_a (NaN where one of them is), and the
+// tile's own u of all channels but the last waits in s_keep; c, the minimum and g are formed ONCE, every channel's tile is multiplied by the same g.
+// ws: 4 doubles per (signal, tile) at (g ld + x) * 4
+template <int C>
 __global__ __launch_bounds__(256) void wave_limit_kernel(const float* __restrict__ wav, lm_rows_t rows, const float* __restrict__ gain, const float* __restrict__ tab,
                                                          int U, int T, const float* __restrict__ win, int H, float* __restrict__ out, double* __restrict__ ws, long ld) {
     __shared__ float s_u[LM_SPAN];
     __shared__ float s_a[LM_NC], s_b[LM_NC];
     __shared__ float s_tab[LM_TAB + 8];
     __shared__ float s_w[LM_WIN + 3];
-    __shared__ float s_o[LM_TILE];
+    __shared__ float s_o[C * LM_TILE];
+    __shared__ float s_keep[C > 1 ? (C - 1) * LM_TILE : 1];
     __shared__ float s_pk[256], s_mg[256];
     __shared__ int s_bad[256], s_ng[256], s_nm[256], s_any;
-    const int r = blockIdx.y, tid = threadIdx.x;
+    const int sg = blockIdx.y, r = sg * C, tid = threadIdx.x;
     const long n = rows.n[r], t0 = (long)blockIdx.x * LM_TILE;
     if (t0 >= n) return;  // (uniform over the workgroup, ahead of its barriers)
     const int nt = n - t0 < LM_TILE ? (int)(n - t0) : LM_TILE;
-    const float* p = wav + rows.off[r];
-    const float gam = gain ? gain[r] : 1.0f;
-    const float C = rows.ceil[r];
+    const float gam = gain ? gain[sg] : 1.0f;
+    const float CL = rows.ceil[r];
     const int below = T > LM_LEAD + 1 ? T - (LM_LEAD + 1) : 0;  // samples below i that y[U i + p] reads
     const int nc = LM_TILE + 4 * H, na = LM_TILE + 2 * H;
+    const int ts = T | 1;  // (an odd row stride: the phases of a wave's lanes fall on different banks)
+    const bool product = U == 4 && T == 21;  // (uniform)
     // the span of u: [t0 - 2 H - below, t0 + 1024 + 2 H + LM_LEAD], begun at most three samples lower, where p + ks is a 16-byte boundary
     const long k_lo = t0 - 2 * H - below;
-    const long ks = k_lo - ((k_lo + (long)(((uintptr_t)p >> 2) & 3)) & 3);
-    const int span = (int)(t0 + LM_TILE + 2 * H + LM_LEAD + 1 - ks);
-    for (int q = tid; 4 * q < span; q += 256) {
-        const long k = ks + 4 * q;
-        float v[4];
-        if (k >= 0 && k + 4 <= n) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(p + k);
-            v[0] = t[0] * gam, v[1] = t[1] * gam, v[2] = t[2] * gam, v[3] = t[3] * gam;
-        } else {
-            for (int e = 0; e < 4; ++e) v[e] = lm_u(p, n, gam, k + e);
-        }
-        for (int e = 0; e < 4; ++e) s_u[4 * q + e] = v[e];
-    }
-    const int ts = T | 1;  // (an odd row stride: the phases of a wave's lanes fall on different banks)
-    for (int i = tid; i < U * T; i += 256) s_tab[(i / T) * ts + i % T] = tab[i];
-    for (int i = tid; i <= 2 * H; i += 256) s_w[i] = win[i];
-    if (tid == 0) s_any = 0;
-    __syncthreads();
-    // m and c over tile +- 2 H; the tile's own samples also feed the stats
-    const bool product = U == 4 && T == 21;  // (uniform)
+    long ks = 0;
     float pk = 0.0f;
     int bad = 0, nm = 0, any = 0;
-    for (int q = tid; q < nc; q += 256) {
-        const long i = t0 - 2 * H + q;
-        float c = 1.0f;
-        if (i >= 0 && i < n) {
-            const float* x = s_u + (i - ks);
-            int nan;
-            const float m = product ? lm_peak<4, 21>(x, s_tab, U, T, ts, nan) : lm_peak<0, 0>(x, s_tab, U, T, ts, nan);
-            const bool over = !nan && m > C;  // (a NaN ceiling compares false: the row is not limited)
-            if (over && m < INFINITY) c = C / m, any = 1;
-            if (i >= t0 && i < t0 + nt) pk = fmaxf(pk, m), bad |= nan, nm += over;
+    for (int ch = 0; ch < C; ++ch) {
+        if (ch > 0) __syncthreads();  // (the last channel's m pass has read s_u)
+        const float* p = wav + rows.off[r + ch];
+        ks = k_lo - ((k_lo + (long)(((uintptr_t)p >> 2) & 3)) & 3);
+        const int span = (int)(t0 + LM_TILE + 2 * H + LM_LEAD + 1 - ks);
+        for (int q = tid; 4 * q < span; q += 256) {
+            const long k = ks + 4 * q;
+            float v[4];
+            if (k >= 0 && k + 4 <= n) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(p + k);
+                v[0] = t[0] * gam, v[1] = t[1] * gam, v[2] = t[2] * gam, v[3] = t[3] * gam;
+            } else {
+                for (int e = 0; e < 4; ++e) v[e] = lm_u(p, n, gam, k + e);
+            }
+            for (int e = 0; e < 4; ++e) s_u[4 * q + e] = v[e];
         }
-        s_a[q] = c;
+        if (ch == 0) {
+            for (int i = tid; i < U * T; i += 256) s_tab[(i / T) * ts + i % T] = tab[i];
+            for (int i = tid; i <= 2 * H; i += 256) s_w[i] = win[i];
+            if (tid == 0) s_any = 0;
+        }
+        __syncthreads();
+        // m and c over tile +- 2 H; the tile's own samples also feed the stats
+        for (int q = tid; q < nc; q += 256) {
+            const long i = t0 - 2 * H + q;
+            float c = ch < C - 1 ? 0.0f : 1.0f;  // (ahead of the last channel s_a holds m so far, 0 outside the row)
+            if (i >= 0 && i < n) {
+                const float* x = s_u + (i - ks);
+                int nan;
+                float m = product ? lm_peak<4, 21>(x, s_tab, U, T, ts, nan) : lm_peak<0, 0>(x, s_tab, U, T, ts, nan);
+                if (ch > 0) {  // (s_a[q] is this thread's own store of the channel before)
+                    const float prev = s_a[q];
+                    nan |= !(prev == prev);
+                    m = fmaxf(m, prev);
+                }
+                if (ch < C - 1) {
+                    c = nan ? NAN : m;
+                } else {
+                    const bool over = !nan && m > CL;  // (a NaN ceiling compares false: the row is not limited)
+                    if (over && m < INFINITY) c = CL / m, any = 1;
+                    if (i >= t0 && i < t0 + nt) pk = fmaxf(pk, m), bad |= nan, nm += over;
+                }
+            }
+            s_a[q] = c;
+        }
+        if (ch < C - 1)
+            for (int e = 0; e < 4; ++e) {
+                const int o = e * 256 + tid;
+                if (o < nt) s_keep[ch * LM_TILE + o] = s_u[t0 - ks + o];
+            }
     }
     if (any) s_any = 1;  // (every writer stores the same value)
     __syncthreads();
@@ -153,27 +178,34 @@ __global__ __launch_bounds__(256) void wave_limit_kernel(const float* __restrict
             float s = 0.0f;
             for (int k = 0; k < W; ++k) s = fmaf(s_w[k], d[k], s);
             const float g = fminf(1.0f - s, cr[e]);
-            s_o[o] = s_u[t0 - ks + o] * g;
+            for (int ch = 0; ch < C - 1; ++ch) s_o[ch * LM_TILE + o] = s_keep[ch * LM_TILE + o] * g;
+            s_o[(C - 1) * LM_TILE + o] = s_u[t0 - ks + o] * g;
             mg = fminf(mg, g), ng += g < 1.0f;
         }
     } else {
         for (int e = 0; e < 4; ++e) {
             const int o = e * 256 + tid;
-            if (o < nt) s_o[o] = s_u[t0 - ks + o];
+            if (o < nt) {
+                for (int ch = 0; ch < C - 1; ++ch) s_o[ch * LM_TILE + o] = s_keep[ch * LM_TILE + o];
+                s_o[(C - 1) * LM_TILE + o] = s_u[t0 - ks + o];
+            }
         }
     }
     s_pk[tid] = pk, s_mg[tid] = mg, s_bad[tid] = bad, s_ng[tid] = ng, s_nm[tid] = nm;
     __syncthreads();
     if (out) {  // quads counted from the 16-byte boundary at or below the tile's first output
-        float* po = out + rows.out_off[r] + t0;
-        const int mis = (int)(((uintptr_t)po >> 2) & 3);
-        for (int q = tid; 4 * q - mis < nt; q += 256) {
-            const int o0 = 4 * q - mis;  // (-3 .. -1 in the first quad of a misaligned tile)
-            if (o0 >= 0 && o0 + 4 <= nt) {
-                *reinterpret_cast<f32x4*>(po + o0) = f32x4{s_o[o0], s_o[o0 + 1], s_o[o0 + 2], s_o[o0 + 3]};
-            } else {
-                for (int e = 0; e < 4; ++e)
-                    if (o0 + e >= 0 && o0 + e < nt) po[o0 + e] = s_o[o0 + e];
+        for (int ch = 0; ch < C; ++ch) {
+            float* po = out + rows.out_off[r + ch] + t0;
+            const float* so = s_o + ch * LM_TILE;
+            const int mis = (int)(((uintptr_t)po >> 2) & 3);
+            for (int q = tid; 4 * q - mis < nt; q += 256) {
+                const int o0 = 4 * q - mis;  // (-3 .. -1 in the first quad of a misaligned tile)
+                if (o0 >= 0 && o0 + 4 <= nt) {
+                    *reinterpret_cast<f32x4*>(po + o0) = f32x4{so[o0], so[o0 + 1], so[o0 + 2], so[o0 + 3]};
+                } else {
+                    for (int e = 0; e < 4; ++e)
+                        if (o0 + e >= 0 && o0 + e < nt) po[o0 + e] = so[o0 + e];
+                }
             }
         }
     }
@@ -185,17 +217,17 @@ __global__ __launch_bounds__(256) void wave_limit_kernel(const float* __restrict
         __syncthreads();
     }
     if (tid == 0) {
-        double* w = ws + ((long)r * ld + blockIdx.x) * 4;
+        double* w = ws + ((long)sg * ld + blockIdx.x) * 4;
         w[0] = s_bad[0] ? (double)NAN : (double)s_pk[0], w[1] = (double)s_mg[0], w[2] = (double)s_ng[0], w[3] = (double)s_nm[0];
     }
 }
 
-// grid R x 256: the tiles of row r folded into its four doubles (an empty row: {0, 1, 0, 0})
-__global__ __launch_bounds__(256) void wave_limit_finish_kernel(lm_rows_t rows, const double* __restrict__ ws, long ld, double* __restrict__ stats) {
+// grid (R / C) x 256: the tiles of signal r (rows [r C, r C + C)) folded into its four doubles (an empty one: {0, 1, 0, 0})
+__global__ __launch_bounds__(256) void wave_limit_finish_kernel(lm_rows_t rows, int C, const double* __restrict__ ws, long ld, double* __restrict__ stats) {
     __shared__ double s_pk[256], s_mg[256], s_ng[256], s_nm[256];
     __shared__ int s_bad[256];
     const int r = blockIdx.x, tid = threadIdx.x;
-    const long nt = ((long)rows.n[r] + LM_TILE - 1) / LM_TILE;
+    const long nt = ((long)rows.n[r * C] + LM_TILE - 1) / LM_TILE;
     double pk = 0.0, mg = 1.0, ng = 0.0, nm = 0.0;
     int bad = 0;
     for (long x = tid; x < nt; x += 256) {
@@ -217,44 +249,54 @@ __global__ __launch_bounds__(256) void wave_limit_finish_kernel(lm_rows_t rows, 
 
 }  // namespace
 
-extern "C" int cbx_wave_limit_f32(const float* wav, const long* row_off, const int* row_len, int R, const float* gain, const double* ceiling, const float* tab, int U,
-                                  int T, const float* win, int H, float* out, const long* out_off, long out_cap, double* stats, double* ws, long ws_cap,
-                                  void* stream) {
-    CBX_REQUIRE(wav && row_off && row_len && ceiling && tab && win && stats && ws, "wave_limit: null pointer");
-    CBX_REQUIRE(!out || out_off, "wave_limit: null pointer (out_off may be NULL only with out)");
-    int rc = cbx_wave_count("wave_limit", row_off, row_len, R);
+// The limiter behind cbx_wave_limit_f32 (C = 1, who = "wave_limit") and cbx_wave_limit_ch_f32 (wave_stereo.hip, which has checked C and the groups' lengths):
+// gain, ceiling and stats have R / C entries, one per signal of C rows; out_off has R.
+int cbx_wave_limit_run(const char* who, const float* wav, const long* row_off, const int* row_len, int R, int C, const float* gain, const double* ceiling,
+                       const float* tab, int U, int T, const float* win, int H, float* out, const long* out_off, long out_cap, double* stats, double* ws, long ws_cap,
+                       void* stream) {
+    CBX_REQUIRE(wav && row_off && row_len && ceiling && tab && win && stats && ws, "%s: null pointer", who);
+    CBX_REQUIRE(!out || out_off, "%s: null pointer (out_off may be NULL only with out)", who);
+    int rc = cbx_wave_count(who, row_off, row_len, R);
     if (rc) return rc;
-    CBX_REQUIRE(U >= 1 && U <= 8, "wave_limit: U = %d outside [1, 8]", U);
-    CBX_REQUIRE(T >= 1 && U * (long)T <= LM_TAB, "wave_limit: T = %d: a table of U T = %ld floats (1 .. %d)", T, U * (long)T, LM_TAB);
-    CBX_REQUIRE(H >= 1 && H <= LM_HMAX, "wave_limit: H = %d outside [1, %d]", H, LM_HMAX);
+    CBX_REQUIRE(U >= 1 && U <= 8, "%s: U = %d outside [1, 8]", who, U);
+    CBX_REQUIRE(T >= 1 && U * (long)T <= LM_TAB, "%s: T = %d: a table of U T = %ld floats (1 .. %d)", who, T, U * (long)T, LM_TAB);
+    CBX_REQUIRE(H >= 1 && H <= LM_HMAX, "%s: H = %d outside [1, %d]", who, H, LM_HMAX);
     lm_rows_t rows = {};  // (entries behind R stay zero: the grids end at R, no kernel reads them)
     cbx_wave_span_t sp, to;
-    if ((rc = cbx_wave_rows("wave_limit", row_off, row_len, R, &rows, &sp))) return rc;
+    if ((rc = cbx_wave_rows(who, row_off, row_len, R, &rows, &sp))) return rc;
     long cnt[CBX_WAVE_MAX_ROWS];
     for (int r = 0; r < R; ++r) {
-        const double c = ceiling[r];
-        CBX_REQUIRE(!(c == c) || (c > 0.0 && c < INFINITY), "wave_limit: row %d has the ceiling %g (a positive finite number, or NaN for a row that is not limited)", r, c);
+        const double c = ceiling[r / C];
+        CBX_REQUIRE(!(c == c) || (c > 0.0 && c < INFINITY), "%s: row %d has the ceiling %g (a positive finite number, or NaN for a row that is not limited)", who, r, c);
         rows.ceil[r] = (float)c;
-        CBX_REQUIRE(!(c == c) || (rows.ceil[r] > 0.0f && rows.ceil[r] < INFINITY), "wave_limit: row %d has the ceiling %g, which is no positive finite float", r, c);
+        CBX_REQUIRE(!(c == c) || (rows.ceil[r] > 0.0f && rows.ceil[r] < INFINITY), "%s: row %d has the ceiling %g, which is no positive finite float", who, r, c);
         if (out) rows.out_off[r] = out_off[r];
         cnt[r] = row_len[r];
     }
-    if (out && (rc = cbx_wave_packed("wave_limit", out_off, cnt, R, out_cap, nullptr, &to))) return rc;  // (the rows' own layout: no sum)
+    if (out && (rc = cbx_wave_packed(who, out_off, cnt, R, out_cap, nullptr, &to))) return rc;  // (the rows' own layout: no sum)
     const long n_max = sp.n_max;
     if (out)
         for (int a = 0; a < R; ++a)
             for (int b = 0; b < R; ++b) {
                 const uintptr_t w0 = (uintptr_t)(wav + row_off[a]), w1 = (uintptr_t)(wav + row_off[a] + row_len[a]);
                 const uintptr_t o0 = (uintptr_t)(out + out_off[b]), o1 = (uintptr_t)(out + out_off[b] + row_len[b]);
-                CBX_REQUIRE(!(row_len[a] > 0 && row_len[b] > 0 && w0 < o1 && o0 < w1), "wave_limit: out row %d overlaps wav row %d (the limiter does not run in place)", b, a);
+                CBX_REQUIRE(!(row_len[a] > 0 && row_len[b] > 0 && w0 < o1 && o0 < w1), "%s: out row %d overlaps wav row %d (the limiter does not run in place)", who, b, a);
             }
     const long ld = (n_max + LM_TILE - 1) / LM_TILE;
-    CBX_REQUIRE(ws_cap >= 4l * R * ld, "wave_limit: workspace of %ld doubles, %d rows of %ld tiles need %ld", ws_cap, R, ld, 4l * R * ld);
+    const int S = R / C;
+    CBX_REQUIRE(ws_cap >= 4l * S * ld, "%s: workspace of %ld doubles, %d rows of %ld tiles need %ld", who, ws_cap, S, ld, 4l * S * ld);
     if (ld > 0) {
-        hipLaunchKernelGGL(wave_limit_kernel, dim3((unsigned)ld, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, gain, tab, U, T, win, H, out, ws, ld);
-        const int e = cbx_check_launch("wave_limit");
+        const auto kernel = C == 2 ? wave_limit_kernel<2> : wave_limit_kernel<1>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)ld, (unsigned)S), dim3(256), 0, (hipStream_t)stream, wav, rows, gain, tab, U, T, win, H, out, ws, ld);
+        const int e = cbx_check_launch(who);
         if (e) return e;
     }
-    hipLaunchKernelGGL(wave_limit_finish_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, (const double*)ws, ld, stats);
-    return cbx_check_launch("wave_limit");
+    hipLaunchKernelGGL(wave_limit_finish_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, rows, C, (const double*)ws, ld, stats);
+    return cbx_check_launch(who);
+}
+
+extern "C" int cbx_wave_limit_f32(const float* wav, const long* row_off, const int* row_len, int R, const float* gain, const double* ceiling, const float* tab, int U,
+                                  int T, const float* win, int H, float* out, const long* out_off, long out_cap, double* stats, double* ws, long ws_cap,
+                                  void* stream) {
+    return cbx_wave_limit_run("wave_limit", wav, row_off, row_len, R, 1, gain, ceiling, tab, U, T, win, H, out, out_off, out_cap, stats, ws, ws_cap, stream);
 }

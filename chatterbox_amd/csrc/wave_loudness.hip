@@ -255,26 +255,34 @@ __device__ __forceinline__ double wl_block_sum(double* sm, int tid, double v) {
     return sm[0];
 }
 
-// grid R x 256: blocks, gates, L, peak and gain of row r.  PUSH (the running meter): ws is the records, ld their stride, rows.n[r] the SEGMENTS of row r so far,
-// and the peak is the record's
-template <bool PUSH>
+// grid (R / C) x 256: blocks, gates, L, peak and gain of signal g = rows [g C, g C + C) of one length (C = 1: row g).  C = 2 (cbx_wave_loudness_ch_f32): the
+// segment energy is e_s = E_(0,s) + E_(1,s), one fp64 add in channel order, and the peak is the larger channel's; C = 1 reads E_s itself.  PUSH (the running
+// meter, C = 1): ws is the records, ld their stride, rows.n[r] the SEGMENTS of row r so far, and the peak is the record's
+template <bool PUSH, int C>
 __global__ __launch_bounds__(256) void wave_loud_row_kernel(cbx_wave_rows_t rows, int R, int hop, wl_target_t target, double ceiling, const double* __restrict__ ws, long ld,
                                                             double* __restrict__ stats, float* __restrict__ gain) {
+    static_assert(!PUSH || C == 1, "the running meter is mono");
     __shared__ double sm[256];
     __shared__ int s_bad[256], s_nan[256];
-    const int r = blockIdx.x, tid = threadIdx.x;
+    const int g = blockIdx.x, r = g * C, tid = threadIdx.x;
     const long n = rows.n[r];
     const long S = PUSH ? n : n / hop, nseg = PUSH ? n : (n + hop - 1) / hop;
     const double* E = PUSH ? ws + (long)r * ld + WL_REC : ws + (4l * R + r) * ld;
     const double* P = ws + (5l * R + r) * ld;  // (not read by PUSH)
+    const auto es = [&](long s) { return C == 1 ? E[s] : E[s] + E[ld + s]; };  // (row r + 1's table follows row r's)
     double pk = 0.0;
     int pnan = 0;
-    long bad = S;  // the first segment whose E is not finite
+    long bad = S;  // the first segment whose energy is not finite
     for (long s = tid; s < nseg; s += 256) {
-        const double v = PUSH ? 0.0 : P[s];
+        double v = PUSH ? 0.0 : P[s];
         pnan |= !(v == v);
+        if (C == 2) {
+            const double v1 = P[ld + s];
+            pnan |= !(v1 == v1);
+            v = fmax(v, v1);
+        }
         pk = fmax(pk, v);
-        if (s < S && !wl_finite(E[s])) bad = s < bad ? s : bad;
+        if (s < S && !wl_finite(es(s))) bad = s < bad ? s : bad;
     }
     sm[tid] = pk, s_bad[tid] = (int)bad, s_nan[tid] = pnan;
     __syncthreads();
@@ -293,7 +301,7 @@ __global__ __launch_bounds__(256) void wave_loud_row_kernel(cbx_wave_rows_t rows
     // absolute gate
     double sum = 0.0, num = 0.0;
     for (long j = tid; j < nb; j += 256) {
-        const double z = j + 3 >= bad ? (double)NAN : (E[j] + E[j + 1] + E[j + 2] + E[j + 3]) / den;
+        const double z = j + 3 >= bad ? (double)NAN : (es(j) + es(j + 1) + es(j + 2) + es(j + 3)) / den;
         const double l = -0.691 + 10.0 * log10(z);
         if (l >= -70.0) sum += z, num += 1.0;
     }
@@ -304,7 +312,7 @@ __global__ __launch_bounds__(256) void wave_loud_row_kernel(cbx_wave_rows_t rows
         const double gate = -0.691 + 10.0 * log10(sum / num) - 10.0;
         double sum2 = 0.0, num2 = 0.0;
         for (long j = tid; j < nb; j += 256) {
-            const double z = j + 3 >= bad ? (double)NAN : (E[j] + E[j + 1] + E[j + 2] + E[j + 3]) / den;
+            const double z = j + 3 >= bad ? (double)NAN : (es(j) + es(j + 1) + es(j + 2) + es(j + 3)) / den;
             const double l = -0.691 + 10.0 * log10(z);
             if (l >= -70.0 && l > gate) sum2 += z, num2 += 1.0;
         }
@@ -313,15 +321,15 @@ __global__ __launch_bounds__(256) void wave_loud_row_kernel(cbx_wave_rows_t rows
         if (num2 > 0.0) L = -0.691 + 10.0 * log10(sum2 / num2), used = num2;
     }
     if (tid == 0) {
-        const double t = target.t[r];
-        double g = 1.0;
+        const double t = target.t[g];
+        double gn = 1.0;
         if (t == t) {
-            g = pow(10.0, (t - L) / 20.0);
-            if (ceiling > 0.0 && peak * g > ceiling) g = ceiling / peak;
-            if (!wl_finite(L) || !wl_finite(peak) || !wl_finite(g)) g = 1.0;
+            gn = pow(10.0, (t - L) / 20.0);
+            if (ceiling > 0.0 && peak * gn > ceiling) gn = ceiling / peak;
+            if (!wl_finite(L) || !wl_finite(peak) || !wl_finite(gn)) gn = 1.0;
         }
-        stats[4 * r] = L, stats[4 * r + 1] = peak, stats[4 * r + 2] = g, stats[4 * r + 3] = used;
-        gain[r] = (float)g;
+        stats[4 * g] = L, stats[4 * g + 1] = peak, stats[4 * g + 2] = gn, stats[4 * g + 3] = used;
+        gain[g] = (float)gn;
     }
 }
 
@@ -390,35 +398,43 @@ void wl_powers(const wl_coef_t& k, int hop, wl_pow_t* pw) {
 
 }  // namespace
 
-extern "C" int cbx_wave_loudness_f32(const float* wav, const long* row_off, const int* row_len, int R, const double* coef, int hop, const double* target,
-                                     double ceiling, double* stats, float* gain, double* ws, long ws_cap, void* stream) {
+// The meter behind cbx_wave_loudness_f32 (C = 1, who = "wave_loudness") and cbx_wave_loudness_ch_f32 (wave_stereo.hip, which has checked C and the groups'
+// lengths): the per-row phases over all R rows, then the row step once per signal of C rows.  target, stats, gain: R / C entries.
+int cbx_wave_loudness_run(const char* who, const float* wav, const long* row_off, const int* row_len, int R, int C, const double* coef, int hop, const double* target,
+                          double ceiling, double* stats, float* gain, double* ws, long ws_cap, void* stream) {
     cbx_wave_rows_t rows;
     cbx_wave_span_t sp;
-    const int rc = cbx_wave_rows("wave_loudness", row_off, row_len, R, &rows, &sp);
+    const int rc = cbx_wave_rows(who, row_off, row_len, R, &rows, &sp);
     if (rc) return rc;
-    CBX_REQUIRE(wav && coef && target && stats && gain && ws, "wave_loudness: null pointer");
-    CBX_REQUIRE(hop >= 1, "wave_loudness: hop = %d (a tenth of a second in samples, at least 1)", hop);
+    CBX_REQUIRE(wav && coef && target && stats && gain && ws, "%s: null pointer", who);
+    CBX_REQUIRE(hop >= 1, "%s: hop = %d (a tenth of a second in samples, at least 1)", who, hop);
     wl_coef_t k;
-    if (const int e = wl_coefs("wave_loudness", coef, &k)) return e;
+    if (const int e = wl_coefs(who, coef, &k)) return e;
     const long nseg = (sp.n_max + hop - 1) / hop;
-    CBX_REQUIRE(ws_cap >= 6l * R * nseg, "wave_loudness: workspace of %ld doubles, %d rows of %ld segments need %ld", ws_cap, R, nseg, 6l * R * nseg);
+    CBX_REQUIRE(ws_cap >= 6l * R * nseg, "%s: workspace of %ld doubles, %d rows of %ld segments need %ld", who, ws_cap, R, nseg, 6l * R * nseg);
     wl_target_t tg;
-    for (int r = 0; r < CBX_WAVE_MAX_ROWS; ++r) tg.t[r] = r < R ? target[r] : (double)NAN;
+    for (int r = 0; r < CBX_WAVE_MAX_ROWS; ++r) tg.t[r] = r < R / C ? target[r] : (double)NAN;
     if (nseg > 0) {
         const long gx = (nseg + 3) / 4;
-        CBX_REQUIRE(gx <= 0x7fffffffl, "wave_loudness: a row of %ld samples is too long for one launch", sp.n_max);
+        CBX_REQUIRE(gx <= 0x7fffffffl, "%s: a row of %ld samples is too long for one launch", who, sp.n_max);
         wl_pow_t pw;
         wl_powers(k, hop, &pw);
         hipLaunchKernelGGL(wave_loud_seg_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, R, k, pw, hop, 0, ws, nseg);
-        int e = cbx_check_launch("wave_loudness");
+        int e = cbx_check_launch(who);
         if (e) return e;
         hipLaunchKernelGGL(wave_loud_chain_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, pw, hop, ws, nseg);
-        if ((e = cbx_check_launch("wave_loudness"))) return e;
+        if ((e = cbx_check_launch(who))) return e;
         hipLaunchKernelGGL(wave_loud_seg_kernel, dim3((unsigned)gx, (unsigned)R), dim3(256), 0, (hipStream_t)stream, wav, rows, R, k, pw, hop, 1, ws, nseg);
-        if ((e = cbx_check_launch("wave_loudness"))) return e;
+        if ((e = cbx_check_launch(who))) return e;
     }
-    hipLaunchKernelGGL(wave_loud_row_kernel<false>, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, rows, R, hop, tg, ceiling, (const double*)ws, nseg, stats, gain);
-    return cbx_check_launch("wave_loudness");
+    const auto row_kernel = C == 2 ? wave_loud_row_kernel<false, 2> : wave_loud_row_kernel<false, 1>;
+    hipLaunchKernelGGL(row_kernel, dim3((unsigned)(R / C)), dim3(256), 0, (hipStream_t)stream, rows, R, hop, tg, ceiling, (const double*)ws, nseg, stats, gain);
+    return cbx_check_launch(who);
+}
+
+extern "C" int cbx_wave_loudness_f32(const float* wav, const long* row_off, const int* row_len, int R, const double* coef, int hop, const double* target,
+                                     double ceiling, double* stats, float* gain, double* ws, long ws_cap, void* stream) {
+    return cbx_wave_loudness_run("wave_loudness", wav, row_off, row_len, R, 1, coef, hop, target, ceiling, stats, gain, ws, ws_cap, stream);
 }
 
 extern "C" int cbx_wave_loudness_push_f32(const float* wav, const long* row_off, const int* row_len, const long* n0, int R, const double* coef, int hop,
@@ -463,7 +479,7 @@ extern "C" int cbx_wave_loudness_push_f32(const float* wav, const long* row_off,
                            rec, rec_ld);
         if ((e = cbx_check_launch("wave_loudness_push"))) return e;
     }
-    hipLaunchKernelGGL(wave_loud_row_kernel<true>, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, segs, R, hop, tg, ceiling, (const double*)rec, rec_ld, stats, gain);
+    hipLaunchKernelGGL((wave_loud_row_kernel<true, 1>), dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, segs, R, hop, tg, ceiling, (const double*)rec, rec_ld, stats, gain);
     return cbx_check_launch("wave_loudness_push");
 }
 

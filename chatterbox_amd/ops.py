@@ -4,6 +4,7 @@ torch is used only as the allocator / stream provider; every function below laun
 from libcbx_hip.so and raises if the library is unavailable (no eager fallback).
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -2012,6 +2013,151 @@ def wave_limit(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None):
     else:
         out = list(out)
     return out, _wave_limit_launch(rows, ceil, gain, look, out)
+
+
+# ----------------------------------------------------------------------------- stereo dialogue: panned mix, channel-summed meter, linked limiter (wave_stereo.hip)
+def check_pan(value, name="pan"):
+    """A stereo position as a float: -1 is hard left, 0 the centre, +1 hard right.  A bool or a non-number is a TypeError, a value that is not finite or lies
+    outside [-1, 1] a ValueError -- raised before anything is launched."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise TypeError(f"{name}: expected a number in [-1, 1] (-1 left, 0 centre, +1 right), got {type(value).__name__}")
+    value = float(value)
+    if not math.isfinite(value) or not -1.0 <= value <= 1.0:
+        raise ValueError(f"{name} = {value}: a stereo position is a finite number in [-1, 1] (-1 left, 0 centre, +1 right)")
+    return value
+
+
+def pan_gains(p):
+    """The constant-power pan law: position p in [-1, 1] -> (left, right) gains as Python floats that hold fp32 values.  theta = (p + 1) pi / 4, left = cos theta,
+    right = sin theta, evaluated in fp64 and rounded to fp32 once; left^2 + right^2 = 1, so a voice keeps its power wherever it sits.  By construction, not by
+    trusting cos(pi / 2): p = -1 is exactly (1, 0), p = +1 exactly (0, 1), and p = 0 gives the SAME float on both sides (the fp32 of sqrt(1 / 2))."""
+    import numpy as np
+    p = check_pan(p, "pan_gains: p")
+    if p == -1.0:
+        return 1.0, 0.0
+    if p == 1.0:
+        return 0.0, 1.0
+    if p == 0.0:
+        c = float(np.float32(math.sqrt(0.5)))
+        return c, c
+    th = (p + 1.0) * math.pi / 4.0
+    return float(np.float32(math.cos(th))), float(np.float32(math.sin(th)))
+
+
+def wave_pan_mix(rows, starts, flags, pan, out, gain=None, gain_idx=None, fade=240, accumulate=False):
+    """cbx_wave_pan_mix_f32 on the current stream: wave_mix into TWO planes.  rows, starts, flags, gain, gain_idx, fade, accumulate: wave_mix's.  pan: R pairs
+    (left gain, right gain) of finite numbers (pan_gains gives the constant-power pair of a position).  out: a contiguous (2, n) fp32 tensor on the rows' device,
+    not the rows' allocation: out[0] is the left plane, out[1] the right.  Row r times its balance gain and fades, times its left / right gain, ADDED into both
+    planes at starts[r]; the covering rows are summed in ascending r per plane (include/cbx.h states the definition).  Every sample of both planes is written
+    (+0.0 where no row is) unless accumulate.  One launch, nothing is synchronised.  Returns out."""
+    rows = list(rows)
+    R = len(rows)
+    starts, flags = [int(s) for s in starts], [int(f) for f in flags]
+    if len(starts) != R or len(flags) != R or len(pan) != R:
+        raise ValueError(f"wave_pan_mix: {len(starts)} starts, {len(flags)} flags and {len(pan)} pan pairs for {R} rows")
+    if any(len(g) != 2 for g in pan):
+        raise ValueError("wave_pan_mix: pan holds one (left, right) pair per row")
+    if gain_idx is not None and len(gain_idx) != R:
+        raise ValueError(f"wave_pan_mix: {len(gain_idx)} gain indices for {R} rows")
+    assert out.dim() == 2 and out.shape[0] == 2 and out.is_contiguous(), "wave_pan_mix: out is a contiguous (2, n) fp32 tensor on the rows' device"
+    _f32(out, "out")
+    n = int(out.shape[1])
+    if _all_empty(rows):  # (such rows may have no allocation to point at)
+        if not 1 <= R <= WAVE_JOIN_MAX_ROWS or any(not 0 <= s <= n for s in starts):
+            raise ValueError(f"wave_pan_mix: {R} empty rows at {starts} of an output of {n}")
+        return out if accumulate else out.zero_()
+    base, offs, lens = _wave_rows(rows, "wave_pan_mix")
+    dev = rows[0].device
+    assert out.device == dev, "wave_pan_mix: out is a contiguous (2, n) fp32 tensor on the rows' device"
+    G = 0
+    if gain is not None:
+        assert gain.dtype == torch.float32 and gain.dim() == 1 and gain.is_contiguous() and gain.device == dev, "wave_pan_mix: gain is (G,) fp32 on the rows' device"
+        G = int(gain.numel())
+    st, fl = (ctypes.c_long * R)(*starts), (ctypes.c_int * R)(*flags)
+    pg = (ctypes.c_float * (2 * R))(*[float(v) for g in pan for v in g])
+    gi = None if gain_idx is None else (ctypes.c_int * R)(*[int(g) for g in gain_idx])
+    check(lib.cbx_wave_pan_mix_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(st), ctypes.addressof(fl), ctypes.addressof(pg), R, _p(gain), G,
+                                   None if gi is None else ctypes.addressof(gi), _p(join_ramp(fade, dev)), int(fade), _p(out), n, n, int(bool(accumulate)), _stream()),
+          "cbx_wave_pan_mix_f32")
+    return out
+
+
+def _channel_groups(rows, channels, who):
+    """the rows of a linked entry: a whole number of signals of `channels` rows of one length each"""
+    rows, C = list(rows), int(channels)
+    if C not in (1, 2):
+        raise ValueError(f"{who}: channels = {channels} outside {{1, 2}}")
+    if len(rows) % C:
+        raise ValueError(f"{who}: {len(rows)} rows are no whole number of signals of {C} channels")
+    if any(rows[k].numel() != rows[k - k % C].numel() for k in range(len(rows))):
+        raise ValueError(f"{who}: the channels of a signal have different lengths")
+    return rows, C
+
+
+def wave_loudness_ch(rows, target=None, ceiling=1.0, fs=WAVE_IN_RATE, channels=2):
+    """cbx_wave_loudness_ch_f32 on the current stream: wave_loudness for len(rows) / channels signals of `channels` (1 or 2) consecutive rows of one length each --
+    the BS.1770-4 loudness of the channels' SUMMED block energies (weights 1: left and right), the larger channel's sample peak, ONE gain per signal.  target:
+    None (measure only), a number, or one number / None per SIGNAL; ceiling: wave_loudness's.  Returns (stats (S, 4) float64, gain (S,) float32) on the device,
+    S = len(rows) / channels; channels=1 is wave_loudness bit for bit.  Nothing is synchronised (include/cbx.h states the definition)."""
+    rows, C = _channel_groups(rows, channels, "wave_loudness_ch")
+    base, offs, lens = _wave_rows(rows, "wave_loudness_ch")
+    R, dev, f = len(lens), rows[0].device, loudness_filter(fs)
+    S = R // C
+    if target is None or not isinstance(target, (list, tuple)):
+        target = [target] * S
+    if len(target) != S:
+        raise ValueError(f"wave_loudness_ch: {len(target)} targets for {S} signals")
+    tg = (ctypes.c_double * S)(*[float("nan") if t is None else float(t) for t in target])
+    coef = (ctypes.c_double * 10)(*f["coef"].tolist())
+    stats = torch.empty(S, 4, dtype=torch.float64, device=dev)
+    gain = torch.empty(S, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(1, 6 * R * -(-max(lens) // f["hop"])), dtype=torch.float64, device=dev)
+    check(lib.cbx_wave_loudness_ch_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, C, ctypes.addressof(coef), f["hop"], ctypes.addressof(tg),
+                                       0.0 if ceiling is None else float(ceiling), _p(stats), _p(gain), _p(ws), ws.numel(), _stream()), "cbx_wave_loudness_ch_f32")
+    return stats, gain
+
+
+def wave_limit_ch(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None, channels=2):
+    """cbx_wave_limit_ch_f32 on the current stream: wave_limit with LINKED channels, for len(rows) / channels signals of `channels` (1 or 2) consecutive rows of one
+    length each: the per-sample peak is the larger channel's, ONE gain envelope multiplies both channels, so a peak on one side does not move the image.
+    ceilings_db: None (measure only: the stats alone, nothing is written), a number of dBTP, or one number / None per SIGNAL (None: the signal comes back as
+    x * gain); gain: an (S,) fp32 device tensor (wave_loudness_ch's) or None.  Returns (out_rows, stats): out_rows in the layout of `rows` (None when measuring only),
+    stats (S, 4) float64 {true peak over the channels of x * gain, min g, samples with g < 1, samples over the ceiling}.  channels=1 is wave_limit bit for bit.
+    Two launches, nothing is synchronised."""
+    rows, C = _channel_groups(rows, channels, "wave_limit_ch")
+    S = len(rows) // C
+    measure = ceilings_db is None and out is None
+    if ceilings_db is None or not isinstance(ceilings_db, (list, tuple)):
+        ceilings_db = [ceilings_db] * S
+    if len(ceilings_db) != S:
+        raise ValueError(f"wave_limit_ch: {len(ceilings_db)} ceilings for {S} signals")
+    ceil = [None if c is None else 10.0 ** (float(c) / 20.0) for c in ceilings_db]
+    limit_window(look)
+    if _all_empty(rows):
+        outs = None if measure else (list(out) if out is not None else [torch.empty(0, dtype=torch.float32, device=w.device) for w in rows])
+        return outs, _empty_limit_stats(rows[:S])
+    base, offs, lens = _wave_rows(rows, "wave_limit_ch")
+    R, dev, f = len(lens), rows[0].device, true_peak_filter()
+    if out is None and not measure:
+        lo = min(a for a, n in zip(offs, lens) if n)
+        buf = torch.empty(max(a + n for a, n in zip(offs, lens) if n) - lo, dtype=torch.float32, device=dev)
+        out = [buf[a - lo: a - lo + n] if n else buf[:0] for a, n in zip(offs, lens)]
+    tab, win = _limit_tables(look, dev)
+    cl = (ctypes.c_double * S)(*[float("nan") if c is None else float(c) for c in ceil])
+    if gain is not None:
+        assert gain.dtype == torch.float32 and gain.numel() == S and gain.is_contiguous() and gain.device == dev, "wave_limit_ch: gain is (S,) fp32 on the rows' device"
+    obase, ooffs, cap = None, None, 0
+    if out is not None:
+        out = list(out)
+        obase, o, olens = _wave_rows(out, "wave_limit_ch: out")
+        if list(olens) != list(lens):
+            raise ValueError("wave_limit_ch: the rows of out have other lengths than the rows")
+        ooffs, cap = ctypes.addressof(o), max((a + n for a, n in zip(o, olens)), default=0)
+    stats = torch.empty(S, 4, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, 4 * S * -(-max(lens) // 1024)), dtype=torch.float64, device=dev)
+    check(lib.cbx_wave_limit_ch_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, C, _p(gain), ctypes.addressof(cl), _p(tab), f["U"], f["T"], _p(win), look,
+                                    obase, ooffs, cap, _p(stats), _p(ws), ws.numel(), _stream()), "cbx_wave_limit_ch_f32")
+    return out, stats
 
 
 # ----------------------------------------------------------------------------- music bed: speech over a background that ducks while someone talks (wave_duck.hip)

@@ -1188,6 +1188,65 @@ int cbx_wave_limit_f32(const float* wav, const long* row_off, const int* row_len
 int cbx_wave_mix_f32(const float* wav, const long* row_off, const int* row_len, const long* start, const int* flags, int R, const float* gain, int G,
                      const int* gain_idx, const float* ramp, int fade, float* out, long out_len, int accumulate, void* stream);
 
+/* ---- stereo dialogue: the rows of a conversation summed into TWO planes, each voice at a place between left and right, then metered and limited as ONE
+ * two-channel signal (added after ABI v16 without a version step: new functions only).  The reference has no counterpart: it returns one mono utterance of one
+ * voice (tts.py:272, mtl_tts.py:352, tts_turbo.py:320).  Two steps cannot be had from the mono entries run once per channel: BS.1770-4 gates on the SUM of the
+ * channels' block energies, and a limiter must apply ONE gain envelope to both channels, or a peak on the left moves the image.
+ * cbx_wave_pan_mix_f32: cbx_wave_mix_f32 with two output planes, out (left) and out + plane_stride (right), out_len floats each, plane_stride >= out_len.  Rows,
+ * start, flags, gain, gain_idx, ramp, fade, accumulate: the mono entry's.  pan: R x 2 HOST floats, pan[2 r] / pan[2 r + 1] the left / right gain of row r
+ * (finite; the constant-power law is the caller's, ops.pan_gains), by value to the kernel like the other host arrays.
+ * Definition, in fp32, for every p in [0, out_len), the rows that cover p taken in ASCENDING r -- the order of summation:
+ *   1. - 3. of cbx_wave_mix_f32 give s_r: the balance gain, then the fade-in, else the fade-out.
+ *   4. t_c = s_r * pan[r][c] for c = 0, 1: one rounded multiply per plane.
+ *   5. acc_c = plane_c[p] when `accumulate` is set, else the first covering row's t_c itself; every further row: acc_c = acc_c + t_c, one rounded add each.
+ *      Products and sums are rounded separately: nothing is fused.
+ *   6. plane_c[p] = acc_c.  A sample that no row covers is written as +0.0 in both planes when accumulate == 0 and is not written when accumulate == 1.
+ * Properties: pan[r] = {1, 1} for every row gives cbx_wave_mix_f32's bits in both planes (x * 1 is x).  Equal left and right gains give L == R bit for bit.  A
+ * gain of 0 gives a plane of zeros (of either sign) for finite rows.  Rows given in groups over several launches behave as in the mono entry.  The result does
+ * not depend on the grid, the tile a sample falls into, or the alignment of wav, a row, out or the right plane.  There are no atomics.  wav is only read; neither
+ * plane may overlap it.  Nothing outside the two planes is written.
+ * One launch reads every source sample once and writes both planes: one workgroup of 256 threads per tile of 4096 outputs per plane (wave_stereo.hip), counted
+ * from the 16-byte boundary at or below out, both planes' sums in registers in row order; 16-byte accesses where the plane's own address allows, 4-byte accesses
+ * at the ragged ends and in a plane that sits off the boundary.  None, rc 0, when out_len == 0.  Nothing synchronises the host.
+ * -22 before any launch, nothing written: every refusal of cbx_wave_mix_f32, a null pan, a pan gain that is not finite, plane_stride < out_len, a plane
+ * overlapping a non-empty row. */
+int cbx_wave_pan_mix_f32(const float* wav, const long* row_off, const int* row_len, const long* start, const int* flags, const float* pan, int R, const float* gain,
+                         int G, const int* gain_idx, const float* ramp, int fade, float* out, long plane_stride, long out_len, int accumulate, void* stream);
+/* cbx_wave_loudness_ch_f32: cbx_wave_loudness_f32 for R / C signals of C consecutive rows each, C in {1, 2}: rows [g C, g C + C) are the channels of signal g and
+ * have ONE length.  target: R / C HOST doubles; stats (R / C, 4) and gain (R / C), per signal.
+ * Definition: the K-weighting, the segments and every segment energy E_(c,s) of channel c are cbx_wave_loudness_f32's, bit for bit -- the same three phases over
+ * all R rows: one source, one arithmetic.  The row step runs once per signal:
+ *   e_s = E_(0,s) + E_(1,s): one fp64 add in channel order, channel weights 1 (L and R of BS.1770-4); C = 1: e_s = E_(0,s) itself.
+ *   z_j = (e_j + e_(j+1) + e_(j+2) + e_(j+3)) / (4 hop), then l_j, both gates, L and the gain exactly as written for cbx_wave_loudness_f32; a signal's segments
+ *   from the first one whose e_s is not finite on count as NaN.
+ *   Peak: the maximum over the channels of max |x| (NaN when a channel holds one); the ceiling limits peak g as there.
+ * Properties: C = 1 is cbx_wave_loudness_f32 bit for bit.  Two equal channels read the mono loudness + 10 log10 2 (3.01 LU) up to rounding.  Swapped channels
+ * give identical bits (an fp64 add commutes).  Fixed reduction order, no floating-point atomics.  Four launches, nothing synchronises the host.
+ * ws: device workspace of ws_cap >= 6 * R * ceil(max_r n_r / hop) doubles (not NULL).
+ * -22 before any launch, nothing written: every refusal of cbx_wave_loudness_f32, C outside {1, 2}, R no multiple of C, two channels of one signal of different
+ * lengths. */
+int cbx_wave_loudness_ch_f32(const float* wav, const long* row_off, const int* row_len, int R, int C, const double* coef, int hop, const double* target,
+                             double ceiling, double* stats, float* gain, double* ws, long ws_cap, void* stream);
+/* cbx_wave_limit_ch_f32: cbx_wave_limit_f32 with LINKED channels, for R / C signals of C consecutive rows of one length, C in {1, 2}.  gain: R / C device floats
+ * (NULL: 1), ceiling: R / C HOST doubles (NaN: the signal is not limited), stats (R / C, 4): ONE pre-gain, ONE ceiling and one stats row per signal.  out_off:
+ * R HOST longs, one per row.  tab, U, T, win, H: the mono entry's.
+ * Definition, the steps of cbx_wave_limit_f32:
+ *   1. - 2. per channel: u_c[i] = x_c[i] * gamma, y_c the oversampled u_c.
+ *   3. m[i] = the maximum over the channels of the per-channel m_c[i]; NaN when any of them is.
+ *   4. - 6. once per signal: c[i], the sliding minimum a[i], the smoothed g[i].
+ *   7. out_c[i] = u_c[i] * g[i] per channel: both channels under the same envelope, the image does not move.
+ * stats per signal: {max_i m[i], min_i g[i], the samples with g < 1, the samples with m > C32}.
+ * Properties: C = 1 is cbx_wave_limit_f32 bit for bit.  Two equal channels return the mono limiter's output in both planes, bit for bit.  A peak in one channel
+ * lowers the other by the same g.  The bound on |out_c| and the locality of cbx_wave_limit_f32 hold per channel.
+ * One workgroup per tile of 1024 samples of a signal (wave_limit.hip, the mono kernel with C as a template parameter): the channels pass through the staging
+ * buffer one after the other, the running maximum of m and every channel's own tile of u wait in LDS (8 KiB more for two channels); the fold launch is the mono
+ * entry's.  Two launches, nothing synchronises the host.
+ * ws: device workspace of ws_cap >= 4 * (R / C) * ceil(max_r n_r / 1024) doubles (not NULL).
+ * -22 before any launch, nothing written: every refusal of cbx_wave_limit_f32, C outside {1, 2}, R no multiple of C, two channels of one signal of different
+ * lengths. */
+int cbx_wave_limit_ch_f32(const float* wav, const long* row_off, const int* row_len, int R, int C, const float* gain, const double* ceiling, const float* tab, int U,
+                          int T, const float* win, int H, float* out, const long* out_off, long out_cap, double* stats, double* ws, long ws_cap, void* stream);
+
 /* ---- music bed: lay the finished speech over a background and pull the background down while someone talks (added after ABI v16 without a version step: new
  * functions only).  The reference has no counterpart: it returns one utterance of one voice as the vocoder left it (tts.py:272, mtl_tts.py:352,
  * tts_turbo.py:320).  All signals are 24 kHz mono fp32.  Rows: R in [1, 64]; speech row r = s_len[r] floats at speech + s_off[r], its bed source b_len[r] floats
