@@ -826,33 +826,69 @@ class _Finish:
         """A device waveform as the reference returns it: CPU float32 (1, n), watermarked if a watermarker is loaded.
         fmt (ops.check_format's dict; None: exactly the above): the (1, n) CPU tensor at fmt's rate in fmt's encoding.  Without a watermarker the engine was given the
         format and `wav` is the converted audio already (converted=True): one copy to the host.  With one -- or when the caller kept the format from the engine
-        (converted=False: generate_long) -- `wav` is 24 kHz fp32: it is watermarked on the host as ever, then converted on the device (_to_format).
-        loud (a LUFS target; generate_long): the 24 kHz waveform is normalised as ONE signal first (_to_loudness); the watermark follows the gain, the conversion
-        the watermark.  peak (a ceiling in dBTP; generate_long): the true-peak limiter follows that gain in the same visit to the device (_to_loudness).
-        bed ((plan, source) of _bed_source; generate_long): the music bed is laid under the waveform in that same visit, ahead of the meter: level and ceiling
-        hold for speech plus bed."""
+        (converted=False: generate_long) -- `wav` is 24 kHz fp32 and goes through the chain (_chain): it is watermarked on the host as ever, then converted on the device.
+        loud (a LUFS target), peak (a ceiling in dBTP), bed ((plan, source) of _bed_source) -- generate_long's: the chain's steps ahead of the watermark, over the
+        24 kHz waveform as ONE signal, in the same visit to the device."""
         if fmt is not None and converted and self.watermarker is None:
             return wav.detach().cpu().unsqueeze(0)
-        wav = wav.detach().float().cpu()
-        if bed is not None:
-            wav = self._to_loudness(wav, loud, peak, bed)
-        elif peak is not None:
-            wav = self._to_loudness(wav, loud, peak)
-        elif loud is not None:
-            wav = self._to_loudness(wav, loud)
-        if self.watermarker is not None:
-            wav = torch.from_numpy(self.watermarker.apply_watermark(wav.numpy(), sample_rate=self.sr))
-        return (wav if fmt is None else self._to_format(wav, fmt)).unsqueeze(0)
+        return self._chain(wav.detach().float(), fmt, loud, peak, bed).unsqueeze(0)
 
     def _device_scope(self):
         dev = torch.device(self.engine.dev)
         return dev, (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext())
 
-    def _to_format(self, wav, fmt):
-        """A 24 kHz fp32 waveform on the host -> the device, ONE ops.wave_format launch, back to the host (1-D)"""
+    def _chain(self, w, fmt=None, loud=None, peak=None, bed=None):
+        """THE finishing chain of generate_long and generate_dialogue.  w: 24 kHz fp32, 1-D or planar (2, n), on the host or on the device.  In this order:
+          the bed (bed: (plan, source) of _bed_source; _lay_bed; mono only) -- the meter and the limiter then see speech plus bed;
+          loudness and true peak over the whole as ONE signal.  With a ceiling (peak, dBTP) the meter gives the FULL gain to the target (loud, LUFS; no gain
+            without one) and the limiter takes it as its pre-gain; without a ceiling the gain is capped at a sample peak of 1.0 and applied in place.  Mono:
+            ops.wave_loudness, ops.wave_limit, ops.wave_normalize.  Two planes, linked: ops.wave_loudness_ch, ops.wave_limit_ch, and ops.wave_gain with the one
+            gain for both.  The stats stay on the device as engine.last_loudness / engine.last_limit;
+          the watermark on the host, per channel, if a watermarker is loaded;
+          the format (_to_format) and the one copy to the host; then model.last_bed (_take_bed).
+        Nothing is uploaded before a step needs the device, and what is there stays there: without a watermarker a call makes ONE visit, with one the round trip
+        to the host lies between the limiter and the format.  Returns the CPU tensor, 1-D or (2, n') as w was."""
+        stereo = w.dim() == 2
+        rows = (lambda t: [t[0], t[1]]) if stereo else (lambda t: [t])
+        if bed is not None or loud is not None or peak is not None:
+            dev, scope = self._device_scope()
+            with scope:
+                w = w.to(dev).contiguous()
+                if bed is not None:
+                    w = self._lay_bed(w, *bed)
+                if peak is not None:
+                    pre = None
+                    if loud is not None:
+                        self.engine.last_loudness, pre = (ops.wave_loudness_ch if stereo else ops.wave_loudness)(rows(w), [float(loud)], None)
+                    if stereo:
+                        lim = torch.empty_like(w)
+                        _, self.engine.last_limit = ops.wave_limit_ch(rows(w), [float(peak)], gain=pre, out=rows(lim))
+                        w = lim
+                    else:
+                        out, self.engine.last_limit = ops.wave_limit(rows(w), [float(peak)], gain=pre)
+                        w = out[0]
+                elif loud is not None and stereo:
+                    self.engine.last_loudness, g1 = ops.wave_loudness_ch(rows(w), [float(loud)], 1.0)
+                    ops.wave_gain(rows(w), g1.repeat(2))
+                elif loud is not None:
+                    self.engine.last_loudness = ops.wave_normalize(rows(w), [float(loud)])
+        if self.watermarker is not None:
+            mark = lambda x: torch.from_numpy(self.watermarker.apply_watermark(x, sample_rate=self.sr))
+            host = w.cpu().numpy()
+            w = torch.stack([mark(host[c]) for c in range(2)]) if stereo else mark(host)
+        w = w.cpu() if fmt is None else self._to_format(w, fmt)
+        if bed is not None:
+            self._take_bed()
+        return w
+
+    def _to_format(self, w, fmt):
+        """The chain's format step: 24 kHz fp32, 1-D or planar (2, n), on the host or already on the device -> ONE ops.wave_format launch (the planes as two
+        rows), then the copy to the host"""
         dev, scope = self._device_scope()
         with scope:
-            return ops.wave_format([wav.to(dev)], fmt)[0].cpu()
+            w = w.to(dev)
+            out = ops.wave_format([w[0], w[1]] if w.dim() == 2 else [w], fmt)
+            return (torch.stack(out) if w.dim() == 2 else out[0]).cpu()
 
     def _bed_source(self, plan):
         """The source of a music bed (plan: ops.check_bed's) at 24 kHz mono, brought there as a voice prompt is: a float32 host array (audio_in = "host":
@@ -892,34 +928,6 @@ class _Finish:
         g, ducked, frames, peak, ls, lb = self._bed_numbers.cpu().tolist()
         self._bed_numbers = None
         self.last_bed = dict(gain=g, speech_lufs=ls, bed_lufs=lb, ducked=int(ducked), frames=int(frames), peak=peak)
-
-    def _to_loudness(self, wav, target, peak=None, bed=None):
-        """A 24 kHz fp32 waveform on the host -> the device, ops.wave_normalize to `target` LUFS (sample peak limited to 1.0), back to the host (1-D); the stats stay
-        on the device as engine.last_loudness.  peak (dBTP): one upload, the meter with the FULL gain to the target (none when target is None), ops.wave_limit
-        with that gain to the ceiling, one download; engine.last_limit keeps the limiter's stats.  bed ((plan, source)): _lay_bed first, on the same upload; the
-        meter and the limiter then see speech plus bed (neither a target nor a ceiling: the sum comes back as it is)."""
-        dev, scope = self._device_scope()
-        with scope:
-            w = wav.to(dev).contiguous()
-            if bed is not None:
-                w = self._lay_bed(w, *bed)
-                if peak is None:
-                    if target is not None:
-                        self.engine.last_loudness = ops.wave_normalize([w], [float(target)])
-                    w = w.cpu()
-                    self._take_bed()
-                    return w
-            if peak is not None:
-                gain = None
-                if target is not None:
-                    self.engine.last_loudness, gain = ops.wave_loudness([w], [float(target)], None)
-                out, self.engine.last_limit = ops.wave_limit([w], [float(peak)], gain=gain)
-                res = out[0].cpu()
-                if bed is not None:
-                    self._take_bed()
-                return res
-            self.engine.last_loudness = ops.wave_normalize([w], [float(target)])
-            return w.cpu()
 
     def _stream_pieces(self, rounds, fmt):
         """The pieces of generate_stream from an engine stream's rounds: (1, n) CPU tensors, empty ones left out.  With a format and a watermarker every piece is
@@ -1291,12 +1299,10 @@ class _TTS(_Finish):
         self._warn_truncated("generate_dialogue", truncated, a["max_chars"])
         if opts.guard is not None:
             self._take_guard(reports, "generate_dialogue")
+        wav, starts, kept = self._mix_dialogue(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts, bed,
+                                               None if place is None else [ops.pan_gains(place["rows"][t]) for t in turn_of])
         if place is not None:
-            wav, starts, kept = self._mix_dialogue_stereo(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts,
-                                                          [ops.pan_gains(place["rows"][t]) for t in turn_of])
             self.last_pan = [dict(voice=k, position=p, left=g[0], right=g[1]) for k, p in zip(keys, place["voices"]) for g in [ops.pan_gains(p)]]
-        else:
-            wav, starts, kept = self._mix_dialogue(pieces, recs, [r["after"] for r in plan["rows"]], row_voice, keys, level, a["join_fade"], opts, bed)
         if bed is not None:  # the speech begins `lead` samples into the result
             starts = [v + opts.bed["lead"] for v in starts]
         if not return_segments:
@@ -1344,97 +1350,41 @@ class _TTS(_Finish):
             stats, gain = ops.wave_loudness([packed[ends[v]: ends[v + 1]] for v in range(len(keys))], [level] * len(keys), 1.0)
         return flat, stats, gain
 
-    def _mix_dialogue(self, pieces, recs, after, row_voice, keys, level, fade, opts, bed=None):
+    def _mix_dialogue(self, pieces, recs, after, row_voice, keys, level, fade, opts, bed=None, pan=None):
         """The finish of generate_dialogue, ONE visit to the device for the whole conversation: the jobs' pieces (host tensors: each the job's trimmed rows back to
         back; recs: their records of offsets and edges) are uploaded into ONE allocation, ops.mix_layout over the kept lengths places the rows, the meter of
-        balance= reads every voice's rows packed back to back (torch.cat: copies, no arithmetic; ONE ops.wave_loudness over the V voices, ceiling 1.0 -> the (V,)
-        gain vector the rows index through gain_idx), ops.wave_mix sums the rows into `out` -- ONE launch for up to 64 rows, whatever pieces they came in; a longer
-        script in launches of 64, the first writing every sample and the others accumulating --, then the music bed (bed: (plan, source) or None; _lay_bed: the
-        mix is measured before the bed, the bed over its whole source), then loudness over the result as ONE signal, true_peak, the watermark
-        on the host if a watermarker is loaded, the format, and the one copy to the host -- the order of _finish / _to_loudness.  (One launch per PIECE would also
-        be the definition's values, but an accumulating launch adds to the +0.0 its predecessor left: a row that begins with -0.0 samples -- the vocoder's do --
-        would differ from generate_long's bits in the sign of those zeros.  With one allocation a script of up to 64 chunks is one launch and has no such seam.)
-        Every row fades in and out over `fade` samples except the very first row's start and the very last row's end where nothing was trimmed there (the join's
-        first / last rule).  Returns (the (1, n) CPU tensor, the rows' starts in 24 kHz samples, their kept (src_start, src_stop))."""
+        balance= reads every voice's MONO rows packed back to back (torch.cat: copies, no arithmetic; ONE ops.wave_loudness over the V voices, ceiling 1.0 -> the (V,)
+        gain vector the rows index through gain_idx), and the mixer sums the rows -- ONE launch for up to 64 rows, whatever pieces they came in; a longer script
+        in launches of 64, the first writing every sample and the others accumulating.  pan None: ops.wave_mix into a (total,) buffer.  pan (the (left, right)
+        gains of every row: ops.pan_gains of its turn's place): ops.wave_pan_mix into a planar (2, total) buffer.  Then the chain (_chain), whose order is
+        _finish's because it is the same code: the music bed (bed: (plan, source) or None, mono only; the mix is measured before the bed, the bed over its whole
+        source), loudness over the result as ONE signal, true_peak, the watermark on the host if a watermarker is loaded, the format, the one copy to the host.
+        (One launch per PIECE would also be the definition's values, but an accumulating launch adds to the +0.0 its predecessor left: a row that begins with
+        -0.0 samples -- the vocoder's do -- would differ from generate_long's bits in the sign of those zeros.  With one allocation a script of up to 64 chunks
+        is one launch and has no such seam.)  Every row fades in and out over `fade` samples except the very first row's start and the very last row's end where
+        nothing was trimmed there (the join's first / last rule).  Returns (the CPU tensor, (1, n) or planar (2, n), the rows' starts in 24 kHz samples, their
+        kept (src_start, src_stop))."""
         kept, lengths, starts, total, flags = self._dialogue_layout(recs, after)
         fmt, loud, peak = opts.fmt, None if opts.loud is None else opts.loud[0], None if opts.peak is None else opts.peak[0]
         self.last_balance = None
         if total == 0 and bed is None:
-            return self._finish(torch.zeros(0), fmt, converted=False), starts, kept
-        dev, scope = self._device_scope()
-        with scope:
-            flat, stats, gain = self._dialogue_upload(pieces, recs, lengths, row_voice, keys, level, dev)
-            out = torch.empty(total, dtype=torch.float32, device=dev)
-            for lo in range(0, len(flat), ops.WAVE_JOIN_MAX_ROWS):
-                hi = min(lo + ops.WAVE_JOIN_MAX_ROWS, len(flat))
-                if total:
-                    ops.wave_mix(flat[lo:hi], starts[lo:hi], flags[lo:hi], out, gain=gain, gain_idx=None if gain is None else row_voice[lo:hi], fade=fade, accumulate=lo > 0)
-            w = out if bed is None else self._lay_bed(out, *bed)
-            if peak is not None:
-                pre = None
-                if loud is not None:
-                    self.engine.last_loudness, pre = ops.wave_loudness([w], [float(loud)], None)
-                o, self.engine.last_limit = ops.wave_limit([w], [float(peak)], gain=pre)
-                w = o[0]
-            elif loud is not None:
-                self.engine.last_loudness = ops.wave_normalize([w], [float(loud)])
-            if self.watermarker is not None:
-                w = torch.from_numpy(self.watermarker.apply_watermark(w.cpu().numpy(), sample_rate=self.sr))
-                if fmt is not None:
-                    w = w.to(dev)
-            if fmt is not None:
-                w = ops.wave_format([w], fmt)[0]
-            w = w.cpu()
-            if bed is not None:
-                self._take_bed()
-            if stats is not None:
-                self.last_balance = [dict(voice=k, lufs=s[0], peak=s[1], gain=s[2], blocks=int(s[3])) for k, s in zip(keys, stats.cpu().tolist())]
-        return w.unsqueeze(0), starts, kept
-
-    def _mix_dialogue_stereo(self, pieces, recs, after, row_voice, keys, level, fade, opts, pan):
-        """_mix_dialogue with pan=: the same ONE visit to the device, two planes.  pan: the (left, right) gains of every row (ops.pan_gains of its turn's place).
-        The upload, the layout, the flags and the meter of balance= (over every voice's MONO rows) are _mix_dialogue's; ops.wave_pan_mix sums the rows into a
-        (2, total) buffer in launches of 64 rows, the first writing both planes and the others accumulating; loudness= reads the two planes as ONE signal
-        (ops.wave_loudness_ch: the channels' summed block energies); true_peak= is the linked limiter (ops.wave_limit_ch) with the meter's gain as its pre-gain;
-        without a ceiling the loudness gain is limited to a sample peak of 1.0 over both channels and applied by ops.wave_gain with the one gain for both planes.
-        The watermark, if loaded, is applied per channel on the host; sample_rate= / encoding= are ONE ops.wave_format call with the planes as two rows; one copy
-        to the host.  Returns (the planar (2, n) CPU tensor, the rows' starts in 24 kHz samples, their kept (src_start, src_stop))."""
-        kept, lengths, starts, total, flags = self._dialogue_layout(recs, after)
-        fmt, loud, peak = opts.fmt, None if opts.loud is None else opts.loud[0], None if opts.peak is None else opts.peak[0]
-        self.last_balance = None
-        if total == 0:
             w = self._finish(torch.zeros(0), fmt, converted=False)
-            return torch.cat([w, w]), starts, kept
+            return (w if pan is None else torch.cat([w, w])), starts, kept
         dev, scope = self._device_scope()
         with scope:
             flat, stats, gain = self._dialogue_upload(pieces, recs, lengths, row_voice, keys, level, dev)
-            out = torch.empty(2, total, dtype=torch.float32, device=dev)
+            out = torch.empty(*(() if pan is None else (2,)), total, dtype=torch.float32, device=dev)
             for lo in range(0, len(flat), ops.WAVE_JOIN_MAX_ROWS):
                 hi = min(lo + ops.WAVE_JOIN_MAX_ROWS, len(flat))
-                ops.wave_pan_mix(flat[lo:hi], starts[lo:hi], flags[lo:hi], pan[lo:hi], out, gain=gain, gain_idx=None if gain is None else row_voice[lo:hi], fade=fade,
-                                 accumulate=lo > 0)
-            w = out
-            if peak is not None:
-                pre = None
-                if loud is not None:
-                    self.engine.last_loudness, pre = ops.wave_loudness_ch([w[0], w[1]], [float(loud)], None)
-                lim = torch.empty_like(w)
-                _, self.engine.last_limit = ops.wave_limit_ch([w[0], w[1]], [float(peak)], gain=pre, out=[lim[0], lim[1]])
-                w = lim
-            elif loud is not None:
-                self.engine.last_loudness, g1 = ops.wave_loudness_ch([w[0], w[1]], [float(loud)], 1.0)
-                ops.wave_gain([w[0], w[1]], g1.repeat(2))
-            if self.watermarker is not None:
-                host = w.cpu().numpy()
-                w = torch.stack([torch.from_numpy(self.watermarker.apply_watermark(host[c], sample_rate=self.sr)) for c in range(2)])
-                if fmt is not None:
-                    w = w.to(dev)
-            if fmt is not None:
-                w = torch.stack(ops.wave_format([w[0], w[1]], fmt))
-            w = w.cpu()
+                kw = dict(gain=gain, gain_idx=None if gain is None else row_voice[lo:hi], fade=fade, accumulate=lo > 0)
+                if pan is not None:
+                    ops.wave_pan_mix(flat[lo:hi], starts[lo:hi], flags[lo:hi], pan[lo:hi], out, **kw)
+                elif total:
+                    ops.wave_mix(flat[lo:hi], starts[lo:hi], flags[lo:hi], out, **kw)
+            w = self._chain(out, fmt, loud, peak, bed)
             if stats is not None:
                 self.last_balance = [dict(voice=k, lufs=s[0], peak=s[1], gain=s[2], blocks=int(s[3])) for k, s in zip(keys, stats.cpu().tolist())]
-        return w, starts, kept
+        return (w.unsqueeze(0) if pan is None else w), starts, kept
 
     def _stream_long(self, chunks, plan, jobs, a, return_segments, opts):
         """generate_long_stream behind its validation, a generator: the jobs run through _run_jobs -- while the consumer holds piece k the throughput schedule has

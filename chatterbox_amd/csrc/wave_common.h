@@ -71,8 +71,12 @@ static inline int cbx_wave_apart(const char* who, const float* wav, const cbx_wa
     return 0;
 }
 
-// The meter and the limiter behind their entries, with the channel count C in {1, 2} of a signal as an argument (wave_loudness.hip, wave_limit.hip): the mono
-// entries are the C = 1 calls, the linked entries of wave_stereo.hip check C and the groups' lengths and call the same code -- one source, one arithmetic.
+// The mixer, the meter and the limiter behind their entries, with the plane count P in {1, 2} of the output or the channel count C in {1, 2} of a signal as an
+// argument (wave_mix.hip, wave_loudness.hip, wave_limit.hip): the mono entries are the P = 1 / C = 1 calls; the entries of wave_stereo.hip are the P = 2 call and,
+// for the linked pair, check C and the groups' lengths and call the same code -- one source, one arithmetic.  `who`: the entry's name in every refusal.
+int cbx_wave_mix_run(const char* who, int P, const float* wav, const long* row_off, const int* row_len, const long* start, const int* flags, const float* pan, int R,
+                     const float* gain, int G, const int* gain_idx, const float* ramp, int fade, float* out, long plane_stride, long out_len, int accumulate,
+                     void* stream);
 int cbx_wave_loudness_run(const char* who, const float* wav, const long* row_off, const int* row_len, int R, int C, const double* coef, int hop, const double* target,
                           double ceiling, double* stats, float* gain, double* ws, long ws_cap, void* stream);
 int cbx_wave_limit_run(const char* who, const float* wav, const long* row_off, const int* row_len, int R, int C, const float* gain, const double* ceiling,

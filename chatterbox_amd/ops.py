@@ -1500,6 +1500,46 @@ def mix_layout(lengths, after):
     return starts, front
 
 
+def _wave_mix(who, rows, starts, flags, pan, out, gain, gain_idx, fade, accumulate):
+    """The one body of wave_mix (pan None: out is 1-D) and wave_pan_mix (pan: R (left, right) pairs, out is (2, n)): the counts, `out`, the shortcut for rows that
+    are all empty, _wave_rows, the gain vector and the ctypes arrays, then ONE call of cbx_<who>_f32, the C entry of the public function `who`.  Returns out."""
+    rows = list(rows)
+    R = len(rows)
+    starts, flags = [int(s) for s in starts], [int(f) for f in flags]
+    if pan is None:
+        counts, shape, planes_ok = f"{len(starts)} starts and {len(flags)} flags", "1-D", out.dim() == 1
+    else:
+        counts, shape, planes_ok = f"{len(starts)} starts, {len(flags)} flags and {len(pan)} pan pairs", "(2, n)", out.dim() == 2 and out.shape[0] == 2
+    if len(starts) != R or len(flags) != R or (pan is not None and len(pan) != R):
+        raise ValueError(f"{who}: {counts} for {R} rows")
+    if pan is not None and any(len(g) != 2 for g in pan):
+        raise ValueError(f"{who}: pan holds one (left, right) pair per row")
+    if gain_idx is not None and len(gain_idx) != R:
+        raise ValueError(f"{who}: {len(gain_idx)} gain indices for {R} rows")
+    assert planes_ok and out.is_contiguous(), f"{who}: out is a contiguous {shape} fp32 tensor on the rows' device"
+    _f32(out, "out")
+    n = int(out.shape[-1])
+    if _all_empty(rows):  # (such rows may have no allocation to point at)
+        if not 1 <= R <= WAVE_JOIN_MAX_ROWS or any(not 0 <= s <= n for s in starts):
+            raise ValueError(f"{who}: {R} empty rows at {starts} of an output of {n}")
+        return out if accumulate else out.zero_()
+    base, offs, lens = _wave_rows(rows, who)
+    dev = rows[0].device
+    assert out.device == dev, f"{who}: out is a contiguous {shape} fp32 tensor on the rows' device"
+    G = 0
+    if gain is not None:
+        assert gain.dtype == torch.float32 and gain.dim() == 1 and gain.is_contiguous() and gain.device == dev, f"{who}: gain is (G,) fp32 on the rows' device"
+        G = int(gain.numel())
+    st, fl = (ctypes.c_long * R)(*starts), (ctypes.c_int * R)(*flags)
+    entry = f"cbx_{who}_f32"
+    pg = None if pan is None else (ctypes.c_float * (2 * R))(*[float(v) for g in pan for v in g])
+    gi = None if gain_idx is None else (ctypes.c_int * R)(*[int(g) for g in gain_idx])
+    check(getattr(lib, entry)(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(st), ctypes.addressof(fl), *(() if pg is None else (ctypes.addressof(pg),)),
+                              R, _p(gain), G, None if gi is None else ctypes.addressof(gi), _p(join_ramp(fade, dev)), int(fade), _p(out),
+                              *(() if pg is None else (n,)), n, int(bool(accumulate)), _stream()), entry)  # (the plane stride of a contiguous (2, n) is n)
+    return out
+
+
 def wave_mix(rows, starts, flags, out, gain=None, gain_idx=None, fade=240, accumulate=False):
     """cbx_wave_mix_f32 on the current stream: row r (_wave_rows: 1 .. 64 1-D fp32 views of ONE allocation) times its gain, with the join's fades, ADDED into
     out[starts[r], starts[r] + n_r) -- rows that cover the same sample are summed in ascending r (include/cbx.h states the definition).  starts: R ints >= 0;
@@ -1507,32 +1547,7 @@ def wave_mix(rows, starts, flags, out, gain=None, gain_idx=None, fade=240, accum
     device, not the rows' allocation; every sample of it is written (+0.0 where no row is) unless accumulate, which adds to what it holds and leaves uncovered
     samples alone.  gain: None (every row at 1, no multiply) or a (G,) fp32 device tensor; gain_idx: None (row r uses gain[r]) or R ints in [0, G).  One launch,
     nothing is synchronised.  Returns out."""
-    rows = list(rows)
-    R = len(rows)
-    starts, flags = [int(s) for s in starts], [int(f) for f in flags]
-    if len(starts) != R or len(flags) != R:
-        raise ValueError(f"wave_mix: {len(starts)} starts and {len(flags)} flags for {R} rows")
-    if gain_idx is not None and len(gain_idx) != R:
-        raise ValueError(f"wave_mix: {len(gain_idx)} gain indices for {R} rows")
-    assert out.dim() == 1 and out.is_contiguous(), "wave_mix: out is a contiguous 1-D fp32 tensor on the rows' device"
-    _f32(out, "out")
-    if _all_empty(rows):  # (such rows may have no allocation to point at)
-        if not 1 <= R <= WAVE_JOIN_MAX_ROWS or any(not 0 <= s <= out.numel() for s in starts):
-            raise ValueError(f"wave_mix: {R} empty rows at {starts} of an output of {out.numel()}")
-        return out if accumulate else out.zero_()
-    base, offs, lens = _wave_rows(rows, "wave_mix")
-    dev = rows[0].device
-    assert out.device == dev, "wave_mix: out is a contiguous 1-D fp32 tensor on the rows' device"
-    G = 0
-    if gain is not None:
-        assert gain.dtype == torch.float32 and gain.dim() == 1 and gain.is_contiguous() and gain.device == dev, "wave_mix: gain is (G,) fp32 on the rows' device"
-        G = int(gain.numel())
-    st, fl = (ctypes.c_long * R)(*starts), (ctypes.c_int * R)(*flags)
-    gi = None if gain_idx is None else (ctypes.c_int * R)(*[int(g) for g in gain_idx])
-    check(lib.cbx_wave_mix_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(st), ctypes.addressof(fl), R, _p(gain), G,
-                               None if gi is None else ctypes.addressof(gi), _p(join_ramp(fade, dev)), int(fade), _p(out), out.numel(), int(bool(accumulate)), _stream()),
-          "cbx_wave_mix_f32")
-    return out
+    return _wave_mix("wave_mix", rows, starts, flags, None, out, gain, gain_idx, fade, accumulate)
 
 
 # ----------------------------------------------------------------------------- pitch control: the waveform read back at a real step (wave_pitch.hip)
@@ -1806,26 +1821,36 @@ def check_loudness(value, B, name="loudness"):
     return _per_request_numbers(value, B, name, LOUDNESS_MIN, LOUDNESS_MAX, "a loudness target is a finite number of LUFS")
 
 
+def _loudness_blocks(who, target, S, unit, f, dev):
+    """What every call of the meter builds for its S signals (`unit`: what `who` calls them): the targets as S doubles (one number serves all; None: NaN, gain 1),
+    the filter's ten coefficients, the (S, 4) float64 stats and the (S,) float32 gain on `dev`."""
+    if target is None or not isinstance(target, (list, tuple)):
+        target = [target] * S
+    if len(target) != S:
+        raise ValueError(f"{who}: {len(target)} targets for {S} {unit}")
+    tg = (ctypes.c_double * S)(*[float("nan") if t is None else float(t) for t in target])
+    return tg, (ctypes.c_double * 10)(*f["coef"].tolist()), torch.empty(S, 4, dtype=torch.float64, device=dev), torch.empty(S, dtype=torch.float32, device=dev)
+
+
+def _wave_loudness(who, rows, C, target, ceiling, fs):
+    """The one body of wave_loudness (C None: cbx_wave_loudness_f32, a signal per row) and wave_loudness_ch (cbx_wave_loudness_ch_f32: signals of C rows)"""
+    base, offs, lens = _wave_rows(rows, who)
+    R, dev, f = len(lens), rows[0].device, loudness_filter(fs)
+    tg, coef, stats, gain = _loudness_blocks(who, target, R // (C or 1), "rows" if C is None else "signals", f, dev)
+    ws = torch.empty(max(1, 6 * R * -(-max(lens) // f["hop"])), dtype=torch.float64, device=dev)
+    entry = f"cbx_{who}_f32"
+    check(getattr(lib, entry)(base, ctypes.addressof(offs), ctypes.addressof(lens), R, *(() if C is None else (C,)), ctypes.addressof(coef), f["hop"], ctypes.addressof(tg),
+                              0.0 if ceiling is None else float(ceiling), _p(stats), _p(gain), _p(ws), ws.numel(), _stream()), entry)
+    return stats, gain
+
+
 def wave_loudness(rows, target=None, ceiling=1.0, fs=WAVE_IN_RATE):
     """cbx_wave_loudness_f32 on the current stream: the BS.1770-4 integrated loudness and the sample peak of every row (_wave_rows: 1 .. 64 1-D fp32 views of ONE
     allocation, sampled at fs), and the gain that brings it to its target.  target: None (measure only), a number, or R numbers / Nones (None: gain 1); no range is
     imposed here (check_loudness is the public arguments' check).  ceiling: the sample peak the gain may not exceed (None or 0: no limit).  Returns (stats, gain):
     stats (R, 4) float64 {L in LUFS (-inf: silence or shorter than 0.4 s), peak, gain in fp64, blocks used} and gain (R,) float32, both on the device; nothing is
     synchronised (include/cbx.h states the definition)."""
-    base, offs, lens = _wave_rows(rows, "wave_loudness")
-    R, dev, f = len(lens), rows[0].device, loudness_filter(fs)
-    if target is None or not isinstance(target, (list, tuple)):
-        target = [target] * R
-    if len(target) != R:
-        raise ValueError(f"wave_loudness: {len(target)} targets for {R} rows")
-    tg = (ctypes.c_double * R)(*[float("nan") if t is None else float(t) for t in target])
-    coef = (ctypes.c_double * 10)(*f["coef"].tolist())
-    stats = torch.empty(R, 4, dtype=torch.float64, device=dev)
-    gain = torch.empty(R, dtype=torch.float32, device=dev)
-    ws = torch.empty(max(1, 6 * R * -(-max(lens) // f["hop"])), dtype=torch.float64, device=dev)
-    check(lib.cbx_wave_loudness_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, ctypes.addressof(coef), f["hop"], ctypes.addressof(tg),
-                                    0.0 if ceiling is None else float(ceiling), _p(stats), _p(gain), _p(ws), ws.numel(), _stream()), "cbx_wave_loudness_f32")
-    return stats, gain
+    return _wave_loudness("wave_loudness", rows, None, target, ceiling, fs)
 
 
 def wave_loudness_push(meter, rows, target=None, ceiling=1.0):
@@ -1837,18 +1862,11 @@ def wave_loudness_push(meter, rows, target=None, ceiling=1.0):
     R, dev, f = len(lens), rows[0].device, meter.f
     if R != meter.R:
         raise ValueError(f"wave_loudness_push: {R} rows for a meter of {meter.R}")
-    if target is None or not isinstance(target, (list, tuple)):
-        target = [target] * R
-    if len(target) != R:
-        raise ValueError(f"wave_loudness_push: {len(target)} targets for {R} rows")
-    tg = (ctypes.c_double * R)(*[float("nan") if t is None else float(t) for t in target])
-    coef = (ctypes.c_double * 10)(*f["coef"].tolist())
+    tg, coef, stats, gain = _loudness_blocks("wave_loudness_push", target, R, "rows", f, dev)
     n0 = (ctypes.c_long * R)(*meter.n0)
     k_max = max((a % f["hop"] + int(n)) // f["hop"] for a, n in zip(meter.n0, lens))
     if meter.ws.numel() < 4 * R * k_max:
         meter.ws = torch.empty(4 * R * k_max, dtype=torch.float64, device=dev)
-    stats = torch.empty(R, 4, dtype=torch.float64, device=dev)
-    gain = torch.empty(R, dtype=torch.float32, device=dev)
     check(lib.cbx_wave_loudness_push_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(n0), R, ctypes.addressof(coef), f["hop"],
                                          ctypes.addressof(tg), 0.0 if ceiling is None else float(ceiling), _p(meter.rec), meter.seg_cap, _p(meter.tail[meter.cur]),
                                          _p(meter.tail[1 - meter.cur]), _p(stats), _p(gain), _p(meter.ws), meter.ws.numel(), _stream()), "cbx_wave_loudness_push_f32")
@@ -1953,42 +1971,50 @@ def check_true_peak(value, B, name="true_peak"):
     return _per_request_numbers(value, B, name, TRUE_PEAK_MIN, TRUE_PEAK_MAX, "a true-peak ceiling is a finite number of dBTP")
 
 
-def _wave_limit_launch(rows, ceilings, gain, look, out):
-    """One cbx_wave_limit_f32 call on the current stream.  ceilings: R linear ceilings / Nones; out: None (measure only) or R rows of the lengths of `rows`, views
-    of ONE allocation that is not the rows'.  Returns the (R, 4) stats on the device."""
-    base, offs, lens = _wave_rows(rows, "wave_limit")
+def _wave_limit(who, rows, C, ceilings_db, gain, look, out, measure):
+    """The one body of wave_limit / wave_true_peak (C None: cbx_wave_limit_f32, a signal per row) and wave_limit_ch (cbx_wave_limit_ch_f32: signals of C rows).
+    ceilings_db: a number of dBTP or None for every signal, or one per signal; out: None (measure: nothing is written; else ONE new allocation in the layout of
+    `rows`) or rows of the lengths of `rows`, views of ONE allocation that is not the rows'.  Returns (out rows or None, the (S, 4) stats on the device)."""
+    rows = list(rows)
+    S, unit, letter = (len(rows), "rows", "R") if C is None else (len(rows) // C, "signals", "S")
+    if ceilings_db is None or not isinstance(ceilings_db, (list, tuple)):
+        ceilings_db = [ceilings_db] * S
+    if len(ceilings_db) != S:
+        raise ValueError(f"{who}: {len(ceilings_db)} ceilings for {S} {unit}")
+    limit_window(look)
+    if _all_empty(rows):
+        outs = None if measure else (list(out) if out is not None else [torch.empty(0, dtype=torch.float32, device=w.device) for w in rows])
+        return outs, torch.tensor([[0.0, 1.0, 0.0, 0.0]] * S, dtype=torch.float64).to(rows[0].device)
+    base, offs, lens = _wave_rows(rows, who)
     R, dev, f = len(lens), rows[0].device, true_peak_filter()
-    if len(ceilings) != R:
-        raise ValueError(f"wave_limit: {len(ceilings)} ceilings for {R} rows")
+    if out is None and not measure:
+        lo = min(a for a, n in zip(offs, lens) if n)
+        buf = torch.empty(max(a + n for a, n in zip(offs, lens) if n) - lo, dtype=torch.float32, device=dev)
+        out = [buf[a - lo: a - lo + n] if n else buf[:0] for a, n in zip(offs, lens)]
     tab, win = _limit_tables(look, dev)
-    ceil = (ctypes.c_double * R)(*[float("nan") if c is None else float(c) for c in ceilings])
+    ceil = (ctypes.c_double * S)(*[float("nan") if c is None else 10.0 ** (float(c) / 20.0) for c in ceilings_db])
     if gain is not None:
-        assert gain.dtype == torch.float32 and gain.numel() == R and gain.is_contiguous() and gain.device == dev, "wave_limit: gain is (R,) fp32 on the rows' device"
+        assert gain.dtype == torch.float32 and gain.numel() == S and gain.is_contiguous() and gain.device == dev, f"{who}: gain is ({letter},) fp32 on the rows' device"
     obase, ooffs, cap = None, None, 0
     if out is not None:
-        obase, o, olens = _wave_rows(out, "wave_limit: out")
+        out = list(out)
+        obase, o, olens = _wave_rows(out, f"{who}: out")
         if list(olens) != list(lens):
-            raise ValueError("wave_limit: the rows of out have other lengths than the rows")
+            raise ValueError(f"{who}: the rows of out have other lengths than the rows")
         ooffs, cap = ctypes.addressof(o), max((a + n for a, n in zip(o, olens)), default=0)
-    stats = torch.empty(R, 4, dtype=torch.float64, device=dev)
-    ws = torch.empty(max(1, 4 * R * -(-max(lens) // 1024)), dtype=torch.float64, device=dev)
-    check(lib.cbx_wave_limit_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, _p(gain), ctypes.addressof(ceil), _p(tab), f["U"], f["T"], _p(win), look,
-                                 obase, ooffs, cap, _p(stats), _p(ws), ws.numel(), _stream()), "cbx_wave_limit_f32")
-    return stats
-
-
-def _empty_limit_stats(rows):
-    return torch.tensor([[0.0, 1.0, 0.0, 0.0]] * len(rows), dtype=torch.float64).to(rows[0].device)
+    stats = torch.empty(S, 4, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(1, 4 * S * -(-max(lens) // 1024)), dtype=torch.float64, device=dev)
+    entry = f"cbx_{who}_f32"
+    check(getattr(lib, entry)(base, ctypes.addressof(offs), ctypes.addressof(lens), R, *(() if C is None else (C,)), _p(gain), ctypes.addressof(ceil), _p(tab), f["U"], f["T"],
+                              _p(win), look, obase, ooffs, cap, _p(stats), _p(ws), ws.numel(), _stream()), entry)
+    return out, stats
 
 
 def wave_true_peak(rows):
     """cbx_wave_limit_f32 as a meter, on the current stream: the true peak (4-times oversampled, linear) of every row (_wave_rows: 1 .. 64 1-D fp32 views of ONE
     allocation at 24 kHz).  Returns the (R, 4) float64 stats {true peak (NaN for a row with a NaN), 1, 0, 0} on the device; nothing is written but them, nothing is
     synchronised."""
-    rows = list(rows)
-    if _all_empty(rows):
-        return _empty_limit_stats(rows)
-    return _wave_limit_launch(rows, [None] * len(rows), None, LIMIT_LOOK, None)
+    return _wave_limit("wave_limit", rows, None, None, None, LIMIT_LOOK, None, True)[1]
 
 
 def wave_limit(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None):
@@ -1998,21 +2024,7 @@ def wave_limit(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None):
     (check_true_peak is the public arguments' check).  Returns (out_rows, stats): out_rows are views of ONE new allocation in the layout of `rows` (out: R rows of
     the same lengths in an allocation of the caller's instead), stats (R, 4) float64 {true peak of x * gain, min g, samples with g < 1, samples over the ceiling} on
     the device.  Two launches, nothing is synchronised."""
-    rows = list(rows)
-    if ceilings_db is None or not isinstance(ceilings_db, (list, tuple)):
-        ceilings_db = [ceilings_db] * len(rows)
-    ceil = [None if c is None else 10.0 ** (float(c) / 20.0) for c in ceilings_db]
-    limit_window(look)
-    if _all_empty(rows):
-        return (list(out) if out is not None else [torch.empty(0, dtype=torch.float32, device=w.device) for w in rows]), _empty_limit_stats(rows)
-    if out is None:
-        base, offs, lens = _wave_rows(rows, "wave_limit")
-        lo = min(a for a, n in zip(offs, lens) if n)
-        buf = torch.empty(max(a + n for a, n in zip(offs, lens) if n) - lo, dtype=torch.float32, device=rows[0].device)
-        out = [buf[a - lo: a - lo + n] if n else buf[:0] for a, n in zip(offs, lens)]
-    else:
-        out = list(out)
-    return out, _wave_limit_launch(rows, ceil, gain, look, out)
+    return _wave_limit("wave_limit", rows, None, ceilings_db, gain, look, out, False)
 
 
 # ----------------------------------------------------------------------------- stereo dialogue: panned mix, channel-summed meter, linked limiter (wave_stereo.hip)
@@ -2050,36 +2062,7 @@ def wave_pan_mix(rows, starts, flags, pan, out, gain=None, gain_idx=None, fade=2
     not the rows' allocation: out[0] is the left plane, out[1] the right.  Row r times its balance gain and fades, times its left / right gain, ADDED into both
     planes at starts[r]; the covering rows are summed in ascending r per plane (include/cbx.h states the definition).  Every sample of both planes is written
     (+0.0 where no row is) unless accumulate.  One launch, nothing is synchronised.  Returns out."""
-    rows = list(rows)
-    R = len(rows)
-    starts, flags = [int(s) for s in starts], [int(f) for f in flags]
-    if len(starts) != R or len(flags) != R or len(pan) != R:
-        raise ValueError(f"wave_pan_mix: {len(starts)} starts, {len(flags)} flags and {len(pan)} pan pairs for {R} rows")
-    if any(len(g) != 2 for g in pan):
-        raise ValueError("wave_pan_mix: pan holds one (left, right) pair per row")
-    if gain_idx is not None and len(gain_idx) != R:
-        raise ValueError(f"wave_pan_mix: {len(gain_idx)} gain indices for {R} rows")
-    assert out.dim() == 2 and out.shape[0] == 2 and out.is_contiguous(), "wave_pan_mix: out is a contiguous (2, n) fp32 tensor on the rows' device"
-    _f32(out, "out")
-    n = int(out.shape[1])
-    if _all_empty(rows):  # (such rows may have no allocation to point at)
-        if not 1 <= R <= WAVE_JOIN_MAX_ROWS or any(not 0 <= s <= n for s in starts):
-            raise ValueError(f"wave_pan_mix: {R} empty rows at {starts} of an output of {n}")
-        return out if accumulate else out.zero_()
-    base, offs, lens = _wave_rows(rows, "wave_pan_mix")
-    dev = rows[0].device
-    assert out.device == dev, "wave_pan_mix: out is a contiguous (2, n) fp32 tensor on the rows' device"
-    G = 0
-    if gain is not None:
-        assert gain.dtype == torch.float32 and gain.dim() == 1 and gain.is_contiguous() and gain.device == dev, "wave_pan_mix: gain is (G,) fp32 on the rows' device"
-        G = int(gain.numel())
-    st, fl = (ctypes.c_long * R)(*starts), (ctypes.c_int * R)(*flags)
-    pg = (ctypes.c_float * (2 * R))(*[float(v) for g in pan for v in g])
-    gi = None if gain_idx is None else (ctypes.c_int * R)(*[int(g) for g in gain_idx])
-    check(lib.cbx_wave_pan_mix_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), ctypes.addressof(st), ctypes.addressof(fl), ctypes.addressof(pg), R, _p(gain), G,
-                                   None if gi is None else ctypes.addressof(gi), _p(join_ramp(fade, dev)), int(fade), _p(out), n, n, int(bool(accumulate)), _stream()),
-          "cbx_wave_pan_mix_f32")
-    return out
+    return _wave_mix("wave_pan_mix", rows, starts, flags, pan, out, gain, gain_idx, fade, accumulate)
 
 
 def _channel_groups(rows, channels, who):
@@ -2100,21 +2083,7 @@ def wave_loudness_ch(rows, target=None, ceiling=1.0, fs=WAVE_IN_RATE, channels=2
     None (measure only), a number, or one number / None per SIGNAL; ceiling: wave_loudness's.  Returns (stats (S, 4) float64, gain (S,) float32) on the device,
     S = len(rows) / channels; channels=1 is wave_loudness bit for bit.  Nothing is synchronised (include/cbx.h states the definition)."""
     rows, C = _channel_groups(rows, channels, "wave_loudness_ch")
-    base, offs, lens = _wave_rows(rows, "wave_loudness_ch")
-    R, dev, f = len(lens), rows[0].device, loudness_filter(fs)
-    S = R // C
-    if target is None or not isinstance(target, (list, tuple)):
-        target = [target] * S
-    if len(target) != S:
-        raise ValueError(f"wave_loudness_ch: {len(target)} targets for {S} signals")
-    tg = (ctypes.c_double * S)(*[float("nan") if t is None else float(t) for t in target])
-    coef = (ctypes.c_double * 10)(*f["coef"].tolist())
-    stats = torch.empty(S, 4, dtype=torch.float64, device=dev)
-    gain = torch.empty(S, dtype=torch.float32, device=dev)
-    ws = torch.empty(max(1, 6 * R * -(-max(lens) // f["hop"])), dtype=torch.float64, device=dev)
-    check(lib.cbx_wave_loudness_ch_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, C, ctypes.addressof(coef), f["hop"], ctypes.addressof(tg),
-                                       0.0 if ceiling is None else float(ceiling), _p(stats), _p(gain), _p(ws), ws.numel(), _stream()), "cbx_wave_loudness_ch_f32")
-    return stats, gain
+    return _wave_loudness("wave_loudness_ch", rows, C, target, ceiling, fs)
 
 
 def wave_limit_ch(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None, channels=2):
@@ -2125,39 +2094,7 @@ def wave_limit_ch(rows, ceilings_db, gain=None, look=LIMIT_LOOK, out=None, chann
     stats (S, 4) float64 {true peak over the channels of x * gain, min g, samples with g < 1, samples over the ceiling}.  channels=1 is wave_limit bit for bit.
     Two launches, nothing is synchronised."""
     rows, C = _channel_groups(rows, channels, "wave_limit_ch")
-    S = len(rows) // C
-    measure = ceilings_db is None and out is None
-    if ceilings_db is None or not isinstance(ceilings_db, (list, tuple)):
-        ceilings_db = [ceilings_db] * S
-    if len(ceilings_db) != S:
-        raise ValueError(f"wave_limit_ch: {len(ceilings_db)} ceilings for {S} signals")
-    ceil = [None if c is None else 10.0 ** (float(c) / 20.0) for c in ceilings_db]
-    limit_window(look)
-    if _all_empty(rows):
-        outs = None if measure else (list(out) if out is not None else [torch.empty(0, dtype=torch.float32, device=w.device) for w in rows])
-        return outs, _empty_limit_stats(rows[:S])
-    base, offs, lens = _wave_rows(rows, "wave_limit_ch")
-    R, dev, f = len(lens), rows[0].device, true_peak_filter()
-    if out is None and not measure:
-        lo = min(a for a, n in zip(offs, lens) if n)
-        buf = torch.empty(max(a + n for a, n in zip(offs, lens) if n) - lo, dtype=torch.float32, device=dev)
-        out = [buf[a - lo: a - lo + n] if n else buf[:0] for a, n in zip(offs, lens)]
-    tab, win = _limit_tables(look, dev)
-    cl = (ctypes.c_double * S)(*[float("nan") if c is None else float(c) for c in ceil])
-    if gain is not None:
-        assert gain.dtype == torch.float32 and gain.numel() == S and gain.is_contiguous() and gain.device == dev, "wave_limit_ch: gain is (S,) fp32 on the rows' device"
-    obase, ooffs, cap = None, None, 0
-    if out is not None:
-        out = list(out)
-        obase, o, olens = _wave_rows(out, "wave_limit_ch: out")
-        if list(olens) != list(lens):
-            raise ValueError("wave_limit_ch: the rows of out have other lengths than the rows")
-        ooffs, cap = ctypes.addressof(o), max((a + n for a, n in zip(o, olens)), default=0)
-    stats = torch.empty(S, 4, dtype=torch.float64, device=dev)
-    ws = torch.empty(max(1, 4 * S * -(-max(lens) // 1024)), dtype=torch.float64, device=dev)
-    check(lib.cbx_wave_limit_ch_f32(base, ctypes.addressof(offs), ctypes.addressof(lens), R, C, _p(gain), ctypes.addressof(cl), _p(tab), f["U"], f["T"], _p(win), look,
-                                    obase, ooffs, cap, _p(stats), _p(ws), ws.numel(), _stream()), "cbx_wave_limit_ch_f32")
-    return out, stats
+    return _wave_limit("wave_limit_ch", rows, C, ceilings_db, gain, look, out, ceilings_db is None and out is None)
 
 
 # ----------------------------------------------------------------------------- music bed: speech over a background that ducks while someone talks (wave_duck.hip)

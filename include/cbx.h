@@ -1205,7 +1205,7 @@ int cbx_wave_mix_f32(const float* wav, const long* row_off, const int* row_len, 
  * gain of 0 gives a plane of zeros (of either sign) for finite rows.  Rows given in groups over several launches behave as in the mono entry.  The result does
  * not depend on the grid, the tile a sample falls into, or the alignment of wav, a row, out or the right plane.  There are no atomics.  wav is only read; neither
  * plane may overlap it.  Nothing outside the two planes is written.
- * One launch reads every source sample once and writes both planes: one workgroup of 256 threads per tile of 4096 outputs per plane (wave_stereo.hip), counted
+ * One launch reads every source sample once and writes both planes: one workgroup of 256 threads per tile of 4096 outputs per plane (wave_mix.hip, P = 2), counted
  * from the 16-byte boundary at or below out, both planes' sums in registers in row order; 16-byte accesses where the plane's own address allows, 4-byte accesses
  * at the ragged ends and in a plane that sits off the boundary.  None, rc 0, when out_len == 0.  Nothing synchronises the host.
  * -22 before any launch, nothing written: every refusal of cbx_wave_mix_f32, a null pan, a pan gain that is not finite, plane_stride < out_len, a plane

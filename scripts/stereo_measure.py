@@ -1,18 +1,21 @@
-"""What the stereo finish costs, one process on one box: the finishing visit of a dialogue of eight chunks of 10 s each (two voices
-alternating, every second turn coming in 0.2 s early, balance=True), with loudness=-16, true_peak=-1, sample_rate=48000, encoding="s16" -- the "-16 LUFS at -1
-dBTP" delivery --, two forms ALTERNATING inside every repetition on the same pieces:
-  mono    _TTS._mix_dialogue: upload, the balance meter, cbx_wave_mix_f32, the meter, the limiter, the format, the one copy to the host -- the parent commit's
-          finish (pan=None takes this path launch for launch)
-  stereo  _TTS._mix_dialogue_stereo with the voices at -0.3 / +0.3: upload, the balance meter, cbx_wave_pan_mix_f32, cbx_wave_loudness_ch_f32,
-          cbx_wave_limit_ch_f32, the format over two rows, the one copy to the host
+"""What the finishing visit costs, one process on one box: the finish of a dialogue of eight chunks of 10 s each (two voices alternating,
+every second turn coming in 0.2 s early, balance=True), with loudness=-16, true_peak=-1, sample_rate=48000, encoding="s16" -- the "-16 LUFS at -1 dBTP"
+delivery --, three forms ALTERNATING inside every repetition on the same pieces:
+  mono    _TTS._mix_dialogue: upload, the balance meter, cbx_wave_mix_f32, then the chain: the meter, the limiter, the format, the one copy to the host
+  stereo  _TTS._mix_dialogue with pan= (the voices at -0.3 / +0.3): upload, the balance meter, cbx_wave_pan_mix_f32, then the chain over two planes:
+          cbx_wave_loudness_ch_f32, cbx_wave_limit_ch_f32, the format over two rows, the one copy to the host
+  long    _Finish._finish(the eight pieces as one 80 s waveform on the host, converted=False, loud=-16, peak=-1): generate_long's finish -- upload, the chain
+          (the waveform is concatenated once, outside the clock)
+The script runs on older checkouts too, so that two commits can be compared in one visit: where the stereo finish is a method of its own
+(_mix_dialogue_stereo) that one is called, and where there is no pan= at all the stereo form is left out.  _finish has had this signature throughout.
 The pieces are synthetic waveforms (seeded noise bursts; the finish does not depend on who spoke them), so no synthesis runs and the model is the small synthetic
 one (two T3 layers): only its device and its delivery options are used.  Times are a host clock around each call; each call ends in the device-to-host copy, which
-synchronises.  Every form is warmed up once (tables, allocator, code objects).  On a checkout without pan= (the parent commit) the mono form alone is measured.
-Writes one JSON line -- median, min and max per form over the repetitions, the ratio of the medians, the sizes -- to the log (default
-profiles/stereo_measure.log) and prints it.
+synchronises.  Every form is warmed up once (tables, allocator, code objects).  Writes one JSON line -- median, min and max per form over the repetitions, the
+ratio of the stereo and mono medians, the sizes -- to the log (default profiles/stereo_measure.log) and prints it.
 
     python scripts/stereo_measure.py [repetitions, default 20] [log path]
 """
+import inspect
 import json
 import os
 import statistics
@@ -42,11 +45,17 @@ recs = [dict(edges=[(0, N)], offsets=[0], n=[N], total=N) for _ in range(CHUNKS)
 after = [(-4800 if k % 2 == 0 else 7200) for k in range(CHUNKS - 1)] + [0]
 row_voice, keys = [k % 2 for k in range(CHUNKS)], ["host", "guest"]
 opts = api._Options(m, loudness=-16, true_peak=-1, sample_rate=48000, encoding="s16")
-forms = {"mono": lambda: m._mix_dialogue(pieces, recs, after, row_voice, keys, api.DIALOGUE_BALANCE, 240, opts)}
-if hasattr(m, "_mix_dialogue_stereo"):
-    pan = [ops.pan_gains((-0.3, 0.3)[v]) for v in row_voice]
-    forms["stereo"] = lambda: m._mix_dialogue_stereo(pieces, recs, after, row_voice, keys, api.DIALOGUE_BALANCE, 240, opts, pan)
-out = {k: fn()[0] for k, fn in forms.items()}   # (the warm-up)
+forms = {"mono": lambda: m._mix_dialogue(pieces, recs, after, row_voice, keys, api.DIALOGUE_BALANCE, 240, opts)[0]}
+pan = [ops.pan_gains((-0.3, 0.3)[v]) for v in row_voice] if hasattr(ops, "pan_gains") else None
+if pan is None:
+    pass
+elif hasattr(m, "_mix_dialogue_stereo"):
+    forms["stereo"] = lambda: m._mix_dialogue_stereo(pieces, recs, after, row_voice, keys, api.DIALOGUE_BALANCE, 240, opts, pan)[0]
+elif "pan" in inspect.signature(m._mix_dialogue).parameters:
+    forms["stereo"] = lambda: m._mix_dialogue(pieces, recs, after, row_voice, keys, api.DIALOGUE_BALANCE, 240, opts, pan=pan)[0]
+whole = torch.cat(pieces)
+forms["long"] = lambda: m._finish(whole, opts.fmt, converted=False, loud=-16.0, peak=-1.0)
+out = {k: fn() for k, fn in forms.items()}   # (the warm-up)
 ms = {k: [] for k in forms}
 for _ in range(reps):
     for name, fn in forms.items():

@@ -41,7 +41,8 @@ def test_the_entries_are_declared_exported_bound_emulated_and_documented_without
     assert all(s in block for s in ("cbx_wave_mix_f32's bits in both planes", "L == R bit for bit", "plane of zeros", "C = 1 is cbx_wave_loudness_f32 bit for bit",
                                     "C = 1 is cbx_wave_limit_f32 bit for bit", "lowers the other by the same g", "-22 before any launch, nothing written"))
     src = open(os.path.join(ROOT, "chatterbox_amd", "csrc", "wave_stereo.hip")).read()
-    assert "tts.py:272" in src and f"WP_TILE = {ops.WAVE_MIX_TILE}" in src and "atomic" not in src
+    assert "tts.py:272" in src and "__global__" not in src and "atomic" not in src, "the three entries hold no kernel of their own"
+    assert f"WM_TILE = {ops.WAVE_MIX_TILE}" in open(os.path.join(ROOT, "chatterbox_amd", "csrc", "wave_mix.hip")).read(), "the one mixer kernel's tile"
     for doc, words in (("README.md", ("pan=",)), ("DESIGN.md", ("DIALOGUE_PAN_SPREAD", "cbx_wave_limit_ch_f32")), ("INTEGRATION.md", tuple(ENTRIES))):
         text = open(os.path.join(ROOT, doc)).read()
         assert all(w in text for w in words), doc
